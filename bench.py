@@ -4,12 +4,14 @@
   python bench.py --gpus N --steps K --warmup W
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
 
 One "step" = one kws_step call: B=4096 concurrent streams per GPU advanced by T=300 mel frames
 (BASELINE.json configs[1]: 2xGRU h=128, n_mel=40, 6 classes, fp32), state carried on the device from
 step to step, logits + softmax + fused ctc_decode2 token events written.  Inputs are resident in HBM
 before the timed region.  Weak scaling: every rank owns its own 4096 streams, no data-path collective.
-Prints ONE JSON line on rank 0.
+Prints ONE JSON line on rank 0.  --dump-outputs DIR writes what the last timed step returned on rank 0
+(see dump_outputs); inputs and weights are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -25,6 +27,32 @@ FLOP_PER_FRAME = {"total": 327168, "layer": [2 * 64512, 2 * (98304 + 768)]}   # 
 BYTES_PER_FRAME = 160 + 24 + 24 + 1                                          # mel in, logits, softmax, token out
 PEAK_FP32_TFLOPS = 157.3                                                      # MI355X_MICROARCH.md
 PEAK_HBM_GBS = 8000.0
+DUMP_LIMIT_BYTES = 64 * 10 ** 6                                               # all files of --dump-outputs together
+
+
+def dump_outputs(dirname, arrays):
+    """Writes {name: (tensor, stream axis)} as dirname/<name>.npy: floating outputs as float32, integer ones exactly (float32
+    up to 16 bits, float64 above).  When the streams of all arrays together exceed DUMP_LIMIT_BYTES, every array keeps the
+    same fixed, seeded sample of streams.  stream_index.npy (float64) lists the streams the rows belong to."""
+    import numpy as np
+    import torch
+
+    def dtype(t):
+        return np.float32 if t.dtype.is_floating_point or t.element_size() <= 2 else np.float64
+
+    n = {t.shape[ax] for t, ax in arrays.values()}
+    assert len(n) == 1, n
+    n = n.pop()
+    per_stream = 8 + sum(t.numel() // n * np.dtype(dtype(t)).itemsize for t, _ in arrays.values())
+    keep = min(n, (DUMP_LIMIT_BYTES - 4096 * (len(arrays) + 1)) // per_stream)       # 4 KiB per file for its .npy header
+    if keep < 1:
+        raise SystemExit("bench.py --dump-outputs: one stream's outputs alone exceed %d bytes" % DUMP_LIMIT_BYTES)
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+    os.makedirs(dirname, exist_ok=True)
+    for name, (t, ax) in arrays.items():
+        rows = t if keep == n else t.index_select(ax, torch.as_tensor(idx, device=t.device))
+        np.save(os.path.join(dirname, name + ".npy"), rows.cpu().numpy().astype(dtype(t)))
+    np.save(os.path.join(dirname, "stream_index.npy"), idx.astype(np.float64))
 
 
 def csrc_hash():
@@ -632,7 +660,11 @@ def main(argv=None, model_factory=None):
                     "multi-process path on a box with fewer GPUs than ranks")
     ap.add_argument("--force-dist", action="store_true", help="initialise the process group even at one rank: runs the RCCL "
                     "init / barrier / reduction / gather code of the N > 1 path on a single-GPU box")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one returned on rank 0 "
+                    "(logits, softmax, tokens, state, prev_word) as DIR/<name>.npy, at most 64 MB in all")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     stub = model_factory is not None
 
     if args.gpus > 1 and int(os.environ.get("WORLD_SIZE", "1")) == 1:
@@ -735,6 +767,9 @@ def main(argv=None, model_factory=None):
     clock_mhz = clock.result()                      # None if unreadable as this user
     ktimes = model.kernel_times(reset=True)
     model.set_profiling(False)
+    if args.dump_outputs and rank == 0:             # before the sustained run below overwrites these buffers
+        dump_outputs(args.dump_outputs, {"logits": (out["logits"], 0), "softmax": (out["softmax"], 0), "tokens": (out["tokens"], 0),
+                                         "state": (state, 1), "prev_word": (prev_word, 0)})
     frames, seconds = sharding.reduce_throughput(dist, B * T * args.steps, elapsed, sync_device)
     ranks_seen = sharding.count_ranks(dist, sync_device)
     # who took part: host, device identity and own rate of every rank, so that an N-GPU line proves N distinct devices and
