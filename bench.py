@@ -5,6 +5,7 @@
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
   python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR
+  python bench.py --gpus 1 --steps K --warmup W --full
 
 One "step" = one kws_step call: B=4096 concurrent streams per GPU advanced by T=300 mel frames
 (BASELINE.json configs[1]: 2xGRU h=128, n_mel=40, 6 classes, fp32), state carried on the device from
@@ -12,6 +13,9 @@ step to step, logits + softmax + fused ctc_decode2 token events written.  Inputs
 before the timed region.  Weak scaling: every rank owns its own 4096 streams, no data-path collective.
 Prints ONE JSON line on rank 0.  --dump-outputs DIR writes what the last timed step returned on rank 0
 (see dump_outputs); inputs and weights are seeded, so two builds can be compared output for output.
+A plain run sets up, warms up, times the steps and prints the line.  --full adds, on one GPU, what takes
+runs of its own after the timed region (about 90 s more): the sustained run, the secondary lines (other
+precisions, sizes and the serving loop, each with its roofline) and the CPU baseline.
 """
 import argparse
 import json
@@ -654,8 +658,12 @@ def main(argv=None, model_factory=None):
     ap.add_argument("--kernel", default="auto")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "f16x3", "bf16", "int8"],
                     help="fp32 = the reference arithmetic (headline); bf16 / int8 = BASELINE configs[2] variants (secondary)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the sustained run, the secondary lines and the CPU baseline")
-    ap.add_argument("--sustain-seconds", type=float, default=10.0, help="length of the sustained-load run after the timed region")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run the sustained run, the secondary "
+                    "lines and the CPU baseline (one GPU only; about 90 s more)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the sustained run, the secondary lines and the CPU "
+                    "baseline even with --full (a plain run skips them anyway)")
+    ap.add_argument("--sustain-seconds", type=float, default=10.0, help="length of the sustained-load run after the timed "
+                    "region (--full)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL over xGMI); gloo only to exercise the "
                     "multi-process path on a box with fewer GPUs than ranks")
     ap.add_argument("--force-dist", action="store_true", help="initialise the process group even at one rank: runs the RCCL "
@@ -839,7 +847,7 @@ def main(argv=None, model_factory=None):
                          "hbm_algorithmic_GBps": BYTES_PER_FRAME * B * T / (all_ms * 1e-3) / 1e9,
                          "hbm_frac_of_peak": BYTES_PER_FRAME * B * T / (all_ms * 1e-3) / 1e9 / PEAK_HBM_GBS},
         }
-        if world == 1 and not args.no_cpu_baseline and not stub:
+        if args.full and world == 1 and not args.no_cpu_baseline and not stub:
             # the headline above is K steps (tens of milliseconds): the same step() for >= 10 s tells whether it holds under
             # sustained power/thermal load (reported beside it, never as `value`)
             line["sustained"] = sustained_run(step, device_sync, B * T, args.sustain_seconds)

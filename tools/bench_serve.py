@@ -11,7 +11,7 @@ pinned host memory, uploads on a copy stream per handle overlapped with compute;
 
   python tools/bench_serve.py [--precision fp32|f16x3|bf16|int8] [--streams-per-manager 16384] [--handles 2] [--periods 40]
                               [--host-fed] [--json]
-bench.py imports sustained_streams() for its `secondary` entries.
+bench.py --full imports sustained_streams() for its `secondary` entries.
 """
 import argparse
 import json
