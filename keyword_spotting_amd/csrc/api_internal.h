@@ -1,0 +1,247 @@
+// Host-side state and helpers shared by the C ABI translation units of libkws_amd.so (api_*.hip, weight_pack.hip,
+// selftest.hip).  Never included by a kernel file: the kernel/host surface is kws_internal.h.
+#pragma once
+#include <algorithm>
+#include <atomic>
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "kws_internal.h"
+
+// Helpers shared across the host files; hidden, so the library's dynamic symbol table holds the C ABI and the kernels only.
+#pragma GCC visibility push(hidden)
+namespace kws_host {
+
+extern thread_local std::string g_last_error;   // kws_last_error(); set by fail()
+// kws_selftest is running on this thread: the temporary handles it creates do not recurse through KWS_SELFTEST=1.  A function,
+// not a shared thread_local: a constant-initialised one read from another file would go through a TLS init hook that a hidden
+// reference cannot resolve to null.
+bool in_selftest();
+
+// Live handles (model / front-end / window): a stream handle borrows all three, and its owner may destroy one of them
+// first.  kws_stream_feed checks its borrowed pointers here -- pointer AND the serial it saw at kws_stream_create, so a new
+// handle that reuses a freed address does not pass -- and fails with KWS_ERR_INVALID_ARGUMENT instead of touching freed
+// memory.
+unsigned long long live_register(const void* h);
+void live_unregister(const void* h);
+unsigned long long live_serial(const void* h);      // 0: not a live handle
+
+int fail(int code, const char* fmt, ...);
+int hip_fail(hipError_t e, const char* what);
+
+// scope guard of kws_model::in_call
+struct BusyGuard {
+    std::atomic<int>* flag;
+    bool owned;
+    explicit BusyGuard(std::atomic<int>& f) : flag(&f), owned(f.exchange(1, std::memory_order_acquire) == 0) {}
+    ~BusyGuard() { if (owned) flag->store(0, std::memory_order_release); }
+    BusyGuard(const BusyGuard&) = delete;
+    BusyGuard& operator=(const BusyGuard&) = delete;
+};
+#define KWS_HIP(call)                                         \
+    do {                                                      \
+        hipError_t e_ = (call);                               \
+        if (e_ != hipSuccess) return kws_host::hip_fail(e_, #call); \
+    } while (0)
+
+// The canonical weight blob (kws_weights_nbytes): per layer Wg [(in+H), 2H], bg [2H], Wc [(in+H), H], bc [H]; then
+// Wfc [H, C] and bfc [C].  Offsets in floats, from the config alone.
+struct BlobLayout {
+    struct Layer { int in; size_t wg, bg, wc, bc; };
+    Layer layer[8];
+    size_t wfc, bfc, total;
+};
+BlobLayout blob_layout(const kws_config& c);
+
+struct LayerDev {
+    int in_dim;
+    // offsets (floats) into the single device allocation
+    size_t wx_res, wx_gen, wh_gen, bias;   // wx_res: first-layer x-part, interleaved k map (resident kernel)
+    int kcx_res, kcx_gen;
+    bool resident_ok;
+};
+
+// Where the packer put each precision's tables in the handle's one device allocation (offsets in floats)
+struct PackedWeights {
+    std::vector<LayerDev> layers;
+    size_t wfc_off = 0, bfc_off = 0;
+    // bf16 stack: offsets (floats) of the packed bf16 A operands
+    size_t bf_w[2] = {0, 0}, bf_wfc = 0;
+    int bf_kx0 = 0;
+    // f16x3 split stack: per layer the packed (hi, lo) fp16 A operands, and the projection's
+    std::vector<size_t> f16_w;
+    size_t f16_wfc = 0;
+    int f16_kx0 = 0;
+    bool f16_generic = false;        // hidden != 128: the L2-streaming kernels (gru_f16x3_generic.hip)
+    // int8 ("octbit") variant: per quantised layer the packed int16 couples + 127*colsum, and the projection
+    struct OctLayer { bool quantised = false; size_t wg = 0, wc = 0, b127 = 0; float scale_g = 0.f, scale_c = 0.f; };
+    std::vector<OctLayer> oct;
+    size_t oct_wfc = 0, oct_b127fc = 0;
+    float oct_scale_fc = 0.f;
+};
+// (config, canonical blob) -> the device image of every table the config's precision launches with, and where each one is.
+// KWS_OK, or the error code with kws_last_error() set.  Host code only.
+int pack_weights(const kws_config& cfg, const float* blob, PackedWeights* pk, std::vector<float>* image);
+
+// The arguments of one kws_step (include/kws_amd.h), and what the stream manager adds to them
+struct StepArgs {
+    const float *mel = nullptr, *state_in = nullptr;
+    float *logits = nullptr, *softmax = nullptr, *state_out = nullptr;
+    const int32_t* seq_len = nullptr;
+    const uint8_t* reset_mask = nullptr;
+    int8_t* tokens = nullptr;
+    int32_t* prev_word = nullptr;
+    float decode2_thres = 0.f;
+    int B = 0, T = 0;
+    hipStream_t stream = nullptr;
+    const kws::WindowTail* wt = nullptr;   // the stream manager's decode window, to ride at the end of the last layer's launch
+    bool locked = false;                   // the caller (kws_stream_feed) already holds the handle and has ordered the stream
+};
+
+// api_step.hip: one step (kws_step and the stream manager), whether its last launch can take a window tail, and the
+// ordering of a call against the handle's previous one
+int step_impl(kws_handle h, const StepArgs& a);
+bool step_takes_window(kws_handle h, int B, int T, int window_chunks);
+int call_enter(kws_handle h, hipStream_t st);
+int call_leave(kws_handle h, hipStream_t st);
+
+}  // namespace kws_host
+#pragma GCC visibility pop
+
+struct kws_model {
+    kws_config cfg;
+    int device = 0;
+    int kernel_kind = KWS_KERNEL_AUTO;
+    kws_host::PackedWeights pk;
+    float* d_weights = nullptr;
+    uint32_t* oct_aq = nullptr;      // int8 activation exchange [groups][2][16][128]
+    float2* oct_range = nullptr;     // [groups*16]
+    int32_t* oct_prev = nullptr;     // [B] copy of prev_word
+    size_t oct_groups = 0;
+    // Inter-layer seams.  ONE device allocation per memory kind that only ever grows (kws_reserve or the first call that
+    // needs more); each kws_step carves the buffers of its launch layout out of it -- sequential (1-2 buffers of T
+    // frames), layers overlapped on HIP streams (2(L-1) buffers of a time block), layer-pipelined (L-1 fine-grained
+    // buffers) -- so alternating layouts never reallocates, and a step within the reserved size never synchronises.
+    struct Arena { char* base = nullptr; size_t bytes = 0; };
+    Arena arena, arena_fine;
+    int scratch_allocs = 0;          // (re)allocations so far; each one synchronised the device (kws_scratch_stats)
+    float4* scratch[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // this call's seams: l -> scratch[l % nscratch]
+    int nscratch = 0;
+    bool pipe_disabled = false;
+    // time-blocked overlap of the layers on separate HIP streams (step_overlapped)
+    hipStream_t lane_stream[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    std::vector<hipEvent_t> ovl_events;
+    hipEvent_t ovl_tail[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // end of the last overlapped call, per lane
+    bool ovl_tail_valid = false;      // fine-grained memory unavailable, or a pipelined launch timed out: sequential launches from then on
+    // layer-pipelined launch of the generic kernel
+    int num_cus = 0;
+    int* pipe_ready = nullptr;       // [L][groups] frames published
+    size_t pipe_groups = 0;
+    int* pipe_error_host = nullptr;  // mapped pinned flag the kernel raises if a wait times out
+    int* pipe_error_dev = nullptr;
+    // One host thread at a time per handle (kws_amd.h): a second thread that enters kws_step / kws_reserve / kws_kernel_times
+    // while another is inside gets KWS_ERR_BUSY instead of racing on the scratch arena and the profiling slots.
+    std::atomic<int> in_call{0};
+    // The seams (and the stream managers' staging below) are shared by all calls of the handle.  Every call records
+    // `last_done` on its stream when its last launch is queued; a call that arrives on ANOTHER HIP stream than the one before
+    // makes its stream wait for that event (device-side ordering: no host stall, nothing that touches other handles' work,
+    // legal under stream capture).  The common path -- same stream as before -- pays one hipEventRecord.
+    hipStream_t last_stream = nullptr;
+    bool last_stream_valid = false;
+    hipEvent_t last_done = nullptr;
+    // Staging of the stream managers that borrow this handle (kws_stream_feed): widened PCM, mel, softmax and the two masks
+    // of ONE chunk.  They live only inside a feed, feeds of one handle are ordered (one host thread at a time, stream
+    // switches ordered by last_done), so every manager on the handle carves the same block: M managers cost M x their
+    // per-stream state, not M x a chunk's intermediates.  Grows at kws_stream_create only.
+    Arena stage;
+    // profiling
+    bool profiling = false;
+    struct Pending { int slot; hipEvent_t a, b; };
+    std::vector<Pending> pending;
+    std::vector<hipEvent_t> event_pool;
+    std::vector<float> ms_sum;
+    std::vector<int32_t> launches;
+    // kernel the last kws_step launched per profiling slot, as a small tag: the name is only formatted when somebody asks
+    // (kws_last_launch, kws_selftest) -- not on the launch path, where a 22-frame call is ~100 us of device time
+    enum LaunchFamily : uint8_t { kNone = 0, kBf16Stack, kF16x3, kPipelined, kOctbit, kOctbitFc, kResident, kGeneric, kF16x3Generic, kF16x3Pipelined };
+    struct LaunchTag { uint8_t family = kNone, kx = 0, first = 0, last = 0, window = 0; };
+    LaunchTag launch_tag[8];
+    std::string launch_name(int slot) const {
+        const LaunchTag& t = launch_tag[slot];
+        char nm[96];
+        nm[0] = 0;
+        switch (t.family) {
+            case kBf16Stack: break;
+            case kF16x3: snprintf(nm, sizeof(nm), "gru_layer_f16x3<%d, %s, %s>", t.kx, t.first ? "true" : "false", t.last ? "true" : "false"); break;
+            case kPipelined: snprintf(nm, sizeof(nm), "gru_stack_generic_pipelined<%d> (all %d layers, one launch)", t.kx, cfg.num_layers); break;
+            case kF16x3Generic: snprintf(nm, sizeof(nm), "gru_layer_f16x3_generic<%d, %s, %s>", t.kx, t.first ? "true" : "false", t.last ? "true" : "false"); break;
+            case kF16x3Pipelined: snprintf(nm, sizeof(nm), "gru_stack_f16x3_pipelined<%d> (all %d layers, one launch)", t.kx, cfg.num_layers); break;
+            case kOctbit: snprintf(nm, sizeof(nm), "gru_layer_octbit_kernel"); break;
+            case kOctbitFc: snprintf(nm, sizeof(nm), "gru_layer_octbit_kernel + octbit_fc_kernel"); break;
+            case kResident: snprintf(nm, sizeof(nm), "gru_layer_resident<%d, %s, %s>", t.kx, t.first ? "true" : "false", t.last ? "true" : "false"); break;
+            case kGeneric: snprintf(nm, sizeof(nm), "gru_layer_generic<%d, %s, %s>", t.kx, t.first ? "true" : "false", t.last ? "true" : "false"); break;
+            default: break;
+        }
+        std::string out = t.family == kBf16Stack ? std::string(kws::gru_stack_bf16_kernel_name(pk.bf_kx0, cfg.num_layers)) : std::string(nm);
+        if (t.window) out += " + window tail";          // the stream manager's decode-window step rode in this launch
+        return out;
+    }
+};
+
+struct kws_window {
+    int B = 0, nq = 0, tmax = 0, tmax_pad = 0, C = 0;
+    float thres = 0.f;
+    int8_t* words = nullptr;
+    int *lens = nullptr, *head = nullptr, *count = nullptr;
+    // the incremental form (kws_window_step_incremental, kws_stream_feed): a summary per queued chunk instead of its frames
+    // (window_device.h); a state of its own -- a window is driven through one of the two entry points, not both
+    uint8_t* inc_tab = nullptr;      // [B][nq][32]  tab | ftab
+    uint32_t* inc_meta = nullptr;    // [B][nq]
+    int *inc_head = nullptr, *inc_count = nullptr;
+    uint8_t* inc_delta_dev = nullptr;   // [256] label matcher of the bound label
+    uint8_t inc_delta[256] = {0};
+    char inc_label[17] = {0};
+    bool inc_bound = false;
+};
+
+struct kws_stream {
+    kws_model* model = nullptr;
+    kws_frontend* fe = nullptr;
+    kws_window* win = nullptr;
+    unsigned long long model_serial = 0, fe_serial = 0, win_serial = 0;   // live_serial() of the three at kws_stream_create
+    int B = 0, max_chunk = 0, tmax = 0, n_carry = 0, cur = 0;
+    float vad_thres = 0.f;
+    char label[17] = {0};
+    float* state = nullptr;          // caller-owned [L,B,H]
+    uint8_t* restart = nullptr;      // caller-owned [B]
+    float* carry[2] = {nullptr, nullptr};   // [B, fft - 1] each: the carried samples ping-pong (the only device memory a manager owns)
+    // one chunk's intermediates, carved out of the MODEL handle's staging block (kws_model::stage) at every feed:
+    size_t off_pcm_f32 = 0;          // [B, max_chunk]  int16 input widened here (front-ends other than the 400-point FFT, sub-frame chunks)
+    size_t off_mel = 0;              // [B, tmax, n_mel]
+    size_t off_softmax = 0;          // [B, tmax, C]
+    size_t off_silent = 0;           // [B]
+    size_t off_reset = 0;            // [B]
+    size_t stage_bytes = 0;
+    // the pointers of the current feed
+    float* pcm_f32 = nullptr;
+    float* mel = nullptr;
+    float* softmax = nullptr;
+    uint8_t* silent = nullptr;
+    uint8_t* reset = nullptr;
+};
+
+struct kws_frontend {
+    kws_frontend_config cfg;
+    float* d_tables = nullptr;
+    size_t dft_off = 0, melw_off = 0;
+    size_t fft_tw_off = 0, fft_mel_off = 0;   // fft_frontend.hip tables (fft_size 400 only)
+    int mel_lo[4] = {0, 0, 0, 0}, mel_cnt[4] = {0, 0, 0, 0}, mel_off[4] = {0, 0, 0, 0};
+    bool use_fft = false;
+    int nf_tiles = 0, mel_tiles = 0, kc4 = 0;
+    std::vector<float> basis;      // [n_mel][fft/2+1]
+};

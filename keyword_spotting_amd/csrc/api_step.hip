@@ -1,0 +1,603 @@
+// C ABI of libkws_amd.so (include/kws_amd.h): kws_step -- launch selection, the seam arenas, profiling slots, the launches.
+
+#include "api_internal.h"
+
+using namespace kws_host;
+
+namespace {
+
+bool is_resident(const kws_model* h, const LayerDev& Ld) {
+    return h->kernel_kind == KWS_KERNEL_RESIDENT || (h->kernel_kind == KWS_KERNEL_AUTO && Ld.resident_ok);
+}
+
+// The layer-pipelined launch needs all L x groups workgroups resident at once (one per CU) and the streaming kernel
+// on every layer; it pays when the layers would otherwise leave CUs idle.
+bool pipeline_eligible(kws_handle h, int B) {
+    // AUTO keeps the resident kernels where they exist even when this launch would be faster (H=128, L=2: +10 % at
+    // B <= 2048; L=4, B=1024: 2.2x; select it with KWS_KERNEL_GENERIC): the two kernel families round differently in
+    // the last bit, and a stream's result must not depend on how many neighbours it is batched or sharded with.
+    if (h->pipe_disabled) return false;
+    const bool f16_streaming = h->cfg.precision == KWS_F16X3 && h->pk.f16_generic;      // gru_stack_f16x3_pipelined
+    if ((h->cfg.precision != KWS_FP32 && !f16_streaming) || h->cfg.num_layers < 2 || h->kernel_kind == KWS_KERNEL_RESIDENT) return false;
+    for (const auto& L : h->pk.layers)
+        if (h->kernel_kind == KWS_KERNEL_AUTO && L.resident_ok) return false;
+    const long long groups = (B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup;
+    return h->num_cus > 0 && groups * h->cfg.num_layers <= h->num_cus;
+}
+
+// ---- scratch: what a call of shape (B, T) needs, and the arena it is carved from ------------------------------------
+#ifndef KWS_OVERLAP_MIN_T
+#define KWS_OVERLAP_MIN_T 64
+#endif
+bool overlap_shape_ok(kws_handle h, int B, int T) {      // step_overlapped, leaving the profiling switch aside
+    const kws_config& c = h->cfg;
+    if (c.precision != KWS_FP32 || c.num_layers < 2 || c.num_layers > 5) return false;
+    if (pipeline_eligible(h, B)) return false;            // the streaming kernel has its own in-kernel pipeline
+    const long long groups = (B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup;
+    return h->num_cus > 0 && groups * c.num_layers <= h->num_cus && T >= KWS_OVERLAP_MIN_T;
+}
+bool overlap_eligible(kws_handle h, int B, int T) { return !h->profiling && overlap_shape_ok(h, B, T); }
+void overlap_blocks(int T, int* nb_out, int* tb_out) {
+    int nb = T / 32 < 8 ? T / 32 : 8;              // more blocks: less fill/drain, more launch prologues (8: +6 % over 4)
+    if (nb < 2) nb = 2;
+    const int Tb = ((T + nb - 1) / nb + 15) & ~15;        // multiple of the epilogue ring
+    *nb_out = (T + Tb - 1) / Tb;
+    *tb_out = Tb;
+}
+
+struct SeamLayout { int nbuf; size_t bytes_each; bool fine; };
+constexpr int kNoFineGrainedMemory = 1;      // carve_seams: internal, never returned through the ABI
+enum { kLayoutSequential = 0, kLayoutOverlapped = 1 };
+SeamLayout seam_layout(kws_handle h, int B, int T, int which) {
+    const kws_config& c = h->cfg;
+    const size_t groups = (size_t)(B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup;
+    const size_t frame_bytes = groups * (size_t)c.hidden * 16 * sizeof(float);
+    SeamLayout s = {0, 0, false};
+    if (c.precision == KWS_BF16 || T <= 0 || B <= 0) return s;                    // the bf16 stack has no seam
+    const bool int8 = c.precision == KWS_INT8;
+    if (c.num_layers < 2 && !int8) return s;
+    if (which == kLayoutOverlapped) {
+        int nb, Tb;
+        overlap_blocks(T, &nb, &Tb);
+        s.nbuf = 2 * (c.num_layers - 1); s.bytes_each = frame_bytes * Tb;
+        return s;
+    }
+    if (pipeline_eligible(h, B)) { s.nbuf = c.num_layers - 1; s.bytes_each = frame_bytes * T; s.fine = true; return s; }
+    s.nbuf = (c.num_layers > 2 || int8) ? 2 : 1;         // sequential launches ping-pong two buffers
+    s.bytes_each = frame_bytes * T;
+    return s;
+}
+
+// Grows the arena if this layout does not fit (the only place kws_step can synchronise: the old block may still be in
+// use) and points h->scratch[] at the call's buffers.
+int carve_seams(kws_handle h, const SeamLayout& want) {
+    SeamLayout s = want;
+    s.bytes_each = (s.bytes_each + 255) & ~size_t(255);
+    kws_model::Arena& A = s.fine ? h->arena_fine : h->arena;
+    const size_t need = (size_t)s.nbuf * s.bytes_each;
+    if (need > A.bytes) {
+        KWS_HIP(hipDeviceSynchronize());
+        if (A.base) { hipFree(A.base); A.base = nullptr; A.bytes = 0; }
+        hipError_t e;
+        // pipelined seams are read by another XCD while the kernel runs: fine-grained (uncached, coherent) memory
+        if (s.fine) e = hipExtMallocWithFlags(reinterpret_cast<void**>(&A.base), need, hipDeviceMallocFinegrained);
+        else e = hipMalloc(reinterpret_cast<void**>(&A.base), need);
+        if (e != hipSuccess) {
+            A.base = nullptr;
+            (void)hipGetLastError();
+            return s.fine ? kNoFineGrainedMemory : hip_fail(e, "hipMalloc(scratch)");
+        }
+        A.bytes = need;
+        ++h->scratch_allocs;
+    }
+    for (int i = 0; i < 8; ++i)
+        h->scratch[i] = i < s.nbuf ? reinterpret_cast<float4*>(A.base + (size_t)i * s.bytes_each) : nullptr;
+    h->nscratch = s.nbuf;
+    return KWS_OK;
+}
+
+// Everything besides the seams that depends on the batch size: int8 exchange buffers, the pipelined launch's counters.
+int ensure_side_buffers(kws_handle h, int B) {
+    const size_t groups = (size_t)(B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup;
+    if (h->cfg.precision == KWS_INT8 && groups > h->oct_groups) {
+        KWS_HIP(hipDeviceSynchronize());
+        if (h->oct_aq) hipFree(h->oct_aq);
+        if (h->oct_range) hipFree(h->oct_range);
+        if (h->oct_prev) hipFree(h->oct_prev);
+        h->oct_aq = nullptr; h->oct_range = nullptr; h->oct_prev = nullptr; h->oct_groups = 0;
+        KWS_HIP(hipMalloc(reinterpret_cast<void**>(&h->oct_aq), groups * 2 * 16 * 128 * sizeof(uint32_t)));
+        KWS_HIP(hipMalloc(reinterpret_cast<void**>(&h->oct_range), groups * 16 * sizeof(float2)));
+        KWS_HIP(hipMalloc(reinterpret_cast<void**>(&h->oct_prev), groups * 16 * sizeof(int32_t)));
+        h->oct_groups = groups;
+        ++h->scratch_allocs;
+    }
+    if (pipeline_eligible(h, B)) {
+        if (!h->pipe_error_host) {
+            KWS_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->pipe_error_host), sizeof(int), hipHostMallocMapped));
+            *h->pipe_error_host = 0;
+            KWS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->pipe_error_dev), h->pipe_error_host, 0));
+        }
+        if (groups > h->pipe_groups) {
+            KWS_HIP(hipDeviceSynchronize());
+            if (h->pipe_ready) hipFree(h->pipe_ready);
+            h->pipe_ready = nullptr; h->pipe_groups = 0;
+            if (hipExtMallocWithFlags(reinterpret_cast<void**>(&h->pipe_ready), (size_t)h->cfg.num_layers * groups * sizeof(int),
+                                      hipDeviceMallocFinegrained) != hipSuccess) {
+                (void)hipGetLastError();
+                h->pipe_ready = nullptr;
+                h->pipe_disabled = true;         // no fine-grained device memory here: layer-by-layer launches from now on
+                return KWS_OK;
+            }
+            h->pipe_groups = groups;
+            ++h->scratch_allocs;
+        }
+    }
+    return KWS_OK;
+}
+
+// Seams of the sequential / pipelined layout for a call of shape (B, T).
+int ensure_scratch(kws_handle h, int B, int T) {
+    int rc = ensure_side_buffers(h, B);
+    if (rc != KWS_OK) return rc;
+    rc = carve_seams(h, seam_layout(h, B, T, kLayoutSequential));
+    if (rc == kNoFineGrainedMemory) {    // fine-grained memory unavailable: give the pipelined launch up for this handle
+        h->pipe_disabled = true;
+        rc = carve_seams(h, seam_layout(h, B, T, kLayoutSequential));
+    }
+    return rc;
+}
+
+// A layer-pipelined launch whose wait for the layer below timed out raises a mapped host flag; its results are invalid.
+// The flag is looked at (without synchronising) on every kws_step, by kws_poll_error, after the event syncs of
+// kws_kernel_times and in kws_destroy -- a step's own flag can only be seen once its kernel has run, so a caller that
+// needs certainty synchronises the stream and asks kws_poll_error.
+int check_pipe_error(kws_handle h) {
+    if (h->pipe_error_host && *reinterpret_cast<volatile int*>(h->pipe_error_host)) {
+        *reinterpret_cast<volatile int*>(h->pipe_error_host) = 0;
+        h->pipe_disabled = true;             // later steps launch layer by layer
+        return fail(KWS_ERR_HIP, "a layer-pipelined launch timed out waiting for the layer below; the results of that step are invalid");
+    }
+    return KWS_OK;
+}
+
+// The profiling slot of one launch (kws_set_profiling): profile_begin takes two events from the pool (or creates them) and
+// records the first; profile_end records the second and queues the pair for kws_kernel_times.  Inert while profiling is off.
+int profile_begin(kws_model* h, hipStream_t st, kws_model::Pending& pd) {
+    if (!h->profiling) return KWS_OK;
+    for (hipEvent_t* ev : {&pd.a, &pd.b}) {
+        if (!h->event_pool.empty()) { *ev = h->event_pool.back(); h->event_pool.pop_back(); }
+        else KWS_HIP(hipEventCreate(ev));
+    }
+    KWS_HIP(hipEventRecord(pd.a, st));
+    return KWS_OK;
+}
+int profile_end(kws_model* h, hipStream_t st, const kws_model::Pending& pd) {
+    if (!h->profiling) return KWS_OK;
+    KWS_HIP(hipEventRecord(pd.b, st));
+    h->pending.push_back(pd);
+    return KWS_OK;
+}
+
+// The last layer's epilogue fields (every layer's parameters carry them), from the step's arguments.  A launch over the time
+// block [t0, t0 + frames) of the call (step_overlapped) passes t0 and its length: the rows keep the call's T as their stride.
+void set_epilogue(kws::GruLayerParams& p, const StepArgs& a, const kws_config& c, bool last, int t0 = 0, int frames = 0) {
+    const int C = c.num_classes;
+    p.logits = a.logits ? a.logits + (size_t)t0 * C : nullptr;
+    p.softmax = a.softmax ? a.softmax + (size_t)t0 * C : nullptr;
+    p.tokens = a.tokens ? a.tokens + t0 : nullptr;
+    p.prev_word = a.prev_word;
+    p.decode_thres = a.decode2_thres;
+    p.value_clip = c.value_clip;
+    p.use_relu = c.use_relu;
+    p.B = a.B; p.T = frames ? frames : a.T; p.C = C;
+    if (frames) { p.t_stride = a.T; p.t_base = t0; }
+    if (a.wt && last) p.win = *a.wt;
+}
+// ... and the frame counters of layer l in a layer-pipelined launch
+void set_pipeline(kws::GruLayerParams& p, const kws_model* h, int l, bool last) {
+    p.ready_in = l == 0 ? nullptr : h->pipe_ready + (size_t)(l - 1) * h->pipe_groups;
+    p.ready_out = last ? nullptr : h->pipe_ready + (size_t)l * h->pipe_groups;
+    p.pipe_error = h->pipe_error_dev;
+}
+
+// Layer l of the fp32 kernels over the whole call (step_overlapped narrows it to a time block)
+void set_fp32_layer(kws::GruLayerParams& p, const kws_model* h, const StepArgs& a, int l, bool resident, bool last) {
+    const LayerDev& Ld = h->pk.layers[l];
+    const size_t state_off = (size_t)l * a.B * h->cfg.hidden;
+    memset(&p, 0, sizeof(p));
+    // resident kernels read the group-of-4 layouts too (dwordx4 prologue), except the first layer's
+    // x-part, whose k map is the interleaved one
+    p.wx = h->d_weights + ((resident && l == 0) ? Ld.wx_res : Ld.wx_gen);
+    p.wh = h->d_weights + Ld.wh_gen;
+    p.bias = h->d_weights + Ld.bias;
+    p.wfc = h->d_weights + h->pk.wfc_off;
+    p.bfc = h->d_weights + h->pk.bfc_off;
+    p.x_mel = a.mel;
+    p.x_prev = l == 0 ? nullptr : h->scratch[(l - 1) % h->nscratch];
+    p.h_out = last ? nullptr : h->scratch[l % h->nscratch];
+    p.state_in = a.state_in + state_off;
+    p.state_out = a.state_out + state_off;
+    p.seq_len = a.seq_len;
+    p.reset = a.reset_mask;
+    set_epilogue(p, a, h->cfg, last);
+    p.I = Ld.in_dim;
+    p.KCX = resident ? Ld.kcx_res : Ld.kcx_gen;
+}
+
+// Layers on separate HIP streams, time-blocked.  When L x groups workgroups fit the chip at once, the layers of a
+// long call need not run one after another: the call is cut into time blocks, layer l works on block k while layer
+// l-1 already works on block k+1 (its own stream, ordered by events; seam buffers double-buffered per block parity).
+// The kernels are the ones a plain call uses -- a call on frames [t0, t1) with the state carried is bit-identical to
+// the corresponding slice of one long call (tests/test_gpu_parity.py) -- so the result does not depend on whether
+// this path was taken.  Wall time ~ (slowest layer) x (1 + 1/blocks) instead of the sum over layers.
+int step_overlapped(kws_handle h, const StepArgs& a) {
+    const kws_config& c = h->cfg;
+    const int H = c.hidden, L = c.num_layers, B = a.B, T = a.T;
+    const hipStream_t st = a.stream;
+    int nb, Tb;
+    overlap_blocks(T, &nb, &Tb);
+    {
+        const int rc = carve_seams(h, seam_layout(h, B, T, kLayoutOverlapped));
+        if (rc != KWS_OK) return rc;
+    }
+    for (int l = 1; l < L; ++l)
+        if (!h->lane_stream[l]) KWS_HIP(hipStreamCreateWithFlags(&h->lane_stream[l], hipStreamNonBlocking));
+    while ((int)h->ovl_events.size() < L * nb + 1) {
+        hipEvent_t ev;
+        KWS_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        h->ovl_events.push_back(ev);
+    }
+    auto done = [&](int l, int k) { return h->ovl_events[1 + l * nb + k]; };
+    KWS_HIP(hipEventRecord(h->ovl_events[0], st));                          // everything queued before this call
+    for (int l = 1; l < L; ++l) KWS_HIP(hipStreamWaitEvent(h->lane_stream[l], h->ovl_events[0], 0));
+    for (int k = 0; k < nb; ++k) {
+        const int t0 = k * Tb, tk = (T - t0 < Tb) ? T - t0 : Tb;
+        for (int l = 0; l < L; ++l) {
+            const LayerDev& Ld = h->pk.layers[l];
+            const bool first = l == 0, last = l == L - 1;
+            const bool resident = is_resident(h, Ld);
+            hipStream_t sx = first ? st : h->lane_stream[l];
+            if (!first) KWS_HIP(hipStreamWaitEvent(sx, done(l - 1, k), 0));                    // its input block
+            if (!last && k >= 2) KWS_HIP(hipStreamWaitEvent(sx, done(l + 1, k - 2), 0));       // its output buffer is free again
+            kws::GruLayerParams p;
+            set_fp32_layer(p, h, a, l, resident, last);
+            p.x_mel = a.mel + (size_t)t0 * c.n_mel;
+            p.x_prev = first ? nullptr : h->scratch[2 * (l - 1) + (k & 1)];
+            p.h_out = last ? nullptr : h->scratch[2 * l + (k & 1)];
+            if (k > 0) { p.state_in = a.state_out + (size_t)l * B * H; p.reset = nullptr; }    // the block before left the state there
+            set_epilogue(p, a, c, last, t0, tk);
+            hipError_t e = resident ? kws::launch_gru_layer_resident(p, first, last, sx)
+                                    : kws::launch_gru_layer_generic(p, H, first, last, sx);
+            if (e != hipSuccess) return hip_fail(e, "launch (overlapped layers)");
+            if (k == 0) h->launch_tag[l] = {(uint8_t)(resident ? kws_model::kResident : kws_model::kGeneric), (uint8_t)(resident ? p.KCX : H / 64), first, last, 0};
+            KWS_HIP(hipEventRecord(done(l, k), sx));
+        }
+    }
+    for (int l = 1; l < L; ++l) {
+        KWS_HIP(hipStreamWaitEvent(st, done(l, nb - 1), 0));                                   // rejoin the caller's stream
+        if (!h->ovl_tail[l]) KWS_HIP(hipEventCreateWithFlags(&h->ovl_tail[l], hipEventDisableTiming));
+        KWS_HIP(hipEventRecord(h->ovl_tail[l], h->lane_stream[l]));
+    }
+    h->ovl_tail_valid = true;
+    return KWS_OK;
+}
+
+int step_body(kws_handle h, const StepArgs& a) {
+    const kws_config& c = h->cfg;
+    const int H = c.hidden, L = c.num_layers, B = a.B, T = a.T;
+    const hipStream_t st = a.stream;
+    {
+        const int rc = check_pipe_error(h);      // raised by an earlier layer-pipelined step of this handle
+        if (rc != KWS_OK) return rc;
+        // the handle's weights and scratch live on the device that was current at kws_create
+        int dev = -1;
+        if (hipGetDevice(&dev) == hipSuccess && dev != h->device)
+            return fail(KWS_ERR_INVALID_ARGUMENT, "handle was created on device %d, the current device is %d", h->device, dev);
+    }
+    if (h->ovl_tail_valid) {
+        // the previous call ran its upper layers on the handle's own streams: whatever stream this call comes in on,
+        // it must not touch the seam buffers (or reallocate them) before those kernels are done
+        for (int l = 1; l < L; ++l)
+            if (h->ovl_tail[l]) KWS_HIP(hipStreamWaitEvent(st, h->ovl_tail[l], 0));
+        h->ovl_tail_valid = false;
+    }
+    if (T == 0) {
+        // dynamic_rnn over zero frames hands the initial state back -- and clean_state() (detector.py:313-316) has already
+        // zeroed it for the streams the mask names
+        if (a.reset_mask) {
+            hipError_t e = kws::launch_state_passthrough(a.state_in, a.state_out, a.reset_mask, a.prev_word, L, B, H, st);
+            if (e != hipSuccess) return hip_fail(e, "launch state_passthrough");
+        } else if (a.state_out != a.state_in) {
+            KWS_HIP(hipMemcpyAsync(a.state_out, a.state_in, (size_t)L * B * H * sizeof(float), hipMemcpyDeviceToDevice, st));
+        }
+        return KWS_OK;
+    }
+    if (!a.mel) return fail(KWS_ERR_INVALID_ARGUMENT, "mel is null");
+    if (c.precision != KWS_BF16 && (c.precision != KWS_F16X3 || h->pk.f16_generic)) {
+        // the streaming kernels address a group's seam (T x H/16 KiB) through buffer instructions with 32-bit offsets
+        bool streaming = c.precision == KWS_F16X3;
+        for (const auto& Ld : h->pk.layers) streaming |= !is_resident(h, Ld);
+        if (streaming && (long long)T * (H / 16) >= (1LL << 21))
+            return fail(KWS_ERR_UNSUPPORTED, "T=%d frames of hidden=%d exceed the 2 GiB a stream group's seam may span: split the call "
+                        "(state carried across calls gives identical results)", T, H);
+    }
+    if ((reinterpret_cast<uintptr_t>(a.mel) & 15) != 0) return fail(KWS_ERR_INVALID_ARGUMENT, "mel must be 16-byte aligned");
+    if (c.precision == KWS_BF16) {
+        kws::GruBf16Params bp;
+        memset(&bp, 0, sizeof(bp));
+        for (int l = 0; l < L; ++l) {
+            bp.w[l] = reinterpret_cast<const uint4*>(h->d_weights + h->pk.bf_w[l]);
+            bp.bias[l] = h->d_weights + h->pk.layers[l].bias;
+        }
+        bp.wfc = reinterpret_cast<const uint4*>(h->d_weights + h->pk.bf_wfc);
+        bp.bfc = h->d_weights + h->pk.bfc_off;
+        bp.x_mel = a.mel; bp.state_in = a.state_in; bp.state_out = a.state_out;
+        bp.seq_len = a.seq_len; bp.reset = a.reset_mask;
+        set_epilogue(bp.epi, a, c, true);
+        bp.B = a.B; bp.T = a.T; bp.I = c.n_mel; bp.L = L;
+        kws_model::Pending pd = {0, nullptr, nullptr};
+        const int rc = profile_begin(h, st, pd);
+        if (rc != KWS_OK) return rc;
+        hipError_t e = kws::launch_gru_stack_bf16(bp, h->pk.bf_kx0, L, st);
+        if (e != hipSuccess) return hip_fail(e, "launch gru_stack_bf16");
+        h->launch_tag[0] = {kws_model::kBf16Stack, 0, 0, 0, (uint8_t)(a.wt != nullptr)};
+        for (int l = 1; l < L; ++l) h->launch_tag[l] = {};
+        return profile_end(h, st, pd);
+    }
+    if (c.precision == KWS_F16X3) {
+        // one launch per layer; the seams (same size as the fp32 ones) hold the layer outputs already split into fp16 pairs
+        int rc = ensure_scratch(h, B, T);
+        if (rc != KWS_OK) return rc;
+        // hidden = 256: weights streamed from L2; all L x groups workgroups in ONE layer-pipelined grid when they fit the chip
+        const bool f16_pipelined = h->pk.f16_generic && pipeline_eligible(h, B);
+        kws::GruF16StackParams fsp;
+        if (f16_pipelined) {
+            KWS_HIP(hipMemsetAsync(h->pipe_ready, 0, (size_t)L * h->pipe_groups * sizeof(int), st));
+            memset(&fsp, 0, sizeof(fsp));
+            fsp.L = L; fsp.G = (B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup; fsp.xcd_affine = (8 % L == 0) ? 1 : 0;
+        }
+        for (int l = 0; l < L; ++l) {
+            const bool first = l == 0, last = l == L - 1;
+            kws::GruF16Params fp;
+            memset(&fp, 0, sizeof(fp));
+            fp.w = reinterpret_cast<const uint4*>(h->d_weights + h->pk.f16_w[l]);
+            fp.bias = h->d_weights + h->pk.layers[l].bias;
+            fp.wfc = reinterpret_cast<const uint4*>(h->d_weights + h->pk.f16_wfc);
+            fp.bfc = h->d_weights + h->pk.bfc_off;
+            fp.x_mel = a.mel;
+            fp.x_prev = first ? nullptr : reinterpret_cast<const uint4*>(h->scratch[(l - 1) % h->nscratch]);
+            fp.h_out = last ? nullptr : reinterpret_cast<uint4*>(h->scratch[l % h->nscratch]);
+            fp.state_in = a.state_in + (size_t)l * B * H;
+            fp.state_out = a.state_out + (size_t)l * B * H;
+            fp.seq_len = a.seq_len; fp.reset = a.reset_mask;
+            set_epilogue(fp.epi, a, c, last);
+            fp.B = B; fp.T = a.T; fp.I = h->pk.layers[l].in_dim;
+            if (f16_pipelined) {
+                set_pipeline(fp.epi, h, l, last);
+                fsp.layer[l] = fp;
+                h->launch_tag[l] = {};
+                if (!last) continue;
+            }
+            kws_model::Pending pd = {l, nullptr, nullptr};
+            rc = profile_begin(h, st, pd);
+            if (rc != KWS_OK) return rc;
+            hipError_t e;
+            if (f16_pipelined) {
+                e = kws::launch_gru_stack_f16x3_pipelined(fsp, H, st);        // timed as the last layer's slot
+                if (e != hipSuccess) return hip_fail(e, "launch gru_stack_f16x3_pipelined");
+                h->launch_tag[l] = {kws_model::kF16x3Pipelined, (uint8_t)(H / 64), 0, 0};
+            } else if (h->pk.f16_generic) {
+                e = kws::launch_gru_layer_f16x3_generic(fp, H, first, last, st);
+                if (e != hipSuccess) return hip_fail(e, "launch gru_layer_f16x3_generic");
+                h->launch_tag[l] = {kws_model::kF16x3Generic, (uint8_t)(H / 64), first, last};
+            } else {
+                e = kws::launch_gru_layer_f16x3(fp, first, last, st);
+                if (e != hipSuccess) return hip_fail(e, "launch gru_layer_f16x3");
+                h->launch_tag[l] = {kws_model::kF16x3, (uint8_t)(first ? h->pk.f16_kx0 : 4), first, last, (uint8_t)(a.wt != nullptr && last)};
+            }
+            rc = profile_end(h, st, pd);
+            if (rc != KWS_OK) return rc;
+        }
+        return KWS_OK;
+    }
+    if (overlap_eligible(h, B, T)) return step_overlapped(h, a);
+    int rc = ensure_scratch(h, B, T);
+    if (rc != KWS_OK) return rc;
+
+    const bool int8 = c.precision == KWS_INT8;
+    if (int8 && a.prev_word)
+        KWS_HIP(hipMemcpyAsync(h->oct_prev, a.prev_word, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+    // layer-pipelined launch (gru_stack_generic_pipelined): all layers of all groups in one grid
+    const bool pipelined = pipeline_eligible(h, B);
+    const int groups = (B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup;
+    kws::GruStackParams sp;
+    if (pipelined) {
+        KWS_HIP(hipMemsetAsync(h->pipe_ready, 0, (size_t)L * h->pipe_groups * sizeof(int), st));
+        memset(&sp, 0, sizeof(sp));
+        sp.L = L; sp.G = groups; sp.xcd_affine = (8 % L == 0) ? 1 : 0;
+    }
+    for (int l = 0; l < L; ++l) {
+        // int8: every GRU layer hands its output rows to the next stage through the xl scratch; the class
+        // projection is its own OctbitMatMul call over the whole [T,H] block (launch_octbit_fc below)
+        const bool first = l == 0, last = !int8 && l == L - 1;
+        const bool resident = !pipelined && is_resident(h, h->pk.layers[l]);
+        kws::GruLayerParams p;
+        set_fp32_layer(p, h, a, l, resident, last);
+        if (pipelined) {
+            set_pipeline(p, h, l, last);
+            sp.layer[l] = p;
+            if (!last) continue;
+        }
+        kws_model::Pending pd = {l, nullptr, nullptr};
+        rc = profile_begin(h, st, pd);
+        if (rc != KWS_OK) return rc;
+        hipError_t e;
+        if (pipelined) {
+            e = kws::launch_gru_stack_generic_pipelined(sp, H, st);       // timed as the last layer's slot
+            if (e != hipSuccess) return hip_fail(e, "launch gru_stack_generic_pipelined");
+        } else if (int8 && h->pk.oct[l].quantised) {
+            const PackedWeights::OctLayer& O = h->pk.oct[l];
+            kws::GruOctbitParams op;
+            memset(&op, 0, sizeof(op));
+            op.wg = reinterpret_cast<const uint32_t*>(h->d_weights + O.wg);
+            op.wc = reinterpret_cast<const uint32_t*>(h->d_weights + O.wc);
+            op.bias = p.bias; op.b127 = h->d_weights + O.b127;
+            op.scale_g = O.scale_g; op.scale_c = O.scale_c;
+            op.x_prev = p.x_prev; op.h_out = p.h_out;
+            op.state_in = p.state_in; op.state_out = p.state_out;
+            op.seq_len = a.seq_len; op.reset = a.reset_mask;
+            op.aq = h->oct_aq; op.B = B; op.T = a.T;
+            op.range = (l == L - 1) ? h->oct_range : nullptr;
+            e = kws::launch_gru_layer_octbit(op, st);
+            if (e != hipSuccess) return hip_fail(e, "launch gru_layer_octbit");
+        } else {
+            e = resident ? kws::launch_gru_layer_resident(p, first, last, st)
+                         : kws::launch_gru_layer_generic(p, H, first, last, st);
+            if (e != hipSuccess) return hip_fail(e, resident ? "launch gru_layer_resident" : "launch gru_layer_generic");
+        }
+        if (pipelined) {
+            h->launch_tag[l] = {kws_model::kPipelined, (uint8_t)(H / 64), 0, 0};
+            for (int k = 0; k < l; ++k) h->launch_tag[k] = {};
+        } else if (int8 && h->pk.oct[l].quantised) h->launch_tag[l] = {(uint8_t)(l == L - 1 ? kws_model::kOctbitFc : kws_model::kOctbit), 0, 0, 0};
+        else if (resident) h->launch_tag[l] = {kws_model::kResident, (uint8_t)p.KCX, first, last, (uint8_t)(a.wt != nullptr && last)};
+        else h->launch_tag[l] = {kws_model::kGeneric, (uint8_t)(H / 64), first, last};
+        if (int8 && l == L - 1) {
+            kws::OctbitFcParams fp;
+            memset(&fp, 0, sizeof(fp));
+            fp.wfc = reinterpret_cast<const uint32_t*>(h->d_weights + h->pk.oct_wfc);
+            fp.b127 = h->d_weights + h->pk.oct_b127fc;
+            fp.bfc = h->d_weights + h->pk.bfc_off;
+            fp.scale_w = h->pk.oct_scale_fc;
+            fp.h_top = h->scratch[l % h->nscratch];
+            fp.range = h->oct_range;
+            fp.range_ready = h->pk.oct[l].quantised ? 1 : 0;
+            fp.prev_in = a.prev_word ? h->oct_prev : nullptr;
+            fp.logits = a.logits; fp.softmax = a.softmax; fp.tokens = a.tokens; fp.prev_word = a.prev_word;
+            fp.decode_thres = a.decode2_thres; fp.value_clip = c.value_clip; fp.use_relu = c.use_relu;
+            fp.B = B; fp.T = a.T; fp.C = c.num_classes;
+            e = kws::launch_octbit_fc(fp, st);
+            if (e != hipSuccess) return hip_fail(e, "launch octbit_fc");
+        }
+        rc = profile_end(h, st, pd);
+        if (rc != KWS_OK) return rc;
+    }
+    return KWS_OK;
+}
+
+}  // namespace
+
+// Can the last layer's launch of a (B, T) step on this handle take the window tail along?  (kws_stream_feed asks before it
+// hands one to step_impl; the kernels without a tail instantiation -- generic, pipelined, overlapped, int8, single-layer fp32,
+// 4-wave bf16 -- are followed by window_inc_kernel instead.)
+bool kws_host::step_takes_window(kws_handle h, int B, int T, int window_chunks) {
+    const kws_config& c = h->cfg;
+    static const bool off = [] { const char* e = getenv("KWS_NO_WINDOW_TAIL"); return e && e[0] == '1'; }();     // A/B switch (tools/bench_e2e.py)
+    if (off || T < 1 || T > kws::kWinTailMaxFrames || window_chunks > kws::kWinTailMaxChunks) return false;
+    // One group per workgroup only: the tail is ~2 us of latency-bound work at the end of a group.  At the end of the launch
+    // that replaces a ~4 us launch of its own; in a persistent workgroup it would sit between two groups, on the critical
+    // path once per group (measured, bf16, 16384 streams: 0.349-0.359 ms per chunk with the tail against 0.338-0.340 with
+    // window_inc_kernel behind the stack)
+    if ((B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup > (h->num_cus > 0 ? h->num_cus : 256)) return false;
+    if (c.precision == KWS_BF16) return kws::gru_stack_bf16_takes_window(h->pk.bf_kx0, c.num_layers);
+    if (c.precision == KWS_F16X3) return !h->pk.f16_generic;
+    if (c.precision != KWS_FP32 || pipeline_eligible(h, B) || overlap_eligible(h, B, T)) return false;
+    return is_resident(h, h->pk.layers[c.num_layers - 1]) && kws::gru_resident_takes_window(c.num_layers == 1, true);
+}
+
+// Ordering of a call against the handle's previous one (kws_model::last_done): device-side, never a host wait.
+int kws_host::call_enter(kws_handle h, hipStream_t st) {
+    if (h->last_stream_valid && st != h->last_stream) KWS_HIP(hipStreamWaitEvent(st, h->last_done, 0));
+    h->last_stream = st;
+    h->last_stream_valid = true;
+    return KWS_OK;
+}
+int kws_host::call_leave(kws_handle h, hipStream_t st) {
+    KWS_HIP(hipEventRecord(h->last_done, st));
+    return KWS_OK;
+}
+
+int kws_host::step_impl(kws_handle h, const StepArgs& a) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    if (a.wt && (a.seq_len || !step_takes_window(h, a.B, a.T, a.wt->nq))) return fail(KWS_ERR_UNSUPPORTED, "internal: this step cannot take a window tail");
+    if (a.B < 0 || a.T < 0) return fail(KWS_ERR_INVALID_ARGUMENT, "negative B=%d or T=%d", a.B, a.T);
+    if (a.B == 0) return KWS_OK;   // nothing to advance (empty tensors have null data pointers)
+    if (!a.state_in || !a.state_out) return fail(KWS_ERR_INVALID_ARGUMENT, "state_in/state_out must not be null");
+    if (a.tokens && !a.prev_word) return fail(KWS_ERR_INVALID_ARGUMENT, "tokens requires prev_word");
+    if (a.locked) return step_body(h, a);
+    BusyGuard busy(h->in_call);
+    if (!busy.owned)
+        return fail(KWS_ERR_BUSY, "kws_step: another host thread is inside a call on this handle (one thread at a time per handle; "
+                    "use one handle per thread)");
+    int rc = call_enter(h, a.stream);       // the previous call's kernels may still own the seams: this stream waits for them on the device
+    if (rc != KWS_OK) return rc;
+    rc = step_body(h, a);
+    const int rl = call_leave(h, a.stream);     // also after a failure: whatever was queued before it is what the next call must wait for
+    return rc != KWS_OK ? rc : rl;
+}
+
+extern "C" {
+
+int kws_step(kws_handle h, const float* mel, const float* state_in, float* logits, float* softmax,
+             float* state_out, const int32_t* seq_len, const uint8_t* reset_mask, int8_t* tokens,
+             int32_t* prev_word, float decode2_thres, int B, int T, void* stream) {
+    const StepArgs a = {mel, state_in, logits, softmax, state_out, seq_len, reset_mask, tokens, prev_word, decode2_thres, B, T,
+                        static_cast<hipStream_t>(stream)};
+    return step_impl(h, a);
+}
+
+int kws_reserve(kws_handle h, int B, int T) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    BusyGuard busy(h->in_call);
+    if (!busy.owned) return fail(KWS_ERR_BUSY, "kws_reserve: another host thread is inside a call on this handle");
+    if (B < 0 || T < 0) return fail(KWS_ERR_INVALID_ARGUMENT, "negative B=%d or T=%d", B, T);
+    // whichever launch layout kws_step picks for (B, T) -- it depends on kws_set_profiling too -- fits afterwards
+    int rc = ensure_scratch(h, B, T);
+    if (rc != KWS_OK) return rc;
+    if (overlap_shape_ok(h, B, T)) rc = carve_seams(h, seam_layout(h, B, T, kLayoutOverlapped));
+    return rc;
+}
+
+int kws_scratch_stats(kws_handle h, size_t* bytes_reserved, int32_t* allocations) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    if (bytes_reserved) *bytes_reserved = h->arena.bytes + h->arena_fine.bytes;
+    if (allocations) *allocations = h->scratch_allocs;
+    return KWS_OK;
+}
+
+int kws_poll_error(kws_handle h) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    return check_pipe_error(h);
+}
+
+int kws_set_profiling(kws_handle h, int enable) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    h->profiling = enable != 0;
+    return KWS_OK;
+}
+
+int kws_kernel_times(kws_handle h, float* ms_sum, int32_t* launches, int reset) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    BusyGuard busy(h->in_call);
+    if (!busy.owned) return fail(KWS_ERR_BUSY, "kws_kernel_times: another host thread is inside a call on this handle");
+    for (auto& pd : h->pending) {
+        KWS_HIP(hipEventSynchronize(pd.b));
+        float ms = 0.f;
+        KWS_HIP(hipEventElapsedTime(&ms, pd.a, pd.b));
+        h->ms_sum[pd.slot] += ms;
+        h->launches[pd.slot] += 1;
+        h->event_pool.push_back(pd.a);
+        h->event_pool.push_back(pd.b);
+    }
+    h->pending.clear();
+    for (int l = 0; l < h->cfg.num_layers; ++l) {
+        if (ms_sum) ms_sum[l] = h->ms_sum[l];
+        if (launches) launches[l] = h->launches[l];
+    }
+    if (reset) {
+        std::fill(h->ms_sum.begin(), h->ms_sum.end(), 0.f);
+        std::fill(h->launches.begin(), h->launches.end(), 0);
+    }
+    return check_pipe_error(h);
+}
+
+}  // extern "C"

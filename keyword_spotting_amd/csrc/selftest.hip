@@ -1,0 +1,221 @@
+// kws_selftest: the library's own known answers, run through kws_step on temporary handles.
+
+#include "api_internal.h"
+
+using namespace kws_host;
+
+// The kernels depend on things the compiler does not check: hand-placed wait states around inline-asm MFMAs (gru_device.h),
+// an internal LLVM option for gru_bf16.hip (csrc/Makefile).  A build by another ROCm can therefore be silently wrong; the
+// GPU test-suite catches that, a deployment has no test-suite.  So the library carries its own known answers: a plain
+// double-precision host loop of the cell (below; the published TF-1.x GRUCell, models/rnn_ctc.py:179-185,228-243) and
+// TensorFlow's own unit-test constants for it (rnn_cell_test.py testGRUCell / testMultiRNNCell: all kernels 0.5, gate bias
+// 1, candidate bias 0, x = 1, h = 0.1 -> 0.175991, 0.156736 for three inputs, 0.13248 from the second stacked cell).
+namespace {
+
+thread_local bool g_in_selftest = false;
+
+// (mel [B,T,I], state [L,B,H]) -> (logits [B,T,C], state'), canonical blob layout of kws_weights_nbytes; double throughout
+void host_forward(const kws_config& c, const float* blob, const float* mel, const float* st0, int B, int T,
+                  std::vector<double>& logits, std::vector<double>& state) {
+    const int H = c.hidden, L = c.num_layers, C = c.num_classes;
+    const BlobLayout bl = blob_layout(c);
+    state.assign(st0, st0 + (size_t)L * B * H);
+    logits.assign((size_t)B * T * C, 0.0);
+    std::vector<double> x, g(2 * H), cand(H), hn(H);
+    for (int b = 0; b < B; ++b)
+        for (int t = 0; t < T; ++t) {
+            x.assign(mel + ((size_t)b * T + t) * c.n_mel, mel + ((size_t)b * T + t + 1) * c.n_mel);
+            for (int l = 0; l < L; ++l) {
+                const int I = bl.layer[l].in;
+                const float *Wg = blob + bl.layer[l].wg, *bg = blob + bl.layer[l].bg, *Wc = blob + bl.layer[l].wc, *bc = blob + bl.layer[l].bc;
+                double* h = &state[((size_t)l * B + b) * H];
+                for (int j = 0; j < 2 * H; ++j) {
+                    double a = bg[j];
+                    for (int k = 0; k < I; ++k) a += x[k] * Wg[(size_t)k * 2 * H + j];
+                    for (int k = 0; k < H; ++k) a += h[k] * Wg[(size_t)(I + k) * 2 * H + j];
+                    g[j] = 1.0 / (1.0 + std::exp(-a));                          // [r | u]
+                }
+                for (int j = 0; j < H; ++j) {
+                    double a = bc[j];
+                    for (int k = 0; k < I; ++k) a += x[k] * Wc[(size_t)k * H + j];
+                    for (int k = 0; k < H; ++k) a += g[k] * h[k] * Wc[(size_t)(I + k) * H + j];   // r (.) h before the matmul
+                    cand[j] = std::tanh(a);
+                }
+                for (int j = 0; j < H; ++j) hn[j] = g[H + j] * h[j] + (1.0 - g[H + j]) * cand[j];
+                std::copy(hn.begin(), hn.end(), h);
+                x = hn;
+            }
+            const float *Wfc = blob + bl.wfc, *bfc = blob + bl.bfc;
+            for (int k = 0; k < C; ++k) {
+                double a = bfc[k];
+                for (int j = 0; j < H; ++j) a += x[j] * Wfc[(size_t)j * C + k];
+                if (c.use_relu) { a = std::max(a, 0.0); if (c.value_clip > 0) a = std::min(a, 20.0); }
+                logits[((size_t)b * T + t) * C + k] = a;
+            }
+        }
+}
+
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) hipFree(p); }
+    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 4); }
+};
+
+// one case through kws_step on a temporary handle; *err_state / *err_logit = max abs deviation from the host loop
+int selftest_case(const kws_config& cfg, int kernel_kind, const std::vector<float>& blob, const std::vector<float>& mel,
+                  const std::vector<float>& st0, int B, int T, double* err_logit, double* err_state, std::vector<float>* state_out,
+                  std::string* kernels) {
+    const int H = cfg.hidden, L = cfg.num_layers, C = cfg.num_classes;
+    kws_handle m = nullptr;
+    int rc = kws_create(&cfg, blob.data(), blob.size() * sizeof(float), &m);
+    if (rc != KWS_OK) return rc;
+    rc = kws_set_kernel(m, kernel_kind);
+    DevBuf d_mel, d_st, d_lg;
+    std::vector<float> lg((size_t)B * T * C), st((size_t)L * B * H);
+    auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && rc == KWS_OK) rc = hip_fail(e, what); };
+    if (rc == KWS_OK) {
+        hip(d_mel.alloc(mel.size() * 4), "selftest hipMalloc");
+        hip(d_st.alloc(st.size() * 4), "selftest hipMalloc");
+        hip(d_lg.alloc(lg.size() * 4), "selftest hipMalloc");
+    }
+    if (rc == KWS_OK) {
+        hip(hipMemcpy(d_mel.p, mel.data(), mel.size() * 4, hipMemcpyHostToDevice), "selftest upload");
+        hip(hipMemcpy(d_st.p, st0.data(), st0.size() * 4, hipMemcpyHostToDevice), "selftest upload");
+        hip(hipDeviceSynchronize(), "selftest sync");
+    }
+    if (rc == KWS_OK)
+        rc = kws_step(m, static_cast<const float*>(d_mel.p), static_cast<const float*>(d_st.p), static_cast<float*>(d_lg.p), nullptr,
+                      static_cast<float*>(d_st.p), nullptr, nullptr, nullptr, nullptr, 0.4f, B, T, nullptr);
+    if (rc == KWS_OK) {
+        hip(hipDeviceSynchronize(), "selftest kernels");
+        hip(hipMemcpy(lg.data(), d_lg.p, lg.size() * 4, hipMemcpyDeviceToHost), "selftest download");
+        hip(hipMemcpy(st.data(), d_st.p, st.size() * 4, hipMemcpyDeviceToHost), "selftest download");
+    }
+    if (rc == KWS_OK) rc = kws_poll_error(m);
+    if (rc == KWS_OK && kernels) {
+        kernels->clear();
+        for (int l = 0; l < L; ++l)
+            if (m->launch_tag[l].family != kws_model::kNone) *kernels += (kernels->empty() ? "" : " + ") + m->launch_name(l);
+    }
+    const std::string keep = g_last_error;
+    kws_destroy(m);
+    if (rc != KWS_OK) { g_last_error = keep; return rc; }
+    std::vector<double> want_l, want_s;
+    host_forward(cfg, blob.data(), mel.data(), st0.data(), B, T, want_l, want_s);
+    double el = 0.0, es = 0.0;
+    for (size_t i = 0; i < lg.size(); ++i) { const double d = std::fabs(lg[i] - want_l[i]); el = (d > el || d != d) ? d : el; }
+    for (size_t i = 0; i < st.size(); ++i) { const double d = std::fabs(st[i] - want_s[i]); es = (d > es || d != d) ? d : es; }
+    *err_logit = el; *err_state = es;
+    if (state_out) *state_out = st;
+    return KWS_OK;
+}
+
+// deterministic pseudo-random floats in [-1, 1) (no <random>: identical on every libstdc++)
+struct Lcg {
+    uint64_t s;
+    float next() { s = s * 6364136223846793005ull + 1442695040888963407ull; return (float)((double)(s >> 11) / 9007199254740992.0 * 2.0 - 1.0); }
+};
+
+}  // namespace
+
+bool kws_host::in_selftest() { return g_in_selftest; }
+
+extern "C" int kws_selftest(kws_handle h) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    if (g_in_selftest) return KWS_OK;
+    struct Guard { Guard() { g_in_selftest = true; } ~Guard() { g_in_selftest = false; } } guard;
+    const kws_config cfg = h->cfg;
+    const int H = cfg.hidden, L = cfg.num_layers, C = cfg.num_classes, I0 = cfg.n_mel;
+    const BlobLayout bl = blob_layout(cfg);
+    // tolerances: what the arithmetic of each precision leaves on these two cases (fp32: observed <= 4e-6 / 1e-7)
+    double tol_rand_logit, tol_rand_state, tol_kat;
+    switch (cfg.precision) {
+        case KWS_BF16: tol_rand_logit = 6e-2; tol_rand_state = 2e-2; tol_kat = 2e-3; break;
+        case KWS_INT8: tol_rand_logit = -1.0; tol_rand_state = -1.0; tol_kat = 2e-2; break;   // int8: known answers only
+        default:       tol_rand_logit = 5e-5; tol_rand_state = 2e-5; tol_kat = 1e-6; break;   // fp32 and the f16x3 split
+    }
+    std::vector<int> kinds;
+    if (cfg.precision == KWS_FP32) {
+        bool res_ok = true;
+        for (const auto& Ld : h->pk.layers) res_ok &= Ld.resident_ok;
+        if (res_ok) kinds.push_back(KWS_KERNEL_RESIDENT);
+        kinds.push_back(KWS_KERNEL_GENERIC);
+    } else {
+        kinds.push_back(KWS_KERNEL_AUTO);
+    }
+    for (int kind : kinds) {
+        std::string kernels;
+        // (1) TensorFlow's published constants, the 2-unit test cell embedded in this shape: units 0,1 and inputs 0..n_in-1 live
+        for (int n_in = 2; n_in <= 3 && n_in <= I0; ++n_in) {
+            std::vector<float> blob(bl.total, 0.f);
+            for (int l = 0; l < L; ++l) {
+                const int in = bl.layer[l].in, live = l == 0 ? n_in : 2;
+                float* Wg = blob.data() + bl.layer[l].wg;
+                float* bg = blob.data() + bl.layer[l].bg;
+                float* Wc = blob.data() + bl.layer[l].wc;
+                for (int j = 0; j < 2 * H; ++j) bg[j] = 1.f;
+                for (int r = 0; r < live + 2; ++r) {
+                    const int row = r < live ? r : in + (r - live);
+                    for (int u = 0; u < 2; ++u) {
+                        Wg[(size_t)row * 2 * H + u] = 0.5f; Wg[(size_t)row * 2 * H + H + u] = 0.5f; Wc[(size_t)row * H + u] = 0.5f;
+                    }
+                }
+            }
+            float* Wfc = blob.data() + bl.wfc;
+            Wfc[0 * C + 0] = 1.f; Wfc[1 * C + 1] = 1.f;
+            const int B = 19, T = 1;
+            std::vector<float> mel((size_t)B * T * I0, 0.f), st0((size_t)L * B * H, 0.f), st;
+            for (int b = 0; b < B; ++b) {
+                for (int k = 0; k < n_in; ++k) mel[(size_t)b * I0 + k] = 1.f;
+                for (int l = 0; l < L; ++l) st0[((size_t)l * B + b) * H + 0] = st0[((size_t)l * B + b) * H + 1] = 0.1f;
+            }
+            double el, es;
+            const int rc = selftest_case(cfg, kind, blob, mel, st0, B, T, &el, &es, &st, &kernels);
+            if (rc != KWS_OK) return rc;
+            const double first = n_in == 2 ? 0.175991 : 0.156736;
+            double worst = 0.0;
+            for (int b = 0; b < B; ++b) {
+                for (int u = 0; u < 2; ++u) worst = std::max(worst, std::fabs(st[(size_t)b * H + u] - first));
+                if (L >= 2 && n_in == 2) for (int u = 0; u < 2; ++u) worst = std::max(worst, std::fabs(st[((size_t)B + b) * H + u] - 0.13248));
+                if (cfg.precision != KWS_INT8)
+                    for (int j = 2; j < H; ++j) if (st[(size_t)b * H + j] != 0.f) worst = 1.0;     // dead units stay exactly 0
+            }
+            if (!(worst <= tol_kat + 1e-6))
+                return fail(KWS_ERR_HIP, "kws_selftest: %s returns TensorFlow's published GRUCell constant (%g) with error %.3g (tolerance %.1g). "
+                            "This build (%s) computes wrong results on this device: rebuild with the ROCm release it was validated on, "
+                            "or run the repository's GPU tests.", kernels.c_str(), first, worst, tol_kat, kws_version());
+        }
+        // (2) 8 random frames of 19 streams against the host double-precision loop
+        if (tol_rand_logit > 0) {
+            Lcg rng{0x9e3779b97f4a7c15ull + (uint64_t)kind};
+            std::vector<float> blob(bl.total);
+            for (int l = 0; l < L; ++l) {
+                const int in = bl.layer[l].in;
+                float* Wg = blob.data() + bl.layer[l].wg;
+                float* bg = blob.data() + bl.layer[l].bg;
+                float* Wc = blob.data() + bl.layer[l].wc;
+                float* bc = blob.data() + bl.layer[l].bc;
+                const float ag = std::sqrt(6.f / (in + H + 2 * H)), ac = std::sqrt(6.f / (in + H + H));
+                for (size_t i = 0; i < (size_t)(in + H) * 2 * H; ++i) Wg[i] = ag * rng.next();
+                for (int j = 0; j < 2 * H; ++j) bg[j] = 1.f + 0.3f * rng.next();
+                for (size_t i = 0; i < (size_t)(in + H) * H; ++i) Wc[i] = ac * rng.next();
+                for (int j = 0; j < H; ++j) bc[j] = 0.3f * rng.next();
+            }
+            float* Wfc = blob.data() + bl.wfc;
+            for (int i = 0; i < H * C + C; ++i) Wfc[i] = rng.next();
+            const int B = 19, T = 8;
+            std::vector<float> mel((size_t)B * T * I0), st0((size_t)L * B * H);
+            for (auto& v : mel) v = 2.f * std::fabs(rng.next());
+            for (auto& v : st0) v = 0.5f * rng.next();
+            double el, es;
+            const int rc = selftest_case(cfg, kind, blob, mel, st0, B, T, &el, &es, nullptr, &kernels);
+            if (rc != KWS_OK) return rc;
+            if (!(el <= tol_rand_logit && es <= tol_rand_state))
+                return fail(KWS_ERR_HIP, "kws_selftest: %s differs from the host double-precision loop on 19 streams x 8 frames: max |dlogit| "
+                            "%.3g (tolerance %.1g), max |dstate| %.3g (tolerance %.1g). This build (%s) computes wrong results on this "
+                            "device: rebuild with the ROCm release it was validated on, or run the repository's GPU tests.",
+                            kernels.c_str(), el, tol_rand_logit, es, tol_rand_state, kws_version());
+        }
+    }
+    return KWS_OK;
+}
