@@ -269,10 +269,43 @@ typedef struct kws_stream* kws_stream_handle;
 int kws_stream_create(kws_handle model, kws_frontend_handle frontend, kws_window_handle window, int B, int max_chunk_samples,
                       float vad_thres, const char* label, float* state, uint8_t* restart, kws_stream_handle* out);
 int kws_stream_destroy(kws_stream_handle h);
-/* Forgets the carried samples (the model state, restart mask and window belong to the caller). */
+/* Forgets the carried samples (the model state, restart mask and window belong to the caller), and returns the handle to
+ * lock-step mode (below).  Host-side only: no device work. */
 int kws_stream_reset(kws_stream_handle h);
 int kws_stream_feed(kws_stream_handle h, const void* pcm /*[B,n] device*/, int n, int pcm_int16, int32_t* hit /*[B] device*/,
                     void* stream);
+/* Per-stream arrival (ragged chunks): the same iteration with stream b reading its own n_b = n_per_stream[b] samples, the
+ * first n_b of row b of `pcm` [B, n_max] (samples at or past n_b are never read into a result; the padding may hold anything).
+ * Each stream follows detector.py:158-209 on its own:
+ *   n_b == 0                 the iteration is skipped for this stream only: no VAD, no reset, no window slot; its carry, GRU
+ *                            state, window and restart[b] stay bitwise as they are; hit[b] = 0.  (A restart requested by an
+ *                            earlier trigger waits for the stream's next non-empty chunk.)
+ *   carry_b + n_b < fft_size VAD over the n_b samples, every sample carried, zero frames, an empty window slot (as above)
+ *   otherwise                VAD, frames(carry_b + n_b) frames with this stream's reset mask, keep_b samples carried, one
+ *                            window slot of those frames, decode, trigger.
+ * The lengths stay on the device: no host read, no host wait (a caller may fill them on the device).  Values outside
+ * [0, n_max] are CLAMPED to it; n_max itself must lie in [0, max_chunk_samples].  Needs the 400-point FFT front-end
+ * (KWS_ERR_UNSUPPORTED otherwise).  A call with n_max == 0 skips every stream: it reads and writes nothing but `hit`, and
+ * leaves the handle's mode (below) as it is.  Launches per call, whatever the lengths: the front-end with the per-stream gate, the GRU
+ * layers with seq_len = each stream's frames (copy-through past them), and window_inc_kernel over each stream's own frames --
+ * FOUR for the fp32 and f16x3 stacks, THREE for the bf16 stack (the window step cannot ride in the last GRU launch: those
+ * instantiations take no lengths).  kws_last_launch reports the GRU launches.
+ *
+ * Mode switch.  A handle starts in LOCK-STEP mode: one carried length for all streams (kws_stream_feed as described above).
+ * Its first kws_stream_feed_ragged or kws_stream_recycle moves it to PER-STREAM carry lengths (device array, no extra launch
+ * in the feed); from then on kws_stream_feed(n) runs the ragged iteration with every n_b = n (the same results as lock-step
+ * feeds would give).  kws_stream_reset returns it to lock-step mode with no carry.  Until a handle's first ragged feed or
+ * recycle, kws_stream_feed runs exactly its lock-step code. */
+int kws_stream_feed_ragged(kws_stream_handle h, const void* pcm /*[B,n_max] device*/, int n_max,
+                           const int32_t* n_per_stream /*[B] device*/, int pcm_int16, int32_t* hit /*[B] device*/, void* stream);
+/* Slot recycling: every stream b with slots[b] != 0 becomes what a freshly created manager's stream is -- carry length 0,
+ * window emptied, state rows [l][b][:] zeroed, restart[b] = 0 -- for a new client taking over the slot.  The other streams stay
+ * bitwise untouched.  One launch; switches the handle to per-stream carry lengths (above).  400-point FFT front-end only. */
+int kws_stream_recycle(kws_stream_handle h, const uint8_t* slots /*[B] device, non-zero = recycle*/, void* stream);
+/* The carried samples as they stand (detector.py:181-183's `res` of every stream), in either mode: stream b's
+ * lengths[b] <= fft_size - 1 samples at samples[b * (fft_size - 1) ...]; the rest of each row is unspecified.  Copies only (no
+ * kernel), ordered like a feed; changes nothing. */
+int kws_stream_carry(kws_stream_handle h, float* samples /*[B, fft_size - 1] device*/, int32_t* lengths /*[B] device*/, void* stream);
 
 /* OctbitMatMul: out[A,N] = (sum_k u8(x)[a,k] * Wq[n,k] - signed*bias[n]) * scale_w * s_x.
  *   x [A,K] f32, Wq [N,K] s8 (pre-transposed), bias [N] f32, out [A,N] f32.  K % 64 == 0, scale_w > 0.

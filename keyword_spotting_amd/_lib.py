@@ -83,6 +83,9 @@ _SIGNATURES = {
     "kws_stream_destroy": (_i, [_vp]),
     "kws_stream_reset": (_i, [_vp]),
     "kws_stream_feed": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
+    "kws_stream_feed_ragged": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp]),
+    "kws_stream_recycle": (_i, [_vp, _vp, _vp]),
+    "kws_stream_carry": (_i, [_vp, _vp, _vp, _vp]),
     "kws_octbit_matmul": (_i, [_vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _vp]),
     "kws_octbit_quantize": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
 }

@@ -220,12 +220,19 @@ struct kws_stream {
     float* state = nullptr;          // caller-owned [L,B,H]
     uint8_t* restart = nullptr;      // caller-owned [B]
     float* carry[2] = {nullptr, nullptr};   // [B, fft - 1] each: the carried samples ping-pong (the only device memory a manager owns)
+    // Carry layout.  Lock-step (ragged == false): every stream carries n_carry samples, rows of n_carry floats.  Ragged (from the
+    // first kws_stream_feed_ragged / kws_stream_recycle until kws_stream_reset): stream b carries carry_len[cur][b] samples, rows
+    // of fft - 1 floats; the lengths ping-pong with the samples.
+    bool ragged = false;
+    int32_t* carry_len[2] = {nullptr, nullptr};   // [B] each
     // one chunk's intermediates, carved out of the MODEL handle's staging block (kws_model::stage) at every feed:
     size_t off_pcm_f32 = 0;          // [B, max_chunk]  int16 input widened here (front-ends other than the 400-point FFT, sub-frame chunks)
     size_t off_mel = 0;              // [B, tmax, n_mel]
     size_t off_softmax = 0;          // [B, tmax, C]
     size_t off_silent = 0;           // [B]
     size_t off_reset = 0;            // [B]
+    size_t off_frames = 0;           // [B] int32  frames of each stream's chunk (ragged feed)
+    size_t off_skip = 0;             // [B]        empty chunk: iteration skipped (ragged feed)
     size_t stage_bytes = 0;
     // the pointers of the current feed
     float* pcm_f32 = nullptr;
@@ -233,6 +240,8 @@ struct kws_stream {
     float* softmax = nullptr;
     uint8_t* silent = nullptr;
     uint8_t* reset = nullptr;
+    int32_t* frames = nullptr;
+    uint8_t* skip = nullptr;
 };
 
 struct kws_frontend {

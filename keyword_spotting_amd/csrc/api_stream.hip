@@ -199,6 +199,96 @@ int stream_feed_locked(kws_stream_handle h, const void* pcm, int n, int pcm_int1
     return KWS_OK;
 }
 
+// One ragged iteration (kws_stream_feed_ragged; kws_stream_feed once the handle is ragged, lens == null: n_max for every stream),
+// with the model handle held and `st` ordered.  Three or four launches whatever the lengths: the FFT front-end with the per-stream
+// gate (vad, masks, next carry and its length, frame count, skip flag), the GRU layers over T = frames of n_max samples after a
+// full carry with seq_len = the per-stream frame counts (copy-through past them; a skipped stream has reset 0 and 0 frames: its
+// state comes back unchanged), and window_inc_kernel over each stream's own frames.  The window step cannot ride in the last GRU
+// launch here: the tail instantiations take no lengths.
+int stream_feed_ragged_locked(kws_stream_handle h, const void* pcm, int n_max, const int32_t* lens, int pcm_int16, int32_t* hit,
+                              hipStream_t st) {
+    const kws_frontend_config& fc = h->fe->cfg;
+    const int fft = fc.fft_size, B = h->B;
+    if (n_max == 0) {           // every stream's chunk is empty: every iteration is skipped (nothing is read or written,
+                                // the carry layout -- and so the handle's mode -- stays as it is; kws_amd.h)
+        KWS_HIP(hipMemsetAsync(hit, 0, (size_t)B * sizeof(int32_t), st));
+        return KWS_OK;
+    }
+    const int T = kws_frontend_frames(&fc, fft - 1 + n_max);
+    kws::FrontendParams p = {};
+    p.gate = 1; p.vad_thres = h->vad_thres; p.restart = h->restart; p.silent = h->silent; p.reset = h->reset;
+    if (pcm_int16) p.pcm_i16 = static_cast<const int16_t*>(pcm);
+    else p.pcm = static_cast<const float*>(pcm);
+    // lock-step layout on the first ragged call: rows of n_carry samples, one length for all; the output is in the ragged layout
+    p.carry = h->carry[h->cur]; p.next = h->carry[h->cur ^ 1]; p.n_next = fft - 1;
+    p.n_carry = h->ragged ? 0 : h->n_carry;
+    p.carry_stride = h->ragged ? fft - 1 : h->n_carry;
+    p.carry_len = h->ragged ? h->carry_len[h->cur] : nullptr;
+    p.next_len = h->carry_len[h->cur ^ 1];
+    p.lens = lens; p.n_max = n_max; p.frames = h->frames; p.skip = h->skip;
+    p.mel = h->mel; p.n_samples = p.n_carry + n_max;
+    p.dft = h->fe->d_tables + h->fe->fft_tw_off; p.melw = h->fe->d_tables + h->fe->fft_mel_off;
+    p.T = T; p.fft = fft; p.hop = fc.hop_size; p.n_mel = fc.n_mel;
+    p.nf_tiles = h->fe->nf_tiles; p.mel_tiles = h->fe->mel_tiles; p.kc4 = h->fe->kc4; p.B = B;
+    for (int m = 0; m < 4; ++m) { p.mel_lo[m] = h->fe->mel_lo[m]; p.mel_cnt[m] = h->fe->mel_cnt[m]; p.mel_off[m] = h->fe->mel_off[m]; }
+    hipError_t e = kws::launch_mel_fft400(p, B, st);
+    if (e != hipSuccess) return hip_fail(e, "launch mel_fft400 (ragged)");
+    h->ragged = true; h->n_carry = 0; h->cur ^= 1;          // the samples and lengths are in the other buffer now
+    StepArgs step;
+    step.mel = h->mel; step.softmax = h->softmax;
+    step.state_in = h->state; step.state_out = h->state; step.reset_mask = h->reset; step.seq_len = h->frames;
+    step.B = B; step.T = T; step.stream = st; step.locked = true;
+    int rc = step_impl(h->model, step);
+    if (rc != KWS_OK) return rc;
+    rc = window_bind_label(h->win, h->label);
+    if (rc != KWS_OK) return rc;
+    kws::WindowIncParams wp;
+    memset(&wp, 0, sizeof(wp));
+    wp.win = window_tail_params(h->win, h->silent, hit, h->restart);
+    memcpy(wp.delta, h->win->inc_delta, 256);
+    wp.softmax = h->softmax; wp.thres = h->win->thres; wp.B = B; wp.T = T; wp.C = h->win->C;
+    wp.frames = h->frames; wp.skip = h->skip;
+    e = kws::launch_window_inc(wp, st);
+    if (e != hipSuccess) return hip_fail(e, "launch window_inc (ragged)");
+    return KWS_OK;
+}
+
+// The checks every stream-handle call shares: the borrowed handles are alive; the per-stream paths need the FFT front-end.
+int stream_check(kws_stream_handle h, bool ragged_call) {
+    if (live_serial(h->model) != h->model_serial || live_serial(h->fe) != h->fe_serial || live_serial(h->win) != h->win_serial)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "the model, front-end or window this stream was created on has been destroyed");
+    if (ragged_call && !(h->fe->use_fft && h->fe->cfg.fft_size == 400))
+        return fail(KWS_ERR_UNSUPPORTED, "per-stream chunk lengths need the 400-point FFT front-end (fft_size=%d%s)", h->fe->cfg.fft_size,
+                    h->fe->cfg.fft_size == 400 ? ", KWS_FRONTEND_DENSE=1" : "");
+    if (ragged_call && (long long)h->B * h->tmax >= (1LL << 31))
+        return fail(KWS_ERR_UNSUPPORTED, "B*T=%lld frames exceed the ragged front-end's grid", (long long)h->B * h->tmax);
+    return KWS_OK;
+}
+
+// Runs `body` with the model handle held (its staging and seams are the handle's) and `stream` ordered behind the handle's
+// previous call when that ran on another stream; the chunk's staging pointers are set for it.
+template <typename F>
+int with_model_held(kws_stream_handle h, hipStream_t st, const char* what, F&& body) {
+    kws_model* model = h->model;
+    BusyGuard busy(model->in_call);
+    if (!busy.owned)
+        return fail(KWS_ERR_BUSY, "%s: another host thread is inside a call on the model handle (one thread at a time per "
+                    "handle; stream managers that run concurrently need a model handle each)", what);
+    if (h->stage_bytes > model->stage.bytes) return fail(KWS_ERR_INVALID_ARGUMENT, "internal: the model handle's staging block is smaller than this stream's");
+    int rc = call_enter(model, st);
+    if (rc != KWS_OK) return rc;
+    h->pcm_f32 = reinterpret_cast<float*>(model->stage.base + h->off_pcm_f32);
+    h->mel = reinterpret_cast<float*>(model->stage.base + h->off_mel);
+    h->softmax = reinterpret_cast<float*>(model->stage.base + h->off_softmax);
+    h->silent = reinterpret_cast<uint8_t*>(model->stage.base + h->off_silent);
+    h->reset = reinterpret_cast<uint8_t*>(model->stage.base + h->off_reset);
+    h->frames = reinterpret_cast<int32_t*>(model->stage.base + h->off_frames);
+    h->skip = reinterpret_cast<uint8_t*>(model->stage.base + h->off_skip);
+    rc = body();
+    const int rl = call_leave(model, st);
+    return rc != KWS_OK ? rc : rl;
+}
+
 }  // namespace
 
 extern "C" {
@@ -491,6 +581,8 @@ int kws_stream_create(kws_handle model, kws_frontend_handle frontend, kws_window
     const size_t carry_bytes = (size_t)B * (fft - 1) * sizeof(float);
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&s->carry[0]), carry_bytes);
     if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->carry[1]), carry_bytes);
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->carry_len[0]), (size_t)B * sizeof(int32_t));
+    if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&s->carry_len[1]), (size_t)B * sizeof(int32_t));
     if (e != hipSuccess) { kws_stream_destroy(s); return hip_fail(e, "hipMalloc(stream buffers)"); }
     // One chunk's intermediates come out of the model handle's staging block: sized here, so a feed never allocates.  The
     // widened copy of int16 PCM is read by the dense-DFT front-end only (the 400-point FFT reads int16 in place); with the
@@ -504,6 +596,8 @@ int kws_stream_create(kws_handle model, kws_frontend_handle frontend, kws_window
         s->off_softmax = take((size_t)B * tm * model->cfg.num_classes * sizeof(float));
         s->off_silent = take((size_t)B);
         s->off_reset = take((size_t)B);
+        s->off_frames = take((size_t)B * sizeof(int32_t));
+        s->off_skip = take((size_t)B);
     }
     int rc = KWS_OK;
     {
@@ -528,7 +622,7 @@ int kws_stream_create(kws_handle model, kws_frontend_handle frontend, kws_window
 int kws_stream_destroy(kws_stream_handle h) {
     if (!h) return KWS_OK;
     hipDeviceSynchronize();
-    for (float* p : {h->carry[0], h->carry[1]}) if (p) hipFree(p);
+    for (void* p : {(void*)h->carry[0], (void*)h->carry[1], (void*)h->carry_len[0], (void*)h->carry_len[1]}) if (p) hipFree(p);
     delete h;
     return KWS_OK;
 }
@@ -536,6 +630,7 @@ int kws_stream_destroy(kws_stream_handle h) {
 int kws_stream_reset(kws_stream_handle h) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
     h->n_carry = 0;
+    h->ragged = false;        // lock-step with no carry: the per-stream lengths are forgotten with the samples
     return KWS_OK;
 }
 
@@ -544,31 +639,74 @@ int kws_stream_feed(kws_stream_handle h, const void* pcm, int n, int pcm_int16, 
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
     if (n < 0 || n > h->max_chunk) return fail(KWS_ERR_INVALID_ARGUMENT, "chunk of %d samples outside [0,%d]", n, h->max_chunk);
     if (!hit || (!pcm && n > 0)) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
-    if (live_serial(h->model) != h->model_serial || live_serial(h->fe) != h->fe_serial || live_serial(h->win) != h->win_serial)
-        return fail(KWS_ERR_INVALID_ARGUMENT, "the model, front-end or window this stream was created on has been destroyed");
+    int rc = stream_check(h, false);
+    if (rc != KWS_OK) return rc;
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (n == 0) {            // detector.py:164-166: an empty read is skipped before anything else happens
         KWS_HIP(hipMemsetAsync(hit, 0, (size_t)h->B * sizeof(int32_t), st));
         return KWS_OK;
     }
-    // The feed holds the model handle from its first launch to its last (the staging and the seams are the handle's), and
-    // orders `stream` behind the handle's previous call when that ran on another stream.
-    kws_model* model = h->model;
-    BusyGuard busy(model->in_call);
-    if (!busy.owned)
-        return fail(KWS_ERR_BUSY, "kws_stream_feed: another host thread is inside a call on the model handle (one thread at a time per "
-                    "handle; stream managers that run concurrently need a model handle each)");
-    if (h->stage_bytes > model->stage.bytes) return fail(KWS_ERR_INVALID_ARGUMENT, "internal: the model handle's staging block is smaller than this stream's");
-    int rc = call_enter(model, st);
+    // a handle in the per-stream carry layout runs the ragged iteration with every stream's length n
+    if (h->ragged) return with_model_held(h, st, "kws_stream_feed", [&] { return stream_feed_ragged_locked(h, pcm, n, nullptr, pcm_int16, hit, st); });
+    return with_model_held(h, st, "kws_stream_feed", [&] { return stream_feed_locked(h, pcm, n, pcm_int16, hit, st); });
+}
+
+int kws_stream_feed_ragged(kws_stream_handle h, const void* pcm, int n_max, const int32_t* n_per_stream, int pcm_int16, int32_t* hit,
+                           void* stream) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    if (n_max < 0 || n_max > h->max_chunk) return fail(KWS_ERR_INVALID_ARGUMENT, "rows of %d samples outside [0,%d]", n_max, h->max_chunk);
+    if (!hit || !n_per_stream || (!pcm && n_max > 0)) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
+    int rc = stream_check(h, true);
     if (rc != KWS_OK) return rc;
-    h->pcm_f32 = reinterpret_cast<float*>(model->stage.base + h->off_pcm_f32);
-    h->mel = reinterpret_cast<float*>(model->stage.base + h->off_mel);
-    h->softmax = reinterpret_cast<float*>(model->stage.base + h->off_softmax);
-    h->silent = reinterpret_cast<uint8_t*>(model->stage.base + h->off_silent);
-    h->reset = reinterpret_cast<uint8_t*>(model->stage.base + h->off_reset);
-    rc = stream_feed_locked(h, pcm, n, pcm_int16, hit, st);
-    const int rl = call_leave(model, st);
-    return rc != KWS_OK ? rc : rl;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return with_model_held(h, st, "kws_stream_feed_ragged", [&] { return stream_feed_ragged_locked(h, pcm, n_max, n_per_stream, pcm_int16, hit, st); });
+}
+
+int kws_stream_recycle(kws_stream_handle h, const uint8_t* slots, void* stream) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    if (!slots) return fail(KWS_ERR_INVALID_ARGUMENT, "slots is null");
+    int rc = stream_check(h, true);
+    if (rc != KWS_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return with_model_held(h, st, "kws_stream_recycle", [&]() -> int {
+        const kws_config& c = h->model->cfg;
+        kws::StreamRecycleParams p;
+        memset(&p, 0, sizeof(p));
+        p.slots = slots; p.state = h->state; p.restart = h->restart; p.head = h->win->inc_head; p.count = h->win->inc_count;
+        p.L = c.num_layers; p.B = h->B; p.H = c.hidden;
+        if (h->ragged) {
+            p.len_out = h->carry_len[h->cur];                     // in place: only the recycled streams' lengths change
+        } else {
+            // leaves the lock-step layout: the other streams' carries move to rows of fft - 1 samples with their length
+            p.carry_in = h->carry[h->cur]; p.n_carry = h->n_carry;
+            p.carry_out = h->carry[h->cur ^ 1]; p.carry_out_stride = h->fe->cfg.fft_size - 1; p.len_out = h->carry_len[h->cur ^ 1];
+        }
+        hipError_t e = kws::launch_stream_recycle(p, st);
+        if (e != hipSuccess) return hip_fail(e, "launch stream_recycle");
+        if (!h->ragged) { h->ragged = true; h->n_carry = 0; h->cur ^= 1; }
+        return KWS_OK;
+    });
+}
+
+int kws_stream_carry(kws_stream_handle h, float* samples, int32_t* lengths, void* stream) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    if (!samples || !lengths) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
+    int rc = stream_check(h, false);
+    if (rc != KWS_OK) return rc;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    return with_model_held(h, st, "kws_stream_carry", [&]() -> int {
+        const size_t B = (size_t)h->B, row = (size_t)(h->fe->cfg.fft_size - 1) * sizeof(float);
+        if (h->ragged) {                       // already the layout handed out
+            KWS_HIP(hipMemcpyAsync(samples, h->carry[h->cur], B * row, hipMemcpyDeviceToDevice, st));
+            KWS_HIP(hipMemcpyAsync(lengths, h->carry_len[h->cur], B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        } else {                               // lock-step: rows of n_carry samples, one length for all
+            if (h->n_carry > 0)
+                KWS_HIP(hipMemcpy2DAsync(samples, row, h->carry[h->cur], (size_t)h->n_carry * sizeof(float), (size_t)h->n_carry * sizeof(float),
+                                         B, hipMemcpyDeviceToDevice, st));
+            KWS_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lengths), h->n_carry, B, st));
+        }
+        return KWS_OK;
+    });
 }
 
 }  // extern "C"

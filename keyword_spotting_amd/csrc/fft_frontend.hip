@@ -100,8 +100,51 @@ constexpr int kSpecRows = 208;                 // spectrum rows (bins 0..200 + z
 #ifndef KWS_FE_OCC
 #define KWS_FE_OCC 6          // workgroups per CU the register allocation aims at (tools/build_variant.sh -DKWS_FE_OCC=n for A/B)
 #endif
-template <int MT, typename SampleT, bool GATE>
+// RaggedRows<S> in place of the sample type S (with GATE; kws_stream_feed_ragged): every stream has its own chunk length
+// (p.lens) and carry length (p.carry_len, or p.n_carry for all); the grid is B x T frames for the longest possible chunk, and
+// frames past a stream's own count load nothing and store zeros.  See ragged_gate below for what the gate writes.  (A tag on
+// the sample type rather than a fourth template parameter: the lock-step instantiations keep their names and their code.)
+template <typename S> struct RaggedRows {};
+namespace {
+template <typename T> struct SampleOf { using type = T; static constexpr bool ragged = false; };
+template <typename S> struct SampleOf<RaggedRows<S>> { using type = S; static constexpr bool ragged = true; };
+
+__device__ __forceinline__ int ragged_len(const FrontendParams& p, unsigned b) {      // clamped to [0, n_max] (kws_amd.h)
+    const int n = p.lens ? p.lens[b] : p.n_max;
+    return n < 0 ? 0 : (n > p.n_max ? p.n_max : n);
+}
+__device__ __forceinline__ int ragged_carry(const FrontendParams& p, unsigned b) { return p.carry_len ? p.carry_len[b] : p.n_carry; }
+__device__ __forceinline__ int ragged_frames(const FrontendParams& p, int total) { return total < p.fft ? 0 : 1 + (total - p.fft) / p.hop; }
+
+// The gate of one stream of a ragged chunk (detector.py:162-183 for this stream alone): n == 0 skips the iteration -- carry
+// copied through, reset 0 (the GRU hands the state back over zero frames), skip set; otherwise the vad masks of its n new samples,
+// the next carry (all samples while fewer than 400, else what detector.py:181-182 keeps) and its frame count.
+template <typename SampleT>
+__device__ __forceinline__ void ragged_gate(const FrontendParams& p, unsigned b, float vad_sum, int n, int nc, const SampleT* row, int tid) {
+    const float* crow = p.carry + (size_t)b * p.carry_stride;
+    float* nrow = p.next + (size_t)b * (p.fft - 1);
+    const int total = nc + n;
+    const int keep = n == 0 || total < p.fft ? total : (total - p.fft) % p.hop + (p.fft - p.hop);
+    if (tid == 0) {
+        if (n > 0) {
+            vad_masks(vad_sum, p.vad_thres, b, p.restart, p.silent, p.reset);
+        } else {
+            p.silent[b] = 0;
+            p.reset[b] = 0;
+        }
+        p.skip[b] = n == 0 ? 1 : 0;
+        p.frames[b] = n == 0 ? 0 : ragged_frames(p, total);
+        p.next_len[b] = keep;
+    }
+    carry_tail<SampleT>(crow, nc, row, n, nrow, keep, tid, 256);
+}
+}  // namespace
+
+template <int MT, typename SampleTag, bool GATE>
 __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const FrontendParams p) {
+    using SampleT = typename SampleOf<SampleTag>::type;
+    constexpr bool RAGGED = SampleOf<SampleTag>::ragged;
+    static_assert(GATE || !RAGGED, "the ragged feed always carries the gate");
     __shared__ __attribute__((aligned(16))) char lds[kFftLds];
     const int tid = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -136,6 +179,7 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
     // workgroups in front of the transforms pulled each XCD's 7 MB of rows through its 4 MB L2 first: 94-100 MB; round 3: 140).
     __shared__ float gate_part[4];
     unsigned gate_b = 0xffffffffu;                      // workgroup-uniform: the stream handled the fast way
+    int gate_n = 0, gate_nc = 0;                        // RAGGED: its chunk and carry lengths
     float gate_v[4][4];
     if constexpr (GATE) {
         const unsigned T = (unsigned)p.T;
@@ -144,6 +188,37 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
         const bool fast = n_chunk <= 4096 && (n_chunk & 3) == 0 && ((size_t)n_chunk * sizeof(SampleT)) % (4 * sizeof(SampleT)) == 0 &&
                           (reinterpret_cast<uintptr_t>(chunk_all) & (4 * sizeof(SampleT) - 1)) == 0;
         for (unsigned sb = sb0; sb < (unsigned)p.B && sb * T < f_end; ++sb) {
+            if constexpr (RAGGED) {
+                // rows of n_max samples, of which the stream's own n count; lengths read once per workgroup (uniform)
+                const int n = __builtin_amdgcn_readfirstlane(ragged_len(p, sb)), nc = __builtin_amdgcn_readfirstlane(ragged_carry(p, sb));
+                const SampleT* row = chunk_all + (size_t)sb * p.n_max;
+                if (n == 0) {
+                    ragged_gate<SampleT>(p, sb, 0.f, 0, nc, row, tid);
+                } else if (sb == sb0 && n <= 4096 && (n & 3) == 0 && (reinterpret_cast<uintptr_t>(row) & (4 * sizeof(SampleT) - 1)) == 0) {
+                    gate_b = sb; gate_n = n; gate_nc = nc;
+                    const int full = n >> 2;
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const int i = tid + 256 * k;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) gate_v[k][e] = 0.f;
+                        if (i < full) {
+                            if constexpr (sizeof(SampleT) == 2) {
+                                const short4 q4 = reinterpret_cast<const short4*>(row)[i];
+                                gate_v[k][0] = (float)q4.x * kScale; gate_v[k][1] = (float)q4.y * kScale; gate_v[k][2] = (float)q4.z * kScale; gate_v[k][3] = (float)q4.w * kScale;
+                            } else {
+                                const float4 q4 = reinterpret_cast<const float4*>(row)[i];
+                                gate_v[k][0] = q4.x; gate_v[k][1] = q4.y; gate_v[k][2] = q4.z; gate_v[k][3] = q4.w;
+                            }
+                        }
+                    }
+                } else {
+                    const float tot = block_abs_sum<SampleT>(row, n, nullptr);
+                    ragged_gate<SampleT>(p, sb, tot, n, nc, row, tid);
+                    __syncthreads();
+                }
+                continue;
+            }
             const SampleT* row = chunk_all + (size_t)sb * n_chunk;
             if (fast && sb == sb0) {
                 gate_b = sb;
@@ -181,30 +256,54 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
         fidx = fidx < total ? fidx : total - 1;         // frames past the end redo the last one (finite values, never stored)
         const unsigned sb = fidx / (unsigned)p.T;
         const int st = (int)(fidx - sb * (unsigned)p.T);
-        // the signal of stream sb is carry[sb] (n_carry samples, may be 0) followed by pcm[sb] (detector.py:179)
-        const float* xc_ = p.carry + (size_t)sb * p.n_carry;
-        const SampleT* xp_ = chunk_all + (size_t)sb * n_chunk;
-        const int s0 = st * p.hop + n2;
         float x[25];
-        const bool seam = s0 - n2 < p.n_carry && s0 - n2 + 400 > p.n_carry;
-        const unsigned long long any_seam = __builtin_amdgcn_ballot_w64(seam);
-        const unsigned long long any_carry = __builtin_amdgcn_ballot_w64(s0 - n2 < p.n_carry);
-        if (!any_carry) {
-            // every frame of this wave lies in the new samples (all but the first rounds of a chunk)
-            const SampleT* src = xp_ + (s0 - p.n_carry);
+        if constexpr (RAGGED) {
+            const int s0 = st * p.hop + n2;
+            // stream sb: carry row (nc samples) followed by its n new samples; frames past its own count are dead: no loads, zeros
+            const int n = ragged_len(p, sb), nc = ragged_carry(p, sb);
+            const bool live = n > 0 && st < ragged_frames(p, nc + n);
+            const float* xc_ = p.carry + (size_t)sb * p.carry_stride;
+            const SampleT* xp_ = chunk_all + (size_t)sb * p.n_max;
+            const unsigned long long any_carry = __builtin_amdgcn_ballot_w64(live && s0 - n2 < nc);
+            if (!live) {
 #pragma unroll
-            for (int n1 = 0; n1 < 25; ++n1) x[n1] = (float)src[16 * n1] * kScale;
-        } else if (!any_seam && sizeof(SampleT) == 4) {
-            // whole frames, some in the carried samples, some in the new ones; one float array each
-            const float* src = s0 - n2 >= p.n_carry ? reinterpret_cast<const float*>(xp_) + (s0 - p.n_carry) : xc_ + s0;
+                for (int n1 = 0; n1 < 25; ++n1) x[n1] = 0.f;
+            } else if (!any_carry) {
+                const SampleT* src = xp_ + (s0 - nc);
 #pragma unroll
-            for (int n1 = 0; n1 < 25; ++n1) x[n1] = src[16 * n1];
+                for (int n1 = 0; n1 < 25; ++n1) x[n1] = (float)src[16 * n1] * kScale;
+            } else {
+#pragma unroll
+                for (int n1 = 0; n1 < 25; ++n1) {
+                    const int idx = s0 + 16 * n1;
+                    x[n1] = idx < nc ? xc_[idx] : (float)xp_[idx - nc] * kScale;
+                }
+            }
         } else {
-            // some frame of this wave straddles the seam (the first two or three frames of a chunk): per-sample select
+            // the signal of stream sb is carry[sb] (n_carry samples, may be 0) followed by pcm[sb] (detector.py:179)
+            const float* xc_ = p.carry + (size_t)sb * p.n_carry;
+            const SampleT* xp_ = chunk_all + (size_t)sb * n_chunk;
+            const int s0 = st * p.hop + n2;
+            const bool seam = s0 - n2 < p.n_carry && s0 - n2 + 400 > p.n_carry;
+            const unsigned long long any_seam = __builtin_amdgcn_ballot_w64(seam);
+            const unsigned long long any_carry = __builtin_amdgcn_ballot_w64(s0 - n2 < p.n_carry);
+            if (!any_carry) {
+                // every frame of this wave lies in the new samples (all but the first rounds of a chunk)
+                const SampleT* src = xp_ + (s0 - p.n_carry);
 #pragma unroll
-            for (int n1 = 0; n1 < 25; ++n1) {
-                const int idx = s0 + 16 * n1;
-                x[n1] = idx < p.n_carry ? xc_[idx] : (float)xp_[idx - p.n_carry] * kScale;
+                for (int n1 = 0; n1 < 25; ++n1) x[n1] = (float)src[16 * n1] * kScale;
+            } else if (!any_seam && sizeof(SampleT) == 4) {
+                // whole frames, some in the carried samples, some in the new ones; one float array each
+                const float* src = s0 - n2 >= p.n_carry ? reinterpret_cast<const float*>(xp_) + (s0 - p.n_carry) : xc_ + s0;
+#pragma unroll
+                for (int n1 = 0; n1 < 25; ++n1) x[n1] = src[16 * n1];
+            } else {
+                // some frame of this wave straddles the seam (the first two or three frames of a chunk): per-sample select
+#pragma unroll
+                for (int n1 = 0; n1 < 25; ++n1) {
+                    const int idx = s0 + 16 * n1;
+                    x[n1] = idx < p.n_carry ? xc_[idx] : (float)xp_[idx - p.n_carry] * kScale;
+                }
             }
         }
         // W400^{n2 k1}, k1 = 1..12, for this lane's n2 (cos, sin): [12][16] float2
@@ -266,9 +365,14 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
     __syncthreads();
     KWS_FE_STAMP(3);
     if (GATE && gate_b != 0xffffffffu) {
-        if (tid == 0) vad_masks((gate_part[0] + gate_part[1]) + (gate_part[2] + gate_part[3]), p.vad_thres, gate_b, p.restart, p.silent, p.reset);
-        carry_tail<SampleT>(p.carry + (size_t)gate_b * p.n_carry, p.n_carry, chunk_all + (size_t)gate_b * n_chunk, n_chunk,
-                            p.next + (size_t)gate_b * p.n_next, p.n_next, tid, 256);
+        if constexpr (RAGGED) {
+            ragged_gate<SampleT>(p, gate_b, (gate_part[0] + gate_part[1]) + (gate_part[2] + gate_part[3]), gate_n, gate_nc,
+                                 chunk_all + (size_t)gate_b * p.n_max, tid);
+        } else {
+            if (tid == 0) vad_masks((gate_part[0] + gate_part[1]) + (gate_part[2] + gate_part[3]), p.vad_thres, gate_b, p.restart, p.silent, p.reset);
+            carry_tail<SampleT>(p.carry + (size_t)gate_b * p.n_carry, p.n_carry, chunk_all + (size_t)gate_b * n_chunk, n_chunk,
+                                p.next + (size_t)gate_b * p.n_next, p.n_next, tid, 256);
+        }
     }
 
     // ---- stage 2: pass q = w, k1 = 4w + g ----
@@ -410,6 +514,10 @@ hipError_t launch_mel_fft400(const FrontendParams& p, int B, hipStream_t st) {
     const unsigned grid = (unsigned)(((total + 15) / 16 + 7) / 8 * 8);     // multiple of 8: the kernel's XCD-aware block map
     FrontendParams q = p;
     q.fft_blocks = (int)grid;
+    if (p.frames) {
+        if (!p.gate || p.fft != 400) return hipErrorInvalidValue;
+        return p.pcm_i16 ? launch_fft400_tiles<RaggedRows<int16_t>, true>(q, grid, st) : launch_fft400_tiles<RaggedRows<float>, true>(q, grid, st);
+    }
     if (!p.gate) return p.pcm_i16 ? launch_fft400_tiles<int16_t, false>(q, grid, st) : launch_fft400_tiles<float, false>(q, grid, st);
     return p.pcm_i16 ? launch_fft400_tiles<int16_t, true>(q, grid, st) : launch_fft400_tiles<float, true>(q, grid, st);
 }

@@ -253,9 +253,28 @@ struct WindowIncParams {
     const float* softmax;
     float thres;
     int B, T, C;
+    // ragged chunks (kws_stream_feed_ragged): stream b's chunk has frames[b] <= T frames (softmax rows keep the stride T);
+    // skip[b] != 0: no slot, no clear, hit 0, restart untouched.  frames == null: every stream has T frames.
+    const int32_t* frames;
+    const uint8_t* skip;
 };
 hipError_t launch_window_inc(const WindowIncParams& p, hipStream_t st);
 hipError_t launch_window_reset(int B, int* head, int* count, hipStream_t st);
+// kws_stream_recycle: the streams with slots[b] != 0 become fresh streams -- state rows [L][b][H] zero, restart 0, window empty
+// (head = count = 0), carry length 0.  carry_out != null: the handle leaves the lock-step carry layout ([B][n_carry] in carry_in)
+// in the same pass -- the other streams' carried samples are copied to rows of fft - 1 floats and len_out = n_carry.
+// carry_out == null: len_out is the per-stream length array in place (recycled streams only).
+struct StreamRecycleParams {
+    const uint8_t* slots;
+    float* state;
+    uint8_t* restart;
+    int *head, *count;
+    const float* carry_in;
+    float* carry_out;
+    int32_t* len_out;
+    int n_carry, carry_out_stride, L, B, H;
+};
+hipError_t launch_stream_recycle(const StreamRecycleParams& p, hipStream_t st);
 
 // PCM -> mel front-end (frontend_kernels.hip)
 struct FrontendParams {
@@ -280,6 +299,14 @@ struct FrontendParams {
     long long* timing;
 #endif
     int mel_lo[4], mel_cnt[4], mel_off[4];   // fft_frontend.hip: per mel tile, first 4-bin group, number of groups (multiple of 4), offset of its fragments in melw (in groups)
+    // fft_frontend.hip, the ragged stream-manager feed (frames != null; kws_stream_feed_ragged): every stream has its own
+    // chunk length and carry length.  T = frames of n_max new samples after a full carry; frames t >= frames[b] are dead.
+    const int32_t* lens;      // [B] new samples of stream b, clamped to [0, n_max]; null: n_max for every stream
+    const int32_t* carry_len; // [B] carried samples of stream b (rows of carry_stride floats); null: n_carry for every stream
+    int32_t* next_len;        // [B] out: samples carried into the next chunk (rows of next: fft - 1 floats)
+    int32_t* frames;          // [B] out: frames of stream b in this chunk
+    uint8_t* skip;            // [B] out: 1 = empty chunk, the iteration is skipped for this stream
+    int n_max, carry_stride;  // row stride of the new samples / of carry (floats)
 };
 hipError_t launch_mel_frontend(const FrontendParams& p, int B, hipStream_t st);
 // fft 400 only (fft_frontend.hip): p.dft = twiddles [12][16] (cos, sin), p.melw = basis fragments [tile][group of its run][64]

@@ -105,7 +105,10 @@ __global__ void __launch_bounds__(64) window_step_kernel(const WindowParams p) {
 // The incremental window as a launch of its own (kws_window_step_incremental; kws_stream_feed where the last GRU layer's
 // kernel has no window tail: generic / pipelined / int8 kernels, chunks of more than 64 frames, zero-frame chunks).  One
 // workgroup = 16 streams, as the tail inside the GRU kernels: the frame rule of ctc_decode2 (utils/prediction.py:67,74-75)
-// over the chunk's softmax rows, then window_tail.
+// over the chunk's softmax rows, then window_tail.  RAGGED (kws_stream_feed_ragged): stream b's chunk is its first
+// p.frames[b] rows (the rows keep the stride p.T), and a stream with p.skip[b] set skips the iteration (detector.py:164-166):
+// no slot, no clear, restart untouched, hit 0.
+template <bool RAGGED>
 __global__ void __launch_bounds__(256) window_inc_kernel(const WindowIncParams p) {
     extern __shared__ __attribute__((aligned(16))) char wlds[];
     const int stride = (p.T + 15) & ~15;
@@ -117,7 +120,8 @@ __global__ void __launch_bounds__(256) window_inc_kernel(const WindowIncParams p
     WindowTailRegs<4> req;
     window_tail_request<4>(p.win, p.B, b0, tid, req);       // in flight behind the frame rule below
     const int s = tid & 15, b = min(b0 + s, p.B - 1);
-    for (int t = tid >> 4; t < p.T; t += 16) {
+    const int Tb = RAGGED ? p.frames[b] : p.T;
+    for (int t = tid >> 4; t < Tb; t += 16) {
         const float* row = p.softmax + ((size_t)b * p.T + t) * C;
         float best = row[1];
         int arg = 0;
@@ -126,7 +130,34 @@ __global__ void __launch_bounds__(256) window_inc_kernel(const WindowIncParams p
         cw[s * stride + t] = (int8_t)(best > p.thres ? arg : -1);
     }
     __syncthreads();
-    window_tail<4>(p.win, p.B, b0, p.T, cw, stride, dl, scratch, tid, req);
+    if constexpr (RAGGED) {
+        const int bt = min(b0 + (tid >> 4), p.B - 1);          // window_tail's stream of this lane
+        const bool skipped = p.skip[bt] != 0;
+        window_tail<4>(p.win, p.B, b0, p.frames[bt], cw, stride, dl, scratch, tid, req, !skipped);
+        if (skipped && (tid & 15) == 0 && b0 + (tid >> 4) < p.B) p.win.hit[bt] = 0;
+    } else {
+        window_tail<4>(p.win, p.B, b0, p.T, cw, stride, dl, scratch, tid, req);
+    }
+}
+
+// kws_stream_recycle (StreamRecycleParams, kws_internal.h): one 64-lane workgroup per stream
+__global__ void __launch_bounds__(64) stream_recycle_kernel(const StreamRecycleParams p) {
+    const int b = blockIdx.x, t = threadIdx.x;
+    const bool rec = p.slots[b] != 0;
+    if (p.carry_out) {
+        if (!rec)
+            for (int j = t; j < p.n_carry; j += 64)
+                p.carry_out[(size_t)b * p.carry_out_stride + j] = p.carry_in[(size_t)b * p.n_carry + j];
+        if (t == 0) p.len_out[b] = rec ? 0 : p.n_carry;
+    } else if (rec && t == 0) {
+        p.len_out[b] = 0;
+    }
+    if (!rec) return;
+    for (int i = t; i < p.L * p.H; i += 64) {
+        const int l = i / p.H, k = i - l * p.H;
+        p.state[((size_t)l * p.B + b) * p.H + k] = 0.f;
+    }
+    if (t == 0) { p.head[b] = 0; p.count[b] = 0; p.restart[b] = 0; }
 }
 
 __global__ void window_reset_kernel(int B, int* head, int* count) {
@@ -141,12 +172,19 @@ hipError_t launch_window_step(const WindowParams& p, hipStream_t st) {
 hipError_t launch_window_inc(const WindowIncParams& p, hipStream_t st) {
     const int stride = (p.T + 15) & ~15;
     const size_t lds = (size_t)16 * (stride > 0 ? stride : 16) + 256 + window_tail_scratch_bytes(p.win.nq);
-    static LdsGrant granted;
+    static LdsGrant granted, granted_ragged;
     if (lds > 48 * 1024) {
-        const hipError_t e = grant_dynamic_lds(window_inc_kernel, granted, lds);
+        const hipError_t e = p.frames ? grant_dynamic_lds(window_inc_kernel<true>, granted_ragged, lds)
+                                      : grant_dynamic_lds(window_inc_kernel<false>, granted, lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(window_inc_kernel, dim3((p.B + 15) / 16), dim3(256), lds, st, p);
+    if (p.frames) hipLaunchKernelGGL(window_inc_kernel<true>, dim3((p.B + 15) / 16), dim3(256), lds, st, p);
+    else hipLaunchKernelGGL(window_inc_kernel<false>, dim3((p.B + 15) / 16), dim3(256), lds, st, p);
+    return hipGetLastError();
+}
+hipError_t launch_stream_recycle(const StreamRecycleParams& p, hipStream_t st) {
+    if (p.B < 1) return hipSuccess;
+    hipLaunchKernelGGL(stream_recycle_kernel, dim3(p.B), dim3(64), 0, st, p);
     return hipGetLastError();
 }
 hipError_t launch_window_reset(int B, int* head, int* count, hipStream_t st) {

@@ -102,14 +102,15 @@ __device__ __forceinline__ void window_tail_request(const WindowTail& W, int B, 
 // Called by the first 256 threads of the workgroup (more may call: they return at once), after window_tail_request.  Streams [b0, b0 + 16) of B; cw: LDS,
 // [16 streams][cw_stride] frame words of this chunk, stream-major (complete and visible: the caller has synchronised); dl:
 // window_tail_prepare's table; scratch: LDS, window_tail_scratch_bytes(W.nq) bytes the caller no longer needs; R: ring slots
-// per lane (16 R >= W.nq).  The caller synchronises before it reuses `scratch` or `cw`.
+// per lane (16 R >= W.nq).  The caller synchronises before it reuses `scratch` or `cw`.  T is read per lane (stream s of the lane:
+// chunks of different lengths may sit side by side); live = false: the lane's stream writes nothing (a skipped iteration).
 template <int R>
 __device__ __forceinline__ void window_tail(const WindowTail& W, int B, int b0, int T, const int8_t* cw, int cw_stride, const uint8_t* dl,
-                                            char* scratch, int tid, const WindowTailRegs<R>& g) {
+                                            char* scratch, int tid, const WindowTailRegs<R>& g, bool live = true) {
     if (tid >= 256) return;
     const int nq = W.nq, nl = W.n_label;
     const int s = tid >> 4, q = tid & 15;
-    const bool valid = b0 + s < B;
+    const bool valid = live && b0 + s < B;
     const int b = valid ? b0 + s : B - 1;
     uint8_t* ring = reinterpret_cast<uint8_t*>(scratch) + (size_t)s * (nq * 32 + 32);   // [nq][tab 16 | ftab 16] of this stream
     uint8_t* ntab = ring + nq * 32;                                  // [16] this chunk's tab

@@ -178,6 +178,30 @@ class HotwordDetector(object):
         return decode_batch(_lib.DECODE, accu, None, 3, 0.5, 0.2)    # :288
 
 
+def _stream_lengths(lengths, batch):
+    """feed_pcm's per-stream lengths -> a [batch] integer tensor (not yet on the device); rejects a wrong shape or dtype."""
+    t = lengths if isinstance(lengths, torch.Tensor) else torch.as_tensor(np.asarray(lengths))
+    if t.dtype == torch.bool or t.dtype.is_floating_point or t.dtype.is_complex:
+        raise _lib.InvalidArgumentError(-1, "lengths must be integers, got %s" % t.dtype)
+    if tuple(t.shape) != (batch,):
+        raise _lib.InvalidArgumentError(-1, "lengths must have shape [%d], got %s" % (batch, list(t.shape)))
+    return t
+
+
+def _recycle_mask(slots, batch):
+    """recycle's slots -> a [batch] uint8 mask: a bool / uint8 mask of that shape, or stream indices."""
+    if isinstance(slots, torch.Tensor) and slots.dtype in (torch.bool, torch.uint8):
+        if tuple(slots.shape) != (batch,):
+            raise _lib.InvalidArgumentError(-1, "a slot mask must have shape [%d], got %s" % (batch, list(slots.shape)))
+        return slots.to(torch.uint8)
+    idx = slots.reshape(-1).cpu().tolist() if isinstance(slots, torch.Tensor) else [int(i) for i in slots]
+    if any(i < 0 or i >= batch for i in idx):
+        raise _lib.InvalidArgumentError(-1, "slot indices must lie in [0, %d)" % batch)
+    mask = torch.zeros(batch, dtype=torch.uint8)
+    mask[idx] = 1
+    return mask
+
+
 class StreamManager(object):
     """The same loop with every per-stream decision on the device.  feed_pcm is ONE native call
     per chunk (kws_stream_feed: VAD gate -> front-end with sample carry -> GRU stack -> 15-chunk window with windowed
@@ -243,12 +267,13 @@ class StreamManager(object):
                                                              _lib.ptr(self.hit), _lib.ptr(self.restart), _lib.current_stream_ptr()))
         return self.hit
 
-    def feed_pcm(self, pcm_chunk, frontend):
+    def feed_pcm(self, pcm_chunk, frontend, lengths=None):
         """pcm_chunk [B, n]: float samples, or int16 PCM as the sound card delivers it (widened on the device as
         buf_to_float does, detector.py:74-79).  One native call per chunk (kws_stream_feed): VAD + reset masks, the
         front-end on [carried samples | chunk] (detector.py:179-183, never concatenated), the GRU stack on the carried
-        state, the window / decode / trigger step.  -> hit [B] int32 device tensor."""
-        import ctypes
+        state, the window / decode / trigger step.  lengths: None (every stream reads all n samples), or a [B] integer tensor /
+        sequence, host or device -- stream b reads the first lengths[b] samples of its row and skips its iteration when that is
+        0 (kws_stream_feed_ragged; values outside [0, n] are clamped).  -> hit [B] int32 device tensor."""
         chunk = torch.as_tensor(pcm_chunk)
         if chunk.dim() == 1:
             chunk = chunk.unsqueeze(0)
@@ -260,7 +285,52 @@ class StreamManager(object):
             is_i16, chunk = 0, chunk.to(torch.float32)
         else:
             raise _lib.InvalidArgumentError(-1, "expected float or int16 PCM, got %s" % chunk.dtype)
-        chunk = chunk.to(self.model.device).contiguous()
+        lens = None if lengths is None else _stream_lengths(lengths, self.batch)
+        dev = self.model.device
+        chunk = chunk.to(dev).contiguous()
+        stream = self._stream_on(frontend)
+        with torch.cuda.device(dev):
+            if lens is None:
+                _lib.check(self._lib.kws_stream_feed(stream, _lib.ptr(chunk), int(chunk.shape[1]), is_i16, _lib.ptr(self.hit),
+                                                     _lib.current_stream_ptr()))
+            else:
+                lens = lens.to(dev, torch.int32).contiguous()         # queued on the current stream, as the feed is
+                _lib.check(self._lib.kws_stream_feed_ragged(stream, _lib.ptr(chunk), int(chunk.shape[1]), _lib.ptr(lens), is_i16,
+                                                            _lib.ptr(self.hit), _lib.current_stream_ptr()))
+        return self.hit
+
+    def recycle(self, slots, frontend=None):
+        """A new client takes over the streams `slots` names ([B] bool / uint8 mask, or a sequence of stream indices): each
+        becomes what a fresh manager's stream is -- no carried samples, zero state, empty window, no restart pending
+        (kws_stream_recycle); the other streams are untouched.  The manager must have been fed PCM before, or `frontend` given."""
+        mask = _recycle_mask(slots, self.batch)
+        if frontend is not None:
+            stream = self._stream_on(frontend)
+        elif self._stream is not None:
+            stream = self._stream
+        else:
+            raise _lib.InvalidArgumentError(-1, "recycle needs the manager's PCM stream handle: feed_pcm first, or pass frontend")
+        dev = self.model.device
+        mask = mask.to(dev).contiguous()
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.kws_stream_recycle(stream, _lib.ptr(mask), _lib.current_stream_ptr()))
+        return self
+
+    def carry(self):
+        """-> (samples [B, fft_size - 1] float32, lengths [B] int32) device tensors: each stream's carried samples, the first
+        lengths[b] of its row (kws_stream_carry; the rest of a row is unspecified).  Needs a manager that was fed PCM."""
+        if self._stream is None:
+            raise _lib.InvalidArgumentError(-1, "no PCM has been fed to this manager: it carries nothing")
+        dev = self.model.device
+        samples = torch.empty(self.batch, self._stream_frontend.config.fft_size - 1, dtype=torch.float32, device=dev)
+        lengths = torch.empty(self.batch, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.kws_stream_carry(self._stream, _lib.ptr(samples), _lib.ptr(lengths), _lib.current_stream_ptr()))
+        return samples, lengths
+
+    def _stream_on(self, frontend):
+        """The native stream handle of this manager on `frontend` (created on first use, again after a front-end change)."""
+        import ctypes
         dev = self.model.device
         if not self.model._handle.value or not frontend._handle.value:
             raise _lib.InvalidArgumentError(-1, "the model or the front-end has been closed")
@@ -273,7 +343,4 @@ class StreamManager(object):
                                                        self.label, _lib.ptr(self.state), _lib.ptr(self.restart),
                                                        ctypes.byref(self._stream)))
             self._stream_frontend, self._stream_fe_handle = frontend, frontend._handle.value
-        with torch.cuda.device(dev):
-            _lib.check(self._lib.kws_stream_feed(self._stream, _lib.ptr(chunk), int(chunk.shape[1]), is_i16, _lib.ptr(self.hit),
-                                                 _lib.current_stream_ptr()))
-        return self.hit
+        return self._stream

@@ -54,13 +54,17 @@ class StreamServer(object):
         return k % len(self.models)
 
     # -- one period ----------------------------------------------------------------------------------------------------
-    def feed_period(self, chunk_of):
+    def feed_period(self, chunk_of, lengths_of=None):
         """Issues one chunk for every manager: chunk_of(k) -> [S, n] PCM (int16 or float, device resident) of manager k, called
-        with the manager's HIP stream current (a host-fed caller queues its upload and the wait for it there).  Asynchronous.
-        Returns the number of native calls issued."""
+        with the manager's HIP stream current (a host-fed caller queues its upload and the wait for it there).  lengths_of(k)
+        -> [S] samples each stream of manager k delivered this period (per-stream arrival, StreamManager.feed_pcm); None:
+        every stream delivered all n.  Asynchronous.  Returns the number of native calls issued."""
         for k, mgr in enumerate(self.managers):
             with torch.cuda.stream(self.streams[k % len(self.models)]):
-                mgr.feed_pcm(chunk_of(k), self.frontend)
+                if lengths_of is None:
+                    mgr.feed_pcm(chunk_of(k), self.frontend)
+                else:
+                    mgr.feed_pcm(chunk_of(k), self.frontend, lengths=lengths_of(k))
         return len(self.managers)
 
     def wait(self):
@@ -89,10 +93,10 @@ class StreamServer(object):
         self.models = []
 
 
-def run_paced(server, chunk_of, periods=40, period_s=0.225):
+def run_paced(server, chunk_of, periods=40, period_s=0.225, lengths_of=None):
     """Feeds `periods` periods in real time: period p is issued at t0 + p x period_s (never earlier: the audio does not exist
     yet) and must be complete -- every manager's decisions on the device -- by t0 + (p + 1) x period_s.  chunk_of(p, k) is manager
-    k's chunk of period p.  -> dict with the per-period compute times (issue start to completion), the deadline misses and the
+    k's chunk of period p; lengths_of(p, k), if given, its streams' per-stream lengths (StreamServer.feed_period).  -> dict with the per-period compute times (issue start to completion), the deadline misses and the
     lateness of the issue itself (a period that starts late because the one before overran)."""
     compute, late_start, misses = [], [], 0
     server.wait()
@@ -103,7 +107,10 @@ def run_paced(server, chunk_of, periods=40, period_s=0.225):
         if now < due:
             time.sleep(due - now)
         t_issue = time.perf_counter()
-        server.feed_period(lambda k: chunk_of(p, k))
+        if lengths_of is None:
+            server.feed_period(lambda k: chunk_of(p, k))
+        else:
+            server.feed_period(lambda k: chunk_of(p, k), lambda k: lengths_of(p, k))
         server.wait()
         t_done = time.perf_counter()
         compute.append(t_done - t_issue)
