@@ -110,14 +110,39 @@ size_t kws_weights_nbytes(const kws_config* cfg);
 /* Stages the weights on the current HIP device (re-tiled into MFMA fragment order) and returns a
  * handle.  `weights_blob` is HOST memory of kws_weights_nbytes(cfg) bytes. */
 int kws_create(const kws_config* cfg, const void* weights_blob, size_t nbytes, kws_handle* out);
+/* Cell wrappers of the reference's get_cell (models/rnn_ctc.py:179-199; config/rnn_config.py:78-79 use_residual /
+ * use_layer_norm, both off by default): every layer is ResidualWrapper(LayerNormalizer(GRUCell)), the residual on layers >= 1
+ * only (utils/custom_wrapper.py:95-158).  Each field is 0 or 1.
+ *   use_layer_norm  the layer's input x (width I_l; layer 0: the mel frame) is normalised per stream and frame before the cell:
+ *                   x^ = (x - mean(x)) / sqrt(var(x) + 1e-5) * ibeta + igamma, with the population variance around the mean.
+ *                   The reference's names are swapped (_ln(inputs, ibeta, igamma) binds to _ln(input, s, b)): ibeta is the
+ *                   SCALAR SCALE (shape [], TF initialises it to 0), igamma the PER-FEATURE SHIFT (shape [I_l], initialised to 1).
+ *   use_residual    the output of layer l >= 1 is 0.7071067811865475 (h' + x), x the layer's input before the layer norm; the
+ *                   next layer and the dense layer read that, the recurrent state (state_out, model/rnn_states:0) stays h'.
+ *                   Rows past seq_len still emit the zero row (logits = bfc) and keep the state.  No effect with num_layers = 1.
+ * kws_weights_nbytes_wrapped: the canonical blob, followed -- with use_layer_norm -- by each layer's ibeta (1 float) and igamma
+ * (I_l floats), in layer order; the residual adds nothing.  kws_create_wrapped takes that blob.  A NULL or all-zero `wrap` is
+ * kws_weights_nbytes / kws_create exactly.  Wrapped handles run the fp32 generic kernels only (KWS_FP32; any other precision:
+ * KWS_ERR_UNSUPPORTED): KWS_KERNEL_AUTO picks them, KWS_KERNEL_RESIDENT is refused (KWS_ERR_UNSUPPORTED), and a stream manager
+ * on such a handle runs its decode window as a launch of its own (window_inc_kernel) behind the GRU layers.  kws_selftest on a
+ * wrapped handle runs the random case only (the published TensorFlow constants are for the plain cell), with both wrappers in
+ * the host loop and random ibeta / igamma. */
+typedef struct kws_cell_wrappers {
+    int32_t use_layer_norm;
+    int32_t use_residual;
+} kws_cell_wrappers;
+size_t kws_sizeof_cell_wrappers(void);
+size_t kws_weights_nbytes_wrapped(const kws_config* cfg, const kws_cell_wrappers* wrap);   /* 0: invalid config or wrappers */
+int kws_create_wrapped(const kws_config* cfg, const kws_cell_wrappers* wrap, const void* weights_blob, size_t nbytes,
+                       kws_handle* out);
 /* Releases the handle and always returns KWS_OK (the handle is gone afterwards, whatever it reports: never retry).  An
  * error a finished asynchronous step had raised and nobody collected is left in kws_last_error(); call kws_poll_error
  * first to get it as a status.  Stream handles created on it (kws_stream_create) fail cleanly afterwards. */
 int kws_destroy(kws_handle h);
 
 /* Kernel family used by kws_step (fp32): AUTO picks the register-resident kernels when the shape allows
- * (hidden == 128 and n_mel in {32, 40, 48, 60, 64}), else the generic ones (hidden 64/128/256, any n_mel).
- * RESIDENT on an unsupported shape -> KWS_ERR_UNSUPPORTED.  Ignored by the bf16 stack. */
+ * (hidden == 128 and n_mel in {32, 40, 48, 60, 64}) and the handle has no cell wrappers, else the generic ones (hidden
+ * 64/128/256, any n_mel).  RESIDENT on an unsupported shape or a wrapped handle -> KWS_ERR_UNSUPPORTED.  Ignored by the bf16 stack. */
 int kws_set_kernel(kws_handle h, int kind);
 /* Pre-sizes the handle's scratch for calls of B streams x up to T frames: afterwards kws_step with this B and T' <= T
  * never allocates or synchronises, whichever launch layout it picks for that shape (sequential layers, layers overlapped
@@ -138,6 +163,8 @@ int kws_poll_error(kws_handle h);
  * family where the shape allows) against known answers the library carries itself: TensorFlow's published GRUCell /
  * MultiRNNCell unit-test constants (0.175991, 0.156736, 0.13248) embedded in the handle's shape, and 19 streams x 8
  * random frames against a plain double-precision host loop of the cell (models/rnn_ctc.py:179-185,228-243 semantics).
+ * On a handle with cell wrappers (kws_create_wrapped) the TensorFlow constants are skipped -- they hold for the plain cell
+ * only -- and the random case runs the wrapped kernels against the host loop with both wrappers, random ibeta and igamma.
  * Uses temporary handles and buffers, synchronises the device, a few milliseconds.  KWS_OK, or KWS_ERR_HIP with a
  * message naming the kernel, the deviation and kws_version().  With KWS_SELFTEST=1 in the environment every
  * kws_create runs it and fails the same way.  (There is still no CPU fallback: a failed self-test is an error.) */

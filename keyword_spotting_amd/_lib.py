@@ -28,6 +28,11 @@ class KwsFrontendConfig(ctypes.Structure):
                 ("n_mel", ctypes.c_int32), ("fmin", ctypes.c_float), ("fmax", ctypes.c_float)]
 
 
+class KwsCellWrappers(ctypes.Structure):
+    """kws_cell_wrappers: the reference's get_cell options (config/rnn_config.py:78-79), 0 or 1 each."""
+    _fields_ = [("use_layer_norm", ctypes.c_int32), ("use_residual", ctypes.c_int32)]
+
+
 class KwsError(RuntimeError):
     """Base of the errors the C ABI reports."""
 
@@ -56,6 +61,9 @@ _SIGNATURES = {
     "kws_sizeof_frontend_config": (ctypes.c_size_t, []),
     "kws_weights_nbytes": (ctypes.c_size_t, [ctypes.POINTER(KwsConfig)]),
     "kws_create": (_i, [ctypes.POINTER(KwsConfig), _vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
+    "kws_sizeof_cell_wrappers": (ctypes.c_size_t, []),
+    "kws_weights_nbytes_wrapped": (ctypes.c_size_t, [ctypes.POINTER(KwsConfig), ctypes.POINTER(KwsCellWrappers)]),
+    "kws_create_wrapped": (_i, [ctypes.POINTER(KwsConfig), ctypes.POINTER(KwsCellWrappers), _vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "kws_destroy": (_i, [_vp]),
     "kws_set_kernel": (_i, [_vp, _i]),
     "kws_reserve": (_i, [_vp, _i, _i]),
@@ -110,7 +118,8 @@ def load():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = res, args
         if lib.kws_sizeof_config() != ctypes.sizeof(KwsConfig) or \
-                lib.kws_sizeof_frontend_config() != ctypes.sizeof(KwsFrontendConfig):
+                lib.kws_sizeof_frontend_config() != ctypes.sizeof(KwsFrontendConfig) or \
+                lib.kws_sizeof_cell_wrappers() != ctypes.sizeof(KwsCellWrappers):
             raise ImportError("%s was built from a different include/kws_amd.h than this binding (struct sizes differ); "
                               "rebuild it" % LIB_PATH)
         _lib = lib

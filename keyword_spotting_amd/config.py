@@ -15,6 +15,8 @@ class Config(object):
         self.fmin = 300                                     # :64
         self.fmax = 8000                                    # :65
         self.num_layers = 2                                 # :76
+        self.use_residual = False                           # :78  ResidualWrapper on layers >= 1 (models/rnn_ctc.py:196-197)
+        self.use_layer_norm = False                         # :79  LayerNormalizer around every GRUCell (models/rnn_ctc.py:186-187)
         self.value_clip = -1.0                              # :80
         self.use_relu = False                               # :83
         self.hidden_size = 128                              # :84

@@ -57,6 +57,9 @@ struct BlobLayout {
     size_t wfc, bfc, total;
 };
 BlobLayout blob_layout(const kws_config& c);
+// ... and behind it, with the layer norm (kws_weights_nbytes_wrapped): per layer ibeta (1 float), igamma (I_l floats)
+struct WrapLayout { size_t ibeta[8], igamma[8], total; };
+WrapLayout wrap_layout(const kws_config& c, const kws_cell_wrappers& w);
 
 struct LayerDev {
     int in_dim;
@@ -83,10 +86,14 @@ struct PackedWeights {
     std::vector<OctLayer> oct;
     size_t oct_wfc = 0, oct_b127fc = 0;
     float oct_scale_fc = 0.f;
+    // cell wrappers (kws_create_wrapped, fp32 generic kernels): per layer the layer norm's igamma padded to the k-groups of the
+    // x-part (16 * kcx_gen / 4 floats, zero past I_l) and its ibeta
+    std::vector<size_t> ln_igamma;
+    std::vector<float> ln_ibeta;
 };
-// (config, canonical blob) -> the device image of every table the config's precision launches with, and where each one is.
-// KWS_OK, or the error code with kws_last_error() set.  Host code only.
-int pack_weights(const kws_config& cfg, const float* blob, PackedWeights* pk, std::vector<float>* image);
+// (config, canonical blob [+ the wrapper tables of wrap_layout]) -> the device image of every table the config's precision
+// launches with, and where each one is.  KWS_OK, or the error code with kws_last_error() set.  Host code only.
+int pack_weights(const kws_config& cfg, const kws_cell_wrappers& wrap, const float* blob, PackedWeights* pk, std::vector<float>* image);
 
 // The arguments of one kws_step (include/kws_amd.h), and what the stream manager adds to them
 struct StepArgs {
@@ -115,6 +122,8 @@ int call_leave(kws_handle h, hipStream_t st);
 
 struct kws_model {
     kws_config cfg;
+    kws_cell_wrappers wrap = {0, 0};
+    bool wrapped = false;            // a wrapper is on: the fp32 generic kernels' wrapped instantiations, never the resident ones
     int device = 0;
     int kernel_kind = KWS_KERNEL_AUTO;
     kws_host::PackedWeights pk;
@@ -168,7 +177,8 @@ struct kws_model {
     std::vector<int32_t> launches;
     // kernel the last kws_step launched per profiling slot, as a small tag: the name is only formatted when somebody asks
     // (kws_last_launch, kws_selftest) -- not on the launch path, where a 22-frame call is ~100 us of device time
-    enum LaunchFamily : uint8_t { kNone = 0, kBf16Stack, kF16x3, kPipelined, kOctbit, kOctbitFc, kResident, kGeneric, kF16x3Generic, kF16x3Pipelined };
+    enum LaunchFamily : uint8_t { kNone = 0, kBf16Stack, kF16x3, kPipelined, kOctbit, kOctbitFc, kResident, kGeneric, kF16x3Generic, kF16x3Pipelined,
+                                  kGenericWrapped, kPipelinedWrapped };
     struct LaunchTag { uint8_t family = kNone, kx = 0, first = 0, last = 0, window = 0; };
     LaunchTag launch_tag[8];
     std::string launch_name(int slot) const {
@@ -185,6 +195,8 @@ struct kws_model {
             case kOctbitFc: snprintf(nm, sizeof(nm), "gru_layer_octbit_kernel + octbit_fc_kernel"); break;
             case kResident: snprintf(nm, sizeof(nm), "gru_layer_resident<%d, %s, %s>", t.kx, t.first ? "true" : "false", t.last ? "true" : "false"); break;
             case kGeneric: snprintf(nm, sizeof(nm), "gru_layer_generic<%d, %s, %s>", t.kx, t.first ? "true" : "false", t.last ? "true" : "false"); break;
+            case kGenericWrapped: snprintf(nm, sizeof(nm), "gru_layer_generic<%d, %s, %s, wrapped>", t.kx, t.first ? "true" : "false", t.last ? "true" : "false"); break;
+            case kPipelinedWrapped: snprintf(nm, sizeof(nm), "gru_stack_generic_pipelined<%d, wrapped> (all %d layers, one launch)", t.kx, cfg.num_layers); break;
             default: break;
         }
         std::string out = t.family == kBf16Stack ? std::string(kws::gru_stack_bf16_kernel_name(pk.bf_kx0, cfg.num_layers)) : std::string(nm);

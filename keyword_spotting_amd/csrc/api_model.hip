@@ -72,6 +72,23 @@ static bool config_ok(const kws_config* c, int* code) {
     return true;
 }
 
+// wrap == null reads as all-zero.  Checked after the config (config_ok).
+static bool wrappers_ok(const kws_config* c, const kws_cell_wrappers* w, int* code) {
+    if (!w) return true;
+    const struct { const char* name; int32_t v; } opt[2] = {{"use_layer_norm", w->use_layer_norm}, {"use_residual", w->use_residual}};
+    for (const auto& o : opt)
+        if (o.v != 0 && o.v != 1) { *code = fail(KWS_ERR_INVALID_ARGUMENT, "cell wrapper %s=%d: must be 0 or 1", o.name, o.v); return false; }
+    static const char* const prec_name[] = {"fp32", "bf16", "int8", "f16x3"};
+    for (const auto& o : opt)
+        if (o.v && c->precision != KWS_FP32) {
+            *code = fail(KWS_ERR_UNSUPPORTED, "cell wrapper %s needs precision fp32 (the wrapped kernels are the fp32 generic ones); got %s",
+                         o.name, prec_name[c->precision]);
+            return false;
+        }
+    return true;
+}
+static kws_cell_wrappers wrappers_of(const kws_cell_wrappers* w) { return w ? *w : kws_cell_wrappers{0, 0}; }
+
 extern "C" {
 
 // Compiler provenance is part of the version string: the fp32 resident kernels rely on hand-placed hazard fences around
@@ -90,19 +107,24 @@ const char* kws_last_error(void) { return g_last_error.c_str(); }
 size_t kws_sizeof_config(void) { return sizeof(kws_config); }
 size_t kws_sizeof_frontend_config(void) { return sizeof(kws_frontend_config); }
 
-size_t kws_weights_nbytes(const kws_config* cfg) {
+size_t kws_sizeof_cell_wrappers(void) { return sizeof(kws_cell_wrappers); }
+
+size_t kws_weights_nbytes(const kws_config* cfg) { return kws_weights_nbytes_wrapped(cfg, nullptr); }
+
+size_t kws_weights_nbytes_wrapped(const kws_config* cfg, const kws_cell_wrappers* wrap) {
     int code;
-    if (!config_ok(cfg, &code)) return 0;
-    return blob_layout(*cfg).total * sizeof(float);
+    if (!config_ok(cfg, &code) || !wrappers_ok(cfg, wrap, &code)) return 0;
+    return wrap_layout(*cfg, wrappers_of(wrap)).total * sizeof(float);
 }
 
-int kws_create(const kws_config* cfg, const void* weights_blob, size_t nbytes, kws_handle* out) {
+int kws_create_wrapped(const kws_config* cfg, const kws_cell_wrappers* wrap, const void* weights_blob, size_t nbytes, kws_handle* out) {
     int code;
     if (!out) return fail(KWS_ERR_INVALID_ARGUMENT, "out handle pointer is null");
     *out = nullptr;
-    if (!config_ok(cfg, &code)) return code;
+    if (!config_ok(cfg, &code) || !wrappers_ok(cfg, wrap, &code)) return code;
     if (!weights_blob) return fail(KWS_ERR_INVALID_ARGUMENT, "weights_blob is null");
-    const size_t need = blob_layout(*cfg).total * sizeof(float);
+    const kws_cell_wrappers wr = wrappers_of(wrap);
+    const size_t need = wrap_layout(*cfg, wr).total * sizeof(float);
     if (nbytes != need)
         return fail(KWS_ERR_INVALID_ARGUMENT, "weights_blob has %zu bytes, config needs %zu", nbytes, need);
     int ndev = 0;
@@ -112,6 +134,8 @@ int kws_create(const kws_config* cfg, const void* weights_blob, size_t nbytes, k
     kws_model* m = new (std::nothrow) kws_model();
     if (!m) return fail(KWS_ERR_OUT_OF_MEMORY, "host allocation failed");
     m->cfg = *cfg;
+    m->wrap = wr;
+    m->wrapped = wr.use_layer_norm || wr.use_residual;
     {
         const hipError_t e = hipGetDevice(&m->device);
         if (e != hipSuccess) { delete m; return hip_fail(e, "hipGetDevice"); }
@@ -122,7 +146,7 @@ int kws_create(const kws_config* cfg, const void* weights_blob, size_t nbytes, k
     }
     std::vector<float> host;
     {
-        const int rc = pack_weights(*cfg, static_cast<const float*>(weights_blob), &m->pk, &host);
+        const int rc = pack_weights(*cfg, wr, static_cast<const float*>(weights_blob), &m->pk, &host);
         if (rc != KWS_OK) { delete m; return rc; }
     }
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->d_weights), host.size() * sizeof(float));
@@ -155,6 +179,10 @@ int kws_create(const kws_config* cfg, const void* weights_blob, size_t nbytes, k
     return KWS_OK;
 }
 
+int kws_create(const kws_config* cfg, const void* weights_blob, size_t nbytes, kws_handle* out) {
+    return kws_create_wrapped(cfg, nullptr, weights_blob, nbytes, out);
+}
+
 int kws_destroy(kws_handle h) {
     if (!h) return KWS_OK;
     live_unregister(h);
@@ -184,6 +212,9 @@ int kws_set_kernel(kws_handle h, int kind) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
     if (kind != KWS_KERNEL_AUTO && kind != KWS_KERNEL_GENERIC && kind != KWS_KERNEL_RESIDENT)
         return fail(KWS_ERR_INVALID_ARGUMENT, "unknown kernel kind %d", kind);
+    if (kind == KWS_KERNEL_RESIDENT && h->wrapped)
+        return fail(KWS_ERR_UNSUPPORTED, "resident kernels have no cell wrappers (use_layer_norm=%d use_residual=%d): a wrapped handle runs "
+                    "the generic kernels", h->wrap.use_layer_norm, h->wrap.use_residual);
     if (kind == KWS_KERNEL_RESIDENT)
         for (const auto& L : h->pk.layers)
             if (!L.resident_ok)

@@ -7,6 +7,7 @@ using namespace kws_host;
 namespace {
 
 bool is_resident(const kws_model* h, const LayerDev& Ld) {
+    if (h->wrapped) return false;                  // the cell wrappers exist in the generic kernels only (kws_set_kernel refuses RESIDENT)
     return h->kernel_kind == KWS_KERNEL_RESIDENT || (h->kernel_kind == KWS_KERNEL_AUTO && Ld.resident_ok);
 }
 
@@ -16,11 +17,14 @@ bool pipeline_eligible(kws_handle h, int B) {
     // AUTO keeps the resident kernels where they exist even when this launch would be faster (H=128, L=2: +10 % at
     // B <= 2048; L=4, B=1024: 2.2x; select it with KWS_KERNEL_GENERIC): the two kernel families round differently in
     // the last bit, and a stream's result must not depend on how many neighbours it is batched or sharded with.
-    if (h->pipe_disabled) return false;
+    // KWS_NO_PIPELINE=1: never this launch -- what a device without fine-grained memory gets (pipe_disabled), for A/B runs
+    // and for the tests of the layouts that take its place (tests/test_gpu_wrapped.py)
+    static const bool no_pipe = [] { const char* e = getenv("KWS_NO_PIPELINE"); return e && e[0] == '1'; }();
+    if (h->pipe_disabled || no_pipe) return false;
     const bool f16_streaming = h->cfg.precision == KWS_F16X3 && h->pk.f16_generic;      // gru_stack_f16x3_pipelined
     if ((h->cfg.precision != KWS_FP32 && !f16_streaming) || h->cfg.num_layers < 2 || h->kernel_kind == KWS_KERNEL_RESIDENT) return false;
     for (const auto& L : h->pk.layers)
-        if (h->kernel_kind == KWS_KERNEL_AUTO && L.resident_ok) return false;
+        if (is_resident(h, L)) return false;
     const long long groups = (B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup;
     return h->num_cus > 0 && groups * h->cfg.num_layers <= h->num_cus;
 }
@@ -224,6 +228,22 @@ void set_fp32_layer(kws::GruLayerParams& p, const kws_model* h, const StepArgs& 
     p.KCX = resident ? Ld.kcx_res : Ld.kcx_gen;
 }
 
+// ... and its cell wrappers (wrapped handles)
+kws::GruWrapLayer wrap_layer(const kws_model* h, int l) {
+    kws::GruWrapLayer w = {nullptr, 0.f, 0};
+    if (h->wrap.use_layer_norm) { w.igamma = h->d_weights + h->pk.ln_igamma[l]; w.ibeta = h->pk.ln_ibeta[l]; }
+    w.residual = h->wrap.use_residual && l > 0;
+    return w;
+}
+// the generic launch of one layer, plain or wrapped; its kernel as a launch tag
+hipError_t launch_generic(const kws_model* h, const kws::GruLayerParams& p, int l, bool first, bool last, hipStream_t st) {
+    return h->wrapped ? kws::launch_gru_layer_generic_wrapped(p, wrap_layer(h, l), h->cfg.hidden, first, last, st)
+                      : kws::launch_gru_layer_generic(p, h->cfg.hidden, first, last, st);
+}
+kws_model::LaunchTag generic_tag(const kws_model* h, bool first, bool last) {
+    return {(uint8_t)(h->wrapped ? kws_model::kGenericWrapped : kws_model::kGeneric), (uint8_t)(h->cfg.hidden / 64), first, last, 0};
+}
+
 // Layers on separate HIP streams, time-blocked.  When L x groups workgroups fit the chip at once, the layers of a
 // long call need not run one after another: the call is cut into time blocks, layer l works on block k while layer
 // l-1 already works on block k+1 (its own stream, ordered by events; seam buffers double-buffered per block parity).
@@ -266,10 +286,9 @@ int step_overlapped(kws_handle h, const StepArgs& a) {
             p.h_out = last ? nullptr : h->scratch[2 * l + (k & 1)];
             if (k > 0) { p.state_in = a.state_out + (size_t)l * B * H; p.reset = nullptr; }    // the block before left the state there
             set_epilogue(p, a, c, last, t0, tk);
-            hipError_t e = resident ? kws::launch_gru_layer_resident(p, first, last, sx)
-                                    : kws::launch_gru_layer_generic(p, H, first, last, sx);
+            hipError_t e = resident ? kws::launch_gru_layer_resident(p, first, last, sx) : launch_generic(h, p, l, first, last, sx);
             if (e != hipSuccess) return hip_fail(e, "launch (overlapped layers)");
-            if (k == 0) h->launch_tag[l] = {(uint8_t)(resident ? kws_model::kResident : kws_model::kGeneric), (uint8_t)(resident ? p.KCX : H / 64), first, last, 0};
+            if (k == 0) h->launch_tag[l] = resident ? kws_model::LaunchTag{kws_model::kResident, (uint8_t)p.KCX, first, last, 0} : generic_tag(h, first, last);
             KWS_HIP(hipEventRecord(done(l, k), sx));
         }
     }
@@ -433,7 +452,14 @@ int step_body(kws_handle h, const StepArgs& a) {
         if (rc != KWS_OK) return rc;
         hipError_t e;
         if (pipelined) {
-            e = kws::launch_gru_stack_generic_pipelined(sp, H, st);       // timed as the last layer's slot
+            if (h->wrapped) {
+                kws::GruWrapParams wp;
+                memset(&wp, 0, sizeof(wp));
+                for (int k = 0; k < L; ++k) wp.layer[k] = wrap_layer(h, k);
+                e = kws::launch_gru_stack_generic_pipelined_wrapped(sp, wp, H, st);
+            } else {
+                e = kws::launch_gru_stack_generic_pipelined(sp, H, st);   // timed as the last layer's slot
+            }
             if (e != hipSuccess) return hip_fail(e, "launch gru_stack_generic_pipelined");
         } else if (int8 && h->pk.oct[l].quantised) {
             const PackedWeights::OctLayer& O = h->pk.oct[l];
@@ -451,16 +477,15 @@ int step_body(kws_handle h, const StepArgs& a) {
             e = kws::launch_gru_layer_octbit(op, st);
             if (e != hipSuccess) return hip_fail(e, "launch gru_layer_octbit");
         } else {
-            e = resident ? kws::launch_gru_layer_resident(p, first, last, st)
-                         : kws::launch_gru_layer_generic(p, H, first, last, st);
+            e = resident ? kws::launch_gru_layer_resident(p, first, last, st) : launch_generic(h, p, l, first, last, st);
             if (e != hipSuccess) return hip_fail(e, resident ? "launch gru_layer_resident" : "launch gru_layer_generic");
         }
         if (pipelined) {
-            h->launch_tag[l] = {kws_model::kPipelined, (uint8_t)(H / 64), 0, 0};
+            h->launch_tag[l] = {(uint8_t)(h->wrapped ? kws_model::kPipelinedWrapped : kws_model::kPipelined), (uint8_t)(H / 64), 0, 0};
             for (int k = 0; k < l; ++k) h->launch_tag[k] = {};
         } else if (int8 && h->pk.oct[l].quantised) h->launch_tag[l] = {(uint8_t)(l == L - 1 ? kws_model::kOctbitFc : kws_model::kOctbit), 0, 0, 0};
         else if (resident) h->launch_tag[l] = {kws_model::kResident, (uint8_t)p.KCX, first, last, (uint8_t)(a.wt != nullptr && last)};
-        else h->launch_tag[l] = {kws_model::kGeneric, (uint8_t)(H / 64), first, last};
+        else h->launch_tag[l] = generic_tag(h, first, last);
         if (int8 && l == L - 1) {
             kws::OctbitFcParams fp;
             memset(&fp, 0, sizeof(fp));

@@ -452,9 +452,21 @@ gru_layer_resident(const GruLayerParams p) {
 // ------------------------------------------------------------------------------------------------
 // Generic kernel: H = 64*TPW, weights streamed from L2 every frame (group-of-4 fragment layout).
 // Same orientation, exchange layout and epilogue; no software pipeline.
+//
+// WRAP (the wrapped instantiations only; every other one compiles exactly as without it): the cell wrappers of GruWrapLayer.
+//   * layer norm: at the top of each frame the layer's input block is staged in LDS, its mean and then the variance around it
+//     are reduced per stream (lane (g, s) holds features 16 k4 + 4g + e of stream s: the four lanes s, s+16, s+32, s+48 span
+//     the vector), and each wave writes its share of the normalised operand (x - mu) * rsqrt(var + 1e-5) * ibeta + igamma
+//     next to it; the existing x-part MFMAs read that.  Padding features (k >= I) stay out of the statistics and feed 0.
+//   * residual: the seam keeps the xl layout, so output tile n of this layer is the register image of the input k-group n of
+//     the same frame: 0.7071 (h' + x) is lane-local.  It goes to the seam / the dense layer; hreg, hbuf and state_out keep h'.
 // ------------------------------------------------------------------------------------------------
-template <int TPW, bool FIRST, bool LAST, bool PIPE>
-__device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, const int group) {
+constexpr float kResidualScale = 0.7071067811865475f;     // utils/custom_wrapper.py:116
+constexpr float kLayerNormEps = 1e-5f;                    // utils/custom_wrapper.py:126
+
+template <int TPW, bool FIRST, bool LAST, bool PIPE, bool WRAP = false>
+__device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, const int group,
+                                                       const GruWrapLayer& wl = GruWrapLayer{nullptr, 0.f, 0}) {
     constexpr int NT = 4 * TPW, H = 64 * TPW;
     const int tid = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -471,6 +483,12 @@ __device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, 
     f32x4* xstage = rhbuf + NT * 64;                                                     // pipelined launch only
     f32x4* biasl = xstage + NT * 64;                                                      // [3][NT][4 g] bias fragments
     const EpilogueLds epi = epilogue_carve(reinterpret_cast<char*>(biasl + 3 * NT * 4));  // LAST only
+    // WRAP: [KCX/4][64] float4, the normalised frame (first layer: staged and normalised in place); the raw input of an upper
+    // layer is staged in xstage.  Behind the epilogue area whether or not this layer is the last (gru_wrapped_extra_lds).
+    f32x4* const xln = WRAP ? reinterpret_cast<f32x4*>(reinterpret_cast<char*>(biasl + 3 * NT * 4) + kEpilogueLdsBytes) : nullptr;
+    const bool w_ln = WRAP && wl.igamma != nullptr;
+    const bool w_res = WRAP && !FIRST && wl.residual != 0;
+    const bool w_staged = w_ln || w_res;                  // the x operand comes from LDS
 
     // The weight stream (and the seam of a layer-by-layer launch) goes through BUFFER loads: lane offset in one VGPR that
     // never changes, everything else in the scalar offset.  With flat global loads every fragment fetched per frame cost
@@ -521,7 +539,9 @@ __device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, 
     // were waited for right before their MFMAs and the kernel ran latency-bound at half the MFMA rate.
     auto x_operand = [&](int t, int k4) -> f32x4 {
         f32x4 xb;
-        if (FIRST) {
+        if (WRAP && w_staged) {
+            xb = (w_ln ? xln : xstage)[k4 * 64 + lane];     // WRAP: staged at the top of the frame (wrap_frame)
+        } else if (FIRST) {
             const int k = 16 * k4 + 4 * g;
             const float* src = xrow + (size_t)t * I + k;
             if (vec_ok && k + 3 < I) {
@@ -567,6 +587,86 @@ __device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, 
         for (int j = 0; j < RT; ++j) r.a[j] = bload(wh_rsrc, ((TPW * w + part * RT + j) * 3 + 2) * NT + kk);
         __builtin_amdgcn_sched_barrier(0);
     };
+    // WRAP: frame t's input block to LDS and, under layer norm, the normalised operand beside it (see the header above)
+    auto mel_operand = [&](int t, int k4) -> f32x4 {     // the first layer's x operand as x_operand reads it (zero past I)
+        f32x4 xb;
+        const int k = 16 * k4 + 4 * g;
+        const float* src = xrow + (size_t)t * I + k;
+        if (vec_ok && k + 3 < I) {
+            xb = ld4(src);
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) xb[e] = (k + e < I) ? src[e] : 0.f;
+        }
+        return xb;
+    };
+    auto wrap_frame = [&](int t) {
+        f32x4* const raw = FIRST ? xln : xstage;
+        if (FIRST) {
+            // wave w stages k-groups w, w + 4, ...: up to four loads in flight ahead of their LDS stores
+            for (int k0 = w; k0 < KCX4; k0 += 16) {
+                f32x4 v[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) if (k0 + 4 * i < KCX4) v[i] = mel_operand(t, k0 + 4 * i);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) if (k0 + 4 * i < KCX4) raw[(k0 + 4 * i) * 64 + lane] = v[i];
+            }
+            __syncthreads();
+        } else if (!PIPE) {                              // the layer-pipelined launch staged it above
+            f32x4 v[NT / 4];
+#pragma unroll
+            for (int i = 0; i < NT / 4; ++i) v[i] = bload(xp_rsrc, t * NT + w + 4 * i);
+#pragma unroll
+            for (int i = 0; i < NT / 4; ++i) raw[(w + 4 * i) * 64 + lane] = v[i];
+            __syncthreads();
+        }
+        if (!w_ln) return;
+        // tf.nn.moments: the mean, then the population variance around it (not E[x^2] - mu^2: mel magnitudes carry a large DC
+        // part) -- per lane over its features, then over the stream's four lanes.  Every wave reduces the whole block in the
+        // same order, and the xor exchanges add the same two values on both lanes: every lane of a stream has the same bits.
+        float sum = 0.f;
+        for (int k4 = 0; k4 < KCX4; ++k4) {
+            const f32x4 v = raw[k4 * 64 + lane];
+            sum += (v[0] + v[1]) + (v[2] + v[3]);
+        }
+        sum += __shfl_xor(sum, 16);
+        sum += __shfl_xor(sum, 32);
+        const float mu = sum / (float)I;
+        float sq = 0.f;
+        for (int k4 = 0; k4 < KCX4; ++k4) {
+            const f32x4 v = raw[k4 * 64 + lane];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float d = v[e] - mu;
+                if (FIRST) d = (16 * k4 + 4 * g + e < I) ? d : 0.f;       // padding features
+                sq = fmaf(d, d, sq);
+            }
+        }
+        sq += __shfl_xor(sq, 16);
+        sq += __shfl_xor(sq, 32);
+        const float scale = wl.ibeta * rsqrtf(sq / (float)I + kLayerNormEps);
+        if (FIRST) __syncthreads();                      // normalised in place: every wave is done reading the raw block
+        for (int k0 = w; k0 < KCX4; k0 += 16) {
+            f32x4 gm[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) if (k0 + 4 * i < KCX4) gm[i] = ld4(wl.igamma + 16 * (k0 + 4 * i) + 4 * g);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int k4 = k0 + 4 * i;
+                if (k4 < KCX4) {
+                    const f32x4 v = raw[k4 * 64 + lane];
+                    f32x4 o;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        o[e] = fmaf(v[e] - mu, scale, gm[i][e]);
+                        if (FIRST) o[e] = (16 * k4 + 4 * g + e < I) ? o[e] : 0.f;   // padding feeds exactly 0
+                    }
+                    xln[k4 * 64 + lane] = o;
+                }
+            }
+        }
+        __syncthreads();
+    };
     for (int t = 0; t < T; ++t) {
         f32x4 acc_r[TPW], acc_u[TPW], acc_c[TPW];
 #pragma unroll
@@ -599,6 +699,9 @@ __device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, 
 #pragma unroll
             for (int i = 0; i < NT / 4; ++i) xstage[(w + 4 * i) * 64 + lane] = xv[i];
             __syncthreads();
+        }
+        if constexpr (WRAP) {
+            if (w_staged) wrap_frame(t);
         }
         // x-part (gates and candidate): rows q = k4 * NP + part, ping-pong, unrolled by two (NP == 2 keeps the parity
         // of q equal to the part, NP == 1 has a single part)
@@ -684,6 +787,8 @@ __device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, 
         for (int j = 0; j < TPW; ++j) {
             const int n = TPW * w + j;
             f32x4 hout;
+            f32x4 xr = splat4(0.f), seam = splat4(0.f);     // WRAP: this tile's input (raw, frame t) and the layer's output
+            if (WRAP && w_res) xr = xstage[n * 64 + lane];
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const float c = tanh_f(acc_c[j][e]);
@@ -692,10 +797,15 @@ __device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, 
                 const float hn = fmaf(u[j][e], hreg[j][e], (1.0f - u[j][e]) * c);
                 hreg[j][e] = bitsel(live, hn, hreg[j][e]);
                 hout[e] = bitsel(live, hn, 0.f);
+                if (WRAP) {
+                    const float o = w_res ? kResidualScale * (hn + xr[e]) : hn;     // utils/custom_wrapper.py:116
+                    hout[e] = bitsel(live, o, 0.f);
+                    seam[e] = bitsel(live, o, hreg[j][e]);
+                }
             }
             hbuf[n * 64 + lane] = hreg[j];
             if (!LAST) {
-                const f32x4 o = hreg[j];
+                const f32x4 o = WRAP ? seam : hreg[j];
                 float4* dst = p.h_out + ((size_t)group * T + t) * NT * 64 + n * 64 + lane;
                 if (PIPE) {
                     typedef int i32x4 __attribute__((ext_vector_type(4)));
@@ -767,6 +877,29 @@ __global__ void __launch_bounds__(256) gru_stack_generic_pipelined(const GruStac
     else if (layer == sp.L - 1) gru_layer_generic_body<TPW, false, true, true>(sp.layer[layer], group);
     else gru_layer_generic_body<TPW, false, false, true>(sp.layer[layer], group);
 }
+
+// The wrapped instantiations (GruWrapLayer): the same launches with the cell wrappers of a second kernel argument.
+template <int TPW, bool FIRST, bool LAST>
+__global__ void __launch_bounds__(256) gru_layer_generic_wrapped(const GruLayerParams p, const GruWrapLayer wl) {
+    gru_layer_generic_body<TPW, FIRST, LAST, false, true>(p, blockIdx.x, wl);
+}
+template <int TPW>
+__global__ void __launch_bounds__(256) gru_stack_generic_pipelined_wrapped(const GruStackParams sp, const GruWrapParams wp) {
+    int layer, group;                           // block -> (layer, group) as gru_stack_generic_pipelined
+    if (sp.xcd_affine) {
+        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per = 8 / sp.L;
+        layer = xcd % sp.L;
+        group = slot * per + xcd / sp.L;
+        if (group >= sp.G) return;
+    } else {
+        layer = blockIdx.x / sp.G;
+        group = blockIdx.x - layer * sp.G;
+    }
+    if (layer == 0) gru_layer_generic_body<TPW, true, false, true, true>(sp.layer[0], group, wp.layer[0]);
+    else if (layer == sp.L - 1) gru_layer_generic_body<TPW, false, true, true, true>(sp.layer[layer], group, wp.layer[layer]);
+    else gru_layer_generic_body<TPW, false, false, true, true>(sp.layer[layer], group, wp.layer[layer]);
+}
+static_assert(sizeof(GruStackParams) + sizeof(GruWrapParams) <= 4096, "kernel arguments");
 
 // ------------------------------------------------------------------------------------------------
 // launchers
@@ -897,6 +1030,61 @@ hipError_t launch_gru_layer_generic(const GruLayerParams& p, int hidden, bool fi
     if (hidden == 128) KWS_GEN(2);
     if (hidden == 256) KWS_GEN(4);
 #undef KWS_GEN
+    return hipErrorInvalidValue;
+}
+
+template <typename K>
+static hipError_t launch_wrapped_with_lds(K kernel, const GruLayerParams& p, const GruWrapLayer& wl, size_t lds, hipStream_t st) {
+    static LdsGrant granted;
+    {
+        const hipError_t e = grant_dynamic_lds(kernel, granted, lds);
+        if (e != hipSuccess) return e;
+    }
+    const int groups = (p.B + kStreamsPerGroup - 1) / kStreamsPerGroup;
+    hipLaunchKernelGGL(kernel, dim3(groups), dim3(256), lds, st, p, wl);
+    return hipGetLastError();
+}
+
+hipError_t launch_gru_layer_generic_wrapped(const GruLayerParams& p, const GruWrapLayer& wl, int hidden, bool first, bool last,
+                                            hipStream_t st) {
+    // the epilogue area is carved whether or not the layer is the last: the normalised frame lies behind it
+    size_t lds = generic_lds_bytes(hidden, true) + gru_wrapped_extra_lds(p.KCX / 4);
+    if (p.t_stride != 0 && lds < kOneWorkgroupPerCuLds) lds = kOneWorkgroupPerCuLds;     // as launch_gru_layer_generic
+#define KWS_GENW(TPW_) \
+    do { \
+        if (first && last) return launch_wrapped_with_lds(gru_layer_generic_wrapped<TPW_, true, true>, p, wl, lds, st); \
+        if (first) return launch_wrapped_with_lds(gru_layer_generic_wrapped<TPW_, true, false>, p, wl, lds, st); \
+        if (last) return launch_wrapped_with_lds(gru_layer_generic_wrapped<TPW_, false, true>, p, wl, lds, st); \
+        return launch_wrapped_with_lds(gru_layer_generic_wrapped<TPW_, false, false>, p, wl, lds, st); \
+    } while (0)
+    if (hidden == 64) KWS_GENW(1);
+    if (hidden == 128) KWS_GENW(2);
+    if (hidden == 256) KWS_GENW(4);
+#undef KWS_GENW
+    return hipErrorInvalidValue;
+}
+
+template <int TPW>
+static hipError_t launch_pipelined_wrapped(const GruStackParams& sp, const GruWrapParams& wp, size_t lds, hipStream_t st) {
+    static LdsGrant granted;
+    {
+        const hipError_t e = grant_dynamic_lds(gru_stack_generic_pipelined_wrapped<TPW>, granted, lds);
+        if (e != hipSuccess) return e;
+    }
+    const int per = sp.xcd_affine ? 8 / sp.L : 0;
+    const int grid = sp.xcd_affine ? 8 * ((sp.G + per - 1) / per) : sp.G * sp.L;
+    hipLaunchKernelGGL(gru_stack_generic_pipelined_wrapped<TPW>, dim3(grid), dim3(256), lds, st, sp, wp);
+    return hipGetLastError();
+}
+
+hipError_t launch_gru_stack_generic_pipelined_wrapped(const GruStackParams& sp, const GruWrapParams& wp, int hidden, hipStream_t st) {
+    int kx4 = 0;
+    for (int l = 0; l < sp.L; ++l) kx4 = sp.layer[l].KCX / 4 > kx4 ? sp.layer[l].KCX / 4 : kx4;
+    size_t lds = generic_lds_bytes(hidden, true) + gru_wrapped_extra_lds(kx4);
+    if (lds < kOneWorkgroupPerCuLds) lds = kOneWorkgroupPerCuLds;        // one workgroup per CU, as the plain launch
+    if (hidden == 64) return launch_pipelined_wrapped<1>(sp, wp, lds, st);
+    if (hidden == 128) return launch_pipelined_wrapped<2>(sp, wp, lds, st);
+    if (hidden == 256) return launch_pipelined_wrapped<4>(sp, wp, lds, st);
     return hipErrorInvalidValue;
 }
 

@@ -144,6 +144,22 @@ struct GruStackParams {
 };
 hipError_t launch_gru_stack_generic_pipelined(const GruStackParams& sp, int hidden, hipStream_t st);
 
+// Cell wrappers of the reference's get_cell (models/rnn_ctc.py:186-197): ResidualWrapper(LayerNormalizer(GRUCell)), the residual on
+// layers >= 1 only (utils/custom_wrapper.py:95-158).  A kernel argument of the wrapped generic instantiations only, so that
+// GruLayerParams / GruStackParams and every plain instantiation stay as they are.
+struct GruWrapLayer {
+    const float* igamma;    // layer norm: the per-feature SHIFT, [16 * KCX/4] floats (zero past I); null: no layer norm on this layer
+    float ibeta;            // layer norm: the scalar SCALE.  The reference binds _ln(inputs, ibeta, igamma) to _ln(input, s, b)
+                            // (custom_wrapper.py:130 against :145): its names are swapped, and kept here as they are in checkpoints
+    int residual;           // 0.7071 (h' + x) is the layer's output (seam / dense layer); the recurrent state stays h'
+};
+struct GruWrapParams { GruWrapLayer layer[8]; };
+// extra dynamic LDS of a wrapped launch whose layers take at most kx4 input k-groups (16 features each): the normalised frame
+constexpr size_t gru_wrapped_extra_lds(int kx4) { return (size_t)kx4 * 64 * 16; }
+hipError_t launch_gru_layer_generic_wrapped(const GruLayerParams& p, const GruWrapLayer& wl, int hidden, bool first, bool last,
+                                            hipStream_t st);
+hipError_t launch_gru_stack_generic_pipelined_wrapped(const GruStackParams& sp, const GruWrapParams& wp, int hidden, hipStream_t st);
+
 // bf16 fused stack (gru_bf16.hip): every layer in one launch, no inter-layer scratch
 struct GruBf16Params {
     const uint4* w[2];      // per layer: [8 tiles][3 gates][KC_l chunks][64 lanes] bf16x8 A operands (x chunks first)

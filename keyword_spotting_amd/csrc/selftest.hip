@@ -14,11 +14,15 @@ namespace {
 
 thread_local bool g_in_selftest = false;
 
-// (mel [B,T,I], state [L,B,H]) -> (logits [B,T,C], state'), canonical blob layout of kws_weights_nbytes; double throughout
-void host_forward(const kws_config& c, const float* blob, const float* mel, const float* st0, int B, int T,
+// (mel [B,T,I], state [L,B,H]) -> (logits [B,T,C], state'), blob layout of kws_weights_nbytes_wrapped; double throughout.
+// With the cell wrappers each layer is ResidualWrapper(LayerNormalizer(GRUCell)) (models/rnn_ctc.py:186-197): the input
+// normalised over its features (mean, population variance, eps 1e-5; scale ibeta, shift igamma: custom_wrapper.py:126-158) before
+// the cell, and on layers >= 1 the output 0.7071 (h' + x) with x the raw input (:112-116), the state h'.
+void host_forward(const kws_config& c, const kws_cell_wrappers& wr, const float* blob, const float* mel, const float* st0, int B, int T,
                   std::vector<double>& logits, std::vector<double>& state) {
     const int H = c.hidden, L = c.num_layers, C = c.num_classes;
     const BlobLayout bl = blob_layout(c);
+    const WrapLayout wl = wrap_layout(c, wr);
     state.assign(st0, st0 + (size_t)L * B * H);
     logits.assign((size_t)B * T * C, 0.0);
     std::vector<double> x, g(2 * H), cand(H), hn(H);
@@ -27,6 +31,16 @@ void host_forward(const kws_config& c, const float* blob, const float* mel, cons
             x.assign(mel + ((size_t)b * T + t) * c.n_mel, mel + ((size_t)b * T + t + 1) * c.n_mel);
             for (int l = 0; l < L; ++l) {
                 const int I = bl.layer[l].in;
+                const std::vector<double> x_raw = x;
+                if (wr.use_layer_norm) {
+                    double mu = 0.0, var = 0.0;
+                    for (int k = 0; k < I; ++k) mu += x[k];
+                    mu /= I;
+                    for (int k = 0; k < I; ++k) var += (x[k] - mu) * (x[k] - mu);
+                    var /= I;
+                    const double scale = blob[wl.ibeta[l]] / std::sqrt(var + 1e-5);
+                    for (int k = 0; k < I; ++k) x[k] = (x[k] - mu) * scale + blob[wl.igamma[l] + k];
+                }
                 const float *Wg = blob + bl.layer[l].wg, *bg = blob + bl.layer[l].bg, *Wc = blob + bl.layer[l].wc, *bc = blob + bl.layer[l].bc;
                 double* h = &state[((size_t)l * B + b) * H];
                 for (int j = 0; j < 2 * H; ++j) {
@@ -44,6 +58,8 @@ void host_forward(const kws_config& c, const float* blob, const float* mel, cons
                 for (int j = 0; j < H; ++j) hn[j] = g[H + j] * h[j] + (1.0 - g[H + j]) * cand[j];
                 std::copy(hn.begin(), hn.end(), h);
                 x = hn;
+                if (wr.use_residual && l > 0)
+                    for (int j = 0; j < H; ++j) x[j] = 0.7071067811865475 * (hn[j] + x_raw[j]);
             }
             const float *Wfc = blob + bl.wfc, *bfc = blob + bl.bfc;
             for (int k = 0; k < C; ++k) {
@@ -62,12 +78,12 @@ struct DevBuf {
 };
 
 // one case through kws_step on a temporary handle; *err_state / *err_logit = max abs deviation from the host loop
-int selftest_case(const kws_config& cfg, int kernel_kind, const std::vector<float>& blob, const std::vector<float>& mel,
-                  const std::vector<float>& st0, int B, int T, double* err_logit, double* err_state, std::vector<float>* state_out,
-                  std::string* kernels) {
+int selftest_case(const kws_config& cfg, const kws_cell_wrappers& wr, int kernel_kind, const std::vector<float>& blob,
+                  const std::vector<float>& mel, const std::vector<float>& st0, int B, int T, double* err_logit, double* err_state,
+                  std::vector<float>* state_out, std::string* kernels) {
     const int H = cfg.hidden, L = cfg.num_layers, C = cfg.num_classes;
     kws_handle m = nullptr;
-    int rc = kws_create(&cfg, blob.data(), blob.size() * sizeof(float), &m);
+    int rc = kws_create_wrapped(&cfg, &wr, blob.data(), blob.size() * sizeof(float), &m);
     if (rc != KWS_OK) return rc;
     rc = kws_set_kernel(m, kernel_kind);
     DevBuf d_mel, d_st, d_lg;
@@ -101,7 +117,7 @@ int selftest_case(const kws_config& cfg, int kernel_kind, const std::vector<floa
     kws_destroy(m);
     if (rc != KWS_OK) { g_last_error = keep; return rc; }
     std::vector<double> want_l, want_s;
-    host_forward(cfg, blob.data(), mel.data(), st0.data(), B, T, want_l, want_s);
+    host_forward(cfg, wr, blob.data(), mel.data(), st0.data(), B, T, want_l, want_s);
     double el = 0.0, es = 0.0;
     for (size_t i = 0; i < lg.size(); ++i) { const double d = std::fabs(lg[i] - want_l[i]); el = (d > el || d != d) ? d : el; }
     for (size_t i = 0; i < st.size(); ++i) { const double d = std::fabs(st[i] - want_s[i]); es = (d > es || d != d) ? d : es; }
@@ -125,8 +141,11 @@ extern "C" int kws_selftest(kws_handle h) {
     if (g_in_selftest) return KWS_OK;
     struct Guard { Guard() { g_in_selftest = true; } ~Guard() { g_in_selftest = false; } } guard;
     const kws_config cfg = h->cfg;
+    const kws_cell_wrappers wr = h->wrap;
+    const kws_cell_wrappers plain = {0, 0};
     const int H = cfg.hidden, L = cfg.num_layers, C = cfg.num_classes, I0 = cfg.n_mel;
     const BlobLayout bl = blob_layout(cfg);
+    const WrapLayout wl = wrap_layout(cfg, wr);
     // tolerances: what the arithmetic of each precision leaves on these two cases (fp32: observed <= 4e-6 / 1e-7)
     double tol_rand_logit, tol_rand_state, tol_kat;
     switch (cfg.precision) {
@@ -137,7 +156,7 @@ extern "C" int kws_selftest(kws_handle h) {
     std::vector<int> kinds;
     if (cfg.precision == KWS_FP32) {
         bool res_ok = true;
-        for (const auto& Ld : h->pk.layers) res_ok &= Ld.resident_ok;
+        for (const auto& Ld : h->pk.layers) res_ok &= Ld.resident_ok && !h->wrapped;
         if (res_ok) kinds.push_back(KWS_KERNEL_RESIDENT);
         kinds.push_back(KWS_KERNEL_GENERIC);
     } else {
@@ -145,8 +164,9 @@ extern "C" int kws_selftest(kws_handle h) {
     }
     for (int kind : kinds) {
         std::string kernels;
-        // (1) TensorFlow's published constants, the 2-unit test cell embedded in this shape: units 0,1 and inputs 0..n_in-1 live
-        for (int n_in = 2; n_in <= 3 && n_in <= I0; ++n_in) {
+        // (1) TensorFlow's published constants, the 2-unit test cell embedded in this shape: units 0,1 and inputs 0..n_in-1 live.
+        // They are constants of the plain cell: a wrapped handle skips them (its kernels are proven by (2) alone).
+        for (int n_in = 2; n_in <= 3 && n_in <= I0 && !h->wrapped; ++n_in) {
             std::vector<float> blob(bl.total, 0.f);
             for (int l = 0; l < L; ++l) {
                 const int in = bl.layer[l].in, live = l == 0 ? n_in : 2;
@@ -170,7 +190,7 @@ extern "C" int kws_selftest(kws_handle h) {
                 for (int l = 0; l < L; ++l) st0[((size_t)l * B + b) * H + 0] = st0[((size_t)l * B + b) * H + 1] = 0.1f;
             }
             double el, es;
-            const int rc = selftest_case(cfg, kind, blob, mel, st0, B, T, &el, &es, &st, &kernels);
+            const int rc = selftest_case(cfg, plain, kind, blob, mel, st0, B, T, &el, &es, &st, &kernels);
             if (rc != KWS_OK) return rc;
             const double first = n_in == 2 ? 0.175991 : 0.156736;
             double worst = 0.0;
@@ -188,7 +208,7 @@ extern "C" int kws_selftest(kws_handle h) {
         // (2) 8 random frames of 19 streams against the host double-precision loop
         if (tol_rand_logit > 0) {
             Lcg rng{0x9e3779b97f4a7c15ull + (uint64_t)kind};
-            std::vector<float> blob(bl.total);
+            std::vector<float> blob(wl.total);
             for (int l = 0; l < L; ++l) {
                 const int in = bl.layer[l].in;
                 float* Wg = blob.data() + bl.layer[l].wg;
@@ -203,12 +223,19 @@ extern "C" int kws_selftest(kws_handle h) {
             }
             float* Wfc = blob.data() + bl.wfc;
             for (int i = 0; i < H * C + C; ++i) Wfc[i] = rng.next();
+            // the layer norm's tables, random: with TF's initial values (ibeta = 0) its output would not depend on the input
+            if (wr.use_layer_norm)
+                for (int l = 0; l < L; ++l) {
+                    const float r = rng.next();
+                    blob[wl.ibeta[l]] = (r < 0.f ? -1.f : 1.f) * (0.5f + 1.5f * std::fabs(r));
+                    for (int k = 0; k < bl.layer[l].in; ++k) blob[wl.igamma[l] + k] = 0.5f * rng.next();
+                }
             const int B = 19, T = 8;
             std::vector<float> mel((size_t)B * T * I0), st0((size_t)L * B * H);
             for (auto& v : mel) v = 2.f * std::fabs(rng.next());
             for (auto& v : st0) v = 0.5f * rng.next();
             double el, es;
-            const int rc = selftest_case(cfg, kind, blob, mel, st0, B, T, &el, &es, nullptr, &kernels);
+            const int rc = selftest_case(cfg, wr, kind, blob, mel, st0, B, T, &el, &es, nullptr, &kernels);
             if (rc != KWS_OK) return rc;
             if (!(el <= tol_rand_logit && es <= tol_rand_state))
                 return fail(KWS_ERR_HIP, "kws_selftest: %s differs from the host double-precision loop on 19 streams x 8 frames: max |dlogit| "

@@ -26,6 +26,18 @@ BlobLayout blob_layout(const kws_config& c) {
     return b;
 }
 
+WrapLayout wrap_layout(const kws_config& c, const kws_cell_wrappers& w) {
+    WrapLayout r;
+    size_t at = blob_layout(c).total;
+    for (int l = 0; l < c.num_layers; ++l) {
+        r.ibeta[l] = at;
+        r.igamma[l] = at + 1;
+        if (w.use_layer_norm) at += 1 + (size_t)(l == 0 ? c.n_mel : c.hidden);
+    }
+    r.total = at;
+    return r;
+}
+
 namespace {
 
 // K-index permutation of the "xl" layout: chunk kc, lane group g -> source row
@@ -295,9 +307,21 @@ int pack_int8(const kws_config& cfg, const float* blob, const BlobLayout& bl, Pa
 
 }  // namespace
 
-int pack_weights(const kws_config& cfg, const float* blob, PackedWeights* pk, std::vector<float>* image) {
+int pack_weights(const kws_config& cfg, const kws_cell_wrappers& wrap, const float* blob, PackedWeights* pk, std::vector<float>* image) {
     const BlobLayout bl = blob_layout(cfg);
     pack_fp32(cfg, blob, bl, pk, *image);
+    if (wrap.use_layer_norm) {
+        // igamma in its natural feature order: lane (g, s) of k-group k4 holds features 16 k4 + 4g + e, which is the mel row's
+        // order and the seam's "xl" order alike (kws_internal.h), so the kernel reads igamma[16 k4 + 4g ..] as it is
+        const WrapLayout wl = wrap_layout(cfg, wrap);
+        for (int l = 0; l < cfg.num_layers; ++l) {
+            const LayerDev& L = pk->layers[l];
+            const size_t off = reserve(*image, (size_t)4 * L.kcx_gen);
+            for (int k = 0; k < L.in_dim; ++k) (*image)[off + k] = blob[wl.igamma[l] + k];
+            pk->ln_igamma.push_back(off);
+            pk->ln_ibeta.push_back(blob[wl.ibeta[l]]);
+        }
+    }
     switch (cfg.precision) {
         case KWS_BF16:
         case KWS_F16X3: return pack_a32(cfg, blob, bl, pk, *image);

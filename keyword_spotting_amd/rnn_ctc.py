@@ -47,9 +47,17 @@ class DeployModel(object):
                                    int(bool(config.use_relu)), float(config.value_clip),
                                    {"fp32": _lib.FP32, "bf16": _lib.BF16, "int8": _lib.INT8, "f16x3": _lib.F16X3}[getattr(config, "precision", "fp32")])
         self._handle = ctypes.c_void_p()
+        # the cell wrappers of get_cell (models/rnn_ctc.py:186-197): kws_create_wrapped, whose blob carries the layer norm's tables
+        self.wrappers = (bool(getattr(config, "use_layer_norm", False)), bool(getattr(config, "use_residual", False)))
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_create(ctypes.byref(self._cfg), blob.ctypes.data_as(ctypes.c_void_p),
-                                            blob.nbytes, ctypes.byref(self._handle)))
+            if any(self.wrappers):
+                wrap = _lib.KwsCellWrappers(int(self.wrappers[0]), int(self.wrappers[1]))
+                _lib.check(self._lib.kws_create_wrapped(ctypes.byref(self._cfg), ctypes.byref(wrap),
+                                                        blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes,
+                                                        ctypes.byref(self._handle)))
+            else:
+                _lib.check(self._lib.kws_create(ctypes.byref(self._cfg), blob.ctypes.data_as(ctypes.c_void_p),
+                                                blob.nbytes, ctypes.byref(self._handle)))
         self.set_kernel(kernel)
 
     # -- lifecycle ---------------------------------------------------------------------------

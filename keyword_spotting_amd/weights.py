@@ -7,12 +7,26 @@ dict layout (one entry per tf.get_variable of the reference graph):
                Wc [I_l+H, H]   .../candidate/kernel
                bc [H]          .../candidate/bias}
   Wfc [H, C] weightsClasses, bfc [C] biasesClasses   (models/rnn_ctc.py:265-273)
+with config.use_layer_norm (LayerNormalizer around each cell: models/rnn_ctc.py:186-187, utils/custom_wrapper.py:120-158),
+per layer also
+               ibeta  []       .../cell_l/LayerNormalizer/ibeta    the SCALAR SCALE (TF initialises it to 0)
+               igamma [I_l]    .../cell_l/LayerNormalizer/igamma   the PER-FEATURE SHIFT (initialised to 1)
+  -- the reference passes them to _ln(input, s, b) as (ibeta, igamma) (custom_wrapper.py:145-148 against :130): the names are
+  swapped against their roles and are kept as the checkpoints have them.  use_residual creates no variables.
+The blob (kws_weights_nbytes_wrapped): the canonical blob, then with the layer norm each layer's ibeta and igamma in layer order.
 """
 import numpy as np
 
 
 def layer_in_dims(config):
     return [config.n_mel if l == 0 else config.hidden_size for l in range(config.num_layers)]
+
+
+def _layer_norm(config):
+    return bool(getattr(config, "use_layer_norm", False))
+
+
+LN_KEYS = ("ibeta", "igamma")
 
 
 def init_weights(config, seed=0):
@@ -29,6 +43,8 @@ def init_weights(config, seed=0):
         a = np.sqrt(6.0 / (k + h))
         wc = rng.uniform(-a, a, size=(k, h)).astype(np.float32)
         layers.append(dict(Wg=wg, bg=np.ones(2 * h, np.float32), Wc=wc, bc=np.zeros(h, np.float32)))
+        if _layer_norm(config):             # TF's initial values (custom_wrapper.py:149-154): the layer norm then outputs igamma
+            layers[-1].update(ibeta=np.zeros((), np.float32), igamma=np.ones(i_l, np.float32))
     wfc = rng.standard_normal((h, c))
     bad = np.abs(wfc) > 2.0
     while bad.any():
@@ -43,7 +59,15 @@ def check_shapes(config, w):
         raise ValueError("expected %d layers, got %d" % (config.num_layers, len(w["layers"])))
     for l, (lay, i_l) in enumerate(zip(w["layers"], layer_in_dims(config))):
         want = dict(Wg=(i_l + h, 2 * h), bg=(2 * h,), Wc=(i_l + h, h), bc=(h,))
+        if _layer_norm(config):
+            want.update(ibeta=(), igamma=(i_l,))
+        else:
+            extra = [k for k in LN_KEYS if k in lay]
+            if extra:
+                raise ValueError("layer %d has LayerNormalizer weights (%s) but config.use_layer_norm is off" % (l, ", ".join(extra)))
         for name, shape in want.items():
+            if name not in lay:
+                raise ValueError("layer %d has no %s (config.use_layer_norm is on)" % (l, name))
             if tuple(lay[name].shape) != shape:
                 raise ValueError("layer %d %s has shape %s, expected %s" % (l, name, lay[name].shape, shape))
     if tuple(w["Wfc"].shape) != (h, c) or tuple(w["bfc"].shape) != (c,):
@@ -57,6 +81,9 @@ def to_blob(config, w):
     for lay in w["layers"]:
         parts += [lay["Wg"], lay["bg"], lay["Wc"], lay["bc"]]
     parts += [w["Wfc"], w["bfc"]]
+    if _layer_norm(config):
+        for lay in w["layers"]:
+            parts += [lay["ibeta"], lay["igamma"]]
     return np.ascontiguousarray(np.concatenate([np.asarray(p, np.float32).ravel() for p in parts]))
 
 
@@ -75,6 +102,10 @@ def from_blob(config, blob):
     for i_l in layer_in_dims(config):
         layers.append(dict(Wg=take(i_l + h, 2 * h), bg=take(2 * h), Wc=take(i_l + h, h), bc=take(h)))
     w = dict(layers=layers, Wfc=take(h, c), bfc=take(c))
+    if _layer_norm(config):
+        for lay, i_l in zip(layers, layer_in_dims(config)):
+            lay["ibeta"] = take(1).reshape(())
+            lay["igamma"] = take(i_l)
     if pos != blob.size:
         raise ValueError("blob has %d floats, config needs %d" % (blob.size, pos))
     return w
@@ -91,7 +122,8 @@ def save_npz(path, w):
 def load_npz(path):
     z = np.load(path)
     n = 1 + max(int(k[1:].split("_")[0]) for k in z.files if k.startswith("l"))
-    return dict(layers=[{k: z["l%d_%s" % (l, k)] for k in ("Wg", "bg", "Wc", "bc")} for l in range(n)],
+    return dict(layers=[{k: z["l%d_%s" % (l, k)] for k in ("Wg", "bg", "Wc", "bc") + LN_KEYS if "l%d_%s" % (l, k) in z.files}
+                        for l in range(n)],
                 Wfc=z["Wfc"], bfc=z["bfc"])
 
 
@@ -102,9 +134,13 @@ def from_tf_variables(config, variables):
       [model/]drnn/multi_rnn_cell/cell_<l>/gru_cell/{gates,candidate}/{kernel,bias}     TF >= 1.2
       ...                                            {gates,candidate}/{weights,biases}  TF 1.0-1.1
       [model/]weightsClasses, [model/]biasesClasses
-    Optimiser slots (".../Adam", ".../Adam_1") and a trailing ":0" are ignored."""
+      [model/]drnn/multi_rnn_cell/cell_<l>/[<scope>/]LayerNormalizer/{ibeta,igamma}   config.use_layer_norm
+    Optimiser slots (".../Adam", ".../Adam_1") and a trailing ":0" are ignored.  LayerNormalizer variables while
+    config.use_layer_norm is off, or none of them while it is on, raise: the model they describe is another function."""
     import re
     pat = re.compile(r"(?:^|/)cell_(\d+)/gru_cell/(gates|candidate)/(kernel|weights|bias|biases)(?::0)?$")
+    ln_pat = re.compile(r"(?:^|/)cell_(\d+)/(?:[^/]+/)?LayerNormalizer/(ibeta|igamma)(?::0)?$")
+    ln = _layer_norm(config)
     slot = {("gates", "kernel"): "Wg", ("gates", "weights"): "Wg", ("gates", "bias"): "bg", ("gates", "biases"): "bg",
             ("candidate", "kernel"): "Wc", ("candidate", "weights"): "Wc", ("candidate", "bias"): "bc",
             ("candidate", "biases"): "bc"}
@@ -121,6 +157,18 @@ def from_tf_variables(config, variables):
                 raise ValueError("two variables map to layer %d %s (second: %s)" % (l, key, name))
             layers[l][key] = np.asarray(arr, np.float32)
             continue
+        m = ln_pat.search(name)
+        if m:
+            if not ln:
+                raise ValueError("variable %s belongs to a LayerNormalizer (use_layer_norm=True in training), but "
+                                 "config.use_layer_norm is off: convert with use_layer_norm on" % name)
+            l, key = int(m.group(1)), m.group(2)
+            if l >= config.num_layers:
+                raise ValueError("variable %s belongs to layer %d, config has %d layers" % (name, l, config.num_layers))
+            if key in layers[l]:
+                raise ValueError("two variables map to layer %d %s (second: %s)" % (l, key, name))
+            layers[l][key] = np.asarray(arr, np.float32)
+            continue
         base = name[:-2] if name.endswith(":0") else name
         base = base.rsplit("/", 1)[-1]
         if base == "weightsClasses":
@@ -131,6 +179,10 @@ def from_tf_variables(config, variables):
         missing = [k for k in ("Wg", "bg", "Wc", "bc") if k not in lay]
         if missing:
             raise ValueError("layer %d: no variable found for %s" % (l, ", ".join(missing)))
+        missing = [k for k in LN_KEYS if ln and k not in lay]
+        if missing:
+            raise ValueError("config.use_layer_norm is on, but no variable drnn/multi_rnn_cell/cell_%d/LayerNormalizer/%s was found"
+                             % (l, missing[0]))
     for k in ("Wfc", "bfc"):
         if k not in w:
             raise ValueError("no variable found for %s (weightsClasses / biasesClasses)" % k)
@@ -146,4 +198,7 @@ def to_tf_variables(w, new_names=True, prefix="model/"):
         base = "%sdrnn/multi_rnn_cell/cell_%d/gru_cell/" % (prefix, l)
         out[base + "gates/" + kn], out[base + "gates/" + bn] = lay["Wg"], lay["bg"]
         out[base + "candidate/" + kn], out[base + "candidate/" + bn] = lay["Wc"], lay["bc"]
+        for k in LN_KEYS:
+            if k in lay:
+                out["%sdrnn/multi_rnn_cell/cell_%d/LayerNormalizer/%s" % (prefix, l, k)] = lay[k]
     return out
