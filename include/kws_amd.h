@@ -345,6 +345,63 @@ int kws_octbit_matmul(const float* x, const int8_t* Wq, float scale_w, const flo
 /* Host-side quantiser: W [K,N] f32 (host) -> Wq [N,K] s8 (host), *scale, bias [N] f32 (host). */
 int kws_octbit_quantize(const float* W, int K, int N, int8_t* Wq, float* scale, float* bias);
 
+/* Self-attention CTC model (models/attention_ctc.py:73-128 `inference`, DeployModel :215-274; config/attention_config.py),
+ * batched over B independent utterances: each utterance's results are what the reference's batch-1 DeployModel gives for it,
+ * whatever the other utterances and the padding.  Utterance b has T_b mel frames; c = combine_frame:
+ *   stacking      c > 1: c - (T_b mod c) zero frames appended (1..c), rows of c frames -> T'_b = T_b / c + 1 rows of c*n_mel;
+ *                 c == 1: T'_b = T_b (kws_attention_frames_out)
+ *   embedding     x = row . W_in + b_in + pe[t'], pe[p][2i] = sin(p / 10000^(2i/H)), pe[p][2i+1] = cos(..), computed in double,
+ *                 stored as float; the pad rows are real positions
+ *   per layer     qkv = x . W_qkv + b_qkv; per head (d = hidden / num_heads) softmax(q k^T / sqrt(d)) v over the utterance's
+ *                 T'_b keys, no mask, no output projection; y = LN_a(att + x); x = LN_b(relu(y . W1 + b1) . W2 + b2 + y)
+ *   LN            tf.contrib.layers.layer_norm of TF 1.x: mean and population variance over the utterance's WHOLE [T'_b, H]
+ *                 block, eps 1e-12, then * gamma + beta
+ *   output        logits = relu?(x . W_out + b_out) (the post-relu logits: an extension, the reference graph exports only the
+ *                 softmax), softmax over the classes
+ * Supported (else KWS_ERR_UNSUPPORTED naming the field): n_mel * combine_frame <= 512, combine_frame 1..4, hidden 64/128/256
+ * with hidden / num_heads 16 or 32, ffn_inner a multiple of 64 up to 1024, num_layers 1..8, num_classes 3..8, use_relu 0/1,
+ * max_frames 1..8192 (the longest utterance a handle takes: the positional table holds max_frames / combine_frame + 1 rows).
+ * Same conventions as a model handle: one host thread at a time per handle (KWS_ERR_BUSY), a call on another stream than the
+ * previous one is ordered behind it by the handle's event, no device-wide wait except create, destroy and scratch growth. */
+typedef struct kws_attention_config {
+    int32_t n_mel;          /* F : mel bins per frame (config/attention_config.py:67: 60)       */
+    int32_t combine_frame;  /* c : frames stacked per row (:79: 2)                               */
+    int32_t hidden;         /* H : model width (:85: 128)                                         */
+    int32_t num_heads;      /* multi_head_num (:84: 8)                                            */
+    int32_t ffn_inner;      /* feed_forward_inner_size (:82: 512)                                 */
+    int32_t num_layers;     /* L (:80: 3)                                                         */
+    int32_t num_classes;    /* C (:88-91: 6)                                                      */
+    int32_t use_relu;       /* relu on the logits (:55: 1)                                        */
+    int32_t max_frames;     /* longest T_max a call may pass                                      */
+} kws_attention_config;
+typedef struct kws_attention* kws_attention_handle;
+size_t kws_sizeof_attention_config(void);
+/* Bytes of the canonical fp32 blob (0: invalid config), row-major, the 1x1 conv kernels squeezed to [in, out]:
+ *   W_in [c*F, H]  b_in [H]
+ *   per layer: W_qkv [H, 3H]  b_qkv [3H]  ln_a beta [H]  ln_a gamma [H]  W1 [H, Fi]  b1 [Fi]  W2 [Fi, H]  b2 [H]
+ *              ln_b beta [H]  ln_b gamma [H]
+ *   W_out [H, C]  b_out [C] */
+size_t kws_attention_weights_nbytes(const kws_attention_config* cfg);
+/* weights_blob: HOST memory of kws_attention_weights_nbytes(cfg) bytes.  With KWS_SELFTEST=1 the create runs
+ * kws_attention_selftest and fails as it does. */
+int kws_attention_create(const kws_attention_config* cfg, const void* weights_blob, size_t nbytes, kws_attention_handle* out);
+int kws_attention_destroy(kws_attention_handle h);   /* always KWS_OK */
+/* T' of an utterance of T frames (>= 0), or a negative kws_status */
+int kws_attention_frames_out(const kws_attention_config* cfg, int T);
+/* Pre-sizes the scratch for calls of B utterances x T_max frames (the scratch only grows; growing synchronises once). */
+int kws_attention_reserve(kws_attention_handle h, int B, int T_max);
+/*   mel      [B, T_max, n_mel] f32 device
+ *   lengths  [B] i32 device or NULL (= T_max): clamped to [0, T_max]; frames at or past T_b are never read into a result
+ *   logits   [B, T'_max, C] f32 out or NULL; softmax [B, T'_max, C] f32 out or NULL (not both NULL); T'_max = frames_out(T_max)
+ * Rows t' >= T'_b of both outputs are written as 0.  B == 0 or T'_max == 0 is a no-op. */
+int kws_attention_run(kws_attention_handle h, const float* mel, const int32_t* lengths, int B, int T_max, float* logits,
+                      float* softmax, void* stream);
+/* Copies the fp32 positional table [max_frames / combine_frame + 1, hidden] (host memory) -- for inspection/tests. */
+int kws_attention_pe_table(kws_attention_handle h, float* host_out);
+/* Runs the handle's kernels on 3 random utterances (lengths T_max, T_max / 2 + 1 and 1) against a double-precision host loop
+ * of the contract above; synchronises.  KWS_OK, or KWS_ERR_HIP with the deviation and kws_version(). */
+int kws_attention_selftest(kws_attention_handle h);
+
 #ifdef __cplusplus
 }
 #endif

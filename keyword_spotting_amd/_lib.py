@@ -33,6 +33,13 @@ class KwsCellWrappers(ctypes.Structure):
     _fields_ = [("use_layer_norm", ctypes.c_int32), ("use_residual", ctypes.c_int32)]
 
 
+class KwsAttentionConfig(ctypes.Structure):
+    """kws_attention_config: the self-attention CTC model (config/attention_config.py) and the longest utterance a handle takes."""
+    _fields_ = [("n_mel", ctypes.c_int32), ("combine_frame", ctypes.c_int32), ("hidden", ctypes.c_int32),
+                ("num_heads", ctypes.c_int32), ("ffn_inner", ctypes.c_int32), ("num_layers", ctypes.c_int32),
+                ("num_classes", ctypes.c_int32), ("use_relu", ctypes.c_int32), ("max_frames", ctypes.c_int32)]
+
+
 class KwsError(RuntimeError):
     """Base of the errors the C ABI reports."""
 
@@ -96,6 +103,15 @@ _SIGNATURES = {
     "kws_stream_carry": (_i, [_vp, _vp, _vp, _vp]),
     "kws_octbit_matmul": (_i, [_vp, _vp, _f, _vp, _vp, _i, _i, _i, _i, _vp]),
     "kws_octbit_quantize": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "kws_sizeof_attention_config": (ctypes.c_size_t, []),
+    "kws_attention_weights_nbytes": (ctypes.c_size_t, [ctypes.POINTER(KwsAttentionConfig)]),
+    "kws_attention_create": (_i, [ctypes.POINTER(KwsAttentionConfig), _vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
+    "kws_attention_destroy": (_i, [_vp]),
+    "kws_attention_frames_out": (_i, [ctypes.POINTER(KwsAttentionConfig), _i]),
+    "kws_attention_reserve": (_i, [_vp, _i, _i]),
+    "kws_attention_run": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
+    "kws_attention_pe_table": (_i, [_vp, _vp]),
+    "kws_attention_selftest": (_i, [_vp]),
 }
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 
@@ -119,7 +135,8 @@ def load():
             fn.restype, fn.argtypes = res, args
         if lib.kws_sizeof_config() != ctypes.sizeof(KwsConfig) or \
                 lib.kws_sizeof_frontend_config() != ctypes.sizeof(KwsFrontendConfig) or \
-                lib.kws_sizeof_cell_wrappers() != ctypes.sizeof(KwsCellWrappers):
+                lib.kws_sizeof_cell_wrappers() != ctypes.sizeof(KwsCellWrappers) or \
+                lib.kws_sizeof_attention_config() != ctypes.sizeof(KwsAttentionConfig):
             raise ImportError("%s was built from a different include/kws_amd.h than this binding (struct sizes differ); "
                               "rebuild it" % LIB_PATH)
         _lib = lib

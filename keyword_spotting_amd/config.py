@@ -37,3 +37,34 @@ class Config(object):
 
 def get_config(**overrides):
     return Config(**overrides)
+
+
+class AttentionConfig(Config):
+    """The fields of config/attention_config.py the self-attention CTC model's inference reads (its defaults: n_mel 60 :67,
+    use_relu :55, combine_frame :79, num_layers :80, feed_forward_inner_size :82, multi_head_num :84, hidden_size :85), and
+    max_frames: the longest utterance (mel frames) a DeployModel takes -- the size of its positional table."""
+
+    def __init__(self, **overrides):
+        self.label_dict = {"ni3": 1, "hao3": 2, "le4": 3}   # :26-27
+        self.label_seqs = "1233"                            # :28
+        self.fft_size = 400                                 # :59
+        self.hop_size = 160                                 # :60
+        self.samplerate = 16000                             # :61
+        self.n_mel = 60                                     # :67
+        self.fmin = 300                                     # :64
+        self.fmax = 8000                                    # :65
+        self.use_relu = True                                # :55
+        self.combine_frame = 2                              # :79
+        self.num_layers = 3                                 # :80
+        self.feed_forward_inner_size = 512                  # :82
+        self.multi_head_num = 8                             # :84
+        self.hidden_size = 128                              # :85
+        self.max_frames = 8192                              # not in the reference: the positional table's extent
+        for k, v in overrides.items():
+            if not hasattr(self, k):
+                raise AttributeError("unknown config key %r" % k)
+            setattr(self, k, type(getattr(self, k))(v) if not isinstance(getattr(self, k), dict) else v)
+
+
+def get_attention_config(**overrides):
+    return AttentionConfig(**overrides)

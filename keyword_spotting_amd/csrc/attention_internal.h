@@ -1,0 +1,57 @@
+// Kernel/host surface of the self-attention CTC model (attention_kernels.hip, api_attention.hip).  Not part of the ABI.
+#pragma once
+#include "kws_internal.h"
+
+namespace kws {
+
+// Row tile of every attention kernel: one workgroup covers 32 rows (stacked frames) of ONE utterance.  Each utterance's
+// activations start at row b * Tp of the scratch, Tp = T'_max rounded up to this tile, so a tile never spans two utterances
+// and the tiling of utterance b depends on T'_b alone (batch independence).
+constexpr int kAttnRows = 32;
+
+// A [K, N] fp32 matrix packed as v_mfma_f32_16x16x4_f32 B operands: [K/16][N/16][64 lanes] float4, lane l, component j =
+// W[16 kc + 4 (l / 16) + j][16 nt + l % 16] (rows past K zero).  The A operand of the same product reads the matching
+// float4 X[m][16 kc + 4 (l / 16) ...] out of LDS, so both sides agree on the k order inside a chunk.
+struct AttnLayerW {
+    const float4* wqkv;   // [H/16][3H/16][64]
+    const float* bqkv;    // [3H]
+    const float* ga;      // LN_a gamma [H]
+    const float* ba;      // LN_a beta  [H]
+    const float4* w1;     // [H/16][Fi/16][64]
+    const float* b1;      // [Fi]
+    const float4* w2;     // [Fi/16][H/16][64]
+    const float* b2;      // [H]
+    const float* gb;      // LN_b gamma [H]
+    const float* bb;      // LN_b beta  [H]
+};
+
+struct AttnParams {
+    const float* mel;       // [B, T_max, F]
+    const int32_t* lengths; // [B] or null (= T_max); clamped to [0, T_max]
+    int B, T_max, F, c;     // c = combine_frame
+    int KE;                 // c * F rounded up to 16 (the embedding GEMM's k extent)
+    int T1max;              // T'_max: rows of the outputs per utterance
+    int Tp, ntile;          // scratch rows per utterance (multiple of kAttnRows) and its tiles
+    int Fi, C, use_relu;
+    const float4* w_in;     // [KE/16][H/16][64]
+    const float* b_in;      // [H]
+    const float* pe;        // [>= T1max][H]
+    const float* w_out;     // [H][C] row-major
+    const float* b_out;     // [C]
+    float* S;               // [B][Tp][H]   layer input before its LN_b (layer 0: the embedding)
+    float* QKV;             // [B][Tp][3H]
+    float* U;               // [B][Tp][H]   att + x, before LN_a
+    float4* st_a;           // [B][ntile]   (count, mean, M2) of U per row tile
+    float4* st_b;           // [B][ntile]   ... of S (the FFN's z + y)
+    float* logits;          // [B][T1max][C] or null
+    float* softmax;         // [B][T1max][C] or null
+};
+
+// prev == null: the layer's input is the embedding (no LN_b in front of it)
+hipError_t launch_attn_embed(const AttnParams& p, int H, hipStream_t st);
+hipError_t launch_attn_qkv(const AttnParams& p, const AttnLayerW& w, const AttnLayerW* prev, int H, hipStream_t st);
+hipError_t launch_attn_core(const AttnParams& p, const AttnLayerW* prev, int H, int D, hipStream_t st);
+hipError_t launch_attn_ffn(const AttnParams& p, const AttnLayerW& w, int H, hipStream_t st);
+hipError_t launch_attn_out(const AttnParams& p, const AttnLayerW& last, int H, hipStream_t st);
+
+}  // namespace kws
