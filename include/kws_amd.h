@@ -239,6 +239,42 @@ int kws_frontend_run_carry(kws_frontend_handle h, const float* carry, int n_carr
 /* Copies the fp32 mel basis [n_mel, fft/2+1] (host memory) the handle was built with -- for inspection/tests. */
 int kws_frontend_mel_basis(kws_frontend_handle h, float* basis_host);
 
+/* Feature front-ends behind the same handle type: what the reference's graphs and reader build from the un-windowed STFT.
+ *   KWS_FEAT_MEL, power 1   |rfft| -> mel: kws_frontend_create(cfg) is exactly {cfg, KWS_FEAT_MEL, 1, 0}
+ *   KWS_FEAT_MEL, power 2   |rfft|^2 -> mel (reader.py:267-268)
+ *   KWS_FEAT_MFCC           config.mfcc (utils/mfcc.py:20-99; models/attention_ctc.py:249-250), per utterance of T frames:
+ *                             m = |rfft|^2 . mel_basis^T      squared whatever config.power says (:77); base.n_mel filters
+ *                             S = 10 log10(max(1e-10, m))     ref_value 1, and NO top_db: every call site leaves it None
+ *                             c = S . D                       D = the orthonormal DCT-II basis [n_mel, n_mfcc] in float32 (:33-42,:93)
+ *                             d[t] = c[min(t+1, T-1)] - c[max(t-1, 0)]     (_delta_order shifts by one frame whatever its order)
+ *                             row t = [c | d / 2 | 0.3 d]     3 * n_mfcc features (:96-99); T = 1 gives zero deltas
+ * kws_frontend_feature_size is the row width: n_mel, or 3 * n_mfcc.  The deltas' right-hand edge makes MFCC a transform of a
+ * WHOLE utterance: kws_frontend_run_carry and kws_stream_create refuse every handle that is not (KWS_FEAT_MEL, power 1) with
+ * KWS_ERR_UNSUPPORTED.  MFCC and power 2 exist for fft_size = 400 only (the FFT kernel; KWS_ERR_UNSUPPORTED otherwise, naming
+ * the field); n_mfcc outside 1..min(n_mel, 32) or power outside {1, 2} is KWS_ERR_INVALID_ARGUMENT.
+ *
+ * kws_frontend_run_lengths: B utterances in rows of n_max samples, utterance b with n_b = clamp(n_samples[b], 0, n_max) of them
+ * (n_samples == NULL: n_max for all).  out is [B, T_max, feature_size] with T_max = kws_frontend_frames(n_max); utterance b has
+ * T_b = kws_frontend_frames(n_b) rows, rows t >= T_b are written as 0, and samples at or past n_b are never read into a result
+ * (the padding may hold anything).  The delta edges of utterance b are its own T_b.  One launch for mel output, two for MFCC
+ * (the coefficients, then the deltas in place), whatever B; no host work per utterance, no allocation, no device-wide wait, any
+ * stream.  kws_frontend_run on an MFCC or power-2 handle is kws_frontend_run_lengths with n_samples == NULL.  On a
+ * (KWS_FEAT_MEL, power 1) handle with another fft_size than 400 only n_samples == NULL is supported. */
+enum { KWS_FEAT_MEL = 0, KWS_FEAT_MFCC = 1 };
+typedef struct kws_feature_config {
+    kws_frontend_config base;   /* samplerate, fft_size, hop_size, n_mel (= mel filters), fmin, fmax */
+    int32_t kind;               /* KWS_FEAT_MEL | KWS_FEAT_MFCC */
+    int32_t power;              /* KWS_FEAT_MEL only: 1 (|X|) or 2 (|X|^2); MFCC ignores it */
+    int32_t n_mfcc;             /* KWS_FEAT_MFCC: 1..min(n_mel, 32); KWS_FEAT_MEL ignores it */
+} kws_feature_config;
+size_t kws_sizeof_feature_config(void);
+int kws_frontend_create_features(const kws_feature_config* cfg, kws_frontend_handle* out);
+int kws_frontend_feature_size(kws_frontend_handle h);
+int kws_frontend_run_lengths(kws_frontend_handle h, const float* pcm /*[B, n_max] device*/, const int32_t* n_samples /*[B] device or NULL*/,
+                             int B, int n_max, float* out /*[B, T_max, feature_size] device*/, void* stream);
+/* Copies the fp32 DCT basis [n_mel, n_mfcc] (host memory) of an MFCC handle -- for inspection/tests. */
+int kws_frontend_dct_basis(kws_frontend_handle h, float* basis_host);
+
 /* Device-side decode window of the streaming loop (detector.py:122,168-209; utils/queue.py): per stream a
  * bounded FIFO of up to `max_chunks` (1..64) softmax chunks (each <= max_frames frames; 2 * max_chunks *
  * round_up(max_frames, 16) bytes must fit 48 KiB, else KWS_ERR_UNSUPPORTED).  The frame ring behind kws_window_step is

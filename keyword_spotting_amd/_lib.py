@@ -15,6 +15,7 @@ KWS_ERR_BUSY = -6
 KERNEL_AUTO, KERNEL_GENERIC, KERNEL_RESIDENT = 0, 1, 2
 DECODE, DECODE2, DECODE_STRICT = 0, 1, 2
 FP32, BF16, INT8, F16X3 = 0, 1, 2, 3
+FEAT_MEL, FEAT_MFCC = 0, 1
 
 
 class KwsConfig(ctypes.Structure):
@@ -26,6 +27,11 @@ class KwsConfig(ctypes.Structure):
 class KwsFrontendConfig(ctypes.Structure):
     _fields_ = [("samplerate", ctypes.c_int32), ("fft_size", ctypes.c_int32), ("hop_size", ctypes.c_int32),
                 ("n_mel", ctypes.c_int32), ("fmin", ctypes.c_float), ("fmax", ctypes.c_float)]
+
+
+class KwsFeatureConfig(ctypes.Structure):
+    """kws_feature_config: what a front-end handle produces (mel of |X| or |X|^2, or MFCC + deltas, utils/mfcc.py)."""
+    _fields_ = [("base", KwsFrontendConfig), ("kind", ctypes.c_int32), ("power", ctypes.c_int32), ("n_mfcc", ctypes.c_int32)]
 
 
 class KwsCellWrappers(ctypes.Structure):
@@ -90,6 +96,11 @@ _SIGNATURES = {
     "kws_frontend_run": (_i, [_vp, _vp, _i, _i, _vp, _vp]),
     "kws_frontend_run_carry": (_i, [_vp, _vp, _i, _vp, _i, _i, _vp, _vp, _i, _vp]),
     "kws_frontend_mel_basis": (_i, [_vp, _vp]),
+    "kws_sizeof_feature_config": (ctypes.c_size_t, []),
+    "kws_frontend_create_features": (_i, [ctypes.POINTER(KwsFeatureConfig), ctypes.POINTER(_vp)]),
+    "kws_frontend_feature_size": (_i, [_vp]),
+    "kws_frontend_run_lengths": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
+    "kws_frontend_dct_basis": (_i, [_vp, _vp]),
     "kws_window_create": (_i, [_i, _i, _i, _i, _f, ctypes.POINTER(_vp)]),
     "kws_window_destroy": (_i, [_vp]),
     "kws_window_step": (_i, [_vp, _vp, _i, _vp, ctypes.c_char_p, _vp, _vp, _vp]),
@@ -136,6 +147,7 @@ def load():
         if lib.kws_sizeof_config() != ctypes.sizeof(KwsConfig) or \
                 lib.kws_sizeof_frontend_config() != ctypes.sizeof(KwsFrontendConfig) or \
                 lib.kws_sizeof_cell_wrappers() != ctypes.sizeof(KwsCellWrappers) or \
+                lib.kws_sizeof_feature_config() != ctypes.sizeof(KwsFeatureConfig) or \
                 lib.kws_sizeof_attention_config() != ctypes.sizeof(KwsAttentionConfig):
             raise ImportError("%s was built from a different include/kws_amd.h than this binding (struct sizes differ); "
                               "rebuild it" % LIB_PATH)

@@ -39,7 +39,8 @@ class DeployModel(object):
         self._lib = _lib.load()
         blob = weights if isinstance(weights, np.ndarray) else _weights.to_blob(config, weights)
         blob = np.ascontiguousarray(blob, np.float32)
-        self._cfg = _lib.KwsAttentionConfig(int(config.n_mel), int(config.combine_frame), int(config.hidden_size),
+        # kws_attention_config.n_mel is the model's input width F: the mel bins, or the 3 * n_mfcc MFCC features (config.mfcc)
+        self._cfg = _lib.KwsAttentionConfig(int(config.freq_size), int(config.combine_frame), int(config.hidden_size),
                                             int(config.multi_head_num), int(config.feed_forward_inner_size),
                                             int(config.num_layers), int(config.num_classes), int(bool(config.use_relu)),
                                             int(config.max_frames))
@@ -64,10 +65,10 @@ class DeployModel(object):
 
     @property
     def frontend(self):
-        """The in-graph audio front-end (models/attention_ctc.py:241-261), created on first use."""
+        """The in-graph audio front-end (models/attention_ctc.py:241-261; :249-250 with config.mfcc), created on first use."""
         if self._frontend is None:
-            from .frontend import MelFrontend
-            self._frontend = MelFrontend(self.config, device=self.device)
+            from .frontend import MelFrontend, MfccFrontend
+            self._frontend = (MfccFrontend if self.config.mfcc else MelFrontend)(self.config, device=self.device)
         return self._frontend
 
     def frames_out(self, frames):
@@ -87,12 +88,12 @@ class DeployModel(object):
         return out
 
     def forward(self, mel, lengths=None, want_logits=True, want_softmax=True, out=None):
-        """mel [B, T, n_mel] (device or host), lengths [B] mel frames or None (= T) -> dict with the requested 'logits' and
-        'softmax' [B, T', C] (rows past each utterance's T'_b are 0) and 'lengths_out' [B] int32 (T'_b)."""
+        """mel [B, T, freq_size] (device or host; the MFCC features with config.mfcc), lengths [B] frames or None (= T) -> dict with the
+        requested 'logits' and 'softmax' [B, T', C] (rows past each utterance's T'_b are 0) and 'lengths_out' [B] int32 (T'_b)."""
         cfg = self.config
         mel = self._dev(mel, torch.float32, "mel")
-        if mel.dim() != 3 or mel.shape[2] != cfg.n_mel:
-            raise _lib.InvalidArgumentError(-1, "mel must be [B,T,%d], got %s" % (cfg.n_mel, tuple(mel.shape)))
+        if mel.dim() != 3 or mel.shape[2] != cfg.freq_size:
+            raise _lib.InvalidArgumentError(-1, "mel must be [B,T,%d], got %s" % (cfg.freq_size, tuple(mel.shape)))
         b, t = int(mel.shape[0]), int(mel.shape[1])
         if lengths is not None:
             lengths = self._dev(lengths, torch.int32, "lengths")
@@ -139,7 +140,11 @@ class DeployModel(object):
         pcm = torch.zeros(len(pcms), n_max, dtype=torch.float32)
         for i, p in enumerate(pcms):
             pcm[i, :p.shape[0]] = p.to(torch.float32).cpu()
-        mel = fe.forward(pcm)                                                 # [B, T, n_mel]; padding frames masked below
+        if self.config.mfcc:
+            # every utterance's own sample count: the zero-padded tail must not enter its last delta (utils/mfcc.py:58-69)
+            mel = fe.forward(pcm, torch.tensor([int(p.shape[0]) for p in pcms], dtype=torch.int32))
+        else:
+            mel = fe.forward(pcm)                                             # [B, T, n_mel]; padding frames masked below
         frames = torch.tensor([fe.num_frames(int(p.shape[0])) for p in pcms], dtype=torch.int32)
         r = self.forward(mel, frames, want_logits=FETCH_LOGIT in names, want_softmax=FETCH_SOFTMAX in names)
         table = {FETCH_SOFTMAX: r.get("softmax"), FETCH_LOGIT: r.get("logits"), FETCH_LENGTHS: r["lengths_out"]}

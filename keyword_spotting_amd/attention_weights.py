@@ -2,7 +2,7 @@
 kws_attention_create takes, and the TF variable names of the reference graph.
 
 dict layout (one entry per variable the reference graph creates, all under `model/`, main.py:54):
-  W_in  [c*F, H]  input_linear_trans/kernel                (a 1x1 conv2d: stored [1, 1, c*F, H] in a checkpoint)
+  W_in  [c*F, H]  input_linear_trans/kernel                (a 1x1 conv2d: stored [1, 1, c*F, H] in a checkpoint; F = config.freq_size)
   b_in  [H]       input_linear_trans/bias
   layers[j] = {W_qkv [H, 3H]   layer_j/self_attention/qkv_transform/kernel    (q, k, v = columns [0,H), [H,2H), [2H,3H))
                b_qkv [3H]      .../qkv_transform/bias
@@ -35,7 +35,7 @@ _KEY_OF_LAYER = {v: k for k, v in _TF_LAYER.items()}
 def shapes(config):
     """({top key: shape}, {layer key: shape}) for `config` (an AttentionConfig)."""
     h, fi, c = config.hidden_size, config.feed_forward_inner_size, config.num_classes
-    k = config.n_mel * config.combine_frame
+    k = config.freq_size * config.combine_frame          # F = n_mel, or 3 * n_mfcc with config.mfcc (config/attention_config.py:97-99)
     top = {"W_in": (k, h), "b_in": (h,), "W_out": (h, c), "b_out": (c,)}
     layer = {"W_qkv": (h, 3 * h), "b_qkv": (3 * h,), "ln_a_beta": (h,), "ln_a_gamma": (h,), "W1": (h, fi), "b1": (fi,),
              "W2": (fi, h), "b2": (h,), "ln_b_beta": (h,), "ln_b_gamma": (h,)}

@@ -42,7 +42,9 @@ def get_config(**overrides):
 class AttentionConfig(Config):
     """The fields of config/attention_config.py the self-attention CTC model's inference reads (its defaults: n_mel 60 :67,
     use_relu :55, combine_frame :79, num_layers :80, feed_forward_inner_size :82, multi_head_num :84, hidden_size :85), and
-    max_frames: the longest utterance (mel frames) a DeployModel takes -- the size of its positional table."""
+    max_frames: the longest utterance (mel frames) a DeployModel takes -- the size of its positional table.
+    mfcc=True switches the in-graph front-end to utils/mfcc.py (models/attention_ctc.py:249-250): the model's input width
+    freq_size becomes 3 * n_mfcc."""
 
     def __init__(self, **overrides):
         self.label_dict = {"ni3": 1, "hao3": 2, "le4": 3}   # :26-27
@@ -50,7 +52,10 @@ class AttentionConfig(Config):
         self.fft_size = 400                                 # :59
         self.hop_size = 160                                 # :60
         self.samplerate = 16000                             # :61
+        self.mfcc = False                                   # :23
+        self.power = 1                                      # :63  (the deploy graph never reads it: |rfft|, or |rfft|^2 inside mfcc())
         self.n_mel = 60                                     # :67
+        self.n_mfcc = 20                                    # :66
         self.fmin = 300                                     # :64
         self.fmax = 8000                                    # :65
         self.use_relu = True                                # :55
@@ -64,6 +69,10 @@ class AttentionConfig(Config):
             if not hasattr(self, k):
                 raise AttributeError("unknown config key %r" % k)
             setattr(self, k, type(getattr(self, k))(v) if not isinstance(getattr(self, k), dict) else v)
+
+    @property
+    def freq_size(self):                                    # :97-99
+        return self.n_mfcc * 3 if self.mfcc else self.n_mel
 
 
 def get_attention_config(**overrides):

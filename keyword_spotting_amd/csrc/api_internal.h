@@ -265,4 +265,9 @@ struct kws_frontend {
     bool use_fft = false;
     int nf_tiles = 0, mel_tiles = 0, kc4 = 0;
     std::vector<float> basis;      // [n_mel][fft/2+1]
+    // kws_frontend_create_features: what the handle produces (kws_frontend_create: mel, power 1)
+    int kind = KWS_FEAT_MEL, power = 1, n_mfcc = 0, dct_tiles = 0;
+    size_t dct_off = 0;            // fft_frontend.hip: A fragments of D^T (MFCC only)
+    std::vector<float> dct;        // [n_mel][n_mfcc]
+    bool plain() const { return kind == KWS_FEAT_MEL && power == 1; }     // what the streaming paths take
 };

@@ -37,6 +37,19 @@ std::vector<float> slaney_mel_basis(int sr, int n_fft, int n_mels, double fmin, 
     return w;
 }
 
+// dct(n_filters, n_input) of utils/mfcc.py:33-42, already transposed as :42 returns it and cast as :93 does: the orthonormal
+// DCT-II basis [n_mel][n_mfcc] in float32
+std::vector<float> dct_basis_f32(int n_mfcc, int n_mel) {
+    const double pi = 3.14159265358979323846;
+    std::vector<float> d((size_t)n_mel * n_mfcc);
+    for (int j = 0; j < n_mel; ++j) {
+        const double sample = (2 * j + 1) * pi / (2.0 * n_mel);
+        d[(size_t)j * n_mfcc] = (float)(1.0 / std::sqrt((double)n_mel));
+        for (int i = 1; i < n_mfcc; ++i) d[(size_t)j * n_mfcc + i] = (float)(std::cos(i * sample) * std::sqrt(2.0 / n_mel));
+    }
+    return d;
+}
+
 // The label matcher of the incremental window: KMP automaton over emitted words, delta[q * 16 + w] = digits of the label
 // matched after reading word w (1..15) with q matched before (q < len); words the label does not contain lead to 0.
 void window_label_delta(const char* label, int n, uint8_t* delta) {
@@ -402,17 +415,39 @@ int kws_frontend_create(const kws_frontend_config* cfg, kws_frontend_handle* out
     if (!out) return fail(KWS_ERR_INVALID_ARGUMENT, "out handle pointer is null");
     *out = nullptr;
     if (!cfg) return fail(KWS_ERR_INVALID_ARGUMENT, "config is null");
+    const kws_feature_config fc = {*cfg, KWS_FEAT_MEL, 1, 0};
+    return kws_frontend_create_features(&fc, out);
+}
+
+size_t kws_sizeof_feature_config(void) { return sizeof(kws_feature_config); }
+
+int kws_frontend_create_features(const kws_feature_config* fcfg, kws_frontend_handle* out) {
+    if (!out) return fail(KWS_ERR_INVALID_ARGUMENT, "out handle pointer is null");
+    *out = nullptr;
+    if (!fcfg) return fail(KWS_ERR_INVALID_ARGUMENT, "config is null");
+    const kws_frontend_config* cfg = &fcfg->base;
     if (cfg->fft_size < 16 || cfg->fft_size > 496 || cfg->fft_size % 16 != 0)
         return fail(KWS_ERR_UNSUPPORTED, "fft_size=%d must be a multiple of 16 in [16,496] (the reference uses 400)", cfg->fft_size);
     if (cfg->hop_size < 1 || cfg->n_mel < 1 || cfg->n_mel > 64 || cfg->samplerate < 1)
         return fail(KWS_ERR_INVALID_ARGUMENT, "bad hop_size/n_mel/samplerate (%d/%d/%d)", cfg->hop_size, cfg->n_mel, cfg->samplerate);
     if (!(cfg->fmin >= 0.f) || !(cfg->fmax > cfg->fmin) || cfg->fmax > cfg->samplerate / 2.0f + 1e-3f)
         return fail(KWS_ERR_INVALID_ARGUMENT, "need 0 <= fmin < fmax <= sr/2");
+    const bool mfcc = fcfg->kind == KWS_FEAT_MFCC;
+    if (fcfg->kind != KWS_FEAT_MEL && !mfcc) return fail(KWS_ERR_INVALID_ARGUMENT, "kind=%d is neither KWS_FEAT_MEL nor KWS_FEAT_MFCC", fcfg->kind);
+    if (!mfcc && fcfg->power != 1 && fcfg->power != 2) return fail(KWS_ERR_INVALID_ARGUMENT, "power=%d must be 1 (|X|) or 2 (|X|^2)", fcfg->power);
+    if (mfcc && (fcfg->n_mfcc < 1 || fcfg->n_mfcc > std::min(cfg->n_mel, 32)))
+        return fail(KWS_ERR_INVALID_ARGUMENT, "n_mfcc=%d outside 1..min(n_mel, 32) = %d", fcfg->n_mfcc, std::min(cfg->n_mel, 32));
+    const char* dense_env = getenv("KWS_FRONTEND_DENSE");      // A/B switch: the dense-DFT kernel also handles 400
+    const bool dense400 = dense_env && dense_env[0] == '1';
+    if ((mfcc || fcfg->power == 2) && (cfg->fft_size != 400 || dense400))
+        return fail(KWS_ERR_UNSUPPORTED, "%s needs the 400-point FFT front-end: fft_size=%d%s unsupported (the dense-DFT kernel produces "
+                    "magnitude mel only)", mfcc ? "kind=KWS_FEAT_MFCC" : "power=2", cfg->fft_size, dense400 ? " with KWS_FRONTEND_DENSE=1" : "");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(KWS_ERR_NO_DEVICE, "no HIP device visible");
     kws_frontend* f = new (std::nothrow) kws_frontend();
     if (!f) return fail(KWS_ERR_OUT_OF_MEMORY, "host allocation failed");
     f->cfg = *cfg;
+    f->kind = fcfg->kind; f->power = mfcc ? 2 : fcfg->power; f->n_mfcc = mfcc ? fcfg->n_mfcc : 0;
     // frontend_kernels.hip: bins k = 0..N/4 are contracted, each over the even and the odd folded samples
     const int N = cfg->fft_size, NF = N / 2 + 1, NH = N / 2, NQ = N / 4, TILES = (NQ + 1 + 15) / 16, KC4 = TILES;
     f->kc4 = KC4;
@@ -491,8 +526,24 @@ int kws_frontend_create(const kws_frontend_config* cfg, kws_frontend_handle* out
                 }
             groups_total += stored;
         }
-        const char* dense = getenv("KWS_FRONTEND_DENSE");      // A/B switch: the dense-DFT kernel also handles 400
-        f->use_fft = !(dense && dense[0] == '1');
+        f->use_fft = !dense400;
+        if (mfcc) {
+            // D^T as the A operand of the DCT behind the mel MFMAs: the B operand is the mel tile's own C image, whose lane (g, f)
+            // holds filters 16 tile + 4g + e, so k-chunk e carries filters {4g + e}.  [tile][coefficient tile][64 lanes][e];
+            // rows of the padding filters >= n_mel stay zero (those lanes hold -100 dB)
+            f->dct = dct_basis_f32(f->n_mfcc, cfg->n_mel);
+            f->dct_tiles = (f->n_mfcc + 15) / 16;
+            f->dct_off = host.size();
+            host.resize(host.size() + (size_t)f->mel_tiles * f->dct_tiles * 64 * 4, 0.f);
+            for (int mt = 0; mt < f->mel_tiles; ++mt)
+                for (int ct = 0; ct < f->dct_tiles; ++ct)
+                    for (int lane = 0; lane < 64; ++lane)
+                        for (int e = 0; e < 4; ++e) {
+                            const int filt = 16 * mt + 4 * (lane >> 4) + e, c = 16 * ct + (lane & 15);
+                            if (filt < cfg->n_mel && c < f->n_mfcc)
+                                host[f->dct_off + (((size_t)mt * f->dct_tiles + ct) * 64 + lane) * 4 + e] = f->dct[(size_t)filt * f->n_mfcc + c];
+                        }
+        }
     }
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&f->d_tables), host.size() * sizeof(float));
     if (e != hipSuccess) { delete f; return hip_fail(e, "hipMalloc(frontend tables)"); }
@@ -522,12 +573,54 @@ int kws_frontend_mel_basis(kws_frontend_handle h, float* basis_host) {
 int kws_frontend_run(kws_frontend_handle h, const float* pcm, int B, int n_samples, float* mel, void* stream) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
     if (B < 0 || n_samples < 0) return fail(KWS_ERR_INVALID_ARGUMENT, "negative dimension");
+    if (!h->plain()) return kws_frontend_run_lengths(h, pcm, nullptr, B, n_samples, mel, stream);
     return frontend_run_impl(h, nullptr, 0, pcm, n_samples, B, mel, stream);
+}
+
+int kws_frontend_feature_size(kws_frontend_handle h) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    return h->kind == KWS_FEAT_MFCC ? 3 * h->n_mfcc : h->cfg.n_mel;
+}
+
+int kws_frontend_dct_basis(kws_frontend_handle h, float* basis_host) {
+    if (!h || !basis_host) return fail(KWS_ERR_INVALID_ARGUMENT, "null argument");
+    if (h->kind != KWS_FEAT_MFCC) return fail(KWS_ERR_INVALID_ARGUMENT, "the front-end has no DCT basis: its kind is KWS_FEAT_MEL");
+    memcpy(basis_host, h->dct.data(), h->dct.size() * sizeof(float));
+    return KWS_OK;
+}
+
+int kws_frontend_run_lengths(kws_frontend_handle h, const float* pcm, const int32_t* n_samples, int B, int n_max, float* out, void* stream) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    if (B < 0 || n_max < 0) return fail(KWS_ERR_INVALID_ARGUMENT, "negative dimension");
+    const int T = kws_frontend_frames(&h->cfg, n_max);
+    if (B == 0 || T == 0) return KWS_OK;
+    if (!pcm || !out) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
+    if (!(h->use_fft && h->cfg.fft_size == 400)) {
+        // (only a magnitude-mel handle gets here: the other kinds are refused at create)
+        if (!n_samples) return frontend_run_impl(h, nullptr, 0, pcm, n_max, B, out, stream);
+        return fail(KWS_ERR_UNSUPPORTED, "per-utterance n_samples need the 400-point FFT front-end (fft_size=%d%s)", h->cfg.fft_size,
+                    h->cfg.fft_size == 400 ? ", KWS_FRONTEND_DENSE=1" : "");
+    }
+    if ((long long)B * T >= (1LL << 31)) return fail(KWS_ERR_UNSUPPORTED, "B*T_max=%lld frames exceed the grid limit", (long long)B * T);
+    kws::FrontendParams p = {};
+    p.pcm = pcm; p.carry = pcm; p.mel = out;
+    p.dft = h->d_tables + h->fft_tw_off; p.melw = h->d_tables + h->fft_mel_off;
+    p.n_samples = n_max; p.T = T; p.fft = h->cfg.fft_size; p.hop = h->cfg.hop_size; p.n_mel = h->cfg.n_mel;
+    p.nf_tiles = h->nf_tiles; p.mel_tiles = h->mel_tiles; p.kc4 = h->kc4; p.B = B;
+    for (int m = 0; m < 4; ++m) { p.mel_lo[m] = h->mel_lo[m]; p.mel_cnt[m] = h->mel_cnt[m]; p.mel_off[m] = h->mel_off[m]; }
+    p.lens = n_samples; p.n_max = n_max;
+    p.power = h->power; p.n_mfcc = h->n_mfcc; p.dct_tiles = h->dct_tiles; p.dct = h->n_mfcc ? h->d_tables + h->dct_off : nullptr;
+    const hipError_t e = kws::launch_features_fft400(p, B, static_cast<hipStream_t>(stream));
+    if (e != hipSuccess) return hip_fail(e, "launch features_fft400");
+    return KWS_OK;
 }
 
 int kws_frontend_run_carry(kws_frontend_handle h, const float* carry, int n_carry, const float* chunk, int n_chunk, int B,
                            float* mel, float* next_carry, int n_next, void* stream) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    if (!h->plain())
+        return fail(KWS_ERR_UNSUPPORTED, "kws_frontend_run_carry streams magnitude mel only: this front-end has %s (MFCC deltas need the whole "
+                    "utterance; use kws_frontend_run_lengths)", h->kind == KWS_FEAT_MFCC ? "kind=KWS_FEAT_MFCC" : "power=2");
     if (B < 0 || n_carry < 0 || n_chunk < 0 || n_next < 0) return fail(KWS_ERR_INVALID_ARGUMENT, "negative dimension");
     if (n_next > n_carry + n_chunk) return fail(KWS_ERR_INVALID_ARGUMENT, "n_next=%d exceeds the %d available samples", n_next, n_carry + n_chunk);
     if (n_next > 0 && !next_carry) return fail(KWS_ERR_INVALID_ARGUMENT, "next_carry is null");
@@ -554,6 +647,9 @@ int kws_stream_create(kws_handle model, kws_frontend_handle frontend, kws_window
     if (!model || !frontend || !window || !state || !restart || !label) return fail(KWS_ERR_INVALID_ARGUMENT, "null argument");
     const unsigned long long ms = live_serial(model), fs = live_serial(frontend), ws = live_serial(window);
     if (!ms || !fs || !ws) return fail(KWS_ERR_INVALID_ARGUMENT, "model, front-end or window handle is not alive (destroyed, or not a handle)");
+    if (!frontend->plain())
+        return fail(KWS_ERR_UNSUPPORTED, "kws_stream_create takes a magnitude-mel front-end only: this one has %s (the reference's streaming "
+                    "detector has no MFCC branch)", frontend->kind == KWS_FEAT_MFCC ? "kind=KWS_FEAT_MFCC" : "power=2");
     if (B < 1 || max_chunk_samples < 1) return fail(KWS_ERR_INVALID_ARGUMENT, "bad stream shape B=%d max_chunk_samples=%d", B, max_chunk_samples);
     const int n = (int)strlen(label);
     if (n > 15) return fail(KWS_ERR_INVALID_ARGUMENT, "label longer than 15 digits (the incremental window's matcher has 16 states)");

@@ -3,6 +3,10 @@
 //   linearspec = |rfft(frames, 400)|          models/rnn_ctc.py:137
 //   melspec = linearspec @ mel_basis^T        models/rnn_ctc.py:139-149
 // (frontend_kernels.hip keeps the dense-DFT kernel for every other frame length.)
+// The same transform also serves the reference's other features of whole utterances (kws_frontend_run_lengths; the Utterances tag below):
+//   power mel        |rfft|^2 @ mel_basis^T                                          reader.py:267-268
+//   MFCC + deltas    10 log10(max(1e-10, |rfft|^2 @ mel_basis^T)) @ dct, [c | d/2 | 0.3 d]    utils/mfcc.py:20-99
+// with the log and the DCT fused behind the mel MFMAs (the mel C tile is the DCT's B operand) and the deltas in a second small launch.
 //
 // 400 = 16 x 25, n = 16 n1 + n2, k = k1 + 25 k2 (Cooley-Tukey):
 //     X[k1 + 25 k2] = sum_{n2<16} W16^{n2 k2} * ( W400^{n2 k1} * Y_{n2}[k1] ),   Y_{n2}[k1] = sum_{n1<25} x[16 n1 + n2] W25^{n1 k1}
@@ -84,6 +88,9 @@ constexpr int kPlaneBytes = 16 * kRowBytes;    // one k1: 16 frames
 constexpr int kFftLds = 13 * kPlaneBytes;      // 26,624 B per workgroup: six workgroups per CU
 constexpr int kMelRegs = 24;                   // basis fragments (4-bin groups) of a mel tile that wait in registers
 constexpr int kSpecRows = 208;                 // spectrum rows (bins 0..200 + zero padding) of 16 frames: 13,312 B of the same space
+constexpr int kMaxDctTiles = 2;                // MFCC: coefficient tiles of 16 (n_mfcc <= 32, kws_amd.h); the mel tiles' partial
+                                               // products [4 tiles][kMaxDctTiles][64 lanes] float4 sit behind the spectrum
+static_assert(kSpecRows * 64 + 4 * kMaxDctTiles * 64 * 16 <= kFftLds, "the DCT partials must fit behind the spectrum");
 
 }  // namespace
 
@@ -105,9 +112,20 @@ constexpr int kSpecRows = 208;                 // spectrum rows (bins 0..200 + z
 // frames past a stream's own count load nothing and store zeros.  See ragged_gate below for what the gate writes.  (A tag on
 // the sample type rather than a fourth template parameter: the lock-step instantiations keep their names and their code.)
 template <typename S> struct RaggedRows {};
+// Utterances<S, EPI> in place of the sample type S (without GATE; kws_frontend_run_lengths): B whole utterances in rows of
+// p.n_max samples, utterance b with its own sample count (p.lens, null: n_max for all) and so its own frame count T_b <= p.T;
+// frames past T_b load nothing.  EPI picks what leaves the kernel (kws_feature_config; utils/mfcc.py:72-99, reader.py:267-268):
+//   kEpiMel    |X| -> mel, as the plain instantiations
+//   kEpiPower  |X|^2 = re^2 + im^2 (no sqrt) -> mel
+//   kEpiMfcc   |X|^2 -> mel -> 10 log10(max(1e-10, .)) -> DCT: the static coefficients [c < n_mfcc] of rows of 3 n_mfcc floats;
+//              rows past T_b are zero.  mfcc_delta_kernel below fills the other two thirds of every row.
+// (A tag again: the mel instantiations above keep their names and their code.)
+constexpr int kEpiMel = 0, kEpiPower = 1, kEpiMfcc = 2;
+template <typename S, int EPI> struct Utterances {};
 namespace {
-template <typename T> struct SampleOf { using type = T; static constexpr bool ragged = false; };
-template <typename S> struct SampleOf<RaggedRows<S>> { using type = S; static constexpr bool ragged = true; };
+template <typename T> struct SampleOf { using type = T; static constexpr bool ragged = false, lengths = false; static constexpr int epi = kEpiMel; };
+template <typename S> struct SampleOf<RaggedRows<S>> { using type = S; static constexpr bool ragged = true, lengths = false; static constexpr int epi = kEpiMel; };
+template <typename S, int EPI> struct SampleOf<Utterances<S, EPI>> { using type = S; static constexpr bool ragged = false, lengths = true; static constexpr int epi = EPI; };
 
 __device__ __forceinline__ int ragged_len(const FrontendParams& p, unsigned b) {      // clamped to [0, n_max] (kws_amd.h)
     const int n = p.lens ? p.lens[b] : p.n_max;
@@ -144,7 +162,10 @@ template <int MT, typename SampleTag, bool GATE>
 __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const FrontendParams p) {
     using SampleT = typename SampleOf<SampleTag>::type;
     constexpr bool RAGGED = SampleOf<SampleTag>::ragged;
+    constexpr bool LENGTHS = SampleOf<SampleTag>::lengths;
+    constexpr int EPI = SampleOf<SampleTag>::epi;
     static_assert(GATE || !RAGGED, "the ragged feed always carries the gate");
+    static_assert(!(GATE && LENGTHS), "whole utterances have no stream gate");
     __shared__ __attribute__((aligned(16))) char lds[kFftLds];
     const int tid = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -257,7 +278,18 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
         const unsigned sb = fidx / (unsigned)p.T;
         const int st = (int)(fidx - sb * (unsigned)p.T);
         float x[25];
-        if constexpr (RAGGED) {
+        if constexpr (LENGTHS) {
+            // utterance sb: the first n samples of its row; a live frame (st < T_b) ends before sample n, a dead one loads nothing
+            const bool live = st < ragged_frames(p, ragged_len(p, sb));
+            const SampleT* src = chunk_all + (size_t)sb * p.n_max + (st * p.hop + n2);
+            if (!live) {
+#pragma unroll
+                for (int n1 = 0; n1 < 25; ++n1) x[n1] = 0.f;
+            } else {
+#pragma unroll
+                for (int n1 = 0; n1 < 25; ++n1) x[n1] = (float)src[16 * n1] * kScale;
+            }
+        } else if constexpr (RAGGED) {
             const int s0 = st * p.hop + n2;
             // stream sb: carry row (nc samples) followed by its n new samples; frames past its own count are dead: no loads, zeros
             const int n = ragged_len(p, sb), nc = ragged_carry(p, sb);
@@ -414,7 +446,10 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
             bfly4(u[0][3], v1, v2, v3, o[3], o[7], o[11], o[15]);
         }
 #pragma unroll
-        for (int k2 = 0; k2 < 16; ++k2) mag[k2] = __builtin_amdgcn_sqrtf(fmaf(o[k2].re, o[k2].re, o[k2].im * o[k2].im));
+        for (int k2 = 0; k2 < 16; ++k2) {
+            if constexpr (EPI == kEpiMel) mag[k2] = __builtin_amdgcn_sqrtf(fmaf(o[k2].re, o[k2].re, o[k2].im * o[k2].im));
+            else mag[k2] = fmaf(o[k2].re, o[k2].re, o[k2].im * o[k2].im);            // utils/mfcc.py:77: the power spectrum itself
+        }
     }
     // basis fragments of this wave's mel tile: the first kMelRegs groups of its run wait in registers (the loads fly while the
     // spectrum is written and the workgroup meets at the barrier); a longer run streams the rest
@@ -453,10 +488,12 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
 
     // ---- mel projection: wave m = mel tile m over its contiguous run of 4-bin groups.  A = basis fragments
     // [tile][group][64 lanes], B = four spectrum rows (k = g) x 16 frames; two accumulators break the dependent chain ----
+    // (kEpiMfcc: every tile takes part in the DCT, one without a weight -- n == 0 -- with mel = 0)
+    const bool project = EPI == kEpiMfcc ? w < MT : n > 0;
 #ifdef KWS_ABL_NOMEL          // experiment builds only (tools/build_variant.sh nomel -DKWS_ABL_NOMEL): the kernel without its mel projection
-    if (n > 0 && p.n_mel < 0) {
+    if (project && p.n_mel < 0) {
 #else
-    if (n > 0) {
+    if (project) {
 #endif
         const float* Sg = S + lo4 * 64 + lane;
         f32x4 acc0 = splat4(0.f), acc1 = splat4(0.f);
@@ -482,7 +519,27 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
         const f32x4 r = acc0 + acc1;
         // D[filter 16w + 4g + e][frame f]
         const unsigned fo = f0 + f;
-        if (fo < total) {
+        if constexpr (EPI == kEpiMfcc) {
+            // This C tile is also the B operand of the DCT (k = g <-> filter 16w + 4g + e in k-chunk e), as the GRU kernels'
+            // exchange layout: S = 10 log10(max(1e-10, mel)) (utils/mfcc.py:23; v_log_f32 is log2, operands >= 1e-10: no
+            // denormals) goes straight back into the matrix pipe against D^T packed the same way (p.dct: [tile][coefficient
+            // tile][64 lanes] float4 over e; rows of filters >= n_mel are zero -- those lanes hold log(floor) = -100 dB, not 0).
+            // The tiles' partial products meet in the half of LDS the spectrum does not use.
+            constexpr float kDbPerLog2 = 3.0102999566398120f;           // 10 log10(2)
+            float s[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) s[e] = __builtin_amdgcn_logf(fmaxf(r[e], 1e-10f)) * kDbPerLog2;
+            f32x4* part = reinterpret_cast<f32x4*>(lds + kSpecRows * 64);
+            for (int ct = 0; ct < p.dct_tiles; ++ct) {
+                const f32x4 d = reinterpret_cast<const f32x4*>(p.dct)[(size_t)(w * p.dct_tiles + ct) * 64 + lane];
+                f32x4 c0 = splat4(0.f), c1 = splat4(0.f);
+                c0 = mfma4(d[0], s[0], c0);
+                c1 = mfma4(d[1], s[1], c1);
+                c0 = mfma4(d[2], s[2], c0);
+                c1 = mfma4(d[3], s[3], c1);
+                part[(w * kMaxDctTiles + ct) * 64 + lane] = c0 + c1;
+            }
+        } else if (fo < total) {
             float* out = p.mel + (size_t)fo * p.n_mel;
             const int c0 = 16 * w + 4 * g;
             if ((p.n_mel & 3) == 0 && (reinterpret_cast<uintptr_t>(p.mel) & 15) == 0) {
@@ -494,7 +551,54 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
             }
         }
     }
+    if constexpr (EPI == kEpiMfcc) {
+        // wave ct adds the tiles' partial products, always in tile order, and stores coefficients 16 ct + 4g + e of frame f:
+        // the static third of the row, zero for a frame past its utterance's own count
+        lds_barrier();
+        if (w < p.dct_tiles) {
+            const f32x4* part = reinterpret_cast<const f32x4*>(lds + kSpecRows * 64);
+            f32x4 c = part[w * 64 + lane];
+#pragma unroll
+            for (int m = 1; m < MT; ++m) c = c + part[(m * kMaxDctTiles + w) * 64 + lane];
+            const unsigned fo = f0 + f;
+            if (fo < total) {
+                const unsigned sb = fo / (unsigned)p.T;
+                const bool live = (int)(fo - sb * (unsigned)p.T) < ragged_frames(p, ragged_len(p, sb));
+                float* out = p.mel + (size_t)fo * (3 * p.n_mfcc);
+                const int c0 = 16 * w + 4 * g;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+                    if (c0 + e < p.n_mfcc) out[c0 + e] = live ? c[e] : 0.f;
+            }
+        }
+    }
     KWS_FE_STAMP(7);
+}
+
+// The delta thirds of the MFCC rows (utils/mfcc.py:45-69,96-99), in place behind the launch above: with
+// d[t] = c[min(t + 1, T_b - 1)] - c[max(t - 1, 0)] (_delta_order shifts by one frame whatever its order, and only scales by it),
+// columns [n_mfcc, 2 n_mfcc) = d / 2 and [2 n_mfcc, 3 n_mfcc) = (1 d + 2 d) / 10.  The edges are the utterance's own T_b; rows past
+// it are zero.  One thread per (frame, coefficient): n_mfcc reads of neighbours in L2, 2 n_mfcc writes per frame.
+__global__ void __launch_bounds__(256) mfcc_delta_kernel(const FrontendParams p) {
+    const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
+    const unsigned nc = (unsigned)p.n_mfcc;
+    const unsigned long long row = i / nc;
+    if (row >= (unsigned long long)p.B * (unsigned)p.T) return;
+    const unsigned c = (unsigned)(i - row * nc);
+    const unsigned b = (unsigned)(row / (unsigned)p.T);
+    const int t = (int)(row - (unsigned long long)b * (unsigned)p.T);
+    const int tb = ragged_frames(p, ragged_len(p, b));
+    float* out = p.mel + (size_t)row * (3 * nc);
+    float d1 = 0.f, d2 = 0.f;
+    if (t < tb) {
+        const float* u = p.mel + (size_t)b * p.T * (3 * nc) + c;
+        const int tn = t + 1 < tb ? t + 1 : tb - 1, tp = t > 0 ? t - 1 : 0;
+        const float d = u[(size_t)tn * (3 * nc)] - u[(size_t)tp * (3 * nc)];
+        d1 = d / 2.f;
+        d2 = (d + 2.f * d) / 10.f;
+    }
+    out[nc + c] = d1;
+    out[2 * nc + c] = d2;
 }
 
 template <typename SampleT, bool GATE>
@@ -506,6 +610,34 @@ static hipError_t launch_fft400_tiles(const FrontendParams& p, unsigned grid, hi
         case 4: hipLaunchKernelGGL((mel_fft400_kernel<4, SampleT, GATE>), dim3(grid), dim3(256), 0, st, p); break;
         default: return hipErrorInvalidValue;
     }
+    return hipGetLastError();
+}
+
+template <int EPI>
+static hipError_t launch_features_tiles(const FrontendParams& p, unsigned grid, hipStream_t st) {
+    switch (p.mel_tiles) {
+        case 1: hipLaunchKernelGGL((mel_fft400_kernel<1, Utterances<float, EPI>, false>), dim3(grid), dim3(256), 0, st, p); break;
+        case 2: hipLaunchKernelGGL((mel_fft400_kernel<2, Utterances<float, EPI>, false>), dim3(grid), dim3(256), 0, st, p); break;
+        case 3: hipLaunchKernelGGL((mel_fft400_kernel<3, Utterances<float, EPI>, false>), dim3(grid), dim3(256), 0, st, p); break;
+        case 4: hipLaunchKernelGGL((mel_fft400_kernel<4, Utterances<float, EPI>, false>), dim3(grid), dim3(256), 0, st, p); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_features_fft400(const FrontendParams& p, int B, hipStream_t st) {
+    const long long total = (long long)B * p.T;        // 0 < total < 2^31 (checked by the caller)
+    if (p.fft != 400 || p.gate || p.pcm_i16 || p.n_carry != 0) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)(((total + 15) / 16 + 7) / 8 * 8);
+    FrontendParams q = p;
+    q.fft_blocks = (int)grid;
+    q.B = B;
+    if (p.n_mfcc == 0) return p.power == 2 ? launch_features_tiles<kEpiPower>(q, grid, st) : launch_features_tiles<kEpiMel>(q, grid, st);
+    if (p.n_mfcc > 16 * kMaxDctTiles || p.dct_tiles != (p.n_mfcc + 15) / 16 || !p.dct) return hipErrorInvalidValue;
+    hipError_t e = launch_features_tiles<kEpiMfcc>(q, grid, st);
+    if (e != hipSuccess) return e;
+    const unsigned long long cells = (unsigned long long)total * (unsigned)p.n_mfcc;       // < 2^36
+    hipLaunchKernelGGL(mfcc_delta_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, q);
     return hipGetLastError();
 }
 

@@ -323,10 +323,17 @@ struct FrontendParams {
     int32_t* frames;          // [B] out: frames of stream b in this chunk
     uint8_t* skip;            // [B] out: 1 = empty chunk, the iteration is skipped for this stream
     int n_max, carry_stride;  // row stride of the new samples / of carry (floats)
+    // fft_frontend.hip, whole utterances of their own lengths (launch_features_fft400; kws_frontend_run_lengths): rows of n_max samples,
+    // lens as above, T = frames of n_max samples.  n_mfcc > 0: mel is [B, T, 3 n_mfcc] (utils/mfcc.py:72-99)
+    const float* dct;         // [mel_tiles][dct_tiles][64 lanes][4]  A fragments of D^T: lane (g, i), component e = D[filter 16 tile + 4g + e][16 ct + i]
+    int n_mfcc, dct_tiles;    // coefficients (0: mel output), ceil(n_mfcc / 16)
+    int power;                // mel output: 1 = |X|, 2 = |X|^2
 };
 hipError_t launch_mel_frontend(const FrontendParams& p, int B, hipStream_t st);
 // fft 400 only (fft_frontend.hip): p.dft = twiddles [12][16] (cos, sin), p.melw = basis fragments [tile][group of its run][64]
 hipError_t launch_mel_fft400(const FrontendParams& p, int B, hipStream_t st);      // honours p.pcm_i16 and p.gate
+// ... B whole utterances with per-utterance lengths -> mel (p.power) or MFCC + deltas (p.n_mfcc > 0: two launches); float PCM, no gate
+hipError_t launch_features_fft400(const FrontendParams& p, int B, hipStream_t st);
 hipError_t launch_carry_tail(const float* carry, int n_carry, const float* chunk, int n_chunk, float* next, int n_next, int B,
                              hipStream_t st);
 

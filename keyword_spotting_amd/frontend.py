@@ -1,5 +1,7 @@
 """MelFrontend -- the in-graph audio front-end of models/rnn_ctc.py:134-149 on the GPU (kws_frontend_*):
-tf_frame(400, 160) -> |rfft(., 400)| -> matmul with librosa.filters.mel(...)^T, power 1, no window."""
+tf_frame(400, 160) -> |rfft(., 400)| -> matmul with librosa.filters.mel(...)^T, power 1, no window.
+MfccFrontend -- the config.mfcc branch of models/attention_ctc.py:249-250 (utils/mfcc.py:72-99): the same frames -> |rfft|^2 -> mel
+-> dB -> DCT -> [c | delta | delta-delta], a whole-utterance transform (kws_frontend_create_features / kws_frontend_run_lengths)."""
 import ctypes
 
 import numpy as np
@@ -73,3 +75,59 @@ class MelFrontend(object):
             _lib.check(self._lib.kws_frontend_run_carry(self._handle, _lib.ptr(carry) if nc else None, nc, _lib.ptr(chunk), n, b,
                                                         _lib.ptr(mel), _lib.ptr(nxt), int(n_next), _lib.current_stream_ptr()))
         return mel, nxt
+
+
+class MfccFrontend(object):
+    """utils/mfcc.py:mfcc on B utterances of their own lengths: features [B, T_max, 3 * n_mfcc], rows past an utterance's own
+    frame count zero, its delta edges at its own last frame."""
+
+    def __init__(self, config, device="cuda:0"):
+        self.config = config
+        self.device = torch.device(device)
+        self._lib = _lib.load()
+        self._cfg = _lib.KwsFeatureConfig(_lib.KwsFrontendConfig(int(config.samplerate), int(config.fft_size), int(config.hop_size),
+                                                                 int(config.n_mel), float(config.fmin), float(config.fmax)),
+                                          _lib.FEAT_MFCC, 2, int(config.n_mfcc))
+        self._handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_frontend_create_features(ctypes.byref(self._cfg), ctypes.byref(self._handle)))
+
+    close = MelFrontend.close
+    __del__ = MelFrontend.__del__
+    mel_basis = MelFrontend.mel_basis
+
+    @property
+    def feature_size(self):
+        return int(self._lib.kws_frontend_feature_size(self._handle))
+
+    def num_frames(self, n_samples):
+        return int(self._lib.kws_frontend_frames(ctypes.byref(self._cfg.base), int(n_samples)))
+
+    def dct_basis(self):
+        """[n_mel, n_mfcc] fp32 -- utils/mfcc.py:dct(n_mfcc, n_mel) as the graph casts it (:93)."""
+        out = np.empty((self.config.n_mel, self.config.n_mfcc), np.float32)
+        _lib.check(self._lib.kws_frontend_dct_basis(self._handle, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def forward(self, pcm, n_samples=None):
+        """pcm [B,N] (or [N]) float, n_samples [B] int32 or None (= N for all) -> features [B,T,3*n_mfcc] (or [T,3*n_mfcc]) on
+        the device, T = num_frames(N)."""
+        x = torch.as_tensor(pcm)
+        if x.dtype != torch.float32:
+            x = x.to(torch.float32)
+        single = x.dim() == 1
+        if single:
+            x = x.unsqueeze(0)
+        if x.dim() != 2:
+            raise _lib.InvalidArgumentError(-1, "expected signal to have rank 2 but was %d" % x.dim())
+        x = x.to(self.device).contiguous()
+        b, n = int(x.shape[0]), int(x.shape[1])
+        if n_samples is not None:
+            n_samples = torch.as_tensor(n_samples).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(n_samples.shape) != (b,):
+                raise _lib.InvalidArgumentError(-1, "n_samples must be [%d]" % b)
+        out = torch.empty(b, self.num_frames(n), 3 * int(self.config.n_mfcc), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_frontend_run_lengths(self._handle, _lib.ptr(x), _lib.ptr(n_samples), b, n, _lib.ptr(out),
+                                                          _lib.current_stream_ptr()))
+        return out[0] if single else out

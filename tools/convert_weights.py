@@ -13,6 +13,7 @@ kws_create_wrapped takes.  The residual has no variables: say so with the flag, 
 --model attention: the self-attention CTC model (models/attention_ctc.py, main.py --model attention) -> the blob
 kws_attention_create takes (model.blob only).  Dump tf.trainable_variables() there: every variable must be one of the model's
 (keyword_spotting_amd/attention_weights.py), none may be missing.  Shape flags default to config/attention_config.py.
+--mfcc [--n-mfcc 20]: the checkpoint was trained on MFCC features (config.mfcc: input_linear_trans takes 3 * n_mfcc per frame).
 """
 import argparse, os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -31,12 +32,14 @@ ap.add_argument("--residual", action="store_true", help="ResidualWrapper on laye
 ap.add_argument("--combine-frame", type=int, default=2, help="attention: frames stacked per row")
 ap.add_argument("--heads", type=int, default=8, help="attention: multi_head_num")
 ap.add_argument("--ffn-inner", type=int, default=512, help="attention: feed_forward_inner_size")
+ap.add_argument("--mfcc", action="store_true", help="attention: trained with config.mfcc (input width 3 * n_mfcc instead of n_mel)")
+ap.add_argument("--n-mfcc", type=int, default=20, help="attention with --mfcc: config.n_mfcc")
 a = ap.parse_args()
 if a.model == "attention":
     from keyword_spotting_amd import attention_weights
     from keyword_spotting_amd.config import get_attention_config
     cfg = get_attention_config(n_mel=a.n_mel or 60, hidden_size=a.hidden, num_layers=a.layers or 3, combine_frame=a.combine_frame,
-                               multi_head_num=a.heads, feed_forward_inner_size=a.ffn_inner)
+                               multi_head_num=a.heads, feed_forward_inner_size=a.ffn_inner, mfcc=a.mfcc, n_mfcc=a.n_mfcc)
     z = np.load(a.src)
     try:
         blob = attention_weights.to_blob(cfg, attention_weights.from_tf_variables(cfg, {k: z[k] for k in z.files}))
