@@ -1,5 +1,6 @@
-// Host-side state and helpers shared by the C ABI translation units of libkws_amd.so (api_*.hip, weight_pack.hip,
-// selftest.hip).  Never included by a kernel file: the kernel/host surface is kws_internal.h.
+// Host-side state and helpers shared by the C ABI translation units of libkws_amd.so: one api_*.hip per surface (model, step, ops,
+// attention, window, frontend, stream; the last drives the two before it through kws_host), weight_pack.hip, selftest.hip.  Never
+// included by a kernel file: the kernel/host surface is kws_internal.h.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -48,6 +49,9 @@ struct BusyGuard {
         hipError_t e_ = (call);                               \
         if (e_ != hipSuccess) return kws_host::hip_fail(e_, #call); \
     } while (0)
+// ... the same for a call that returns a KWS code, and a launcher's hipError_t as one (KWS_OK, or hip_fail(e, what))
+#define KWS_TRY(call) do { const int rc_ = (call); if (rc_ != KWS_OK) return rc_; } while (0)
+inline int hip_done(hipError_t e, const char* what) { return e == hipSuccess ? KWS_OK : hip_fail(e, what); }
 
 // The canonical weight blob (kws_weights_nbytes): per layer Wg [(in+H), 2H], bg [2H], Wc [(in+H), H], bc [H]; then
 // Wfc [H, C] and bfc [C].  Offsets in floats, from the config alone.
@@ -116,6 +120,26 @@ int step_impl(kws_handle h, const StepArgs& a);
 bool step_takes_window(kws_handle h, int B, int T, int window_chunks);
 int call_enter(kws_handle h, hipStream_t st);
 int call_leave(kws_handle h, hipStream_t st);
+
+// api_window.hip: the one label rule (digits 1..9, else the error); the n digits go to `digits` as numbers when it is given
+int label_digits(const char* label, int n, int32_t* digits);
+// ... the LDS one incremental window step over chunks of T frames needs, and what a workgroup may hold
+size_t window_inc_lds_bytes(int T, int nq);
+constexpr size_t kWindowIncLdsMax = 160 * 1024;
+// ... binds `label` to the window's incremental state (the queued summaries are label-specific)
+int window_bind_label(kws_window* w, const char* label);
+// ... the incremental window as kernel arguments: of window_inc_kernel, or of the tail of a GRU launch (StepArgs::wt)
+kws::WindowTail window_tail_params(kws_window* w, const uint8_t* clear_before, int32_t* hit, uint8_t* restart);
+
+// api_frontend.hip: the 400-point FFT kernel takes a launch of B x T frames (else the dense-DFT kernel, which has magnitude mel only)
+bool frontend_takes_fft400(const kws_frontend* h, int B, int T);
+// ... the refusal of `what` ("per-stream chunk lengths") on a handle whose launches go to the dense-DFT kernel
+int frontend_needs_fft400(const kws_frontend* h, const char* what);
+// ... `seed` (or zeros) with everything that comes from the handle and the call shape; the samples, lengths and outputs are the caller's
+kws::FrontendParams frontend_params(const kws_frontend* h, bool fft400, int B, int T, const kws::FrontendParams* seed = nullptr);
+// ... mel of [carry | chunk]; `gate` (FFT kernel only): its gate fields ride along -- pcm_i16 (read in place of chunk), vad, masks, next carry
+int frontend_run_impl(kws_frontend_handle h, const float* carry, int n_carry, const float* chunk, int n_chunk, int B, float* mel,
+                      void* stream, const kws::FrontendParams* gate = nullptr);
 
 }  // namespace kws_host
 #pragma GCC visibility pop
@@ -237,37 +261,31 @@ struct kws_stream {
     // of fft - 1 floats; the lengths ping-pong with the samples.
     bool ragged = false;
     int32_t* carry_len[2] = {nullptr, nullptr};   // [B] each
-    // one chunk's intermediates, carved out of the MODEL handle's staging block (kws_model::stage) at every feed:
-    size_t off_pcm_f32 = 0;          // [B, max_chunk]  int16 input widened here (front-ends other than the 400-point FFT, sub-frame chunks)
-    size_t off_mel = 0;              // [B, tmax, n_mel]
-    size_t off_softmax = 0;          // [B, tmax, C]
-    size_t off_silent = 0;           // [B]
-    size_t off_reset = 0;            // [B]
-    size_t off_frames = 0;           // [B] int32  frames of each stream's chunk (ragged feed)
-    size_t off_skip = 0;             // [B]        empty chunk: iteration skipped (ragged feed)
+    // one chunk's intermediates, carved out of the MODEL handle's staging block (kws_model::stage) at every feed by stream_carve
+    // (api_stream.hip), which also sizes them at kws_stream_create:
     size_t stage_bytes = 0;
-    // the pointers of the current feed
-    float* pcm_f32 = nullptr;
-    float* mel = nullptr;
-    float* softmax = nullptr;
-    uint8_t* silent = nullptr;
-    uint8_t* reset = nullptr;
-    int32_t* frames = nullptr;
-    uint8_t* skip = nullptr;
+    float* pcm_f32 = nullptr;        // [B, max_chunk]  int16 input widened here (front-ends other than the 400-point FFT, sub-frame chunks)
+    float* mel = nullptr;            // [B, tmax, n_mel]
+    float* softmax = nullptr;        // [B, tmax, C]
+    uint8_t* silent = nullptr;       // [B]
+    uint8_t* reset = nullptr;        // [B]
+    int32_t* frames = nullptr;       // [B] int32  frames of each stream's chunk (ragged feed)
+    uint8_t* skip = nullptr;         // [B]        empty chunk: iteration skipped (ragged feed)
 };
 
 struct kws_frontend {
     kws_frontend_config cfg;
+    // kws_frontend_create_features: what the handle produces (kws_frontend_create: mel, power 1)
+    int kind = KWS_FEAT_MEL, power = 1, n_mfcc = 0;
+    bool plain() const { return kind == KWS_FEAT_MEL && power == 1; }     // what the streaming paths take
+    // pack_frontend_tables (api_frontend.hip): the kernel tables in the one device allocation (offsets in floats), and the two bases
     float* d_tables = nullptr;
-    size_t dft_off = 0, melw_off = 0;
+    size_t dft_off = 0, melw_off = 0;         // frontend_kernels.hip tables (every fft_size)
     size_t fft_tw_off = 0, fft_mel_off = 0;   // fft_frontend.hip tables (fft_size 400 only)
     int mel_lo[4] = {0, 0, 0, 0}, mel_cnt[4] = {0, 0, 0, 0}, mel_off[4] = {0, 0, 0, 0};
-    bool use_fft = false;
-    int nf_tiles = 0, mel_tiles = 0, kc4 = 0;
+    bool use_fft = false;          // fft_size 400 without KWS_FRONTEND_DENSE=1
+    int nf_tiles = 0, mel_tiles = 0, kc4 = 0, dct_tiles = 0;
     std::vector<float> basis;      // [n_mel][fft/2+1]
-    // kws_frontend_create_features: what the handle produces (kws_frontend_create: mel, power 1)
-    int kind = KWS_FEAT_MEL, power = 1, n_mfcc = 0, dct_tiles = 0;
     size_t dct_off = 0;            // fft_frontend.hip: A fragments of D^T (MFCC only)
     std::vector<float> dct;        // [n_mel][n_mfcc]
-    bool plain() const { return kind == KWS_FEAT_MEL && power == 1; }     // what the streaming paths take
 };

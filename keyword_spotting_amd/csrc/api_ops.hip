@@ -42,10 +42,7 @@ int kws_ctc_predict(const int32_t* words, const int32_t* counts, int B, int max_
     const int n = (int)strlen(label);
     if (n > 16) return fail(KWS_ERR_INVALID_ARGUMENT, "label longer than 16 digits");
     int32_t digits[16] = {0};
-    for (int i = 0; i < n; ++i) {
-        if (label[i] < '1' || label[i] > '9') return fail(KWS_ERR_INVALID_ARGUMENT, "label must be digits 1..9, got '%s'", label);
-        digits[i] = label[i] - '0';
-    }
+    KWS_TRY(label_digits(label, n, digits));
     if (B < 0 || max_words < 0) return fail(KWS_ERR_INVALID_ARGUMENT, "negative dimension");
     if (B == 0) return KWS_OK;
     if (!counts || !hit || (!words && max_words > 0)) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");

@@ -10,16 +10,19 @@ import torch
 from . import _lib
 
 
-class MelFrontend(object):
-    def __init__(self, config, device="cuda:0"):
+class _Frontend(object):
+    """What the two front-ends share: the handle and its lifetime, the mel basis, the PCM normalisation."""
+
+    def __init__(self, config, device, create, features=None):
         self.config = config
         self.device = torch.device(device)
         self._lib = _lib.load()
-        self._cfg = _lib.KwsFrontendConfig(int(config.samplerate), int(config.fft_size), int(config.hop_size),
-                                           int(config.n_mel), float(config.fmin), float(config.fmax))
+        self._base = _lib.KwsFrontendConfig(int(config.samplerate), int(config.fft_size), int(config.hop_size),
+                                            int(config.n_mel), float(config.fmin), float(config.fmax))
+        self._cfg = self._base if features is None else _lib.KwsFeatureConfig(self._base, *features)
         self._handle = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_frontend_create(ctypes.byref(self._cfg), ctypes.byref(self._handle)))
+            _lib.check(getattr(self._lib, create)(ctypes.byref(self._cfg), ctypes.byref(self._handle)))
 
     def close(self):
         if getattr(self, "_handle", None) is not None and self._handle.value:
@@ -33,7 +36,7 @@ class MelFrontend(object):
             pass
 
     def num_frames(self, n_samples):
-        return int(self._lib.kws_frontend_frames(ctypes.byref(self._cfg), int(n_samples)))
+        return int(self._lib.kws_frontend_frames(ctypes.byref(self._base), int(n_samples)))
 
     def mel_basis(self):
         """[n_mel, fft/2+1] fp32 -- librosa.filters.mel layout (the graph uses its transpose)."""
@@ -41,8 +44,8 @@ class MelFrontend(object):
         _lib.check(self._lib.kws_frontend_mel_basis(self._handle, out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
-    def forward(self, pcm):
-        """pcm [B,N] (or [N]) float -> mel [B,T,n_mel] (or [T,n_mel]) on the device."""
+    def _pcm(self, pcm):
+        """pcm [B,N] (or [N]) -> (contiguous float32 [B,N] on the device, B, N, whether it was [N])."""
         x = torch.as_tensor(pcm)
         if x.dtype != torch.float32:
             x = x.to(torch.float32)
@@ -51,8 +54,16 @@ class MelFrontend(object):
             x = x.unsqueeze(0)
         if x.dim() != 2:
             raise _lib.InvalidArgumentError(-1, "expected signal to have rank 2 but was %d" % x.dim())
-        x = x.to(self.device).contiguous()
-        b, n = int(x.shape[0]), int(x.shape[1])
+        return x.to(self.device).contiguous(), int(x.shape[0]), int(x.shape[1]), single
+
+
+class MelFrontend(_Frontend):
+    def __init__(self, config, device="cuda:0"):
+        super(MelFrontend, self).__init__(config, device, "kws_frontend_create")
+
+    def forward(self, pcm):
+        """pcm [B,N] (or [N]) float -> mel [B,T,n_mel] (or [T,n_mel]) on the device."""
+        x, b, n, single = self._pcm(pcm)
         t = self.num_frames(n)
         mel = torch.empty(b, t, self.config.n_mel, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
@@ -77,31 +88,16 @@ class MelFrontend(object):
         return mel, nxt
 
 
-class MfccFrontend(object):
+class MfccFrontend(_Frontend):
     """utils/mfcc.py:mfcc on B utterances of their own lengths: features [B, T_max, 3 * n_mfcc], rows past an utterance's own
     frame count zero, its delta edges at its own last frame."""
 
     def __init__(self, config, device="cuda:0"):
-        self.config = config
-        self.device = torch.device(device)
-        self._lib = _lib.load()
-        self._cfg = _lib.KwsFeatureConfig(_lib.KwsFrontendConfig(int(config.samplerate), int(config.fft_size), int(config.hop_size),
-                                                                 int(config.n_mel), float(config.fmin), float(config.fmax)),
-                                          _lib.FEAT_MFCC, 2, int(config.n_mfcc))
-        self._handle = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_frontend_create_features(ctypes.byref(self._cfg), ctypes.byref(self._handle)))
-
-    close = MelFrontend.close
-    __del__ = MelFrontend.__del__
-    mel_basis = MelFrontend.mel_basis
+        super(MfccFrontend, self).__init__(config, device, "kws_frontend_create_features", (_lib.FEAT_MFCC, 2, int(config.n_mfcc)))
 
     @property
     def feature_size(self):
         return int(self._lib.kws_frontend_feature_size(self._handle))
-
-    def num_frames(self, n_samples):
-        return int(self._lib.kws_frontend_frames(ctypes.byref(self._cfg.base), int(n_samples)))
 
     def dct_basis(self):
         """[n_mel, n_mfcc] fp32 -- utils/mfcc.py:dct(n_mfcc, n_mel) as the graph casts it (:93)."""
@@ -112,16 +108,7 @@ class MfccFrontend(object):
     def forward(self, pcm, n_samples=None):
         """pcm [B,N] (or [N]) float, n_samples [B] int32 or None (= N for all) -> features [B,T,3*n_mfcc] (or [T,3*n_mfcc]) on
         the device, T = num_frames(N)."""
-        x = torch.as_tensor(pcm)
-        if x.dtype != torch.float32:
-            x = x.to(torch.float32)
-        single = x.dim() == 1
-        if single:
-            x = x.unsqueeze(0)
-        if x.dim() != 2:
-            raise _lib.InvalidArgumentError(-1, "expected signal to have rank 2 but was %d" % x.dim())
-        x = x.to(self.device).contiguous()
-        b, n = int(x.shape[0]), int(x.shape[1])
+        x, b, n, single = self._pcm(pcm)
         if n_samples is not None:
             n_samples = torch.as_tensor(n_samples).to(device=self.device, dtype=torch.int32).contiguous()
             if tuple(n_samples.shape) != (b,):
