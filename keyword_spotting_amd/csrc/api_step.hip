@@ -1,6 +1,7 @@
 // C ABI of libkws_amd.so (include/kws_amd.h): kws_step -- launch selection, the seam arenas, profiling slots, the launches.
 
 #include "api_internal.h"
+#include "launch.h"
 
 using namespace kws_host;
 
@@ -25,7 +26,7 @@ bool pipeline_eligible(kws_handle h, int B) {
     if ((h->cfg.precision != KWS_FP32 && !f16_streaming) || h->cfg.num_layers < 2 || h->kernel_kind == KWS_KERNEL_RESIDENT) return false;
     for (const auto& L : h->pk.layers)
         if (is_resident(h, L)) return false;
-    const long long groups = (B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup;
+    const long long groups = kws::groups_of(B);
     return h->num_cus > 0 && groups * h->cfg.num_layers <= h->num_cus;
 }
 
@@ -37,7 +38,7 @@ bool overlap_shape_ok(kws_handle h, int B, int T) {      // step_overlapped, lea
     const kws_config& c = h->cfg;
     if (c.precision != KWS_FP32 || c.num_layers < 2 || c.num_layers > 5) return false;
     if (pipeline_eligible(h, B)) return false;            // the streaming kernel has its own in-kernel pipeline
-    const long long groups = (B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup;
+    const long long groups = kws::groups_of(B);
     return h->num_cus > 0 && groups * c.num_layers <= h->num_cus && T >= KWS_OVERLAP_MIN_T;
 }
 bool overlap_eligible(kws_handle h, int B, int T) { return !h->profiling && overlap_shape_ok(h, B, T); }
@@ -54,7 +55,7 @@ constexpr int kNoFineGrainedMemory = 1;      // carve_seams: internal, never ret
 enum { kLayoutSequential = 0, kLayoutOverlapped = 1 };
 SeamLayout seam_layout(kws_handle h, int B, int T, int which) {
     const kws_config& c = h->cfg;
-    const size_t groups = (size_t)(B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup;
+    const size_t groups = (size_t)kws::groups_of(B);
     const size_t frame_bytes = groups * (size_t)c.hidden * 16 * sizeof(float);
     SeamLayout s = {0, 0, false};
     if (c.precision == KWS_BF16 || T <= 0 || B <= 0) return s;                    // the bf16 stack has no seam
@@ -102,7 +103,7 @@ int carve_seams(kws_handle h, const SeamLayout& want) {
 
 // Everything besides the seams that depends on the batch size: int8 exchange buffers, the pipelined launch's counters.
 int ensure_side_buffers(kws_handle h, int B) {
-    const size_t groups = (size_t)(B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup;
+    const size_t groups = (size_t)kws::groups_of(B);
     if (h->cfg.precision == KWS_INT8 && groups > h->oct_groups) {
         KWS_HIP(hipDeviceSynchronize());
         if (h->oct_aq) hipFree(h->oct_aq);
@@ -197,7 +198,17 @@ void set_epilogue(kws::GruLayerParams& p, const StepArgs& a, const kws_config& c
     if (frames) { p.t_stride = a.T; p.t_base = t0; }
     if (a.wt && last) p.win = *a.wt;
 }
-// ... and the frame counters of layer l in a layer-pipelined launch
+// Head of a layer-pipelined launch (GruStackParams / GruF16StackParams): the frame counters cleared on the call's stream,
+// the stack's shape and block map
+template <typename Stack>
+int begin_pipelined(const kws_model* h, Stack& sp, int B, hipStream_t st) {
+    const int L = h->cfg.num_layers;
+    KWS_HIP(hipMemsetAsync(h->pipe_ready, 0, (size_t)L * h->pipe_groups * sizeof(int), st));
+    memset(&sp, 0, sizeof(sp));
+    sp.L = L; sp.G = kws::groups_of(B); sp.xcd_affine = kws::pipelined_xcd_affine(L);
+    return KWS_OK;
+}
+// ... and the frame counters of layer l in it
 void set_pipeline(kws::GruLayerParams& p, const kws_model* h, int l, bool last) {
     p.ready_in = l == 0 ? nullptr : h->pipe_ready + (size_t)(l - 1) * h->pipe_groups;
     p.ready_out = last ? nullptr : h->pipe_ready + (size_t)l * h->pipe_groups;
@@ -370,11 +381,7 @@ int step_body(kws_handle h, const StepArgs& a) {
         // hidden = 256: weights streamed from L2; all L x groups workgroups in ONE layer-pipelined grid when they fit the chip
         const bool f16_pipelined = h->pk.f16_generic && pipeline_eligible(h, B);
         kws::GruF16StackParams fsp;
-        if (f16_pipelined) {
-            KWS_HIP(hipMemsetAsync(h->pipe_ready, 0, (size_t)L * h->pipe_groups * sizeof(int), st));
-            memset(&fsp, 0, sizeof(fsp));
-            fsp.L = L; fsp.G = (B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup; fsp.xcd_affine = (8 % L == 0) ? 1 : 0;
-        }
+        if (f16_pipelined && (rc = begin_pipelined(h, fsp, B, st)) != KWS_OK) return rc;
         for (int l = 0; l < L; ++l) {
             const bool first = l == 0, last = l == L - 1;
             kws::GruF16Params fp;
@@ -428,13 +435,8 @@ int step_body(kws_handle h, const StepArgs& a) {
         KWS_HIP(hipMemcpyAsync(h->oct_prev, a.prev_word, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
     // layer-pipelined launch (gru_stack_generic_pipelined): all layers of all groups in one grid
     const bool pipelined = pipeline_eligible(h, B);
-    const int groups = (B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup;
     kws::GruStackParams sp;
-    if (pipelined) {
-        KWS_HIP(hipMemsetAsync(h->pipe_ready, 0, (size_t)L * h->pipe_groups * sizeof(int), st));
-        memset(&sp, 0, sizeof(sp));
-        sp.L = L; sp.G = groups; sp.xcd_affine = (8 % L == 0) ? 1 : 0;
-    }
+    if (pipelined && (rc = begin_pipelined(h, sp, B, st)) != KWS_OK) return rc;
     for (int l = 0; l < L; ++l) {
         // int8: every GRU layer hands its output rows to the next stage through the xl scratch; the class
         // projection is its own OctbitMatMul call over the whole [T,H] block (launch_octbit_fc below)
@@ -522,7 +524,7 @@ bool kws_host::step_takes_window(kws_handle h, int B, int T, int window_chunks) 
     // that replaces a ~4 us launch of its own; in a persistent workgroup it would sit between two groups, on the critical
     // path once per group (measured, bf16, 16384 streams: 0.349-0.359 ms per chunk with the tail against 0.338-0.340 with
     // window_inc_kernel behind the stack)
-    if ((B + kws::kStreamsPerGroup - 1) / kws::kStreamsPerGroup > (h->num_cus > 0 ? h->num_cus : 256)) return false;
+    if (kws::groups_of(B) > (h->num_cus > 0 ? h->num_cus : 256)) return false;
     if (c.precision == KWS_BF16) return kws::gru_stack_bf16_takes_window(h->pk.bf_kx0, c.num_layers);
     if (c.precision == KWS_F16X3) return !h->pk.f16_generic;
     if (c.precision != KWS_FP32 || pipeline_eligible(h, B) || overlap_eligible(h, B, T)) return false;

@@ -18,6 +18,7 @@
 // the lane.  The running max / sum of a query therefore live in one lane column: no LDS round trip for P, and the rescale of
 // O by exp(m_old - m_new) is a per-lane scalar.
 #include "attention_internal.h"
+#include "launch.h"
 
 namespace kws {
 namespace {
@@ -405,86 +406,36 @@ __global__ __launch_bounds__(256) void attn_out_kernel(AttnParams p, const float
     }
 }
 
-namespace {
-
-template <class K, class... A>
-hipError_t launch(K kernel, LdsGrant* grant, size_t lds, dim3 grid, hipStream_t st, A... args) {
-    if (grant) {
-        const hipError_t e = grant_dynamic_lds(kernel, *grant, lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, args...);
-    return hipGetLastError();
-}
-
-template <int H>
-hipError_t embed_h(const AttnParams& p, hipStream_t st) {
-    static LdsGrant grant;
-    return launch(attn_embed_kernel<H>, &grant, (size_t)RT * (p.KE + 4) * sizeof(float), dim3(p.ntile, p.B), st, p);
-}
-template <int H>
-hipError_t qkv_h(const AttnParams& p, const AttnLayerW& w, const AttnLayerW* prev, hipStream_t st) {
-    if (prev) return launch(attn_qkv_kernel<H, true>, nullptr, 0, dim3(p.ntile, p.B), st, p, w, prev->gb, prev->bb);
-    return launch(attn_qkv_kernel<H, false>, nullptr, 0, dim3(p.ntile, p.B), st, p, w, (const float*)nullptr, (const float*)nullptr);
-}
-template <int H, int D>
-hipError_t core_hd(const AttnParams& p, const AttnLayerW* prev, hipStream_t st) {
-    static LdsGrant grant[2];
-    const size_t lds = (size_t)(RT * (H + 4) + H * (RT + 4)) * sizeof(float);
-    if (prev) return launch(attn_core_kernel<H, D, true>, &grant[1], lds, dim3(p.ntile, p.B), st, p, prev->gb, prev->bb);
-    return launch(attn_core_kernel<H, D, false>, &grant[0], lds, dim3(p.ntile, p.B), st, p, (const float*)nullptr, (const float*)nullptr);
-}
-
-}  // namespace
-
 hipError_t launch_attn_embed(const AttnParams& p, int H, hipStream_t st) {
-    switch (H) {
-        case 64: return embed_h<64>(p, st);
-        case 128: return embed_h<128>(p, st);
-        case 256: return embed_h<256>(p, st);
-    }
-    return hipErrorInvalidValue;
+    return with_int<64, 128, 256>(H, [&](auto h) {
+        return launch_lds<attn_embed_kernel<h()>>(dim3(p.ntile, p.B), dim3(256), (size_t)RT * (p.KE + 4) * sizeof(float), st, p);
+    });
 }
 hipError_t launch_attn_qkv(const AttnParams& p, const AttnLayerW& w, const AttnLayerW* prev, int H, hipStream_t st) {
-    switch (H) {
-        case 64: return qkv_h<64>(p, w, prev, st);
-        case 128: return qkv_h<128>(p, w, prev, st);
-        case 256: return qkv_h<256>(p, w, prev, st);
-    }
-    return hipErrorInvalidValue;
+    const float *gb = prev ? prev->gb : nullptr, *bb = prev ? prev->bb : nullptr;      // the layer norm of the layer below, fused in
+    return with_int<64, 128, 256>(H, [&](auto h) {
+        return with_bool(prev != nullptr, [&](auto ln) {
+            return launch_lds<attn_qkv_kernel<h(), ln()>>(dim3(p.ntile, p.B), dim3(256), 0, st, p, w, gb, bb);
+        });
+    });
 }
 hipError_t launch_attn_core(const AttnParams& p, const AttnLayerW* prev, int H, int D, hipStream_t st) {
-    if (D == 16) {
-        switch (H) {
-            case 64: return core_hd<64, 16>(p, prev, st);
-            case 128: return core_hd<128, 16>(p, prev, st);
-            case 256: return core_hd<256, 16>(p, prev, st);
-        }
-    } else if (D == 32) {
-        switch (H) {
-            case 64: return core_hd<64, 32>(p, prev, st);
-            case 128: return core_hd<128, 32>(p, prev, st);
-            case 256: return core_hd<256, 32>(p, prev, st);
-        }
-    }
-    return hipErrorInvalidValue;
+    const float *gb = prev ? prev->gb : nullptr, *bb = prev ? prev->bb : nullptr;
+    return with_int<16, 32>(D, [&](auto d) {
+        return with_int<64, 128, 256>(H, [&](auto h) {
+            const size_t lds = (size_t)(RT * (h() + 4) + h() * (RT + 4)) * sizeof(float);
+            return with_bool(prev != nullptr, [&](auto ln) {
+                return launch_lds<attn_core_kernel<h(), d(), ln()>>(dim3(p.ntile, p.B), dim3(256), lds, st, p, gb, bb);
+            });
+        });
+    });
 }
 hipError_t launch_attn_ffn(const AttnParams& p, const AttnLayerW& w, int H, hipStream_t st) {
-    switch (H) {
-        case 64: return launch(attn_ffn_kernel<64>, nullptr, 0, dim3(p.ntile, p.B), st, p, w);
-        case 128: return launch(attn_ffn_kernel<128>, nullptr, 0, dim3(p.ntile, p.B), st, p, w);
-        case 256: return launch(attn_ffn_kernel<256>, nullptr, 0, dim3(p.ntile, p.B), st, p, w);
-    }
-    return hipErrorInvalidValue;
+    return with_int<64, 128, 256>(H, [&](auto h) { return launch_lds<attn_ffn_kernel<h()>>(dim3(p.ntile, p.B), dim3(256), 0, st, p, w); });
 }
 hipError_t launch_attn_out(const AttnParams& p, const AttnLayerW& last, int H, hipStream_t st) {
     const dim3 grid((p.T1max + RT - 1) / RT, p.B);
-    switch (H) {
-        case 64: return launch(attn_out_kernel<64>, nullptr, 0, grid, st, p, last.gb, last.bb);
-        case 128: return launch(attn_out_kernel<128>, nullptr, 0, grid, st, p, last.gb, last.bb);
-        case 256: return launch(attn_out_kernel<256>, nullptr, 0, grid, st, p, last.gb, last.bb);
-    }
-    return hipErrorInvalidValue;
+    return with_int<64, 128, 256>(H, [&](auto h) { return launch_lds<attn_out_kernel<h()>>(grid, dim3(256), 0, st, p, last.gb, last.bb); });
 }
 
 }  // namespace kws

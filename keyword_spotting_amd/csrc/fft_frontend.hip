@@ -24,6 +24,7 @@
 #include <cstdlib>
 
 #include "gru_device.h"
+#include "launch.h"
 #include "vad_device.h"
 
 #pragma clang fp contract(off)      // only the fmaf() written below fuse: every frame sees one fixed instruction sequence
@@ -603,26 +604,13 @@ __global__ void __launch_bounds__(256) mfcc_delta_kernel(const FrontendParams p)
 
 template <typename SampleT, bool GATE>
 static hipError_t launch_fft400_tiles(const FrontendParams& p, unsigned grid, hipStream_t st) {
-    switch (p.mel_tiles) {
-        case 1: hipLaunchKernelGGL((mel_fft400_kernel<1, SampleT, GATE>), dim3(grid), dim3(256), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((mel_fft400_kernel<2, SampleT, GATE>), dim3(grid), dim3(256), 0, st, p); break;
-        case 3: hipLaunchKernelGGL((mel_fft400_kernel<3, SampleT, GATE>), dim3(grid), dim3(256), 0, st, p); break;
-        case 4: hipLaunchKernelGGL((mel_fft400_kernel<4, SampleT, GATE>), dim3(grid), dim3(256), 0, st, p); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return with_int<1, 2, 3, 4>(p.mel_tiles, [&](auto mt) {
+        return launch_lds<mel_fft400_kernel<mt(), SampleT, GATE>>(dim3(grid), dim3(256), 0, st, p);
+    });
 }
-
 template <int EPI>
 static hipError_t launch_features_tiles(const FrontendParams& p, unsigned grid, hipStream_t st) {
-    switch (p.mel_tiles) {
-        case 1: hipLaunchKernelGGL((mel_fft400_kernel<1, Utterances<float, EPI>, false>), dim3(grid), dim3(256), 0, st, p); break;
-        case 2: hipLaunchKernelGGL((mel_fft400_kernel<2, Utterances<float, EPI>, false>), dim3(grid), dim3(256), 0, st, p); break;
-        case 3: hipLaunchKernelGGL((mel_fft400_kernel<3, Utterances<float, EPI>, false>), dim3(grid), dim3(256), 0, st, p); break;
-        case 4: hipLaunchKernelGGL((mel_fft400_kernel<4, Utterances<float, EPI>, false>), dim3(grid), dim3(256), 0, st, p); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_fft400_tiles<Utterances<float, EPI>, false>(p, grid, st);
 }
 
 hipError_t launch_features_fft400(const FrontendParams& p, int B, hipStream_t st) {
@@ -637,8 +625,7 @@ hipError_t launch_features_fft400(const FrontendParams& p, int B, hipStream_t st
     hipError_t e = launch_features_tiles<kEpiMfcc>(q, grid, st);
     if (e != hipSuccess) return e;
     const unsigned long long cells = (unsigned long long)total * (unsigned)p.n_mfcc;       // < 2^36
-    hipLaunchKernelGGL(mfcc_delta_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, q);
-    return hipGetLastError();
+    return launch_lds<mfcc_delta_kernel>(dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, q);
 }
 
 hipError_t launch_mel_fft400(const FrontendParams& p, int B, hipStream_t st) {

@@ -21,6 +21,7 @@
 // mirrored set -- no transpose anywhere.  A further radix step (k, NQ-k, ...) would halve the matrix work again;
 // staging and the mel stage are now as expensive as the DFT itself.
 #include "gru_device.h"
+#include "launch.h"
 
 namespace kws {
 
@@ -259,20 +260,8 @@ __global__ void __launch_bounds__(256) carry_tail_kernel(const float* __restrict
 }
 hipError_t launch_carry_tail(const float* carry, int n_carry, const float* chunk, int n_chunk, float* next, int n_next, int B,
                              hipStream_t st) {
-    hipLaunchKernelGGL(carry_tail_kernel, dim3((n_next + 255) / 256 > 0 ? (n_next + 255) / 256 : 1, B), dim3(256), 0, st, carry, n_carry,
-                       chunk, n_chunk, next, n_next);
-    return hipGetLastError();
-}
-
-template <int UPW>
-static hipError_t launch_upw(const FrontendParams& p, unsigned grid, size_t lds, hipStream_t st) {
-    static LdsGrant granted;             // per kernel instantiation (one static per template instance) and device
-    {
-        const hipError_t e = grant_dynamic_lds(mel_frontend_kernel<UPW>, granted, lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(mel_frontend_kernel<UPW>, dim3(grid), dim3(256), lds, st, p);
-    return hipGetLastError();
+    return launch_lds<carry_tail_kernel>(dim3((n_next + 255) / 256 > 0 ? (n_next + 255) / 256 : 1, B), dim3(256), 0, st, carry, n_carry,
+                                         chunk, n_chunk, next, n_next);
 }
 
 hipError_t launch_mel_frontend(const FrontendParams& p, int B, hipStream_t st) {
@@ -282,17 +271,9 @@ hipError_t launch_mel_frontend(const FrontendParams& p, int B, hipStream_t st) {
     const size_t lds = windows > sums ? windows : sums;
     const long long total = (long long)B * p.T;
     const unsigned grid = (unsigned)((total + 16 * kFT - 1) / (16 * kFT));
-    switch (p.nf_tiles) {
-        case 1: return launch_upw<1>(p, grid, lds, st);
-        case 2: return launch_upw<2>(p, grid, lds, st);
-        case 3: return launch_upw<3>(p, grid, lds, st);
-        case 4: return launch_upw<4>(p, grid, lds, st);
-        case 5: return launch_upw<5>(p, grid, lds, st);
-        case 6: return launch_upw<6>(p, grid, lds, st);
-        case 7: return launch_upw<7>(p, grid, lds, st);
-        case 8: return launch_upw<8>(p, grid, lds, st);
-        default: return hipErrorInvalidValue;
-    }
+    return with_int<1, 2, 3, 4, 5, 6, 7, 8>(p.nf_tiles, [&](auto upw) {
+        return launch_lds<mel_frontend_kernel<upw()>>(dim3(grid), dim3(256), lds, st, p);
+    });
 }
 
 }  // namespace kws

@@ -17,6 +17,7 @@
 #include <cstddef>
 
 #include "gru_device.h"
+#include "launch.h"
 #include "window_device.h"
 
 namespace kws {
@@ -797,38 +798,13 @@ bool gru_bf16_supported(int hidden, int n_mel, int layers) {
 
 template <int KX0, int NL>
 static hipError_t launch_bf16(const GruBf16Params& p, hipStream_t st) {
-    const size_t lds = gru_bf16_lds_bytes(KX0, NL);
-    static LdsGrant granted;             // per kernel instantiation (one static per template instance) and device
-    {
-        const hipError_t e = grant_dynamic_lds(gru_stack_bf16<KX0, NL>, granted, lds);
-        if (e != hipSuccess) return e;
-    }
-    const int groups = (p.B + kStreamsPerGroup - 1) / kStreamsPerGroup;
-    hipLaunchKernelGGL((gru_stack_bf16<KX0, NL>), dim3(groups), dim3(256), lds, st, p);
-    return hipGetLastError();
+    return launch_lds<gru_stack_bf16<KX0, NL>>(dim3(groups_of(p.B)), dim3(256), gru_bf16_lds_bytes(KX0, NL), st, p);
 }
 
+// the 8-wave kernel loops over stream groups itself: one workgroup per CU at most
 template <int KX0, bool WINDOW = false>
 static hipError_t launch_bf16_ls(const GruBf16Params& p, hipStream_t st) {
-    const size_t lds = gru_bf16_ls_lds_bytes(KX0, WINDOW);
-    static LdsGrant granted;
-    {
-        const hipError_t e = grant_dynamic_lds(gru_stack_bf16_ls<KX0, WINDOW>, granted, lds);
-        if (e != hipSuccess) return e;
-    }
-    const int groups = (p.B + kStreamsPerGroup - 1) / kStreamsPerGroup;
-    int dev = 0, cus = 256;
-    hipDeviceProp_t prop;
-    static std::atomic<int> cu_cache[kMaxDevices];
-    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices) {
-        cus = cu_cache[dev].load(std::memory_order_relaxed);
-        if (cus <= 0) {
-            cus = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-            cu_cache[dev].store(cus, std::memory_order_relaxed);
-        }
-    }
-    hipLaunchKernelGGL((gru_stack_bf16_ls<KX0, WINDOW>), dim3(groups < cus ? groups : cus), dim3(512), lds, st, p);
-    return hipGetLastError();
+    return launch_lds<gru_stack_bf16_ls<KX0, WINDOW>>(dim3(persistent_grid(p.B)), dim3(512), gru_bf16_ls_lds_bytes(KX0, WINDOW), st, p);
 }
 
 static bool bf16_four_waves() {

@@ -1,4 +1,5 @@
-// Device helpers shared by the GRU kernels (fp32: gru_kernels.hip, bf16: gru_bf16.hip).
+// Device helpers shared by the GRU kernels (gru_kernels.hip, gru_bf16.hip, gru_f16x3.hip, gru_f16x3_generic.hip, gru_octbit.hip)
+// and the mel front-ends (frontend_kernels.hip, fft_frontend.hip).
 #pragma once
 #include <type_traits>
 

@@ -53,6 +53,7 @@
 #include <cstdlib>
 
 #include "gru_device.h"
+#include "launch.h"
 #include "window_device.h"
 
 namespace kws {
@@ -64,7 +65,7 @@ typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr float kLoScale = 2048.f, kLoInv = 1.f / 2048.f;
-constexpr float kMelScale = 1.f / 256.f;       // kws_api.hip multiplies the first layer's x-part weights by 256
+constexpr float kMelScale = 1.f / 256.f;       // weight_pack.hip multiplies the first layer's x-part weights by 256
 constexpr float kHalfMax = 65504.f;
 
 __device__ __forceinline__ f16x8 as_f16x8(u32x4 v) { return __builtin_bit_cast(f16x8, v); }
@@ -719,23 +720,6 @@ bool gru_f16x3_supported(int hidden, int n_mel) { return hidden == 128 && n_mel 
 
 template <int KX, bool FIRST, bool LAST, bool MASKED, bool WINDOW = false>
 static hipError_t launch_f16x3m(const GruF16Params& p, hipStream_t st) {
-    const size_t lds = gru_f16x3_lds_bytes(KX, FIRST, LAST, WINDOW);
-    static LdsGrant granted;
-    {
-        const hipError_t e = grant_dynamic_lds(gru_layer_f16x3<KX, FIRST, LAST, MASKED, WINDOW>, granted, lds);
-        if (e != hipSuccess) return e;
-    }
-    const int groups = (p.B + kStreamsPerGroup - 1) / kStreamsPerGroup;
-    int dev = 0, cus = 256;
-    hipDeviceProp_t prop;
-    static std::atomic<int> cu_cache[kMaxDevices];
-    if (hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < kMaxDevices) {
-        cus = cu_cache[dev].load(std::memory_order_relaxed);
-        if (cus <= 0) {
-            cus = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-            cu_cache[dev].store(cus, std::memory_order_relaxed);
-        }
-    }
 #ifdef KWS_F16_TIMING
     static long long* tbuf = nullptr;
     if (!tbuf) {
@@ -744,7 +728,9 @@ static hipError_t launch_f16x3m(const GruF16Params& p, hipStream_t st) {
         (void)hipMemcpyToSymbol(HIP_SYMBOL(g_timing), &tbuf, sizeof(tbuf));
     }
 #endif
-    hipLaunchKernelGGL((gru_layer_f16x3<KX, FIRST, LAST, MASKED, WINDOW>), dim3(groups < cus ? groups : cus), dim3(256), lds, st, p);
+    // the kernel loops over stream groups itself: one workgroup per CU at most
+    const hipError_t e = launch_lds<gru_layer_f16x3<KX, FIRST, LAST, MASKED, WINDOW>>(dim3(persistent_grid(p.B)), dim3(256),
+                                                                                      gru_f16x3_lds_bytes(KX, FIRST, LAST, WINDOW), st, p);
 #ifdef KWS_F16_TIMING
     if (getenv("KWS_F16_TIMING")) {
         (void)hipDeviceSynchronize();
@@ -759,14 +745,14 @@ static hipError_t launch_f16x3m(const GruF16Params& p, hipStream_t st) {
         fprintf(stderr, "\n");
     }
 #endif
-    return hipGetLastError();
+    return e;
 }
 
 // the copy-through past seq_len costs 16 VALU instructions per frame: its own instantiation, used only when lengths are given
 template <int KX, bool FIRST, bool LAST>
 static hipError_t launch_f16x3(const GruF16Params& p, hipStream_t st) {
     if constexpr (LAST) {
-        // the window tail exists without the length mask only: the stream manager never passes seq_len (kws_api.hip checks)
+        // the window tail exists without the length mask only: the stream manager never passes seq_len (step_impl in api_step.hip checks)
         if (p.epi.win.tab != nullptr) return p.seq_len ? hipErrorInvalidValue : launch_f16x3m<KX, FIRST, LAST, false, true>(p, st);
     }
     return p.seq_len ? launch_f16x3m<KX, FIRST, LAST, true>(p, st) : launch_f16x3m<KX, FIRST, LAST, false>(p, st);

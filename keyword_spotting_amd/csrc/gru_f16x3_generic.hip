@@ -21,6 +21,7 @@
 #include <cstddef>
 
 #include "gru_device.h"
+#include "launch.h"
 
 namespace kws {
 
@@ -444,57 +445,21 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 
 bool gru_f16x3_generic_supported(int hidden, int n_mel) { return (hidden == 128 || hidden == 256) && n_mel % 4 == 0 && n_mel >= 4 && n_mel <= 64; }
 
-constexpr size_t kF16GenericOneWorkgroupPerCuLds = 82 * 1024;      // > 160 KB / 2
-
-template <typename K>
-static hipError_t launch_f16g(K kernel, const GruF16Params& p, size_t lds, hipStream_t st) {
-    static LdsGrant granted;
-    {
-        const hipError_t e = grant_dynamic_lds(kernel, granted, lds);
-        if (e != hipSuccess) return e;
-    }
-    const int groups = (p.B + kStreamsPerGroup - 1) / kStreamsPerGroup;
-    hipLaunchKernelGGL(kernel, dim3(groups), dim3(256), lds, st, p);
-    return hipGetLastError();
-}
-
 hipError_t launch_gru_layer_f16x3_generic(const GruF16Params& p, int hidden, bool first, bool last, hipStream_t st) {
     if (p.T <= 0 || p.B <= 0) return hipSuccess;
     // one workgroup per CU (each wants the whole register file)
-    size_t lds = gru_f16x3_generic_lds_bytes(hidden, last);
-    if (lds < kF16GenericOneWorkgroupPerCuLds) lds = kF16GenericOneWorkgroupPerCuLds;
-#define KWS_F16G(TPW_) \
-    do { \
-        if (first && last) return launch_f16g(gru_layer_f16x3_generic<TPW_, true, true>, p, lds, st); \
-        if (first) return launch_f16g(gru_layer_f16x3_generic<TPW_, true, false>, p, lds, st); \
-        if (last) return launch_f16g(gru_layer_f16x3_generic<TPW_, false, true>, p, lds, st); \
-        return launch_f16g(gru_layer_f16x3_generic<TPW_, false, false>, p, lds, st); \
-    } while (0)
-    if (hidden == 128) KWS_F16G(2);
-    if (hidden == 256) KWS_F16G(4);
-#undef KWS_F16G
-    return hipErrorInvalidValue;
-}
-
-template <int TPW>
-static hipError_t launch_f16_pipelined(const GruF16StackParams& sp, size_t lds, hipStream_t st) {
-    static LdsGrant granted;
-    {
-        const hipError_t e = grant_dynamic_lds(gru_stack_f16x3_pipelined<TPW>, granted, lds);
-        if (e != hipSuccess) return e;
-    }
-    const int per = sp.xcd_affine ? 8 / sp.L : 0;
-    const int grid = sp.xcd_affine ? 8 * ((sp.G + per - 1) / per) : sp.G * sp.L;
-    hipLaunchKernelGGL(gru_stack_f16x3_pipelined<TPW>, dim3(grid), dim3(256), lds, st, sp);
-    return hipGetLastError();
+    const size_t lds = one_workgroup_per_cu(gru_f16x3_generic_lds_bytes(hidden, last));
+    return with_layer_shape<2, 4>(hidden, first, last, [&](auto tpw, auto fi, auto la) {
+        return launch_lds<gru_layer_f16x3_generic<tpw(), fi(), la()>>(dim3(groups_of(p.B)), dim3(256), lds, st, p);
+    });
 }
 
 hipError_t launch_gru_stack_f16x3_pipelined(const GruF16StackParams& sp, int hidden, hipStream_t st) {
-    size_t lds = gru_f16x3_generic_lds_bytes(hidden, true);
-    if (lds < kF16GenericOneWorkgroupPerCuLds) lds = kF16GenericOneWorkgroupPerCuLds;
-    if (hidden == 128) return launch_f16_pipelined<2>(sp, lds, st);
-    if (hidden == 256) return launch_f16_pipelined<4>(sp, lds, st);
-    return hipErrorInvalidValue;
+    const size_t lds = one_workgroup_per_cu(gru_f16x3_generic_lds_bytes(hidden, true));
+    const dim3 grid(pipelined_grid(sp.L, sp.G, sp.xcd_affine));
+    return with_tpw<2, 4>(hidden, [&](auto tpw) {
+        return launch_lds<gru_stack_f16x3_pipelined<tpw()>>(grid, dim3(256), lds, st, sp);
+    });
 }
 
 }  // namespace kws

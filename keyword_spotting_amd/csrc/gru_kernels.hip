@@ -21,6 +21,7 @@
 #include <cstddef>
 
 #include "gru_device.h"
+#include "launch.h"
 #include "window_device.h"
 
 namespace kws {
@@ -910,8 +911,6 @@ static size_t resident_lds_bytes(int kcx, bool first, bool last) {
     if (first) n += (size_t)64 * xs_stride(kcx) * 4;
     return n;
 }
-constexpr size_t kOneWorkgroupPerCuLds = 82 * 1024;      // > 160 KB / 2
-
 static size_t generic_lds_bytes(int hidden, bool last) {
     size_t n = (size_t)3 * (hidden / 16) * 64 * 16 + (size_t)3 * hidden * 4;
     if (last) n += kEpilogueLdsBytes;
@@ -929,87 +928,31 @@ bool gru_resident_supported(int hidden, int in_dim, bool first) {
     return in_dim == 32 || in_dim == 40 || in_dim == 48 || in_dim == 60 || in_dim == 64;
 }
 
-template <typename K>
-static hipError_t launch_with_lds(K kernel, const GruLayerParams& p, size_t lds, hipStream_t st) {
-    static LdsGrant granted;             // per kernel instantiation (one static per template instance) and device
-    {
-        const hipError_t e = grant_dynamic_lds(kernel, granted, lds);
-        if (e != hipSuccess) return e;
-    }
-    const int groups = (p.B + kStreamsPerGroup - 1) / kStreamsPerGroup;
-    hipLaunchKernelGGL(kernel, dim3(groups), dim3(256), lds, st, p);
-    return hipGetLastError();
-}
+bool gru_resident_takes_window(bool first, bool last) { return last && !first; }
 
 // the resident kernels loop over stream groups themselves: one workgroup per CU at most (each fills a CU's register file),
 // the weights staged once per workgroup however many groups it takes
-static int device_cu_count() {
-    static std::atomic<int> cached[kMaxDevices];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return 256;
-    int n = cached[dev].load(std::memory_order_relaxed);
-    if (n <= 0) {
-        hipDeviceProp_t prop;
-        n = hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        cached[dev].store(n, std::memory_order_relaxed);
-    }
-    return n;
-}
-template <typename K>
-static hipError_t launch_resident(K kernel, const GruLayerParams& p, size_t lds, hipStream_t st) {
-    static LdsGrant granted;
-    {
-        const hipError_t e = grant_dynamic_lds(kernel, granted, lds);
-        if (e != hipSuccess) return e;
-    }
-    const int groups = (p.B + kStreamsPerGroup - 1) / kStreamsPerGroup, cus = device_cu_count();
-    hipLaunchKernelGGL(kernel, dim3(groups < cus ? groups : cus), dim3(256), lds, st, p);
-    return hipGetLastError();
-}
-
-bool gru_resident_takes_window(bool first, bool last) { return last && !first; }
-
 hipError_t launch_gru_layer_resident(const GruLayerParams& p, bool first, bool last, hipStream_t st) {
     const size_t lds = resident_lds_bytes(p.KCX, first, last);
+    const dim3 grid(persistent_grid(p.B));
     if (p.win.tab != nullptr) {               // with the window tail: the last layer of a stack only
         if (!gru_resident_takes_window(first, last) || p.seq_len) return hipErrorInvalidValue;
-        return launch_resident(gru_layer_resident<32, false, true, true>, p, lds + kWinTailWordsBytes, st);
+        return launch_lds<gru_layer_resident<32, false, true, true>>(grid, dim3(256), lds + kWinTailWordsBytes, st, p);
     }
-#define KWS_RES(KCX_, F_, L_) return launch_resident(gru_layer_resident<KCX_, F_, L_>, p, lds, st)
-    if (first) {
-        if (p.KCX == 8) { if (last) KWS_RES(8, true, true); else KWS_RES(8, true, false); }
-        if (p.KCX == 10) { if (last) KWS_RES(10, true, true); else KWS_RES(10, true, false); }
-        if (p.KCX == 12) { if (last) KWS_RES(12, true, true); else KWS_RES(12, true, false); }
-        if (p.KCX == 15) { if (last) KWS_RES(15, true, true); else KWS_RES(15, true, false); }
-        if (p.KCX == 16) { if (last) KWS_RES(16, true, true); else KWS_RES(16, true, false); }
-        return hipErrorInvalidValue;
-    }
-    if (last) KWS_RES(32, false, true); else KWS_RES(32, false, false);
-#undef KWS_RES
-}
-
-template <int TPW>
-static hipError_t launch_pipelined(const GruStackParams& sp, size_t lds, hipStream_t st) {
-    static LdsGrant granted;             // per kernel instantiation (one static per template instance) and device
-    {
-        const hipError_t e = grant_dynamic_lds(gru_stack_generic_pipelined<TPW>, granted, lds);
-        if (e != hipSuccess) return e;
-    }
-    const int per = sp.xcd_affine ? 8 / sp.L : 0;
-    const int grid = sp.xcd_affine ? 8 * ((sp.G + per - 1) / per) : sp.G * sp.L;
-    hipLaunchKernelGGL(gru_stack_generic_pipelined<TPW>, dim3(grid), dim3(256), lds, st, sp);
-    return hipGetLastError();
+    return with_bool(last, [&](auto la) {
+        if (!first) return launch_lds<gru_layer_resident<32, false, la()>>(grid, dim3(256), lds, st, p);
+        return with_int<8, 10, 12, 15, 16>(p.KCX, [&](auto kcx) {
+            return launch_lds<gru_layer_resident<kcx(), true, la()>>(grid, dim3(256), lds, st, p);
+        });
+    });
 }
 
 hipError_t launch_gru_stack_generic_pipelined(const GruStackParams& sp, int hidden, hipStream_t st) {
-    // ask for more than half a CU's LDS: one workgroup per CU, so that the L x G workgroups spread over L x G CUs
-    // instead of doubling up on some of them
-    size_t lds = generic_lds_bytes(hidden, true);
-    if (lds < kOneWorkgroupPerCuLds) lds = kOneWorkgroupPerCuLds;
-    if (hidden == 64) return launch_pipelined<1>(sp, lds, st);
-    if (hidden == 128) return launch_pipelined<2>(sp, lds, st);
-    if (hidden == 256) return launch_pipelined<4>(sp, lds, st);
-    return hipErrorInvalidValue;
+    const size_t lds = one_workgroup_per_cu(generic_lds_bytes(hidden, true));
+    const dim3 grid(pipelined_grid(sp.L, sp.G, sp.xcd_affine));
+    return with_tpw<1, 2, 4>(hidden, [&](auto tpw) {
+        return launch_lds<gru_stack_generic_pipelined<tpw()>>(grid, dim3(256), lds, st, sp);
+    });
 }
 
 hipError_t launch_gru_layer_generic(const GruLayerParams& p, int hidden, bool first, bool last,
@@ -1018,74 +961,30 @@ hipError_t launch_gru_layer_generic(const GruLayerParams& p, int hidden, bool fi
     // a time block of an overlapped call (t_stride set): another layer's kernel runs beside this one on another stream;
     // keep one workgroup per CU or the dispatcher stacks both kernels onto the same CUs (measured: 2.2x slower each;
     // within ONE launch it spreads workgroups by itself, and padding then only costs occupancy when groups > CUs)
-    if (p.t_stride != 0 && lds < kOneWorkgroupPerCuLds) lds = kOneWorkgroupPerCuLds;
-#define KWS_GEN(TPW_) \
-    do { \
-        if (first && last) return launch_with_lds(gru_layer_generic<TPW_, true, true>, p, lds, st); \
-        if (first) return launch_with_lds(gru_layer_generic<TPW_, true, false>, p, lds, st); \
-        if (last) return launch_with_lds(gru_layer_generic<TPW_, false, true>, p, lds, st); \
-        return launch_with_lds(gru_layer_generic<TPW_, false, false>, p, lds, st); \
-    } while (0)
-    if (hidden == 64) KWS_GEN(1);
-    if (hidden == 128) KWS_GEN(2);
-    if (hidden == 256) KWS_GEN(4);
-#undef KWS_GEN
-    return hipErrorInvalidValue;
-}
-
-template <typename K>
-static hipError_t launch_wrapped_with_lds(K kernel, const GruLayerParams& p, const GruWrapLayer& wl, size_t lds, hipStream_t st) {
-    static LdsGrant granted;
-    {
-        const hipError_t e = grant_dynamic_lds(kernel, granted, lds);
-        if (e != hipSuccess) return e;
-    }
-    const int groups = (p.B + kStreamsPerGroup - 1) / kStreamsPerGroup;
-    hipLaunchKernelGGL(kernel, dim3(groups), dim3(256), lds, st, p, wl);
-    return hipGetLastError();
+    if (p.t_stride != 0) lds = one_workgroup_per_cu(lds);
+    return with_layer_shape<1, 2, 4>(hidden, first, last, [&](auto tpw, auto fi, auto la) {
+        return launch_lds<gru_layer_generic<tpw(), fi(), la()>>(dim3(groups_of(p.B)), dim3(256), lds, st, p);
+    });
 }
 
 hipError_t launch_gru_layer_generic_wrapped(const GruLayerParams& p, const GruWrapLayer& wl, int hidden, bool first, bool last,
                                             hipStream_t st) {
     // the epilogue area is carved whether or not the layer is the last: the normalised frame lies behind it
     size_t lds = generic_lds_bytes(hidden, true) + gru_wrapped_extra_lds(p.KCX / 4);
-    if (p.t_stride != 0 && lds < kOneWorkgroupPerCuLds) lds = kOneWorkgroupPerCuLds;     // as launch_gru_layer_generic
-#define KWS_GENW(TPW_) \
-    do { \
-        if (first && last) return launch_wrapped_with_lds(gru_layer_generic_wrapped<TPW_, true, true>, p, wl, lds, st); \
-        if (first) return launch_wrapped_with_lds(gru_layer_generic_wrapped<TPW_, true, false>, p, wl, lds, st); \
-        if (last) return launch_wrapped_with_lds(gru_layer_generic_wrapped<TPW_, false, true>, p, wl, lds, st); \
-        return launch_wrapped_with_lds(gru_layer_generic_wrapped<TPW_, false, false>, p, wl, lds, st); \
-    } while (0)
-    if (hidden == 64) KWS_GENW(1);
-    if (hidden == 128) KWS_GENW(2);
-    if (hidden == 256) KWS_GENW(4);
-#undef KWS_GENW
-    return hipErrorInvalidValue;
-}
-
-template <int TPW>
-static hipError_t launch_pipelined_wrapped(const GruStackParams& sp, const GruWrapParams& wp, size_t lds, hipStream_t st) {
-    static LdsGrant granted;
-    {
-        const hipError_t e = grant_dynamic_lds(gru_stack_generic_pipelined_wrapped<TPW>, granted, lds);
-        if (e != hipSuccess) return e;
-    }
-    const int per = sp.xcd_affine ? 8 / sp.L : 0;
-    const int grid = sp.xcd_affine ? 8 * ((sp.G + per - 1) / per) : sp.G * sp.L;
-    hipLaunchKernelGGL(gru_stack_generic_pipelined_wrapped<TPW>, dim3(grid), dim3(256), lds, st, sp, wp);
-    return hipGetLastError();
+    if (p.t_stride != 0) lds = one_workgroup_per_cu(lds);     // as launch_gru_layer_generic
+    return with_layer_shape<1, 2, 4>(hidden, first, last, [&](auto tpw, auto fi, auto la) {
+        return launch_lds<gru_layer_generic_wrapped<tpw(), fi(), la()>>(dim3(groups_of(p.B)), dim3(256), lds, st, p, wl);
+    });
 }
 
 hipError_t launch_gru_stack_generic_pipelined_wrapped(const GruStackParams& sp, const GruWrapParams& wp, int hidden, hipStream_t st) {
     int kx4 = 0;
     for (int l = 0; l < sp.L; ++l) kx4 = sp.layer[l].KCX / 4 > kx4 ? sp.layer[l].KCX / 4 : kx4;
-    size_t lds = generic_lds_bytes(hidden, true) + gru_wrapped_extra_lds(kx4);
-    if (lds < kOneWorkgroupPerCuLds) lds = kOneWorkgroupPerCuLds;        // one workgroup per CU, as the plain launch
-    if (hidden == 64) return launch_pipelined_wrapped<1>(sp, wp, lds, st);
-    if (hidden == 128) return launch_pipelined_wrapped<2>(sp, wp, lds, st);
-    if (hidden == 256) return launch_pipelined_wrapped<4>(sp, wp, lds, st);
-    return hipErrorInvalidValue;
+    const size_t lds = one_workgroup_per_cu(generic_lds_bytes(hidden, true) + gru_wrapped_extra_lds(kx4));     // as the plain launch
+    const dim3 grid(pipelined_grid(sp.L, sp.G, sp.xcd_affine));
+    return with_tpw<1, 2, 4>(hidden, [&](auto tpw) {
+        return launch_lds<gru_stack_generic_pipelined_wrapped<tpw()>>(grid, dim3(256), lds, st, sp, wp);
+    });
 }
 
 }  // namespace kws

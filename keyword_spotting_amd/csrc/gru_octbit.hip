@@ -26,6 +26,7 @@
 // s_load_dwordx16 (scalar cache, invalidated after each exchange); LDS cannot feed a uniform operand
 // without paying a full 64-lane return per read, which would make LDS the bound by 2.7x.
 #include "gru_device.h"
+#include "launch.h"
 
 namespace kws {
 namespace {
@@ -504,22 +505,16 @@ __global__ void __launch_bounds__(512) octbit_fc_kernel(const OctbitFcParams p) 
 size_t gru_octbit_lds_bytes() { return (size_t)(3 * 16 * kHS + 16384 + 32 + 32 + 16) * 4; }
 
 hipError_t launch_gru_layer_octbit(const GruOctbitParams& p, hipStream_t st) {
-    const int groups = (p.B + 15) / 16;
-    static LdsGrant granted;
-    {
-        const hipError_t e = grant_dynamic_lds(gru_layer_octbit_kernel, granted, gru_octbit_lds_bytes());
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL(gru_layer_octbit_kernel, dim3(groups), dim3(512), gru_octbit_lds_bytes(), st, p);
-    return hipGetLastError();
+    return launch_lds<gru_layer_octbit_kernel>(dim3(groups_of(p.B)), dim3(512), gru_octbit_lds_bytes(), st, p);
 }
 
 hipError_t launch_octbit_fc(const OctbitFcParams& p, hipStream_t st) {
-    const int groups = (p.B + 15) / 16;
-    if (!p.range_ready)          // top layer ran on the fp32 kernels (one-layer models): scan its rows
-        hipLaunchKernelGGL(octbit_top_range_kernel, dim3(groups), dim3(512), 0, st, p.h_top, p.T, p.range);
-    hipLaunchKernelGGL(octbit_fc_kernel, dim3(groups, (p.T + kFcFrames - 1) / kFcFrames), dim3(512), 0, st, p);
-    return hipGetLastError();
+    const int groups = groups_of(p.B);
+    if (!p.range_ready) {        // top layer ran on the fp32 kernels (one-layer models): scan its rows
+        const hipError_t e = launch_lds<octbit_top_range_kernel>(dim3(groups), dim3(512), 0, st, p.h_top, p.T, p.range);
+        if (e != hipSuccess) return e;
+    }
+    return launch_lds<octbit_fc_kernel>(dim3(groups, (p.T + kFcFrames - 1) / kFcFrames), dim3(512), 0, st, p);
 }
 
 }  // namespace kws

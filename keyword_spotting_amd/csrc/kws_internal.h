@@ -3,8 +3,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <atomic>
-
 #include "kws_amd.h"
 
 // Experiment / test switches compiled into the kernel sources (timing counters, ablations, the self-test's negative control).
@@ -54,27 +52,6 @@ namespace kws {
 
 constexpr int kStreamsPerGroup = 16;  // MFMA N dimension: one workgroup advances 16 streams
 constexpr int kMaxClasses = 8;
-
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-device property of a kernel: one process may drive several GPUs
-// (one handle each) from several host threads, so the "already granted" cache is per (kernel instantiation, device)
-// and atomic.  Setting the attribute twice is harmless; skipping it on a second device makes the launch fail there.
-constexpr int kMaxDevices = 64;
-struct LdsGrant { std::atomic<size_t> bytes[kMaxDevices]; };
-template <typename K>
-inline hipError_t grant_dynamic_lds(K kernel, LdsGrant& cache, size_t lds) {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    const bool cached = dev >= 0 && dev < kMaxDevices;
-    if (cached && cache.bytes[dev].load(std::memory_order_acquire) >= lds) return hipSuccess;
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    if (cached) {
-        size_t seen = cache.bytes[dev].load(std::memory_order_relaxed);
-        while (seen < lds && !cache.bytes[dev].compare_exchange_weak(seen, lds, std::memory_order_release)) {}
-    }
-    return hipSuccess;
-}
 
 // One launch = one GRU layer over all T frames of the call, for every 16-stream group.
 //

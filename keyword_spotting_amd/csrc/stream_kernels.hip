@@ -7,6 +7,7 @@
 //   * on trigger: clear the window and request a state reset (detector.py:202-208) -> restart[b] = 1
 // One wave per stream (window_step_kernel below).
 #include "kws_internal.h"
+#include "launch.h"
 #include "window_device.h"
 
 namespace kws {
@@ -166,30 +167,21 @@ __global__ void window_reset_kernel(int B, int* head, int* count) {
 }
 
 hipError_t launch_window_step(const WindowParams& p, hipStream_t st) {
-    hipLaunchKernelGGL(window_step_kernel, dim3(p.B), dim3(64), (size_t)2 * p.nq * p.tmax, st, p);
-    return hipGetLastError();
+    return launch_lds<window_step_kernel>(dim3(p.B), dim3(64), (size_t)2 * p.nq * p.tmax, st, p);
 }
 hipError_t launch_window_inc(const WindowIncParams& p, hipStream_t st) {
     const int stride = (p.T + 15) & ~15;
     const size_t lds = (size_t)16 * (stride > 0 ? stride : 16) + 256 + window_tail_scratch_bytes(p.win.nq);
-    static LdsGrant granted, granted_ragged;
-    if (lds > 48 * 1024) {
-        const hipError_t e = p.frames ? grant_dynamic_lds(window_inc_kernel<true>, granted_ragged, lds)
-                                      : grant_dynamic_lds(window_inc_kernel<false>, granted, lds);
-        if (e != hipSuccess) return e;
-    }
-    if (p.frames) hipLaunchKernelGGL(window_inc_kernel<true>, dim3((p.B + 15) / 16), dim3(256), lds, st, p);
-    else hipLaunchKernelGGL(window_inc_kernel<false>, dim3((p.B + 15) / 16), dim3(256), lds, st, p);
-    return hipGetLastError();
+    return with_bool(p.frames != nullptr, [&](auto ragged) {
+        return launch_lds<window_inc_kernel<ragged()>>(dim3(groups_of(p.B)), dim3(256), lds, st, p);
+    });
 }
 hipError_t launch_stream_recycle(const StreamRecycleParams& p, hipStream_t st) {
     if (p.B < 1) return hipSuccess;
-    hipLaunchKernelGGL(stream_recycle_kernel, dim3(p.B), dim3(64), 0, st, p);
-    return hipGetLastError();
+    return launch_lds<stream_recycle_kernel>(dim3(p.B), dim3(64), 0, st, p);
 }
 hipError_t launch_window_reset(int B, int* head, int* count, hipStream_t st) {
-    hipLaunchKernelGGL(window_reset_kernel, dim3((B + 63) / 64), dim3(64), 0, st, B, head, count);
-    return hipGetLastError();
+    return launch_lds<window_reset_kernel>(dim3((B + 63) / 64), dim3(64), 0, st, B, head, count);
 }
 
 }  // namespace kws
