@@ -275,6 +275,37 @@ int kws_frontend_run_lengths(kws_frontend_handle h, const float* pcm /*[B, n_max
 /* Copies the fp32 DCT basis [n_mel, n_mfcc] (host memory) of an MFCC handle -- for inspection/tests. */
 int kws_frontend_dct_basis(kws_frontend_handle h, float* basis_host);
 
+/* The features the reference's models are trained and validated on (process_wav.py:38-44,69-78 -> reader.py:264-269; the same
+ * framing in server_demo.py:59-82): |librosa.stft(y, 400, 160)| instead of the deploy graph's un-windowed, un-padded frames, in
+ * front of the same kws_feature_config.  For one utterance x[0..n) of float32 samples, h = hop_size, c = pre_emphasis:
+ *   y[0] = x[0], y[i] = x[i] - fl32(c * x[i-1])     only if c != 0 (config.pre_emphasis: 0.97); float32, multiply and subtract
+ *                                                   rounded separately, as numpy does it
+ *   T(n) = 1 + n / h for n >= 201, 0 for n <= 200   center=True: frame t is centred on sample h t
+ *   frame t, tap i in [0, 400): s = h t + i - 200; s < 0: s = -s; s >= n: s = 2 (n - 1) - s; frame[i] = y[s] * w[i]
+ *                                                   np.pad(y, 200, mode='reflect'): one reflection at most for n >= 201
+ *   w[i] = 0.5 - 0.5 cos(2 pi i / 400)              the periodic Hann window (scipy.signal.get_window('hann', 400)), float32
+ *   |rfft(frame, 400)| -> what cfg.feat says: mel of |X| or |X|^2, or MFCC + deltas with the delta edges at T(n_b)
+ * np.pad's REPEATED reflection of a signal shorter than the pad (n <= 200) is deliberately not reproduced: such an utterance has no
+ * frames.  fft_size = 400 and the FFT kernel only (KWS_ERR_UNSUPPORTED otherwise, naming the field; KWS_FRONTEND_DENSE=1 included).
+ * {feat, KWS_FRAMES_DEPLOY, 0} is kws_frontend_create_features(&feat) exactly; KWS_FRAMES_DEPLOY with pre_emphasis != 0, a framing
+ * outside the enum, or a pre_emphasis that is not finite or outside [0, 1) is KWS_ERR_INVALID_ARGUMENT.
+ * A dataset handle runs through kws_frontend_run_lengths (kws_frontend_run forwards to it): out is [B, T(n_max), feature_size],
+ * rows t >= T(n_b) are written as 0, samples at or past n_b are never read into a result (the reflection reads indices < n_b
+ * only); one launch for mel output, two for MFCC.  Centred frames need the utterance's end: kws_frontend_run_carry and
+ * kws_stream_create (so every stream feed) refuse a dataset handle with KWS_ERR_UNSUPPORTED.
+ * kws_frontend_frames_of is the handle's own frame count of n_samples -- the deploy rule (kws_frontend_frames, which keeps its
+ * meaning) or T(n) above.  kws_frontend_window copies the 400 float32 window values (host memory) of a dataset handle. */
+enum { KWS_FRAMES_DEPLOY = 0, KWS_FRAMES_DATASET = 1 };
+typedef struct kws_dataset_config {
+    kws_feature_config feat;
+    int32_t framing;            /* KWS_FRAMES_DEPLOY | KWS_FRAMES_DATASET */
+    float pre_emphasis;         /* KWS_FRAMES_DATASET only: 0 (none) or the coefficient, in [0, 1) */
+} kws_dataset_config;
+size_t kws_sizeof_dataset_config(void);
+int kws_frontend_create_dataset(const kws_dataset_config* cfg, kws_frontend_handle* out);
+int kws_frontend_frames_of(kws_frontend_handle h, int n_samples);
+int kws_frontend_window(kws_frontend_handle h, float* window_host);
+
 /* Device-side decode window of the streaming loop (detector.py:122,168-209; utils/queue.py): per stream a
  * bounded FIFO of up to `max_chunks` (1..64) softmax chunks (each <= max_frames frames; 2 * max_chunks *
  * round_up(max_frames, 16) bytes must fit 48 KiB, else KWS_ERR_UNSUPPORTED).  The frame ring behind kws_window_step is

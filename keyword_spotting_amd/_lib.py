@@ -16,6 +16,7 @@ KERNEL_AUTO, KERNEL_GENERIC, KERNEL_RESIDENT = 0, 1, 2
 DECODE, DECODE2, DECODE_STRICT = 0, 1, 2
 FP32, BF16, INT8, F16X3 = 0, 1, 2, 3
 FEAT_MEL, FEAT_MFCC = 0, 1
+FRAMES_DEPLOY, FRAMES_DATASET = 0, 1
 
 
 class KwsConfig(ctypes.Structure):
@@ -32,6 +33,12 @@ class KwsFrontendConfig(ctypes.Structure):
 class KwsFeatureConfig(ctypes.Structure):
     """kws_feature_config: what a front-end handle produces (mel of |X| or |X|^2, or MFCC + deltas, utils/mfcc.py)."""
     _fields_ = [("base", KwsFrontendConfig), ("kind", ctypes.c_int32), ("power", ctypes.c_int32), ("n_mfcc", ctypes.c_int32)]
+
+
+class KwsDatasetConfig(ctypes.Structure):
+    """kws_dataset_config: a feature front-end and how it frames the utterance -- as the deploy graph, or as the dataset's
+    librosa.stft (centred, reflect-padded, Hann-windowed) behind an optional pre-emphasis (process_wav.py:38-44,69-78)."""
+    _fields_ = [("feat", KwsFeatureConfig), ("framing", ctypes.c_int32), ("pre_emphasis", ctypes.c_float)]
 
 
 class KwsCellWrappers(ctypes.Structure):
@@ -101,6 +108,10 @@ _SIGNATURES = {
     "kws_frontend_feature_size": (_i, [_vp]),
     "kws_frontend_run_lengths": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp]),
     "kws_frontend_dct_basis": (_i, [_vp, _vp]),
+    "kws_sizeof_dataset_config": (ctypes.c_size_t, []),
+    "kws_frontend_create_dataset": (_i, [ctypes.POINTER(KwsDatasetConfig), ctypes.POINTER(_vp)]),
+    "kws_frontend_frames_of": (_i, [_vp, _i]),
+    "kws_frontend_window": (_i, [_vp, _vp]),
     "kws_window_create": (_i, [_i, _i, _i, _i, _f, ctypes.POINTER(_vp)]),
     "kws_window_destroy": (_i, [_vp]),
     "kws_window_step": (_i, [_vp, _vp, _i, _vp, ctypes.c_char_p, _vp, _vp, _vp]),
@@ -148,6 +159,7 @@ def load():
                 lib.kws_sizeof_frontend_config() != ctypes.sizeof(KwsFrontendConfig) or \
                 lib.kws_sizeof_cell_wrappers() != ctypes.sizeof(KwsCellWrappers) or \
                 lib.kws_sizeof_feature_config() != ctypes.sizeof(KwsFeatureConfig) or \
+                lib.kws_sizeof_dataset_config() != ctypes.sizeof(KwsDatasetConfig) or \
                 lib.kws_sizeof_attention_config() != ctypes.sizeof(KwsAttentionConfig):
             raise ImportError("%s was built from a different include/kws_amd.h than this binding (struct sizes differ); "
                               "rebuild it" % LIB_PATH)

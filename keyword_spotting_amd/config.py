@@ -56,6 +56,7 @@ class AttentionConfig(Config):
         self.power = 1                                      # :63  (the deploy graph never reads it: |rfft|, or |rfft|^2 inside mfcc())
         self.n_mel = 60                                     # :67
         self.n_mfcc = 20                                    # :66
+        self.pre_emphasis = False                           # :68  process_wav.py:72-73, in front of the dataset's STFT (DatasetFrontend)
         self.fmin = 300                                     # :64
         self.fmax = 8000                                    # :65
         self.use_relu = True                                # :55

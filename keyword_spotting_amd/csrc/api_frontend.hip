@@ -151,7 +151,17 @@ void pack_dct(kws_frontend* f, std::vector<float>& img) {
                 }
 }
 
-// (the handle's validated cfg / kind / n_mfcc, KWS_FRONTEND_DENSE) -> the device image of every table its kernels launch with, and in the
+// FrontendParams::win of fft_frontend.hip: the periodic Hann window of the dataset's frames, scipy.signal.get_window('hann', 400) as
+// librosa.stft builds it: in double, stored as float
+void pack_window(kws_frontend* f, std::vector<float>& img) {
+    const int N = f->cfg.fft_size;
+    f->window.resize(N);
+    for (int i = 0; i < N; ++i) f->window[i] = (float)(0.5 - 0.5 * std::cos(kTwoPi * i / N));
+    f->win_off = img.size();
+    img.insert(img.end(), f->window.begin(), f->window.end());
+}
+
+// (the handle's validated cfg / kind / n_mfcc / framing, KWS_FRONTEND_DENSE) -> the device image of every table its kernels launch with, and in the
 // handle where each one is: the dense-DFT pair for every frame length, behind it the FFT tables of a 400-sample frame.  Host code only.
 std::vector<float> pack_frontend_tables(kws_frontend* f, bool dense400) {
     const kws_frontend_config& c = f->cfg;
@@ -165,11 +175,54 @@ std::vector<float> pack_frontend_tables(kws_frontend* f, bool dense400) {
     pack_fft_tw(f, image);
     pack_fft_mel(f, image);
     f->use_fft = !dense400;
-    if (f->kind != KWS_FEAT_MFCC) return image;
-    f->dct = dct_basis_f32(f->n_mfcc, c.n_mel);
-    f->dct_tiles = (f->n_mfcc + 15) / 16;
-    pack_dct(f, image);
+    if (f->kind == KWS_FEAT_MFCC) {
+        f->dct = dct_basis_f32(f->n_mfcc, c.n_mel);
+        f->dct_tiles = (f->n_mfcc + 15) / 16;
+        pack_dct(f, image);
+    }
+    if (f->framing == KWS_FRAMES_DATASET) pack_window(f, image);
     return image;
+}
+
+// The checks and the handle behind kws_frontend_create_features and kws_frontend_create_dataset (which has validated framing and
+// pre_emphasis on their own): every argument check in front of the device check.
+int create_frontend(const kws_feature_config* fcfg, int framing, float pre_emphasis, kws_frontend_handle* out) {
+    const kws_frontend_config* cfg = &fcfg->base;
+    if (cfg->fft_size < 16 || cfg->fft_size > 496 || cfg->fft_size % 16 != 0)
+        return fail(KWS_ERR_UNSUPPORTED, "fft_size=%d must be a multiple of 16 in [16,496] (the reference uses 400)", cfg->fft_size);
+    if (cfg->hop_size < 1 || cfg->n_mel < 1 || cfg->n_mel > 64 || cfg->samplerate < 1)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "bad hop_size/n_mel/samplerate (%d/%d/%d)", cfg->hop_size, cfg->n_mel, cfg->samplerate);
+    if (!(cfg->fmin >= 0.f) || !(cfg->fmax > cfg->fmin) || cfg->fmax > cfg->samplerate / 2.0f + 1e-3f)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "need 0 <= fmin < fmax <= sr/2");
+    const bool mfcc = fcfg->kind == KWS_FEAT_MFCC;
+    if (fcfg->kind != KWS_FEAT_MEL && !mfcc) return fail(KWS_ERR_INVALID_ARGUMENT, "kind=%d is neither KWS_FEAT_MEL nor KWS_FEAT_MFCC", fcfg->kind);
+    if (!mfcc && fcfg->power != 1 && fcfg->power != 2) return fail(KWS_ERR_INVALID_ARGUMENT, "power=%d must be 1 (|X|) or 2 (|X|^2)", fcfg->power);
+    if (mfcc && (fcfg->n_mfcc < 1 || fcfg->n_mfcc > std::min(cfg->n_mel, 32)))
+        return fail(KWS_ERR_INVALID_ARGUMENT, "n_mfcc=%d outside 1..min(n_mel, 32) = %d", fcfg->n_mfcc, std::min(cfg->n_mel, 32));
+    const char* dense_env = getenv("KWS_FRONTEND_DENSE");      // A/B switch: the dense-DFT kernel also handles 400
+    const bool dense400 = dense_env && dense_env[0] == '1';
+    if ((mfcc || fcfg->power == 2) && (cfg->fft_size != 400 || dense400))
+        return fail(KWS_ERR_UNSUPPORTED, "%s needs the 400-point FFT front-end: fft_size=%d%s unsupported (the dense-DFT kernel produces "
+                    "magnitude mel only)", mfcc ? "kind=KWS_FEAT_MFCC" : "power=2", cfg->fft_size, dense400 ? " with KWS_FRONTEND_DENSE=1" : "");
+    if (framing == KWS_FRAMES_DATASET && (cfg->fft_size != 400 || dense400))
+        return fail(KWS_ERR_UNSUPPORTED, "framing=KWS_FRAMES_DATASET needs the 400-point FFT front-end: fft_size=%d%s unsupported (the dense-DFT "
+                    "kernel frames as the deploy graph only)", cfg->fft_size, dense400 ? " with KWS_FRONTEND_DENSE=1" : "");
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(KWS_ERR_NO_DEVICE, "no HIP device visible");
+    kws_frontend* f = new (std::nothrow) kws_frontend();
+    if (!f) return fail(KWS_ERR_OUT_OF_MEMORY, "host allocation failed");
+    f->cfg = *cfg;
+    f->kind = fcfg->kind; f->power = mfcc ? 2 : fcfg->power; f->n_mfcc = mfcc ? fcfg->n_mfcc : 0;
+    f->framing = framing; f->pre_emphasis = pre_emphasis;
+    const std::vector<float> host = pack_frontend_tables(f, dense400);
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&f->d_tables), host.size() * sizeof(float));
+    if (e != hipSuccess) { delete f; return hip_fail(e, "hipMalloc(frontend tables)"); }
+    e = hipMemcpy(f->d_tables, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipDeviceSynchronize();
+    if (e != hipSuccess) { hipFree(f->d_tables); delete f; return hip_fail(e, "hipMemcpy(frontend tables)"); }
+    live_register(f);
+    *out = f;
+    return KWS_OK;
 }
 
 }  // namespace
@@ -177,6 +230,11 @@ std::vector<float> pack_frontend_tables(kws_frontend* f, bool dense400) {
 namespace kws_host {
 
 bool frontend_takes_fft400(const kws_frontend* h, int B, int T) { return h->use_fft && (long long)B * T < (1LL << 31); }
+
+int frontend_needs_deploy_frames(const char* who) {
+    return fail(KWS_ERR_UNSUPPORTED, "%s takes deploy framing only: this front-end has framing=KWS_FRAMES_DATASET (centred frames need the "
+                "utterance's end; use kws_frontend_run_lengths)", who);
+}
 
 int frontend_needs_fft400(const kws_frontend* h, const char* what) {
     return fail(KWS_ERR_UNSUPPORTED, "%s need the 400-point FFT front-end (fft_size=%d%s)", what, h->cfg.fft_size,
@@ -191,6 +249,7 @@ kws::FrontendParams frontend_params(const kws_frontend* h, bool fft400, int B, i
     p.fft = h->cfg.fft_size; p.hop = h->cfg.hop_size; p.n_mel = h->cfg.n_mel;
     p.nf_tiles = h->nf_tiles; p.mel_tiles = h->mel_tiles; p.kc4 = h->kc4; p.B = B; p.T = T;
     p.power = h->power; p.n_mfcc = h->n_mfcc; p.dct_tiles = h->dct_tiles; p.dct = h->n_mfcc ? h->d_tables + h->dct_off : nullptr;
+    p.centred = h->framing == KWS_FRAMES_DATASET; p.pre_emphasis = h->pre_emphasis; p.win = p.centred ? h->d_tables + h->win_off : nullptr;
     return p;
 }
 
@@ -231,37 +290,34 @@ int kws_frontend_create_features(const kws_feature_config* fcfg, kws_frontend_ha
     if (!out) return fail(KWS_ERR_INVALID_ARGUMENT, "out handle pointer is null");
     *out = nullptr;
     if (!fcfg) return fail(KWS_ERR_INVALID_ARGUMENT, "config is null");
-    const kws_frontend_config* cfg = &fcfg->base;
-    if (cfg->fft_size < 16 || cfg->fft_size > 496 || cfg->fft_size % 16 != 0)
-        return fail(KWS_ERR_UNSUPPORTED, "fft_size=%d must be a multiple of 16 in [16,496] (the reference uses 400)", cfg->fft_size);
-    if (cfg->hop_size < 1 || cfg->n_mel < 1 || cfg->n_mel > 64 || cfg->samplerate < 1)
-        return fail(KWS_ERR_INVALID_ARGUMENT, "bad hop_size/n_mel/samplerate (%d/%d/%d)", cfg->hop_size, cfg->n_mel, cfg->samplerate);
-    if (!(cfg->fmin >= 0.f) || !(cfg->fmax > cfg->fmin) || cfg->fmax > cfg->samplerate / 2.0f + 1e-3f)
-        return fail(KWS_ERR_INVALID_ARGUMENT, "need 0 <= fmin < fmax <= sr/2");
-    const bool mfcc = fcfg->kind == KWS_FEAT_MFCC;
-    if (fcfg->kind != KWS_FEAT_MEL && !mfcc) return fail(KWS_ERR_INVALID_ARGUMENT, "kind=%d is neither KWS_FEAT_MEL nor KWS_FEAT_MFCC", fcfg->kind);
-    if (!mfcc && fcfg->power != 1 && fcfg->power != 2) return fail(KWS_ERR_INVALID_ARGUMENT, "power=%d must be 1 (|X|) or 2 (|X|^2)", fcfg->power);
-    if (mfcc && (fcfg->n_mfcc < 1 || fcfg->n_mfcc > std::min(cfg->n_mel, 32)))
-        return fail(KWS_ERR_INVALID_ARGUMENT, "n_mfcc=%d outside 1..min(n_mel, 32) = %d", fcfg->n_mfcc, std::min(cfg->n_mel, 32));
-    const char* dense_env = getenv("KWS_FRONTEND_DENSE");      // A/B switch: the dense-DFT kernel also handles 400
-    const bool dense400 = dense_env && dense_env[0] == '1';
-    if ((mfcc || fcfg->power == 2) && (cfg->fft_size != 400 || dense400))
-        return fail(KWS_ERR_UNSUPPORTED, "%s needs the 400-point FFT front-end: fft_size=%d%s unsupported (the dense-DFT kernel produces "
-                    "magnitude mel only)", mfcc ? "kind=KWS_FEAT_MFCC" : "power=2", cfg->fft_size, dense400 ? " with KWS_FRONTEND_DENSE=1" : "");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(KWS_ERR_NO_DEVICE, "no HIP device visible");
-    kws_frontend* f = new (std::nothrow) kws_frontend();
-    if (!f) return fail(KWS_ERR_OUT_OF_MEMORY, "host allocation failed");
-    f->cfg = *cfg;
-    f->kind = fcfg->kind; f->power = mfcc ? 2 : fcfg->power; f->n_mfcc = mfcc ? fcfg->n_mfcc : 0;
-    const std::vector<float> host = pack_frontend_tables(f, dense400);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&f->d_tables), host.size() * sizeof(float));
-    if (e != hipSuccess) { delete f; return hip_fail(e, "hipMalloc(frontend tables)"); }
-    e = hipMemcpy(f->d_tables, host.data(), host.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { hipFree(f->d_tables); delete f; return hip_fail(e, "hipMemcpy(frontend tables)"); }
-    live_register(f);
-    *out = f;
+    return create_frontend(fcfg, KWS_FRAMES_DEPLOY, 0.f, out);
+}
+
+size_t kws_sizeof_dataset_config(void) { return sizeof(kws_dataset_config); }
+
+int kws_frontend_create_dataset(const kws_dataset_config* dcfg, kws_frontend_handle* out) {
+    if (!out) return fail(KWS_ERR_INVALID_ARGUMENT, "out handle pointer is null");
+    *out = nullptr;
+    if (!dcfg) return fail(KWS_ERR_INVALID_ARGUMENT, "config is null");
+    if (dcfg->framing != KWS_FRAMES_DEPLOY && dcfg->framing != KWS_FRAMES_DATASET)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "framing=%d is neither KWS_FRAMES_DEPLOY nor KWS_FRAMES_DATASET", dcfg->framing);
+    if (!std::isfinite(dcfg->pre_emphasis) || dcfg->pre_emphasis < 0.f || dcfg->pre_emphasis >= 1.f)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "pre_emphasis=%g must be finite and in [0, 1)", (double)dcfg->pre_emphasis);
+    if (dcfg->framing == KWS_FRAMES_DEPLOY && dcfg->pre_emphasis != 0.f)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "pre_emphasis=%g with framing=KWS_FRAMES_DEPLOY: the deploy graph has no pre-emphasis", (double)dcfg->pre_emphasis);
+    return create_frontend(&dcfg->feat, dcfg->framing, dcfg->pre_emphasis, out);
+}
+
+int kws_frontend_frames_of(kws_frontend_handle h, int n_samples) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    if (h->framing != KWS_FRAMES_DATASET) return kws_frontend_frames(&h->cfg, n_samples);
+    return n_samples > h->cfg.fft_size / 2 ? 1 + n_samples / h->cfg.hop_size : 0;
+}
+
+int kws_frontend_window(kws_frontend_handle h, float* window_host) {
+    if (!h || !window_host) return fail(KWS_ERR_INVALID_ARGUMENT, "null argument");
+    if (h->framing != KWS_FRAMES_DATASET) return fail(KWS_ERR_INVALID_ARGUMENT, "the front-end has no window: its framing is KWS_FRAMES_DEPLOY");
+    memcpy(window_host, h->window.data(), h->window.size() * sizeof(float));
     return KWS_OK;
 }
 
@@ -302,7 +358,7 @@ int kws_frontend_dct_basis(kws_frontend_handle h, float* basis_host) {
 int kws_frontend_run_lengths(kws_frontend_handle h, const float* pcm, const int32_t* n_samples, int B, int n_max, float* out, void* stream) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
     if (B < 0 || n_max < 0) return fail(KWS_ERR_INVALID_ARGUMENT, "negative dimension");
-    const int T = kws_frontend_frames(&h->cfg, n_max);
+    const int T = kws_frontend_frames_of(h, n_max);
     if (B == 0 || T == 0) return KWS_OK;
     if (!pcm || !out) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
     if (!h->use_fft) {
@@ -319,6 +375,7 @@ int kws_frontend_run_lengths(kws_frontend_handle h, const float* pcm, const int3
 int kws_frontend_run_carry(kws_frontend_handle h, const float* carry, int n_carry, const float* chunk, int n_chunk, int B,
                            float* mel, float* next_carry, int n_next, void* stream) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    if (h->framing != KWS_FRAMES_DEPLOY) return frontend_needs_deploy_frames("kws_frontend_run_carry");
     if (!h->plain())
         return fail(KWS_ERR_UNSUPPORTED, "kws_frontend_run_carry streams magnitude mel only: this front-end has %s (MFCC deltas need the whole "
                     "utterance; use kws_frontend_run_lengths)", h->kind == KWS_FEAT_MFCC ? "kind=KWS_FEAT_MFCC" : "power=2");

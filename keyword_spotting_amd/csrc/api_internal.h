@@ -135,6 +135,8 @@ kws::WindowTail window_tail_params(kws_window* w, const uint8_t* clear_before, i
 bool frontend_takes_fft400(const kws_frontend* h, int B, int T);
 // ... the refusal of `what` ("per-stream chunk lengths") on a handle whose launches go to the dense-DFT kernel
 int frontend_needs_fft400(const kws_frontend* h, const char* what);
+// ... the refusal of a KWS_FRAMES_DATASET handle by the streaming entry point `who`
+int frontend_needs_deploy_frames(const char* who);
 // ... `seed` (or zeros) with everything that comes from the handle and the call shape; the samples, lengths and outputs are the caller's
 kws::FrontendParams frontend_params(const kws_frontend* h, bool fft400, int B, int T, const kws::FrontendParams* seed = nullptr);
 // ... mel of [carry | chunk]; `gate` (FFT kernel only): its gate fields ride along -- pcm_i16 (read in place of chunk), vad, masks, next carry
@@ -277,7 +279,10 @@ struct kws_frontend {
     kws_frontend_config cfg;
     // kws_frontend_create_features: what the handle produces (kws_frontend_create: mel, power 1)
     int kind = KWS_FEAT_MEL, power = 1, n_mfcc = 0;
-    bool plain() const { return kind == KWS_FEAT_MEL && power == 1; }     // what the streaming paths take
+    // kws_frontend_create_dataset: how the utterance is framed (kws_frontend_create_features: KWS_FRAMES_DEPLOY, 0)
+    int framing = KWS_FRAMES_DEPLOY;
+    float pre_emphasis = 0.f;
+    bool plain() const { return kind == KWS_FEAT_MEL && power == 1 && framing == KWS_FRAMES_DEPLOY; }     // what the streaming paths take
     // pack_frontend_tables (api_frontend.hip): the kernel tables in the one device allocation (offsets in floats), and the two bases
     float* d_tables = nullptr;
     size_t dft_off = 0, melw_off = 0;         // frontend_kernels.hip tables (every fft_size)
@@ -288,4 +293,6 @@ struct kws_frontend {
     std::vector<float> basis;      // [n_mel][fft/2+1]
     size_t dct_off = 0;            // fft_frontend.hip: A fragments of D^T (MFCC only)
     std::vector<float> dct;        // [n_mel][n_mfcc]
+    size_t win_off = 0;            // fft_frontend.hip: the Hann window (KWS_FRAMES_DATASET only)
+    std::vector<float> window;     // [fft]
 };

@@ -159,6 +159,7 @@ int kws_stream_create(kws_handle model, kws_frontend_handle frontend, kws_window
     if (!model || !frontend || !window || !state || !restart || !label) return fail(KWS_ERR_INVALID_ARGUMENT, "null argument");
     const unsigned long long ms = live_serial(model), fs = live_serial(frontend), ws = live_serial(window);
     if (!ms || !fs || !ws) return fail(KWS_ERR_INVALID_ARGUMENT, "model, front-end or window handle is not alive (destroyed, or not a handle)");
+    if (frontend->framing != KWS_FRAMES_DEPLOY) return frontend_needs_deploy_frames("kws_stream_create");
     if (!frontend->plain())
         return fail(KWS_ERR_UNSUPPORTED, "kws_stream_create takes a magnitude-mel front-end only: this one has %s (the reference's streaming "
                     "detector has no MFCC branch)", frontend->kind == KWS_FEAT_MFCC ? "kind=KWS_FEAT_MFCC" : "power=2");

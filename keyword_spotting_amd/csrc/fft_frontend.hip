@@ -7,6 +7,10 @@
 //   power mel        |rfft|^2 @ mel_basis^T                                          reader.py:267-268
 //   MFCC + deltas    10 log10(max(1e-10, |rfft|^2 @ mel_basis^T)) @ dct, [c | d/2 | 0.3 d]    utils/mfcc.py:20-99
 // with the log and the DCT fused behind the mel MFMAs (the mel C tile is the DCT's B operand) and the deltas in a second small launch.
+// ... and the features the reference's models are trained and validated on (kws_frontend_create_dataset; the DatasetFrames tag below):
+//   y = pre_emphasis(x)  (optional)                                                  process_wav.py:38-44,72-73
+//   |librosa.stft(y, 400, 160)|: centred frames of the reflect-padded utterance, periodic Hann window    process_wav.py:74-78, server_demo.py:59-82
+// in front of the same three epilogues: only the sample load of stage 1 differs.
 //
 // 400 = 16 x 25, n = 16 n1 + n2, k = k1 + 25 k2 (Cooley-Tukey):
 //     X[k1 + 25 k2] = sum_{n2<16} W16^{n2 k2} * ( W400^{n2 k1} * Y_{n2}[k1] ),   Y_{n2}[k1] = sum_{n1<25} x[16 n1 + n2] W25^{n1 k1}
@@ -123,10 +127,25 @@ template <typename S> struct RaggedRows {};
 // (A tag again: the mel instantiations above keep their names and their code.)
 constexpr int kEpiMel = 0, kEpiPower = 1, kEpiMfcc = 2;
 template <typename S, int EPI> struct Utterances {};
+// DatasetFrames<S, EPI, PRE> in place of the sample type S: Utterances<S, EPI> with the dataset's framing (p.centred; kws_amd.h).
+// Frame t of utterance b (n samples) is centred on sample t * hop: tap i reads s = t * hop + i - 200, reflected once at either end
+// (s < 0: -s; s >= n: 2 (n - 1) - s -- np.pad(mode='reflect') for n >= 201, the shortest utterance that has frames), times the
+// Hann window p.win[i]; T_b = 1 + n / hop.  PRE: the samples pass y[0] = x[0], y[i] = x[i] - fl32(p.pre_emphasis * x[i-1]) first, two
+// roundings as numpy's float32 arrays take them.  Frames whose 400 taps and their predecessors all lie inside the utterance -- all
+// but the first two and the last two or three -- load as the other instantiations do; the others take the index per tap.
+// (A tag again: every instantiation above keeps its name and its code.)
+template <typename S, int EPI, bool PRE> struct DatasetFrames {};
 namespace {
-template <typename T> struct SampleOf { using type = T; static constexpr bool ragged = false, lengths = false; static constexpr int epi = kEpiMel; };
-template <typename S> struct SampleOf<RaggedRows<S>> { using type = S; static constexpr bool ragged = true, lengths = false; static constexpr int epi = kEpiMel; };
-template <typename S, int EPI> struct SampleOf<Utterances<S, EPI>> { using type = S; static constexpr bool ragged = false, lengths = true; static constexpr int epi = EPI; };
+template <typename T> struct SampleOf {
+    using type = T;
+    static constexpr bool ragged = false, lengths = false, centred = false, pre = false;
+    static constexpr int epi = kEpiMel;
+};
+template <typename S> struct SampleOf<RaggedRows<S>> : SampleOf<S> { static constexpr bool ragged = true; };
+template <typename S, int EPI> struct SampleOf<Utterances<S, EPI>> : SampleOf<S> { static constexpr bool lengths = true; static constexpr int epi = EPI; };
+template <typename S, int EPI, bool PRE> struct SampleOf<DatasetFrames<S, EPI, PRE>> : SampleOf<Utterances<S, EPI>> {
+    static constexpr bool centred = true, pre = PRE;
+};
 
 __device__ __forceinline__ int ragged_len(const FrontendParams& p, unsigned b) {      // clamped to [0, n_max] (kws_amd.h)
     const int n = p.lens ? p.lens[b] : p.n_max;
@@ -134,6 +153,12 @@ __device__ __forceinline__ int ragged_len(const FrontendParams& p, unsigned b) {
 }
 __device__ __forceinline__ int ragged_carry(const FrontendParams& p, unsigned b) { return p.carry_len ? p.carry_len[b] : p.n_carry; }
 __device__ __forceinline__ int ragged_frames(const FrontendParams& p, int total) { return total < p.fft ? 0 : 1 + (total - p.fft) / p.hop; }
+__device__ __forceinline__ int centred_frames(const FrontendParams& p, int n) { return n > p.fft / 2 ? 1 + n / p.hop : 0; }
+// frames of a whole utterance of n samples under the instantiation's framing
+template <bool CENTRED> __device__ __forceinline__ int utterance_frames(const FrontendParams& p, int n) {
+    if constexpr (CENTRED) return centred_frames(p, n);
+    else return ragged_frames(p, n);
+}
 
 // The gate of one stream of a ragged chunk (detector.py:162-183 for this stream alone): n == 0 skips the iteration -- carry
 // copied through, reset 0 (the GRU hands the state back over zero frames), skip set; otherwise the vad masks of its n new samples,
@@ -165,6 +190,7 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
     constexpr bool RAGGED = SampleOf<SampleTag>::ragged;
     constexpr bool LENGTHS = SampleOf<SampleTag>::lengths;
     constexpr int EPI = SampleOf<SampleTag>::epi;
+    constexpr bool CENTRED = SampleOf<SampleTag>::centred, PRE = SampleOf<SampleTag>::pre;
     static_assert(GATE || !RAGGED, "the ragged feed always carries the gate");
     static_assert(!(GATE && LENGTHS), "whole utterances have no stream gate");
     __shared__ __attribute__((aligned(16))) char lds[kFftLds];
@@ -279,7 +305,50 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
         const unsigned sb = fidx / (unsigned)p.T;
         const int st = (int)(fidx - sb * (unsigned)p.T);
         float x[25];
-        if constexpr (LENGTHS) {
+        if constexpr (CENTRED) {
+            static_assert(sizeof(SampleT) == 4, "the dataset's utterances are float PCM");
+            // utterance sb: frame st spans samples [s0, s0 + 400) of its reflected signal.  An interior frame (and, for PRE, the
+            // sample in front of it) lies inside [0, n); a wave of interior frames loads as Utterances does, one with an edge frame
+            // -- decided by ballot, as the seam path below -- takes the reflected index per tap.  Same operations on the same
+            // samples either way: a frame's bits do not depend on its neighbours in the wave.
+            const int n = ragged_len(p, sb);
+            const bool live = st < centred_frames(p, n);
+            const int s0 = st * p.hop - 200;
+            const unsigned long long any_edge = __builtin_amdgcn_ballot_w64(live && (s0 < 1 || s0 + 400 > n));
+            const SampleT* row = chunk_all + (size_t)sb * p.n_max;
+            if (!live) {
+#pragma unroll
+                for (int n1 = 0; n1 < 25; ++n1) x[n1] = 0.f;
+            } else {
+                float win[25];
+#pragma unroll
+                for (int n1 = 0; n1 < 25; ++n1) win[n1] = p.win[16 * n1 + n2];
+                if (!any_edge) {
+                    const SampleT* src = row + (s0 + n2);
+#pragma unroll
+                    for (int n1 = 0; n1 < 25; ++n1) {
+                        float v = src[16 * n1];
+                        if constexpr (PRE) v = v - p.pre_emphasis * src[16 * n1 - 1];
+                        x[n1] = v * win[n1];
+                    }
+                } else {
+#pragma unroll
+                    for (int n1 = 0; n1 < 25; ++n1) {
+                        int s = s0 + n2 + 16 * n1;                  // n >= 201: one reflection at most, then 0 <= s < n
+                        s = s < 0 ? -s : s;
+                        s = s >= n ? 2 * (n - 1) - s : s;
+                        float v = row[s];
+                        if constexpr (PRE) {
+                            const float pred = p.pre_emphasis * row[s > 0 ? s - 1 : 0];
+                            v = s > 0 ? v - pred : v;
+                        }
+                        x[n1] = v * win[n1];
+                        // the rare path: five taps' loads in flight at a time, not 25 addresses (the register budget of six workgroups per CU)
+                        if (n1 % 5 == 4) __builtin_amdgcn_sched_barrier(0);
+                    }
+                }
+            }
+        } else if constexpr (LENGTHS) {
             // utterance sb: the first n samples of its row; a live frame (st < T_b) ends before sample n, a dead one loads nothing
             const bool live = st < ragged_frames(p, ragged_len(p, sb));
             const SampleT* src = chunk_all + (size_t)sb * p.n_max + (st * p.hop + n2);
@@ -564,7 +633,7 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
             const unsigned fo = f0 + f;
             if (fo < total) {
                 const unsigned sb = fo / (unsigned)p.T;
-                const bool live = (int)(fo - sb * (unsigned)p.T) < ragged_frames(p, ragged_len(p, sb));
+                const bool live = (int)(fo - sb * (unsigned)p.T) < utterance_frames<CENTRED>(p, ragged_len(p, sb));
                 float* out = p.mel + (size_t)fo * (3 * p.n_mfcc);
                 const int c0 = 16 * w + 4 * g;
 #pragma unroll
@@ -578,8 +647,9 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
 
 // The delta thirds of the MFCC rows (utils/mfcc.py:45-69,96-99), in place behind the launch above: with
 // d[t] = c[min(t + 1, T_b - 1)] - c[max(t - 1, 0)] (_delta_order shifts by one frame whatever its order, and only scales by it),
-// columns [n_mfcc, 2 n_mfcc) = d / 2 and [2 n_mfcc, 3 n_mfcc) = (1 d + 2 d) / 10.  The edges are the utterance's own T_b; rows past
-// it are zero.  One thread per (frame, coefficient): n_mfcc reads of neighbours in L2, 2 n_mfcc writes per frame.
+// columns [n_mfcc, 2 n_mfcc) = d / 2 and [2 n_mfcc, 3 n_mfcc) = (1 d + 2 d) / 10.  The edges are the utterance's own T_b, by the
+// framing of the launch in front (p.centred); rows past it are zero.  One thread per (frame, coefficient): n_mfcc reads of
+// neighbours in L2, 2 n_mfcc writes per frame.
 __global__ void __launch_bounds__(256) mfcc_delta_kernel(const FrontendParams p) {
     const unsigned long long i = (unsigned long long)blockIdx.x * 256u + threadIdx.x;
     const unsigned nc = (unsigned)p.n_mfcc;
@@ -588,7 +658,7 @@ __global__ void __launch_bounds__(256) mfcc_delta_kernel(const FrontendParams p)
     const unsigned c = (unsigned)(i - row * nc);
     const unsigned b = (unsigned)(row / (unsigned)p.T);
     const int t = (int)(row - (unsigned long long)b * (unsigned)p.T);
-    const int tb = ragged_frames(p, ragged_len(p, b));
+    const int tb = p.centred ? centred_frames(p, ragged_len(p, b)) : ragged_frames(p, ragged_len(p, b));
     float* out = p.mel + (size_t)row * (3 * nc);
     float d1 = 0.f, d2 = 0.f;
     if (t < tb) {
@@ -610,12 +680,14 @@ static hipError_t launch_fft400_tiles(const FrontendParams& p, unsigned grid, hi
 }
 template <int EPI>
 static hipError_t launch_features_tiles(const FrontendParams& p, unsigned grid, hipStream_t st) {
-    return launch_fft400_tiles<Utterances<float, EPI>, false>(p, grid, st);
+    if (!p.centred) return launch_fft400_tiles<Utterances<float, EPI>, false>(p, grid, st);
+    if (p.pre_emphasis != 0.f) return launch_fft400_tiles<DatasetFrames<float, EPI, true>, false>(p, grid, st);
+    return launch_fft400_tiles<DatasetFrames<float, EPI, false>, false>(p, grid, st);
 }
 
 hipError_t launch_features_fft400(const FrontendParams& p, int B, hipStream_t st) {
     const long long total = (long long)B * p.T;        // 0 < total < 2^31 (checked by the caller)
-    if (p.fft != 400 || p.gate || p.pcm_i16 || p.n_carry != 0) return hipErrorInvalidValue;
+    if (p.fft != 400 || p.gate || p.pcm_i16 || p.n_carry != 0 || (p.centred && !p.win)) return hipErrorInvalidValue;
     const unsigned grid = (unsigned)(((total + 15) / 16 + 7) / 8 * 8);
     FrontendParams q = p;
     q.fft_blocks = (int)grid;

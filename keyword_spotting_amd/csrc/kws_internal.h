@@ -305,11 +305,17 @@ struct FrontendParams {
     const float* dct;         // [mel_tiles][dct_tiles][64 lanes][4]  A fragments of D^T: lane (g, i), component e = D[filter 16 tile + 4g + e][16 ct + i]
     int n_mfcc, dct_tiles;    // coefficients (0: mel output), ceil(n_mfcc / 16)
     int power;                // mel output: 1 = |X|, 2 = |X|^2
+    // fft_frontend.hip, the dataset's framing of whole utterances (centred != 0; kws_frontend_create_dataset): frame t is centred on
+    // sample t * hop of an utterance reflected at both ends, under a Hann window; T_b = 1 + n_b / hop frames (0 for n_b <= fft / 2)
+    int centred;
+    float pre_emphasis;       // c: y[0] = x[0], y[i] = x[i] - c x[i-1] in front of the frames (0: none)
+    const float* win;         // [fft] the window
 };
 hipError_t launch_mel_frontend(const FrontendParams& p, int B, hipStream_t st);
 // fft 400 only (fft_frontend.hip): p.dft = twiddles [12][16] (cos, sin), p.melw = basis fragments [tile][group of its run][64]
 hipError_t launch_mel_fft400(const FrontendParams& p, int B, hipStream_t st);      // honours p.pcm_i16 and p.gate
-// ... B whole utterances with per-utterance lengths -> mel (p.power) or MFCC + deltas (p.n_mfcc > 0: two launches); float PCM, no gate
+// ... B whole utterances with per-utterance lengths -> mel (p.power) or MFCC + deltas (p.n_mfcc > 0: two launches); float PCM, no gate;
+// p.centred: the dataset's frames (DatasetFrames)
 hipError_t launch_features_fft400(const FrontendParams& p, int B, hipStream_t st);
 hipError_t launch_carry_tail(const float* carry, int n_carry, const float* chunk, int n_chunk, float* next, int n_next, int B,
                              hipStream_t st);

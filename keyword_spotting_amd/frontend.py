@@ -1,7 +1,10 @@
 """MelFrontend -- the in-graph audio front-end of models/rnn_ctc.py:134-149 on the GPU (kws_frontend_*):
 tf_frame(400, 160) -> |rfft(., 400)| -> matmul with librosa.filters.mel(...)^T, power 1, no window.
 MfccFrontend -- the config.mfcc branch of models/attention_ctc.py:249-250 (utils/mfcc.py:72-99): the same frames -> |rfft|^2 -> mel
--> dB -> DCT -> [c | delta | delta-delta], a whole-utterance transform (kws_frontend_create_features / kws_frontend_run_lengths)."""
+-> dB -> DCT -> [c | delta | delta-delta], a whole-utterance transform (kws_frontend_create_features / kws_frontend_run_lengths).
+DatasetFrontend -- the features the models are trained and validated on (process_wav.py:38-44,69-78 -> reader.py:264-269;
+server_demo.py:59-82): optional pre-emphasis -> |librosa.stft(y, 400, 160)| (centred, reflect-padded, Hann-windowed) -> mel of |X| or
+|X|^2, or MFCC + deltas (kws_frontend_create_dataset / kws_frontend_run_lengths)."""
 import ctypes
 
 import numpy as np
@@ -13,13 +16,15 @@ from . import _lib
 class _Frontend(object):
     """What the two front-ends share: the handle and its lifetime, the mel basis, the PCM normalisation."""
 
-    def __init__(self, config, device, create, features=None):
+    def __init__(self, config, device, create, features=None, dataset=None):
         self.config = config
         self.device = torch.device(device)
         self._lib = _lib.load()
         self._base = _lib.KwsFrontendConfig(int(config.samplerate), int(config.fft_size), int(config.hop_size),
                                             int(config.n_mel), float(config.fmin), float(config.fmax))
         self._cfg = self._base if features is None else _lib.KwsFeatureConfig(self._base, *features)
+        if dataset is not None:
+            self._cfg = _lib.KwsDatasetConfig(self._cfg, *dataset)
         self._handle = ctypes.c_void_p()
         with torch.cuda.device(self.device):
             _lib.check(getattr(self._lib, create)(ctypes.byref(self._cfg), ctypes.byref(self._handle)))
@@ -55,6 +60,20 @@ class _Frontend(object):
         if x.dim() != 2:
             raise _lib.InvalidArgumentError(-1, "expected signal to have rank 2 but was %d" % x.dim())
         return x.to(self.device).contiguous(), int(x.shape[0]), int(x.shape[1]), single
+
+
+    def _run_lengths(self, pcm, n_samples, width):
+        """kws_frontend_run_lengths: pcm [B,N] (or [N]), n_samples [B] or None -> [B,T,width] (or [T,width]), T = num_frames(N)."""
+        x, b, n, single = self._pcm(pcm)
+        if n_samples is not None:
+            n_samples = torch.as_tensor(n_samples).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(n_samples.shape) != (b,):
+                raise _lib.InvalidArgumentError(-1, "n_samples must be [%d]" % b)
+        out = torch.empty(b, self.num_frames(n), width, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_frontend_run_lengths(self._handle, _lib.ptr(x), _lib.ptr(n_samples), b, n, _lib.ptr(out),
+                                                          _lib.current_stream_ptr()))
+        return out[0] if single else out
 
 
 class MelFrontend(_Frontend):
@@ -108,13 +127,42 @@ class MfccFrontend(_Frontend):
     def forward(self, pcm, n_samples=None):
         """pcm [B,N] (or [N]) float, n_samples [B] int32 or None (= N for all) -> features [B,T,3*n_mfcc] (or [T,3*n_mfcc]) on
         the device, T = num_frames(N)."""
-        x, b, n, single = self._pcm(pcm)
-        if n_samples is not None:
-            n_samples = torch.as_tensor(n_samples).to(device=self.device, dtype=torch.int32).contiguous()
-            if tuple(n_samples.shape) != (b,):
-                raise _lib.InvalidArgumentError(-1, "n_samples must be [%d]" % b)
-        out = torch.empty(b, self.num_frames(n), 3 * int(self.config.n_mfcc), dtype=torch.float32, device=self.device)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_frontend_run_lengths(self._handle, _lib.ptr(x), _lib.ptr(n_samples), b, n, _lib.ptr(out),
-                                                          _lib.current_stream_ptr()))
-        return out[0] if single else out
+        return self._run_lengths(pcm, n_samples, 3 * int(self.config.n_mfcc))
+
+
+class DatasetFrontend(_Frontend):
+    """The dataset's features of B utterances of their own lengths: [B, T_max, feature_size] with T = 1 + n // hop centred
+    frames per utterance (none for n <= fft_size // 2), rows past an utterance's own frame count zero.  What the rows hold follows the
+    config as reader.py:264-269 decides: config.mfcc -> MFCC + deltas (3 * n_mfcc), else mel of |X| ** config.power (n_mel).
+    pre_emphasis: the coefficient, or None for config.pre_emphasis (True: 0.97, process_wav.py:38)."""
+
+    def __init__(self, config, device="cuda:0", pre_emphasis=None):
+        if pre_emphasis is None:
+            pre_emphasis = getattr(config, "pre_emphasis", False)
+        if pre_emphasis is True or pre_emphasis is False:
+            pre_emphasis = 0.97 if pre_emphasis else 0.0
+        self.pre_emphasis = float(pre_emphasis)
+        if getattr(config, "mfcc", False):
+            features = (_lib.FEAT_MFCC, 2, int(config.n_mfcc))
+        else:
+            features = (_lib.FEAT_MEL, int(getattr(config, "power", 1)), 0)
+        super(DatasetFrontend, self).__init__(config, device, "kws_frontend_create_dataset", features,
+                                              (_lib.FRAMES_DATASET, self.pre_emphasis))
+
+    def num_frames(self, n_samples):
+        return int(self._lib.kws_frontend_frames_of(self._handle, int(n_samples)))
+
+    @property
+    def feature_size(self):
+        return int(self._lib.kws_frontend_feature_size(self._handle))
+
+    def window(self):
+        """[fft_size] fp32 -- the periodic Hann window the frames are multiplied by."""
+        out = np.empty(int(self.config.fft_size), np.float32)
+        _lib.check(self._lib.kws_frontend_window(self._handle, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def forward(self, pcm, n_samples=None):
+        """pcm [B,N] (or [N]) float, n_samples [B] int32 or None (= N for all) -> features [B,T,feature_size] (or
+        [T,feature_size]) on the device, T = num_frames(N)."""
+        return self._run_lengths(pcm, n_samples, self.feature_size)
