@@ -114,8 +114,8 @@ struct StepArgs {
     bool locked = false;                   // the caller (kws_stream_feed) already holds the handle and has ordered the stream
 };
 
-// api_step.hip: one step (kws_step and the stream manager), whether its last launch can take a window tail, and the
-// ordering of a call against the handle's previous one
+// api_step.hip: one step (kws_step and the stream manager), whether its launch plan (plan_step) lets the last launch take a window
+// tail, and the ordering of a call against the handle's previous one
 int step_impl(kws_handle h, const StepArgs& a);
 bool step_takes_window(kws_handle h, int B, int T, int window_chunks);
 int call_enter(kws_handle h, hipStream_t st);
@@ -167,12 +167,12 @@ struct kws_model {
     int scratch_allocs = 0;          // (re)allocations so far; each one synchronised the device (kws_scratch_stats)
     float4* scratch[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // this call's seams: l -> scratch[l % nscratch]
     int nscratch = 0;
-    bool pipe_disabled = false;
+    bool pipe_disabled = false;      // fine-grained memory unavailable, or a pipelined launch timed out: never the pipelined launch again
     // time-blocked overlap of the layers on separate HIP streams (step_overlapped)
     hipStream_t lane_stream[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     std::vector<hipEvent_t> ovl_events;
     hipEvent_t ovl_tail[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};   // end of the last overlapped call, per lane
-    bool ovl_tail_valid = false;      // fine-grained memory unavailable, or a pipelined launch timed out: sequential launches from then on
+    bool ovl_tail_valid = false;     // the last call was overlapped: the next one waits for ovl_tail before it touches the seams
     // layer-pipelined launch of the generic kernel
     int num_cus = 0;
     int* pipe_ready = nullptr;       // [L][groups] frames published

@@ -6,73 +6,101 @@
 using namespace kws_host;
 
 namespace {
-
-bool is_resident(const kws_model* h, const LayerDev& Ld) {
-    if (h->wrapped) return false;                  // the cell wrappers exist in the generic kernels only (kws_set_kernel refuses RESIDENT)
-    return h->kernel_kind == KWS_KERNEL_RESIDENT || (h->kernel_kind == KWS_KERNEL_AUTO && Ld.resident_ok);
-}
-
-// The layer-pipelined launch needs all L x groups workgroups resident at once (one per CU) and the streaming kernel
-// on every layer; it pays when the layers would otherwise leave CUs idle.
-bool pipeline_eligible(kws_handle h, int B) {
-    // AUTO keeps the resident kernels where they exist even when this launch would be faster (H=128, L=2: +10 % at
-    // B <= 2048; L=4, B=1024: 2.2x; select it with KWS_KERNEL_GENERIC): the two kernel families round differently in
-    // the last bit, and a stream's result must not depend on how many neighbours it is batched or sharded with.
-    // KWS_NO_PIPELINE=1: never this launch -- what a device without fine-grained memory gets (pipe_disabled), for A/B runs
-    // and for the tests of the layouts that take its place (tests/test_gpu_wrapped.py)
-    static const bool no_pipe = [] { const char* e = getenv("KWS_NO_PIPELINE"); return e && e[0] == '1'; }();
-    if (h->pipe_disabled || no_pipe) return false;
-    const bool f16_streaming = h->cfg.precision == KWS_F16X3 && h->pk.f16_generic;      // gru_stack_f16x3_pipelined
-    if ((h->cfg.precision != KWS_FP32 && !f16_streaming) || h->cfg.num_layers < 2 || h->kernel_kind == KWS_KERNEL_RESIDENT) return false;
-    for (const auto& L : h->pk.layers)
-        if (is_resident(h, L)) return false;
-    const long long groups = kws::groups_of(B);
-    return h->num_cus > 0 && groups * h->cfg.num_layers <= h->num_cus;
-}
-
-// ---- scratch: what a call of shape (B, T) needs, and the arena it is carved from ------------------------------------
+// ---- the launch plan: what a kws_step of shape (B, T) launches, decided once ------------------------------------------
 #ifndef KWS_OVERLAP_MIN_T
 #define KWS_OVERLAP_MIN_T 64
 #endif
-bool overlap_shape_ok(kws_handle h, int B, int T) {      // step_overlapped, leaving the profiling switch aside
-    const kws_config& c = h->cfg;
-    if (c.precision != KWS_FP32 || c.num_layers < 2 || c.num_layers > 5) return false;
-    if (pipeline_eligible(h, B)) return false;            // the streaming kernel has its own in-kernel pipeline
-    const long long groups = kws::groups_of(B);
-    return h->num_cus > 0 && groups * c.num_layers <= h->num_cus && T >= KWS_OVERLAP_MIN_T;
-}
-bool overlap_eligible(kws_handle h, int B, int T) { return !h->profiling && overlap_shape_ok(h, B, T); }
-void overlap_blocks(int T, int* nb_out, int* tb_out) {
-    int nb = T / 32 < 8 ? T / 32 : 8;              // more blocks: less fill/drain, more launch prologues (8: +6 % over 4)
-    if (nb < 2) nb = 2;
-    const int Tb = ((T + nb - 1) / nb + 15) & ~15;        // multiple of the epilogue ring
-    *nb_out = (T + Tb - 1) / Tb;
-    *tb_out = Tb;
-}
-
 struct SeamLayout { int nbuf; size_t bytes_each; bool fine; };
-constexpr int kNoFineGrainedMemory = 1;      // carve_seams: internal, never returned through the ABI
-enum { kLayoutSequential = 0, kLayoutOverlapped = 1 };
-SeamLayout seam_layout(kws_handle h, int B, int T, int which) {
+constexpr int kNoFineGrainedMemory = 1;      // ensure_side_buffers, carve_seams: internal, never returned through the ABI
+
+struct StepPlan {
+    // kStack: the whole stack in one launch, no seam (bf16).  kSequential: one launch per layer.  kPipelined: all L x groups
+    // workgroups in one grid, layer l consuming frame t of layer l-1 as soon as it is published.  kOverlapped: the per-layer
+    // kernels on separate HIP streams over time blocks (step_overlapped).
+    enum Layout : uint8_t { kZeroFrames, kStack, kSequential, kPipelined, kOverlapped } layout;
+    kws_model::LaunchTag tag[8];   // per profiling slot, exactly what kws_last_launch is to report after this step; empty: no launch
+    SeamLayout seams;
+    int nb, Tb;                    // kOverlapped only: time blocks and their length
+    bool streaming;                // some layer addresses its seam through 32-bit buffer offsets (the 2 GiB check)
+};
+
+// The one place that decides kernel family, launch layout, window tail and seams.  Pure: reads the handle, touches nothing.
+// `profiling`: kws_set_profiling's switch (a parameter, so that kws_reserve can ask for both answers); `window`: a decode-window
+// tail that fits the fused form is offered (StepArgs::wt, step_takes_window).
+StepPlan plan_step(const kws_model* h, int B, int T, bool profiling, bool window) {
+    using M = kws_model;
+    // KWS_NO_PIPELINE=1: never the layer-pipelined launch -- what a device without fine-grained memory gets (pipe_disabled), for A/B
+    // runs and for the tests of the layouts that take its place (tests/test_gpu_wrapped.py)
+    static const bool no_pipe = [] { const char* e = getenv("KWS_NO_PIPELINE"); return e && e[0] == '1'; }();
+    static const bool no_tail = [] { const char* e = getenv("KWS_NO_WINDOW_TAIL"); return e && e[0] == '1'; }();     // A/B switch (tools/bench_e2e.py)
     const kws_config& c = h->cfg;
-    const size_t groups = (size_t)kws::groups_of(B);
-    const size_t frame_bytes = groups * (size_t)c.hidden * 16 * sizeof(float);
-    SeamLayout s = {0, 0, false};
-    if (c.precision == KWS_BF16 || T <= 0 || B <= 0) return s;                    // the bf16 stack has no seam
-    const bool int8 = c.precision == KWS_INT8;
-    if (c.num_layers < 2 && !int8) return s;
-    if (which == kLayoutOverlapped) {
-        int nb, Tb;
-        overlap_blocks(T, &nb, &Tb);
-        s.nbuf = 2 * (c.num_layers - 1); s.bytes_each = frame_bytes * Tb;
-        return s;
+    const int L = c.num_layers, H = c.hidden;
+    StepPlan p = {};
+    if (B <= 0 || T <= 0) return p;
+    const long long groups = kws::groups_of(B);
+    const bool fits = h->num_cus > 0 && groups * L <= h->num_cus;      // all L x groups workgroups on the chip at once, one per CU
+    // The tail rides only where the last layer's kernel has a tail instantiation (below, per family), for chunks and windows its LDS
+    // staging holds, and with one group per workgroup: it is ~2 us of latency-bound work at the end of a group.  At the end of the
+    // launch that replaces a ~4 us launch of its own; in a persistent workgroup it would sit between two groups, on the critical
+    // path once per group (measured, bf16, 16384 streams: 0.349-0.359 ms per chunk with the tail against 0.338-0.340 with
+    // window_inc_kernel behind the stack).  Everywhere else window_inc_kernel follows the stack.
+    window = window && !no_tail && T <= kws::kWinTailMaxFrames && groups <= (h->num_cus > 0 ? h->num_cus : 256);
+
+    if (c.precision == KWS_BF16) {
+        p.layout = StepPlan::kStack;
+        p.tag[0] = {M::kBf16Stack, 0, 0, 0, (uint8_t)(window && kws::gru_stack_bf16_takes_window(h->pk.bf_kx0, L))};
+        return p;
     }
-    if (pipeline_eligible(h, B)) { s.nbuf = c.num_layers - 1; s.bytes_each = frame_bytes * T; s.fine = true; return s; }
-    s.nbuf = (c.num_layers > 2 || int8) ? 2 : 1;         // sequential launches ping-pong two buffers
-    s.bytes_each = frame_bytes * T;
-    return s;
+    const bool int8 = c.precision == KWS_INT8, f16 = c.precision == KWS_F16X3;
+    // the cell wrappers exist in the generic kernels only (kws_set_kernel refuses RESIDENT on a wrapped handle)
+    auto resident = [&](int l) {
+        return !h->wrapped && (h->kernel_kind == KWS_KERNEL_RESIDENT || (h->kernel_kind == KWS_KERNEL_AUTO && h->pk.layers[l].resident_ok));
+    };
+    bool any_resident = false, all_resident = true;
+    for (int l = 0; l < L; ++l) { any_resident |= resident(l); all_resident &= resident(l); }
+    const bool f16_streams = f16 && h->pk.f16_generic;      // hidden = 256: weights streamed from L2 (gru_f16x3_generic.hip)
+    p.streaming = f16_streams || (!f16 && !all_resident);
+    // The layer-pipelined launch needs the streaming kernel on every layer; it pays when the layers would otherwise leave CUs idle.
+    // AUTO keeps the resident kernels where they exist even when this launch would be faster (H=128, L=2: +10 % at B <= 2048;
+    // L=4, B=1024: 2.2x; select it with KWS_KERNEL_GENERIC): the two kernel families round differently in the last bit, and a
+    // stream's result must not depend on how many neighbours it is batched or sharded with.
+    const bool pipelined = !h->pipe_disabled && !no_pipe && (c.precision == KWS_FP32 || f16_streams) && L >= 2 &&
+                           h->kernel_kind != KWS_KERNEL_RESIDENT && !any_resident && fits;
+    // Layers overlapped on HIP streams: the pipelined kernel has its own in-kernel pipeline; profiling times one launch after another
+    const bool overlapped = !profiling && c.precision == KWS_FP32 && L >= 2 && L <= 5 && !pipelined && fits && T >= KWS_OVERLAP_MIN_T;
+    p.layout = pipelined ? StepPlan::kPipelined : overlapped ? StepPlan::kOverlapped : StepPlan::kSequential;
+
+    if (pipelined) {      // one launch, timed as the last layer's slot
+        const uint8_t family = f16 ? M::kF16x3Pipelined : h->wrapped ? M::kPipelinedWrapped : M::kPipelined;
+        p.tag[L - 1] = {family, (uint8_t)(H / 64), 0, 0, 0};
+    }
+    for (int l = 0; l < L && !pipelined; ++l) {
+        // int8: no GRU layer is `last` -- every layer hands its output rows on through the seam, and the class projection is its
+        // own OctbitMatMul call over the whole [T,H] block behind the top layer (kOctbitFc; launch_slot)
+        const bool first = l == 0, last = !int8 && l == L - 1;
+        const uint8_t tail = window && last && !overlapped;
+        if (f16_streams) p.tag[l] = {M::kF16x3Generic, (uint8_t)(H / 64), first, last, 0};
+        else if (f16) p.tag[l] = {M::kF16x3, (uint8_t)(first ? h->pk.f16_kx0 : 4), first, last, tail};
+        else if (int8 && h->pk.oct[l].quantised) p.tag[l] = {(uint8_t)(l == L - 1 ? M::kOctbitFc : M::kOctbit), 0, 0, 0, 0};
+        else if (resident(l))
+            p.tag[l] = {M::kResident, (uint8_t)h->pk.layers[l].kcx_res, first, last, (uint8_t)(tail && kws::gru_resident_takes_window(first, last))};
+        else p.tag[l] = {(uint8_t)(h->wrapped ? M::kGenericWrapped : M::kGeneric), (uint8_t)(H / 64), first, last, 0};
+    }
+
+    if (L >= 2 || int8) {      // a single fp32 / f16x3 layer has no seam
+        const size_t frame_bytes = (size_t)groups * (size_t)H * 16 * sizeof(float);
+        if (pipelined) p.seams = {L - 1, frame_bytes * T, true};      // read by another XCD while the kernel runs: fine-grained memory
+        else if (overlapped) {
+            const int nb = std::max(2, std::min(8, T / 32));      // more blocks: less fill/drain, more launch prologues (8: +6 % over 4)
+            p.Tb = ((T + nb - 1) / nb + 15) & ~15;                // multiple of the epilogue ring
+            p.nb = (T + p.Tb - 1) / p.Tb;
+            p.seams = {2 * (L - 1), frame_bytes * p.Tb, false};       // double-buffered per block parity
+        } else p.seams = {(L > 2 || int8) ? 2 : 1, frame_bytes * T, false};      // sequential launches ping-pong two buffers
+    }
+    return p;
 }
 
+// ---- scratch: the arena a plan's seams are carved from, and the side buffers ----------------------------------------
 // Grows the arena if this layout does not fit (the only place kws_step can synchronise: the old block may still be in
 // use) and points h->scratch[] at the call's buffers.
 int carve_seams(kws_handle h, const SeamLayout& want) {
@@ -84,7 +112,6 @@ int carve_seams(kws_handle h, const SeamLayout& want) {
         KWS_HIP(hipDeviceSynchronize());
         if (A.base) { hipFree(A.base); A.base = nullptr; A.bytes = 0; }
         hipError_t e;
-        // pipelined seams are read by another XCD while the kernel runs: fine-grained (uncached, coherent) memory
         if (s.fine) e = hipExtMallocWithFlags(reinterpret_cast<void**>(&A.base), need, hipDeviceMallocFinegrained);
         else e = hipMalloc(reinterpret_cast<void**>(&A.base), need);
         if (e != hipSuccess) {
@@ -102,7 +129,7 @@ int carve_seams(kws_handle h, const SeamLayout& want) {
 }
 
 // Everything besides the seams that depends on the batch size: int8 exchange buffers, the pipelined launch's counters.
-int ensure_side_buffers(kws_handle h, int B) {
+int ensure_side_buffers(kws_handle h, int B, bool pipelined) {
     const size_t groups = (size_t)kws::groups_of(B);
     if (h->cfg.precision == KWS_INT8 && groups > h->oct_groups) {
         KWS_HIP(hipDeviceSynchronize());
@@ -116,7 +143,7 @@ int ensure_side_buffers(kws_handle h, int B) {
         h->oct_groups = groups;
         ++h->scratch_allocs;
     }
-    if (pipeline_eligible(h, B)) {
+    if (pipelined) {
         if (!h->pipe_error_host) {
             KWS_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->pipe_error_host), sizeof(int), hipHostMallocMapped));
             *h->pipe_error_host = 0;
@@ -130,8 +157,7 @@ int ensure_side_buffers(kws_handle h, int B) {
                                       hipDeviceMallocFinegrained) != hipSuccess) {
                 (void)hipGetLastError();
                 h->pipe_ready = nullptr;
-                h->pipe_disabled = true;         // no fine-grained device memory here: layer-by-layer launches from now on
-                return KWS_OK;
+                return kNoFineGrainedMemory;
             }
             h->pipe_groups = groups;
             ++h->scratch_allocs;
@@ -140,14 +166,17 @@ int ensure_side_buffers(kws_handle h, int B) {
     return KWS_OK;
 }
 
-// Seams of the sequential / pipelined layout for a call of shape (B, T).
-int ensure_scratch(kws_handle h, int B, int T) {
-    int rc = ensure_side_buffers(h, B);
-    if (rc != KWS_OK) return rc;
-    rc = carve_seams(h, seam_layout(h, B, T, kLayoutSequential));
-    if (rc == kNoFineGrainedMemory) {    // fine-grained memory unavailable: give the pipelined launch up for this handle
+// The buffers `plan` launches with.  A device without fine-grained memory gives the pipelined launch up for this handle, and the
+// call is planned again, once: this call runs its layers one launch after another (planned as under profiling, whose one effect
+// is that the layers are not overlapped); only later calls may overlap them.
+int provision(kws_handle h, StepPlan& plan, int B, int T, bool window) {
+    if (plan.layout == StepPlan::kStack) return KWS_OK;
+    int rc = ensure_side_buffers(h, B, plan.layout == StepPlan::kPipelined);
+    if (rc == KWS_OK) rc = carve_seams(h, plan.seams);
+    if (rc == kNoFineGrainedMemory) {
         h->pipe_disabled = true;
-        rc = carve_seams(h, seam_layout(h, B, T, kLayoutSequential));
+        plan = plan_step(h, B, T, /*profiling=*/true, window);
+        rc = carve_seams(h, plan.seams);
     }
     return rc;
 }
@@ -165,26 +194,26 @@ int check_pipe_error(kws_handle h) {
     return KWS_OK;
 }
 
-// The profiling slot of one launch (kws_set_profiling): profile_begin takes two events from the pool (or creates them) and
-// records the first; profile_end records the second and queues the pair for kws_kernel_times.  Inert while profiling is off.
-int profile_begin(kws_model* h, hipStream_t st, kws_model::Pending& pd) {
-    if (!h->profiling) return KWS_OK;
+// One profiling slot around `launch` (kws_set_profiling): two events from the pool (or new ones), recorded before and behind it
+// and queued for kws_kernel_times.  Just `launch` while profiling is off.
+template <typename Launch>
+int profiled(kws_model* h, hipStream_t st, int slot, Launch&& launch) {
+    if (!h->profiling) return launch();
+    kws_model::Pending pd = {slot, nullptr, nullptr};
     for (hipEvent_t* ev : {&pd.a, &pd.b}) {
         if (!h->event_pool.empty()) { *ev = h->event_pool.back(); h->event_pool.pop_back(); }
         else KWS_HIP(hipEventCreate(ev));
     }
     KWS_HIP(hipEventRecord(pd.a, st));
-    return KWS_OK;
-}
-int profile_end(kws_model* h, hipStream_t st, const kws_model::Pending& pd) {
-    if (!h->profiling) return KWS_OK;
+    KWS_TRY(launch());
     KWS_HIP(hipEventRecord(pd.b, st));
     h->pending.push_back(pd);
     return KWS_OK;
 }
 
-// The last layer's epilogue fields (every layer's parameters carry them), from the step's arguments.  A launch over the time
-// block [t0, t0 + frames) of the call (step_overlapped) passes t0 and its length: the rows keep the call's T as their stride.
+// ---- one family's parameters from the step's arguments ---------------------------------------------------------------
+// The last layer's epilogue fields (every layer's parameters carry them).  A launch over the time block [t0, t0 + frames) of the
+// call (step_overlapped) passes t0 and its length: the rows keep the call's T as their stride.
 void set_epilogue(kws::GruLayerParams& p, const StepArgs& a, const kws_config& c, bool last, int t0 = 0, int frames = 0) {
     const int C = c.num_classes;
     p.logits = a.logits ? a.logits + (size_t)t0 * C : nullptr;
@@ -198,15 +227,11 @@ void set_epilogue(kws::GruLayerParams& p, const StepArgs& a, const kws_config& c
     if (frames) { p.t_stride = a.T; p.t_base = t0; }
     if (a.wt && last) p.win = *a.wt;
 }
-// Head of a layer-pipelined launch (GruStackParams / GruF16StackParams): the frame counters cleared on the call's stream,
-// the stack's shape and block map
+// Head of a layer-pipelined launch (GruStackParams / GruF16StackParams): the stack's shape and block map
 template <typename Stack>
-int begin_pipelined(const kws_model* h, Stack& sp, int B, hipStream_t st) {
-    const int L = h->cfg.num_layers;
-    KWS_HIP(hipMemsetAsync(h->pipe_ready, 0, (size_t)L * h->pipe_groups * sizeof(int), st));
+void begin_pipelined(const kws_model* h, Stack& sp, int B) {
     memset(&sp, 0, sizeof(sp));
-    sp.L = L; sp.G = kws::groups_of(B); sp.xcd_affine = kws::pipelined_xcd_affine(L);
-    return KWS_OK;
+    sp.L = h->cfg.num_layers; sp.G = kws::groups_of(B); sp.xcd_affine = kws::pipelined_xcd_affine(sp.L);
 }
 // ... and the frame counters of layer l in it
 void set_pipeline(kws::GruLayerParams& p, const kws_model* h, int l, bool last) {
@@ -215,7 +240,7 @@ void set_pipeline(kws::GruLayerParams& p, const kws_model* h, int l, bool last) 
     p.pipe_error = h->pipe_error_dev;
 }
 
-// Layer l of the fp32 kernels over the whole call (step_overlapped narrows it to a time block)
+// Layer l of the fp32 kernels over the whole call (launch_slot narrows it to a time block)
 void set_fp32_layer(kws::GruLayerParams& p, const kws_model* h, const StepArgs& a, int l, bool resident, bool last) {
     const LayerDev& Ld = h->pk.layers[l];
     const size_t state_off = (size_t)l * a.B * h->cfg.hidden;
@@ -238,7 +263,6 @@ void set_fp32_layer(kws::GruLayerParams& p, const kws_model* h, const StepArgs& 
     p.I = Ld.in_dim;
     p.KCX = resident ? Ld.kcx_res : Ld.kcx_gen;
 }
-
 // ... and its cell wrappers (wrapped handles)
 kws::GruWrapLayer wrap_layer(const kws_model* h, int l) {
     kws::GruWrapLayer w = {nullptr, 0.f, 0};
@@ -246,13 +270,159 @@ kws::GruWrapLayer wrap_layer(const kws_model* h, int l) {
     w.residual = h->wrap.use_residual && l > 0;
     return w;
 }
-// the generic launch of one layer, plain or wrapped; its kernel as a launch tag
-hipError_t launch_generic(const kws_model* h, const kws::GruLayerParams& p, int l, bool first, bool last, hipStream_t st) {
-    return h->wrapped ? kws::launch_gru_layer_generic_wrapped(p, wrap_layer(h, l), h->cfg.hidden, first, last, st)
-                      : kws::launch_gru_layer_generic(p, h->cfg.hidden, first, last, st);
+
+// Layer l of the f16x3 kernels; the seams (same size as the fp32 ones) hold the layer outputs already split into fp16 pairs
+void set_f16_layer(kws::GruF16Params& fp, const kws_model* h, const StepArgs& a, int l, bool last) {
+    const size_t state_off = (size_t)l * a.B * h->cfg.hidden;
+    memset(&fp, 0, sizeof(fp));
+    fp.w = reinterpret_cast<const uint4*>(h->d_weights + h->pk.f16_w[l]);
+    fp.bias = h->d_weights + h->pk.layers[l].bias;
+    fp.wfc = reinterpret_cast<const uint4*>(h->d_weights + h->pk.f16_wfc);
+    fp.bfc = h->d_weights + h->pk.bfc_off;
+    fp.x_mel = a.mel;
+    fp.x_prev = l == 0 ? nullptr : reinterpret_cast<const uint4*>(h->scratch[(l - 1) % h->nscratch]);
+    fp.h_out = last ? nullptr : reinterpret_cast<uint4*>(h->scratch[l % h->nscratch]);
+    fp.state_in = a.state_in + state_off;
+    fp.state_out = a.state_out + state_off;
+    fp.seq_len = a.seq_len; fp.reset = a.reset_mask;
+    set_epilogue(fp.epi, a, h->cfg, last);
+    fp.B = a.B; fp.T = a.T; fp.I = h->pk.layers[l].in_dim;
 }
-kws_model::LaunchTag generic_tag(const kws_model* h, bool first, bool last) {
-    return {(uint8_t)(h->wrapped ? kws_model::kGenericWrapped : kws_model::kGeneric), (uint8_t)(h->cfg.hidden / 64), first, last, 0};
+
+// Both layers of the bf16 stack
+void set_bf16_stack(kws::GruBf16Params& bp, const kws_model* h, const StepArgs& a) {
+    const int L = h->cfg.num_layers;
+    memset(&bp, 0, sizeof(bp));
+    for (int l = 0; l < L; ++l) {
+        bp.w[l] = reinterpret_cast<const uint4*>(h->d_weights + h->pk.bf_w[l]);
+        bp.bias[l] = h->d_weights + h->pk.layers[l].bias;
+    }
+    bp.wfc = reinterpret_cast<const uint4*>(h->d_weights + h->pk.bf_wfc);
+    bp.bfc = h->d_weights + h->pk.bfc_off;
+    bp.x_mel = a.mel; bp.state_in = a.state_in; bp.state_out = a.state_out;
+    bp.seq_len = a.seq_len; bp.reset = a.reset_mask;
+    set_epilogue(bp.epi, a, h->cfg, true);
+    bp.B = a.B; bp.T = a.T; bp.I = h->cfg.n_mel; bp.L = L;
+}
+
+// Quantised layer l of the int8 graph, and the class projection behind its top layer
+void set_octbit_layer(kws::GruOctbitParams& op, const kws_model* h, const StepArgs& a, int l) {
+    const PackedWeights::OctLayer& O = h->pk.oct[l];
+    const size_t state_off = (size_t)l * a.B * h->cfg.hidden;
+    memset(&op, 0, sizeof(op));
+    op.wg = reinterpret_cast<const uint32_t*>(h->d_weights + O.wg);
+    op.wc = reinterpret_cast<const uint32_t*>(h->d_weights + O.wc);
+    op.bias = h->d_weights + h->pk.layers[l].bias; op.b127 = h->d_weights + O.b127;
+    op.scale_g = O.scale_g; op.scale_c = O.scale_c;
+    op.x_prev = l == 0 ? nullptr : h->scratch[(l - 1) % h->nscratch];
+    op.h_out = h->scratch[l % h->nscratch];
+    op.state_in = a.state_in + state_off; op.state_out = a.state_out + state_off;
+    op.seq_len = a.seq_len; op.reset = a.reset_mask;
+    op.aq = h->oct_aq; op.B = a.B; op.T = a.T;
+    op.range = (l == h->cfg.num_layers - 1) ? h->oct_range : nullptr;
+}
+void set_octbit_fc(kws::OctbitFcParams& fp, const kws_model* h, const StepArgs& a) {
+    const kws_config& c = h->cfg;
+    const int top = c.num_layers - 1;
+    memset(&fp, 0, sizeof(fp));
+    fp.wfc = reinterpret_cast<const uint32_t*>(h->d_weights + h->pk.oct_wfc);
+    fp.b127 = h->d_weights + h->pk.oct_b127fc;
+    fp.bfc = h->d_weights + h->pk.bfc_off;
+    fp.scale_w = h->pk.oct_scale_fc;
+    fp.h_top = h->scratch[top % h->nscratch];
+    fp.range = h->oct_range;
+    fp.range_ready = h->pk.oct[top].quantised ? 1 : 0;
+    fp.prev_in = a.prev_word ? h->oct_prev : nullptr;
+    fp.logits = a.logits; fp.softmax = a.softmax; fp.tokens = a.tokens; fp.prev_word = a.prev_word;
+    fp.decode_thres = a.decode2_thres; fp.value_clip = c.value_clip; fp.use_relu = c.use_relu;
+    fp.B = a.B; fp.T = a.T; fp.C = c.num_classes;
+}
+
+// ---- the launches ----------------------------------------------------------------------------------------------------
+// The launch of profiling slot l as the plan tagged it, on `st`.  step_overlapped passes the time block [t0, t0 + frames) of the
+// call: seams double-buffered per block parity, and behind block 0 the state is the one the block before left in state_out.
+int launch_slot(const kws_model* h, const StepArgs& a, const StepPlan& plan, int l, hipStream_t st, int t0 = 0, int frames = 0) {
+    using M = kws_model;
+    const kws_config& c = h->cfg;
+    const int H = c.hidden, L = c.num_layers;
+    const M::LaunchTag& t = plan.tag[l];
+    hipError_t e = hipSuccess;
+    const char* what = "";
+    switch (t.family) {
+        case M::kBf16Stack: {
+            kws::GruBf16Params bp;
+            set_bf16_stack(bp, h, a);
+            e = kws::launch_gru_stack_bf16(bp, h->pk.bf_kx0, L, st); what = "launch gru_stack_bf16";
+            break;
+        }
+        case M::kF16x3: case M::kF16x3Generic: {
+            kws::GruF16Params fp;
+            set_f16_layer(fp, h, a, l, t.last);
+            if (t.family == M::kF16x3) { e = kws::launch_gru_layer_f16x3(fp, t.first, t.last, st); what = "launch gru_layer_f16x3"; }
+            else { e = kws::launch_gru_layer_f16x3_generic(fp, H, t.first, t.last, st); what = "launch gru_layer_f16x3_generic"; }
+            break;
+        }
+        case M::kF16x3Pipelined: {
+            kws::GruF16StackParams sp;
+            begin_pipelined(h, sp, a.B);
+            for (int k = 0; k < L; ++k) {
+                set_f16_layer(sp.layer[k], h, a, k, k == L - 1);
+                set_pipeline(sp.layer[k].epi, h, k, k == L - 1);
+            }
+            e = kws::launch_gru_stack_f16x3_pipelined(sp, H, st); what = "launch gru_stack_f16x3_pipelined";
+            break;
+        }
+        case M::kPipelined: case M::kPipelinedWrapped: {
+            kws::GruStackParams sp;
+            begin_pipelined(h, sp, a.B);
+            for (int k = 0; k < L; ++k) {
+                set_fp32_layer(sp.layer[k], h, a, k, false, k == L - 1);
+                set_pipeline(sp.layer[k], h, k, k == L - 1);
+            }
+            if (t.family == M::kPipelinedWrapped) {
+                kws::GruWrapParams wp;
+                memset(&wp, 0, sizeof(wp));
+                for (int k = 0; k < L; ++k) wp.layer[k] = wrap_layer(h, k);
+                e = kws::launch_gru_stack_generic_pipelined_wrapped(sp, wp, H, st);
+            } else {
+                e = kws::launch_gru_stack_generic_pipelined(sp, H, st);
+            }
+            what = "launch gru_stack_generic_pipelined";
+            break;
+        }
+        case M::kOctbit: case M::kOctbitFc: {
+            kws::GruOctbitParams op;
+            set_octbit_layer(op, h, a, l);
+            e = kws::launch_gru_layer_octbit(op, st); what = "launch gru_layer_octbit";
+            break;
+        }
+        case M::kResident: case M::kGeneric: case M::kGenericWrapped: {
+            const bool first = l == 0;
+            kws::GruLayerParams p;
+            set_fp32_layer(p, h, a, l, t.family == M::kResident, t.last);
+            if (plan.layout == StepPlan::kOverlapped) {
+                const int parity = (t0 / plan.Tb) & 1;
+                p.x_mel = a.mel + (size_t)t0 * c.n_mel;
+                p.x_prev = first ? nullptr : h->scratch[2 * (l - 1) + parity];
+                p.h_out = t.last ? nullptr : h->scratch[2 * l + parity];
+                if (t0 > 0) { p.state_in = p.state_out; p.reset = nullptr; }
+                set_epilogue(p, a, c, t.last, t0, frames);
+                what = "launch (overlapped layers)";
+            } else {
+                what = t.family == M::kResident ? "launch gru_layer_resident" : "launch gru_layer_generic";
+            }
+            if (t.family == M::kResident) e = kws::launch_gru_layer_resident(p, t.first, t.last, st);
+            else if (t.family == M::kGenericWrapped) e = kws::launch_gru_layer_generic_wrapped(p, wrap_layer(h, l), H, t.first, t.last, st);
+            else e = kws::launch_gru_layer_generic(p, H, t.first, t.last, st);
+            break;
+        }
+        default: return KWS_OK;      // an empty slot: its layer runs inside another slot's launch
+    }
+    if (e != hipSuccess) return hip_fail(e, what);
+    if (c.precision != KWS_INT8 || l != L - 1) return KWS_OK;
+    kws::OctbitFcParams fp;      // the class projection, inside the top layer's slot whichever kernel ran that layer
+    set_octbit_fc(fp, h, a);
+    return hip_done(kws::launch_octbit_fc(fp, st), "launch octbit_fc");
 }
 
 // Layers on separate HIP streams, time-blocked.  When L x groups workgroups fit the chip at once, the layers of a
@@ -261,16 +431,9 @@ kws_model::LaunchTag generic_tag(const kws_model* h, bool first, bool last) {
 // The kernels are the ones a plain call uses -- a call on frames [t0, t1) with the state carried is bit-identical to
 // the corresponding slice of one long call (tests/test_gpu_parity.py) -- so the result does not depend on whether
 // this path was taken.  Wall time ~ (slowest layer) x (1 + 1/blocks) instead of the sum over layers.
-int step_overlapped(kws_handle h, const StepArgs& a) {
-    const kws_config& c = h->cfg;
-    const int H = c.hidden, L = c.num_layers, B = a.B, T = a.T;
+int step_overlapped(kws_handle h, const StepArgs& a, const StepPlan& plan) {
+    const int L = h->cfg.num_layers, T = a.T, nb = plan.nb, Tb = plan.Tb;
     const hipStream_t st = a.stream;
-    int nb, Tb;
-    overlap_blocks(T, &nb, &Tb);
-    {
-        const int rc = carve_seams(h, seam_layout(h, B, T, kLayoutOverlapped));
-        if (rc != KWS_OK) return rc;
-    }
     for (int l = 1; l < L; ++l)
         if (!h->lane_stream[l]) KWS_HIP(hipStreamCreateWithFlags(&h->lane_stream[l], hipStreamNonBlocking));
     while ((int)h->ovl_events.size() < L * nb + 1) {
@@ -284,22 +447,11 @@ int step_overlapped(kws_handle h, const StepArgs& a) {
     for (int k = 0; k < nb; ++k) {
         const int t0 = k * Tb, tk = (T - t0 < Tb) ? T - t0 : Tb;
         for (int l = 0; l < L; ++l) {
-            const LayerDev& Ld = h->pk.layers[l];
             const bool first = l == 0, last = l == L - 1;
-            const bool resident = is_resident(h, Ld);
             hipStream_t sx = first ? st : h->lane_stream[l];
             if (!first) KWS_HIP(hipStreamWaitEvent(sx, done(l - 1, k), 0));                    // its input block
             if (!last && k >= 2) KWS_HIP(hipStreamWaitEvent(sx, done(l + 1, k - 2), 0));       // its output buffer is free again
-            kws::GruLayerParams p;
-            set_fp32_layer(p, h, a, l, resident, last);
-            p.x_mel = a.mel + (size_t)t0 * c.n_mel;
-            p.x_prev = first ? nullptr : h->scratch[2 * (l - 1) + (k & 1)];
-            p.h_out = last ? nullptr : h->scratch[2 * l + (k & 1)];
-            if (k > 0) { p.state_in = a.state_out + (size_t)l * B * H; p.reset = nullptr; }    // the block before left the state there
-            set_epilogue(p, a, c, last, t0, tk);
-            hipError_t e = resident ? kws::launch_gru_layer_resident(p, first, last, sx) : launch_generic(h, p, l, first, last, sx);
-            if (e != hipSuccess) return hip_fail(e, "launch (overlapped layers)");
-            if (k == 0) h->launch_tag[l] = resident ? kws_model::LaunchTag{kws_model::kResident, (uint8_t)p.KCX, first, last, 0} : generic_tag(h, first, last);
+            KWS_TRY(launch_slot(h, a, plan, l, sx, t0, tk));
             KWS_HIP(hipEventRecord(done(l, k), sx));
         }
     }
@@ -316,14 +468,11 @@ int step_body(kws_handle h, const StepArgs& a) {
     const kws_config& c = h->cfg;
     const int H = c.hidden, L = c.num_layers, B = a.B, T = a.T;
     const hipStream_t st = a.stream;
-    {
-        const int rc = check_pipe_error(h);      // raised by an earlier layer-pipelined step of this handle
-        if (rc != KWS_OK) return rc;
-        // the handle's weights and scratch live on the device that was current at kws_create
-        int dev = -1;
-        if (hipGetDevice(&dev) == hipSuccess && dev != h->device)
-            return fail(KWS_ERR_INVALID_ARGUMENT, "handle was created on device %d, the current device is %d", h->device, dev);
-    }
+    KWS_TRY(check_pipe_error(h));      // raised by an earlier layer-pipelined step of this handle
+    // the handle's weights and scratch live on the device that was current at kws_create
+    int dev = -1;
+    if (hipGetDevice(&dev) == hipSuccess && dev != h->device)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "handle was created on device %d, the current device is %d", h->device, dev);
     if (h->ovl_tail_valid) {
         // the previous call ran its upper layers on the handle's own streams: whatever stream this call comes in on,
         // it must not touch the seam buffers (or reallocate them) before those kernels are done
@@ -333,202 +482,44 @@ int step_body(kws_handle h, const StepArgs& a) {
     }
     if (T == 0) {
         // dynamic_rnn over zero frames hands the initial state back -- and clean_state() (detector.py:313-316) has already
-        // zeroed it for the streams the mask names
-        if (a.reset_mask) {
-            hipError_t e = kws::launch_state_passthrough(a.state_in, a.state_out, a.reset_mask, a.prev_word, L, B, H, st);
-            if (e != hipSuccess) return hip_fail(e, "launch state_passthrough");
-        } else if (a.state_out != a.state_in) {
+        // zeroed it for the streams the mask names.  No GRU kernel runs: h->launch_tag stays what the step before left.
+        if (a.reset_mask)
+            return hip_done(kws::launch_state_passthrough(a.state_in, a.state_out, a.reset_mask, a.prev_word, L, B, H, st), "launch state_passthrough");
+        if (a.state_out != a.state_in)
             KWS_HIP(hipMemcpyAsync(a.state_out, a.state_in, (size_t)L * B * H * sizeof(float), hipMemcpyDeviceToDevice, st));
-        }
         return KWS_OK;
     }
+    StepPlan plan = plan_step(h, B, T, h->profiling, a.wt != nullptr);
     if (!a.mel) return fail(KWS_ERR_INVALID_ARGUMENT, "mel is null");
-    if (c.precision != KWS_BF16 && (c.precision != KWS_F16X3 || h->pk.f16_generic)) {
-        // the streaming kernels address a group's seam (T x H/16 KiB) through buffer instructions with 32-bit offsets
-        bool streaming = c.precision == KWS_F16X3;
-        for (const auto& Ld : h->pk.layers) streaming |= !is_resident(h, Ld);
-        if (streaming && (long long)T * (H / 16) >= (1LL << 21))
-            return fail(KWS_ERR_UNSUPPORTED, "T=%d frames of hidden=%d exceed the 2 GiB a stream group's seam may span: split the call "
-                        "(state carried across calls gives identical results)", T, H);
-    }
+    // the streaming kernels address a group's seam (T x H/16 KiB) through buffer instructions with 32-bit offsets
+    if (plan.streaming && (long long)T * (H / 16) >= (1LL << 21))
+        return fail(KWS_ERR_UNSUPPORTED, "T=%d frames of hidden=%d exceed the 2 GiB a stream group's seam may span: split the call "
+                    "(state carried across calls gives identical results)", T, H);
     if ((reinterpret_cast<uintptr_t>(a.mel) & 15) != 0) return fail(KWS_ERR_INVALID_ARGUMENT, "mel must be 16-byte aligned");
-    if (c.precision == KWS_BF16) {
-        kws::GruBf16Params bp;
-        memset(&bp, 0, sizeof(bp));
-        for (int l = 0; l < L; ++l) {
-            bp.w[l] = reinterpret_cast<const uint4*>(h->d_weights + h->pk.bf_w[l]);
-            bp.bias[l] = h->d_weights + h->pk.layers[l].bias;
-        }
-        bp.wfc = reinterpret_cast<const uint4*>(h->d_weights + h->pk.bf_wfc);
-        bp.bfc = h->d_weights + h->pk.bfc_off;
-        bp.x_mel = a.mel; bp.state_in = a.state_in; bp.state_out = a.state_out;
-        bp.seq_len = a.seq_len; bp.reset = a.reset_mask;
-        set_epilogue(bp.epi, a, c, true);
-        bp.B = a.B; bp.T = a.T; bp.I = c.n_mel; bp.L = L;
-        kws_model::Pending pd = {0, nullptr, nullptr};
-        const int rc = profile_begin(h, st, pd);
-        if (rc != KWS_OK) return rc;
-        hipError_t e = kws::launch_gru_stack_bf16(bp, h->pk.bf_kx0, L, st);
-        if (e != hipSuccess) return hip_fail(e, "launch gru_stack_bf16");
-        h->launch_tag[0] = {kws_model::kBf16Stack, 0, 0, 0, (uint8_t)(a.wt != nullptr)};
-        for (int l = 1; l < L; ++l) h->launch_tag[l] = {};
-        return profile_end(h, st, pd);
+    KWS_TRY(provision(h, plan, B, T, a.wt != nullptr));
+    if (plan.layout == StepPlan::kOverlapped) {
+        KWS_TRY(step_overlapped(h, a, plan));
+    } else {      // kStack, kSequential, kPipelined: every tagged slot is one launch on the call's stream
+        if (c.precision == KWS_INT8 && a.prev_word)
+            KWS_HIP(hipMemcpyAsync(h->oct_prev, a.prev_word, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        if (plan.layout == StepPlan::kPipelined)      // the frame counters, cleared on the call's stream first
+            KWS_HIP(hipMemsetAsync(h->pipe_ready, 0, (size_t)L * h->pipe_groups * sizeof(int), st));
+        for (int l = 0; l < L; ++l)
+            if (plan.tag[l].family != kws_model::kNone) KWS_TRY(profiled(h, st, l, [&] { return launch_slot(h, a, plan, l, st); }));
     }
-    if (c.precision == KWS_F16X3) {
-        // one launch per layer; the seams (same size as the fp32 ones) hold the layer outputs already split into fp16 pairs
-        int rc = ensure_scratch(h, B, T);
-        if (rc != KWS_OK) return rc;
-        // hidden = 256: weights streamed from L2; all L x groups workgroups in ONE layer-pipelined grid when they fit the chip
-        const bool f16_pipelined = h->pk.f16_generic && pipeline_eligible(h, B);
-        kws::GruF16StackParams fsp;
-        if (f16_pipelined && (rc = begin_pipelined(h, fsp, B, st)) != KWS_OK) return rc;
-        for (int l = 0; l < L; ++l) {
-            const bool first = l == 0, last = l == L - 1;
-            kws::GruF16Params fp;
-            memset(&fp, 0, sizeof(fp));
-            fp.w = reinterpret_cast<const uint4*>(h->d_weights + h->pk.f16_w[l]);
-            fp.bias = h->d_weights + h->pk.layers[l].bias;
-            fp.wfc = reinterpret_cast<const uint4*>(h->d_weights + h->pk.f16_wfc);
-            fp.bfc = h->d_weights + h->pk.bfc_off;
-            fp.x_mel = a.mel;
-            fp.x_prev = first ? nullptr : reinterpret_cast<const uint4*>(h->scratch[(l - 1) % h->nscratch]);
-            fp.h_out = last ? nullptr : reinterpret_cast<uint4*>(h->scratch[l % h->nscratch]);
-            fp.state_in = a.state_in + (size_t)l * B * H;
-            fp.state_out = a.state_out + (size_t)l * B * H;
-            fp.seq_len = a.seq_len; fp.reset = a.reset_mask;
-            set_epilogue(fp.epi, a, c, last);
-            fp.B = B; fp.T = a.T; fp.I = h->pk.layers[l].in_dim;
-            if (f16_pipelined) {
-                set_pipeline(fp.epi, h, l, last);
-                fsp.layer[l] = fp;
-                h->launch_tag[l] = {};
-                if (!last) continue;
-            }
-            kws_model::Pending pd = {l, nullptr, nullptr};
-            rc = profile_begin(h, st, pd);
-            if (rc != KWS_OK) return rc;
-            hipError_t e;
-            if (f16_pipelined) {
-                e = kws::launch_gru_stack_f16x3_pipelined(fsp, H, st);        // timed as the last layer's slot
-                if (e != hipSuccess) return hip_fail(e, "launch gru_stack_f16x3_pipelined");
-                h->launch_tag[l] = {kws_model::kF16x3Pipelined, (uint8_t)(H / 64), 0, 0};
-            } else if (h->pk.f16_generic) {
-                e = kws::launch_gru_layer_f16x3_generic(fp, H, first, last, st);
-                if (e != hipSuccess) return hip_fail(e, "launch gru_layer_f16x3_generic");
-                h->launch_tag[l] = {kws_model::kF16x3Generic, (uint8_t)(H / 64), first, last};
-            } else {
-                e = kws::launch_gru_layer_f16x3(fp, first, last, st);
-                if (e != hipSuccess) return hip_fail(e, "launch gru_layer_f16x3");
-                h->launch_tag[l] = {kws_model::kF16x3, (uint8_t)(first ? h->pk.f16_kx0 : 4), first, last, (uint8_t)(a.wt != nullptr && last)};
-            }
-            rc = profile_end(h, st, pd);
-            if (rc != KWS_OK) return rc;
-        }
-        return KWS_OK;
-    }
-    if (overlap_eligible(h, B, T)) return step_overlapped(h, a);
-    int rc = ensure_scratch(h, B, T);
-    if (rc != KWS_OK) return rc;
-
-    const bool int8 = c.precision == KWS_INT8;
-    if (int8 && a.prev_word)
-        KWS_HIP(hipMemcpyAsync(h->oct_prev, a.prev_word, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
-    // layer-pipelined launch (gru_stack_generic_pipelined): all layers of all groups in one grid
-    const bool pipelined = pipeline_eligible(h, B);
-    kws::GruStackParams sp;
-    if (pipelined && (rc = begin_pipelined(h, sp, B, st)) != KWS_OK) return rc;
-    for (int l = 0; l < L; ++l) {
-        // int8: every GRU layer hands its output rows to the next stage through the xl scratch; the class
-        // projection is its own OctbitMatMul call over the whole [T,H] block (launch_octbit_fc below)
-        const bool first = l == 0, last = !int8 && l == L - 1;
-        const bool resident = !pipelined && is_resident(h, h->pk.layers[l]);
-        kws::GruLayerParams p;
-        set_fp32_layer(p, h, a, l, resident, last);
-        if (pipelined) {
-            set_pipeline(p, h, l, last);
-            sp.layer[l] = p;
-            if (!last) continue;
-        }
-        kws_model::Pending pd = {l, nullptr, nullptr};
-        rc = profile_begin(h, st, pd);
-        if (rc != KWS_OK) return rc;
-        hipError_t e;
-        if (pipelined) {
-            if (h->wrapped) {
-                kws::GruWrapParams wp;
-                memset(&wp, 0, sizeof(wp));
-                for (int k = 0; k < L; ++k) wp.layer[k] = wrap_layer(h, k);
-                e = kws::launch_gru_stack_generic_pipelined_wrapped(sp, wp, H, st);
-            } else {
-                e = kws::launch_gru_stack_generic_pipelined(sp, H, st);   // timed as the last layer's slot
-            }
-            if (e != hipSuccess) return hip_fail(e, "launch gru_stack_generic_pipelined");
-        } else if (int8 && h->pk.oct[l].quantised) {
-            const PackedWeights::OctLayer& O = h->pk.oct[l];
-            kws::GruOctbitParams op;
-            memset(&op, 0, sizeof(op));
-            op.wg = reinterpret_cast<const uint32_t*>(h->d_weights + O.wg);
-            op.wc = reinterpret_cast<const uint32_t*>(h->d_weights + O.wc);
-            op.bias = p.bias; op.b127 = h->d_weights + O.b127;
-            op.scale_g = O.scale_g; op.scale_c = O.scale_c;
-            op.x_prev = p.x_prev; op.h_out = p.h_out;
-            op.state_in = p.state_in; op.state_out = p.state_out;
-            op.seq_len = a.seq_len; op.reset = a.reset_mask;
-            op.aq = h->oct_aq; op.B = B; op.T = a.T;
-            op.range = (l == L - 1) ? h->oct_range : nullptr;
-            e = kws::launch_gru_layer_octbit(op, st);
-            if (e != hipSuccess) return hip_fail(e, "launch gru_layer_octbit");
-        } else {
-            e = resident ? kws::launch_gru_layer_resident(p, first, last, st) : launch_generic(h, p, l, first, last, st);
-            if (e != hipSuccess) return hip_fail(e, resident ? "launch gru_layer_resident" : "launch gru_layer_generic");
-        }
-        if (pipelined) {
-            h->launch_tag[l] = {(uint8_t)(h->wrapped ? kws_model::kPipelinedWrapped : kws_model::kPipelined), (uint8_t)(H / 64), 0, 0};
-            for (int k = 0; k < l; ++k) h->launch_tag[k] = {};
-        } else if (int8 && h->pk.oct[l].quantised) h->launch_tag[l] = {(uint8_t)(l == L - 1 ? kws_model::kOctbitFc : kws_model::kOctbit), 0, 0, 0};
-        else if (resident) h->launch_tag[l] = {kws_model::kResident, (uint8_t)p.KCX, first, last, (uint8_t)(a.wt != nullptr && last)};
-        else h->launch_tag[l] = generic_tag(h, first, last);
-        if (int8 && l == L - 1) {
-            kws::OctbitFcParams fp;
-            memset(&fp, 0, sizeof(fp));
-            fp.wfc = reinterpret_cast<const uint32_t*>(h->d_weights + h->pk.oct_wfc);
-            fp.b127 = h->d_weights + h->pk.oct_b127fc;
-            fp.bfc = h->d_weights + h->pk.bfc_off;
-            fp.scale_w = h->pk.oct_scale_fc;
-            fp.h_top = h->scratch[l % h->nscratch];
-            fp.range = h->oct_range;
-            fp.range_ready = h->pk.oct[l].quantised ? 1 : 0;
-            fp.prev_in = a.prev_word ? h->oct_prev : nullptr;
-            fp.logits = a.logits; fp.softmax = a.softmax; fp.tokens = a.tokens; fp.prev_word = a.prev_word;
-            fp.decode_thres = a.decode2_thres; fp.value_clip = c.value_clip; fp.use_relu = c.use_relu;
-            fp.B = B; fp.T = a.T; fp.C = c.num_classes;
-            e = kws::launch_octbit_fc(fp, st);
-            if (e != hipSuccess) return hip_fail(e, "launch octbit_fc");
-        }
-        rc = profile_end(h, st, pd);
-        if (rc != KWS_OK) return rc;
-    }
+    for (int l = 0; l < 8; ++l) h->launch_tag[l] = plan.tag[l];
     return KWS_OK;
 }
 
 }  // namespace
 
-// Can the last layer's launch of a (B, T) step on this handle take the window tail along?  (kws_stream_feed asks before it
-// hands one to step_impl; the kernels without a tail instantiation -- generic, pipelined, overlapped, int8, single-layer fp32,
-// 4-wave bf16 -- are followed by window_inc_kernel instead.)
+// Can the last layer's launch of a (B, T) step on this handle take the window tail along?  (kws_stream_feed asks before it hands
+// one to step_impl, which asks again; where the plan says no, window_inc_kernel follows the stack instead.)
 bool kws_host::step_takes_window(kws_handle h, int B, int T, int window_chunks) {
-    const kws_config& c = h->cfg;
-    static const bool off = [] { const char* e = getenv("KWS_NO_WINDOW_TAIL"); return e && e[0] == '1'; }();     // A/B switch (tools/bench_e2e.py)
-    if (off || T < 1 || T > kws::kWinTailMaxFrames || window_chunks > kws::kWinTailMaxChunks) return false;
-    // One group per workgroup only: the tail is ~2 us of latency-bound work at the end of a group.  At the end of the launch
-    // that replaces a ~4 us launch of its own; in a persistent workgroup it would sit between two groups, on the critical
-    // path once per group (measured, bf16, 16384 streams: 0.349-0.359 ms per chunk with the tail against 0.338-0.340 with
-    // window_inc_kernel behind the stack)
-    if (kws::groups_of(B) > (h->num_cus > 0 ? h->num_cus : 256)) return false;
-    if (c.precision == KWS_BF16) return kws::gru_stack_bf16_takes_window(h->pk.bf_kx0, c.num_layers);
-    if (c.precision == KWS_F16X3) return !h->pk.f16_generic;
-    if (c.precision != KWS_FP32 || pipeline_eligible(h, B) || overlap_eligible(h, B, T)) return false;
-    return is_resident(h, h->pk.layers[c.num_layers - 1]) && kws::gru_resident_takes_window(c.num_layers == 1, true);
+    const StepPlan plan = plan_step(h, B, T, h->profiling, window_chunks <= kws::kWinTailMaxChunks);
+    for (int l = h->cfg.num_layers - 1; l >= 0; --l)
+        if (plan.tag[l].family != kws_model::kNone) return plan.tag[l].window != 0;      // the last launch of the step
+    return false;
 }
 
 // Ordering of a call against the handle's previous one (kws_model::last_done): device-side, never a host wait.
@@ -577,11 +568,12 @@ int kws_reserve(kws_handle h, int B, int T) {
     BusyGuard busy(h->in_call);
     if (!busy.owned) return fail(KWS_ERR_BUSY, "kws_reserve: another host thread is inside a call on this handle");
     if (B < 0 || T < 0) return fail(KWS_ERR_INVALID_ARGUMENT, "negative B=%d or T=%d", B, T);
-    // whichever launch layout kws_step picks for (B, T) -- it depends on kws_set_profiling too -- fits afterwards
-    int rc = ensure_scratch(h, B, T);
-    if (rc != KWS_OK) return rc;
-    if (overlap_shape_ok(h, B, T)) rc = carve_seams(h, seam_layout(h, B, T, kLayoutOverlapped));
-    return rc;
+    // whichever launch layout kws_step picks for (B, T) -- it depends on kws_set_profiling too -- fits afterwards: the arenas only grow
+    for (const bool profiling : {true, false}) {
+        StepPlan plan = plan_step(h, B, T, profiling, false);
+        KWS_TRY(provision(h, plan, B, T, false));
+    }
+    return KWS_OK;
 }
 
 int kws_scratch_stats(kws_handle h, size_t* bytes_reserved, int32_t* allocations) {

@@ -1,7 +1,7 @@
 """The configuration grid of tests/test_gpu_config_space.py and tests/test_config_space_refs.py: rows inside the space
 kws_create accepts (api_model.hip:config_ok), the launch layout api_step.hip picks for each, and the rows just outside it.
 
-`expected_names` restates the selection rules of api_step.hip (is_resident, pipeline_eligible, overlap_shape_ok) and of
+`expected_names` restates the selection rules of api_step.hip (plan_step, the one place that holds them) and of
 the packer (weight_pack.hip: resident_ok, f16_kx0, bf_kx0), so that a row's layout column is checked against the rules
 and kernel_names() is checked against both."""
 import zlib

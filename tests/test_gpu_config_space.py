@@ -247,3 +247,31 @@ def test_layout_twin_on_shared_streams(row, oracle_c):
     got = {k: big[k].cpu().numpy() for k in ("logits", "state", "softmax")}
     _check_values(row, got["logits"][pick], got["state"][:, pick], got["softmax"][pick], want_l, want_s, oracle_c,
                   np.ascontiguousarray(mel[pick]), np.ascontiguousarray(st0[:, pick]))
+
+
+def test_profiling_plans_sequential_launches_and_zero_frames_keep_the_names():
+    """Two rules of plan_step that no row pins, at the smallest overlap-eligible shape (one group, T == KWS_OVERLAP_MIN_T):
+    kws_set_profiling turns the overlapped call into one launch per layer -- same bits, inside what kws_reserve sized for
+    either answer -- and a zero-frame call launches no GRU kernel, so kernel_names() keeps the step before."""
+    row = S.R("fp32_res_n40_L2_ovl_min", "fp32", "auto", 40, 128, 2, 4, 16, S.OVERLAP_MIN_T, "ovl", wfc=2.0)
+    cus = _cus()
+    b, t = row.batch, row.frames
+    assert S.layout_of(row, b, t, cus) == "ovl" and S.layout_of(row, b, t - 1, cus) == "seq"
+    m = _model(row)
+    mel, st0, _, _ = inputs(row)
+    m.reserve(b, t)
+    stats = m.scratch_stats()
+    ovl = _forward(m, mel, st0)
+    assert m.kernel_names() == S.expected_names(row, b, t, cus)
+    assert m.scratch_stats() == stats
+    m.set_profiling(True)
+    seq = _forward(m, mel, st0)
+    seq_names = S.expected_names(row, b, t - 1, cus)      # the row's names with the layout forced to sequential
+    assert m.kernel_names() == seq_names
+    assert [n for _, n in m.kernel_times()] == [1] * row.layers      # one timed launch per layer: not the time blocks
+    for k in ("logits", "softmax", "state"):
+        assert torch.equal(seq[k], ovl[k]), k
+    assert m.scratch_stats() == stats
+    none = _forward(m, mel[:, :0], st0)
+    assert none["logits"].shape[1] == 0 and torch.equal(none["state"].cpu(), _t(st0))
+    assert m.kernel_names() == seq_names
