@@ -82,7 +82,11 @@ enum { KWS_FP32 = 0, KWS_BF16 = 1, KWS_INT8 = 2,
        /* fp32 results on the fp16 matrix pipe: every matmul operand split into two fp16 pieces (22 mantissa bits), three
           v_mfma_f32_16x16x32_f16 per product, fp32 accumulation, activations and state (csrc/gru_f16x3.hip).  Meets the
           fp32 path's tolerance (logits within 1e-4 of the reference semantics; observed ~3e-6) at ~2.5x its throughput;
-          it is NOT bit-identical to KWS_FP32.  hidden = 128, n_mel % 4 == 0 and <= 64, any num_layers; |weights| < 64. */
+          it is NOT bit-identical to KWS_FP32.  Every matrix weight must be finite with |w| < 64 (else KWS_ERR_UNSUPPORTED naming it).
+          GRU handles (kws_create): hidden 128 on the register-resident kernels (n_mel % 4 == 0 and <= 64), otherwise the
+          L2-streaming ones (csrc/gru_f16x3_generic.hip); any num_layers.  Attention handles (kws_attention_create_precision): the
+          whole config space kws_attention_create takes; the embedding, qkv and FFN products run split (csrc/attention_f16x3.hip),
+          the attention core, layer norm and output projection stay fp32. */
        KWS_F16X3 = 3 };
 
 typedef struct kws_model* kws_handle;
@@ -452,6 +456,13 @@ size_t kws_attention_weights_nbytes(const kws_attention_config* cfg);
 /* weights_blob: HOST memory of kws_attention_weights_nbytes(cfg) bytes.  With KWS_SELFTEST=1 the create runs
  * kws_attention_selftest and fails as it does. */
 int kws_attention_create(const kws_attention_config* cfg, const void* weights_blob, size_t nbytes, kws_attention_handle* out);
+/* ... with the precision of the matrix products: KWS_FP32 (exactly kws_attention_create) or KWS_F16X3 (the embedding, qkv and FFN
+ * products on the fp16 matrix pipe, operands split into two fp16 pieces; same blob, same contract, same tolerance, NOT bit-identical
+ * to KWS_FP32; activations, the attention core, layer norm, the output projection and softmax stay fp32).  KWS_BF16 / KWS_INT8:
+ * KWS_ERR_UNSUPPORTED naming the precision.  KWS_F16X3 needs every W_in / W_qkv / W1 / W2 entry finite with |w| < 64, else
+ * KWS_ERR_UNSUPPORTED naming the matrix, the layer and the value.  Precision and weights are validated before the device is probed. */
+int kws_attention_create_precision(const kws_attention_config* cfg, int precision, const void* weights_blob, size_t nbytes,
+                                   kws_attention_handle* out);
 int kws_attention_destroy(kws_attention_handle h);   /* always KWS_OK */
 /* T' of an utterance of T frames (>= 0), or a negative kws_status */
 int kws_attention_frames_out(const kws_attention_config* cfg, int T);

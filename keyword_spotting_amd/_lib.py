@@ -128,6 +128,7 @@ _SIGNATURES = {
     "kws_sizeof_attention_config": (ctypes.c_size_t, []),
     "kws_attention_weights_nbytes": (ctypes.c_size_t, [ctypes.POINTER(KwsAttentionConfig)]),
     "kws_attention_create": (_i, [ctypes.POINTER(KwsAttentionConfig), _vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
+    "kws_attention_create_precision": (_i, [ctypes.POINTER(KwsAttentionConfig), _i, _vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
     "kws_attention_destroy": (_i, [_vp]),
     "kws_attention_frames_out": (_i, [ctypes.POINTER(KwsAttentionConfig), _i]),
     "kws_attention_reserve": (_i, [_vp, _i, _i]),

@@ -1,7 +1,7 @@
 """DeployModel of the self-attention CTC model (models/attention_ctc.py:215-274) batched over B independent utterances, on
 the HIP kernels behind kws_attention_* (include/kws_amd.h, csrc/attention_kernels.hip).
 
-    model = DeployModel(get_attention_config(), weights)
+    model = DeployModel(get_attention_config(), weights)                        # precision="f16x3": the GEMMs on the fp16 matrix pipe
     r = model.forward(mel, lengths)        # mel [B, T, n_mel] -> logits / softmax [B, T', C], lengths_out [B] (T'_b)
     softmax = model.run(['model/softmax:0'], {'model/inputX:0': pcm})[0]        # the reference's 1-D PCM feed: [1, T', C]
     seqs, hits = model.decode(r["softmax"], r["lengths_out"])                      # main.py:186-191 per utterance
@@ -29,8 +29,17 @@ def frames_out(config, frames):
     return frames // c + 1 if c > 1 else frames
 
 
+PRECISIONS = {"fp32": _lib.FP32, "f16x3": _lib.F16X3}
+
+
 class DeployModel(object):
-    def __init__(self, config, weights, device="cuda:0"):
+    def __init__(self, config, weights, device="cuda:0", precision="fp32"):
+        """precision "fp32" (exact fp32 products) or "f16x3" (the embedding, qkv and FFN products on the fp16 matrix pipe with split
+        operands: same tolerance, not bit-identical; needs |w| < 64 in every matrix)."""
+        if precision not in PRECISIONS:
+            raise _lib.UnsupportedError(_lib.KWS_ERR_UNSUPPORTED, "precision %r unsupported for the attention model (%s)"
+                                        % (precision, ", ".join(sorted(PRECISIONS))))
+        self.precision = precision
         self.config = config
         self._frontend = None
         self.device = torch.device(device)
@@ -46,8 +55,10 @@ class DeployModel(object):
                                             int(config.max_frames))
         self._handle = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_attention_create(ctypes.byref(self._cfg), blob.ctypes.data_as(ctypes.c_void_p),
-                                                      blob.nbytes, ctypes.byref(self._handle)))
+            # "fp32" through this entry is kws_attention_create itself
+            _lib.check(self._lib.kws_attention_create_precision(ctypes.byref(self._cfg), PRECISIONS[precision],
+                                                                blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes,
+                                                                ctypes.byref(self._handle)))
 
     def close(self):
         if getattr(self, "_frontend", None) is not None:

@@ -1,5 +1,6 @@
 // C ABI of the self-attention CTC model (include/kws_amd.h, kws_attention_*): validation, the blob layout, the packed device
-// image and positional table, the launch sequence (attention_kernels.hip) and the self-test against a double host loop.
+// image of the handle's precision (fp32 MFMA operands, or the split fp16 ones of attention_f16x3.hip) and positional table, the
+// launch sequence (attention_kernels.hip, attention_f16x3.hip) and the self-test against a double host loop.
 #include <new>
 #include <random>
 
@@ -10,6 +11,7 @@ using namespace kws_host;
 
 struct kws_attention {
     kws_attention_config cfg;
+    int precision = KWS_FP32;         // KWS_FP32 or KWS_F16X3: which GEMM image d_w holds and which GEMM kernels run
     std::vector<float> blob;          // the canonical blob (the self-test's host loop reads it)
     std::vector<float> pe;            // [pe_rows][H]
     int pe_rows = 0, KE = 0;
@@ -84,6 +86,36 @@ size_t pack_b(std::vector<float>& img, const float* W, int K, int N) {
                     out[(((size_t)kc * NT + nt) * 64 + lane) * 4 + j] = k < K ? W[(size_t)k * N + 16 * nt + (lane & 15)] : 0.f;
                 }
     return at;
+}
+// W [K, N] row-major, times `scale` (a power of two) -> v_mfma_f32_16x16x32_f16 B operands [ceil(K/32)][N/16][hi | lo][64][8 halves]
+// (attention_internal.h), rows past K zero, appended to img: 4 bytes per weight, as the fp32 image
+size_t pack_b16(std::vector<float>& img, const float* W, int K, int N, float scale) {
+    const size_t at = img.size();
+    const int KC = (K + 31) / 32, NT = N / 16;
+    img.resize(at + (size_t)KC * NT * 2 * 64 * 4, 0.f);
+    uint16_t* out = reinterpret_cast<uint16_t*>(img.data() + at);
+    for (int kc = 0; kc < KC; ++kc)
+        for (int nt = 0; nt < NT; ++nt)
+            for (int lane = 0; lane < 64; ++lane)
+                for (int j = 0; j < 8; ++j) {
+                    const int k = 32 * kc + 8 * (lane >> 4) + j;
+                    uint16_t hi = 0, lo = 0;
+                    if (k < K) f16_split(W[(size_t)k * N + 16 * nt + (lane & 15)] * scale, &hi, &lo);
+                    const size_t base = (((size_t)kc * NT + nt) * 2 * 64 + lane) * 8 + j;
+                    out[base] = hi;
+                    out[base + 64 * 8] = lo;
+                }
+    return at;
+}
+// f16x3: only the matrices become fp16 operands (W_in scaled by 256: 256 * 64 < 65504); biases, LN tables and W_out stay fp32
+bool f16x3_range_ok(const float* w, size_t off, size_t n, const char* what, int layer, int* code) {
+    for (size_t i = off; i < off + n; ++i)
+        if (!(std::fabs(w[i]) < 64.0f)) {
+            *code = fail(KWS_ERR_UNSUPPORTED, "f16x3 path: %s weight of layer %d (blob index %zu) = %g is outside (-64, 64) (fp16 operands; "
+                         "W_in scaled by 256)", what, layer, i, (double)w[i]);
+            return false;
+        }
+    return true;
 }
 // a plain table, padded so that the next section stays 16-byte aligned
 size_t append(std::vector<float>& img, const float* v, size_t n) {
@@ -207,24 +239,45 @@ int kws_attention_frames_out(const kws_attention_config* cfg, int T) {
 }
 
 int kws_attention_create(const kws_attention_config* cfg, const void* weights_blob, size_t nbytes, kws_attention_handle* out) {
+    return kws_attention_create_precision(cfg, KWS_FP32, weights_blob, nbytes, out);
+}
+
+int kws_attention_create_precision(const kws_attention_config* cfg, int precision, const void* weights_blob, size_t nbytes,
+                                   kws_attention_handle* out) {
     int code;
     if (!out) return fail(KWS_ERR_INVALID_ARGUMENT, "out handle pointer is null");
     *out = nullptr;
     if (!attn_config_ok(cfg, &code)) return code;
+    if (precision == KWS_BF16 || precision == KWS_INT8)
+        return fail(KWS_ERR_UNSUPPORTED, "precision %s is not served for the attention model (KWS_FP32 or KWS_F16X3)",
+                    precision == KWS_BF16 ? "KWS_BF16" : "KWS_INT8");
+    if (precision != KWS_FP32 && precision != KWS_F16X3)
+        return fail(KWS_ERR_UNSUPPORTED, "precision=%d unsupported (KWS_FP32 or KWS_F16X3)", precision);
     if (!weights_blob) return fail(KWS_ERR_INVALID_ARGUMENT, "weights_blob is null");
     const AttnLayout lay = attn_layout(*cfg);
     if (nbytes != lay.total * sizeof(float))
         return fail(KWS_ERR_INVALID_ARGUMENT, "weights_blob has %zu bytes, config needs %zu", nbytes, lay.total * sizeof(float));
+    const bool f16 = precision == KWS_F16X3;
+    if (f16) {
+        const float* wb = static_cast<const float*>(weights_blob);
+        const size_t Hh = cfg->hidden, Fii = cfg->ffn_inner;
+        bool ok = f16x3_range_ok(wb, lay.w_in, (size_t)cfg->n_mel * cfg->combine_frame * Hh, "W_in", 0, &code);
+        for (int l = 0; l < cfg->num_layers && ok; ++l)
+            ok = f16x3_range_ok(wb, lay.layer[l][kQkvW], Hh * 3 * Hh, "W_qkv", l, &code) &&
+                 f16x3_range_ok(wb, lay.layer[l][kW1], Hh * Fii, "W1", l, &code) && f16x3_range_ok(wb, lay.layer[l][kW2], Fii * Hh, "W2", l, &code);
+        if (!ok) return code;
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(KWS_ERR_NO_DEVICE, "no HIP device visible");
 
     kws_attention* m = new (std::nothrow) kws_attention();
     if (!m) return fail(KWS_ERR_OUT_OF_MEMORY, "host allocation failed");
     m->cfg = *cfg;
+    m->precision = precision;
     const float* w = static_cast<const float*>(weights_blob);
     m->blob.assign(w, w + lay.total);
     const int H = cfg->hidden, Fi = cfg->ffn_inner, C = cfg->num_classes, cF = cfg->n_mel * cfg->combine_frame;
-    m->KE = (cF + 15) / 16 * 16;
+    m->KE = f16 ? (cF + 31) / 32 * 32 : (cF + 15) / 16 * 16;
     // positional_encoding_op.cc:44-48: double, stored as float
     m->pe_rows = cfg->max_frames / cfg->combine_frame + 1;
     m->pe.resize((size_t)m->pe_rows * H);
@@ -234,19 +287,21 @@ int kws_attention_create(const kws_attention_config* cfg, const void* weights_bl
             m->pe[(size_t)p * H + 2 * i] = (float)std::sin(a);
             m->pe[(size_t)p * H + 2 * i + 1] = (float)std::cos(a);
         }
+    // one GEMM image per handle: the fp32 operands, or the split fp16 ones (W_in times 2^8 against the kernel's mel * 2^-8)
     std::vector<float> img;
+    auto pack = [&](const float* W, int K, int N, float scale) { return f16 ? pack_b16(img, W, K, N, scale) : pack_b(img, W, K, N); };
     struct LOff { size_t wqkv, bqkv, ga, ba, w1, b1, w2, b2, gb, bb; } lo[8];
-    const size_t o_win = pack_b(img, w + lay.w_in, cF, H);
+    const size_t o_win = pack(w + lay.w_in, cF, H, 256.f);
     const size_t o_bin = append(img, w + lay.b_in, H);
     for (int l = 0; l < cfg->num_layers; ++l) {
         const size_t* L = lay.layer[l];
-        lo[l].wqkv = pack_b(img, w + L[kQkvW], H, 3 * H);
+        lo[l].wqkv = pack(w + L[kQkvW], H, 3 * H, 1.f);
         lo[l].bqkv = append(img, w + L[kQkvB], 3 * H);
         lo[l].ga = append(img, w + L[kLnaGamma], H);
         lo[l].ba = append(img, w + L[kLnaBeta], H);
-        lo[l].w1 = pack_b(img, w + L[kW1], H, Fi);
+        lo[l].w1 = pack(w + L[kW1], H, Fi, 1.f);
         lo[l].b1 = append(img, w + L[kB1], Fi);
-        lo[l].w2 = pack_b(img, w + L[kW2], Fi, H);
+        lo[l].w2 = pack(w + L[kW2], Fi, H, 1.f);
         lo[l].b2 = append(img, w + L[kB2], H);
         lo[l].gb = append(img, w + L[kLnbGamma], H);
         lo[l].bb = append(img, w + L[kLnbBeta], H);
@@ -340,12 +395,14 @@ int kws_attention_run(kws_attention_handle h, const float* mel, const int32_t* l
     p.st_b = p.st_a + (size_t)B * p.ntile;
     p.logits = logits, p.softmax = softmax;
 
-    hipError_t e = kws::launch_attn_embed(p, H, st);
+    // the three GEMM kernels in the handle's precision; the core and the output kernel are fp32 for both
+    const bool f16 = h->precision == KWS_F16X3;
+    hipError_t e = f16 ? kws::launch_attn_embed_f16x3(p, H, st) : kws::launch_attn_embed(p, H, st);
     for (int l = 0; l < c.num_layers && e == hipSuccess; ++l) {
         const kws::AttnLayerW* prev = l > 0 ? &h->layer[l - 1] : nullptr;
-        e = kws::launch_attn_qkv(p, h->layer[l], prev, H, st);
+        e = f16 ? kws::launch_attn_qkv_f16x3(p, h->layer[l], prev, H, st) : kws::launch_attn_qkv(p, h->layer[l], prev, H, st);
         if (e == hipSuccess) e = kws::launch_attn_core(p, prev, H, H / c.num_heads, st);
-        if (e == hipSuccess) e = kws::launch_attn_ffn(p, h->layer[l], H, st);
+        if (e == hipSuccess) e = f16 ? kws::launch_attn_ffn_f16x3(p, h->layer[l], H, st) : kws::launch_attn_ffn(p, h->layer[l], H, st);
     }
     if (e == hipSuccess) e = kws::launch_attn_out(p, h->layer[c.num_layers - 1], H, st);
     const hipError_t er = hipEventRecord(h->last_done, st);   // also after a failure: what was queued is what the next call waits for

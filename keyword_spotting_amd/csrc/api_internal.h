@@ -53,6 +53,27 @@ struct BusyGuard {
 #define KWS_TRY(call) do { const int rc_ = (call); if (rc_ != KWS_OK) return rc_; } while (0)
 inline int hip_done(hipError_t e, const char* what) { return e == hipSuccess ? KWS_OK : hip_fail(e, what); }
 
+// fp32 -> fp16 bits, round to nearest even (what v_cvt_f16_f32 does); the host compiler is clang: _Float16 is native
+inline uint16_t f16_rne(float x) {
+    const _Float16 h = static_cast<_Float16>(x);
+    uint16_t u;
+    memcpy(&u, &h, 2);
+    return u;
+}
+inline float f16_value(uint16_t u) {
+    _Float16 h;
+    memcpy(&h, &u, 2);
+    return static_cast<float>(h);
+}
+// v = hi + 2^-11 lo (gru_f16x3.hip, attention_f16x3.hip): the two fp16 pieces of a weight
+inline void f16_split(float v, uint16_t* hi, uint16_t* lo) {
+    *hi = f16_rne(v);
+    *lo = f16_rne((v - f16_value(*hi)) * 2048.0f);
+#ifdef KWS_EXP_F16_WLO_ZERO      // experiment builds only (tools/build_variant.sh wlo0 -DKWS_EXP_F16_WLO_ZERO): single-piece fp16 WEIGHTS in the
+    *lo = 0;                     // f16x3 kernels -- the hardware check of the rounding model behind the "f16x1" decision
+#endif
+}
+
 // The canonical weight blob (kws_weights_nbytes): per layer Wg [(in+H), 2H], bg [2H], Wc [(in+H), H], bc [H]; then
 // Wfc [H, C] and bfc [C].  Offsets in floats, from the config alone.
 struct BlobLayout {

@@ -12,6 +12,9 @@ constexpr int kAttnRows = 32;
 // A [K, N] fp32 matrix packed as v_mfma_f32_16x16x4_f32 B operands: [K/16][N/16][64 lanes] float4, lane l, component j =
 // W[16 kc + 4 (l / 16) + j][16 nt + l % 16] (rows past K zero).  The A operand of the same product reads the matching
 // float4 X[m][16 kc + 4 (l / 16) ...] out of LDS, so both sides agree on the k order inside a chunk.
+// f16x3 handles (attention_f16x3.hip) carry the same matrices as v_mfma_f32_16x16x32_f16 B operands behind the same pointers:
+// [K/32][N/16][hi | lo][64 lanes] x 8 halves (16 bytes, the unit the float4 pointers count), lane l, element j =
+// W[32 kc + 8 (l / 16) + j][16 nt + l % 16], hi = fp16(w), lo = fp16((w - hi) 2^11); W_in is stored times 2^8.
 struct AttnLayerW {
     const float4* wqkv;   // [H/16][3H/16][64]
     const float* bqkv;    // [3H]
@@ -29,7 +32,7 @@ struct AttnParams {
     const float* mel;       // [B, T_max, F]
     const int32_t* lengths; // [B] or null (= T_max); clamped to [0, T_max]
     int B, T_max, F, c;     // c = combine_frame
-    int KE;                 // c * F rounded up to 16 (the embedding GEMM's k extent)
+    int KE;                 // c * F rounded up to 16 (the embedding GEMM's k extent; f16x3: to 32)
     int T1max;              // T'_max: rows of the outputs per utterance
     int Tp, ntile;          // scratch rows per utterance (multiple of kAttnRows) and its tiles
     int Fi, C, use_relu;
@@ -53,5 +56,9 @@ hipError_t launch_attn_qkv(const AttnParams& p, const AttnLayerW& w, const AttnL
 hipError_t launch_attn_core(const AttnParams& p, const AttnLayerW* prev, int H, int D, hipStream_t st);
 hipError_t launch_attn_ffn(const AttnParams& p, const AttnLayerW& w, int H, hipStream_t st);
 hipError_t launch_attn_out(const AttnParams& p, const AttnLayerW& last, int H, hipStream_t st);
+// the f16x3 forms of the three GEMM kernels (attention_f16x3.hip); the core and the output kernel are shared
+hipError_t launch_attn_embed_f16x3(const AttnParams& p, int H, hipStream_t st);
+hipError_t launch_attn_qkv_f16x3(const AttnParams& p, const AttnLayerW& w, const AttnLayerW* prev, int H, hipStream_t st);
+hipError_t launch_attn_ffn_f16x3(const AttnParams& p, const AttnLayerW& w, int H, hipStream_t st);
 
 }  // namespace kws

@@ -57,26 +57,6 @@ inline uint16_t bf16_rne(float x) {
     u += 0x7fffu + ((u >> 16) & 1u);
     return (uint16_t)(u >> 16);
 }
-// fp32 -> fp16 bits, round to nearest even (what v_cvt_f16_f32 does); the host compiler is clang: _Float16 is native
-inline uint16_t f16_rne(float x) {
-    const _Float16 h = static_cast<_Float16>(x);
-    uint16_t u;
-    memcpy(&u, &h, 2);
-    return u;
-}
-inline float f16_value(uint16_t u) {
-    _Float16 h;
-    memcpy(&h, &u, 2);
-    return static_cast<float>(h);
-}
-// v = hi + 2^-11 lo (gru_f16x3.hip): the two fp16 pieces of a weight
-inline void f16_split(float v, uint16_t* hi, uint16_t* lo) {
-    *hi = f16_rne(v);
-    *lo = f16_rne((v - f16_value(*hi)) * 2048.0f);
-#ifdef KWS_EXP_F16_WLO_ZERO      // experiment builds only (tools/build_variant.sh wlo0 -DKWS_EXP_F16_WLO_ZERO): single-piece fp16 WEIGHTS in the
-    *lo = 0;                     // f16x3 kernels -- the hardware check of the rounding model behind the "f16x1" decision
-#endif
-}
 // ... and with the lo piece at its own magnitude: v = hi + lo.  Below 2^-14 the piece is an fp16 subnormal (absolute precision
 // 2^-25): the value keeps max(2^-23 |v|, 2^-25) -- fp32's own rounding down to |v| = 1/4, a 3e-8 absolute floor below that
 inline void f16_split_unscaled(float v, uint16_t* hi, uint16_t* lo) {

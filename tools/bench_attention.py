@@ -3,9 +3,11 @@
 over B in {1, 16, 256, 4096} x T in {100, 300, 1000} mel frames, equal lengths and ragged lengths uniform in [T/2, T]:
 ms per call (HIP events, median), utterances/s, mel-frames/s, algorithmic TFLOP/s and its fraction of the 157.3 TF fp32
 matrix peak, and a torch-eager fp32 build of the same model on the same GPU (cuBLAS-class GEMMs, SDPA, masked layer norm),
-timed the same way and checked against ours.
+timed the same way and checked against ours.  --precision fp32,f16x3: one row per precision and shape, both handles in the same
+process, and on every row after the first precision's its speed-up over that one (`vs_<first>`); rows carry the spread
+(min, max) of their repetitions.
 
-    python tools/bench_attention.py [--shapes 4096x300,...] [--reps 10] [--out bench_attention.json]
+    python tools/bench_attention.py [--shapes 4096x300,...] [--precision fp32,f16x3] [--reps 10] [--out bench_attention.json]
 
 FLOPs per utterance (multiply-add = 2): 2 T' c F H + L (6 T' H^2 + 4 T'^2 H + 4 T' H Fi) + 2 T' H C, T' = T // c + 1.
 """
@@ -99,12 +101,14 @@ def main():
     ap.add_argument("--shapes", default="1x100,1x300,1x1000,16x100,16x300,16x1000,256x100,256x300,256x1000,4096x100,4096x300,4096x1000")
     ap.add_argument("--ragged", default="both", choices=("both", "equal", "ragged"))
     ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--precision", default="fp32", help="comma-separated: fp32, f16x3")
     ap.add_argument("--no-eager", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     cfg = get_attention_config()
     w = AW.init(cfg, 0)
-    model = DeployModel(cfg, w)
+    precisions = a.precision.split(",")
+    models = {pr: DeployModel(cfg, w, precision=pr) for pr in precisions}
     eager = None if a.no_eager else Eager(cfg, w)
     rows = []
     for shape in a.shapes.split(","):
@@ -113,26 +117,33 @@ def main():
             g = torch.Generator(device="cpu").manual_seed(B * 7 + T)
             mel = torch.randn(B, T, cfg.n_mel, generator=g).cuda()
             lengths = (torch.randint(T // 2, T + 1, (B,), generator=g) if ragged else torch.full((B,), T)).to(torch.int32).cuda()
-            model.reserve(B, T)
-            med, _ = timed(lambda: model.forward(mel, lengths, want_logits=False), a.reps)
             t1 = [frames_out(cfg, int(v)) for v in lengths.cpu()]
             fl = flops(cfg, t1)
-            row = dict(B=B, T=T, ragged=ragged, ms=round(med, 4), utt_per_s=round(B / med * 1e3, 1),
-                       mel_frames_per_s=round(float(lengths.sum()) / med * 1e3, 1), gflop=round(fl / 1e9, 3),
-                       tflops=round(fl / med / 1e9, 2), frac_peak=round(fl / med / 1e9 / PEAK_TF, 3))
-            t1max = frames_out(cfg, T)
-            if eager is not None and B * cfg.multi_head_num * t1max * t1max * 4 <= EAGER_SCORE_BYTES:
-                with torch.no_grad():
-                    e_med, _ = timed(lambda: eager(mel, lengths), max(3, a.reps // 2))
-                    el, es = eager(mel, lengths)
-                r = model.forward(mel, lengths)
-                row.update(eager_ms=round(e_med, 4), speedup_vs_eager=round(e_med / med, 2),
-                           eager_max_dlogit=float((el - r["logits"]).abs().max()), eager_max_dsoftmax=float((es - r["softmax"]).abs().max()))
-                del el, es, r
-            else:
-                row.update(eager_ms=None)
-            rows.append(row)
-            print(json.dumps(row), flush=True)
+            base_ms = None
+            for pr in precisions:
+                model = models[pr]
+                model.reserve(B, T)
+                med, ms = timed(lambda: model.forward(mel, lengths, want_logits=False), a.reps)
+                row = dict(B=B, T=T, ragged=ragged, precision=pr, ms=round(med, 4), ms_min=round(min(ms), 4), ms_max=round(max(ms), 4),
+                           utt_per_s=round(B / med * 1e3, 1), mel_frames_per_s=round(float(lengths.sum()) / med * 1e3, 1),
+                           gflop=round(fl / 1e9, 3), tflops=round(fl / med / 1e9, 2), frac_peak=round(fl / med / 1e9 / PEAK_TF, 3))
+                if base_ms is None:
+                    base_ms = med
+                else:
+                    row["vs_" + precisions[0]] = round(base_ms / med, 3)
+                t1max = frames_out(cfg, T)
+                if eager is not None and B * cfg.multi_head_num * t1max * t1max * 4 <= EAGER_SCORE_BYTES:
+                    with torch.no_grad():
+                        e_med, _ = timed(lambda: eager(mel, lengths), max(3, a.reps // 2))
+                        el, es = eager(mel, lengths)
+                    r = model.forward(mel, lengths)
+                    row.update(eager_ms=round(e_med, 4), speedup_vs_eager=round(e_med / med, 2),
+                               eager_max_dlogit=float((el - r["logits"]).abs().max()), eager_max_dsoftmax=float((es - r["softmax"]).abs().max()))
+                    del el, es, r
+                else:
+                    row.update(eager_ms=None)
+                rows.append(row)
+                print(json.dumps(row), flush=True)
             del mel, lengths
             torch.cuda.empty_cache()
     if a.out:
