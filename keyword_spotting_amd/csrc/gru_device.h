@@ -1,4 +1,4 @@
-// Device helpers shared by the GRU kernels (gru_kernels.hip, gru_bf16.hip, gru_f16x3.hip, gru_f16x3_generic.hip, gru_octbit.hip)
+// Device helpers shared by the GRU kernels (gru_kernels.hip, gru_resident.hip, gru_bf16.hip, gru_f16x3.hip, gru_f16x3_generic.hip, gru_octbit.hip)
 // and the mel front-ends (frontend_kernels.hip, fft_frontend.hip).
 #pragma once
 #include <type_traits>
@@ -25,8 +25,14 @@ __device__ __forceinline__ float tanh_f(float x) {
 // v_accvgpr_read + s_nop (39 cycles per MFMA instead of 32, tools/ubench/mfma_issue.hip); the "a"
 // constraint removes the copy.  The statement is opaque to the hazard recogniser: every chain of these
 // ends with mfma_fence() before any non-MFMA instruction touches the accumulators.
+// KWS_RESIDENT_VGPR_FORM (gru_resident.hip only, see the Makefile): the accumulators of builtin MFMAs stay in VGPRs there, the
+// compiler reads an "+a"-pinned fragment as source A by itself and knows every hazard: the builtin, and no fences.
+#if KWS_RESIDENT_VGPR_FORM
+#define KWS_MFMA_A(acc, wa, bv) acc = mfma4(wa, bv, acc)
+#else
 #define KWS_MFMA_A(acc, wa, bv) \
     asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc) : "a"(wa), "v"(bv))
+#endif
 // XDL 8-pass write -> VALU read needs 11 wait states (s_nop 15 = 16); the "+v" ties order it after the
 // chain and ahead of every consumer
 __device__ __forceinline__ void mfma_fence(f32x4& a, f32x4& b, f32x4& c, f32x4& d) {

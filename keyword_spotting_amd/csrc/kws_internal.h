@@ -320,7 +320,7 @@ hipError_t launch_features_fft400(const FrontendParams& p, int B, hipStream_t st
 hipError_t launch_carry_tail(const float* carry, int n_carry, const float* chunk, int n_chunk, float* next, int n_next, int B,
                              hipStream_t st);
 
-// launchers (gru_kernels.hip)
+// launchers (gru_resident.hip, gru_kernels.hip)
 bool gru_resident_supported(int hidden, int in_dim, bool first);
 int gru_resident_kcx(int in_dim, bool first);
 hipError_t launch_gru_layer_resident(const GruLayerParams& p, bool first, bool last, hipStream_t st);    // p.win.tab != null: with the window tail

@@ -1,12 +1,17 @@
 #!/usr/bin/env python3
 """A/B of library builds on one GPU box: runs bench.py once per library (interleaved, `--rounds` times) and prints the
-per-layer kernel times.  usage: tools/ab_variants.py [--rounds 2] [--args "--precision int8"] name=path.so ...
-(`base` = the in-tree library)."""
+per-layer kernel times.  usage: tools/ab_variants.py [--rounds 2] [--steps 10 --warmup 3] [--args "--precision int8"] [--out FILE]
+name=path.so ...  (`base` = the in-tree library).  With two or more libraries the summary judges every later one against the FIRST
+and against the one listed before it, by the project's rule for a gain: every run faster than every run of the first, and the median ratio above
+1 + 2 x (first's max - min) / (first's median)."""
 import argparse, json, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ap = argparse.ArgumentParser()
 ap.add_argument("--rounds", type=int, default=2)
+ap.add_argument("--steps", type=int, default=10)
+ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--args", default="")
+ap.add_argument("--out", help="also append the report to this file")
 ap.add_argument("libs", nargs="+")
 a = ap.parse_args()
 libs = []
@@ -19,13 +24,30 @@ for r in range(a.rounds):
         env = dict(os.environ)
         if path:
             env["KWS_AMD_LIB"] = path
-        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "10", "--warmup", "3", "--no-cpu-baseline"] + a.args.split(),
-                             env=env, capture_output=True, text=True)
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps), "--warmup", str(a.warmup), "--no-cpu-baseline"] + a.args.split(),
+                             env=env, capture_output=True, text=True, timeout=300)
         lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
-        if not lines:
-            print(name, "FAILED", out.stderr[-500:]); continue
+        if out.returncode != 0 or not lines:      # nothing more is started on a GPU that a run has just failed on
+            print(name, "FAILED rc=%d" % out.returncode, out.stderr[-500:])
+            sys.exit(1)
         d = json.loads(lines[-1])
         res[name].append((d["value"], d["roofline"]["per_layer_ms"]))
+lines = ["bench.py --steps %d --warmup %d %s, %d interleaved rounds" % (a.steps, a.warmup, a.args, a.rounds)]
 for name, _ in libs:
     for v, pl in res[name]:
-        print("%-16s %8.1f M frames/s   per-layer ms %s" % (name, v / 1e6, " ".join("%.4f" % x for x in pl)))
+        lines.append("%-16s %8.2f M frames/s   per-layer ms %s" % (name, v / 1e6, " ".join("%.4f" % x for x in pl)))
+median = lambda xs: sorted(xs)[len(xs) // 2] if len(xs) % 2 else sum(sorted(xs)[len(xs) // 2 - 1:len(xs) // 2 + 1]) / 2
+pairs = [(libs[0][0], n) for n, _ in libs[1:]] + [(libs[i][0], libs[i + 1][0]) for i in range(1, len(libs) - 1)]
+for ref, name in pairs:                    # every library against the first, and against the one listed before it
+    base, new = [v for v, _ in res[ref]], [v for v, _ in res[name]]
+    if not base or not new:
+        continue
+    bar = 1 + 2 * (max(base) - min(base)) / median(base)
+    ratio = median(new) / median(base)
+    lines.append("%s vs %s: median ratio %.4f (bar %.4f), slowest %s run %.2f vs fastest %s run %.2f M frames/s -> %s"
+                 % (name, ref, ratio, bar, name, min(new) / 1e6, ref, max(base) / 1e6,
+                    "GAIN" if min(new) > max(base) and ratio > bar else "no gain under the rule"))
+print("\n".join(lines))
+if a.out:
+    with open(a.out, "a") as f:
+        f.write("\n".join(lines) + "\n")

@@ -1,9 +1,9 @@
 #!/bin/bash
 # tools/build_variant.sh <name> [--patch tools/patches/<x>.patch ...] [-DFLAG ...]  ->  variants/libkws_<name>.so
 # Experiment builds (timing instrumentation, ablations) are made from a patched COPY of the sources, so the product
-# sources carry no experiment code.  tools/patches/timing_ablation.patch re-adds the s_memtime phase counters
-# (-DKWS_TIMING) and the KWS_ABL_* ablation switches as they were at the end of round 1 (it applies to that
-# revision of the kernels; refresh it when the frame loop changes).  Load the result with KWS_AMD_LIB=variants/libkws_<name>.so.
+# sources carry no experiment code.  tools/patches/timing_ablation.patch adds the KWS_ABL_* ablation switches of the fp32 resident
+# kernel (csrc/gru_resident.hip, csrc/gru_device.h; its header lists them -- refresh it when the frame loop changes).
+# Load the result with KWS_AMD_LIB=variants/libkws_<name>.so.
 set -e
 NAME=$1; shift
 ROOT=$(cd $(dirname $0)/.. && pwd)
