@@ -196,6 +196,44 @@ int kws_step(kws_handle h, const float* mel, const float* state_in, float* logit
              float* state_out, const int32_t* seq_len, const uint8_t* reset_mask, int8_t* tokens,
              int32_t* prev_word, float decode2_thres, int B, int T, void* stream);
 
+/* Customised-keyword models (the reference's README.md:109-132 and server_demo.py:107-129): the GRU stack is frozen, a second
+ * projection [H, C2] is trained beside the first, and the model is served with both dense layers on the same top-layer rows
+ * (model/softmax1:0, model/softmax2:0), next to those rows themselves (model/nn_outputs:0).
+ *   kws_weights_nbytes_heads  the canonical blob of `cfg`, then Wfc2[H, C2] and bfc2[C2]; 0: invalid config, C2 outside 3..8,
+ *                             or a precision the heads do not serve.
+ *   kws_create_heads          a model handle with the second head.  KWS_FP32 only: bf16 (no seam between its layers), int8 and
+ *                             f16x3 (seams in another format) are KWS_ERR_UNSUPPORTED, decided before the device is probed;
+ *                             there is no wrapped form.  The handle is a normal model handle: kws_step, kws_stream_create,
+ *                             kws_selftest and the rest behave as on a kws_create handle of the canonical part of the blob
+ *                             (head 1, fused into the last layer's launch); kws_selftest additionally proves kws_step_heads.
+ *   kws_step_heads            kws_step with both heads: every layer writes its rows to a seam (one launch per layer, the
+ *                             kernel family of kws_set_kernel; never the overlapped or layer-pipelined layouts) and one more
+ *                             launch reads the top layer's seam once for everything below.  mel, state_in, state_out, seq_len,
+ *                             reset_mask, B, T, stream: as kws_step.  head1 / head2 (either may be NULL: that head is not
+ *                             computed) carry, per head, what kws_step takes for its one: logits [B,T,C_i], softmax [B,T,C_i],
+ *                             tokens [B,T] (each may be NULL), prev_word [B] in/out (required iff tokens != NULL) and the
+ *                             head's own decode2_thres.  reset_mask sets both heads' prev_word to -1.
+ *                             nn_outputs [B,T,H] f32, 16-byte aligned, may be NULL: the top layer's output rows, batch-major
+ *                             (dynamic_rnn's outputs, models/rnn_ctc.py:238-243).
+ *                             Rows with t >= seq_len[b]: nn_outputs = 0, logits = bfc_i (then relu / clip), tokens = 0, and
+ *                             the frame counts as "no word" for the token rule and for prev_word.
+ *                             Only on a kws_create_heads handle (else KWS_ERR_INVALID_ARGUMENT).  kws_reserve on such a
+ *                             handle sizes the scratch for kws_step and kws_step_heads alike.  With profiling on, the heads'
+ *                             launch is timed in slot L-1 with the top layer, and kws_last_launch names both kernels. */
+typedef struct kws_head_io {
+    float* logits;
+    float* softmax;
+    int8_t* tokens;
+    int32_t* prev_word;
+    float decode2_thres;
+} kws_head_io;
+size_t kws_sizeof_head_io(void);
+size_t kws_weights_nbytes_heads(const kws_config* cfg, int32_t num_classes2);
+int kws_create_heads(const kws_config* cfg, int32_t num_classes2, const void* weights_blob, size_t nbytes, kws_handle* out);
+int kws_step_heads(kws_handle h, const float* mel, const float* state_in, float* state_out, const int32_t* seq_len,
+                   const uint8_t* reset_mask, float* nn_outputs, const kws_head_io* head1, const kws_head_io* head2, int B, int T,
+                   void* stream);
+
 /* Per-kernel timing (bench.py roofline): when enabled, kws_step brackets each kernel launch with
  * hipEvents on `stream`.  kws_kernel_times synchronises those events and returns, per layer kernel
  * slot (0..L-1), the summed milliseconds and the launch count since the last reset. */

@@ -46,6 +46,13 @@ class KwsCellWrappers(ctypes.Structure):
     _fields_ = [("use_layer_norm", ctypes.c_int32), ("use_residual", ctypes.c_int32)]
 
 
+class KwsHeadIo(ctypes.Structure):
+    """kws_head_io: one class head's outputs in kws_step_heads -- logits / softmax [B,T,C_i], tokens [B,T], prev_word [B] (device
+    pointers, each may be NULL; tokens needs prev_word) and the head's ctc_decode2 threshold."""
+    _fields_ = [("logits", ctypes.c_void_p), ("softmax", ctypes.c_void_p), ("tokens", ctypes.c_void_p),
+                ("prev_word", ctypes.c_void_p), ("decode2_thres", ctypes.c_float)]
+
+
 class KwsAttentionConfig(ctypes.Structure):
     """kws_attention_config: the self-attention CTC model (config/attention_config.py) and the longest utterance a handle takes."""
     _fields_ = [("n_mel", ctypes.c_int32), ("combine_frame", ctypes.c_int32), ("hidden", ctypes.c_int32),
@@ -84,6 +91,10 @@ _SIGNATURES = {
     "kws_sizeof_cell_wrappers": (ctypes.c_size_t, []),
     "kws_weights_nbytes_wrapped": (ctypes.c_size_t, [ctypes.POINTER(KwsConfig), ctypes.POINTER(KwsCellWrappers)]),
     "kws_create_wrapped": (_i, [ctypes.POINTER(KwsConfig), ctypes.POINTER(KwsCellWrappers), _vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
+    "kws_sizeof_head_io": (ctypes.c_size_t, []),
+    "kws_weights_nbytes_heads": (ctypes.c_size_t, [ctypes.POINTER(KwsConfig), ctypes.c_int32]),
+    "kws_create_heads": (_i, [ctypes.POINTER(KwsConfig), ctypes.c_int32, _vp, ctypes.c_size_t, ctypes.POINTER(_vp)]),
+    "kws_step_heads": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(KwsHeadIo), ctypes.POINTER(KwsHeadIo), _i, _i, _vp]),
     "kws_destroy": (_i, [_vp]),
     "kws_set_kernel": (_i, [_vp, _i]),
     "kws_reserve": (_i, [_vp, _i, _i]),
@@ -161,7 +172,8 @@ def load():
                 lib.kws_sizeof_cell_wrappers() != ctypes.sizeof(KwsCellWrappers) or \
                 lib.kws_sizeof_feature_config() != ctypes.sizeof(KwsFeatureConfig) or \
                 lib.kws_sizeof_dataset_config() != ctypes.sizeof(KwsDatasetConfig) or \
-                lib.kws_sizeof_attention_config() != ctypes.sizeof(KwsAttentionConfig):
+                lib.kws_sizeof_attention_config() != ctypes.sizeof(KwsAttentionConfig) or \
+                lib.kws_sizeof_head_io() != ctypes.sizeof(KwsHeadIo):
             raise ImportError("%s was built from a different include/kws_amd.h than this binding (struct sizes differ); "
                               "rebuild it" % LIB_PATH)
         _lib = lib

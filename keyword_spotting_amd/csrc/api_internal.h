@@ -115,11 +115,21 @@ struct PackedWeights {
     // x-part (16 * kcx_gen / 4 floats, zero past I_l) and its ibeta
     std::vector<size_t> ln_igamma;
     std::vector<float> ln_ibeta;
+    // second class head (kws_create_heads): its fragments and padded bias, behind every other table
+    size_t wfc2_off = 0, bfc2_off = 0;
 };
 // (config, canonical blob [+ the wrapper tables of wrap_layout]) -> the device image of every table the config's precision
 // launches with, and where each one is.  KWS_OK, or the error code with kws_last_error() set.  Host code only.
-int pack_weights(const kws_config& cfg, const kws_cell_wrappers& wrap, const float* blob, PackedWeights* pk, std::vector<float>* image);
+// num_classes2 > 0: Wfc2 [H, C2] and bfc2 [C2] follow in the blob (kws_weights_nbytes_heads) and are packed as the first head is.
+int pack_weights(const kws_config& cfg, const kws_cell_wrappers& wrap, const float* blob, PackedWeights* pk, std::vector<float>* image,
+                 int num_classes2 = 0);
 
+// What kws_step_heads adds to a step: the top layer's rows and the outputs of each head (on[i]: head i is wanted)
+struct HeadsArgs {
+    float* nn_outputs = nullptr;
+    kws_head_io head[2] = {};
+    bool on[2] = {false, false};
+};
 // The arguments of one kws_step (include/kws_amd.h), and what the stream manager adds to them
 struct StepArgs {
     const float *mel = nullptr, *state_in = nullptr;
@@ -132,6 +142,7 @@ struct StepArgs {
     int B = 0, T = 0;
     hipStream_t stream = nullptr;
     const kws::WindowTail* wt = nullptr;   // the stream manager's decode window, to ride at the end of the last layer's launch
+    const struct HeadsArgs* heads = nullptr;   // kws_step_heads: no layer is `last`, dense_heads_kernel follows the top layer
     bool locked = false;                   // the caller (kws_stream_feed) already holds the handle and has ordered the stream
 };
 
@@ -179,6 +190,9 @@ struct kws_model {
     float2* oct_range = nullptr;     // [groups*16]
     int32_t* oct_prev = nullptr;     // [B] copy of prev_word
     size_t oct_groups = 0;
+    int num_classes2 = 0;            // > 0: a heads handle (kws_create_heads); kws_step_heads serves both heads
+    int32_t* heads_prev = nullptr;   // [2][heads_groups * 16] copies of the two heads' prev_word (dense_heads.hip)
+    size_t heads_groups = 0;
     // Inter-layer seams.  ONE device allocation per memory kind that only ever grows (kws_reserve or the first call that
     // needs more); each kws_step carves the buffers of its launch layout out of it -- sequential (1-2 buffers of T
     // frames), layers overlapped on HIP streams (2(L-1) buffers of a time block), layer-pipelined (L-1 fine-grained
@@ -226,7 +240,7 @@ struct kws_model {
     // (kws_last_launch, kws_selftest) -- not on the launch path, where a 22-frame call is ~100 us of device time
     enum LaunchFamily : uint8_t { kNone = 0, kBf16Stack, kF16x3, kPipelined, kOctbit, kOctbitFc, kResident, kGeneric, kF16x3Generic, kF16x3Pipelined,
                                   kGenericWrapped, kPipelinedWrapped };
-    struct LaunchTag { uint8_t family = kNone, kx = 0, first = 0, last = 0, window = 0; };
+    struct LaunchTag { uint8_t family = kNone, kx = 0, first = 0, last = 0, window = 0, heads = 0; };
     LaunchTag launch_tag[8];
     std::string launch_name(int slot) const {
         const LaunchTag& t = launch_tag[slot];
@@ -248,6 +262,7 @@ struct kws_model {
         }
         std::string out = t.family == kBf16Stack ? std::string(kws::gru_stack_bf16_kernel_name(pk.bf_kx0, cfg.num_layers)) : std::string(nm);
         if (t.window) out += " + window tail";          // the stream manager's decode-window step rode in this launch
+        if (t.heads) out += " + dense_heads_kernel<" + std::to_string(cfg.hidden / 16) + ">";      // timed in the top layer's slot
         return out;
     }
 };

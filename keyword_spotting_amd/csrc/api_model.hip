@@ -89,6 +89,28 @@ static bool wrappers_ok(const kws_config* c, const kws_cell_wrappers* w, int* co
 }
 static kws_cell_wrappers wrappers_of(const kws_cell_wrappers* w) { return w ? *w : kws_cell_wrappers{0, 0}; }
 
+// The second class head of kws_create_heads.  Checked after the config (config_ok), before any device work.
+static bool heads_ok(const kws_config* c, int32_t num_classes2, int* code) {
+    if (num_classes2 < 3 || num_classes2 > kws::kMaxClasses) {
+        *code = fail(KWS_ERR_UNSUPPORTED, "num_classes2=%d unsupported (3..8)", num_classes2);
+        return false;
+    }
+    const char* why = nullptr;
+    switch (c->precision) {
+        case KWS_BF16: why = "bf16: the fused bf16 stack has no seam between its layers for the heads to read"; break;
+        case KWS_INT8: why = "int8: its class projection is the quantised OctbitMatMul behind the stack"; break;
+        case KWS_F16X3: why = "f16x3: its seams hold fp16 pairs, not fp32 rows"; break;
+        default: break;
+    }
+    if (why) { *code = fail(KWS_ERR_UNSUPPORTED, "a second class head needs precision fp32 (%s)", why); return false; }
+    return true;
+}
+static size_t heads_floats(const kws_config* c, int32_t num_classes2) { return (size_t)c->hidden * num_classes2 + num_classes2; }
+
+// kws_create_wrapped / kws_create_heads behind their argument checks: `need` bytes of blob, num_classes2 > 0: with the second head
+static int create_model(const kws_config* cfg, const kws_cell_wrappers& wr, int num_classes2, const void* weights_blob, size_t nbytes,
+                        size_t need, kws_handle* out);
+
 extern "C" {
 
 // Compiler provenance is part of the version string: the fp32 resident kernels rely on hand-placed hazard fences around
@@ -122,9 +144,32 @@ int kws_create_wrapped(const kws_config* cfg, const kws_cell_wrappers* wrap, con
     if (!out) return fail(KWS_ERR_INVALID_ARGUMENT, "out handle pointer is null");
     *out = nullptr;
     if (!config_ok(cfg, &code) || !wrappers_ok(cfg, wrap, &code)) return code;
-    if (!weights_blob) return fail(KWS_ERR_INVALID_ARGUMENT, "weights_blob is null");
     const kws_cell_wrappers wr = wrappers_of(wrap);
-    const size_t need = wrap_layout(*cfg, wr).total * sizeof(float);
+    return create_model(cfg, wr, 0, weights_blob, nbytes, wrap_layout(*cfg, wr).total * sizeof(float), out);
+}
+
+size_t kws_sizeof_head_io(void) { return sizeof(kws_head_io); }
+
+size_t kws_weights_nbytes_heads(const kws_config* cfg, int32_t num_classes2) {
+    int code;
+    if (!config_ok(cfg, &code) || !heads_ok(cfg, num_classes2, &code)) return 0;
+    return (blob_layout(*cfg).total + heads_floats(cfg, num_classes2)) * sizeof(float);
+}
+
+int kws_create_heads(const kws_config* cfg, int32_t num_classes2, const void* weights_blob, size_t nbytes, kws_handle* out) {
+    int code;
+    if (!out) return fail(KWS_ERR_INVALID_ARGUMENT, "out handle pointer is null");
+    *out = nullptr;
+    if (!config_ok(cfg, &code) || !heads_ok(cfg, num_classes2, &code)) return code;
+    return create_model(cfg, kws_cell_wrappers{0, 0}, num_classes2, weights_blob, nbytes,
+                        (blob_layout(*cfg).total + heads_floats(cfg, num_classes2)) * sizeof(float), out);
+}
+
+}  // extern "C"
+
+static int create_model(const kws_config* cfg, const kws_cell_wrappers& wr, int num_classes2, const void* weights_blob, size_t nbytes,
+                        size_t need, kws_handle* out) {
+    if (!weights_blob) return fail(KWS_ERR_INVALID_ARGUMENT, "weights_blob is null");
     if (nbytes != need)
         return fail(KWS_ERR_INVALID_ARGUMENT, "weights_blob has %zu bytes, config needs %zu", nbytes, need);
     int ndev = 0;
@@ -136,6 +181,7 @@ int kws_create_wrapped(const kws_config* cfg, const kws_cell_wrappers* wrap, con
     m->cfg = *cfg;
     m->wrap = wr;
     m->wrapped = wr.use_layer_norm || wr.use_residual;
+    m->num_classes2 = num_classes2;
     {
         const hipError_t e = hipGetDevice(&m->device);
         if (e != hipSuccess) { delete m; return hip_fail(e, "hipGetDevice"); }
@@ -146,7 +192,7 @@ int kws_create_wrapped(const kws_config* cfg, const kws_cell_wrappers* wrap, con
     }
     std::vector<float> host;
     {
-        const int rc = pack_weights(*cfg, wr, static_cast<const float*>(weights_blob), &m->pk, &host);
+        const int rc = pack_weights(*cfg, wr, static_cast<const float*>(weights_blob), &m->pk, &host, num_classes2);
         if (rc != KWS_OK) { delete m; return rc; }
     }
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&m->d_weights), host.size() * sizeof(float));
@@ -179,6 +225,8 @@ int kws_create_wrapped(const kws_config* cfg, const kws_cell_wrappers* wrap, con
     return KWS_OK;
 }
 
+extern "C" {
+
 int kws_create(const kws_config* cfg, const void* weights_blob, size_t nbytes, kws_handle* out) {
     return kws_create_wrapped(cfg, nullptr, weights_blob, nbytes, out);
 }
@@ -198,7 +246,7 @@ int kws_destroy(kws_handle h) {
     for (auto ev : h->ovl_events) hipEventDestroy(ev);
     for (auto ev : h->ovl_tail) if (ev) hipEventDestroy(ev);
     for (auto sx : h->lane_stream) if (sx) hipStreamDestroy(sx);
-    for (void* p : {(void*)h->oct_aq, (void*)h->oct_range, (void*)h->oct_prev}) if (p) hipFree(p);
+    for (void* p : {(void*)h->oct_aq, (void*)h->oct_range, (void*)h->oct_prev, (void*)h->heads_prev}) if (p) hipFree(p);
     delete h;
     // The handle is gone whatever happened before: always KWS_OK (a caller that read a failure as "still alive" would free it
     // twice).  A pipelined step that timed out and was never followed by another call is left in kws_last_error().

@@ -26,8 +26,10 @@ struct StepPlan {
 
 // The one place that decides kernel family, launch layout, window tail and seams.  Pure: reads the handle, touches nothing.
 // `profiling`: kws_set_profiling's switch (a parameter, so that kws_reserve can ask for both answers); `window`: a decode-window
-// tail that fits the fused form is offered (StepArgs::wt, step_takes_window).
-StepPlan plan_step(const kws_model* h, int B, int T, bool profiling, bool window) {
+// tail that fits the fused form is offered (StepArgs::wt, step_takes_window); `heads`: a kws_step_heads call (StepArgs::heads) --
+// one launch per layer, none of them `last`, the top layer's seam among the buffers, dense_heads_kernel in the top layer's slot.
+// The overlapped and layer-pipelined layouts stay with kws_step.
+StepPlan plan_step(const kws_model* h, int B, int T, bool profiling, bool window, bool heads = false) {
     using M = kws_model;
     // KWS_NO_PIPELINE=1: never the layer-pipelined launch -- what a device without fine-grained memory gets (pipe_disabled), for A/B
     // runs and for the tests of the layouts that take its place (tests/test_gpu_wrapped.py)
@@ -64,10 +66,10 @@ StepPlan plan_step(const kws_model* h, int B, int T, bool profiling, bool window
     // AUTO keeps the resident kernels where they exist even when this launch would be faster (H=128, L=2: +10 % at B <= 2048;
     // L=4, B=1024: 2.2x; select it with KWS_KERNEL_GENERIC): the two kernel families round differently in the last bit, and a
     // stream's result must not depend on how many neighbours it is batched or sharded with.
-    const bool pipelined = !h->pipe_disabled && !no_pipe && (c.precision == KWS_FP32 || f16_streams) && L >= 2 &&
+    const bool pipelined = !heads && !h->pipe_disabled && !no_pipe && (c.precision == KWS_FP32 || f16_streams) && L >= 2 &&
                            h->kernel_kind != KWS_KERNEL_RESIDENT && !any_resident && fits;
     // Layers overlapped on HIP streams: the pipelined kernel has its own in-kernel pipeline; profiling times one launch after another
-    const bool overlapped = !profiling && c.precision == KWS_FP32 && L >= 2 && L <= 5 && !pipelined && fits && T >= KWS_OVERLAP_MIN_T;
+    const bool overlapped = !heads && !profiling && c.precision == KWS_FP32 && L >= 2 && L <= 5 && !pipelined && fits && T >= KWS_OVERLAP_MIN_T;
     p.layout = pipelined ? StepPlan::kPipelined : overlapped ? StepPlan::kOverlapped : StepPlan::kSequential;
 
     if (pipelined) {      // one launch, timed as the last layer's slot
@@ -77,7 +79,7 @@ StepPlan plan_step(const kws_model* h, int B, int T, bool profiling, bool window
     for (int l = 0; l < L && !pipelined; ++l) {
         // int8: no GRU layer is `last` -- every layer hands its output rows on through the seam, and the class projection is its
         // own OctbitMatMul call over the whole [T,H] block behind the top layer (kOctbitFc; launch_slot)
-        const bool first = l == 0, last = !int8 && l == L - 1;
+        const bool first = l == 0, last = !int8 && !heads && l == L - 1;
         const uint8_t tail = window && last && !overlapped;
         if (f16_streams) p.tag[l] = {M::kF16x3Generic, (uint8_t)(H / 64), first, last, 0};
         else if (f16) p.tag[l] = {M::kF16x3, (uint8_t)(first ? h->pk.f16_kx0 : 4), first, last, tail};
@@ -87,7 +89,10 @@ StepPlan plan_step(const kws_model* h, int B, int T, bool profiling, bool window
         else p.tag[l] = {(uint8_t)(h->wrapped ? M::kGenericWrapped : M::kGeneric), (uint8_t)(H / 64), first, last, 0};
     }
 
-    if (L >= 2 || int8) {      // a single fp32 / f16x3 layer has no seam
+    if (heads) {               // every layer has a seam, the top one's is what the heads read
+        p.tag[L - 1].heads = 1;
+        p.seams = {L >= 2 ? 2 : 1, (size_t)groups * (size_t)H * 16 * sizeof(float) * T, false};
+    } else if (L >= 2 || int8) {      // a single fp32 / f16x3 layer has no seam
         const size_t frame_bytes = (size_t)groups * (size_t)H * 16 * sizeof(float);
         if (pipelined) p.seams = {L - 1, frame_bytes * T, true};      // read by another XCD while the kernel runs: fine-grained memory
         else if (overlapped) {
@@ -129,8 +134,16 @@ int carve_seams(kws_handle h, const SeamLayout& want) {
 }
 
 // Everything besides the seams that depends on the batch size: int8 exchange buffers, the pipelined launch's counters.
-int ensure_side_buffers(kws_handle h, int B, bool pipelined) {
+int ensure_side_buffers(kws_handle h, int B, bool pipelined, bool heads) {
     const size_t groups = (size_t)kws::groups_of(B);
+    if (heads && groups > h->heads_groups) {      // the two heads' prev_word as they were before the launch (dense_heads.hip)
+        KWS_HIP(hipDeviceSynchronize());
+        if (h->heads_prev) hipFree(h->heads_prev);
+        h->heads_prev = nullptr; h->heads_groups = 0;
+        KWS_HIP(hipMalloc(reinterpret_cast<void**>(&h->heads_prev), 2 * groups * 16 * sizeof(int32_t)));
+        h->heads_groups = groups;
+        ++h->scratch_allocs;
+    }
     if (h->cfg.precision == KWS_INT8 && groups > h->oct_groups) {
         KWS_HIP(hipDeviceSynchronize());
         if (h->oct_aq) hipFree(h->oct_aq);
@@ -169,13 +182,13 @@ int ensure_side_buffers(kws_handle h, int B, bool pipelined) {
 // The buffers `plan` launches with.  A device without fine-grained memory gives the pipelined launch up for this handle, and the
 // call is planned again, once: this call runs its layers one launch after another (planned as under profiling, whose one effect
 // is that the layers are not overlapped); only later calls may overlap them.
-int provision(kws_handle h, StepPlan& plan, int B, int T, bool window) {
+int provision(kws_handle h, StepPlan& plan, int B, int T, bool window, bool heads = false) {
     if (plan.layout == StepPlan::kStack) return KWS_OK;
-    int rc = ensure_side_buffers(h, B, plan.layout == StepPlan::kPipelined);
+    int rc = ensure_side_buffers(h, B, plan.layout == StepPlan::kPipelined, heads);
     if (rc == KWS_OK) rc = carve_seams(h, plan.seams);
     if (rc == kNoFineGrainedMemory) {
         h->pipe_disabled = true;
-        plan = plan_step(h, B, T, /*profiling=*/true, window);
+        plan = plan_step(h, B, T, /*profiling=*/true, window, heads);
         rc = carve_seams(h, plan.seams);
     }
     return rc;
@@ -338,6 +351,30 @@ void set_octbit_fc(kws::OctbitFcParams& fp, const kws_model* h, const StepArgs& 
     fp.B = a.B; fp.T = a.T; fp.C = c.num_classes;
 }
 
+// The heads behind the top layer of a kws_step_heads call
+void set_dense_heads(kws::DenseHeadsParams& dp, const kws_model* h, const StepArgs& a) {
+    const kws_config& c = h->cfg;
+    const HeadsArgs& ha = *a.heads;
+    memset(&dp, 0, sizeof(dp));
+    dp.h_top = h->scratch[(c.num_layers - 1) % h->nscratch];
+    dp.seq_len = a.seq_len; dp.reset = a.reset_mask;
+    dp.nn_outputs = ha.nn_outputs;
+    const size_t wfc[2] = {h->pk.wfc_off, h->pk.wfc2_off}, bfc[2] = {h->pk.bfc_off, h->pk.bfc2_off};
+    const int C[2] = {c.num_classes, h->num_classes2};
+    for (int i = 0; i < 2; ++i) {
+        if (!ha.on[i]) continue;
+        kws::DenseHead& d = dp.head[i];
+        const kws_head_io& io = ha.head[i];
+        d.wfc = h->d_weights + wfc[i]; d.bfc = h->d_weights + bfc[i];
+        d.logits = io.logits; d.softmax = io.softmax; d.tokens = io.tokens; d.prev_word = io.prev_word;
+        d.prev_in = io.prev_word ? h->heads_prev + (size_t)i * h->heads_groups * 16 : nullptr;
+        d.decode_thres = io.decode2_thres;
+        d.C = C[i];
+    }
+    dp.value_clip = c.value_clip; dp.use_relu = c.use_relu;
+    dp.B = a.B; dp.T = a.T;
+}
+
 // ---- the launches ----------------------------------------------------------------------------------------------------
 // The launch of profiling slot l as the plan tagged it, on `st`.  step_overlapped passes the time block [t0, t0 + frames) of the
 // call: seams double-buffered per block parity, and behind block 0 the state is the one the block before left in state_out.
@@ -419,6 +456,11 @@ int launch_slot(const kws_model* h, const StepArgs& a, const StepPlan& plan, int
         default: return KWS_OK;      // an empty slot: its layer runs inside another slot's launch
     }
     if (e != hipSuccess) return hip_fail(e, what);
+    if (t.heads) {      // the class heads, inside the top layer's slot
+        kws::DenseHeadsParams dp;
+        set_dense_heads(dp, h, a);
+        return hip_done(kws::launch_dense_heads(dp, H, st), "launch dense_heads");
+    }
     if (c.precision != KWS_INT8 || l != L - 1) return KWS_OK;
     kws::OctbitFcParams fp;      // the class projection, inside the top layer's slot whichever kernel ran that layer
     set_octbit_fc(fp, h, a);
@@ -483,25 +525,38 @@ int step_body(kws_handle h, const StepArgs& a) {
     if (T == 0) {
         // dynamic_rnn over zero frames hands the initial state back -- and clean_state() (detector.py:313-316) has already
         // zeroed it for the streams the mask names.  No GRU kernel runs: h->launch_tag stays what the step before left.
+        if (a.reset_mask && a.heads) {      // both heads' prev_word; the second pass copies state_out onto itself
+            KWS_TRY(hip_done(kws::launch_state_passthrough(a.state_in, a.state_out, a.reset_mask, a.heads->head[0].prev_word, L, B, H, st),
+                             "launch state_passthrough"));
+            return hip_done(kws::launch_state_passthrough(a.state_out, a.state_out, a.reset_mask, a.heads->head[1].prev_word, L, B, H, st),
+                            "launch state_passthrough");
+        }
         if (a.reset_mask)
             return hip_done(kws::launch_state_passthrough(a.state_in, a.state_out, a.reset_mask, a.prev_word, L, B, H, st), "launch state_passthrough");
         if (a.state_out != a.state_in)
             KWS_HIP(hipMemcpyAsync(a.state_out, a.state_in, (size_t)L * B * H * sizeof(float), hipMemcpyDeviceToDevice, st));
         return KWS_OK;
     }
-    StepPlan plan = plan_step(h, B, T, h->profiling, a.wt != nullptr);
+    StepPlan plan = plan_step(h, B, T, h->profiling, a.wt != nullptr, a.heads != nullptr);
+    if (a.heads && !a.heads->on[0] && !a.heads->on[1] && !a.heads->nn_outputs) plan.tag[L - 1].heads = 0;      // nothing behind the stack (launch_slot)
     if (!a.mel) return fail(KWS_ERR_INVALID_ARGUMENT, "mel is null");
     // the streaming kernels address a group's seam (T x H/16 KiB) through buffer instructions with 32-bit offsets
     if (plan.streaming && (long long)T * (H / 16) >= (1LL << 21))
         return fail(KWS_ERR_UNSUPPORTED, "T=%d frames of hidden=%d exceed the 2 GiB a stream group's seam may span: split the call "
                     "(state carried across calls gives identical results)", T, H);
     if ((reinterpret_cast<uintptr_t>(a.mel) & 15) != 0) return fail(KWS_ERR_INVALID_ARGUMENT, "mel must be 16-byte aligned");
-    KWS_TRY(provision(h, plan, B, T, a.wt != nullptr));
+    if (a.heads && T > kws::kHeadsMaxFrames)
+        return fail(KWS_ERR_UNSUPPORTED, "T=%d frames exceed the %d a kws_step_heads call takes: split the call", T, kws::kHeadsMaxFrames);
+    KWS_TRY(provision(h, plan, B, T, a.wt != nullptr, a.heads != nullptr));
     if (plan.layout == StepPlan::kOverlapped) {
         KWS_TRY(step_overlapped(h, a, plan));
     } else {      // kStack, kSequential, kPipelined: every tagged slot is one launch on the call's stream
         if (c.precision == KWS_INT8 && a.prev_word)
             KWS_HIP(hipMemcpyAsync(h->oct_prev, a.prev_word, (size_t)B * sizeof(int32_t), hipMemcpyDeviceToDevice, st));
+        for (int i = 0; a.heads && i < 2; ++i)        // what the heads' first frame block reads while their last one writes prev_word
+            if (a.heads->on[i] && a.heads->head[i].prev_word)
+                KWS_HIP(hipMemcpyAsync(h->heads_prev + (size_t)i * h->heads_groups * 16, a.heads->head[i].prev_word, (size_t)B * sizeof(int32_t),
+                                       hipMemcpyDeviceToDevice, st));
         if (plan.layout == StepPlan::kPipelined)      // the frame counters, cleared on the call's stream first
             KWS_HIP(hipMemsetAsync(h->pipe_ready, 0, (size_t)L * h->pipe_groups * sizeof(int), st));
         for (int l = 0; l < L; ++l)
@@ -541,6 +596,13 @@ int kws_host::step_impl(kws_handle h, const StepArgs& a) {
     if (a.B == 0) return KWS_OK;   // nothing to advance (empty tensors have null data pointers)
     if (!a.state_in || !a.state_out) return fail(KWS_ERR_INVALID_ARGUMENT, "state_in/state_out must not be null");
     if (a.tokens && !a.prev_word) return fail(KWS_ERR_INVALID_ARGUMENT, "tokens requires prev_word");
+    if (a.heads) {
+        if (h->num_classes2 <= 0) return fail(KWS_ERR_INVALID_ARGUMENT, "kws_step_heads needs a handle with a second class head (kws_create_heads)");
+        for (int i = 0; i < 2; ++i)
+            if (a.heads->on[i] && a.heads->head[i].tokens && !a.heads->head[i].prev_word)
+                return fail(KWS_ERR_INVALID_ARGUMENT, "head%d: tokens requires prev_word", i + 1);
+        if ((reinterpret_cast<uintptr_t>(a.heads->nn_outputs) & 15) != 0) return fail(KWS_ERR_INVALID_ARGUMENT, "nn_outputs must be 16-byte aligned");
+    }
     if (a.locked) return step_body(h, a);
     BusyGuard busy(h->in_call);
     if (!busy.owned)
@@ -563,6 +625,20 @@ int kws_step(kws_handle h, const float* mel, const float* state_in, float* logit
     return step_impl(h, a);
 }
 
+int kws_step_heads(kws_handle h, const float* mel, const float* state_in, float* state_out, const int32_t* seq_len,
+                   const uint8_t* reset_mask, float* nn_outputs, const kws_head_io* head1, const kws_head_io* head2, int B, int T,
+                   void* stream) {
+    HeadsArgs ha;
+    ha.nn_outputs = nn_outputs;
+    if (head1) { ha.head[0] = *head1; ha.on[0] = true; }
+    if (head2) { ha.head[1] = *head2; ha.on[1] = true; }
+    StepArgs a;
+    a.mel = mel; a.state_in = state_in; a.state_out = state_out; a.seq_len = seq_len; a.reset_mask = reset_mask;
+    a.B = B; a.T = T; a.stream = static_cast<hipStream_t>(stream);
+    a.heads = &ha;
+    return step_impl(h, a);
+}
+
 int kws_reserve(kws_handle h, int B, int T) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
     BusyGuard busy(h->in_call);
@@ -572,6 +648,10 @@ int kws_reserve(kws_handle h, int B, int T) {
     for (const bool profiling : {true, false}) {
         StepPlan plan = plan_step(h, B, T, profiling, false);
         KWS_TRY(provision(h, plan, B, T, false));
+    }
+    if (h->num_classes2 > 0) {      // a heads handle: kws_step_heads' layout too (one answer, whatever the profiling switch)
+        StepPlan plan = plan_step(h, B, T, h->profiling, false, true);
+        KWS_TRY(provision(h, plan, B, T, false, true));
     }
     return KWS_OK;
 }

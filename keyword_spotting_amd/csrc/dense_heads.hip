@@ -1,0 +1,191 @@
+// The class heads of a multi-head step (kws_step_heads): one launch behind the GRU stack that reads the top layer's seam once
+// and produces, for up to two dense layers, logits -> relu / clip -> softmax -> the ctc_decode2 frame rule, and optionally the
+// top layer's rows themselves (model/nn_outputs:0, [B,T,H] row-major).
+//
+// One workgroup = one 16-stream group x kHeadFrames frames.  Wave w projects the frames of slots w, w + 4, ...: a lane's xl
+// float4 of tile n (kws_internal.h) is the B operand of the k-chunks 4n..4n+3, the A operands are the fragments of Wfc^T
+// (padded to 16 rows) the fused epilogue of the GRU kernels uses, and the 16x16 result holds class 4g + r of stream s in lane
+// (g, s).  The logits wait in LDS; behind a barrier one thread per (stream, frame) does the row's softmax and word, consecutive
+// lanes on consecutive frames of one stream, so that a stream's rows leave as one contiguous run.
+//
+// Rows past seq_len.  A GRU layer that is not the last one stores its carried state for frames t >= seq_len[b]
+// (gru_resident.hip, the frame's store of hreg), where dynamic_rnn emits the zero row.  This kernel therefore takes seq_len
+// itself and replaces the loaded row by zeros: nn_outputs = 0, logits = bfc (the accumulator's initial value, every product
+// an exact zero), and the frame has no word.  It never depends on what the seam holds there.
+//
+// prev_word is in/out, and the frame blocks of one stream are different workgroups: the block with t = 0 reads it, the block
+// with t = T - 1 writes it.  Settled by construction: the host copies each head's prev_word into a side buffer on the call's
+// stream ahead of the launch (DenseHead::prev_in, as the int8 path's oct_prev), and only that copy is read here.  A block with
+// t0 > 0 gets the word of frame t0 - 1 by projecting that frame itself in slot 0 -- the same loop body, so the same
+// instruction sequence and the same bits as the block that owns the frame.
+#include "gru_device.h"
+#include "launch.h"
+
+namespace kws {
+
+namespace {
+
+constexpr int kHeadSlots = kHeadFrames + 1;        // slot f <-> frame t0 - 1 + f; slot 0 is the halo
+
+// relu / clip, softmax and the ctc_decode2 frame rule of one row: the arithmetic of epilogue_flush (gru_device.h)
+__device__ __forceinline__ int head_row(float (&lg)[kMaxClasses], float (&pr)[kMaxClasses], int C, int use_relu, float value_clip, float thres) {
+    if (use_relu) {
+#pragma unroll
+        for (int c = 0; c < kMaxClasses; ++c) {
+            lg[c] = fmaxf(lg[c], 0.f);
+            if (value_clip > 0.f) lg[c] = fminf(lg[c], 20.f);
+        }
+    }
+    float m = lg[0];
+#pragma unroll
+    for (int c = 1; c < kMaxClasses; ++c) m = (c < C) ? fmaxf(m, lg[c]) : m;
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < kMaxClasses; ++c) {
+        pr[c] = (c < C) ? __expf(lg[c] - m) : 0.f;
+        sum += pr[c];
+    }
+    const float inv = __builtin_amdgcn_rcpf(sum);
+#pragma unroll
+    for (int c = 0; c < kMaxClasses; ++c) pr[c] *= inv;
+    // classes 1..C-2 (utils/prediction.py:67,74-75): first maximum, strict >
+    int word = -1;
+    float best = -1.f;
+#pragma unroll
+    for (int c = 1; c < kMaxClasses - 1; ++c) {
+        if (c < C - 1 && pr[c] > best) { best = pr[c]; word = c - 1; }
+    }
+    return best > thres ? word : -1;
+}
+
+// a row of C floats; rows of an even C are 8-byte aligned (the outputs are, as kws_step's)
+__device__ __forceinline__ void store_row(float* dst, const float (&v)[kMaxClasses], int C) {
+    if ((C & 1) == 0) {
+        float2* o = reinterpret_cast<float2*>(dst);
+#pragma unroll
+        for (int c = 0; c < kMaxClasses / 2; ++c)
+            if (2 * c < C) o[c] = make_float2(v[2 * c], v[2 * c + 1]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < kMaxClasses; ++c)
+            if (c < C) dst[c] = v[c];
+    }
+}
+
+}  // namespace
+
+template <int NT>
+__global__ void __launch_bounds__(256) dense_heads_kernel(const DenseHeadsParams p) {
+    constexpr int H = 16 * NT;
+    __shared__ float lgs[2][16][kHeadSlots][8];      // logits of [head][stream][slot]: a lane of the row phase reads its 8 as two float4
+    __shared__ int words[2][16][kHeadSlots];
+    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, g = lane >> 4, s = lane & 15;
+    const int G = blockIdx.x, t0 = blockIdx.y * kHeadFrames, T = p.T;
+    const int b = G * kStreamsPerGroup + s;
+    const bool bvalid = b < p.B;
+
+    // A operands: Wfc^T of each head, k-chunk kc in wa[hd][kc]; an absent head (C == 0) keeps zeros and is skipped below
+    float wa[2][4 * NT];
+    f32x4 bias4[2];
+#pragma unroll
+    for (int hd = 0; hd < 2; ++hd) {
+        const bool on = p.head[hd].C > 0;
+#pragma unroll
+        for (int kc = 0; kc < 4 * NT; ++kc) wa[hd][kc] = on ? p.head[hd].wfc[kc * 64 + lane] : 0.f;
+        bias4[hd] = on ? ld4(p.head[hd].bfc + 4 * g) : splat4(0.f);
+    }
+    int len_s = T;
+    if (p.seq_len && bvalid) len_s = p.seq_len[b];
+
+    const float4* src = p.h_top + (size_t)G * T * NT * 64 + lane;
+    const int f_end = min(kHeadSlots, T - t0 + 1);
+    for (int f = (w == 0 && t0 == 0) ? 4 : w; f < f_end; f += 4) {      // the first block has no halo
+        const int t = t0 - 1 + f;
+        f32x4 v[NT];
+#pragma unroll
+        for (int n = 0; n < NT; ++n) {
+            const float4 x = src[((size_t)t * NT + n) * 64];
+            v[n] = (f32x4){x.x, x.y, x.z, x.w};
+        }
+        if (t >= len_s) {             // dynamic_rnn's zero row
+#pragma unroll
+            for (int n = 0; n < NT; ++n) v[n] = splat4(0.f);
+        }
+        if (p.nn_outputs && f > 0 && bvalid) {
+            float4* dst = reinterpret_cast<float4*>(p.nn_outputs + ((size_t)b * T + t) * H + 4 * g);
+#pragma unroll
+            for (int n = 0; n < NT; ++n) dst[4 * n] = make_float4(v[n][0], v[n][1], v[n][2], v[n][3]);
+        }
+#pragma unroll
+        for (int hd = 0; hd < 2; ++hd) {
+            if (p.head[hd].C == 0) continue;
+            // The summation order of the fused epilogue (gru_resident.hip, gru_kernels.hip): four partial sums over a quarter of the
+            // units each -- there one per wave, the first one starting from bfc, the others from zero -- folded ((0 + 1) + 2) + 3
+            // (epilogue_fold), so that head 1 here and through kws_step is the same sum of the same products.
+            f32x4 part[4] = {bias4[hd], splat4(0.f), splat4(0.f), splat4(0.f)};
+#pragma unroll
+            for (int n = 0; n < NT; ++n)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) part[n / (NT / 4)] = mfma4(wa[hd][4 * n + e], v[n][e], part[n / (NT / 4)]);
+            const f32x4 acc = ((part[0] + part[1]) + part[2]) + part[3];
+            if (g < 2) *reinterpret_cast<f32x4*>(&lgs[hd][s][f][4 * g]) = acc;
+        }
+    }
+    __syncthreads();
+
+    // one thread per (stream, slot): the row's relu / clip, softmax and word
+    for (int item = tid; item < 16 * kHeadSlots; item += 256) {
+        const int si = item / kHeadSlots, f = item - si * kHeadSlots;
+        const int t = t0 - 1 + f, bi = G * kStreamsPerGroup + si;
+        const bool in_call = t >= 0 && t < T;
+        const int len = (p.seq_len && bi < p.B) ? p.seq_len[bi] : T;
+#pragma unroll
+        for (int hd = 0; hd < 2; ++hd) {
+            const DenseHead& hp = p.head[hd];
+            if (hp.C == 0) continue;
+            if (!in_call) { words[hd][si][f] = -1; continue; }
+            float lg[kMaxClasses], pr[kMaxClasses];
+            {
+                const f32x4* row = reinterpret_cast<const f32x4*>(&lgs[hd][si][f][0]);
+                const f32x4 lo = row[0], hi = row[1];
+#pragma unroll
+                for (int c = 0; c < 4; ++c) { lg[c] = lo[c]; lg[4 + c] = hi[c]; }
+            }
+            const int word = head_row(lg, pr, hp.C, p.use_relu, p.value_clip, hp.decode_thres);
+            words[hd][si][f] = t < len ? word : -1;
+            if (f > 0 && bi < p.B) {
+                const size_t row = (size_t)bi * T + t;
+                if (hp.logits) store_row(hp.logits + row * hp.C, lg, hp.C);
+                if (hp.softmax) store_row(hp.softmax + row * hp.C, pr, hp.C);
+            }
+        }
+    }
+    __syncthreads();
+
+    // tokens (utils/prediction.py:76-80) and the carried word
+    for (int item = tid; item < 16 * kHeadFrames; item += 256) {
+        const int si = item / kHeadFrames, f = 1 + (item - si * kHeadFrames);
+        const int t = t0 - 1 + f, bi = G * kStreamsPerGroup + si;
+        if (t >= T || bi >= p.B) continue;
+#pragma unroll
+        for (int hd = 0; hd < 2; ++hd) {
+            const DenseHead& hp = p.head[hd];
+            if (hp.C == 0 || !hp.prev_word) continue;
+            const int word = words[hd][si][f];
+            int prev;
+            if (t == 0) prev = (p.reset && p.reset[bi]) ? -1 : hp.prev_in[bi];
+            else prev = words[hd][si][f - 1];
+            if (hp.tokens) hp.tokens[(size_t)bi * T + t] = (int8_t)((word >= 0 && word != prev) ? word + 1 : 0);
+            if (t == T - 1) hp.prev_word[bi] = word;
+        }
+    }
+}
+
+hipError_t launch_dense_heads(const DenseHeadsParams& p, int hidden, hipStream_t st) {
+    const dim3 grid(groups_of(p.B), (p.T + kHeadFrames - 1) / kHeadFrames);
+    return with_int<4, 8, 16>(hidden % 16 == 0 ? hidden / 16 : -1, [&](auto nt) {
+        return launch_lds<dense_heads_kernel<nt()>>(grid, dim3(256), 0, st, p);
+    });
+}
+
+}  // namespace kws

@@ -223,6 +223,31 @@ struct OctbitFcParams {
 hipError_t launch_gru_layer_octbit(const GruOctbitParams& p, hipStream_t st);
 hipError_t launch_octbit_fc(const OctbitFcParams& p, hipStream_t st);
 
+// the class heads of a multi-head step (dense_heads.hip): behind a stack whose top layer wrote a seam like every other layer
+struct DenseHead {
+    const float* wfc;       // [H/4][64] fragments of Wfc^T padded to 16 rows (GruLayerParams::wfc)
+    const float* bfc;       // [16] padded
+    float* logits;          // [B,T,C] or null
+    float* softmax;         // [B,T,C] or null
+    int8_t* tokens;         // [B,T] or null
+    int32_t* prev_word;     // [B] or null: written by the block that holds frame T - 1
+    const int32_t* prev_in; // copy of prev_word taken before the launch (null iff prev_word is)
+    float decode_thres;
+    int C;                  // 0: this head is not wanted
+};
+struct DenseHeadsParams {
+    const float4* h_top;    // top layer output, xl layout [G][T][H/16][64]
+    const int32_t* seq_len; // [B] or null: frames t >= seq_len[b] are the zero row, whatever the seam holds there
+    const uint8_t* reset;   // [B] or null: non-zero -> the stream's previous word is -1
+    float* nn_outputs;      // [B,T,H] row-major or null, 16-byte aligned
+    DenseHead head[2];
+    float value_clip;
+    int use_relu, B, T;
+};
+constexpr int kHeadFrames = 32;          // frames per workgroup
+constexpr int kHeadsMaxFrames = 65535 * kHeadFrames;      // grid.y
+hipError_t launch_dense_heads(const DenseHeadsParams& p, int hidden, hipStream_t st);
+
 // decode window of the stream manager (stream_kernels.hip)
 struct WindowParams {
     int8_t* words;            // [B][nq][tmax] per-frame ctc_decode2 word (-1 none); tmax % 16 == 0

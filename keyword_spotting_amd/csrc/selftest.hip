@@ -18,18 +18,25 @@ thread_local bool g_in_selftest = false;
 // With the cell wrappers each layer is ResidualWrapper(LayerNormalizer(GRUCell)) (models/rnn_ctc.py:186-197): the input
 // normalised over its features (mean, population variance, eps 1e-5; scale ibeta, shift igamma: custom_wrapper.py:126-158) before
 // the cell, and on layers >= 1 the output 0.7071 (h' + x) with x the raw input (:112-116), the state h'.
+// seq_len: frames t >= seq_len[b] keep the state and project the zero row (dynamic_rnn).  top: the rows the dense layer reads,
+// [B,T,H].  C2 > 0: the second head (Wfc2 [H,C2], bfc2 [C2] behind the blob, kws_weights_nbytes_heads) on the same rows -> logits2.
 void host_forward(const kws_config& c, const kws_cell_wrappers& wr, const float* blob, const float* mel, const float* st0, int B, int T,
-                  std::vector<double>& logits, std::vector<double>& state) {
+                  std::vector<double>& logits, std::vector<double>& state, const int32_t* seq_len = nullptr, std::vector<double>* top = nullptr,
+                  int C2 = 0, std::vector<double>* logits2 = nullptr) {
     const int H = c.hidden, L = c.num_layers, C = c.num_classes;
     const BlobLayout bl = blob_layout(c);
     const WrapLayout wl = wrap_layout(c, wr);
     state.assign(st0, st0 + (size_t)L * B * H);
     logits.assign((size_t)B * T * C, 0.0);
+    if (top) top->assign((size_t)B * T * H, 0.0);
+    if (logits2) logits2->assign((size_t)B * T * C2, 0.0);
     std::vector<double> x, g(2 * H), cand(H), hn(H);
     for (int b = 0; b < B; ++b)
         for (int t = 0; t < T; ++t) {
             x.assign(mel + ((size_t)b * T + t) * c.n_mel, mel + ((size_t)b * T + t + 1) * c.n_mel);
-            for (int l = 0; l < L; ++l) {
+            const bool live = !seq_len || t < seq_len[b];
+            if (!live) x.assign(H, 0.0);
+            for (int l = 0; l < L && live; ++l) {
                 const int I = bl.layer[l].in;
                 const std::vector<double> x_raw = x;
                 if (wr.use_layer_norm) {
@@ -67,6 +74,14 @@ void host_forward(const kws_config& c, const kws_cell_wrappers& wr, const float*
                 for (int j = 0; j < H; ++j) a += x[j] * Wfc[(size_t)j * C + k];
                 if (c.use_relu) { a = std::max(a, 0.0); if (c.value_clip > 0) a = std::min(a, 20.0); }
                 logits[((size_t)b * T + t) * C + k] = a;
+            }
+            if (top) std::copy(x.begin(), x.end(), top->begin() + ((size_t)b * T + t) * H);
+            const float *Wfc2 = blob + wl.total, *bfc2 = Wfc2 + (size_t)H * C2;
+            for (int k = 0; k < C2 && logits2; ++k) {
+                double a = bfc2[k];
+                for (int j = 0; j < H; ++j) a += x[j] * Wfc2[(size_t)j * C2 + k];
+                if (c.use_relu) { a = std::max(a, 0.0); if (c.value_clip > 0) a = std::min(a, 20.0); }
+                (*logits2)[((size_t)b * T + t) * C2 + k] = a;
             }
         }
 }
@@ -123,6 +138,67 @@ int selftest_case(const kws_config& cfg, const kws_cell_wrappers& wr, int kernel
     for (size_t i = 0; i < st.size(); ++i) { const double d = std::fabs(st[i] - want_s[i]); es = (d > es || d != d) ? d : es; }
     *err_logit = el; *err_state = es;
     if (state_out) *state_out = st;
+    return KWS_OK;
+}
+
+// the same case through kws_step_heads on a temporary heads handle (blob: with the second head behind it), stream 1 with a short
+// seq_len: max abs deviation of both heads' logits, of nn_outputs and of the state from the host loop
+int selftest_heads_case(const kws_config& cfg, int C2, int kernel_kind, const std::vector<float>& blob, const std::vector<float>& mel,
+                        const std::vector<float>& st0, int B, int T, double* err_logit, double* err_rows, double* err_state, std::string* kernels) {
+    const int H = cfg.hidden, L = cfg.num_layers, C = cfg.num_classes;
+    std::vector<int32_t> len(B, T);
+    len[1] = T / 2;
+    kws_handle m = nullptr;
+    int rc = kws_create_heads(&cfg, C2, blob.data(), blob.size() * sizeof(float), &m);
+    if (rc != KWS_OK) return rc;
+    rc = kws_set_kernel(m, kernel_kind);
+    DevBuf d_mel, d_st, d_len, d_l1, d_l2, d_nn;
+    std::vector<float> l1((size_t)B * T * C), l2((size_t)B * T * C2), nn((size_t)B * T * H), st((size_t)L * B * H);
+    auto hip = [&](hipError_t e, const char* what) { if (e != hipSuccess && rc == KWS_OK) rc = hip_fail(e, what); };
+    if (rc == KWS_OK) {
+        hip(d_mel.alloc(mel.size() * 4), "selftest hipMalloc");
+        hip(d_st.alloc(st.size() * 4), "selftest hipMalloc");
+        hip(d_len.alloc(len.size() * 4), "selftest hipMalloc");
+        hip(d_l1.alloc(l1.size() * 4), "selftest hipMalloc");
+        hip(d_l2.alloc(l2.size() * 4), "selftest hipMalloc");
+        hip(d_nn.alloc(nn.size() * 4), "selftest hipMalloc");
+    }
+    if (rc == KWS_OK) {
+        hip(hipMemcpy(d_mel.p, mel.data(), mel.size() * 4, hipMemcpyHostToDevice), "selftest upload");
+        hip(hipMemcpy(d_st.p, st0.data(), st0.size() * 4, hipMemcpyHostToDevice), "selftest upload");
+        hip(hipMemcpy(d_len.p, len.data(), len.size() * 4, hipMemcpyHostToDevice), "selftest upload");
+        hip(hipDeviceSynchronize(), "selftest sync");
+    }
+    if (rc == KWS_OK) {
+        const kws_head_io h1 = {static_cast<float*>(d_l1.p), nullptr, nullptr, nullptr, 0.4f};
+        const kws_head_io h2 = {static_cast<float*>(d_l2.p), nullptr, nullptr, nullptr, 0.4f};
+        rc = kws_step_heads(m, static_cast<const float*>(d_mel.p), static_cast<const float*>(d_st.p), static_cast<float*>(d_st.p),
+                            static_cast<const int32_t*>(d_len.p), nullptr, static_cast<float*>(d_nn.p), &h1, &h2, B, T, nullptr);
+    }
+    if (rc == KWS_OK) {
+        hip(hipDeviceSynchronize(), "selftest kernels");
+        hip(hipMemcpy(l1.data(), d_l1.p, l1.size() * 4, hipMemcpyDeviceToHost), "selftest download");
+        hip(hipMemcpy(l2.data(), d_l2.p, l2.size() * 4, hipMemcpyDeviceToHost), "selftest download");
+        hip(hipMemcpy(nn.data(), d_nn.p, nn.size() * 4, hipMemcpyDeviceToHost), "selftest download");
+        hip(hipMemcpy(st.data(), d_st.p, st.size() * 4, hipMemcpyDeviceToHost), "selftest download");
+    }
+    if (rc == KWS_OK && kernels) {
+        kernels->clear();
+        for (int l = 0; l < L; ++l)
+            if (m->launch_tag[l].family != kws_model::kNone) *kernels += (kernels->empty() ? "" : " + ") + m->launch_name(l);
+    }
+    const std::string keep = g_last_error;
+    kws_destroy(m);
+    if (rc != KWS_OK) { g_last_error = keep; return rc; }
+    std::vector<double> want_1, want_2, want_rows, want_s;
+    host_forward(cfg, kws_cell_wrappers{0, 0}, blob.data(), mel.data(), st0.data(), B, T, want_1, want_s, len.data(), &want_rows, C2, &want_2);
+    auto worst = [](const std::vector<float>& got, const std::vector<double>& want, double e) {
+        for (size_t i = 0; i < got.size(); ++i) { const double d = std::fabs(got[i] - want[i]); e = (d > e || d != d) ? d : e; }
+        return e;
+    };
+    *err_logit = worst(l2, want_2, worst(l1, want_1, 0.0));
+    *err_rows = worst(nn, want_rows, 0.0);
+    *err_state = worst(st, want_s, 0.0);
     return KWS_OK;
 }
 
@@ -242,6 +318,20 @@ extern "C" int kws_selftest(kws_handle h) {
                             "%.3g (tolerance %.1g), max |dstate| %.3g (tolerance %.1g). This build (%s) computes wrong results on this "
                             "device: rebuild with the ROCm release it was validated on, or run the repository's GPU tests.",
                             kernels.c_str(), el, tol_rand_logit, es, tol_rand_state, kws_version());
+            // a heads handle (kws_create_heads, fp32): the same case through kws_step_heads, a random second head behind the blob
+            if (h->num_classes2 > 0) {
+                const int C2 = h->num_classes2;
+                for (int i = 0; i < H * C2 + C2; ++i) blob.push_back(rng.next());
+                double er;
+                const int rh = selftest_heads_case(cfg, C2, kind, blob, mel, st0, B, T, &el, &er, &es, &kernels);
+                if (rh != KWS_OK) return rh;
+                if (!(el <= tol_rand_logit && er <= tol_rand_state && es <= tol_rand_state))
+                    return fail(KWS_ERR_HIP, "kws_selftest: kws_step_heads (%s) differs from the host double-precision loop on 19 streams x 8 frames, "
+                                "one of them 4 frames long: max |dlogit| %.3g over both heads (tolerance %.1g), max |dnn_outputs| %.3g, max |dstate| "
+                                "%.3g (tolerance %.1g). This build (%s) computes wrong results on this device: rebuild with the ROCm release it was "
+                                "validated on, or run the repository's GPU tests.",
+                                kernels.c_str(), el, tol_rand_logit, er, es, tol_rand_state, kws_version());
+            }
         }
     }
     return KWS_OK;

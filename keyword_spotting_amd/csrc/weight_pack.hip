@@ -86,6 +86,19 @@ size_t reserve(std::vector<float>& host, size_t n) {
     return off;
 }
 
+// dense: Wfc [H,C] -> A fragments of Wfc^T padded to 16 rows, [H/4][64]; bias padded to 16
+void pack_dense(const float* Wfc, const float* bfc, int H, int C, size_t* wfc_off, size_t* bfc_off, std::vector<float>& host) {
+    const int KCH = H / 4;
+    *wfc_off = reserve(host, (size_t)KCH * 64);
+    for (int kc = 0; kc < KCH; ++kc)
+        for (int lane = 0; lane < 64; ++lane) {
+            const int g = lane >> 4, i = lane & 15;
+            host[*wfc_off + (size_t)kc * 64 + lane] = i < C ? Wfc[(size_t)kmap_grouped(kc, g) * C + i] : 0.f;
+        }
+    *bfc_off = reserve(host, 16);
+    for (int i = 0; i < C; ++i) host[*bfc_off + i] = bfc[i];
+}
+
 // fp32 tables: every precision's biases, and the resident / generic kernels' fragments
 void pack_fp32(const kws_config& cfg, const float* blob, const BlobLayout& bl, PackedWeights* pk, std::vector<float>& host) {
     const int H = cfg.hidden, NT = H / 16, KCH = H / 4, C = cfg.num_classes;
@@ -132,17 +145,7 @@ void pack_fp32(const kws_config& cfg, const float* blob, const BlobLayout& bl, P
                 }
         pk->layers.push_back(L);
     }
-    // dense: Wfc [H,C] -> A fragments of Wfc^T padded to 16 rows, [KCH][64]; bias padded to 16
-    const float* Wfc = blob + bl.wfc;
-    const float* bfc = blob + bl.bfc;
-    pk->wfc_off = reserve(host, (size_t)KCH * 64);
-    for (int kc = 0; kc < KCH; ++kc)
-        for (int lane = 0; lane < 64; ++lane) {
-            const int g = lane >> 4, i = lane & 15;
-            host[pk->wfc_off + (size_t)kc * 64 + lane] = i < C ? Wfc[(size_t)kmap_grouped(kc, g) * C + i] : 0.f;
-        }
-    pk->bfc_off = reserve(host, 16);
-    for (int i = 0; i < C; ++i) host[pk->bfc_off + i] = bfc[i];
+    pack_dense(blob + bl.wfc, blob + bl.bfc, H, C, &pk->wfc_off, &pk->bfc_off, host);
 }
 
 // A operands of the 16x16x32 MFMAs, bf16 or f16x3 (gru_bf16.hip, gru_f16x3*.hip): [H/16 tiles][3 gates][kc chunks][pieces][64 lanes]
@@ -287,9 +290,14 @@ int pack_int8(const kws_config& cfg, const float* blob, const BlobLayout& bl, Pa
 
 }  // namespace
 
-int pack_weights(const kws_config& cfg, const kws_cell_wrappers& wrap, const float* blob, PackedWeights* pk, std::vector<float>* image) {
+int pack_weights(const kws_config& cfg, const kws_cell_wrappers& wrap, const float* blob, PackedWeights* pk, std::vector<float>* image,
+                 int num_classes2) {
     const BlobLayout bl = blob_layout(cfg);
     pack_fp32(cfg, blob, bl, pk, *image);
+    if (num_classes2 > 0) {      // fp32 handles without wrappers only (kws_create_heads): the second head follows the canonical blob
+        const float* Wfc2 = blob + bl.total;
+        pack_dense(Wfc2, Wfc2 + (size_t)cfg.hidden * num_classes2, cfg.hidden, num_classes2, &pk->wfc2_off, &pk->bfc2_off, *image);
+    }
     if (wrap.use_layer_norm) {
         // igamma in its natural feature order: lane (g, s) of k-group k4 holds features 16 k4 + 4g + e, which is the mel row's
         // order and the seam's "xl" order alike (kws_internal.h), so the kernel reads igamma[16 k4 + 4g ..] as it is

@@ -31,6 +31,11 @@ FETCH_SOFTMAX = "model/softmax:0"
 FETCH_LOGIT = "model/logit:0"
 FETCH_STATE = "model/rnn_states:0"
 FETCH_TOKENS = "model/ctc_decode2_tokens:0"     # extension: fused per-frame ctc_decode2 events
+# a customised-keyword model (config.num_classes2; server_demo.py:107-109, main.py:278-302): both dense layers and the top GRU rows
+FETCH_SOFTMAX1 = "model/softmax1:0"
+FETCH_SOFTMAX2 = "model/softmax2:0"
+FETCH_NN_OUTPUTS = "model/nn_outputs:0"
+HEADS_FETCHES = (FETCH_SOFTMAX1, FETCH_SOFTMAX2, FETCH_NN_OUTPUTS)
 
 
 class DeployModel(object):
@@ -49,8 +54,17 @@ class DeployModel(object):
         self._handle = ctypes.c_void_p()
         # the cell wrappers of get_cell (models/rnn_ctc.py:186-197): kws_create_wrapped, whose blob carries the layer norm's tables
         self.wrappers = (bool(getattr(config, "use_layer_norm", False)), bool(getattr(config, "use_residual", False)))
+        # a second dense layer on the same stack (README "Customize keyword"): kws_create_heads, whose blob carries Wfc2 / bfc2
+        self.num_classes2 = _weights.num_classes2(config)
         with torch.cuda.device(self.device):
-            if any(self.wrappers):
+            if self.num_classes2:
+                if any(self.wrappers):
+                    raise _lib.UnsupportedError(_lib.KWS_ERR_UNSUPPORTED, "a second class head (config.num_classes2) has no wrapped form: "
+                                                "use_layer_norm and use_residual must be off")
+                _lib.check(self._lib.kws_create_heads(ctypes.byref(self._cfg), self.num_classes2,
+                                                      blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes,
+                                                      ctypes.byref(self._handle)))
+            elif any(self.wrappers):
                 wrap = _lib.KwsCellWrappers(int(self.wrappers[0]), int(self.wrappers[1]))
                 _lib.check(self._lib.kws_create_wrapped(ctypes.byref(self._cfg), ctypes.byref(wrap),
                                                         blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes,
@@ -189,6 +203,65 @@ class DeployModel(object):
             res["tokens"] = tokens
         return res
 
+    def forward_heads(self, mel, state, seq_len=None, reset_mask=None, heads=(1, 2), want_nn_outputs=True, want_logits=True,
+                      want_softmax=True, prev_words=None, decode2_thres=(0.4, 0.4), state_out=None):
+        """One sess.run of a customised-keyword graph on B streams (kws_step_heads): the GRU stack once, then both dense layers
+        on the top layer's rows.  Returns {'state', 'nn_outputs' [B,T,H], 'head1': {...}, 'head2': {...}} with each requested
+        head's 'logits' / 'softmax' [B,T,C_i] and, if prev_words = (pw1, pw2) is given (either may be None), its 'tokens' [B,T]
+        (that prev_word is updated in place).  heads: which of the two to compute."""
+        if not self.num_classes2:
+            raise _lib.InvalidArgumentError(-1, "forward_heads needs a model with a second head (config.num_classes2)")
+        cfg = self.config
+        mel = self._dev(mel, torch.float32, "mel")
+        state = self._dev(state, torch.float32, "state")
+        if mel.dim() != 3 or mel.shape[2] != cfg.n_mel:
+            raise _lib.InvalidArgumentError(-1, "mel must be [B,T,%d], got %s" % (cfg.n_mel, tuple(mel.shape)))
+        b, t = int(mel.shape[0]), int(mel.shape[1])
+        if tuple(state.shape) != (cfg.num_layers, b, cfg.hidden_size):
+            raise _lib.InvalidArgumentError(-1, "state must be [%d,%d,%d], got %s"
+                                            % (cfg.num_layers, b, cfg.hidden_size, tuple(state.shape)))
+        if seq_len is not None:
+            seq_len = self._dev(seq_len, torch.int32, "seq_len")
+            if tuple(seq_len.shape) != (b,):
+                raise _lib.InvalidArgumentError(-1, "seq_len must be [%d]" % b)
+        if reset_mask is not None:
+            reset_mask = self._dev(reset_mask, torch.uint8, "reset_mask")
+            if tuple(reset_mask.shape) != (b,):
+                raise _lib.InvalidArgumentError(-1, "reset_mask must be [%d]" % b)
+        prev_words = tuple(prev_words) if prev_words is not None else (None, None)
+        res, ios, keep = {}, [None, None], []
+        for i, c in enumerate((cfg.num_classes, self.num_classes2)):
+            if i + 1 not in heads:
+                continue
+            out = {}
+            if want_logits:
+                out["logits"] = torch.empty(b, t, c, dtype=torch.float32, device=self.device)
+            if want_softmax:
+                out["softmax"] = torch.empty(b, t, c, dtype=torch.float32, device=self.device)
+            pw = prev_words[i]
+            if pw is not None:
+                pw = self._dev(pw, torch.int32, "prev_word")
+                out["tokens"] = torch.empty(b, t, dtype=torch.int8, device=self.device)
+                keep.append(pw)
+
+            def addr(x):
+                return None if x is None else x.data_ptr()
+            ios[i] = _lib.KwsHeadIo(addr(out.get("logits")), addr(out.get("softmax")), addr(out.get("tokens")), addr(pw),
+                                    float(decode2_thres[i]))
+            res["head%d" % (i + 1)] = out
+        nn_outputs = torch.empty(b, t, cfg.hidden_size, dtype=torch.float32, device=self.device) if want_nn_outputs else None
+        if state_out is None:
+            state_out = torch.empty_like(state)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_step_heads(
+                self._handle, _lib.ptr(mel), _lib.ptr(state), _lib.ptr(state_out), _lib.ptr(seq_len), _lib.ptr(reset_mask),
+                _lib.ptr(nn_outputs), ctypes.byref(ios[0]) if ios[0] is not None else None,
+                ctypes.byref(ios[1]) if ios[1] is not None else None, b, t, _lib.current_stream_ptr()))
+        res["state"] = state_out
+        if want_nn_outputs:
+            res["nn_outputs"] = nn_outputs
+        return res
+
     def step(self, mel_chunk, prev_state, **kw):
         """(mel_chunk, prev_state) -> (logits, next_state)."""
         r = self.forward(mel_chunk, prev_state, want_logits=True, want_softmax=False, **kw)
@@ -204,6 +277,8 @@ class DeployModel(object):
         single = isinstance(fetches, str)
         names = [fetches] if single else list(fetches)
         known = (FETCH_SOFTMAX, FETCH_LOGIT, FETCH_STATE)
+        if self.num_classes2:           # a one-head model keeps refusing the customised-keyword names, with the message it always had
+            known = known + HEADS_FETCHES
         for n in names:
             if n not in known:
                 raise _lib.InvalidArgumentError(-1, "unknown fetch %r (graph exports %s)" % (n, ", ".join(known)))
@@ -224,12 +299,33 @@ class DeployModel(object):
         squeeze = mel.dim() == 2
         if squeeze:
             mel = mel.unsqueeze(0)
+        if any(n in HEADS_FETCHES for n in names):
+            return self._run_heads(names, single, mel, feed_dict[FEED_STATE], squeeze)
         r = self.forward(mel, feed_dict[FEED_STATE], want_logits=FETCH_LOGIT in names,
                          want_softmax=FETCH_SOFTMAX in names)
         # SURVEY 8a footnote 1: consumers index model/softmax:0 as [T,C] (detector.py:197,285) and
         # model/logit:0 as [1,T,C] (detector.py:249-250) at batch 1
         table = {FETCH_STATE: r["state"], FETCH_LOGIT: r.get("logits"),
                  FETCH_SOFTMAX: (r["softmax"][0] if squeeze else r["softmax"]) if "softmax" in r else None}
+        outs = [table[n] for n in names]
+        return outs[0] if single else outs
+
+    def _run_heads(self, names, single, mel, state, squeeze):
+        """run() of a fetch list that names model/softmax1:0, model/softmax2:0 or model/nn_outputs:0: one kws_step_heads.  Head 1 is
+        the graph's first dense layer, so model/softmax:0 and model/logit:0 in the same list are its outputs; nn_outputs is
+        [B,T,H], batch-major as dynamic_rnn returns it (models/rnn_ctc.py:238-243), and squeezed at batch 1 as the softmaxes are."""
+        want1 = any(n in names for n in (FETCH_SOFTMAX1, FETCH_SOFTMAX, FETCH_LOGIT))
+        heads = tuple(i for i, on in ((1, want1), (2, FETCH_SOFTMAX2 in names)) if on)
+        r = self.forward_heads(mel, state, heads=heads, want_nn_outputs=FETCH_NN_OUTPUTS in names,
+                               want_logits=FETCH_LOGIT in names)
+
+        def sq(x):
+            return x[0] if squeeze else x
+        h1, h2 = r.get("head1", {}), r.get("head2", {})
+        table = {FETCH_STATE: r["state"], FETCH_LOGIT: h1.get("logits"),
+                 FETCH_SOFTMAX: sq(h1["softmax"]) if h1 else None, FETCH_SOFTMAX1: sq(h1["softmax"]) if h1 else None,
+                 FETCH_SOFTMAX2: sq(h2["softmax"]) if h2 else None,
+                 FETCH_NN_OUTPUTS: sq(r["nn_outputs"]) if "nn_outputs" in r else None}
         outs = [table[n] for n in names]
         return outs[0] if single else outs
 

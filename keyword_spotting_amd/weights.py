@@ -14,6 +14,10 @@ per layer also
   -- the reference passes them to _ln(input, s, b) as (ibeta, igamma) (custom_wrapper.py:145-148 against :130): the names are
   swapped against their roles and are kept as the checkpoints have them.  use_residual creates no variables.
 The blob (kws_weights_nbytes_wrapped): the canonical blob, then with the layer norm each layer's ibeta and igamma in layer order.
+with config.num_classes2 (a customised-keyword model, the reference's README "Customize keyword": a second dense layer on the same
+GRU stack) also
+  Wfc2 [H, C2], bfc2 [C2]   arrays only: the customize branch's variable names are not in the reference tree
+and the blob (kws_weights_nbytes_heads) is the canonical blob, then Wfc2 and bfc2.
 """
 import numpy as np
 
@@ -27,6 +31,25 @@ def _layer_norm(config):
 
 
 LN_KEYS = ("ibeta", "igamma")
+
+
+def num_classes2(config):
+    """Class count of the second dense layer, or 0 for a one-head model (config.num_classes2 absent or None)."""
+    return int(getattr(config, "num_classes2", None) or 0)
+
+
+def extend_head(wfc, bfc, new_columns, new_bias):
+    """The README's [H, C + n] matrix from the trained head [H, C] and n new columns [H, n]: the original columns keep
+    their order, the new ones stand in front of the last (ctc blank) column -- (space, words, garbage | new | blank); the
+    bias [C + n] likewise.  -> (Wfc2, bfc2), float32."""
+    wfc, bfc = np.asarray(wfc, np.float32), np.asarray(bfc, np.float32)
+    new_columns, new_bias = np.asarray(new_columns, np.float32), np.asarray(new_bias, np.float32)
+    if wfc.ndim != 2 or bfc.shape != (wfc.shape[1],):
+        raise ValueError("head has shapes %s %s, expected [H, C] and [C]" % (wfc.shape, bfc.shape))
+    if new_columns.ndim != 2 or new_columns.shape[0] != wfc.shape[0] or new_bias.shape != (new_columns.shape[1],):
+        raise ValueError("new columns have shapes %s %s, expected [%d, n] and [n]" % (new_columns.shape, new_bias.shape, wfc.shape[0]))
+    return (np.ascontiguousarray(np.concatenate([wfc[:, :-1], new_columns, wfc[:, -1:]], axis=1)),
+            np.concatenate([bfc[:-1], new_bias, bfc[-1:]]))
 
 
 def init_weights(config, seed=0):
@@ -73,6 +96,15 @@ def check_shapes(config, w):
     if tuple(w["Wfc"].shape) != (h, c) or tuple(w["bfc"].shape) != (c,):
         raise ValueError("fc weights have shapes %s %s, expected %s %s"
                          % (w["Wfc"].shape, w["bfc"].shape, (h, c), (c,)))
+    c2 = num_classes2(config)
+    if c2:
+        if "Wfc2" not in w or "bfc2" not in w:
+            raise ValueError("config.num_classes2=%d but the weights have no Wfc2 / bfc2" % c2)
+        if tuple(w["Wfc2"].shape) != (h, c2) or tuple(w["bfc2"].shape) != (c2,):
+            raise ValueError("second fc weights have shapes %s %s, expected %s %s"
+                             % (w["Wfc2"].shape, w["bfc2"].shape, (h, c2), (c2,)))
+    elif "Wfc2" in w or "bfc2" in w:
+        raise ValueError("the weights have a second head (Wfc2 / bfc2) but config.num_classes2 is not set")
 
 
 def to_blob(config, w):
@@ -81,6 +113,10 @@ def to_blob(config, w):
     for lay in w["layers"]:
         parts += [lay["Wg"], lay["bg"], lay["Wc"], lay["bc"]]
     parts += [w["Wfc"], w["bfc"]]
+    if num_classes2(config):
+        if _layer_norm(config):
+            raise ValueError("a second head (config.num_classes2) has no wrapped form: use_layer_norm must be off")
+        parts += [w["Wfc2"], w["bfc2"]]
     if _layer_norm(config):
         for lay in w["layers"]:
             parts += [lay["ibeta"], lay["igamma"]]
@@ -102,6 +138,9 @@ def from_blob(config, blob):
     for i_l in layer_in_dims(config):
         layers.append(dict(Wg=take(i_l + h, 2 * h), bg=take(2 * h), Wc=take(i_l + h, h), bc=take(h)))
     w = dict(layers=layers, Wfc=take(h, c), bfc=take(c))
+    c2 = num_classes2(config)
+    if c2:
+        w.update(Wfc2=take(h, c2), bfc2=take(c2))
     if _layer_norm(config):
         for lay, i_l in zip(layers, layer_in_dims(config)):
             lay["ibeta"] = take(1).reshape(())
