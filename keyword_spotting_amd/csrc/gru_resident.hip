@@ -3,7 +3,8 @@
 // Semantics, MFMA orientation and the xl exchange layout are those of gru_kernels.hip (see its header and DESIGN.md
 // "Kernels"); this kernel keeps the layer's recurrent + candidate weights in registers (AGPR side of the unified file,
 // 192 + 2*KCX fragments per wave) and the gate x-part in LDS, so nothing but the mel / previous layer's h stream is
-// read per step.  The x-part MFMAs of frame t+1 are issued behind frame t's two barriers (software pipeline), so the
+// read per step.  (Builtin build: the gate x-part sits in the AGPRs that the recurrent weights leave free -- all of it in the
+// first layer, 16 of 32 k-chunks above it -- and only the rest streams from LDS, see resident_kreg.)  The x-part MFMAs of frame t+1 are issued behind frame t's two barriers (software pipeline), so the
 // LDS exchange latency overlaps independent matrix work.
 //
 // A translation unit of its own because of its code generation: with KWS_RESIDENT_VGPR_FORM (set by the Makefile when
@@ -22,18 +23,29 @@ namespace kws {
 // The h-part chains of the frame loop: asm MFMAs need their wait states placed by hand (gru_device.h); builtin ones do not.
 #if KWS_RESIDENT_VGPR_FORM
 template <class... A> __device__ __forceinline__ void resident_prefence(A&...) {}
-template <class... A> __device__ __forceinline__ void resident_fence(A&...) {}
+// (the activations behind an h-part chain stay one VALU cluster: nothing is scheduled across the end of the chain)
+template <class... A> __device__ __forceinline__ void resident_fence(A&...) { __builtin_amdgcn_sched_barrier(0); }
 #else
 template <class... A> __device__ __forceinline__ void resident_prefence(A&... a) { mfma_prefence(a...); }
 template <class... A> __device__ __forceinline__ void resident_fence(A&... a) { mfma_fence(a...); }
 #endif
 
 
+// Gate x-part k-chunks (4 A fragments each: {r0,u0,r1,u1}) that stay in AGPRs for the whole launch.  The recurrent and
+// candidate h-part fragments take 192 of the 256 accumulator registers; with builtin MFMAs (source A straight from an AGPR)
+// the other 64 hold gate x-part chunks instead of idling: the whole x-part of a first layer (KCX <= 16), 16 of the 32 chunks
+// above it, 10 in the window-tail kernel (its tail needs the registers).  The weights are call-invariant, so every chunk
+// kept here is one ds_read_b128 per wave and frame that is not issued.  The inline-asm build takes the A operand of its
+// builtin x-part MFMAs from VGPRs and keeps the earlier placement (two chunks above the first layer).
+#if KWS_RESIDENT_VGPR_FORM
+constexpr int resident_kreg(int kcx, bool first, bool last, bool window) { return first ? kcx : (last && window) ? 10 : 16; }
+#else
+constexpr int resident_kreg(int, bool first, bool, bool) { return first ? 0 : 2; }
+#endif
 // LDS of one workgroup: hbuf | rhbuf | the gate x-part chunks that are not in registers | upper layers: the x block |
 // last layer: the epilogue | first layer: the mel frame.  (The window tail adds kWinTailWordsBytes behind that.)
-constexpr int resident_kreg(bool first) { return first ? 0 : 2; }
-constexpr size_t resident_lds_bytes(int kcx, bool first, bool last) {
-    size_t n = 2 * 8 * 64 * 16 + (size_t)4 * (kcx - resident_kreg(first)) * 64 * 16;
+constexpr size_t resident_lds_bytes(int kcx, bool first, bool last, bool window) {
+    size_t n = 2 * 8 * 64 * 16 + (size_t)4 * (kcx - resident_kreg(kcx, first, last, window)) * 64 * 16;
     if (!first) n += 8 * 64 * 16;
     if (last) n += kEpilogueLdsBytes;
     if (first) n += (size_t)64 * xs_stride(kcx) * 4;
@@ -45,10 +57,12 @@ constexpr size_t resident_lds_bytes(int kcx, bool first, bool last) {
 // ------------------------------------------------------------------------------------------------
 // WINDOW (instantiated for the upper last layer only): the decode-window step of the stream manager rides at the end of
 // every group (window_device.h); every other instantiation compiles exactly as without the parameter.
-template <int KCX, bool FIRST, bool LAST, bool WINDOW = false>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
-gru_layer_resident(const GruLayerParams p) {
+// MASKED: the call carries seq_len (dynamic_rnn copy-through past a stream's length).  Without it the kernel never reads
+// p.seq_len and the state update has no select.  The body is shared by the two kernel templates below it.
+template <int KCX, bool FIRST, bool LAST, bool MASKED, bool WINDOW>
+__device__ __forceinline__ void gru_layer_resident_body(const GruLayerParams& p) {
     static_assert(!WINDOW || (LAST && !FIRST), "the window tail belongs to the last layer of a stack");
+    static_assert(!WINDOW || !MASKED, "the window tail refuses seq_len");
     constexpr int H = 128, NT = 8, KCH = 32;
     const int tid = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -67,12 +81,13 @@ gru_layer_resident(const GruLayerParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* hbuf = reinterpret_cast<f32x4*>(smem);       // [NT][64]  h_{t-1}, xl layout
     f32x4* rhbuf = hbuf + NT * 64;                       // [NT][64]  r (.) h_{t-1}
-    // Upper layers keep gate x-part k-chunks 0 and 1 in registers (KREG): the 8 KiB that frees hold the group's x block (xsb)
-    constexpr int KREG = resident_kreg(FIRST), KL = KCX - KREG;
+    // Gate x-part k-chunks 0..KREG-1 stay in registers (resident_kreg); the rest, KL chunks, streams from LDS every frame
+    constexpr int KREG = resident_kreg(KCX, FIRST, LAST, WINDOW), KL = KCX - KREG;
+    static_assert(KREG >= 0 && KREG <= KCX && 192 + 4 * KREG <= 256, "the register chunks share the 256 AGPRs with the recurrent weights");
     f32x4* wlds = rhbuf + NT * 64;                       // [4 waves][KL][64] gate x-part, k-chunks KREG..KCX-1: {r0,u0,r1,u1}
     f32x4* xsb = wlds + 4 * KL * 64;                     // [NT][64]  upper layers: x(t+1) of the group, xl layout (see "x stream")
     char* const lds_tail = reinterpret_cast<char*>(xsb + (FIRST ? 0 : NT * 64));
-    static_assert(resident_lds_bytes(KCX, FIRST, LAST) + (WINDOW ? kWinTailWordsBytes : 0) <= 160 * 1024, "LDS per CU");
+    static_assert(resident_lds_bytes(KCX, FIRST, LAST, WINDOW) + (WINDOW ? kWinTailWordsBytes : 0) <= 160 * 1024, "LDS per CU");
     EpilogueLds epi = epilogue_carve(lds_tail);          // LAST only
     if constexpr (WINDOW) epi.cwords = reinterpret_cast<int8_t*>(lds_tail + kEpilogueLdsBytes);
     const uint8_t* win_dl = reinterpret_cast<const uint8_t*>(epi.cwords) + 16 * kWinTailWordsStride;     // WINDOW only: the label matcher
@@ -89,7 +104,7 @@ gru_layer_resident(const GruLayerParams p) {
     float wgh[2][2][KCH];   // [tile][r|u][k-chunk]  A fragments of Wg rows I..I+H
     float wch[2][KCH];      // candidate, h-part
     float wcx[2][KCX];      // candidate, x-part
-    float wgx[KREG ? KREG : 1][4];   // upper layers: gate x-part k-chunks 0..KREG-1, {r0,u0,r1,u1} as in wlds
+    float wgx[KREG ? KREG : 1][4];   // gate x-part k-chunks 0..KREG-1, {r0,u0,r1,u1} as in wlds
     const f32x4* wh4 = reinterpret_cast<const f32x4*>(p.wh);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
@@ -112,13 +127,15 @@ gru_layer_resident(const GruLayerParams p) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int kc = 0; kc < KCX; ++kc) wcx[j][kc] = p.wx[(((2 * w + j) * 3 + 2) * KCX + kc) * 64 + lane];
+#pragma unroll
         for (int kc = 0; kc < KCX; ++kc) {
             f32x4 v;
             v.x = p.wx[((n0 * 3 + 0) * KCX + kc) * 64 + lane];
             v.y = p.wx[((n0 * 3 + 1) * KCX + kc) * 64 + lane];
             v.z = p.wx[((n1 * 3 + 0) * KCX + kc) * 64 + lane];
             v.w = p.wx[((n1 * 3 + 1) * KCX + kc) * 64 + lane];
-            wlds[(w * KL + kc) * 64 + lane] = v;       // (KREG == 0 in the first layer)
+            if (kc < KREG) { const int kr = kc < KREG ? kc : 0; wgx[kr][0] = v[0]; wgx[kr][1] = v[1]; wgx[kr][2] = v[2]; wgx[kr][3] = v[3]; }
+            else wlds[(w * KL + kc - KREG) * 64 + lane] = v;
         }
     } else {
         const f32x4* wx4 = reinterpret_cast<const f32x4*>(p.wx);
@@ -130,7 +147,6 @@ gru_layer_resident(const GruLayerParams p) {
 #pragma unroll
                 for (int e = 0; e < 4; ++e) wcx[j][4 * k4 + e] = vc[e];
             }
-        static_assert(KREG <= 4, "the register chunks come out of the first group of four");
 #pragma unroll
         for (int k4 = 0; k4 < KCX / 4; ++k4) {
             const f32x4 r0 = wx4[((n0 * 3 + 0) * (KCX / 4) + k4) * 64 + lane];
@@ -140,12 +156,13 @@ gru_layer_resident(const GruLayerParams p) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 const f32x4 v = {r0[e], u0[e], r1[e], u1[e]};
-                if (e < KREG && k4 == 0) { wgx[e][0] = v[0]; wgx[e][1] = v[1]; wgx[e][2] = v[2]; wgx[e][3] = v[3]; }
-                if (e >= KREG || k4 != 0) wlds[(w * KL + 4 * k4 + e - KREG) * 64 + lane] = v;
+                const int kc = 4 * k4 + e, kr = kc < KREG ? kc : 0;
+                if (kc < KREG) { wgx[kr][0] = v[0]; wgx[kr][1] = v[1]; wgx[kr][2] = v[2]; wgx[kr][3] = v[3]; }
+                else wlds[(w * KL + kc - KREG) * 64 + lane] = v;
             }
         }
     }
-    // park the recurrent fragments in AGPRs for the whole launch (192 of the 256)
+    // park the recurrent fragments in AGPRs for the whole launch (192 of the 256; the register chunks of the gate x-part behind them)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
 #pragma unroll
@@ -183,7 +200,7 @@ gru_layer_resident(const GruLayerParams p) {
     }
 
     // ---- per-group state: set by enter_group() -----------------------------------------------------
-    int len_s = T;
+    int len_s = T;                       // MASKED only
     f32x4 hreg[2];
     const float4* xl_src = nullptr;
     const float4* xprev = nullptr;
@@ -197,7 +214,7 @@ gru_layer_resident(const GruLayerParams p) {
         bvalid = b_raw < p.B;
         b = bvalid ? b_raw : p.B - 1;
         const bool do_reset = p.reset != nullptr && p.reset[b] != 0;
-        len_s = p.seq_len ? p.seq_len[b] - p.t_base : T;
+        if constexpr (MASKED) len_s = p.seq_len ? p.seq_len[b] - p.t_base : T;
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             const int n = 2 * w + j;
@@ -406,8 +423,8 @@ gru_layer_resident(const GruLayerParams p) {
         }
         resident_fence(acc_c[0], acc_c[1]);
         // ---- region B: tanh + state update as one VALU cluster
-        const unsigned live = t < len_s ? 0xffffffffu : 0u;   // dynamic_rnn copy-through past seq_len
-        f32x4 hout[2];
+        const unsigned live = !MASKED || t < len_s ? 0xffffffffu : 0u;   // MASKED: dynamic_rnn copy-through past seq_len
+        f32x4 hout[2];                                                    // MASKED && LAST: zero output rows past seq_len
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
 #pragma unroll
@@ -415,7 +432,14 @@ gru_layer_resident(const GruLayerParams p) {
                 const f32x2 c = tanh2((f32x2){acc_c[j][2 * h2], acc_c[j][2 * h2 + 1]});
                 const f32x2 uu = {u[j][2 * h2], u[j][2 * h2 + 1]};
                 const f32x2 hh = {hreg[j][2 * h2], hreg[j][2 * h2 + 1]};
-                const f32x2 hn = (1.0f - uu) * c + uu * hh;       // u*h + (1-u)*c
+                // u*h + (1-u)*c with (1-u)*c rounded on its own and u*h fused into the sum: written out, because left to
+                // contraction the compiler picks which product to fuse per instantiation, and the last bit follows its pick
+                const f32x2 hn = __builtin_elementwise_fma(uu, hh, (1.0f - uu) * c);
+                if constexpr (!MASKED) {
+                    hreg[j][2 * h2] = hn.x;
+                    hreg[j][2 * h2 + 1] = hn.y;
+                    continue;
+                }
                 hreg[j][2 * h2] = bitsel(live, hn.x, hh.x);
                 hreg[j][2 * h2 + 1] = bitsel(live, hn.y, hh.y);
                 if (LAST) {
@@ -453,7 +477,7 @@ gru_layer_resident(const GruLayerParams p) {
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) accf = mfma4(wfc[j][e], hout[j][e], accf);
+                for (int e = 0; e < 4; ++e) accf = mfma4(wfc[j][e], MASKED ? hout[j][e] : hreg[j][e], accf);
             if (g < 2) *reinterpret_cast<f32x4*>(epi.pstage + (w * 16 + s) * 8 + 4 * g) = accf;
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -529,6 +553,16 @@ gru_layer_resident(const GruLayerParams p) {
     }
 }
 
+// The kernels: a call without seq_len runs gru_layer_resident, one with it gru_layer_resident_masked (never the window tail).
+template <int KCX, bool FIRST, bool LAST, bool WINDOW = false>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
+gru_layer_resident(const GruLayerParams p) { gru_layer_resident_body<KCX, FIRST, LAST, false, WINDOW>(p); }
+template <int KCX, bool FIRST, bool LAST>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
+gru_layer_resident_masked(const GruLayerParams p) { gru_layer_resident_body<KCX, FIRST, LAST, true, false>(p); }
+template <int KCX, bool FIRST, bool LAST, bool MASKED>
+inline constexpr auto resident_kernel = MASKED ? &gru_layer_resident_masked<KCX, FIRST, LAST> : &gru_layer_resident<KCX, FIRST, LAST, false>;
+
 // ------------------------------------------------------------------------------------------------
 // launcher
 // ------------------------------------------------------------------------------------------------
@@ -548,16 +582,19 @@ bool gru_resident_takes_window(bool first, bool last) { return last && !first; }
 // the resident kernels loop over stream groups themselves: one workgroup per CU at most (each fills a CU's register file),
 // the weights staged once per workgroup however many groups it takes
 hipError_t launch_gru_layer_resident(const GruLayerParams& p, bool first, bool last, hipStream_t st) {
-    const size_t lds = resident_lds_bytes(p.KCX, first, last);
+    const bool window = p.win.tab != nullptr;
+    const size_t lds = resident_lds_bytes(p.KCX, first, last, window);
     const dim3 grid(persistent_grid(p.B));
-    if (p.win.tab != nullptr) {               // with the window tail: the last layer of a stack only
+    if (window) {                             // with the window tail: the last layer of a stack only
         if (!gru_resident_takes_window(first, last) || p.seq_len) return hipErrorInvalidValue;
         return launch_lds<gru_layer_resident<32, false, true, true>>(grid, dim3(256), lds + kWinTailWordsBytes, st, p);
     }
-    return with_bool(last, [&](auto la) {
-        if (!first) return launch_lds<gru_layer_resident<32, false, la()>>(grid, dim3(256), lds, st, p);
-        return with_int<8, 10, 12, 15, 16>(p.KCX, [&](auto kcx) {
-            return launch_lds<gru_layer_resident<kcx(), true, la()>>(grid, dim3(256), lds, st, p);
+    return with_bool(p.seq_len != nullptr, [&](auto ma) {
+        return with_bool(last, [&](auto la) {
+            if (!first) return launch_lds<resident_kernel<32, false, la(), ma()>>(grid, dim3(256), lds, st, p);
+            return with_int<8, 10, 12, 15, 16>(p.KCX, [&](auto kcx) {
+                return launch_lds<resident_kernel<kcx(), true, la(), ma()>>(grid, dim3(256), lds, st, p);
+            });
         });
     });
 }

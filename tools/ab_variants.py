@@ -31,15 +31,17 @@ for r in range(a.rounds):
             print(name, "FAILED rc=%d" % out.returncode, out.stderr[-500:])
             sys.exit(1)
         d = json.loads(lines[-1])
-        res[name].append((d["value"], d["roofline"]["per_layer_ms"]))
+        clock = (d.get("per_rank") or [{}])[0].get("clock_mhz_if_readable")      # a lower clock on a denser stream is a finding
+        res[name].append((d["value"], d["roofline"]["per_layer_ms"], clock))
+        print("round %d %s done" % (r + 1, name), file=sys.stderr, flush=True)
 lines = ["bench.py --steps %d --warmup %d %s, %d interleaved rounds" % (a.steps, a.warmup, a.args, a.rounds)]
 for name, _ in libs:
-    for v, pl in res[name]:
-        lines.append("%-16s %8.2f M frames/s   per-layer ms %s" % (name, v / 1e6, " ".join("%.4f" % x for x in pl)))
+    for v, pl, clock in res[name]:
+        lines.append("%-16s %8.2f M frames/s   per-layer ms %s   shader clock %s" % (name, v / 1e6, " ".join("%.4f" % x for x in pl), "unreadable" if clock is None else "%s MHz" % clock))
 median = lambda xs: sorted(xs)[len(xs) // 2] if len(xs) % 2 else sum(sorted(xs)[len(xs) // 2 - 1:len(xs) // 2 + 1]) / 2
 pairs = [(libs[0][0], n) for n, _ in libs[1:]] + [(libs[i][0], libs[i + 1][0]) for i in range(1, len(libs) - 1)]
 for ref, name in pairs:                    # every library against the first, and against the one listed before it
-    base, new = [v for v, _ in res[ref]], [v for v, _ in res[name]]
+    base, new = [r[0] for r in res[ref]], [r[0] for r in res[name]]
     if not base or not new:
         continue
     bar = 1 + 2 * (max(base) - min(base)) / median(base)
@@ -47,6 +49,12 @@ for ref, name in pairs:                    # every library against the first, an
     lines.append("%s vs %s: median ratio %.4f (bar %.4f), slowest %s run %.2f vs fastest %s run %.2f M frames/s -> %s"
                  % (name, ref, ratio, bar, name, min(new) / 1e6, ref, max(base) / 1e6,
                     "GAIN" if min(new) > max(base) and ratio > bar else "no gain under the rule"))
+    for l in range(len(res[ref][0][1])):   # the same rule per layer, on kernel ms (lower is better): median lower by more than the reference's max - min
+        b_ms, n_ms = [r[1][l] for r in res[ref]], [r[1][l] for r in res[name]]
+        diff, spread = median(n_ms) - median(b_ms), max(b_ms) - min(b_ms)
+        lines.append("    layer %d kernel ms: %s median %.4f (min %.4f max %.4f), %s median %.4f (min %.4f max %.4f): %+.4f ms against a spread of %.4f -> %s"
+                     % (l, ref, median(b_ms), min(b_ms), max(b_ms), name, median(n_ms), min(n_ms), max(n_ms), diff, spread,
+                        "lower" if diff < -spread else "higher" if diff > spread else "within the spread"))
 print("\n".join(lines))
 if a.out:
     with open(a.out, "a") as f:
