@@ -14,6 +14,8 @@
  *   kws_ctc_predict            utils/prediction.py:111 ctc_predict
  *   kws_vad                    utils/basic_vad.py:17 vad
  *   kws_stream_feed            one iteration of HotwordDetector.start's loop, detector.py:158-209, for B streams
+ *   kws_stream_create_heads    ... on a customised-keyword model: both dense layers decoded per chunk ("do softmax and decode
+ *                              respectively", README "Customize keyword"), the decisions ORed (server_demo.py:122-129)
  *   kws_octbit_matmul          REGISTER_OP("OctbitMatMul") octbit/octbit_ops_reg.cc:7-15,
  *                              OctbitMatMulOp::Compute octbit/octbit_mat_mul_op.cc:49-183
  *   kws_octbit_quantize        octize_weight_int8_signed octbit/octbit_graph.py:191-215
@@ -442,6 +444,42 @@ int kws_stream_recycle(kws_stream_handle h, const uint8_t* slots /*[B] device, n
  * lengths[b] <= fft_size - 1 samples at samples[b * (fft_size - 1) ...]; the rest of each row is unspecified.  Copies only (no
  * kernel), ordered like a feed; changes nothing. */
 int kws_stream_carry(kws_stream_handle h, float* samples /*[B, fft_size - 1] device*/, int32_t* lengths /*[B] device*/, void* stream);
+
+/* A stream manager on a customised-keyword model (kws_create_heads): BOTH class heads decoded per chunk, the stack run once.
+ * The reference README ("Customize keyword") keeps both dense layers on the frozen stack and says "do softmax and decode
+ * respectively"; server_demo.py:122-129 ORs the two decisions.  Per chunk and stream, detector.py:158-209 applied per head:
+ *   VAD      a silent chunk clears BOTH windows and resets the state (clear_before applies to both)
+ *   stack    once; every layer writes its rows to a seam, as kws_step_heads plans it
+ *   head k   its softmax rows go into window k, ctc_decode2 over the window at window k's threshold, hit_k = label_k occurs
+ *   coupling fired = hit_1 | hit_2: BOTH windows are cleared and the restart is requested, whichever head fired
+ *   output   hit[b] = hit_1 | hit_2 << 1 (0 nothing, 1 / 2 / 3 which head fired: non-zero is "detected")
+ * A chunk that completes no frame puts an empty entry into both windows; a skipped stream of the ragged feed gets no slot in
+ * either, hit 0, restart untouched.  Launches per chunk: front-end + L layers + 1 -- heads_window_kernel behind the stack does both
+ * projections, both softmaxes, both windows and the coupling (kws_last_launch names it in the top layer's slot, and with profiling
+ * on it is timed there); lock-step and ragged feeds alike.  It stages a 32-frame block of logits (32 KiB), both heads' frame words
+ * (2 * 16 * round_up(T, 16) bytes), two label tables and the two windows' rings (16 * (32 * max_chunks + 32) bytes each) in LDS:
+ * more than 160 KiB is refused with KWS_ERR_UNSUPPORTED and the byte counts.
+ *   kws_stream_create_heads   as kws_stream_create, with `window1` (C = num_classes, label1) and `window2` (C = num_classes2,
+ *                             label2): each window is bound to its own label.  Refuses (KWS_ERR_INVALID_ARGUMENT) a model without
+ *                             a second head, a window whose C or B does not fit its head, windows that hold fewer frames per
+ *                             chunk than max_chunk_samples gives, bad labels, and everything kws_stream_create refuses.  The
+ *                             handle is a stream handle: kws_stream_feed / _feed_ragged / _recycle (empties both windows of a
+ *                             recycled stream; two launches) / _carry / _reset / _destroy take it.  A feed stages nothing beyond
+ *                             what kws_reserve sizes for a heads step, and never allocates.  kws_stream_create on the same model
+ *                             handle stays what it is -- head 1 through the fused tail -- and both kinds of handle may coexist.
+ *   kws_step_heads_window     the same iteration from mel on: kws_step_heads' stack on `mel` [B,T,n_mel] (T >= 0) with `reset_mask`,
+ *                             then the one launch on the two windows (`clear_before` [B] or NULL).  softmax1 [B,T,num_classes] /
+ *                             softmax2 [B,T,num_classes2], each or NULL: bitwise the rows kws_step_heads writes for the same mel
+ *                             and state.  restart [B] or NULL.  The labels are bound to the windows as kws_window_step_incremental
+ *                             binds them; mel-fed and PCM-fed chunks may alternate on the same windows.
+ * Out of scope: f16x3 / bf16 / int8 heads and the cell wrappers (kws_create_heads refuses them), more than two heads, the MFCC and
+ * dataset front-ends. */
+int kws_stream_create_heads(kws_handle model, kws_frontend_handle frontend, kws_window_handle window1, kws_window_handle window2, int B,
+                            int max_chunk_samples, float vad_thres, const char* label1, const char* label2, float* state, uint8_t* restart,
+                            kws_stream_handle* out);
+int kws_step_heads_window(kws_handle model, const float* mel, const float* state_in, float* state_out, const uint8_t* reset_mask, int B, int T,
+                          kws_window_handle window1, kws_window_handle window2, const char* label1, const char* label2,
+                          const uint8_t* clear_before, float* softmax1, float* softmax2, int32_t* hit /*[B]*/, uint8_t* restart, void* stream);
 
 /* OctbitMatMul: out[A,N] = (sum_k u8(x)[a,k] * Wq[n,k] - signed*bias[n]) * scale_w * s_x.
  *   x [A,K] f32, Wq [N,K] s8 (pre-transposed), bias [N] f32, out [A,N] f32.  K % 64 == 0, scale_w > 0.

@@ -129,6 +129,10 @@ struct HeadsArgs {
     float* nn_outputs = nullptr;
     kws_head_io head[2] = {};
     bool on[2] = {false, false};
+    // a two-head stream manager's iteration (kws_step_heads_window, kws_stream_feed on a kws_stream_create_heads handle): instead of
+    // dense_heads_kernel, heads_window_kernel follows the top layer -- these parameters, with the seam and the heads' weights filled
+    // in by the launch; with T == 0 it is the step's only launch besides the state pass
+    const kws::HeadsWindowParams* window = nullptr;
 };
 // The arguments of one kws_step (include/kws_amd.h), and what the stream manager adds to them
 struct StepArgs {
@@ -162,6 +166,26 @@ constexpr size_t kWindowIncLdsMax = 160 * 1024;
 int window_bind_label(kws_window* w, const char* label);
 // ... the incremental window as kernel arguments: of window_inc_kernel, or of the tail of a GRU launch (StepArgs::wt)
 kws::WindowTail window_tail_params(kws_window* w, const uint8_t* clear_before, int32_t* hit, uint8_t* restart);
+
+// api_step.hip: one iteration of a two-head manager from mel on -- the stack planned as a heads step, then heads_window_kernel on the
+// two windows (labels bound by the caller).  frames / skip: the ragged feed's per-stream frame counts and skip flags, or null.
+struct HeadsWindowCall {
+    const float* mel = nullptr;
+    const float* state_in = nullptr;
+    float* state_out = nullptr;
+    const uint8_t *reset_mask = nullptr, *clear_before = nullptr;
+    const int32_t* frames = nullptr;
+    const uint8_t* skip = nullptr;
+    float *softmax1 = nullptr, *softmax2 = nullptr;
+    int32_t* hit = nullptr;
+    uint8_t* restart = nullptr;
+    int B = 0, T = 0;
+    hipStream_t stream = nullptr;
+    bool locked = false;
+};
+int heads_window_step(kws_handle h, kws_window* w1, kws_window* w2, const HeadsWindowCall& c);
+// ... the refusals a pair of windows shares between kws_stream_create_heads and kws_step_heads_window (class counts, batch, LDS)
+int heads_window_check(const kws_model* h, const kws_window* w1, const kws_window* w2, int B, int T);
 
 // api_frontend.hip: the 400-point FFT kernel takes a launch of B x T frames (else the dense-DFT kernel, which has magnitude mel only)
 bool frontend_takes_fft400(const kws_frontend* h, int B, int T);
@@ -262,7 +286,8 @@ struct kws_model {
         }
         std::string out = t.family == kBf16Stack ? std::string(kws::gru_stack_bf16_kernel_name(pk.bf_kx0, cfg.num_layers)) : std::string(nm);
         if (t.window) out += " + window tail";          // the stream manager's decode-window step rode in this launch
-        if (t.heads) out += " + dense_heads_kernel<" + std::to_string(cfg.hidden / 16) + ">";      // timed in the top layer's slot
+        if (t.heads == 1) out += " + dense_heads_kernel<" + std::to_string(cfg.hidden / 16) + ">";      // timed in the top layer's slot
+        if (t.heads == 2) out += " + heads_window_kernel<" + std::to_string(cfg.hidden / 16) + ">";     // (a two-head stream manager's iteration)
         return out;
     }
 };
@@ -287,10 +312,12 @@ struct kws_stream {
     kws_model* model = nullptr;
     kws_frontend* fe = nullptr;
     kws_window* win = nullptr;
-    unsigned long long model_serial = 0, fe_serial = 0, win_serial = 0;   // live_serial() of the three at kws_stream_create
+    kws_window* win2 = nullptr;      // kws_stream_create_heads: head 2's window (null: a plain manager, head 1 through the fused tail)
+    unsigned long long model_serial = 0, fe_serial = 0, win_serial = 0, win2_serial = 0;   // live_serial() of the borrowed handles at create
     int B = 0, max_chunk = 0, tmax = 0, n_carry = 0, cur = 0;
     float vad_thres = 0.f;
     char label[17] = {0};
+    char label2[17] = {0};           // win2's
     float* state = nullptr;          // caller-owned [L,B,H]
     uint8_t* restart = nullptr;      // caller-owned [B]
     float* carry[2] = {nullptr, nullptr};   // [B, fft - 1] each: the carried samples ping-pong (the only device memory a manager owns)
@@ -304,7 +331,7 @@ struct kws_stream {
     size_t stage_bytes = 0;
     float* pcm_f32 = nullptr;        // [B, max_chunk]  int16 input widened here (front-ends other than the 400-point FFT, sub-frame chunks)
     float* mel = nullptr;            // [B, tmax, n_mel]
-    float* softmax = nullptr;        // [B, tmax, C]
+    float* softmax = nullptr;        // [B, tmax, C]; not carved for a two-head manager (its words never leave the kernel)
     uint8_t* silent = nullptr;       // [B]
     uint8_t* reset = nullptr;        // [B]
     int32_t* frames = nullptr;       // [B] int32  frames of each stream's chunk (ragged feed)

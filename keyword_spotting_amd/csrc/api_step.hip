@@ -375,6 +375,21 @@ void set_dense_heads(kws::DenseHeadsParams& dp, const kws_model* h, const StepAr
     dp.B = a.B; dp.T = a.T;
 }
 
+// heads_window_kernel behind the top layer of a two-head manager's iteration: the caller's windows and outputs, this handle's heads
+void set_heads_window(kws::HeadsWindowParams& hp, const kws_model* h, const StepArgs& a) {
+    const kws_config& c = h->cfg;
+    hp = *a.heads->window;
+    hp.h_top = a.T > 0 ? h->scratch[(c.num_layers - 1) % h->nscratch] : nullptr;
+    const size_t wfc[2] = {h->pk.wfc_off, h->pk.wfc2_off}, bfc[2] = {h->pk.bfc_off, h->pk.bfc2_off};
+    const int C[2] = {c.num_classes, h->num_classes2};
+    for (int i = 0; i < 2; ++i) {
+        hp.head[i].wfc = h->d_weights + wfc[i]; hp.head[i].bfc = h->d_weights + bfc[i];
+        hp.head[i].C = C[i];
+    }
+    hp.value_clip = c.value_clip; hp.use_relu = c.use_relu;
+    hp.B = a.B; hp.T = a.T;
+}
+
 // ---- the launches ----------------------------------------------------------------------------------------------------
 // The launch of profiling slot l as the plan tagged it, on `st`.  step_overlapped passes the time block [t0, t0 + frames) of the
 // call: seams double-buffered per block parity, and behind block 0 the state is the one the block before left in state_out.
@@ -456,6 +471,11 @@ int launch_slot(const kws_model* h, const StepArgs& a, const StepPlan& plan, int
         default: return KWS_OK;      // an empty slot: its layer runs inside another slot's launch
     }
     if (e != hipSuccess) return hip_fail(e, what);
+    if (t.heads == 2) {      // both heads and both windows of a two-head manager, inside the top layer's slot
+        kws::HeadsWindowParams hp;
+        set_heads_window(hp, h, a);
+        return hip_done(kws::launch_heads_window(hp, H, st), "launch heads_window");
+    }
     if (t.heads) {      // the class heads, inside the top layer's slot
         kws::DenseHeadsParams dp;
         set_dense_heads(dp, h, a);
@@ -525,6 +545,15 @@ int step_body(kws_handle h, const StepArgs& a) {
     if (T == 0) {
         // dynamic_rnn over zero frames hands the initial state back -- and clean_state() (detector.py:313-316) has already
         // zeroed it for the streams the mask names.  No GRU kernel runs: h->launch_tag stays what the step before left.
+        if (a.heads && a.heads->window) {   // a two-head manager: the state pass, then an empty entry into both windows
+            if (a.reset_mask)
+                KWS_TRY(hip_done(kws::launch_state_passthrough(a.state_in, a.state_out, a.reset_mask, nullptr, L, B, H, st), "launch state_passthrough"));
+            else if (a.state_out != a.state_in)
+                KWS_HIP(hipMemcpyAsync(a.state_out, a.state_in, (size_t)L * B * H * sizeof(float), hipMemcpyDeviceToDevice, st));
+            kws::HeadsWindowParams hp;
+            set_heads_window(hp, h, a);
+            return hip_done(kws::launch_heads_window(hp, H, st), "launch heads_window");
+        }
         if (a.reset_mask && a.heads) {      // both heads' prev_word; the second pass copies state_out onto itself
             KWS_TRY(hip_done(kws::launch_state_passthrough(a.state_in, a.state_out, a.reset_mask, a.heads->head[0].prev_word, L, B, H, st),
                              "launch state_passthrough"));
@@ -538,7 +567,8 @@ int step_body(kws_handle h, const StepArgs& a) {
         return KWS_OK;
     }
     StepPlan plan = plan_step(h, B, T, h->profiling, a.wt != nullptr, a.heads != nullptr);
-    if (a.heads && !a.heads->on[0] && !a.heads->on[1] && !a.heads->nn_outputs) plan.tag[L - 1].heads = 0;      // nothing behind the stack (launch_slot)
+    if (a.heads && a.heads->window) plan.tag[L - 1].heads = 2;      // heads_window_kernel in dense_heads_kernel's place (launch_slot)
+    else if (a.heads && !a.heads->on[0] && !a.heads->on[1] && !a.heads->nn_outputs) plan.tag[L - 1].heads = 0;      // nothing behind the stack (launch_slot)
     if (!a.mel) return fail(KWS_ERR_INVALID_ARGUMENT, "mel is null");
     // the streaming kernels address a group's seam (T x H/16 KiB) through buffer instructions with 32-bit offsets
     if (plan.streaming && (long long)T * (H / 16) >= (1LL << 21))
@@ -615,7 +645,67 @@ int kws_host::step_impl(kws_handle h, const StepArgs& a) {
     return rc != KWS_OK ? rc : rl;
 }
 
+int kws_host::heads_window_check(const kws_model* h, const kws_window* w1, const kws_window* w2, int B, int T) {
+    if (h->num_classes2 <= 0)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "a two-head stream manager needs a model handle with a second class head (kws_create_heads)");
+    if (w1 == w2) return fail(KWS_ERR_INVALID_ARGUMENT, "window1 and window2 are the same handle: each head queues its own chunks");
+    const kws_window* w[2] = {w1, w2};
+    const int C[2] = {h->cfg.num_classes, h->num_classes2};
+    for (int i = 0; i < 2; ++i) {
+        if (w[i]->C != C[i] || w[i]->B != B)
+            return fail(KWS_ERR_INVALID_ARGUMENT, "window%d was created for B=%d C=%d, head %d needs B=%d C=%d", i + 1, w[i]->B, w[i]->C, i + 1, B, C[i]);
+        if (T > w[i]->tmax)
+            return fail(KWS_ERR_INVALID_ARGUMENT, "chunks of up to %d frames, window%d holds %d per chunk", T, i + 1, w[i]->tmax);
+    }
+    const size_t lds = kws::heads_window_lds_bytes(T, w1->nq, w2->nq);
+    if (lds > kWindowIncLdsMax)
+        return fail(KWS_ERR_UNSUPPORTED, "chunks of up to %d frames with windows of %d and %d chunks need %zu bytes of LDS in the two-head window step "
+                    "(logits %zu, frame words %zu, label tables 512, rings %zu + %zu; limit %zu): use shorter chunks", T, w1->nq, w2->nq, lds,
+                    kws::kHeadsWindowLogitsBytes, (size_t)2 * 16 * kws::heads_window_stride(T), kws::window_tail_scratch_bytes(w1->nq),
+                    kws::window_tail_scratch_bytes(w2->nq), kWindowIncLdsMax);
+    return KWS_OK;
+}
+
+int kws_host::heads_window_step(kws_handle h, kws_window* w1, kws_window* w2, const HeadsWindowCall& c) {
+    kws::HeadsWindowParams hp = {};
+    // the tails write hit of their own window where the coupling overwrites it, and leave restart to the coupling
+    hp.win[0] = window_tail_params(w1, c.clear_before, c.hit, nullptr);
+    hp.win[1] = window_tail_params(w2, c.clear_before, c.hit, nullptr);
+    hp.head[0].softmax = c.softmax1; hp.head[0].decode_thres = w1->thres;
+    hp.head[1].softmax = c.softmax2; hp.head[1].decode_thres = w2->thres;
+    hp.hit = c.hit; hp.restart = c.restart; hp.frames = c.frames; hp.skip = c.skip;
+    HeadsArgs ha;
+    ha.window = &hp;
+    StepArgs a;
+    a.mel = c.mel; a.state_in = c.state_in; a.state_out = c.state_out; a.seq_len = c.frames; a.reset_mask = c.reset_mask;
+    a.B = c.B; a.T = c.T; a.stream = c.stream; a.heads = &ha; a.locked = c.locked;
+    return step_impl(h, a);
+}
+
 extern "C" {
+
+int kws_step_heads_window(kws_handle h, const float* mel, const float* state_in, float* state_out, const uint8_t* reset_mask, int B, int T,
+                          kws_window_handle window1, kws_window_handle window2, const char* label1, const char* label2,
+                          const uint8_t* clear_before, float* softmax1, float* softmax2, int32_t* hit, uint8_t* restart, void* stream) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    if (!window1 || !window2 || !label1 || !label2 || !hit || !state_in || !state_out || (!mel && T > 0))
+        return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
+    if (B < 1 || T < 0) return fail(KWS_ERR_INVALID_ARGUMENT, "bad shape B=%d T=%d", B, T);
+    if (!live_serial(h) || !live_serial(window1) || !live_serial(window2))
+        return fail(KWS_ERR_INVALID_ARGUMENT, "model or window handle is not alive (destroyed, or not a handle)");
+    KWS_TRY(heads_window_check(h, window1, window2, B, T));
+    // rows of an even class count leave as float2 (store_row)
+    if ((h->cfg.num_classes % 2 == 0 && (reinterpret_cast<uintptr_t>(softmax1) & 7) != 0) ||
+        (h->num_classes2 % 2 == 0 && (reinterpret_cast<uintptr_t>(softmax2) & 7) != 0))
+        return fail(KWS_ERR_INVALID_ARGUMENT, "softmax1 / softmax2 must be 8-byte aligned");
+    KWS_TRY(window_bind_label(window1, label1));
+    KWS_TRY(window_bind_label(window2, label2));
+    HeadsWindowCall c;
+    c.mel = mel; c.state_in = state_in; c.state_out = state_out; c.reset_mask = reset_mask; c.clear_before = clear_before;
+    c.softmax1 = softmax1; c.softmax2 = softmax2; c.hit = hit; c.restart = restart; c.B = B; c.T = T;
+    c.stream = static_cast<hipStream_t>(stream);
+    return heads_window_step(h, window1, window2, c);
+}
 
 int kws_step(kws_handle h, const float* mel, const float* state_in, float* logits, float* softmax,
              float* state_out, const int32_t* seq_len, const uint8_t* reset_mask, int8_t* tokens,

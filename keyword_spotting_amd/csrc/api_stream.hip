@@ -1,4 +1,8 @@
 // C ABI of libkws_amd.so (include/kws_amd.h): the stream manager -- gate, front-end, GRU step and decode window of one chunk per call.
+// A manager created by kws_stream_create_heads (kws_stream::win2 set) decodes BOTH heads of a customised-keyword model per chunk: the
+// same gate and front-end, the stack planned as a heads step (every layer to a seam), then heads_window_kernel -- both heads' rows,
+// both windows and the coupled clear + restart in one launch (heads_window.hip) -- in lock-step and ragged feeds alike; recycling
+// empties both windows.  Every other entry point takes such a handle unchanged.
 #include <new>
 
 #include "api_internal.h"
@@ -30,6 +34,18 @@ int stream_feed_locked(kws_stream_handle h, const void* pcm, int n, int pcm_int1
         KWS_TRY(hip_done(kws::launch_vad_gate(pcm, pcm_int16, B, n, h->vad_thres, h->pcm_f32, h->restart, h->silent, h->reset, carry,
                                               h->n_carry, next, keep, st), "launch vad_gate"));
         if (T) KWS_TRY(kws_frontend_run_carry(h->fe, carry, h->n_carry, chunk, n, B, h->mel, nullptr, 0, st));
+    }
+    if (h->win2) {
+        // a two-head manager: front-end + L layers + 1 launches -- the stack once, every layer to a seam as a heads step plans it, then
+        // heads_window_kernel: both heads' rows -> words -> their own windows, and the coupled clear + restart (heads_window.hip)
+        KWS_TRY(window_bind_label(h->win, h->label));
+        KWS_TRY(window_bind_label(h->win2, h->label2));
+        HeadsWindowCall c;
+        c.mel = T ? h->mel : nullptr; c.state_in = h->state; c.state_out = h->state; c.reset_mask = h->reset; c.clear_before = h->silent;
+        c.hit = hit; c.restart = h->restart; c.B = B; c.T = T; c.stream = st; c.locked = true;
+        KWS_TRY(heads_window_step(h->model, h->win, h->win2, c));
+        h->n_carry = keep; h->cur ^= 1;
+        return KWS_OK;
     }
     // the GRU step of the chunk: the manager's state in place, reset where the gate found silence
     StepArgs step;
@@ -85,6 +101,15 @@ int stream_feed_ragged_locked(kws_stream_handle h, const void* pcm, int n_max, c
     p.mel = h->mel; p.n_samples = p.n_carry + n_max;
     KWS_TRY(hip_done(kws::launch_mel_fft400(p, B, st), "launch mel_fft400 (ragged)"));
     h->ragged = true; h->n_carry = 0; h->cur ^= 1;          // the samples and lengths are in the other buffer now
+    if (h->win2) {          // a two-head manager: the layers with seq_len = frames, then heads_window_kernel<.., true> over each stream's own frames
+        KWS_TRY(window_bind_label(h->win, h->label));
+        KWS_TRY(window_bind_label(h->win2, h->label2));
+        HeadsWindowCall c;
+        c.mel = h->mel; c.state_in = h->state; c.state_out = h->state; c.reset_mask = h->reset; c.clear_before = h->silent;
+        c.frames = h->frames; c.skip = h->skip;
+        c.hit = hit; c.restart = h->restart; c.B = B; c.T = T; c.stream = st; c.locked = true;
+        return heads_window_step(h->model, h->win, h->win2, c);
+    }
     StepArgs step;
     step.mel = h->mel; step.softmax = h->softmax;
     step.state_in = h->state; step.state_out = h->state; step.reset_mask = h->reset; step.seq_len = h->frames;
@@ -101,7 +126,8 @@ int stream_feed_ragged_locked(kws_stream_handle h, const void* pcm, int n_max, c
 
 // The checks every stream-handle call shares: the borrowed handles are alive; the per-stream paths need the FFT front-end.
 int stream_check(kws_stream_handle h, bool ragged_call) {
-    if (live_serial(h->model) != h->model_serial || live_serial(h->fe) != h->fe_serial || live_serial(h->win) != h->win_serial)
+    if (live_serial(h->model) != h->model_serial || live_serial(h->fe) != h->fe_serial || live_serial(h->win) != h->win_serial ||
+        (h->win2 && live_serial(h->win2) != h->win2_serial))
         return fail(KWS_ERR_INVALID_ARGUMENT, "the model, front-end or window this stream was created on has been destroyed");
     if (ragged_call && !h->fe->use_fft) return frontend_needs_fft400(h->fe, "per-stream chunk lengths");
     if (ragged_call && !frontend_takes_fft400(h->fe, h->B, h->tmax))
@@ -122,7 +148,7 @@ size_t stream_carve(kws_stream* s, uintptr_t base) {
     const bool fused_gate = frontend_takes_fft400(s->fe, s->B, (int)tm);       // then for every chunk with a frame
     take(s->pcm_f32, B * (fused_gate ? std::min(s->max_chunk, s->fe->cfg.fft_size - 1) : s->max_chunk));
     take(s->mel, B * tm * s->model->cfg.n_mel);
-    take(s->softmax, B * tm * s->model->cfg.num_classes);
+    take(s->softmax, s->win2 ? 0 : B * tm * s->model->cfg.num_classes);
     take(s->silent, B);
     take(s->reset, B);
     take(s->frames, B);
@@ -148,25 +174,30 @@ int with_model_held(kws_stream_handle h, void* stream, const char* what, F&& bod
     return rc != KWS_OK ? rc : rl;
 }
 
-}  // namespace
-
-extern "C" {
-
-int kws_stream_create(kws_handle model, kws_frontend_handle frontend, kws_window_handle window, int B, int max_chunk_samples,
-                      float vad_thres, const char* label, float* state, uint8_t* restart, kws_stream_handle* out) {
+// kws_stream_create (window2 == null) and kws_stream_create_heads (`who` names the entry point in the refusals)
+int stream_create_impl(const char* who, kws_handle model, kws_frontend_handle frontend, kws_window_handle window, kws_window_handle window2,
+                       int B, int max_chunk_samples, float vad_thres, const char* label, const char* label2, float* state, uint8_t* restart,
+                       kws_stream_handle* out) {
     if (!out) return fail(KWS_ERR_INVALID_ARGUMENT, "out handle pointer is null");
     *out = nullptr;
     if (!model || !frontend || !window || !state || !restart || !label) return fail(KWS_ERR_INVALID_ARGUMENT, "null argument");
     const unsigned long long ms = live_serial(model), fs = live_serial(frontend), ws = live_serial(window);
-    if (!ms || !fs || !ws) return fail(KWS_ERR_INVALID_ARGUMENT, "model, front-end or window handle is not alive (destroyed, or not a handle)");
-    if (frontend->framing != KWS_FRAMES_DEPLOY) return frontend_needs_deploy_frames("kws_stream_create");
+    const unsigned long long ws2 = window2 ? live_serial(window2) : 0;
+    if (!ms || !fs || !ws || (window2 && !ws2))
+        return fail(KWS_ERR_INVALID_ARGUMENT, "model, front-end or window handle is not alive (destroyed, or not a handle)");
+    if (window2 && model->num_classes2 <= 0)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "%s needs a model handle with a second class head (kws_create_heads)", who);
+    if (frontend->framing != KWS_FRAMES_DEPLOY) return frontend_needs_deploy_frames(who);
     if (!frontend->plain())
-        return fail(KWS_ERR_UNSUPPORTED, "kws_stream_create takes a magnitude-mel front-end only: this one has %s (the reference's streaming "
-                    "detector has no MFCC branch)", frontend->kind == KWS_FEAT_MFCC ? "kind=KWS_FEAT_MFCC" : "power=2");
+        return fail(KWS_ERR_UNSUPPORTED, "%s takes a magnitude-mel front-end only: this one has %s (the reference's streaming "
+                    "detector has no MFCC branch)", who, frontend->kind == KWS_FEAT_MFCC ? "kind=KWS_FEAT_MFCC" : "power=2");
     if (B < 1 || max_chunk_samples < 1) return fail(KWS_ERR_INVALID_ARGUMENT, "bad stream shape B=%d max_chunk_samples=%d", B, max_chunk_samples);
     const int n = (int)strlen(label);
     if (n > 15) return fail(KWS_ERR_INVALID_ARGUMENT, "label longer than 15 digits (the incremental window's matcher has 16 states)");
     KWS_TRY(label_digits(label, n, nullptr));
+    const int n2 = window2 ? (int)strlen(label2) : 0;
+    if (n2 > 15) return fail(KWS_ERR_INVALID_ARGUMENT, "label2 longer than 15 digits (the incremental window's matcher has 16 states)");
+    if (window2) KWS_TRY(label_digits(label2, n2, nullptr));
     if (frontend->cfg.n_mel != model->cfg.n_mel)
         return fail(KWS_ERR_INVALID_ARGUMENT, "front-end produces %d mel bins, the model takes %d", frontend->cfg.n_mel, model->cfg.n_mel);
     if (window->B != B || window->C != model->cfg.num_classes)
@@ -177,12 +208,15 @@ int kws_stream_create(kws_handle model, kws_frontend_handle frontend, kws_window
     if (tmax > window->tmax)
         return fail(KWS_ERR_INVALID_ARGUMENT, "chunks of %d samples give up to %d frames, the window holds %d per chunk", max_chunk_samples,
                     tmax, window->tmax);
-    if (window_inc_lds_bytes(tmax, window->nq) > kWindowIncLdsMax)
+    if (window2) KWS_TRY(heads_window_check(model, window, window2, B, tmax));      // both windows' class counts, batch, frames; the LDS of the launch
+    if (!window2 && window_inc_lds_bytes(tmax, window->nq) > kWindowIncLdsMax)
         return fail(KWS_ERR_UNSUPPORTED, "chunks of up to %d frames with a %d-chunk window need %zu bytes of LDS in the incremental window step "
                     "(limit %zu): use shorter chunks", tmax, window->nq, window_inc_lds_bytes(tmax, window->nq), kWindowIncLdsMax);
     kws_stream* s = new (std::nothrow) kws_stream();
     if (!s) return fail(KWS_ERR_OUT_OF_MEMORY, "host allocation failed");
     s->model_serial = ms; s->fe_serial = fs; s->win_serial = ws;
+    s->win2 = window2; s->win2_serial = ws2;
+    if (window2) memcpy(s->label2, label2, n2);
     s->model = model; s->fe = frontend; s->win = window; s->B = B; s->max_chunk = max_chunk_samples; s->tmax = tmax;
     s->vad_thres = vad_thres; s->state = state; s->restart = restart;
     memcpy(s->label, label, n);
@@ -208,9 +242,29 @@ int kws_stream_create(kws_handle model, kws_frontend_handle frontend, kws_window
     }
     if (rc == KWS_OK) rc = kws_reserve(model, B, tmax);            // the GRU step of a chunk never allocates afterwards
     if (rc == KWS_OK) rc = window_bind_label(window, s->label);      // the window's summaries are built for this label
+    if (rc == KWS_OK && window2) rc = window_bind_label(window2, s->label2);      // ... each window for its own
     if (rc != KWS_OK) { kws_stream_destroy(s); return rc; }
     *out = s;
     return KWS_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int kws_stream_create(kws_handle model, kws_frontend_handle frontend, kws_window_handle window, int B, int max_chunk_samples,
+                      float vad_thres, const char* label, float* state, uint8_t* restart, kws_stream_handle* out) {
+    return stream_create_impl("kws_stream_create", model, frontend, window, nullptr, B, max_chunk_samples, vad_thres, label, nullptr, state,
+                              restart, out);
+}
+
+int kws_stream_create_heads(kws_handle model, kws_frontend_handle frontend, kws_window_handle window1, kws_window_handle window2, int B,
+                            int max_chunk_samples, float vad_thres, const char* label1, const char* label2, float* state, uint8_t* restart,
+                            kws_stream_handle* out) {
+    if (out) *out = nullptr;
+    if (!window2 || !label2) return fail(KWS_ERR_INVALID_ARGUMENT, "null argument");
+    return stream_create_impl("kws_stream_create_heads", model, frontend, window1, window2, B, max_chunk_samples, vad_thres, label1, label2,
+                              state, restart, out);
 }
 
 int kws_stream_destroy(kws_stream_handle h) {
@@ -270,6 +324,8 @@ int kws_stream_recycle(kws_stream_handle h, const uint8_t* slots, void* stream) 
         }
         KWS_TRY(hip_done(kws::launch_stream_recycle(p, st), "launch stream_recycle"));
         if (!h->ragged) { h->ragged = true; h->n_carry = 0; h->cur ^= 1; }
+        if (h->win2)      // a two-head manager: head 2's window of the same streams (two stores per recycled stream)
+            KWS_TRY(hip_done(kws::launch_window_reset_masked(slots, h->B, h->win2->inc_head, h->win2->inc_count, st), "launch window_reset (window 2)"));
         return KWS_OK;
     });
 }

@@ -18,7 +18,7 @@
 // stream ahead of the launch (DenseHead::prev_in, as the int8 path's oct_prev), and only that copy is read here.  A block with
 // t0 > 0 gets the word of frame t0 - 1 by projecting that frame itself in slot 0 -- the same loop body, so the same
 // instruction sequence and the same bits as the block that owns the frame.
-#include "gru_device.h"
+#include "dense_heads_device.h"
 #include "launch.h"
 
 namespace kws {
@@ -26,51 +26,6 @@ namespace kws {
 namespace {
 
 constexpr int kHeadSlots = kHeadFrames + 1;        // slot f <-> frame t0 - 1 + f; slot 0 is the halo
-
-// relu / clip, softmax and the ctc_decode2 frame rule of one row: the arithmetic of epilogue_flush (gru_device.h)
-__device__ __forceinline__ int head_row(float (&lg)[kMaxClasses], float (&pr)[kMaxClasses], int C, int use_relu, float value_clip, float thres) {
-    if (use_relu) {
-#pragma unroll
-        for (int c = 0; c < kMaxClasses; ++c) {
-            lg[c] = fmaxf(lg[c], 0.f);
-            if (value_clip > 0.f) lg[c] = fminf(lg[c], 20.f);
-        }
-    }
-    float m = lg[0];
-#pragma unroll
-    for (int c = 1; c < kMaxClasses; ++c) m = (c < C) ? fmaxf(m, lg[c]) : m;
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < kMaxClasses; ++c) {
-        pr[c] = (c < C) ? __expf(lg[c] - m) : 0.f;
-        sum += pr[c];
-    }
-    const float inv = __builtin_amdgcn_rcpf(sum);
-#pragma unroll
-    for (int c = 0; c < kMaxClasses; ++c) pr[c] *= inv;
-    // classes 1..C-2 (utils/prediction.py:67,74-75): first maximum, strict >
-    int word = -1;
-    float best = -1.f;
-#pragma unroll
-    for (int c = 1; c < kMaxClasses - 1; ++c) {
-        if (c < C - 1 && pr[c] > best) { best = pr[c]; word = c - 1; }
-    }
-    return best > thres ? word : -1;
-}
-
-// a row of C floats; rows of an even C are 8-byte aligned (the outputs are, as kws_step's)
-__device__ __forceinline__ void store_row(float* dst, const float (&v)[kMaxClasses], int C) {
-    if ((C & 1) == 0) {
-        float2* o = reinterpret_cast<float2*>(dst);
-#pragma unroll
-        for (int c = 0; c < kMaxClasses / 2; ++c)
-            if (2 * c < C) o[c] = make_float2(v[2 * c], v[2 * c + 1]);
-    } else {
-#pragma unroll
-        for (int c = 0; c < kMaxClasses; ++c)
-            if (c < C) dst[c] = v[c];
-    }
-}
 
 }  // namespace
 
@@ -119,15 +74,7 @@ __global__ void __launch_bounds__(256) dense_heads_kernel(const DenseHeadsParams
 #pragma unroll
         for (int hd = 0; hd < 2; ++hd) {
             if (p.head[hd].C == 0) continue;
-            // The summation order of the fused epilogue (gru_resident.hip, gru_kernels.hip): four partial sums over a quarter of the
-            // units each -- there one per wave, the first one starting from bfc, the others from zero -- folded ((0 + 1) + 2) + 3
-            // (epilogue_fold), so that head 1 here and through kws_step is the same sum of the same products.
-            f32x4 part[4] = {bias4[hd], splat4(0.f), splat4(0.f), splat4(0.f)};
-#pragma unroll
-            for (int n = 0; n < NT; ++n)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) part[n / (NT / 4)] = mfma4(wa[hd][4 * n + e], v[n][e], part[n / (NT / 4)]);
-            const f32x4 acc = ((part[0] + part[1]) + part[2]) + part[3];
+            KWS_HEAD_PROJECT(acc, NT, wa[hd], bias4[hd], v);      // dense_heads_device.h: the fused epilogue's summation order
             if (g < 2) *reinterpret_cast<f32x4*>(&lgs[hd][s][f][4 * g]) = acc;
         }
     }

@@ -248,6 +248,37 @@ constexpr int kHeadFrames = 32;          // frames per workgroup
 constexpr int kHeadsMaxFrames = 65535 * kHeadFrames;      // grid.y
 hipError_t launch_dense_heads(const DenseHeadsParams& p, int hidden, hipStream_t st);
 
+// Both class heads AND both decode windows of a two-head stream manager (heads_window.hip): one launch behind a stack planned as
+// a heads step, one workgroup per 16-stream group over the whole chunk -- each head's rows -> frame words -> that head's
+// incremental window, then the coupling: a hit of either head clears both windows and requests the restart.
+struct HeadsWindowHead {
+    const float* wfc;       // as DenseHead
+    const float* bfc;
+    float* softmax;         // [B,T,C] or null: bitwise dense_heads_kernel's rows
+    float decode_thres;     // the window's threshold
+    int C;
+};
+struct HeadsWindowParams {
+    const float4* h_top;    // top layer output, xl layout [G][T][H/16][64]; unused when T == 0
+    HeadsWindowHead head[2];
+    WindowTail win[2];      // clear_before is the same array in both; hit / restart of the tails are overwritten by the coupling
+    int32_t* hit;           // [B] hit_1 | hit_2 << 1
+    uint8_t* restart;       // [B] or null
+    // ragged chunks (kws_stream_feed_ragged): stream b's chunk is its first frames[b] <= T rows; skip[b] != 0: no slot in either
+    // window, no clear, hit 0, restart untouched.  frames == null: every stream has T frames.
+    const int32_t* frames;
+    const uint8_t* skip;
+    float value_clip;
+    int use_relu, B, T;
+};
+constexpr size_t kHeadsWindowLogitsBytes = (size_t)2 * 16 * kHeadFrames * 8 * sizeof(float);      // [head][stream][frame][8]
+// LDS of the launch: logits of a frame block, both heads' frame words [2][16][round_up(T, 16)], two label matchers, two rings
+__host__ __device__ inline int heads_window_stride(int T) { return T > 0 ? (T + 15) & ~15 : 16; }
+__host__ __device__ inline size_t heads_window_lds_bytes(int T, int nq1, int nq2) {
+    return kHeadsWindowLogitsBytes + (size_t)2 * 16 * heads_window_stride(T) + 512 + window_tail_scratch_bytes(nq1) + window_tail_scratch_bytes(nq2);
+}
+hipError_t launch_heads_window(const HeadsWindowParams& p, int hidden, hipStream_t st);
+
 // decode window of the stream manager (stream_kernels.hip)
 struct WindowParams {
     int8_t* words;            // [B][nq][tmax] per-frame ctc_decode2 word (-1 none); tmax % 16 == 0
@@ -278,6 +309,8 @@ struct WindowIncParams {
 };
 hipError_t launch_window_inc(const WindowIncParams& p, hipStream_t st);
 hipError_t launch_window_reset(int B, int* head, int* count, hipStream_t st);
+// ... of the streams with slots[b] != 0 only (kws_stream_recycle on a two-head manager: head 2's window)
+hipError_t launch_window_reset_masked(const uint8_t* slots, int B, int* head, int* count, hipStream_t st);
 // kws_stream_recycle: the streams with slots[b] != 0 become fresh streams -- state rows [L][b][H] zero, restart 0, window empty
 // (head = count = 0), carry length 0.  carry_out != null: the handle leaves the lock-step carry layout ([B][n_carry] in carry_in)
 // in the same pass -- the other streams' carried samples are copied to rows of fft - 1 floats and len_out = n_carry.

@@ -104,10 +104,12 @@ __device__ __forceinline__ void window_tail_request(const WindowTail& W, int B, 
 // window_tail_prepare's table; scratch: LDS, window_tail_scratch_bytes(W.nq) bytes the caller no longer needs; R: ring slots
 // per lane (16 R >= W.nq).  The caller synchronises before it reuses `scratch` or `cw`.  T is read per lane (stream s of the lane:
 // chunks of different lengths may sit side by side); live = false: the lane's stream writes nothing (a skipped iteration).
+// Returns the lane's stream's hit (the same in its 16 lanes; meaningless where nothing is written): heads_window_kernel couples
+// two windows on it, every other caller drops it.
 template <int R>
-__device__ __forceinline__ void window_tail(const WindowTail& W, int B, int b0, int T, const int8_t* cw, int cw_stride, const uint8_t* dl,
+__device__ __forceinline__ bool window_tail(const WindowTail& W, int B, int b0, int T, const int8_t* cw, int cw_stride, const uint8_t* dl,
                                             char* scratch, int tid, const WindowTailRegs<R>& g, bool live = true) {
-    if (tid >= 256) return;
+    if (tid >= 256) return false;
     const int nq = W.nq, nl = W.n_label;
     const int s = tid >> 4, q = tid & 15;
     const bool valid = live && b0 + s < B;
@@ -199,6 +201,7 @@ __device__ __forceinline__ void window_tail(const WindowTail& W, int B, int b0, 
         W.hit[b] = hit ? 1 : 0;
         if (W.restart) W.restart[b] = hit ? 1 : 0;
     }
+    return hit;
 }
 
 }  // namespace kws

@@ -4,6 +4,10 @@ dense layers (README "Customize keyword": the trained [H, C] head and a second [
 
     model = DeployModel(config, weights)          # config.num_classes2 set, weights with Wfc2 / bfc2
     hit, text = predict_ctc(model, pcm, config.label_seqs)
+
+That is the whole-utterance form.  The streaming form -- both heads decoded per chunk in the detector loop, one stack run, a
+window per head -- is detector.StreamManager(model, batch, label=..., label2=...) (device) and its host mirror
+detector.HotwordDetector(model, label=..., label2=...).
 """
 from . import prediction as _prediction
 from .rnn_ctc import FEED_INPUT, FEED_STATE, FETCH_NN_OUTPUTS, FETCH_SOFTMAX1, FETCH_SOFTMAX2

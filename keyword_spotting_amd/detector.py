@@ -12,6 +12,11 @@ What is reproduced, per sess.run-sized chunk and per stream:
   * sample carry arithmetic between PCM chunks (detector.py:179-183) -- ChunkFramer
   * test2: chunked replay of a whole utterance, one ctc_decode at the end (detector.py:254-289)
 
+A customised-keyword model (config.num_classes2: a second dense layer on the frozen stack, README "Customize keyword": "do
+softmax and decode respectively") streams BOTH heads when label2 is given: the stack once per chunk, a window per head, each
+decoded at its own threshold against its own label, the two decisions ORed (server_demo.py:122-129), and a detection of EITHER
+head clears both windows and restarts the state (detector.py:202-208).  hit = hit_1 | hit_2 << 1 per stream.
+
 B independent streams run in lock step (one kws_step per chunk for all of them); the window
 bookkeeping is per stream.  feed() takes the mel variant of the graph (models/rnn_ctc.py:150-153); feed_pcm() is
 the shipped graph's contract (PCM in, front-end on the device).
@@ -54,9 +59,20 @@ class ChunkFramer(object):
         return frames
 
 
+def _second_head(model, label2, decode_thres2, decode_thres):
+    """(label2, threshold 2) of a two-head detector / manager; label2 None: (None, None), the one-head loop as it always was."""
+    if label2 is None:
+        if decode_thres2 is not None:
+            raise _lib.InvalidArgumentError(-1, "decode_thres2 needs label2")
+        return None, None
+    if not getattr(model, "num_classes2", 0):
+        raise _lib.InvalidArgumentError(-1, "label2 needs a model with a second class head (config.num_classes2)")
+    return str(label2), float(decode_thres if decode_thres2 is None else decode_thres2)
+
+
 class HotwordDetector(object):
     def __init__(self, model, batch=1, window_chunks=15, vad_thres=30, label=None, decode_thres=0.4,
-                 detected_callback=None):
+                 detected_callback=None, label2=None, decode_thres2=None):
         self.model = model
         self.config = model.config
         self.batch = int(batch)
@@ -65,6 +81,10 @@ class HotwordDetector(object):
         self.decode_thres = decode_thres
         self.detected_callback = detected_callback
         self.prob_queue = [SimpleQueue(window_chunks) for _ in range(self.batch)]
+        # the second head of a customised-keyword model: its own queue, label and threshold; the host mirror of StreamManager(label2=...)
+        self.label2, self.decode_thres2 = _second_head(model, label2, decode_thres2, decode_thres)
+        self.prob_queue2 = [SimpleQueue(window_chunks) for _ in range(self.batch)] if self.label2 is not None else None
+        self.hit_mask = np.zeros(self.batch, np.int32)      # the last chunk's hit_1 | hit_2 << 1 per stream
         self.state = model.zero_state(self.batch)
         self.reset_next = torch.zeros(self.batch, dtype=torch.uint8, device=model.device)
         self.triggers = [0] * self.batch
@@ -93,6 +113,10 @@ class HotwordDetector(object):
             for b in np.nonzero(~np.asarray(speech, bool))[0]:       # :171-177
                 self.clean_state(int(b))
                 self.prob_queue[int(b)].clear()
+                if self.prob_queue2 is not None:
+                    self.prob_queue2[int(b)].clear()
+        if self.label2 is not None:
+            return self._feed_heads(mel)
         # (zero frames: dynamic_rnn hands the state back, clean_state() has zeroed it where the mask says so)
         r = self.model.forward(mel, self.state, reset_mask=self.reset_next, want_logits=False, want_softmax=True,
                                state_out=self.state)
@@ -100,14 +124,8 @@ class HotwordDetector(object):
         softmax = r["softmax"]
         for b in range(self.batch):                                  # :195
             self.prob_queue[b].add(softmax[b])
-        windows = [torch.cat(q.get_all(), 0) for q in self.prob_queue]   # :197
-        lens = torch.tensor([w.shape[0] for w in windows], dtype=torch.int32)
-        tmax = int(lens.max()) if self.batch else 0
-        padded = torch.zeros(self.batch, max(tmax, 1), self.config.num_classes, device=self.model.device)
-        for b, w in enumerate(windows):
-            padded[b, :w.shape[0]] = w
-        words, counts = decode_batch(_lib.DECODE2, padded, lens, 3, self.decode_thres, 0.0)   # :200
-        hits = _ctc_predict((words, counts), self.label).cpu().numpy()                        # :201
+        hits = self._window_hits(self.prob_queue, self.config.num_classes, self.decode_thres, self.label)
+        self.hit_mask = hits.astype(np.int32)
         fired = []
         for b in np.nonzero(hits)[0]:
             b = int(b)
@@ -117,6 +135,42 @@ class HotwordDetector(object):
                 self.detected_callback(b)
             self.prob_queue[b].clear()                               # :203
             self.clean_state(b)                                      # :208
+        return fired
+
+    def _window_hits(self, queues, num_classes, thres, label):
+        """detector.py:197-201 for every stream of one head: concatenate the window, ctc_decode2, ctc_predict -> [B] 0 / 1."""
+        windows = [torch.cat(q.get_all(), 0) for q in queues]            # :197
+        lens = torch.tensor([w.shape[0] for w in windows], dtype=torch.int32)
+        tmax = int(lens.max()) if self.batch else 0
+        padded = torch.zeros(self.batch, max(tmax, 1), num_classes, device=self.model.device)
+        for b, w in enumerate(windows):
+            padded[b, :w.shape[0]] = w
+        words, counts = decode_batch(_lib.DECODE2, padded, lens, 3, thres, 0.0)   # :200
+        return _ctc_predict((words, counts), label).cpu().numpy()                 # :201
+
+    def _feed_heads(self, mel):
+        """The loop body for both heads (the VAD part is done): the stack once, head k's softmax into queue k, each window decoded
+        at its own threshold against its own label; a hit of either head clears both queues and restarts the state."""
+        r = self.model.forward_heads(mel, self.state, reset_mask=self.reset_next, want_nn_outputs=False, want_logits=False,
+                                     state_out=self.state)
+        self.reset_next.zero_()
+        sm1, sm2 = r["head1"]["softmax"], r["head2"]["softmax"]
+        for b in range(self.batch):
+            self.prob_queue[b].add(sm1[b])
+            self.prob_queue2[b].add(sm2[b])
+        hit1 = self._window_hits(self.prob_queue, self.config.num_classes, self.decode_thres, self.label)
+        hit2 = self._window_hits(self.prob_queue2, self.model.num_classes2, self.decode_thres2, self.label2)
+        self.hit_mask = (hit1 != 0).astype(np.int32) | ((hit2 != 0).astype(np.int32) << 1)
+        fired = []
+        for b in np.nonzero(self.hit_mask)[0]:
+            b = int(b)
+            fired.append(b)
+            self.triggers[b] += 1
+            if self.detected_callback is not None:
+                self.detected_callback(b)
+            self.prob_queue[b].clear()
+            self.prob_queue2[b].clear()
+            self.clean_state(b)
         return fired
 
     def feed_pcm(self, pcm_chunk, frontend):
@@ -131,6 +185,7 @@ class HotwordDetector(object):
         if not hasattr(self, "res"):
             self.res = chunk[:, :0]                                   # :125
         if chunk.shape[1] == 0:                                       # :164-166: an empty read is skipped
+            self.hit_mask = np.zeros(self.batch, np.int32)
             return []
         data = torch.cat([self.res, chunk], 1)                        # :179
         fft, hop = self.config.fft_size, self.config.hop_size
@@ -207,18 +262,30 @@ class StreamManager(object):
     per chunk (kws_stream_feed: VAD gate -> front-end with sample carry -> GRU stack -> 15-chunk window with windowed
     ctc_decode2 + ctc_predict, trigger -> clear + restart; the window step rides inside the last GRU layer's launch); feed
     takes mel chunks and chains kws_step and kws_window_step_incremental itself.  No per-stream host work; results are identical to HotwordDetector
-    (tests/test_gpu_detector.py, tests/test_gpu_frontend.py)."""
+    (tests/test_gpu_detector.py, tests/test_gpu_frontend.py).
 
-    def __init__(self, model, batch, window_chunks=15, max_frames=32, vad_thres=30, label=None, decode_thres=0.4):
+    label2 (on a model with a second class head): both heads per chunk on one manager -- a second window (C = num_classes2,
+    threshold decode_thres2, default decode_thres), the stack run once, ONE launch behind it for both projections, both windows
+    and the coupled clear + restart (kws_stream_create_heads / kws_step_heads_window; front-end + L layers + 1 launches per chunk).
+    hit carries hit_1 | hit_2 << 1: non-zero = detected.  Identical to HotwordDetector(label2=...) (tests/test_gpu_heads_stream.py).
+    Without label2 the manager is what it always was, on a two-head model too: head 1 through the fused tail."""
+
+    def __init__(self, model, batch, window_chunks=15, max_frames=32, vad_thres=30, label=None, decode_thres=0.4, label2=None,
+                 decode_thres2=None):
         import ctypes
         self.model, self.config, self.batch = model, model.config, int(batch)
         self.vad_thres, self.decode_thres = vad_thres, decode_thres
         self.label = (label or self.config.label_seqs).encode()
+        label2, self.decode_thres2 = _second_head(model, label2, decode_thres2, decode_thres)
+        self.label2 = None if label2 is None else label2.encode()
         self._lib = _lib.load()
-        self._win = ctypes.c_void_p()
+        self._win, self._win2 = ctypes.c_void_p(), ctypes.c_void_p()
         with torch.cuda.device(model.device):
             _lib.check(self._lib.kws_window_create(self.batch, int(window_chunks), int(max_frames),
                                                    self.config.num_classes, float(decode_thres), ctypes.byref(self._win)))
+            if self.label2 is not None:
+                _lib.check(self._lib.kws_window_create(self.batch, int(window_chunks), int(max_frames), model.num_classes2,
+                                                       self.decode_thres2, ctypes.byref(self._win2)))
         dev = model.device
         self.state = model.zero_state(self.batch)
         self.restart = torch.zeros(self.batch, dtype=torch.uint8, device=dev)     # reset requested by a trigger
@@ -236,6 +303,9 @@ class StreamManager(object):
         if getattr(self, "_win", None) is not None and self._win.value:
             self._lib.kws_window_destroy(self._win)
             self._win.value = None
+        if getattr(self, "_win2", None) is not None and self._win2.value:
+            self._lib.kws_window_destroy(self._win2)
+            self._win2.value = None
 
     def __del__(self):
         try:
@@ -244,7 +314,7 @@ class StreamManager(object):
             pass
 
     def feed(self, mel_chunk, pcm_chunk=None, speech=None):
-        """-> hit [B] int32 device tensor (1 = keyword detected on this chunk)."""
+        """-> hit [B] int32 device tensor (1 = keyword detected on this chunk; with label2: hit_1 | hit_2 << 1)."""
         mel = torch.as_tensor(mel_chunk)
         if mel.dim() == 2:
             mel = mel.unsqueeze(0)
@@ -257,6 +327,8 @@ class StreamManager(object):
         else:
             silent = (torch.as_tensor(speech).to(dev) == 0).to(torch.uint8)
         reset = torch.maximum(self.restart, silent)                       # detector.py:171-177 and :208
+        if self.label2 is not None:
+            return self._feed_heads(mel, reset, silent)
         r = self.model.forward(mel, self.state, reset_mask=reset, want_logits=False, want_softmax=True,
                                state_out=self.state)
         sm = r["softmax"]
@@ -265,6 +337,21 @@ class StreamManager(object):
             # chunks may alternate on one manager
             _lib.check(self._lib.kws_window_step_incremental(self._win, _lib.ptr(sm), int(sm.shape[1]), _lib.ptr(silent), self.label,
                                                              _lib.ptr(self.hit), _lib.ptr(self.restart), _lib.current_stream_ptr()))
+        return self.hit
+
+    def _feed_heads(self, mel, reset, silent):
+        """One mel-fed iteration of the two-head manager (kws_step_heads_window): the stack as a heads step, then the one launch
+        on both windows."""
+        model, cfg = self.model, self.config
+        mel = model._dev(mel, torch.float32, "mel")
+        if mel.dim() != 3 or mel.shape[0] != self.batch or mel.shape[2] != cfg.n_mel:
+            raise _lib.InvalidArgumentError(-1, "mel must be [%d,T,%d], got %s" % (self.batch, cfg.n_mel, tuple(mel.shape)))
+        t = int(mel.shape[1])
+        with torch.cuda.device(model.device):
+            _lib.check(self._lib.kws_step_heads_window(
+                model._handle, _lib.ptr(mel), _lib.ptr(self.state), _lib.ptr(self.state), _lib.ptr(reset), self.batch, t,
+                self._win, self._win2, self.label, self.label2, _lib.ptr(silent), None, None,
+                _lib.ptr(self.hit), _lib.ptr(self.restart), _lib.current_stream_ptr()))
         return self.hit
 
     def feed_pcm(self, pcm_chunk, frontend, lengths=None):
@@ -338,9 +425,15 @@ class StreamManager(object):
             self._close_stream()
             self._stream = ctypes.c_void_p()
             with torch.cuda.device(dev):
-                _lib.check(self._lib.kws_stream_create(self.model._handle, frontend._handle, self._win, self.batch,
-                                                       self.max_frames * int(self.config.hop_size), float(self.vad_thres),
-                                                       self.label, _lib.ptr(self.state), _lib.ptr(self.restart),
-                                                       ctypes.byref(self._stream)))
+                if self.label2 is not None:
+                    _lib.check(self._lib.kws_stream_create_heads(self.model._handle, frontend._handle, self._win, self._win2, self.batch,
+                                                                 self.max_frames * int(self.config.hop_size), float(self.vad_thres),
+                                                                 self.label, self.label2, _lib.ptr(self.state), _lib.ptr(self.restart),
+                                                                 ctypes.byref(self._stream)))
+                else:
+                    _lib.check(self._lib.kws_stream_create(self.model._handle, frontend._handle, self._win, self.batch,
+                                                           self.max_frames * int(self.config.hop_size), float(self.vad_thres),
+                                                           self.label, _lib.ptr(self.state), _lib.ptr(self.restart),
+                                                           ctypes.byref(self._stream)))
             self._stream_frontend, self._stream_fe_handle = frontend, frontend._handle.value
         return self._stream

@@ -22,7 +22,7 @@ from .rnn_ctc import DeployModel
 
 class StreamServer(object):
     def __init__(self, config, weights=None, device="cuda:0", streams_per_manager=16384, handles=2, label=None,
-                 window_chunks=15, max_frames=32, vad_thres=30, decode_thres=0.4):
+                 window_chunks=15, max_frames=32, vad_thres=30, decode_thres=0.4, label2=None, decode_thres2=None):
         self.config, self.device = config, torch.device(device)
         self.streams_per_manager = int(streams_per_manager)
         w = weights if weights is not None else _weights.init_weights(config, seed=0)
@@ -31,6 +31,8 @@ class StreamServer(object):
         self.frontend = MelFrontend(config, device=self.device)       # immutable tables: shared by every handle
         self._mgr_args = dict(window_chunks=window_chunks, max_frames=max_frames, vad_thres=vad_thres, label=label,
                               decode_thres=decode_thres)
+        if label2 is not None:          # a customised-keyword model: every manager decodes both heads (StreamManager; hits() = hit_1 | hit_2 << 1)
+            self._mgr_args.update(label2=label2, decode_thres2=decode_thres2)
         self.managers = []
 
     # -- population ----------------------------------------------------------------------------------------------------
