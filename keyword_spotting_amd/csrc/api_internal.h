@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "kws_internal.h"
@@ -129,10 +130,14 @@ struct HeadsArgs {
     float* nn_outputs = nullptr;
     kws_head_io head[2] = {};
     bool on[2] = {false, false};
-    // a two-head stream manager's iteration (kws_step_heads_window, kws_stream_feed on a kws_stream_create_heads handle): instead of
-    // dense_heads_kernel, heads_window_kernel follows the top layer -- these parameters, with the seam and the heads' weights filled
-    // in by the launch; with T == 0 it is the step's only launch besides the state pass
-    const kws::HeadsWindowParams* window = nullptr;
+    // a two-head stream manager's iteration (kws_step_heads_window, kws_stream_feed on a kws_stream_create_heads handle; filled by
+    // heads_window_args): heads_window_kernel follows the top layer in dense_heads_kernel's place, on these two windows' tails; head[i]
+    // gives window i's threshold and an optional softmax; frames (StepArgs::seq_len too) / skip: the ragged feed's per-stream frame
+    // counts and skip flags, or null.  With T == 0 it is the step's only launch besides the state pass
+    bool window = false;
+    kws::WindowTail win[2] = {};
+    const int32_t* frames = nullptr; const uint8_t* skip = nullptr;
+    int32_t* hit = nullptr; uint8_t* restart = nullptr;
 };
 // The arguments of one kws_step (include/kws_amd.h), and what the stream manager adds to them
 struct StepArgs {
@@ -146,16 +151,20 @@ struct StepArgs {
     int B = 0, T = 0;
     hipStream_t stream = nullptr;
     const kws::WindowTail* wt = nullptr;   // the stream manager's decode window, to ride at the end of the last layer's launch
-    const struct HeadsArgs* heads = nullptr;   // kws_step_heads: no layer is `last`, dense_heads_kernel follows the top layer
+    const HeadsArgs* heads = nullptr;      // kws_step_heads: no layer is `last`, the heads follow the top layer (kws_model::Tail)
     bool locked = false;                   // the caller (kws_stream_feed) already holds the handle and has ordered the stream
 };
 
-// api_step.hip: one step (kws_step and the stream manager), whether its launch plan (plan_step) lets the last launch take a window
-// tail, and the ordering of a call against the handle's previous one
+// api_step.hip: one step (kws_step and the stream manager), whether the launch plan of `a` (plan_step; a.wt offered) lets the last
+// launch take the window tail, and the ordering of a call against the handle's previous one
 int step_impl(kws_handle h, const StepArgs& a);
-bool step_takes_window(kws_handle h, int B, int T, int window_chunks);
+bool step_takes_window(kws_handle h, const StepArgs& a);
 int call_enter(kws_handle h, hipStream_t st);
 int call_leave(kws_handle h, hipStream_t st);
+// ... device blocks that only grow, `have` their common size in the owner's unit: when want > *have the device is synchronised (the
+// old blocks may still be in use), every block is freed and allocated anew (fine: fine-grained memory), *have = want and
+// scratch_allocs counts ONE growth.  KWS_OK, the error of `what`, or -- fine only -- api_step.hip's internal kNoFineGrainedMemory
+int grow_device(kws_model* h, size_t* have, size_t want, bool fine, std::initializer_list<std::pair<void**, size_t>> blocks, const char* what);
 
 // api_window.hip: the one label rule (digits 1..9, else the error); the n digits go to `digits` as numbers when it is given
 int label_digits(const char* label, int n, int32_t* digits);
@@ -167,23 +176,9 @@ int window_bind_label(kws_window* w, const char* label);
 // ... the incremental window as kernel arguments: of window_inc_kernel, or of the tail of a GRU launch (StepArgs::wt)
 kws::WindowTail window_tail_params(kws_window* w, const uint8_t* clear_before, int32_t* hit, uint8_t* restart);
 
-// api_step.hip: one iteration of a two-head manager from mel on -- the stack planned as a heads step, then heads_window_kernel on the
-// two windows (labels bound by the caller).  frames / skip: the ragged feed's per-stream frame counts and skip flags, or null.
-struct HeadsWindowCall {
-    const float* mel = nullptr;
-    const float* state_in = nullptr;
-    float* state_out = nullptr;
-    const uint8_t *reset_mask = nullptr, *clear_before = nullptr;
-    const int32_t* frames = nullptr;
-    const uint8_t* skip = nullptr;
-    float *softmax1 = nullptr, *softmax2 = nullptr;
-    int32_t* hit = nullptr;
-    uint8_t* restart = nullptr;
-    int B = 0, T = 0;
-    hipStream_t stream = nullptr;
-    bool locked = false;
-};
-int heads_window_step(kws_handle h, kws_window* w1, kws_window* w2, const HeadsWindowCall& c);
+// api_step.hip: the HeadsArgs of a two-head manager's iteration on windows w1 and w2 (labels bound by the caller), for a StepArgs
+// with heads = the result: the stack planned as a heads step, then heads_window_kernel.  The caller adds softmax / frames / skip.
+HeadsArgs heads_window_args(kws_window* w1, kws_window* w2, const uint8_t* clear_before, int32_t* hit, uint8_t* restart);
 // ... the refusals a pair of windows shares between kws_stream_create_heads and kws_step_heads_window (class counts, batch, LDS)
 int heads_window_check(const kws_model* h, const kws_window* w1, const kws_window* w2, int B, int T);
 
@@ -262,32 +257,35 @@ struct kws_model {
     std::vector<int32_t> launches;
     // kernel the last kws_step launched per profiling slot, as a small tag: the name is only formatted when somebody asks
     // (kws_last_launch, kws_selftest) -- not on the launch path, where a 22-frame call is ~100 us of device time
-    enum LaunchFamily : uint8_t { kNone = 0, kBf16Stack, kF16x3, kPipelined, kOctbit, kOctbitFc, kResident, kGeneric, kF16x3Generic, kF16x3Pipelined,
+    enum LaunchFamily : uint8_t { kNone = 0, kBf16Stack, kF16x3, kPipelined, kOctbit, kResident, kGeneric, kF16x3Generic, kF16x3Pipelined,
                                   kGenericWrapped, kPipelinedWrapped };
-    struct LaunchTag { uint8_t family = kNone, kx = 0, first = 0, last = 0, window = 0, heads = 0; };
+    // What follows the top layer inside its profiling slot: nothing (also every layer below; a kws_step_heads call that wants no head and
+    // no nn_outputs), the class epilogue in the layer's own kernel -- alone, or with the stream manager's window step behind it --, or
+    // one more launch: the int8 projection, the two class heads, the two heads with their windows
+    enum Tail : uint8_t { kTailNone = 0, kTailEpilogue, kTailWindow, kTailOctbitFc, kTailDenseHeads, kTailHeadsWindow };
+    struct LaunchTag {
+        uint8_t family = kNone, kx = 0, first = 0, tail = kTailNone;
+        bool last() const { return tail == kTailEpilogue || tail == kTailWindow; }      // the kernels' template argument
+    };
     LaunchTag launch_tag[8];
     std::string launch_name(int slot) const {
         const LaunchTag& t = launch_tag[slot];
-        char nm[96];
-        nm[0] = 0;
-        switch (t.family) {
-            case kBf16Stack: break;
-            case kF16x3: snprintf(nm, sizeof(nm), "gru_layer_f16x3<%d, %s, %s>", t.kx, t.first ? "true" : "false", t.last ? "true" : "false"); break;
-            case kPipelined: snprintf(nm, sizeof(nm), "gru_stack_generic_pipelined<%d> (all %d layers, one launch)", t.kx, cfg.num_layers); break;
-            case kF16x3Generic: snprintf(nm, sizeof(nm), "gru_layer_f16x3_generic<%d, %s, %s>", t.kx, t.first ? "true" : "false", t.last ? "true" : "false"); break;
-            case kF16x3Pipelined: snprintf(nm, sizeof(nm), "gru_stack_f16x3_pipelined<%d> (all %d layers, one launch)", t.kx, cfg.num_layers); break;
-            case kOctbit: snprintf(nm, sizeof(nm), "gru_layer_octbit_kernel"); break;
-            case kOctbitFc: snprintf(nm, sizeof(nm), "gru_layer_octbit_kernel + octbit_fc_kernel"); break;
-            case kResident: snprintf(nm, sizeof(nm), "gru_layer_resident<%d, %s, %s>", t.kx, t.first ? "true" : "false", t.last ? "true" : "false"); break;
-            case kGeneric: snprintf(nm, sizeof(nm), "gru_layer_generic<%d, %s, %s>", t.kx, t.first ? "true" : "false", t.last ? "true" : "false"); break;
-            case kGenericWrapped: snprintf(nm, sizeof(nm), "gru_layer_generic<%d, %s, %s, wrapped>", t.kx, t.first ? "true" : "false", t.last ? "true" : "false"); break;
-            case kPipelinedWrapped: snprintf(nm, sizeof(nm), "gru_stack_generic_pipelined<%d, wrapped> (all %d layers, one launch)", t.kx, cfg.num_layers); break;
-            default: break;
-        }
+        const uint8_t f = t.family;
+        const char* layer = f == kF16x3 ? "gru_layer_f16x3" : f == kF16x3Generic ? "gru_layer_f16x3_generic" : f == kResident ? "gru_layer_resident" :
+                            f == kGeneric || f == kGenericWrapped ? "gru_layer_generic" : nullptr;
+        const char* stack = f == kPipelined || f == kPipelinedWrapped ? "gru_stack_generic_pipelined" : f == kF16x3Pipelined ? "gru_stack_f16x3_pipelined" : nullptr;
+        const char* wrapped = f == kGenericWrapped || f == kPipelinedWrapped ? ", wrapped" : "";
+        char nm[96] = "";
+        if (layer) snprintf(nm, sizeof(nm), "%s<%d, %s, %s%s>", layer, t.kx, t.first ? "true" : "false", t.last() ? "true" : "false", wrapped);
+        else if (stack) snprintf(nm, sizeof(nm), "%s<%d%s> (all %d layers, one launch)", stack, t.kx, wrapped, cfg.num_layers);
+        else if (f == kOctbit) snprintf(nm, sizeof(nm), "gru_layer_octbit_kernel");
         std::string out = t.family == kBf16Stack ? std::string(kws::gru_stack_bf16_kernel_name(pk.bf_kx0, cfg.num_layers)) : std::string(nm);
-        if (t.window) out += " + window tail";          // the stream manager's decode-window step rode in this launch
-        if (t.heads == 1) out += " + dense_heads_kernel<" + std::to_string(cfg.hidden / 16) + ">";      // timed in the top layer's slot
-        if (t.heads == 2) out += " + heads_window_kernel<" + std::to_string(cfg.hidden / 16) + ">";     // (a two-head stream manager's iteration)
+        switch (t.tail) {      // what ran behind the layer is timed in its slot
+            case kTailWindow: out += " + window tail"; break;
+            case kTailOctbitFc: if (t.family == kOctbit) out += " + octbit_fc_kernel"; break;      // (a one-layer int8 model's fp32 layer is named alone)
+            case kTailDenseHeads: out += " + dense_heads_kernel<" + std::to_string(cfg.hidden / 16) + ">"; break;
+            case kTailHeadsWindow: out += " + heads_window_kernel<" + std::to_string(cfg.hidden / 16) + ">"; break;
+        }
         return out;
     }
 };

@@ -6,12 +6,30 @@
 using namespace kws_host;
 
 namespace {
+using M = kws_model;
 // ---- the launch plan: what a kws_step of shape (B, T) launches, decided once ------------------------------------------
 #ifndef KWS_OVERLAP_MIN_T
 #define KWS_OVERLAP_MIN_T 64
 #endif
 struct SeamLayout { int nbuf; size_t bytes_each; bool fine; };
-constexpr int kNoFineGrainedMemory = 1;      // ensure_side_buffers, carve_seams: internal, never returned through the ABI
+constexpr int kNoFineGrainedMemory = 1;      // grow_device, provision: internal, never returned through the ABI
+using Tail = kws_model::Tail;
+
+// What a step asks of the plan: its shape, kws_set_profiling's switch (a field, so that kws_reserve can ask for both answers), and
+// what the caller wants behind the stack -- the class epilogue (kws_step), the window tail where it fits (StepArgs::wt), or, for a
+// kws_step_heads call, dense_heads_kernel, heads_window_kernel or nothing.
+struct PlanRequest {
+    int B, T;
+    bool profiling;
+    Tail want;
+    bool heads() const { return want != M::kTailEpilogue && want != M::kTailWindow; }
+};
+PlanRequest plan_request(const kws_model* h, const StepArgs& a) {
+    Tail want = M::kTailEpilogue;
+    if (a.heads) want = a.heads->window ? M::kTailHeadsWindow : (a.heads->on[0] || a.heads->on[1] || a.heads->nn_outputs) ? M::kTailDenseHeads : M::kTailNone;
+    else if (a.wt && a.wt->nq <= kws::kWinTailMaxChunks) want = M::kTailWindow;
+    return {a.B, a.T, h->profiling, want};
+}
 
 struct StepPlan {
     // kStack: the whole stack in one launch, no seam (bf16).  kSequential: one launch per layer.  kPipelined: all L x groups
@@ -19,18 +37,18 @@ struct StepPlan {
     // kernels on separate HIP streams over time blocks (step_overlapped).
     enum Layout : uint8_t { kZeroFrames, kStack, kSequential, kPipelined, kOverlapped } layout;
     kws_model::LaunchTag tag[8];   // per profiling slot, exactly what kws_last_launch is to report after this step; empty: no launch
+    Tail tail;                     // what follows the top layer: the tail of the last tagged slot (every other slot has none)
     SeamLayout seams;
     int nb, Tb;                    // kOverlapped only: time blocks and their length
     bool streaming;                // some layer addresses its seam through 32-bit buffer offsets (the 2 GiB check)
 };
 
-// The one place that decides kernel family, launch layout, window tail and seams.  Pure: reads the handle, touches nothing.
-// `profiling`: kws_set_profiling's switch (a parameter, so that kws_reserve can ask for both answers); `window`: a decode-window
-// tail that fits the fused form is offered (StepArgs::wt, step_takes_window); `heads`: a kws_step_heads call (StepArgs::heads) --
-// one launch per layer, none of them `last`, the top layer's seam among the buffers, dense_heads_kernel in the top layer's slot.
-// The overlapped and layer-pipelined layouts stay with kws_step.
-StepPlan plan_step(const kws_model* h, int B, int T, bool profiling, bool window, bool heads = false) {
-    using M = kws_model;
+// The one place that decides kernel family, launch layout, what follows the top layer and the seams.  Pure: reads the handle, touches
+// nothing, and nobody writes to its result.  A heads step (PlanRequest::heads) is one launch per layer, none of them `last`, the top
+// layer's seam among the buffers; the overlapped and layer-pipelined layouts stay with kws_step.
+StepPlan plan_step(const kws_model* h, const PlanRequest& r) {
+    const int B = r.B, T = r.T;
+    const bool profiling = r.profiling, heads = r.heads();
     // KWS_NO_PIPELINE=1: never the layer-pipelined launch -- what a device without fine-grained memory gets (pipe_disabled), for A/B
     // runs and for the tests of the layouts that take its place (tests/test_gpu_wrapped.py)
     static const bool no_pipe = [] { const char* e = getenv("KWS_NO_PIPELINE"); return e && e[0] == '1'; }();
@@ -46,11 +64,12 @@ StepPlan plan_step(const kws_model* h, int B, int T, bool profiling, bool window
     // launch that replaces a ~4 us launch of its own; in a persistent workgroup it would sit between two groups, on the critical
     // path once per group (measured, bf16, 16384 streams: 0.349-0.359 ms per chunk with the tail against 0.338-0.340 with
     // window_inc_kernel behind the stack).  Everywhere else window_inc_kernel follows the stack.
-    window = window && !no_tail && T <= kws::kWinTailMaxFrames && groups <= (h->num_cus > 0 ? h->num_cus : 256);
+    const bool window = r.want == M::kTailWindow && !no_tail && T <= kws::kWinTailMaxFrames && groups <= (h->num_cus > 0 ? h->num_cus : 256);
 
     if (c.precision == KWS_BF16) {
         p.layout = StepPlan::kStack;
-        p.tag[0] = {M::kBf16Stack, 0, 0, 0, (uint8_t)(window && kws::gru_stack_bf16_takes_window(h->pk.bf_kx0, L))};
+        p.tail = window && kws::gru_stack_bf16_takes_window(h->pk.bf_kx0, L) ? M::kTailWindow : M::kTailEpilogue;
+        p.tag[0] = {M::kBf16Stack, 0, 0, p.tail};
         return p;
     }
     const bool int8 = c.precision == KWS_INT8, f16 = c.precision == KWS_F16X3;
@@ -72,25 +91,25 @@ StepPlan plan_step(const kws_model* h, int B, int T, bool profiling, bool window
     const bool overlapped = !heads && !profiling && c.precision == KWS_FP32 && L >= 2 && L <= 5 && !pipelined && fits && T >= KWS_OVERLAP_MIN_T;
     p.layout = pipelined ? StepPlan::kPipelined : overlapped ? StepPlan::kOverlapped : StepPlan::kSequential;
 
+    // int8: no GRU layer is `last` -- every layer hands its output rows on through the seam, and the class projection is its own
+    // OctbitMatMul call over the whole [T,H] block behind the top layer, whichever kernel ran that layer
+    p.tail = heads ? r.want : int8 ? M::kTailOctbitFc : M::kTailEpilogue;
     if (pipelined) {      // one launch, timed as the last layer's slot
         const uint8_t family = f16 ? M::kF16x3Pipelined : h->wrapped ? M::kPipelinedWrapped : M::kPipelined;
-        p.tag[L - 1] = {family, (uint8_t)(H / 64), 0, 0, 0};
+        p.tag[L - 1] = {family, (uint8_t)(H / 64), 0, p.tail};
     }
     for (int l = 0; l < L && !pipelined; ++l) {
-        // int8: no GRU layer is `last` -- every layer hands its output rows on through the seam, and the class projection is its
-        // own OctbitMatMul call over the whole [T,H] block behind the top layer (kOctbitFc; launch_slot)
-        const bool first = l == 0, last = !int8 && !heads && l == L - 1;
-        const uint8_t tail = window && last && !overlapped;
-        if (f16_streams) p.tag[l] = {M::kF16x3Generic, (uint8_t)(H / 64), first, last, 0};
-        else if (f16) p.tag[l] = {M::kF16x3, (uint8_t)(first ? h->pk.f16_kx0 : 4), first, last, tail};
-        else if (int8 && h->pk.oct[l].quantised) p.tag[l] = {(uint8_t)(l == L - 1 ? M::kOctbitFc : M::kOctbit), 0, 0, 0, 0};
-        else if (resident(l))
-            p.tag[l] = {M::kResident, (uint8_t)h->pk.layers[l].kcx_res, first, last, (uint8_t)(tail && kws::gru_resident_takes_window(first, last))};
-        else p.tag[l] = {(uint8_t)(h->wrapped ? M::kGenericWrapped : M::kGeneric), (uint8_t)(H / 64), first, last, 0};
+        const bool first = l == 0, top = l == L - 1;
+        const uint8_t family = f16_streams ? M::kF16x3Generic : f16 ? M::kF16x3 : (int8 && h->pk.oct[l].quantised) ? M::kOctbit :
+                               resident(l) ? M::kResident : h->wrapped ? M::kGenericWrapped : M::kGeneric;
+        const int kx = family == M::kF16x3 ? (first ? h->pk.f16_kx0 : 4) : family == M::kResident ? h->pk.layers[l].kcx_res : H / 64;
+        // the window tail rides behind the epilogue where the top layer's kernel has a tail instantiation
+        const bool has_tail = family == M::kF16x3 || (family == M::kResident && kws::gru_resident_takes_window(first, true));
+        if (top && window && has_tail && p.tail == M::kTailEpilogue && !overlapped) p.tail = M::kTailWindow;
+        p.tag[l] = {family, (uint8_t)kx, first, top ? p.tail : M::kTailNone};
     }
 
     if (heads) {               // every layer has a seam, the top one's is what the heads read
-        p.tag[L - 1].heads = 1;
         p.seams = {L >= 2 ? 2 : 1, (size_t)groups * (size_t)H * 16 * sizeof(float) * T, false};
     } else if (L >= 2 || int8) {      // a single fp32 / f16x3 layer has no seam
         const size_t frame_bytes = (size_t)groups * (size_t)H * 16 * sizeof(float);
@@ -113,20 +132,7 @@ int carve_seams(kws_handle h, const SeamLayout& want) {
     s.bytes_each = (s.bytes_each + 255) & ~size_t(255);
     kws_model::Arena& A = s.fine ? h->arena_fine : h->arena;
     const size_t need = (size_t)s.nbuf * s.bytes_each;
-    if (need > A.bytes) {
-        KWS_HIP(hipDeviceSynchronize());
-        if (A.base) { hipFree(A.base); A.base = nullptr; A.bytes = 0; }
-        hipError_t e;
-        if (s.fine) e = hipExtMallocWithFlags(reinterpret_cast<void**>(&A.base), need, hipDeviceMallocFinegrained);
-        else e = hipMalloc(reinterpret_cast<void**>(&A.base), need);
-        if (e != hipSuccess) {
-            A.base = nullptr;
-            (void)hipGetLastError();
-            return s.fine ? kNoFineGrainedMemory : hip_fail(e, "hipMalloc(scratch)");
-        }
-        A.bytes = need;
-        ++h->scratch_allocs;
-    }
+    KWS_TRY(grow_device(h, &A.bytes, need, s.fine, {{reinterpret_cast<void**>(&A.base), need}}, "hipMalloc(scratch)"));
     for (int i = 0; i < 8; ++i)
         h->scratch[i] = i < s.nbuf ? reinterpret_cast<float4*>(A.base + (size_t)i * s.bytes_each) : nullptr;
     h->nscratch = s.nbuf;
@@ -136,59 +142,34 @@ int carve_seams(kws_handle h, const SeamLayout& want) {
 // Everything besides the seams that depends on the batch size: int8 exchange buffers, the pipelined launch's counters.
 int ensure_side_buffers(kws_handle h, int B, bool pipelined, bool heads) {
     const size_t groups = (size_t)kws::groups_of(B);
-    if (heads && groups > h->heads_groups) {      // the two heads' prev_word as they were before the launch (dense_heads.hip)
-        KWS_HIP(hipDeviceSynchronize());
-        if (h->heads_prev) hipFree(h->heads_prev);
-        h->heads_prev = nullptr; h->heads_groups = 0;
-        KWS_HIP(hipMalloc(reinterpret_cast<void**>(&h->heads_prev), 2 * groups * 16 * sizeof(int32_t)));
-        h->heads_groups = groups;
-        ++h->scratch_allocs;
-    }
-    if (h->cfg.precision == KWS_INT8 && groups > h->oct_groups) {
-        KWS_HIP(hipDeviceSynchronize());
-        if (h->oct_aq) hipFree(h->oct_aq);
-        if (h->oct_range) hipFree(h->oct_range);
-        if (h->oct_prev) hipFree(h->oct_prev);
-        h->oct_aq = nullptr; h->oct_range = nullptr; h->oct_prev = nullptr; h->oct_groups = 0;
-        KWS_HIP(hipMalloc(reinterpret_cast<void**>(&h->oct_aq), groups * 2 * 16 * 128 * sizeof(uint32_t)));
-        KWS_HIP(hipMalloc(reinterpret_cast<void**>(&h->oct_range), groups * 16 * sizeof(float2)));
-        KWS_HIP(hipMalloc(reinterpret_cast<void**>(&h->oct_prev), groups * 16 * sizeof(int32_t)));
-        h->oct_groups = groups;
-        ++h->scratch_allocs;
-    }
+    auto block = [](auto** p, size_t bytes) { return std::pair<void**, size_t>(reinterpret_cast<void**>(p), bytes); };
+    if (heads)      // the two heads' prev_word as they were before the launch (dense_heads.hip)
+        KWS_TRY(grow_device(h, &h->heads_groups, groups, false, {block(&h->heads_prev, 2 * groups * 16 * sizeof(int32_t))}, "hipMalloc(heads prev_word)"));
+    if (h->cfg.precision == KWS_INT8)
+        KWS_TRY(grow_device(h, &h->oct_groups, groups, false, {block(&h->oct_aq, groups * 2 * 16 * 128 * sizeof(uint32_t)),
+                            block(&h->oct_range, groups * 16 * sizeof(float2)), block(&h->oct_prev, groups * 16 * sizeof(int32_t))}, "hipMalloc(int8 exchange)"));
     if (pipelined) {
         if (!h->pipe_error_host) {
             KWS_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->pipe_error_host), sizeof(int), hipHostMallocMapped));
             *h->pipe_error_host = 0;
             KWS_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h->pipe_error_dev), h->pipe_error_host, 0));
         }
-        if (groups > h->pipe_groups) {
-            KWS_HIP(hipDeviceSynchronize());
-            if (h->pipe_ready) hipFree(h->pipe_ready);
-            h->pipe_ready = nullptr; h->pipe_groups = 0;
-            if (hipExtMallocWithFlags(reinterpret_cast<void**>(&h->pipe_ready), (size_t)h->cfg.num_layers * groups * sizeof(int),
-                                      hipDeviceMallocFinegrained) != hipSuccess) {
-                (void)hipGetLastError();
-                h->pipe_ready = nullptr;
-                return kNoFineGrainedMemory;
-            }
-            h->pipe_groups = groups;
-            ++h->scratch_allocs;
-        }
+        KWS_TRY(grow_device(h, &h->pipe_groups, groups, true, {block(&h->pipe_ready, (size_t)h->cfg.num_layers * groups * sizeof(int))}, "hipMalloc(pipe_ready)"));
     }
     return KWS_OK;
 }
 
 // The buffers `plan` launches with.  A device without fine-grained memory gives the pipelined launch up for this handle, and the
-// call is planned again, once: this call runs its layers one launch after another (planned as under profiling, whose one effect
-// is that the layers are not overlapped); only later calls may overlap them.
-int provision(kws_handle h, StepPlan& plan, int B, int T, bool window, bool heads = false) {
+// call is planned again, once -- the one write to a plan after plan_step: this call runs its layers one launch after another
+// (planned as under profiling, whose one effect is that the layers are not overlapped); only later calls may overlap them.
+int provision(kws_handle h, StepPlan& plan, PlanRequest r) {
     if (plan.layout == StepPlan::kStack) return KWS_OK;
-    int rc = ensure_side_buffers(h, B, plan.layout == StepPlan::kPipelined, heads);
+    int rc = ensure_side_buffers(h, r.B, plan.layout == StepPlan::kPipelined, r.heads());
     if (rc == KWS_OK) rc = carve_seams(h, plan.seams);
     if (rc == kNoFineGrainedMemory) {
         h->pipe_disabled = true;
-        plan = plan_step(h, B, T, /*profiling=*/true, window, heads);
+        r.profiling = true;
+        plan = plan_step(h, r);
         rc = carve_seams(h, plan.seams);
     }
     return rc;
@@ -351,6 +332,13 @@ void set_octbit_fc(kws::OctbitFcParams& fp, const kws_model* h, const StepArgs& 
     fp.B = a.B; fp.T = a.T; fp.C = c.num_classes;
 }
 
+// Head i's weights, bias and class count (DenseHead, HeadsWindowHead)
+template <typename Head>
+void bind_head(Head& d, const kws_model* h, int i) {
+    d.wfc = h->d_weights + (i ? h->pk.wfc2_off : h->pk.wfc_off);
+    d.bfc = h->d_weights + (i ? h->pk.bfc2_off : h->pk.bfc_off);
+    d.C = i ? h->num_classes2 : h->cfg.num_classes;
+}
 // The heads behind the top layer of a kws_step_heads call
 void set_dense_heads(kws::DenseHeadsParams& dp, const kws_model* h, const StepArgs& a) {
     const kws_config& c = h->cfg;
@@ -359,33 +347,30 @@ void set_dense_heads(kws::DenseHeadsParams& dp, const kws_model* h, const StepAr
     dp.h_top = h->scratch[(c.num_layers - 1) % h->nscratch];
     dp.seq_len = a.seq_len; dp.reset = a.reset_mask;
     dp.nn_outputs = ha.nn_outputs;
-    const size_t wfc[2] = {h->pk.wfc_off, h->pk.wfc2_off}, bfc[2] = {h->pk.bfc_off, h->pk.bfc2_off};
-    const int C[2] = {c.num_classes, h->num_classes2};
     for (int i = 0; i < 2; ++i) {
         if (!ha.on[i]) continue;
         kws::DenseHead& d = dp.head[i];
         const kws_head_io& io = ha.head[i];
-        d.wfc = h->d_weights + wfc[i]; d.bfc = h->d_weights + bfc[i];
+        bind_head(d, h, i);
         d.logits = io.logits; d.softmax = io.softmax; d.tokens = io.tokens; d.prev_word = io.prev_word;
         d.prev_in = io.prev_word ? h->heads_prev + (size_t)i * h->heads_groups * 16 : nullptr;
         d.decode_thres = io.decode2_thres;
-        d.C = C[i];
     }
     dp.value_clip = c.value_clip; dp.use_relu = c.use_relu;
     dp.B = a.B; dp.T = a.T;
 }
-
 // heads_window_kernel behind the top layer of a two-head manager's iteration: the caller's windows and outputs, this handle's heads
 void set_heads_window(kws::HeadsWindowParams& hp, const kws_model* h, const StepArgs& a) {
     const kws_config& c = h->cfg;
-    hp = *a.heads->window;
+    const HeadsArgs& ha = *a.heads;
+    memset(&hp, 0, sizeof(hp));
     hp.h_top = a.T > 0 ? h->scratch[(c.num_layers - 1) % h->nscratch] : nullptr;
-    const size_t wfc[2] = {h->pk.wfc_off, h->pk.wfc2_off}, bfc[2] = {h->pk.bfc_off, h->pk.bfc2_off};
-    const int C[2] = {c.num_classes, h->num_classes2};
     for (int i = 0; i < 2; ++i) {
-        hp.head[i].wfc = h->d_weights + wfc[i]; hp.head[i].bfc = h->d_weights + bfc[i];
-        hp.head[i].C = C[i];
+        bind_head(hp.head[i], h, i);
+        hp.head[i].softmax = ha.head[i].softmax; hp.head[i].decode_thres = ha.head[i].decode2_thres;
+        hp.win[i] = ha.win[i];
     }
+    hp.hit = ha.hit; hp.restart = ha.restart; hp.frames = ha.frames; hp.skip = ha.skip;
     hp.value_clip = c.value_clip; hp.use_relu = c.use_relu;
     hp.B = a.B; hp.T = a.T;
 }
@@ -394,7 +379,6 @@ void set_heads_window(kws::HeadsWindowParams& hp, const kws_model* h, const Step
 // The launch of profiling slot l as the plan tagged it, on `st`.  step_overlapped passes the time block [t0, t0 + frames) of the
 // call: seams double-buffered per block parity, and behind block 0 the state is the one the block before left in state_out.
 int launch_slot(const kws_model* h, const StepArgs& a, const StepPlan& plan, int l, hipStream_t st, int t0 = 0, int frames = 0) {
-    using M = kws_model;
     const kws_config& c = h->cfg;
     const int H = c.hidden, L = c.num_layers;
     const M::LaunchTag& t = plan.tag[l];
@@ -409,9 +393,9 @@ int launch_slot(const kws_model* h, const StepArgs& a, const StepPlan& plan, int
         }
         case M::kF16x3: case M::kF16x3Generic: {
             kws::GruF16Params fp;
-            set_f16_layer(fp, h, a, l, t.last);
-            if (t.family == M::kF16x3) { e = kws::launch_gru_layer_f16x3(fp, t.first, t.last, st); what = "launch gru_layer_f16x3"; }
-            else { e = kws::launch_gru_layer_f16x3_generic(fp, H, t.first, t.last, st); what = "launch gru_layer_f16x3_generic"; }
+            set_f16_layer(fp, h, a, l, t.last());
+            if (t.family == M::kF16x3) { e = kws::launch_gru_layer_f16x3(fp, t.first, t.last(), st); what = "launch gru_layer_f16x3"; }
+            else { e = kws::launch_gru_layer_f16x3_generic(fp, H, t.first, t.last(), st); what = "launch gru_layer_f16x3_generic"; }
             break;
         }
         case M::kF16x3Pipelined: {
@@ -442,49 +426,53 @@ int launch_slot(const kws_model* h, const StepArgs& a, const StepPlan& plan, int
             what = "launch gru_stack_generic_pipelined";
             break;
         }
-        case M::kOctbit: case M::kOctbitFc: {
+        case M::kOctbit: {
             kws::GruOctbitParams op;
             set_octbit_layer(op, h, a, l);
             e = kws::launch_gru_layer_octbit(op, st); what = "launch gru_layer_octbit";
             break;
         }
         case M::kResident: case M::kGeneric: case M::kGenericWrapped: {
-            const bool first = l == 0;
+            const bool first = l == 0, last = t.last();
             kws::GruLayerParams p;
-            set_fp32_layer(p, h, a, l, t.family == M::kResident, t.last);
+            set_fp32_layer(p, h, a, l, t.family == M::kResident, last);
             if (plan.layout == StepPlan::kOverlapped) {
                 const int parity = (t0 / plan.Tb) & 1;
                 p.x_mel = a.mel + (size_t)t0 * c.n_mel;
                 p.x_prev = first ? nullptr : h->scratch[2 * (l - 1) + parity];
-                p.h_out = t.last ? nullptr : h->scratch[2 * l + parity];
+                p.h_out = last ? nullptr : h->scratch[2 * l + parity];
                 if (t0 > 0) { p.state_in = p.state_out; p.reset = nullptr; }
-                set_epilogue(p, a, c, t.last, t0, frames);
+                set_epilogue(p, a, c, last, t0, frames);
                 what = "launch (overlapped layers)";
             } else {
                 what = t.family == M::kResident ? "launch gru_layer_resident" : "launch gru_layer_generic";
             }
-            if (t.family == M::kResident) e = kws::launch_gru_layer_resident(p, t.first, t.last, st);
-            else if (t.family == M::kGenericWrapped) e = kws::launch_gru_layer_generic_wrapped(p, wrap_layer(h, l), H, t.first, t.last, st);
-            else e = kws::launch_gru_layer_generic(p, H, t.first, t.last, st);
+            if (t.family == M::kResident) e = kws::launch_gru_layer_resident(p, t.first, last, st);
+            else if (t.family == M::kGenericWrapped) e = kws::launch_gru_layer_generic_wrapped(p, wrap_layer(h, l), H, t.first, last, st);
+            else e = kws::launch_gru_layer_generic(p, H, t.first, last, st);
             break;
         }
         default: return KWS_OK;      // an empty slot: its layer runs inside another slot's launch
     }
     if (e != hipSuccess) return hip_fail(e, what);
-    if (t.heads == 2) {      // both heads and both windows of a two-head manager, inside the top layer's slot
-        kws::HeadsWindowParams hp;
-        set_heads_window(hp, h, a);
-        return hip_done(kws::launch_heads_window(hp, H, st), "launch heads_window");
+    switch (t.tail) {      // one more launch inside the top layer's slot, on the rows it left in its seam
+        case M::kTailHeadsWindow: {      // both heads and both windows of a two-head manager
+            kws::HeadsWindowParams hp;
+            set_heads_window(hp, h, a);
+            return hip_done(kws::launch_heads_window(hp, H, st), "launch heads_window");
+        }
+        case M::kTailDenseHeads: {       // the class heads
+            kws::DenseHeadsParams dp;
+            set_dense_heads(dp, h, a);
+            return hip_done(kws::launch_dense_heads(dp, H, st), "launch dense_heads");
+        }
+        case M::kTailOctbitFc: {         // the int8 class projection, whichever kernel ran the top layer
+            kws::OctbitFcParams fp;
+            set_octbit_fc(fp, h, a);
+            return hip_done(kws::launch_octbit_fc(fp, st), "launch octbit_fc");
+        }
+        default: return KWS_OK;          // the layer's own kernel did it (epilogue, window tail), or nothing is wanted
     }
-    if (t.heads) {      // the class heads, inside the top layer's slot
-        kws::DenseHeadsParams dp;
-        set_dense_heads(dp, h, a);
-        return hip_done(kws::launch_dense_heads(dp, H, st), "launch dense_heads");
-    }
-    if (c.precision != KWS_INT8 || l != L - 1) return KWS_OK;
-    kws::OctbitFcParams fp;      // the class projection, inside the top layer's slot whichever kernel ran that layer
-    set_octbit_fc(fp, h, a);
-    return hip_done(kws::launch_octbit_fc(fp, st), "launch octbit_fc");
 }
 
 // Layers on separate HIP streams, time-blocked.  When L x groups workgroups fit the chip at once, the layers of a
@@ -526,6 +514,27 @@ int step_overlapped(kws_handle h, const StepArgs& a, const StepPlan& plan) {
     return KWS_OK;
 }
 
+// A step over zero frames.  dynamic_rnn hands the initial state back -- and clean_state() (detector.py:313-316) has already zeroed
+// it for the streams the mask names, together with the previous word of every head the call names: one state pass per prev_word array
+// (kws_step: one; kws_step_heads: two, the second pass copying state_out onto itself), or a plain copy without a mask.  A two-head
+// manager then makes its empty entry into both windows.  No GRU kernel runs: h->launch_tag stays what the step before left.
+int step_zero_frames(kws_handle h, const StepArgs& a) {
+    const int H = h->cfg.hidden, L = h->cfg.num_layers, B = a.B;
+    const hipStream_t st = a.stream;
+    const bool window = a.heads && a.heads->window;
+    int32_t* prev[2] = {a.prev_word, nullptr};      // kws_step's; a two-head manager keeps no words outside its windows
+    int passes = 1;
+    if (a.heads && !window) { prev[0] = a.heads->head[0].prev_word; prev[1] = a.heads->head[1].prev_word; passes = 2; }
+    for (int i = 0; a.reset_mask && i < passes; ++i)
+        KWS_TRY(hip_done(kws::launch_state_passthrough(i ? a.state_out : a.state_in, a.state_out, a.reset_mask, prev[i], L, B, H, st), "launch state_passthrough"));
+    if (!a.reset_mask && a.state_out != a.state_in)
+        KWS_HIP(hipMemcpyAsync(a.state_out, a.state_in, (size_t)L * B * H * sizeof(float), hipMemcpyDeviceToDevice, st));
+    if (!window) return KWS_OK;
+    kws::HeadsWindowParams hp;
+    set_heads_window(hp, h, a);
+    return hip_done(kws::launch_heads_window(hp, H, st), "launch heads_window");
+}
+
 int step_body(kws_handle h, const StepArgs& a) {
     const kws_config& c = h->cfg;
     const int H = c.hidden, L = c.num_layers, B = a.B, T = a.T;
@@ -542,33 +551,9 @@ int step_body(kws_handle h, const StepArgs& a) {
             if (h->ovl_tail[l]) KWS_HIP(hipStreamWaitEvent(st, h->ovl_tail[l], 0));
         h->ovl_tail_valid = false;
     }
-    if (T == 0) {
-        // dynamic_rnn over zero frames hands the initial state back -- and clean_state() (detector.py:313-316) has already
-        // zeroed it for the streams the mask names.  No GRU kernel runs: h->launch_tag stays what the step before left.
-        if (a.heads && a.heads->window) {   // a two-head manager: the state pass, then an empty entry into both windows
-            if (a.reset_mask)
-                KWS_TRY(hip_done(kws::launch_state_passthrough(a.state_in, a.state_out, a.reset_mask, nullptr, L, B, H, st), "launch state_passthrough"));
-            else if (a.state_out != a.state_in)
-                KWS_HIP(hipMemcpyAsync(a.state_out, a.state_in, (size_t)L * B * H * sizeof(float), hipMemcpyDeviceToDevice, st));
-            kws::HeadsWindowParams hp;
-            set_heads_window(hp, h, a);
-            return hip_done(kws::launch_heads_window(hp, H, st), "launch heads_window");
-        }
-        if (a.reset_mask && a.heads) {      // both heads' prev_word; the second pass copies state_out onto itself
-            KWS_TRY(hip_done(kws::launch_state_passthrough(a.state_in, a.state_out, a.reset_mask, a.heads->head[0].prev_word, L, B, H, st),
-                             "launch state_passthrough"));
-            return hip_done(kws::launch_state_passthrough(a.state_out, a.state_out, a.reset_mask, a.heads->head[1].prev_word, L, B, H, st),
-                            "launch state_passthrough");
-        }
-        if (a.reset_mask)
-            return hip_done(kws::launch_state_passthrough(a.state_in, a.state_out, a.reset_mask, a.prev_word, L, B, H, st), "launch state_passthrough");
-        if (a.state_out != a.state_in)
-            KWS_HIP(hipMemcpyAsync(a.state_out, a.state_in, (size_t)L * B * H * sizeof(float), hipMemcpyDeviceToDevice, st));
-        return KWS_OK;
-    }
-    StepPlan plan = plan_step(h, B, T, h->profiling, a.wt != nullptr, a.heads != nullptr);
-    if (a.heads && a.heads->window) plan.tag[L - 1].heads = 2;      // heads_window_kernel in dense_heads_kernel's place (launch_slot)
-    else if (a.heads && !a.heads->on[0] && !a.heads->on[1] && !a.heads->nn_outputs) plan.tag[L - 1].heads = 0;      // nothing behind the stack (launch_slot)
+    if (T == 0) return step_zero_frames(h, a);
+    const PlanRequest req = plan_request(h, a);
+    StepPlan plan = plan_step(h, req);
     if (!a.mel) return fail(KWS_ERR_INVALID_ARGUMENT, "mel is null");
     // the streaming kernels address a group's seam (T x H/16 KiB) through buffer instructions with 32-bit offsets
     if (plan.streaming && (long long)T * (H / 16) >= (1LL << 21))
@@ -577,7 +562,7 @@ int step_body(kws_handle h, const StepArgs& a) {
     if ((reinterpret_cast<uintptr_t>(a.mel) & 15) != 0) return fail(KWS_ERR_INVALID_ARGUMENT, "mel must be 16-byte aligned");
     if (a.heads && T > kws::kHeadsMaxFrames)
         return fail(KWS_ERR_UNSUPPORTED, "T=%d frames exceed the %d a kws_step_heads call takes: split the call", T, kws::kHeadsMaxFrames);
-    KWS_TRY(provision(h, plan, B, T, a.wt != nullptr, a.heads != nullptr));
+    KWS_TRY(provision(h, plan, req));
     if (plan.layout == StepPlan::kOverlapped) {
         KWS_TRY(step_overlapped(h, a, plan));
     } else {      // kStack, kSequential, kPipelined: every tagged slot is one launch on the call's stream
@@ -598,13 +583,25 @@ int step_body(kws_handle h, const StepArgs& a) {
 
 }  // namespace
 
-// Can the last layer's launch of a (B, T) step on this handle take the window tail along?  (kws_stream_feed asks before it hands
-// one to step_impl, which asks again; where the plan says no, window_inc_kernel follows the stack instead.)
-bool kws_host::step_takes_window(kws_handle h, int B, int T, int window_chunks) {
-    const StepPlan plan = plan_step(h, B, T, h->profiling, window_chunks <= kws::kWinTailMaxChunks);
-    for (int l = h->cfg.num_layers - 1; l >= 0; --l)
-        if (plan.tag[l].family != kws_model::kNone) return plan.tag[l].window != 0;      // the last launch of the step
-    return false;
+// Does the plan of `a` -- a step that offers a window tail (a.wt) -- let the last launch take it along?  (kws_stream_feed asks before
+// it hands one to step_impl, which asks again; where the plan says no, window_inc_kernel follows the stack instead.)
+bool kws_host::step_takes_window(kws_handle h, const StepArgs& a) { return plan_step(h, plan_request(h, a)).tail == M::kTailWindow; }
+
+int kws_host::grow_device(kws_model* h, size_t* have, size_t want, bool fine, std::initializer_list<std::pair<void**, size_t>> blocks, const char* what) {
+    if (want <= *have) return KWS_OK;
+    KWS_HIP(hipDeviceSynchronize());
+    for (const auto& b : blocks) { if (*b.first) hipFree(*b.first); *b.first = nullptr; }
+    *have = 0;
+    for (const auto& b : blocks) {
+        const hipError_t e = fine ? hipExtMallocWithFlags(b.first, b.second, hipDeviceMallocFinegrained) : hipMalloc(b.first, b.second);
+        if (e == hipSuccess) continue;
+        *b.first = nullptr;
+        (void)hipGetLastError();
+        return fine ? kNoFineGrainedMemory : hip_fail(e, what);
+    }
+    *have = want;
+    ++h->scratch_allocs;
+    return KWS_OK;
 }
 
 // Ordering of a call against the handle's previous one (kws_model::last_done): device-side, never a host wait.
@@ -621,7 +618,7 @@ int kws_host::call_leave(kws_handle h, hipStream_t st) {
 
 int kws_host::step_impl(kws_handle h, const StepArgs& a) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
-    if (a.wt && (a.seq_len || !step_takes_window(h, a.B, a.T, a.wt->nq))) return fail(KWS_ERR_UNSUPPORTED, "internal: this step cannot take a window tail");
+    if (a.wt && (a.seq_len || !step_takes_window(h, a))) return fail(KWS_ERR_UNSUPPORTED, "internal: this step cannot take a window tail");
     if (a.B < 0 || a.T < 0) return fail(KWS_ERR_INVALID_ARGUMENT, "negative B=%d or T=%d", a.B, a.T);
     if (a.B == 0) return KWS_OK;   // nothing to advance (empty tensors have null data pointers)
     if (!a.state_in || !a.state_out) return fail(KWS_ERR_INVALID_ARGUMENT, "state_in/state_out must not be null");
@@ -666,20 +663,15 @@ int kws_host::heads_window_check(const kws_model* h, const kws_window* w1, const
     return KWS_OK;
 }
 
-int kws_host::heads_window_step(kws_handle h, kws_window* w1, kws_window* w2, const HeadsWindowCall& c) {
-    kws::HeadsWindowParams hp = {};
-    // the tails write hit of their own window where the coupling overwrites it, and leave restart to the coupling
-    hp.win[0] = window_tail_params(w1, c.clear_before, c.hit, nullptr);
-    hp.win[1] = window_tail_params(w2, c.clear_before, c.hit, nullptr);
-    hp.head[0].softmax = c.softmax1; hp.head[0].decode_thres = w1->thres;
-    hp.head[1].softmax = c.softmax2; hp.head[1].decode_thres = w2->thres;
-    hp.hit = c.hit; hp.restart = c.restart; hp.frames = c.frames; hp.skip = c.skip;
+HeadsArgs kws_host::heads_window_args(kws_window* w1, kws_window* w2, const uint8_t* clear_before, int32_t* hit, uint8_t* restart) {
     HeadsArgs ha;
-    ha.window = &hp;
-    StepArgs a;
-    a.mel = c.mel; a.state_in = c.state_in; a.state_out = c.state_out; a.seq_len = c.frames; a.reset_mask = c.reset_mask;
-    a.B = c.B; a.T = c.T; a.stream = c.stream; a.heads = &ha; a.locked = c.locked;
-    return step_impl(h, a);
+    ha.window = true;
+    // the tails write hit of their own window where the coupling overwrites it, and leave restart to the coupling
+    ha.win[0] = window_tail_params(w1, clear_before, hit, nullptr);
+    ha.win[1] = window_tail_params(w2, clear_before, hit, nullptr);
+    ha.head[0].decode2_thres = w1->thres; ha.head[1].decode2_thres = w2->thres;
+    ha.hit = hit; ha.restart = restart;
+    return ha;
 }
 
 extern "C" {
@@ -700,11 +692,12 @@ int kws_step_heads_window(kws_handle h, const float* mel, const float* state_in,
         return fail(KWS_ERR_INVALID_ARGUMENT, "softmax1 / softmax2 must be 8-byte aligned");
     KWS_TRY(window_bind_label(window1, label1));
     KWS_TRY(window_bind_label(window2, label2));
-    HeadsWindowCall c;
-    c.mel = mel; c.state_in = state_in; c.state_out = state_out; c.reset_mask = reset_mask; c.clear_before = clear_before;
-    c.softmax1 = softmax1; c.softmax2 = softmax2; c.hit = hit; c.restart = restart; c.B = B; c.T = T;
-    c.stream = static_cast<hipStream_t>(stream);
-    return heads_window_step(h, window1, window2, c);
+    HeadsArgs ha = heads_window_args(window1, window2, clear_before, hit, restart);
+    ha.head[0].softmax = softmax1; ha.head[1].softmax = softmax2;
+    StepArgs a;
+    a.mel = mel; a.state_in = state_in; a.state_out = state_out; a.reset_mask = reset_mask;
+    a.B = B; a.T = T; a.stream = static_cast<hipStream_t>(stream); a.heads = &ha;
+    return step_impl(h, a);
 }
 
 int kws_step(kws_handle h, const float* mel, const float* state_in, float* logits, float* softmax,
@@ -735,15 +728,19 @@ int kws_reserve(kws_handle h, int B, int T) {
     if (!busy.owned) return fail(KWS_ERR_BUSY, "kws_reserve: another host thread is inside a call on this handle");
     if (B < 0 || T < 0) return fail(KWS_ERR_INVALID_ARGUMENT, "negative B=%d or T=%d", B, T);
     // whichever launch layout kws_step picks for (B, T) -- it depends on kws_set_profiling too -- fits afterwards: the arenas only grow
-    for (const bool profiling : {true, false}) {
-        StepPlan plan = plan_step(h, B, T, profiling, false);
-        KWS_TRY(provision(h, plan, B, T, false));
-    }
-    if (h->num_classes2 > 0) {      // a heads handle: kws_step_heads' layout too (one answer, whatever the profiling switch)
-        StepPlan plan = plan_step(h, B, T, h->profiling, false, true);
-        KWS_TRY(provision(h, plan, B, T, false, true));
-    }
-    return KWS_OK;
+    auto reserve = [&](const StepArgs& a, bool profiling) {
+        PlanRequest r = plan_request(h, a);
+        r.profiling = profiling;
+        StepPlan plan = plan_step(h, r);
+        return provision(h, plan, r);
+    };
+    StepArgs a;
+    a.B = B; a.T = T;
+    KWS_TRY(reserve(a, true));
+    KWS_TRY(reserve(a, false));
+    const HeadsArgs ha;      // a heads handle: kws_step_heads' layout too (one answer, whatever the profiling switch or the heads wanted)
+    a.heads = &ha;
+    return h->num_classes2 > 0 ? reserve(a, h->profiling) : KWS_OK;
 }
 
 int kws_scratch_stats(kws_handle h, size_t* bytes_reserved, int32_t* allocations) {

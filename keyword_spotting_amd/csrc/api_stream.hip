@@ -11,6 +11,43 @@ using namespace kws_host;
 
 namespace {
 
+// The decode half of an iteration, behind the gate and the front-end: the GRU step of the chunk's T frames on the manager's state in
+// place (reset where the gate found silence) and the window step, in the one form the chunk allows.  frames / skip: the ragged
+// feed's per-stream frame counts and skip flags (the step's seq_len: copy-through past them; a skipped stream has reset 0 and 0
+// frames, its state comes back unchanged), or null.
+int stream_decode(kws_stream_handle h, int T, const int32_t* frames, const uint8_t* skip, int32_t* hit, hipStream_t st) {
+    StepArgs step;
+    step.state_in = h->state; step.state_out = h->state; step.reset_mask = h->reset; step.seq_len = frames;
+    step.B = h->B; step.T = T; step.stream = st; step.locked = true;
+    if (T) step.mel = h->mel;
+    KWS_TRY(window_bind_label(h->win, h->label));      // (bound at kws_stream_create; refuses a window that went on with another label)
+    if (h->win2) {
+        // a two-head manager: front-end + L layers + 1 launches -- the stack once, every layer to a seam as a heads step plans it, then
+        // heads_window_kernel: both heads' rows -> words -> their own windows, and the coupled clear + restart (heads_window.hip)
+        KWS_TRY(window_bind_label(h->win2, h->label2));
+        HeadsArgs ha = heads_window_args(h->win, h->win2, h->silent, hit, h->restart);
+        ha.frames = frames; ha.skip = skip;
+        step.heads = &ha;
+        return step_impl(h->model, step);
+    }
+    const kws::WindowTail wt = window_tail_params(h->win, h->silent, hit, h->restart);
+    StepArgs fused = step;
+    fused.wt = &wt; fused.decode2_thres = h->win->thres;
+    // THREE launches per chunk (two for the bf16 stack): the decode-window step (prob_queue.add, ctc_decode2 over the window,
+    // ctc_predict, clear + restart on a hit: detector.py:195-209) rides at the end of the last layer's launch, on the frame words its
+    // flush has just produced -- no softmax round trip, no fourth launch.  The window's threshold is the fused decoder's (ctc_decode2's
+    // frame rule, utils/prediction.py:74).  Not on a ragged chunk: the tail instantiations take no lengths
+    if (T && !frames && step_takes_window(h->model, fused)) return step_impl(h->model, fused);
+    if (T) step.softmax = h->softmax;
+    KWS_TRY(step_impl(h->model, step));
+    kws::WindowIncParams wp = {};      // window_inc_kernel behind the stack, over each stream's own frames
+    wp.win = wt;
+    memcpy(wp.delta, h->win->inc_delta, 256);
+    wp.softmax = step.softmax; wp.thres = h->win->thres; wp.B = h->B; wp.T = T; wp.C = h->win->C;
+    wp.frames = frames; wp.skip = skip;
+    return hip_done(kws::launch_window_inc(wp, st), "launch window_inc");
+}
+
 // One iteration with the model handle held and `st` ordered (kws_stream_feed below).  A chunk that completes no frame is the same
 // iteration over T = 0 frames, as in the reference (detector.py:168-209): vad -> clean_state() + prob_queue.clear() when silent, the
 // samples are carried (:179-183 keeps all of them), sess.run over zero frames returns the state unchanged and an empty softmax,
@@ -35,48 +72,15 @@ int stream_feed_locked(kws_stream_handle h, const void* pcm, int n, int pcm_int1
                                               h->n_carry, next, keep, st), "launch vad_gate"));
         if (T) KWS_TRY(kws_frontend_run_carry(h->fe, carry, h->n_carry, chunk, n, B, h->mel, nullptr, 0, st));
     }
-    if (h->win2) {
-        // a two-head manager: front-end + L layers + 1 launches -- the stack once, every layer to a seam as a heads step plans it, then
-        // heads_window_kernel: both heads' rows -> words -> their own windows, and the coupled clear + restart (heads_window.hip)
-        KWS_TRY(window_bind_label(h->win, h->label));
-        KWS_TRY(window_bind_label(h->win2, h->label2));
-        HeadsWindowCall c;
-        c.mel = T ? h->mel : nullptr; c.state_in = h->state; c.state_out = h->state; c.reset_mask = h->reset; c.clear_before = h->silent;
-        c.hit = hit; c.restart = h->restart; c.B = B; c.T = T; c.stream = st; c.locked = true;
-        KWS_TRY(heads_window_step(h->model, h->win, h->win2, c));
-        h->n_carry = keep; h->cur ^= 1;
-        return KWS_OK;
-    }
-    // the GRU step of the chunk: the manager's state in place, reset where the gate found silence
-    StepArgs step;
-    step.state_in = h->state; step.state_out = h->state; step.reset_mask = h->reset;
-    step.B = B; step.T = T; step.stream = st; step.locked = true;
-    if (T) step.mel = h->mel;
-    if (T) KWS_TRY(window_bind_label(h->win, h->label));      // (bound at kws_stream_create; refuses a window that went on with another label)
-    if (T && step_takes_window(h->model, B, T, h->win->nq)) {
-        // THREE launches per chunk (two for the bf16 stack): the decode-window step (prob_queue.add, ctc_decode2 over the
-        // window, ctc_predict, clear + restart on a hit: detector.py:195-209) rides at the end of the last layer's launch, on
-        // the frame words its flush has just produced -- no softmax round trip, no fourth launch.  The window's threshold
-        // is the fused decoder's (ctc_decode2's frame rule, utils/prediction.py:74)
-        const kws::WindowTail wt = window_tail_params(h->win, h->silent, hit, h->restart);
-        step.decode2_thres = h->win->thres;
-        step.wt = &wt;
-        KWS_TRY(step_impl(h->model, step));
-    } else {
-        if (T) step.softmax = h->softmax;
-        KWS_TRY(step_impl(h->model, step));
-        KWS_TRY(kws_window_step_incremental(h->win, step.softmax, T, h->silent, h->label, hit, h->restart, st));
-    }
+    KWS_TRY(stream_decode(h, T, nullptr, nullptr, hit, st));
     h->n_carry = keep; h->cur ^= 1;
     return KWS_OK;
 }
 
 // One ragged iteration (kws_stream_feed_ragged; kws_stream_feed once the handle is ragged, lens == null: n_max for every stream),
 // with the model handle held and `st` ordered.  Three or four launches whatever the lengths: the FFT front-end with the per-stream
-// gate (vad, masks, next carry and its length, frame count, skip flag), the GRU layers over T = frames of n_max samples after a
-// full carry with seq_len = the per-stream frame counts (copy-through past them; a skipped stream has reset 0 and 0 frames: its
-// state comes back unchanged), and window_inc_kernel over each stream's own frames.  The window step cannot ride in the last GRU
-// launch here: the tail instantiations take no lengths.
+// gate (vad, masks, next carry and its length, frame count, skip flag), then stream_decode over T = frames of n_max samples after a
+// full carry, each stream on its own frames.
 int stream_feed_ragged_locked(kws_stream_handle h, const void* pcm, int n_max, const int32_t* lens, int pcm_int16, int32_t* hit,
                               hipStream_t st) {
     const kws_frontend_config& fc = h->fe->cfg;
@@ -101,27 +105,7 @@ int stream_feed_ragged_locked(kws_stream_handle h, const void* pcm, int n_max, c
     p.mel = h->mel; p.n_samples = p.n_carry + n_max;
     KWS_TRY(hip_done(kws::launch_mel_fft400(p, B, st), "launch mel_fft400 (ragged)"));
     h->ragged = true; h->n_carry = 0; h->cur ^= 1;          // the samples and lengths are in the other buffer now
-    if (h->win2) {          // a two-head manager: the layers with seq_len = frames, then heads_window_kernel<.., true> over each stream's own frames
-        KWS_TRY(window_bind_label(h->win, h->label));
-        KWS_TRY(window_bind_label(h->win2, h->label2));
-        HeadsWindowCall c;
-        c.mel = h->mel; c.state_in = h->state; c.state_out = h->state; c.reset_mask = h->reset; c.clear_before = h->silent;
-        c.frames = h->frames; c.skip = h->skip;
-        c.hit = hit; c.restart = h->restart; c.B = B; c.T = T; c.stream = st; c.locked = true;
-        return heads_window_step(h->model, h->win, h->win2, c);
-    }
-    StepArgs step;
-    step.mel = h->mel; step.softmax = h->softmax;
-    step.state_in = h->state; step.state_out = h->state; step.reset_mask = h->reset; step.seq_len = h->frames;
-    step.B = B; step.T = T; step.stream = st; step.locked = true;
-    KWS_TRY(step_impl(h->model, step));
-    KWS_TRY(window_bind_label(h->win, h->label));
-    kws::WindowIncParams wp = {};
-    wp.win = window_tail_params(h->win, h->silent, hit, h->restart);
-    memcpy(wp.delta, h->win->inc_delta, 256);
-    wp.softmax = h->softmax; wp.thres = h->win->thres; wp.B = B; wp.T = T; wp.C = h->win->C;
-    wp.frames = h->frames; wp.skip = h->skip;
-    return hip_done(kws::launch_window_inc(wp, st), "launch window_inc (ragged)");
+    return stream_decode(h, T, h->frames, h->skip, hit, st);
 }
 
 // The checks every stream-handle call shares: the borrowed handles are alive; the per-stream paths need the FFT front-end.
@@ -231,14 +215,9 @@ int stream_create_impl(const char* who, kws_handle model, kws_frontend_handle fr
     {
         BusyGuard busy(model->in_call);
         if (!busy.owned) rc = fail(KWS_ERR_BUSY, "kws_stream_create: another host thread is inside a call on the model handle");
-        else if (s->stage_bytes > model->stage.bytes) {
-            // grows only here; the old block may still be read by a feed in flight
-            hipError_t es = hipDeviceSynchronize();
-            if (es == hipSuccess && model->stage.base) { hipFree(model->stage.base); model->stage.base = nullptr; model->stage.bytes = 0; }
-            if (es == hipSuccess) es = hipMalloc(reinterpret_cast<void**>(&model->stage.base), s->stage_bytes);
-            if (es != hipSuccess) { model->stage.base = nullptr; rc = hip_fail(es, "hipMalloc(stream staging)"); }
-            else { model->stage.bytes = s->stage_bytes; ++model->scratch_allocs; }
-        }
+        else      // grows only here; the old block may still be read by a feed in flight
+            rc = grow_device(model, &model->stage.bytes, s->stage_bytes, false, {{reinterpret_cast<void**>(&model->stage.base), s->stage_bytes}},
+                             "hipMalloc(stream staging)");
     }
     if (rc == KWS_OK) rc = kws_reserve(model, B, tmax);            // the GRU step of a chunk never allocates afterwards
     if (rc == KWS_OK) rc = window_bind_label(window, s->label);      // the window's summaries are built for this label

@@ -279,13 +279,16 @@ class StreamManager(object):
         label2, self.decode_thres2 = _second_head(model, label2, decode_thres2, decode_thres)
         self.label2 = None if label2 is None else label2.encode()
         self._lib = _lib.load()
-        self._win, self._win2 = ctypes.c_void_p(), ctypes.c_void_p()
+        # one decode window per head in use: (classes, threshold) -> handle
+        heads = [(self.config.num_classes, decode_thres)] + ([(model.num_classes2, self.decode_thres2)] if self.label2 is not None else [])
+        self._wins = []
         with torch.cuda.device(model.device):
-            _lib.check(self._lib.kws_window_create(self.batch, int(window_chunks), int(max_frames),
-                                                   self.config.num_classes, float(decode_thres), ctypes.byref(self._win)))
-            if self.label2 is not None:
-                _lib.check(self._lib.kws_window_create(self.batch, int(window_chunks), int(max_frames), model.num_classes2,
-                                                       self.decode_thres2, ctypes.byref(self._win2)))
+            for classes, thres in heads:
+                self._wins.append(ctypes.c_void_p())
+                _lib.check(self._lib.kws_window_create(self.batch, int(window_chunks), int(max_frames), classes, float(thres),
+                                                       ctypes.byref(self._wins[-1])))
+        # the same handle objects by head, as callers outside the class name them (_win2: a null handle on a one-head manager)
+        self._win, self._win2 = (self._wins + [ctypes.c_void_p()])[:2]
         dev = model.device
         self.state = model.zero_state(self.batch)
         self.restart = torch.zeros(self.batch, dtype=torch.uint8, device=dev)     # reset requested by a trigger
@@ -300,12 +303,10 @@ class StreamManager(object):
 
     def close(self):
         self._close_stream()
-        if getattr(self, "_win", None) is not None and self._win.value:
-            self._lib.kws_window_destroy(self._win)
-            self._win.value = None
-        if getattr(self, "_win2", None) is not None and self._win2.value:
-            self._lib.kws_window_destroy(self._win2)
-            self._win2.value = None
+        for win in getattr(self, "_wins", None) or ():
+            if win.value:
+                self._lib.kws_window_destroy(win)
+                win.value = None
 
     def __del__(self):
         try:
@@ -335,7 +336,7 @@ class StreamManager(object):
         with torch.cuda.device(dev):
             # the incremental form of the window step: the state kws_stream_feed (feed_pcm) keeps, so mel-fed and PCM-fed
             # chunks may alternate on one manager
-            _lib.check(self._lib.kws_window_step_incremental(self._win, _lib.ptr(sm), int(sm.shape[1]), _lib.ptr(silent), self.label,
+            _lib.check(self._lib.kws_window_step_incremental(self._wins[0], _lib.ptr(sm), int(sm.shape[1]), _lib.ptr(silent), self.label,
                                                              _lib.ptr(self.hit), _lib.ptr(self.restart), _lib.current_stream_ptr()))
         return self.hit
 
@@ -350,7 +351,7 @@ class StreamManager(object):
         with torch.cuda.device(model.device):
             _lib.check(self._lib.kws_step_heads_window(
                 model._handle, _lib.ptr(mel), _lib.ptr(self.state), _lib.ptr(self.state), _lib.ptr(reset), self.batch, t,
-                self._win, self._win2, self.label, self.label2, _lib.ptr(silent), None, None,
+                self._wins[0], self._wins[1], self.label, self.label2, _lib.ptr(silent), None, None,
                 _lib.ptr(self.hit), _lib.ptr(self.restart), _lib.current_stream_ptr()))
         return self.hit
 
@@ -425,15 +426,10 @@ class StreamManager(object):
             self._close_stream()
             self._stream = ctypes.c_void_p()
             with torch.cuda.device(dev):
-                if self.label2 is not None:
-                    _lib.check(self._lib.kws_stream_create_heads(self.model._handle, frontend._handle, self._win, self._win2, self.batch,
-                                                                 self.max_frames * int(self.config.hop_size), float(self.vad_thres),
-                                                                 self.label, self.label2, _lib.ptr(self.state), _lib.ptr(self.restart),
-                                                                 ctypes.byref(self._stream)))
-                else:
-                    _lib.check(self._lib.kws_stream_create(self.model._handle, frontend._handle, self._win, self.batch,
-                                                           self.max_frames * int(self.config.hop_size), float(self.vad_thres),
-                                                           self.label, _lib.ptr(self.state), _lib.ptr(self.restart),
-                                                           ctypes.byref(self._stream)))
+                # (model, front-end, window per head, B, samples, vad, label per head, state, restart, out)
+                create = self._lib.kws_stream_create if len(self._wins) == 1 else self._lib.kws_stream_create_heads
+                labels = [self.label, self.label2][:len(self._wins)]
+                _lib.check(create(self.model._handle, frontend._handle, *self._wins, self.batch, self.max_frames * int(self.config.hop_size),
+                                  float(self.vad_thres), *labels, _lib.ptr(self.state), _lib.ptr(self.restart), ctypes.byref(self._stream)))
             self._stream_frontend, self._stream_fe_handle = frontend, frontend._handle.value
         return self._stream

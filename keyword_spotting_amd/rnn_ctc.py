@@ -151,11 +151,8 @@ class DeployModel(object):
         return torch.full((batch,), -1, dtype=torch.int32, device=self.device)
 
     # -- compute -----------------------------------------------------------------------------
-    def forward(self, mel, state, seq_len=None, reset_mask=None, want_logits=True, want_softmax=True,
-                prev_word=None, decode2_thres=0.4, state_out=None, out=None):
-        """One sess.run of the deploy graph on B streams.  Returns a dict with the requested
-        'logits', 'softmax', 'state' and, if prev_word is given, 'tokens' (prev_word is updated
-        in place)."""
+    def _step_inputs(self, mel, state, seq_len, reset_mask):
+        """The inputs forward and forward_heads share, on the device and checked -> (mel, state, seq_len, reset_mask, B, T)."""
         cfg = self.config
         mel = self._dev(mel, torch.float32, "mel")
         state = self._dev(state, torch.float32, "state")
@@ -173,6 +170,15 @@ class DeployModel(object):
             reset_mask = self._dev(reset_mask, torch.uint8, "reset_mask")
             if tuple(reset_mask.shape) != (b,):
                 raise _lib.InvalidArgumentError(-1, "reset_mask must be [%d]" % b)
+        return mel, state, seq_len, reset_mask, b, t
+
+    def forward(self, mel, state, seq_len=None, reset_mask=None, want_logits=True, want_softmax=True,
+                prev_word=None, decode2_thres=0.4, state_out=None, out=None):
+        """One sess.run of the deploy graph on B streams.  Returns a dict with the requested
+        'logits', 'softmax', 'state' and, if prev_word is given, 'tokens' (prev_word is updated
+        in place)."""
+        cfg = self.config
+        mel, state, seq_len, reset_mask, b, t = self._step_inputs(mel, state, seq_len, reset_mask)
         out = out or {}
         c = cfg.num_classes
         logits = out.get("logits") if want_logits else None
@@ -212,22 +218,7 @@ class DeployModel(object):
         if not self.num_classes2:
             raise _lib.InvalidArgumentError(-1, "forward_heads needs a model with a second head (config.num_classes2)")
         cfg = self.config
-        mel = self._dev(mel, torch.float32, "mel")
-        state = self._dev(state, torch.float32, "state")
-        if mel.dim() != 3 or mel.shape[2] != cfg.n_mel:
-            raise _lib.InvalidArgumentError(-1, "mel must be [B,T,%d], got %s" % (cfg.n_mel, tuple(mel.shape)))
-        b, t = int(mel.shape[0]), int(mel.shape[1])
-        if tuple(state.shape) != (cfg.num_layers, b, cfg.hidden_size):
-            raise _lib.InvalidArgumentError(-1, "state must be [%d,%d,%d], got %s"
-                                            % (cfg.num_layers, b, cfg.hidden_size, tuple(state.shape)))
-        if seq_len is not None:
-            seq_len = self._dev(seq_len, torch.int32, "seq_len")
-            if tuple(seq_len.shape) != (b,):
-                raise _lib.InvalidArgumentError(-1, "seq_len must be [%d]" % b)
-        if reset_mask is not None:
-            reset_mask = self._dev(reset_mask, torch.uint8, "reset_mask")
-            if tuple(reset_mask.shape) != (b,):
-                raise _lib.InvalidArgumentError(-1, "reset_mask must be [%d]" % b)
+        mel, state, seq_len, reset_mask, b, t = self._step_inputs(mel, state, seq_len, reset_mask)
         prev_words = tuple(prev_words) if prev_words is not None else (None, None)
         res, ios, keep = {}, [None, None], []
         for i, c in enumerate((cfg.num_classes, self.num_classes2)):
