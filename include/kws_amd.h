@@ -16,6 +16,8 @@
  *   kws_stream_feed            one iteration of HotwordDetector.start's loop, detector.py:158-209, for B streams
  *   kws_stream_create_heads    ... on a customised-keyword model: both dense layers decoded per chunk ("do softmax and decode
  *                              respectively", README "Customize keyword"), the decisions ORed (server_demo.py:122-129)
+ *   kws_enroll_fit             the training of the README's "Customize keyword" step: tf.nn.ctc_loss + AdamOptimizer on the new
+ *                              columns of the class projection (models/rnn_ctc.py:59-101), frozen stack
  *   kws_octbit_matmul          REGISTER_OP("OctbitMatMul") octbit/octbit_ops_reg.cc:7-15,
  *                              OctbitMatMulOp::Compute octbit/octbit_mat_mul_op.cc:49-183
  *   kws_octbit_quantize        octize_weight_int8_signed octbit/octbit_graph.py:191-215
@@ -480,6 +482,51 @@ int kws_stream_create_heads(kws_handle model, kws_frontend_handle frontend, kws_
 int kws_step_heads_window(kws_handle model, const float* mel, const float* state_in, float* state_out, const uint8_t* reset_mask, int B, int T,
                           kws_window_handle window1, kws_window_handle window2, const char* label1, const char* label2,
                           const uint8_t* clear_before, float* softmax1, float* softmax2, int32_t* hit /*[B]*/, uint8_t* restart, void* stream);
+
+/* Customised-keyword enrolment (README "Customize keyword"; models/rnn_ctc.py:59-101): the GRU stack and every column of the trained
+ * [H, C] projection stay frozen, n_new columns [H, n_new] and their bias are trained on a few utterances with tf.nn.ctc_loss and
+ * tf.train.AdamOptimizer, and stand in front of the blank column of the second head (kws_create_heads).  The stack runs ONCE
+ * (kws_step_heads: nn_outputs and head 1's logits, which are the second head's frozen logits); every optimiser step after that is
+ * the fit below.
+ *
+ * The CTC loss (both entry points): the blank is the LAST class; labels index classes 0..classes-2; extended label sequence blank,
+ * l_1, blank, ..., l_S, blank with S <= 31.  Frames t >= seq_len[b] contribute nothing.  seq_len[b] == 0 is an empty slot: loss 0,
+ * gradient 0, its label ignored.  An utterance without a valid path (seq_len < S + repeats) has loss +inf and gradient exactly 0.
+ * seq_len [B], labels [B,S_max] and label_len [B] are HOST memory: they are range-checked before anything is launched
+ * (KWS_ERR_INVALID_ARGUMENT) and reach the device as one stream-ordered copy.  LDS: 4 T (8 + 2 S_max + 1) bytes per utterance; more
+ * than 160 KiB per workgroup is KWS_ERR_UNSUPPORTED with the byte counts.
+ *
+ *   kws_ctc_loss   logits [B,T,C] f32 device, C in 3..8 -> loss [B] (-log P) and, unless NULL, grad_logits [B,T,C] = softmax -
+ *                  occupancy / P, zero at t >= seq_len[b].  One wave per utterance. */
+int kws_ctc_loss(const float* logits, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int C, int S_max,
+                 float* loss, float* grad_logits_or_null, void* stream);
+/* An enrolment handle: E independent enrolments of K utterance slots each (K in 1..4, B = E*K utterances, enrolment e owns
+ * utterances e*K .. e*K+K-1), for a model of hidden size H (64, 128, 256) whose trained head has C classes (3..7) and n_new new
+ * ones (C + n_new <= 8).  It owns the new columns Wn [E,H,n_new], their bias bn [E,n_new], Adam's two moments and the step count.
+ *   kws_enroll_set    Wn, bn (device) -> the handle; zeroes the moments and the step count
+ *   kws_enroll_fit    `iterations` optimiser steps in ONE launch, one workgroup per enrolment.  nn_outputs [B,T,H] and logits1 [B,T,C]
+ *                     (device): what kws_step_heads returns for the utterances, of a model without use_relu / value_clip.  Per step:
+ *                     logits2 = (logits1[.., 0..C-2] | nn_outputs . Wn + bn | logits1[.., C-1]), the CTC loss of every slot on
+ *                     `labels` (which index the C + n_new classes of that head), its gradient with respect to Wn and bn summed over
+ *                     the K slots in slot order and divided by K (config.batch_size; empty slots add 0), then TensorFlow's Adam:
+ *                     lr_t = lr sqrt(1 - 0.999^t) / (1 - 0.9^t), theta -= lr_t m / (sqrt(v) + 1e-8); no gradient clipping.
+ *                     loss_trace [iterations, B] (device) or NULL: every slot's loss at every step, before that step's update.
+ *                     N calls of one iteration give the bits of one call of N.
+ *   kws_enroll_get    the handle's Wn, bn -> device buffers
+ *   kws_enroll_moments  Adam's m and v, each [E,H,n_new] followed by [E,n_new], -> device buffers (inspection / tests)
+ *   kws_enroll_stats  device bytes the handle holds, device (re)allocations since create (one at the first fit of a shape; each
+ *                     waited for the device) and optimiser steps since kws_enroll_set; any pointer may be NULL
+ * One host thread at a time per handle (KWS_ERR_BUSY); a call on another stream than the previous one is ordered behind it by the
+ * handle's event.  No call synchronises except create, destroy and the first fit at a larger B * (2 + S_max). */
+typedef struct kws_enroll* kws_enroll_handle;
+int kws_enroll_create(int H, int C, int n_new, int E, int K, kws_enroll_handle* out);
+int kws_enroll_destroy(kws_enroll_handle h);   /* always KWS_OK */
+int kws_enroll_set(kws_enroll_handle h, const float* Wn, const float* bn, void* stream);
+int kws_enroll_fit(kws_enroll_handle h, const float* nn_outputs, const float* logits1, const int32_t* seq_len, const int32_t* labels,
+                   const int32_t* label_len, int T, int S_max, float lr, int iterations, float* loss_trace_or_null, void* stream);
+int kws_enroll_get(kws_enroll_handle h, float* Wn, float* bn, void* stream);
+int kws_enroll_moments(kws_enroll_handle h, float* m, float* v, void* stream);
+int kws_enroll_stats(kws_enroll_handle h, size_t* device_bytes, int32_t* allocs, int32_t* steps);
 
 /* OctbitMatMul: out[A,N] = (sum_k u8(x)[a,k] * Wq[n,k] - signed*bias[n]) * scale_w * s_x.
  *   x [A,K] f32, Wq [N,K] s8 (pre-transposed), bias [N] f32, out [A,N] f32.  K % 64 == 0, scale_w > 0.

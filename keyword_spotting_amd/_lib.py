@@ -148,6 +148,14 @@ _SIGNATURES = {
     "kws_attention_run": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "kws_attention_pe_table": (_i, [_vp, _vp]),
     "kws_attention_selftest": (_i, [_vp]),
+    "kws_ctc_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "kws_enroll_create": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_vp)]),
+    "kws_enroll_destroy": (_i, [_vp]),
+    "kws_enroll_set": (_i, [_vp, _vp, _vp, _vp]),
+    "kws_enroll_fit": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp]),
+    "kws_enroll_get": (_i, [_vp, _vp, _vp, _vp]),
+    "kws_enroll_moments": (_i, [_vp, _vp, _vp, _vp]),
+    "kws_enroll_stats": (_i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
 }
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 

@@ -1,5 +1,5 @@
 // Host-side state and helpers shared by the C ABI translation units of libkws_amd.so: one api_*.hip per surface (model, step, ops,
-// attention, window, frontend, stream; the last drives the two before it through kws_host), weight_pack.hip, selftest.hip.  Never
+// attention, window, frontend, stream -- which drives the two before it through kws_host --, enroll), weight_pack.hip, selftest.hip.  Never
 // included by a kernel file: the kernel/host surface is kws_internal.h.
 #pragma once
 #include <algorithm>

@@ -403,6 +403,26 @@ hipError_t launch_state_passthrough(const float* state_in, float* state_out, con
 hipError_t launch_vad_gate(const void* pcm, int pcm_int16, int B, int N, float thres, float* pcm_f32, const uint8_t* restart,
                            uint8_t* silent, uint8_t* reset, const float* carry, int n_carry, float* next, int n_next, hipStream_t st);
 
+// enroll_kernels.hip (ctc_device.h): the LDS one wave's utterance takes -- lp [T][8] and alpha [T][2 S_max + 1], in floats
+__host__ __device__ inline size_t ctc_wave_lds_floats(int T, int S_max) { return (size_t)T * (8 + 2 * S_max + 1); }
+inline size_t ctc_loss_lds_bytes(int T, int S_max) { return sizeof(float) * ctc_wave_lds_floats(T, S_max); }
+// ... and an enrolment's workgroup: parameters, both Adam moments and the K slots' partial gradients ((H + 1) n floats each), K waves
+inline size_t enroll_fit_lds_bytes(int H, int n, int K, int T, int S_max) {
+    return sizeof(float) * ((size_t)(3 + K) * (H + 1) * n + (size_t)K * ctc_wave_lds_floats(T, S_max));
+}
+// logits [B,T,C]; seq_len / label_len [B], labels [B,S_max]: device copies the host side has range-checked; grad [B,T,C] or null
+hipError_t launch_ctc_loss(const float* logits, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int C,
+                           int S_max, float* loss, float* grad, hipStream_t st);
+struct EnrollFitParams {
+    const float *nn, *logits1;                      // [E*K,T,H], [E*K,T,C]
+    const int32_t *seq_len, *labels, *label_len;    // [E*K], [E*K,S_max], [E*K]
+    float *W, *b, *mW, *mb, *vW, *vb;               // [E,H,n] / [E,n]: the new columns, their bias, Adam's moments
+    float* loss_trace;                              // [iterations, E*K] or null
+    float lr;
+    int K, n, C, T, S_max, iterations, step0;       // step0: optimiser steps taken before this launch
+};
+hipError_t launch_enroll_fit(const EnrollFitParams& p, int hidden, int E, hipStream_t st);
+
 // octbit_kernels.hip
 hipError_t launch_octbit_matmul(const float* x, const int8_t* Wq, float scale_w, const float* bias,
                                 float* out, int A, int K, int N, int per_row, float* range_ws,

@@ -8,8 +8,24 @@ dense layers (README "Customize keyword": the trained [H, C] head and a second [
 That is the whole-utterance form.  The streaming form -- both heads decoded per chunk in the detector loop, one stack run, a
 window per head -- is detector.StreamManager(model, batch, label=..., label2=...) (device) and its host mirror
 detector.HotwordDetector(model, label=..., label2=...).
+
+Producing the second head is the README's training step -- freeze the stack and the trained head, train n new columns on about
+three utterances with the CTC loss and Adam (models/rnn_ctc.py:59-101):
+
+    weights2 = enroll(model, [mel1, mel2, mel3], ctc_label([5, 6]), n_new=2)    # one user
+    enroller = Enroller(model, n_new=2, enrolments=4096, utterances_per_enrolment=3)   # thousands of users, one launch
+    new_columns, new_bias, loss_trace = enroller.fit(mel, lengths, labels, steps=100)
+
+The stack runs once (kws_step_heads: nn_outputs and head 1's logits); every optimiser step is inside kws_enroll_fit.
 """
+import copy
+import ctypes
+
+import numpy as np
+
+from . import _lib
 from . import prediction as _prediction
+from . import weights as _weights
 from .rnn_ctc import FEED_INPUT, FEED_STATE, FETCH_NN_OUTPUTS, FETCH_SOFTMAX1, FETCH_SOFTMAX2
 
 
@@ -26,3 +42,186 @@ def predict_ctc(model, inputX, label_seqs, decoders=_prediction):
     output2 = decoders.ctc_decode(softmax2, classes2)
     result = decoders.ctc_predict(output1, label_seqs) | decoders.ctc_predict(output2, label_seqs)
     return result, output1, output2
+
+
+MAX_LABEL = 31        # states of the extended label: one lane of a wave each
+
+
+def _pack_labels(labels, batch, what="labels"):
+    """A list of `batch` label sequences (or one sequence for all) -> (labels [batch, S_max] int32, label_len [batch] int32)."""
+    if len(labels) and np.ndim(labels[0]) == 0:
+        labels = [labels] * batch
+    if len(labels) != batch:
+        raise _lib.InvalidArgumentError(-1, "%s: %d sequences for %d utterances" % (what, len(labels), batch))
+    rows = [np.asarray(l, np.int64).ravel() for l in labels]
+    s_max = max([len(r) for r in rows] + [1])
+    out, lens = np.zeros((batch, s_max), np.int32), np.zeros(batch, np.int32)
+    for i, r in enumerate(rows):
+        out[i, :len(r)] = r
+        lens[i] = len(r)
+    return out, lens
+
+
+def _ints(a):
+    a = np.ascontiguousarray(a, np.int32)
+    return a, a.ctypes.data_as(ctypes.c_void_p)
+
+
+def ctc_loss(logits, seq_len, labels, want_grad=True):
+    """kws_ctc_loss: logits [B,T,C] (device tensor or array; the blank is class C-1), seq_len [B], labels: B sequences over
+    0..C-2 -> (loss [B], grad_logits [B,T,C] or None), device tensors.  torch's F.ctc_loss(log_softmax(logits), blank=C-1,
+    reduction='none', zero_infinity=True) with its gradient, except that an utterance without a valid path reports loss +inf."""
+    import torch
+    lib = _lib.load()
+    lg = torch.as_tensor(logits)
+    if lg.dim() != 3:
+        raise _lib.InvalidArgumentError(-1, "logits must be [B,T,C], got %s" % (tuple(lg.shape),))
+    if not lg.is_cuda:
+        lg = lg.to("cuda:0")
+    lg = lg.to(torch.float32).contiguous()
+    b, t, c = (int(v) for v in lg.shape)
+    lab, lab_len = _pack_labels(labels, b)
+    sl, sl_p = _ints(np.full(b, t) if seq_len is None else seq_len)
+    lab, lab_p = _ints(lab)
+    lab_len, lab_len_p = _ints(lab_len)
+    loss = torch.empty(b, dtype=torch.float32, device=lg.device)
+    grad = torch.empty_like(lg) if want_grad else None
+    with torch.cuda.device(lg.device):
+        _lib.check(lib.kws_ctc_loss(_lib.ptr(lg), sl_p, lab_p, lab_len_p, b, t, c, int(lab.shape[1]), _lib.ptr(loss), _lib.ptr(grad),
+                                    _lib.current_stream_ptr()))
+    return loss, grad
+
+
+def truncated_normal(shape, seed=0):
+    """tf.truncated_normal's distribution (models/rnn_ctc.py:266): standard normal, redrawn outside two sigma."""
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal(shape)
+    bad = np.abs(x) > 2.0
+    while bad.any():
+        x[bad] = rng.standard_normal(int(bad.sum()))
+        bad = np.abs(x) > 2.0
+    return x.astype(np.float32)
+
+
+class Enroller(object):
+    """E independent enrolments of K utterances each on one frozen one-head fp32 model: n_new columns [H, n_new] and their bias
+    per enrolment, trained with the CTC loss and TensorFlow's Adam inside one kernel launch per fit (kws_enroll_fit).
+
+    The frozen part comes from a heads handle of the enroller's own: the model's weights (DeployModel.weights_blob) with a
+    second head whose new columns are zero -- kws_step_heads on it returns nn_outputs and head 1's logits in one stack run."""
+
+    def __init__(self, model, n_new, enrolments=1, utterances_per_enrolment=3):
+        cfg = model.config
+        if getattr(model, "num_classes2", 0):
+            raise _lib.InvalidArgumentError(-1, "Enroller takes the one-head model the new head is derived from, not a model that has a second head")
+        if getattr(cfg, "precision", "fp32") != "fp32":
+            raise _lib.UnsupportedError(_lib.KWS_ERR_UNSUPPORTED, "Enroller needs an fp32 model, got precision %r" % cfg.precision)
+        if cfg.use_relu:
+            raise _lib.UnsupportedError(_lib.KWS_ERR_UNSUPPORTED, "Enroller: use_relu / value_clip models are out of scope (the gradient of "
+                                        "TensorFlow's relu and clip at their ties is not pinned)")
+        if any(getattr(model, "wrappers", (False, False))):
+            raise _lib.UnsupportedError(_lib.KWS_ERR_UNSUPPORTED, "Enroller: a second class head has no wrapped form (use_layer_norm / use_residual)")
+        self.n_new, self.enrolments, self.slots = int(n_new), int(enrolments), int(utterances_per_enrolment)
+        self.config, self.device = cfg, model.device
+        self.num_classes2 = cfg.num_classes + self.n_new
+        self._lib = _lib.load()
+        self._handle = ctypes.c_void_p()
+        import torch
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_enroll_create(cfg.hidden_size, cfg.num_classes, self.n_new, self.enrolments, self.slots,
+                                                   ctypes.byref(self._handle)))
+        from .rnn_ctc import DeployModel
+        self.weights = _weights.from_blob(cfg, model.weights_blob)
+        zeros = np.zeros((cfg.hidden_size, self.n_new), np.float32)
+        self._stack = DeployModel(self.heads_config(), self.extended_weights(zeros, zeros[0]), device=str(self.device))
+
+    def heads_config(self):
+        """The model's config with num_classes2 = C + n_new: what the extended weights are served with."""
+        cfg2 = copy.copy(self.config)
+        cfg2.num_classes2 = self.num_classes2
+        return cfg2
+
+    def extended_weights(self, new_columns, new_bias):
+        """The model's weights with the second head built from one enrolment's columns [H, n_new] and bias [n_new] (weights.extend_head)."""
+        w = dict(self.weights)
+        w["Wfc2"], w["bfc2"] = _weights.extend_head(w["Wfc"], w["bfc"], new_columns, new_bias)
+        return w
+
+    def close(self):
+        if getattr(self, "_handle", None) is not None and self._handle.value:
+            self._lib.kws_enroll_destroy(self._handle)
+            self._handle = ctypes.c_void_p()
+        if getattr(self, "_stack", None) is not None:
+            self._stack.close()
+            self._stack = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def stats(self):
+        """(device bytes the handle holds, device allocations since create, optimiser steps since the last fit began)."""
+        nbytes, allocs, steps = ctypes.c_size_t(), ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(self._lib.kws_enroll_stats(self._handle, ctypes.byref(nbytes), ctypes.byref(allocs), ctypes.byref(steps)))
+        return int(nbytes.value), int(allocs.value), int(steps.value)
+
+    def features(self, inputs, lengths=None):
+        """The frozen part of every step, computed once: mel [B,T,n_mel] from the zero state -> (nn_outputs [B,T,H], logits1 [B,T,C])."""
+        r = self._stack.forward_heads(inputs, self._stack.zero_state(self.enrolments * self.slots), seq_len=lengths, heads=(1,),
+                                      want_softmax=False)
+        return r["nn_outputs"], r["head1"]["logits"]
+
+    def fit(self, inputs, lengths, labels, steps, lr=1.5e-3, init=None, seed=0):
+        """inputs: mel [E*K, T, n_mel] (enrolment e owns rows e*K .. e*K+K-1); lengths [E*K] frames (0: an empty slot) or None;
+        labels: E*K sequences over the C + n_new classes of the new head (prediction.ctc_label form), or one for all; `steps` Adam
+        steps at learning rate lr from `init` = (columns [E,H,n_new], bias [E,n_new]) or, None, the reference's truncated normal
+        (models/rnn_ctc.py:266) with zero bias.  -> (new_columns [E,H,n_new], new_bias [E,n_new], loss_trace [steps, E*K]):
+        device tensors; loss_trace[s] holds every slot's loss before step s's update."""
+        import torch
+        e, k, h, n = self.enrolments, self.slots, self.config.hidden_size, self.n_new
+        b = e * k
+        lab, lab_len = _pack_labels(labels, b)
+        if lab.shape[1] > MAX_LABEL:
+            raise _lib.InvalidArgumentError(-1, "labels of up to %d entries, got %d" % (MAX_LABEL, lab.shape[1]))
+        nn, logits1 = self.features(inputs, lengths)
+        t = int(nn.shape[1])
+        if init is None:
+            init = (truncated_normal((e, h, n), seed), np.zeros((e, n), np.float32))
+        wn = torch.as_tensor(init[0]).to(device=self.device, dtype=torch.float32).contiguous()
+        bn = torch.as_tensor(init[1]).to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(wn.shape) != (e, h, n) or tuple(bn.shape) != (e, n):
+            raise _lib.InvalidArgumentError(-1, "init must be ([%d,%d,%d], [%d,%d]), got %s %s" % (e, h, n, e, n, tuple(wn.shape), tuple(bn.shape)))
+        sl, sl_p = _ints(np.full(b, t) if lengths is None else torch.as_tensor(lengths).cpu().numpy())
+        lab, lab_p = _ints(lab)
+        lab_len, lab_len_p = _ints(lab_len)
+        trace = torch.empty(int(steps), b, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            stream = _lib.current_stream_ptr()
+            _lib.check(self._lib.kws_enroll_set(self._handle, _lib.ptr(wn), _lib.ptr(bn), stream))
+            _lib.check(self._lib.kws_enroll_fit(self._handle, _lib.ptr(nn), _lib.ptr(logits1), sl_p, lab_p, lab_len_p, t, int(lab.shape[1]),
+                                                float(lr), int(steps), _lib.ptr(trace), stream))
+            out_w, out_b = torch.empty_like(wn), torch.empty_like(bn)
+            _lib.check(self._lib.kws_enroll_get(self._handle, _lib.ptr(out_w), _lib.ptr(out_b), stream))
+        return out_w, out_b, trace
+
+
+def enroll(model, utterances, label, n_new, steps=300, lr=1.5e-3, init=None, seed=0):
+    """The README's single-user flow: up to four utterances (mel [T_i, n_mel] each) of the new keyword, `label` its
+    prediction.ctc_label over the extended classes (the new words are classes C-1 .. C+n_new-2) -> the weights dict of the
+    customised model, ready for DeployModel with config.num_classes2 = C + n_new."""
+    import torch
+    mels = [torch.as_tensor(u, dtype=torch.float32) for u in utterances]
+    if not mels or any(m.dim() != 2 for m in mels):
+        raise _lib.InvalidArgumentError(-1, "enroll takes a list of mel utterances [T, n_mel]")
+    t = max(int(m.shape[0]) for m in mels)
+    batch = torch.zeros(len(mels), t, int(mels[0].shape[1]))
+    for i, m in enumerate(mels):
+        batch[i, :m.shape[0]] = m
+    enroller = Enroller(model, n_new, enrolments=1, utterances_per_enrolment=len(mels))
+    try:
+        wn, bn, _ = enroller.fit(batch, [int(m.shape[0]) for m in mels], list(label), steps, lr=lr, init=init, seed=seed)
+        return enroller.extended_weights(wn[0].cpu().numpy(), bn[0].cpu().numpy())
+    finally:
+        enroller.close()

@@ -121,3 +121,16 @@ def tokens_to_seq(tokens_row):
     seq = np.zeros(2 * len(w) + 1, np.int32)
     seq[1::2] = w
     return seq
+
+
+def ctc_label(words):
+    """The dataset's label form (process_wav.py:57-66 convert_label): the word classes with the space class 0 around and between
+    them, [0, w1, 0, w2, ..., 0] -- what tf.nn.ctc_loss is trained on, and what kws_ctc_loss / kws_enroll_fit take as `labels`."""
+    words = [int(w) for w in words]
+    if not words:
+        raise _lib.InvalidArgumentError(-1, "ctc_label needs at least one word (convert_label asserts len(label) > 0)")
+    if any(w < 1 for w in words):
+        raise _lib.InvalidArgumentError(-1, "ctc_label words are classes >= 1 (0 is the space), got %s" % (words,))
+    out = np.zeros(2 * len(words) + 1, np.int32)
+    out[1::2] = words
+    return out

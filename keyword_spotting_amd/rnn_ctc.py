@@ -48,6 +48,7 @@ class DeployModel(object):
         self._lib = _lib.load()
         blob = weights if isinstance(weights, np.ndarray) else _weights.to_blob(config, weights)
         blob = np.ascontiguousarray(blob, np.float32)
+        self.weights_blob = blob        # the host copy the handle was created from (custom_keyword.Enroller reads the trained head back)
         self._cfg = _lib.KwsConfig(config.n_mel, config.hidden_size, config.num_layers, config.num_classes,
                                    int(bool(config.use_relu)), float(config.value_clip),
                                    {"fp32": _lib.FP32, "bf16": _lib.BF16, "int8": _lib.INT8, "f16x3": _lib.F16X3}[getattr(config, "precision", "fp32")])
