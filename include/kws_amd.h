@@ -528,6 +528,62 @@ int kws_enroll_get(kws_enroll_handle h, float* Wn, float* bn, void* stream);
 int kws_enroll_moments(kws_enroll_handle h, float* m, float* v, void* stream);
 int kws_enroll_stats(kws_enroll_handle h, size_t* device_bytes, int32_t* allocs, int32_t* steps);
 
+/* Per-user customised keywords: ONE bank of enrolled heads behind one frozen model.  kws_enroll_fit produces one set of columns per
+ * user; a heads handle bakes one second head into the model.  A bank keeps `capacity` slots of n_new columns Wn[u] [H, n_new] and their
+ * bias bn[u] [n_new] on the device (all zero at creation) for a model of hidden size H (64 / 128 / 256) whose trained head has C classes
+ * (3..7, C + n_new <= 8), and a step takes user [B] int32 (device): the slot of each stream.
+ *   stream b, u = user[b] in [0, capacity):  head 1 is exactly head 1 of kws_step_heads.  Head 2 has C2 = C + n_new classes: head 1's
+ *       logits for classes 0..C-2, then nn_outputs[b,t,:] . Wn[u] + bn[u], then head 1's blank logit (kws_enroll_fit's splice); on that
+ *       row relu / clip, softmax and the ctc_decode2 frame rule at head 2's own threshold.
+ *   user[b] outside [0, capacity) (-1 by convention; any other out-of-range value reads as -1, nothing is read out of bounds):  the
+ *       stream has no second head -- its logits2 / softmax2 rows are zeros, its head-2 tokens are 0, its head-2 prev_word becomes -1;
+ *       in a stream manager window 2 takes its chunk entries like any other, all of them wordless, so hit_2 is never set: the stream
+ *       behaves exactly as a stream of a plain one-head manager.
+ *   rows past seq_len[b]:  as kws_step_heads -- nn_outputs 0, head 1 = bfc, head 2's new classes = bn[u], no word.
+ *   kws_bank_create   range refusals (KWS_ERR_UNSUPPORTED for H, KWS_ERR_INVALID_ARGUMENT for C / n_new / capacity < 1) are decided
+ *                     before the device is probed.
+ *   kws_bank_set      slots [first, first + count) <- Wn [count,H,n_new], bn [count,n_new] (device): the layout kws_enroll_get writes,
+ *                     so enrol -> serve is two calls and no host copy.  Stream-ordered; the caller orders it against the feeds that
+ *                     read those slots.  first + count > capacity is refused.
+ *   kws_bank_get      the same slots -> device buffers (tests).
+ *   kws_step_bank     kws_step_heads with head 2 from the bank.  `model` is a kws_create_heads handle (its plan, seams and side buffers
+ *                     serve the step, so kws_reserve covers it unchanged; its OWN second head is not read); the bank's H and C are the
+ *                     model's.  head2 rows have C + n_new classes.  Everything else as kws_step_heads.  kws_last_launch names
+ *                     bank_heads_kernel<H/16> in the top layer's slot, and profiling times it there.
+ *   kws_stream_create_bank   kws_stream_create_heads with head 2 from the bank: window2 has C + n_new classes; `user` [B] (device) is
+ *                     borrowed like state / restart -- the caller rewrites user[b] on the device when a slot is recycled for a new
+ *                     client.  The policy is kws_stream_create_heads' unchanged (silence clears both windows and resets the state;
+ *                     fired = hit_1 | hit_2 clears both and requests the restart; hit[b] = hit_1 | hit_2 << 1; a zero-frame chunk puts
+ *                     an empty entry into both windows; a skipped stream of the ragged feed gets no slot in either).  ONE label2 is
+ *                     bound to window 2 for the whole manager: with a fixed n_new the new words are classes C-1 .. C+n_new-2 for
+ *                     every user, so "56" is everybody's keyword pattern over their own columns; users whose keyword has another word
+ *                     pattern belong to another manager.  The handle is a stream handle (kws_stream_feed / _feed_ragged / _recycle /
+ *                     _carry / _reset / _destroy); recycling does what it does on a heads manager.  The launch stages the group's
+ *                     columns (16 H n_new floats + 512 bytes) next to what heads_window_kernel stages: more than 160 KiB of LDS is
+ *                     KWS_ERR_UNSUPPORTED with the byte counts.
+ *   kws_step_bank_window     kws_step_heads_window with `bank, user` added (mel-fed); softmax2 rows are bitwise kws_step_bank's.
+ * One host thread at a time per bank (KWS_ERR_BUSY) in kws_bank_set / _get, kws_step_bank and kws_step_bank_window.  The feeds of a bank
+ * manager (kws_stream_feed / _feed_ragged) do NOT take the bank's guard: they only queue launches that read the bank's fixed device
+ * block, so a kws_bank_set from another thread is ordered against them by the caller, on the stream, like any other writer of memory
+ * a feed reads.  Out of scope: per-stream labels or per-stream n_new, more than two heads, and
+ * whatever kws_create_heads refuses (f16x3 / bf16 / int8 stacks, the cell wrappers). */
+typedef struct kws_bank* kws_bank_handle;
+int kws_bank_create(int H, int C, int n_new, int capacity, kws_bank_handle* out);
+int kws_bank_destroy(kws_bank_handle bank);   /* always KWS_OK */
+int kws_bank_set(kws_bank_handle bank, int first, int count, const float* Wn /*[count,H,n_new] device*/, const float* bn /*[count,n_new] device*/,
+                 void* stream);
+int kws_bank_get(kws_bank_handle bank, int first, int count, float* Wn, float* bn, void* stream);
+int kws_step_bank(kws_handle model, kws_bank_handle bank, const int32_t* user /*[B] device*/, const float* mel, const float* state_in,
+                  float* state_out, const int32_t* seq_len, const uint8_t* reset_mask, float* nn_outputs, const kws_head_io* head1,
+                  const kws_head_io* head2, int B, int T, void* stream);
+int kws_stream_create_bank(kws_handle model, kws_frontend_handle frontend, kws_window_handle window1, kws_window_handle window2,
+                           kws_bank_handle bank, const int32_t* user /*[B] device*/, int B, int max_chunk_samples, float vad_thres,
+                           const char* label1, const char* label2, float* state, uint8_t* restart, kws_stream_handle* out);
+int kws_step_bank_window(kws_handle model, kws_bank_handle bank, const int32_t* user /*[B] device*/, const float* mel, const float* state_in,
+                         float* state_out, const uint8_t* reset_mask, int B, int T, kws_window_handle window1, kws_window_handle window2,
+                         const char* label1, const char* label2, const uint8_t* clear_before, float* softmax1, float* softmax2,
+                         int32_t* hit /*[B]*/, uint8_t* restart, void* stream);
+
 /* OctbitMatMul: out[A,N] = (sum_k u8(x)[a,k] * Wq[n,k] - signed*bias[n]) * scale_w * s_x.
  *   x [A,K] f32, Wq [N,K] s8 (pre-transposed), bias [N] f32, out [A,N] f32.  K % 64 == 0, scale_w > 0.
  *   per_row_scale = 0: one dynamic activation range over the whole x (the reference op, whose A is

@@ -156,6 +156,14 @@ _SIGNATURES = {
     "kws_enroll_get": (_i, [_vp, _vp, _vp, _vp]),
     "kws_enroll_moments": (_i, [_vp, _vp, _vp, _vp]),
     "kws_enroll_stats": (_i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    # a bank of enrolled heads: per-user customised keywords on one frozen model
+    "kws_bank_create": (_i, [_i, _i, _i, _i, ctypes.POINTER(_vp)]),
+    "kws_bank_destroy": (_i, [_vp]),
+    "kws_bank_set": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "kws_bank_get": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "kws_step_bank": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(KwsHeadIo), ctypes.POINTER(KwsHeadIo), _i, _i, _vp]),
+    "kws_stream_create_bank": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, ctypes.c_char_p, ctypes.c_char_p, _vp, _vp, ctypes.POINTER(_vp)]),
+    "kws_step_bank_window": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, ctypes.c_char_p, ctypes.c_char_p, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
 

@@ -1,5 +1,5 @@
 // Host-side state and helpers shared by the C ABI translation units of libkws_amd.so: one api_*.hip per surface (model, step, ops,
-// attention, window, frontend, stream -- which drives the two before it through kws_host --, enroll), weight_pack.hip, selftest.hip.  Never
+// attention, window, frontend, stream -- which drives the two before it through kws_host --, enroll, bank), weight_pack.hip, selftest.hip.  Never
 // included by a kernel file: the kernel/host surface is kws_internal.h.
 #pragma once
 #include <algorithm>
@@ -138,6 +138,9 @@ struct HeadsArgs {
     kws::WindowTail win[2] = {};
     const int32_t* frames = nullptr; const uint8_t* skip = nullptr;
     int32_t* hit = nullptr; uint8_t* restart = nullptr;
+    // a bank of enrolled heads (kws_step_bank, kws_step_bank_window, a kws_stream_create_bank manager): head 2 of stream b comes from bank
+    // slot user[b] instead of the handle's own second head -- bank_heads_kernel / bank_heads_window_kernel in the two kernels' places
+    const kws::BankRef* bank = nullptr;
 };
 // The arguments of one kws_step (include/kws_amd.h), and what the stream manager adds to them
 struct StepArgs {
@@ -180,7 +183,18 @@ kws::WindowTail window_tail_params(kws_window* w, const uint8_t* clear_before, i
 // with heads = the result: the stack planned as a heads step, then heads_window_kernel.  The caller adds softmax / frames / skip.
 HeadsArgs heads_window_args(kws_window* w1, kws_window* w2, const uint8_t* clear_before, int32_t* hit, uint8_t* restart);
 // ... the refusals a pair of windows shares between kws_stream_create_heads and kws_step_heads_window (class counts, batch, LDS)
-int heads_window_check(const kws_model* h, const kws_window* w1, const kws_window* w2, int B, int T);
+// bank != null: head 2 has the bank's C + n_new classes and the launch stages the group's columns too
+int heads_window_check(const kws_model* h, const kws_window* w1, const kws_window* w2, int B, int T, const kws_bank* bank = nullptr);
+
+// api_stream.hip: kws_stream_create (window2 == null), kws_stream_create_heads and kws_stream_create_bank (bank and user given; checked
+// by the caller with bank_serves); `who` names the entry point in the refusals
+int stream_create_impl(const char* who, kws_handle model, kws_frontend_handle frontend, kws_window_handle window, kws_window_handle window2,
+                       int B, int max_chunk_samples, float vad_thres, const char* label, const char* label2, float* state, uint8_t* restart,
+                       kws_stream_handle* out, kws_bank* bank = nullptr, const int32_t* user = nullptr);
+// api_bank.hip: the refusal of a bank that is not alive or was created for another hidden size / class count than the model's
+int bank_serves(const kws_bank* bank, const kws_model* h, const char* who);
+// ... the bank and a launch's per-stream slots as kernel arguments
+kws::BankRef bank_ref(const kws_bank* bank, const int32_t* user);
 
 // api_frontend.hip: the 400-point FFT kernel takes a launch of B x T frames (else the dense-DFT kernel, which has magnitude mel only)
 bool frontend_takes_fft400(const kws_frontend* h, int B, int T);
@@ -196,6 +210,15 @@ int frontend_run_impl(kws_frontend_handle h, const float* carry, int n_carry, co
 
 }  // namespace kws_host
 #pragma GCC visibility pop
+
+// A bank of enrolled heads (api_bank.hip): `capacity` slots of n_new columns [H, n_new] + bias for a model of hidden size H whose
+// trained head has C classes.  One device allocation, fixed for the handle's life; kws_bank_set is a stream-ordered copy into it.
+struct kws_bank {
+    int H = 0, C = 0, n_new = 0, capacity = 0;
+    float* store = nullptr;          // Wn [capacity,H,n_new] | bn [capacity,n_new]
+    float *Wn = nullptr, *bn = nullptr;
+    std::atomic<int> in_call{0};
+};
 
 struct kws_model {
     kws_config cfg;
@@ -262,7 +285,7 @@ struct kws_model {
     // What follows the top layer inside its profiling slot: nothing (also every layer below; a kws_step_heads call that wants no head and
     // no nn_outputs), the class epilogue in the layer's own kernel -- alone, or with the stream manager's window step behind it --, or
     // one more launch: the int8 projection, the two class heads, the two heads with their windows
-    enum Tail : uint8_t { kTailNone = 0, kTailEpilogue, kTailWindow, kTailOctbitFc, kTailDenseHeads, kTailHeadsWindow };
+    enum Tail : uint8_t { kTailNone = 0, kTailEpilogue, kTailWindow, kTailOctbitFc, kTailDenseHeads, kTailHeadsWindow, kTailBankHeads, kTailBankWindow };
     struct LaunchTag {
         uint8_t family = kNone, kx = 0, first = 0, tail = kTailNone;
         bool last() const { return tail == kTailEpilogue || tail == kTailWindow; }      // the kernels' template argument
@@ -285,6 +308,8 @@ struct kws_model {
             case kTailOctbitFc: if (t.family == kOctbit) out += " + octbit_fc_kernel"; break;      // (a one-layer int8 model's fp32 layer is named alone)
             case kTailDenseHeads: out += " + dense_heads_kernel<" + std::to_string(cfg.hidden / 16) + ">"; break;
             case kTailHeadsWindow: out += " + heads_window_kernel<" + std::to_string(cfg.hidden / 16) + ">"; break;
+            case kTailBankHeads: out += " + bank_heads_kernel<" + std::to_string(cfg.hidden / 16) + ">"; break;
+            case kTailBankWindow: out += " + bank_heads_window_kernel<" + std::to_string(cfg.hidden / 16) + ">"; break;
         }
         return out;
     }
@@ -316,6 +341,9 @@ struct kws_stream {
     float vad_thres = 0.f;
     char label[17] = {0};
     char label2[17] = {0};           // win2's
+    kws_bank* bank = nullptr;        // kws_stream_create_bank: head 2 of stream b from bank slot user[b] (null: the model's own second head)
+    unsigned long long bank_serial = 0;
+    const int32_t* user = nullptr;   // caller-owned [B], borrowed like state / restart
     float* state = nullptr;          // caller-owned [L,B,H]
     uint8_t* restart = nullptr;      // caller-owned [B]
     float* carry[2] = {nullptr, nullptr};   // [B, fft - 1] each: the carried samples ping-pong (the only device memory a manager owns)

@@ -26,7 +26,11 @@ struct PlanRequest {
 };
 PlanRequest plan_request(const kws_model* h, const StepArgs& a) {
     Tail want = M::kTailEpilogue;
-    if (a.heads) want = a.heads->window ? M::kTailHeadsWindow : (a.heads->on[0] || a.heads->on[1] || a.heads->nn_outputs) ? M::kTailDenseHeads : M::kTailNone;
+    if (a.heads) {
+        const bool bank = a.heads->bank != nullptr;      // head 2 from a bank of enrolled columns: the bank kernels in the two kernels' places
+        want = a.heads->window ? (bank ? M::kTailBankWindow : M::kTailHeadsWindow) :
+               (a.heads->on[0] || a.heads->on[1] || a.heads->nn_outputs) ? (bank ? M::kTailBankHeads : M::kTailDenseHeads) : M::kTailNone;
+    }
     else if (a.wt && a.wt->nq <= kws::kWinTailMaxChunks) want = M::kTailWindow;
     return {a.B, a.T, h->profiling, want};
 }
@@ -375,6 +379,32 @@ void set_heads_window(kws::HeadsWindowParams& hp, const kws_model* h, const Step
     hp.B = a.B; hp.T = a.T;
 }
 
+// ... and their bank forms: head 2 has the bank's C + n_new classes and no weights of its own; head 1 is always bound (projected for
+// head 2's frozen logits even where none of its outputs is wanted)
+void set_bank_heads(kws::BankHeadsParams& bp, const kws_model* h, const StepArgs& a) {
+    set_dense_heads(bp.d, h, a);
+    kws::DenseHead& h1 = bp.d.head[0];
+    if (!a.heads->on[0]) { bind_head(h1, h, 0); h1.decode_thres = 0.f; }
+    bp.bank = *a.heads->bank;
+    if (a.heads->on[1]) bp.d.head[1].C = h->cfg.num_classes + bp.bank.n_new;
+}
+void set_bank_window(kws::BankWindowParams& bp, const kws_model* h, const StepArgs& a) {
+    set_heads_window(bp.w, h, a);
+    bp.bank = *a.heads->bank;
+    bp.w.head[1].C = h->cfg.num_classes + bp.bank.n_new;
+}
+// heads_window_kernel, or its bank form, on the windows of a.heads (behind the top layer, or alone on a zero-frame chunk)
+int launch_window_tail_kernel(const kws_model* h, const StepArgs& a, hipStream_t st) {
+    if (a.heads->bank) {
+        kws::BankWindowParams bp;
+        set_bank_window(bp, h, a);
+        return hip_done(kws::launch_bank_heads_window(bp, h->cfg.hidden, st), "launch bank_heads_window");
+    }
+    kws::HeadsWindowParams hp;
+    set_heads_window(hp, h, a);
+    return hip_done(kws::launch_heads_window(hp, h->cfg.hidden, st), "launch heads_window");
+}
+
 // ---- the launches ----------------------------------------------------------------------------------------------------
 // The launch of profiling slot l as the plan tagged it, on `st`.  step_overlapped passes the time block [t0, t0 + frames) of the
 // call: seams double-buffered per block parity, and behind block 0 the state is the one the block before left in state_out.
@@ -456,10 +486,12 @@ int launch_slot(const kws_model* h, const StepArgs& a, const StepPlan& plan, int
     }
     if (e != hipSuccess) return hip_fail(e, what);
     switch (t.tail) {      // one more launch inside the top layer's slot, on the rows it left in its seam
-        case M::kTailHeadsWindow: {      // both heads and both windows of a two-head manager
-            kws::HeadsWindowParams hp;
-            set_heads_window(hp, h, a);
-            return hip_done(kws::launch_heads_window(hp, H, st), "launch heads_window");
+        case M::kTailHeadsWindow: case M::kTailBankWindow:      // both heads and both windows of a two-head manager
+            return launch_window_tail_kernel(h, a, st);
+        case M::kTailBankHeads: {        // the class heads, head 2 from each stream's bank slot
+            kws::BankHeadsParams bp;
+            set_bank_heads(bp, h, a);
+            return hip_done(kws::launch_bank_heads(bp, H, st), "launch bank_heads");
         }
         case M::kTailDenseHeads: {       // the class heads
             kws::DenseHeadsParams dp;
@@ -530,9 +562,7 @@ int step_zero_frames(kws_handle h, const StepArgs& a) {
     if (!a.reset_mask && a.state_out != a.state_in)
         KWS_HIP(hipMemcpyAsync(a.state_out, a.state_in, (size_t)L * B * H * sizeof(float), hipMemcpyDeviceToDevice, st));
     if (!window) return KWS_OK;
-    kws::HeadsWindowParams hp;
-    set_heads_window(hp, h, a);
-    return hip_done(kws::launch_heads_window(hp, H, st), "launch heads_window");
+    return launch_window_tail_kernel(h, a, st);
 }
 
 int step_body(kws_handle h, const StepArgs& a) {
@@ -642,12 +672,12 @@ int kws_host::step_impl(kws_handle h, const StepArgs& a) {
     return rc != KWS_OK ? rc : rl;
 }
 
-int kws_host::heads_window_check(const kws_model* h, const kws_window* w1, const kws_window* w2, int B, int T) {
+int kws_host::heads_window_check(const kws_model* h, const kws_window* w1, const kws_window* w2, int B, int T, const kws_bank* bank) {
     if (h->num_classes2 <= 0)
         return fail(KWS_ERR_INVALID_ARGUMENT, "a two-head stream manager needs a model handle with a second class head (kws_create_heads)");
     if (w1 == w2) return fail(KWS_ERR_INVALID_ARGUMENT, "window1 and window2 are the same handle: each head queues its own chunks");
     const kws_window* w[2] = {w1, w2};
-    const int C[2] = {h->cfg.num_classes, h->num_classes2};
+    const int C[2] = {h->cfg.num_classes, bank ? h->cfg.num_classes + bank->n_new : h->num_classes2};
     for (int i = 0; i < 2; ++i) {
         if (w[i]->C != C[i] || w[i]->B != B)
             return fail(KWS_ERR_INVALID_ARGUMENT, "window%d was created for B=%d C=%d, head %d needs B=%d C=%d", i + 1, w[i]->B, w[i]->C, i + 1, B, C[i]);
@@ -660,6 +690,12 @@ int kws_host::heads_window_check(const kws_model* h, const kws_window* w1, const
                     "(logits %zu, frame words %zu, label tables 512, rings %zu + %zu; limit %zu): use shorter chunks", T, w1->nq, w2->nq, lds,
                     kws::kHeadsWindowLogitsBytes, (size_t)2 * 16 * kws::heads_window_stride(T), kws::window_tail_scratch_bytes(w1->nq),
                     kws::window_tail_scratch_bytes(w2->nq), kWindowIncLdsMax);
+    if (bank && lds + kws::bank_stage_bytes(bank->H, bank->n_new) > kWindowIncLdsMax)
+        return fail(KWS_ERR_UNSUPPORTED, "chunks of up to %d frames with windows of %d and %d chunks and a bank of %d new classes at hidden=%d need %zu "
+                    "bytes of LDS in the bank window step (logits %zu, frame words %zu, label tables 512, rings %zu + %zu, the group's columns %zu; "
+                    "limit %zu): use shorter chunks or windows", T, w1->nq, w2->nq, bank->n_new, bank->H, lds + kws::bank_stage_bytes(bank->H, bank->n_new),
+                    kws::kHeadsWindowLogitsBytes, (size_t)2 * 16 * kws::heads_window_stride(T), kws::window_tail_scratch_bytes(w1->nq),
+                    kws::window_tail_scratch_bytes(w2->nq), kws::bank_stage_bytes(bank->H, bank->n_new), kWindowIncLdsMax);
     return KWS_OK;
 }
 

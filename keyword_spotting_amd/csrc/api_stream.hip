@@ -27,6 +27,8 @@ int stream_decode(kws_stream_handle h, int T, const int32_t* frames, const uint8
         KWS_TRY(window_bind_label(h->win2, h->label2));
         HeadsArgs ha = heads_window_args(h->win, h->win2, h->silent, hit, h->restart);
         ha.frames = frames; ha.skip = skip;
+        const kws::BankRef bank = h->bank ? bank_ref(h->bank, h->user) : kws::BankRef{};
+        if (h->bank) ha.bank = &bank;            // head 2 of every stream from its own bank slot (bank_heads_window_kernel)
         step.heads = &ha;
         return step_impl(h->model, step);
     }
@@ -111,8 +113,8 @@ int stream_feed_ragged_locked(kws_stream_handle h, const void* pcm, int n_max, c
 // The checks every stream-handle call shares: the borrowed handles are alive; the per-stream paths need the FFT front-end.
 int stream_check(kws_stream_handle h, bool ragged_call) {
     if (live_serial(h->model) != h->model_serial || live_serial(h->fe) != h->fe_serial || live_serial(h->win) != h->win_serial ||
-        (h->win2 && live_serial(h->win2) != h->win2_serial))
-        return fail(KWS_ERR_INVALID_ARGUMENT, "the model, front-end or window this stream was created on has been destroyed");
+        (h->win2 && live_serial(h->win2) != h->win2_serial) || (h->bank && live_serial(h->bank) != h->bank_serial))
+        return fail(KWS_ERR_INVALID_ARGUMENT, "the model, front-end, window or bank this stream was created on has been destroyed");
     if (ragged_call && !h->fe->use_fft) return frontend_needs_fft400(h->fe, "per-stream chunk lengths");
     if (ragged_call && !frontend_takes_fft400(h->fe, h->B, h->tmax))
         return fail(KWS_ERR_UNSUPPORTED, "B*T=%lld frames exceed the ragged front-end's grid", (long long)h->B * h->tmax);
@@ -158,10 +160,12 @@ int with_model_held(kws_stream_handle h, void* stream, const char* what, F&& bod
     return rc != KWS_OK ? rc : rl;
 }
 
-// kws_stream_create (window2 == null) and kws_stream_create_heads (`who` names the entry point in the refusals)
-int stream_create_impl(const char* who, kws_handle model, kws_frontend_handle frontend, kws_window_handle window, kws_window_handle window2,
-                       int B, int max_chunk_samples, float vad_thres, const char* label, const char* label2, float* state, uint8_t* restart,
-                       kws_stream_handle* out) {
+}  // namespace
+
+// kws_stream_create (window2 == null), kws_stream_create_heads and kws_stream_create_bank (`who` names the entry point in the refusals)
+int kws_host::stream_create_impl(const char* who, kws_handle model, kws_frontend_handle frontend, kws_window_handle window,
+                                 kws_window_handle window2, int B, int max_chunk_samples, float vad_thres, const char* label, const char* label2,
+                                 float* state, uint8_t* restart, kws_stream_handle* out, kws_bank* bank, const int32_t* user) {
     if (!out) return fail(KWS_ERR_INVALID_ARGUMENT, "out handle pointer is null");
     *out = nullptr;
     if (!model || !frontend || !window || !state || !restart || !label) return fail(KWS_ERR_INVALID_ARGUMENT, "null argument");
@@ -192,7 +196,7 @@ int stream_create_impl(const char* who, kws_handle model, kws_frontend_handle fr
     if (tmax > window->tmax)
         return fail(KWS_ERR_INVALID_ARGUMENT, "chunks of %d samples give up to %d frames, the window holds %d per chunk", max_chunk_samples,
                     tmax, window->tmax);
-    if (window2) KWS_TRY(heads_window_check(model, window, window2, B, tmax));      // both windows' class counts, batch, frames; the LDS of the launch
+    if (window2) KWS_TRY(heads_window_check(model, window, window2, B, tmax, bank));      // both windows' class counts, batch, frames; the LDS of the launch
     if (!window2 && window_inc_lds_bytes(tmax, window->nq) > kWindowIncLdsMax)
         return fail(KWS_ERR_UNSUPPORTED, "chunks of up to %d frames with a %d-chunk window need %zu bytes of LDS in the incremental window step "
                     "(limit %zu): use shorter chunks", tmax, window->nq, window_inc_lds_bytes(tmax, window->nq), kWindowIncLdsMax);
@@ -200,6 +204,7 @@ int stream_create_impl(const char* who, kws_handle model, kws_frontend_handle fr
     if (!s) return fail(KWS_ERR_OUT_OF_MEMORY, "host allocation failed");
     s->model_serial = ms; s->fe_serial = fs; s->win_serial = ws;
     s->win2 = window2; s->win2_serial = ws2;
+    s->bank = bank; s->bank_serial = bank ? live_serial(bank) : 0; s->user = user;
     if (window2) memcpy(s->label2, label2, n2);
     s->model = model; s->fe = frontend; s->win = window; s->B = B; s->max_chunk = max_chunk_samples; s->tmax = tmax;
     s->vad_thres = vad_thres; s->state = state; s->restart = restart;
@@ -226,8 +231,6 @@ int stream_create_impl(const char* who, kws_handle model, kws_frontend_handle fr
     *out = s;
     return KWS_OK;
 }
-
-}  // namespace
 
 extern "C" {
 

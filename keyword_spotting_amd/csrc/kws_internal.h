@@ -279,6 +279,28 @@ __host__ __device__ inline size_t heads_window_lds_bytes(int T, int nq1, int nq2
 }
 hipError_t launch_heads_window(const HeadsWindowParams& p, int hidden, hipStream_t st);
 
+// A bank of enrolled heads (bank_heads.hip, bank_device.h): head 2 of stream b is head 1's logits with the n_new columns of bank slot
+// user[b] spliced in front of the blank.  The two kernels keep the grid and phases of dense_heads_kernel / heads_window_kernel; of
+// head[1] they read C (= head 1's C + n_new), the threshold and the outputs -- never wfc / bfc.
+struct BankRef {
+    const float* Wn;        // [capacity][H][n_new]  (the layout kws_enroll_get writes)
+    const float* bn;        // [capacity][n_new]
+    const int32_t* user;    // [B] slot of each stream; outside [0, capacity): the stream has no second head
+    int capacity, n_new;
+};
+struct BankHeadsParams { DenseHeadsParams d; BankRef bank; };       // d.head[0] is always bound (its outputs may all be null)
+struct BankWindowParams { HeadsWindowParams w; BankRef bank; };
+constexpr size_t kBankHeadsLogitsBytes = (size_t)2 * 16 * (kHeadFrames + 1) * 8 * sizeof(float);      // [head 1 | new classes][stream][slot][8]
+constexpr size_t kBankHeadsWordsBytes = (size_t)2 * 16 * (kHeadFrames + 1) * sizeof(int);
+// LDS of a group's staged columns [n_new][H/16][64 lanes][4] and biases [16][8]
+__host__ __device__ inline size_t bank_stage_bytes(int H, int n_new) { return ((size_t)16 * H * n_new + 128) * sizeof(float); }
+__host__ __device__ inline size_t bank_heads_lds_bytes(int H, int n_new) { return kBankHeadsLogitsBytes + kBankHeadsWordsBytes + bank_stage_bytes(H, n_new); }
+__host__ __device__ inline size_t bank_window_lds_bytes(int T, int nq1, int nq2, int H, int n_new) {
+    return heads_window_lds_bytes(T, nq1, nq2) + bank_stage_bytes(H, n_new);
+}
+hipError_t launch_bank_heads(const BankHeadsParams& p, int hidden, hipStream_t st);
+hipError_t launch_bank_heads_window(const BankWindowParams& p, int hidden, hipStream_t st);
+
 // decode window of the stream manager (stream_kernels.hip)
 struct WindowParams {
     int8_t* words;            // [B][nq][tmax] per-frame ctc_decode2 word (-1 none); tmax % 16 == 0

@@ -17,6 +17,14 @@ three utterances with the CTC loss and Adam (models/rnn_ctc.py:59-101):
     new_columns, new_bias, loss_trace = enroller.fit(mel, lengths, labels, steps=100)
 
 The stack runs once (kws_step_heads: nn_outputs and head 1's logits); every optimiser step is inside kws_enroll_fit.
+
+Serving thousands of users who each enrolled their own keyword takes ONE bank of those columns on one frozen model, not a model handle
+per user:
+
+    bank = KeywordBank(model, n_new=2, capacity=4096)
+    bank.set(0, new_columns, new_bias)            # device tensors straight from Enroller.fit: no host copy
+    r = bank.forward(mel, state, users)           # users [B] int32: the slot of each stream (-1: no second head)
+    manager = detector.StreamManager(model, batch, label="12", bank=bank, users=users, label2="56")
 """
 import copy
 import ctypes
@@ -112,15 +120,7 @@ class Enroller(object):
 
     def __init__(self, model, n_new, enrolments=1, utterances_per_enrolment=3):
         cfg = model.config
-        if getattr(model, "num_classes2", 0):
-            raise _lib.InvalidArgumentError(-1, "Enroller takes the one-head model the new head is derived from, not a model that has a second head")
-        if getattr(cfg, "precision", "fp32") != "fp32":
-            raise _lib.UnsupportedError(_lib.KWS_ERR_UNSUPPORTED, "Enroller needs an fp32 model, got precision %r" % cfg.precision)
-        if cfg.use_relu:
-            raise _lib.UnsupportedError(_lib.KWS_ERR_UNSUPPORTED, "Enroller: use_relu / value_clip models are out of scope (the gradient of "
-                                        "TensorFlow's relu and clip at their ties is not pinned)")
-        if any(getattr(model, "wrappers", (False, False))):
-            raise _lib.UnsupportedError(_lib.KWS_ERR_UNSUPPORTED, "Enroller: a second class head has no wrapped form (use_layer_norm / use_residual)")
+        _frozen_model_check("Enroller", model)
         self.n_new, self.enrolments, self.slots = int(n_new), int(enrolments), int(utterances_per_enrolment)
         self.config, self.device = cfg, model.device
         self.num_classes2 = cfg.num_classes + self.n_new
@@ -205,6 +205,104 @@ class Enroller(object):
             out_w, out_b = torch.empty_like(wn), torch.empty_like(bn)
             _lib.check(self._lib.kws_enroll_get(self._handle, _lib.ptr(out_w), _lib.ptr(out_b), stream))
         return out_w, out_b, trace
+
+
+def _frozen_model_check(who, model):
+    """The refusals Enroller and KeywordBank share: the one-head fp32 model without relu / clip and without cell wrappers."""
+    cfg = model.config
+    if getattr(model, "num_classes2", 0):
+        raise _lib.InvalidArgumentError(-1, "%s takes the one-head model the new head is derived from, not a model that has a second head" % who)
+    if getattr(cfg, "precision", "fp32") != "fp32":
+        raise _lib.UnsupportedError(_lib.KWS_ERR_UNSUPPORTED, "%s needs an fp32 model, got precision %r" % (who, cfg.precision))
+    if cfg.use_relu:
+        raise _lib.UnsupportedError(_lib.KWS_ERR_UNSUPPORTED, "%s: use_relu / value_clip models are out of scope (the gradient of "
+                                    "TensorFlow's relu and clip at their ties is not pinned)" % who)
+    if any(getattr(model, "wrappers", (False, False))):
+        raise _lib.UnsupportedError(_lib.KWS_ERR_UNSUPPORTED, "%s: a second class head has no wrapped form (use_layer_norm / use_residual)" % who)
+
+
+class KeywordBank(object):
+    """`capacity` slots of enrolled columns [H, n_new] + bias [n_new] on the device for one frozen one-head fp32 model (kws_bank):
+    stream b of a step or a stream manager projects its new classes with the columns of slot users[b].  Every slot is zero at creation.
+
+    Like Enroller the bank builds a heads handle of its own from the model's weights (DeployModel.weights_blob) -- `stack`, whose plan
+    and seams serve the bank step; its own second head (zero new columns) is never read by a bank call."""
+
+    def __init__(self, model, n_new, capacity, kernel="auto"):
+        _frozen_model_check("KeywordBank", model)
+        cfg = model.config
+        self.n_new, self.capacity = int(n_new), int(capacity)
+        if self.n_new < 1 or cfg.num_classes + self.n_new > 8:
+            raise _lib.InvalidArgumentError(-1, "n_new=%d: the extended head has num_classes + n_new <= 8 classes" % self.n_new)
+        if self.capacity < 1:
+            raise _lib.InvalidArgumentError(-1, "capacity=%d slots: at least one" % self.capacity)
+        self.config, self.device = cfg, model.device
+        self.model = model               # the one-head model the bank was built on (StreamManager / HotwordDetector check it)
+        self.num_classes2 = cfg.num_classes + self.n_new
+        self._lib = _lib.load()
+        self._handle = ctypes.c_void_p()
+        import torch
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_bank_create(cfg.hidden_size, cfg.num_classes, self.n_new, self.capacity, ctypes.byref(self._handle)))
+        from .rnn_ctc import DeployModel
+        w = dict(_weights.from_blob(cfg, model.weights_blob))
+        zeros = np.zeros((cfg.hidden_size, self.n_new), np.float32)
+        w["Wfc2"], w["bfc2"] = _weights.extend_head(w["Wfc"], w["bfc"], zeros, zeros[0])
+        cfg2 = copy.copy(cfg)
+        cfg2.num_classes2 = self.num_classes2
+        self.stack = DeployModel(cfg2, w, device=str(self.device), kernel=kernel)      # kernel: DeployModel's kernel family switch
+
+    def close(self):
+        if getattr(self, "_handle", None) is not None and self._handle.value:
+            self._lib.kws_bank_destroy(self._handle)
+            self._handle = ctypes.c_void_p()
+        if getattr(self, "stack", None) is not None:
+            self.stack.close()
+            self.stack = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _slots(self, columns, bias):
+        import torch
+        wn = torch.as_tensor(columns).to(device=self.device, dtype=torch.float32).contiguous()
+        bn = torch.as_tensor(bias).to(device=self.device, dtype=torch.float32).contiguous()
+        if wn.dim() == 2:
+            wn, bn = wn.unsqueeze(0), bn.reshape(1, -1)
+        h, n = self.config.hidden_size, self.n_new
+        if wn.dim() != 3 or tuple(wn.shape[1:]) != (h, n) or tuple(bn.shape) != (wn.shape[0], n):
+            raise _lib.InvalidArgumentError(-1, "columns / bias must be [count,%d,%d] / [count,%d], got %s %s" % (h, n, n, tuple(wn.shape), tuple(bn.shape)))
+        return wn, bn
+
+    def set(self, first, columns, bias):
+        """Slots first .. first+count-1 <- columns [count,H,n_new], bias [count,n_new] (device tensors or arrays, e.g. straight from
+        Enroller.fit; one slot may come as [H,n_new], [n_new]).  Stream-ordered on the current stream (kws_bank_set)."""
+        import torch
+        wn, bn = self._slots(columns, bias)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_bank_set(self._handle, int(first), int(wn.shape[0]), _lib.ptr(wn), _lib.ptr(bn), _lib.current_stream_ptr()))
+        return self
+
+    def get(self, first=0, count=None):
+        """-> (columns [count,H,n_new], bias [count,n_new]) device tensors: the slots as the bank holds them (kws_bank_get)."""
+        import torch
+        count = self.capacity - int(first) if count is None else int(count)
+        wn = torch.empty(max(count, 0), self.config.hidden_size, self.n_new, dtype=torch.float32, device=self.device)
+        bn = torch.empty(max(count, 0), self.n_new, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_bank_get(self._handle, int(first), count, _lib.ptr(wn), _lib.ptr(bn), _lib.current_stream_ptr()))
+        return wn, bn
+
+    def zero_state(self, batch=1):
+        return self.stack.zero_state(batch)
+
+    def forward(self, inputs, state, users, seq_len=None, heads=(1, 2), **kw):
+        """DeployModel.forward_heads with head 2 of stream b from slot users[b] (kws_step_bank): the same dict, head2 rows of
+        num_classes + n_new classes.  users [B] int32, host or device; outside [0, capacity) (-1): no second head for that stream."""
+        return self.stack.forward_heads(inputs, state, seq_len=seq_len, heads=heads, bank=self, users=users, **kw)
 
 
 def enroll(model, utterances, label, n_new, steps=300, lr=1.5e-3, init=None, seed=0):

@@ -70,9 +70,32 @@ def _second_head(model, label2, decode_thres2, decode_thres):
     return str(label2), float(decode_thres if decode_thres2 is None else decode_thres2)
 
 
+def _bank_model(model, bank, users, label2, batch):
+    """(model to step, users [batch] int32 on its device) of a detector / manager whose head 2 comes from a custom_keyword.KeywordBank:
+    the bank's own heads stack stands in for `model` (the same weights, a second head of num_classes + n_new classes).  `model` has to
+    be the one-head model the bank was built on (bank.model), or None for "the bank's"; any other model is refused.  bank None:
+    (model, None)."""
+    if bank is None:
+        if users is not None:
+            raise _lib.InvalidArgumentError(-1, "users needs bank")
+        return model, None
+    if users is None or label2 is None:
+        raise _lib.InvalidArgumentError(-1, "bank needs users (the slot of each stream) and label2 (the new words' pattern)")
+    if model is not None and model is not getattr(bank, "model", None):
+        raise _lib.InvalidArgumentError(-1, "model is not the model this bank was built on (pass bank.model, or None)")
+    users = torch.as_tensor(users)
+    if users.dtype.is_floating_point or tuple(users.shape) != (batch,):
+        raise _lib.InvalidArgumentError(-1, "users must be [%d] integers, got %s %s" % (batch, users.dtype, list(users.shape)))
+    return bank.stack, users.to(bank.device, torch.int32).contiguous()
+
+
 class HotwordDetector(object):
     def __init__(self, model, batch=1, window_chunks=15, vad_thres=30, label=None, decode_thres=0.4,
-                 detected_callback=None, label2=None, decode_thres2=None):
+                 detected_callback=None, label2=None, decode_thres2=None, bank=None, users=None):
+        # head 2 per stream from a bank of enrolled columns: the host mirror of StreamManager(bank=..., users=...); a stream with
+        # user -1 has all-zero softmax2 rows, which decode to nothing -- a plain detector
+        model, self.users = _bank_model(model, bank, users, label2, int(batch))
+        self.bank = bank
         self.model = model
         self.config = model.config
         self.batch = int(batch)
@@ -152,7 +175,7 @@ class HotwordDetector(object):
         """The loop body for both heads (the VAD part is done): the stack once, head k's softmax into queue k, each window decoded
         at its own threshold against its own label; a hit of either head clears both queues and restarts the state."""
         r = self.model.forward_heads(mel, self.state, reset_mask=self.reset_next, want_nn_outputs=False, want_logits=False,
-                                     state_out=self.state)
+                                     state_out=self.state, bank=self.bank, users=self.users)
         self.reset_next.zero_()
         sm1, sm2 = r["head1"]["softmax"], r["head2"]["softmax"]
         for b in range(self.batch):
@@ -268,11 +291,20 @@ class StreamManager(object):
     threshold decode_thres2, default decode_thres), the stack run once, ONE launch behind it for both projections, both windows
     and the coupled clear + restart (kws_stream_create_heads / kws_step_heads_window; front-end + L layers + 1 launches per chunk).
     hit carries hit_1 | hit_2 << 1: non-zero = detected.  Identical to HotwordDetector(label2=...) (tests/test_gpu_heads_stream.py).
-    Without label2 the manager is what it always was, on a two-head model too: head 1 through the fused tail."""
+    Without label2 the manager is what it always was, on a two-head model too: head 1 through the fused tail.
+
+    bank (custom_keyword.KeywordBank) with users [B] and label2: per-user customised keywords on one manager -- head 2 of stream b is
+    projected with the columns of bank slot users[b] (kws_stream_create_bank / kws_step_bank_window), everything else as with label2
+    alone; `model` is the one-head model the bank was built on, the manager runs on the bank's own heads stack.  self.users is the
+    device tensor the feeds read: rewrite users[b] in place when a slot is recycled for a new client (-1: no second head).  One label2
+    serves the whole manager: with a fixed n_new every user's new words are classes C-1 .. C+n_new-2 over their own columns.
+    Identical to HotwordDetector(bank=..., users=..., label2=...) (tests/test_gpu_bank_stream.py)."""
 
     def __init__(self, model, batch, window_chunks=15, max_frames=32, vad_thres=30, label=None, decode_thres=0.4, label2=None,
-                 decode_thres2=None):
+                 decode_thres2=None, bank=None, users=None):
         import ctypes
+        model, self.users = _bank_model(model, bank, users, label2, int(batch))
+        self.bank = bank
         self.model, self.config, self.batch = model, model.config, int(batch)
         self.vad_thres, self.decode_thres = vad_thres, decode_thres
         self.label = (label or self.config.label_seqs).encode()
@@ -349,8 +381,10 @@ class StreamManager(object):
             raise _lib.InvalidArgumentError(-1, "mel must be [%d,T,%d], got %s" % (self.batch, cfg.n_mel, tuple(mel.shape)))
         t = int(mel.shape[1])
         with torch.cuda.device(model.device):
-            _lib.check(self._lib.kws_step_heads_window(
-                model._handle, _lib.ptr(mel), _lib.ptr(self.state), _lib.ptr(self.state), _lib.ptr(reset), self.batch, t,
+            step = self._lib.kws_step_heads_window if self.bank is None else self._lib.kws_step_bank_window
+            lead = (model._handle,) if self.bank is None else (model._handle, self.bank._handle, _lib.ptr(self.users))
+            _lib.check(step(
+                *lead, _lib.ptr(mel), _lib.ptr(self.state), _lib.ptr(self.state), _lib.ptr(reset), self.batch, t,
                 self._wins[0], self._wins[1], self.label, self.label2, _lib.ptr(silent), None, None,
                 _lib.ptr(self.hit), _lib.ptr(self.restart), _lib.current_stream_ptr()))
         return self.hit
@@ -429,7 +463,10 @@ class StreamManager(object):
                 # (model, front-end, window per head, B, samples, vad, label per head, state, restart, out)
                 create = self._lib.kws_stream_create if len(self._wins) == 1 else self._lib.kws_stream_create_heads
                 labels = [self.label, self.label2][:len(self._wins)]
-                _lib.check(create(self.model._handle, frontend._handle, *self._wins, self.batch, self.max_frames * int(self.config.hop_size),
+                bank = ()
+                if self.bank is not None:
+                    create, bank = self._lib.kws_stream_create_bank, (self.bank._handle, _lib.ptr(self.users))
+                _lib.check(create(self.model._handle, frontend._handle, *self._wins, *bank, self.batch, self.max_frames * int(self.config.hop_size),
                                   float(self.vad_thres), *labels, _lib.ptr(self.state), _lib.ptr(self.restart), ctypes.byref(self._stream)))
             self._stream_frontend, self._stream_fe_handle = frontend, frontend._handle.value
         return self._stream

@@ -211,18 +211,26 @@ class DeployModel(object):
         return res
 
     def forward_heads(self, mel, state, seq_len=None, reset_mask=None, heads=(1, 2), want_nn_outputs=True, want_logits=True,
-                      want_softmax=True, prev_words=None, decode2_thres=(0.4, 0.4), state_out=None):
+                      want_softmax=True, prev_words=None, decode2_thres=(0.4, 0.4), state_out=None, bank=None, users=None):
         """One sess.run of a customised-keyword graph on B streams (kws_step_heads): the GRU stack once, then both dense layers
         on the top layer's rows.  Returns {'state', 'nn_outputs' [B,T,H], 'head1': {...}, 'head2': {...}} with each requested
         head's 'logits' / 'softmax' [B,T,C_i] and, if prev_words = (pw1, pw2) is given (either may be None), its 'tokens' [B,T]
-        (that prev_word is updated in place).  heads: which of the two to compute."""
+        (that prev_word is updated in place).  heads: which of the two to compute.
+        bank (custom_keyword.KeywordBank) with users [B] int32: head 2 of stream b comes from bank slot users[b] (kws_step_bank) and has
+        num_classes + bank.n_new classes; a stream whose user is outside [0, capacity) has no second head (zero rows, no word)."""
         if not self.num_classes2:
             raise _lib.InvalidArgumentError(-1, "forward_heads needs a model with a second head (config.num_classes2)")
         cfg = self.config
         mel, state, seq_len, reset_mask, b, t = self._step_inputs(mel, state, seq_len, reset_mask)
+        if (bank is None) != (users is None):
+            raise _lib.InvalidArgumentError(-1, "bank and users go together")
+        if bank is not None:
+            users = self._dev(users, torch.int32, "users")
+            if tuple(users.shape) != (b,):
+                raise _lib.InvalidArgumentError(-1, "users must have shape [%d], got %s" % (b, list(users.shape)))
         prev_words = tuple(prev_words) if prev_words is not None else (None, None)
         res, ios, keep = {}, [None, None], []
-        for i, c in enumerate((cfg.num_classes, self.num_classes2)):
+        for i, c in enumerate((cfg.num_classes, self.num_classes2 if bank is None else cfg.num_classes + bank.n_new)):
             if i + 1 not in heads:
                 continue
             out = {}
@@ -245,8 +253,10 @@ class DeployModel(object):
         if state_out is None:
             state_out = torch.empty_like(state)
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_step_heads(
-                self._handle, _lib.ptr(mel), _lib.ptr(state), _lib.ptr(state_out), _lib.ptr(seq_len), _lib.ptr(reset_mask),
+            step = self._lib.kws_step_heads if bank is None else self._lib.kws_step_bank
+            lead = (self._handle,) if bank is None else (self._handle, bank._handle, _lib.ptr(users))
+            _lib.check(step(
+                *lead, _lib.ptr(mel), _lib.ptr(state), _lib.ptr(state_out), _lib.ptr(seq_len), _lib.ptr(reset_mask),
                 _lib.ptr(nn_outputs), ctypes.byref(ios[0]) if ios[0] is not None else None,
                 ctypes.byref(ios[1]) if ios[1] is not None else None, b, t, _lib.current_stream_ptr()))
         res["state"] = state_out

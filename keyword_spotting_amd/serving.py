@@ -22,7 +22,7 @@ from .rnn_ctc import DeployModel
 
 class StreamServer(object):
     def __init__(self, config, weights=None, device="cuda:0", streams_per_manager=16384, handles=2, label=None,
-                 window_chunks=15, max_frames=32, vad_thres=30, decode_thres=0.4, label2=None, decode_thres2=None):
+                 window_chunks=15, max_frames=32, vad_thres=30, decode_thres=0.4, label2=None, decode_thres2=None, bank=None, users=None):
         self.config, self.device = config, torch.device(device)
         self.streams_per_manager = int(streams_per_manager)
         w = weights if weights is not None else _weights.init_weights(config, seed=0)
@@ -33,6 +33,14 @@ class StreamServer(object):
                               decode_thres=decode_thres)
         if label2 is not None:          # a customised-keyword model: every manager decodes both heads (StreamManager; hits() = hit_1 | hit_2 << 1)
             self._mgr_args.update(label2=label2, decode_thres2=decode_thres2)
+        # per-user customised keywords (StreamManager(bank=, users=)): one custom_keyword.KeywordBank per model handle (or one for a
+        # single handle), and users(k) -> the [streams_per_manager] slot indices of manager k
+        if (bank is None) != (users is None):
+            raise ValueError("bank and users go together")
+        self._banks = None if bank is None else (list(bank) if isinstance(bank, (list, tuple)) else [bank])
+        if self._banks is not None and len(self._banks) != len(self.models):
+            raise ValueError("one bank per model handle: %d banks for %d handles" % (len(self._banks), len(self.models)))
+        self._users = users
         self.managers = []
 
     # -- population ----------------------------------------------------------------------------------------------------
@@ -43,7 +51,8 @@ class StreamServer(object):
         with torch.cuda.device(self.device):
             while len(self.managers) < n_managers:
                 k = len(self.managers)
-                self.managers.append(StreamManager(self.models[k % len(self.models)], self.streams_per_manager, **self._mgr_args))
+                extra = {} if self._banks is None else dict(bank=self._banks[k % len(self.models)], users=self._users(k))
+                self.managers.append(StreamManager(self.models[k % len(self.models)], self.streams_per_manager, **self._mgr_args, **extra))
         # the managers' zeroed state was queued on the creating thread's current stream; the feeds run on the server's own
         torch.cuda.current_stream(self.device).synchronize()
         return self
