@@ -114,6 +114,7 @@ __device__ __forceinline__ void lds_barrier() {
 // over the whole group instead of stalling three waves behind one.
 //   pstage [4 waves][16 streams][8]     lring [16 frames][16 streams][8]
 //   words  [16 frames][16 streams]      carry [2][16]   (previous block's last word, ping-pong)
+// (The fp32 resident kernels have an epilogue of their own without the fold: epilogue_flush_partials, below.)
 // ------------------------------------------------------------------------------------------------
 constexpr int kRingFrames = 16;
 constexpr int xs_stride(int kcx) { return 4 * ((((kcx + 3) / 4) & 1) ? (kcx + 3) / 4 : (kcx + 3) / 4 + 1); }
@@ -142,23 +143,6 @@ __device__ __forceinline__ void epilogue_fold(const EpilogueLds& e, int t, int l
         f32x4 v = *reinterpret_cast<const f32x4*>(e.pstage + (0 * 16 + s) * 8 + 4 * half);
 #pragma unroll
         for (int w = 1; w < 4; ++w) v += *reinterpret_cast<const f32x4*>(e.pstage + (w * 16 + s) * 8 + 4 * half);
-        *reinterpret_cast<f32x4*>(e.lring + (((t & (kRingFrames - 1)) * 16 + s) * 8 + 4 * half)) = v;
-    }
-}
-
-// the same fold in two halves, so the LDS round trip can sit behind independent MFMAs
-struct FoldRegs { f32x4 v[4]; };
-__device__ __forceinline__ void epilogue_fold_load(const EpilogueLds& e, int lane, FoldRegs& r) {
-    if (lane < 32) {
-        const int s = lane >> 1, half = lane & 1;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) r.v[w] = *reinterpret_cast<const f32x4*>(e.pstage + (w * 16 + s) * 8 + 4 * half);
-    }
-}
-__device__ __forceinline__ void epilogue_fold_store(const EpilogueLds& e, int t, int lane, const FoldRegs& r) {
-    if (lane < 32) {
-        const int s = lane >> 1, half = lane & 1;
-        const f32x4 v = ((r.v[0] + r.v[1]) + r.v[2]) + r.v[3];        // same order as epilogue_fold
         *reinterpret_cast<f32x4*>(e.lring + (((t & (kRingFrames - 1)) * 16 + s) * 8 + 4 * half)) = v;
     }
 }
@@ -254,6 +238,109 @@ __device__ __forceinline__ void epilogue_flush(const GruLayerParams& p, const Ep
         else if (b < p.B && p.prev_word) p.prev_word[b] = word;
     }
     if (mine && p.tokens) p.tokens[row] = (int8_t)token;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Last-layer epilogue of the resident kernels (gru_resident.hip): no per-frame fold and no barrier of its own.
+//   partials [kRingFrames][4 waves][16 streams][8] (+ 4 floats per frame, below)
+// Every wave writes the partial logits of frame t into slot t & 15 ahead of the frame's second barrier.  In the flush wave w
+// takes streams 4w..4w+3 x 16 frames, lane = 16 * (stream in wave) + frame: it adds the four partials in the order of
+// epilogue_fold, ((p0 + p1) + p2) + p3, and goes on exactly as epilogue_flush does.  A 16-lane row is one stream in frame order,
+// so the previous frame's word is the lane below (row_shr:1) and the word carried from the block before is a register of the
+// row (`carry`: set from prev_word at the top of a group, refreshed here from the row's last valid frame).
+// Why it needs no barrier: the second barrier of frame t has published every partial of the block that the flush behind it
+// reads, and a slot is next written behind the FIRST barrier of the following frame, which no wave passes before every wave
+// has left this flush; the last block of a group is followed by the group's closing __syncthreads() in the same way.
+// The frame slots are 4 floats longer than their contents: the flush reads 16 frames of one stream with one ds_read_b128
+// lane group, and whole slots of 2 KiB would put all 16 on the same four banks.
+// ------------------------------------------------------------------------------------------------
+constexpr int kPartialSlotFloats = 4 * 16 * 8 + 4;
+constexpr size_t kPartialRingLdsBytes = (size_t)kRingFrames * kPartialSlotFloats * 4;
+__device__ __forceinline__ float* partial_slot(float* ring, int t) { return ring + (t & (kRingFrames - 1)) * kPartialSlotFloats; }
+
+// flush frames [t0, t0+n) of the partial ring; called by all four waves of the group together, every lane active.
+// cwords: the window tail's [16 streams][kWinTailWordsStride] frame words of the whole call, or nullptr.
+// (Everything derived from the lane index comes from an opaque copy of it, as in epilogue_flush<true>: hoisted out of the frame
+// loop those values would take registers the loop has not got.)
+__device__ __forceinline__ void epilogue_flush_partials(const GruLayerParams& p, const float* ring, int8_t* cwords, int group,
+                                                        int t0, int n, int w, int lane, bool final_flush, int& carry) {
+    asm volatile("" : "+v"(lane));
+    const int f = lane & 15;                   // frame within the block
+    const int s = 4 * w + (lane >> 4);
+    const int b = group * kStreamsPerGroup + s;
+    const int C = p.C;
+    float lg[kMaxClasses];
+    {
+        const f32x4* row = reinterpret_cast<const f32x4*>(ring + f * kPartialSlotFloats + s * 8);
+        f32x4 lo = row[0], hi = row[1];
+#pragma unroll
+        for (int k = 1; k < 4; ++k) { lo += row[k * 32]; hi += row[k * 32 + 1]; }      // wave k's partial: 16 streams x 8 floats on
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { lg[c] = lo[c]; lg[4 + c] = hi[c]; }
+    }
+    if (p.use_relu) {
+#pragma unroll
+        for (int c = 0; c < kMaxClasses; ++c) {
+            lg[c] = fmaxf(lg[c], 0.f);
+            if (p.value_clip > 0.f) lg[c] = fminf(lg[c], 20.f);
+        }
+    }
+    float m = lg[0];
+#pragma unroll
+    for (int c = 1; c < kMaxClasses; ++c) m = (c < C) ? fmaxf(m, lg[c]) : m;
+    float pr[kMaxClasses];
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < kMaxClasses; ++c) {
+        pr[c] = (c < C) ? __expf(lg[c] - m) : 0.f;     // arguments <= 0: abs error < 1e-7
+        sum += pr[c];
+    }
+    const float inv = __builtin_amdgcn_rcpf(sum);
+#pragma unroll
+    for (int c = 0; c < kMaxClasses; ++c) pr[c] *= inv;
+    // ctc_decode2 frame rule over classes 1..C-2 (utils/prediction.py:67,74-75): first maximum, strict >
+    int word = -1;
+    float best = -1.f;
+#pragma unroll
+    for (int c = 1; c < kMaxClasses - 1; ++c) {
+        if (c < C - 1 && pr[c] > best) { best = pr[c]; word = c - 1; }
+    }
+    if (!(best > p.decode_thres)) word = -1;
+    if (cwords != nullptr && f < n) cwords[s * kWinTailWordsStride + t0 + f] = (int8_t)word;
+    const bool mine = b < p.B && f < n;
+    const size_t row = (size_t)b * (p.t_stride ? p.t_stride : p.T) + (t0 + f);
+    if (mine) {
+        if (C == 6) {       // rows are 24 B: three 8-byte stores
+            if (p.logits) {
+                float2* o = reinterpret_cast<float2*>(p.logits + row * 6);
+                o[0] = make_float2(lg[0], lg[1]); o[1] = make_float2(lg[2], lg[3]); o[2] = make_float2(lg[4], lg[5]);
+            }
+            if (p.softmax) {
+                float2* o = reinterpret_cast<float2*>(p.softmax + row * 6);
+                o[0] = make_float2(pr[0], pr[1]); o[1] = make_float2(pr[2], pr[3]); o[2] = make_float2(pr[4], pr[5]);
+            }
+        } else {
+            if (p.logits) {
+#pragma unroll
+                for (int c = 0; c < kMaxClasses; ++c)
+                    if (c < C) p.logits[row * C + c] = lg[c];
+            }
+            if (p.softmax) {
+#pragma unroll
+                for (int c = 0; c < kMaxClasses; ++c)
+                    if (c < C) p.softmax[row * C + c] = pr[c];
+            }
+        }
+    }
+    // row_shr:1 -- lane f takes the word of lane f - 1 of its row; the row's first lane has no source and keeps `carry`
+    const int prev = __builtin_amdgcn_update_dpp(carry, word, 0x111, 0xf, 0xf, false);
+    const int token = (word >= 0 && word != prev) ? word + 1 : 0;   // utils/prediction.py:76-80
+    if (mine && p.tokens) p.tokens[row] = (int8_t)token;
+    if (final_flush) {
+        if (f == n - 1 && b < p.B && p.prev_word) p.prev_word[b] = word;
+    } else {
+        carry = __builtin_amdgcn_ds_bpermute(((lane & 48) + n - 1) << 2, word);     // the row's last frame, to every lane of the row
+    }
 }
 
 

@@ -43,11 +43,11 @@ constexpr int resident_kreg(int kcx, bool first, bool last, bool window) { retur
 constexpr int resident_kreg(int, bool first, bool, bool) { return first ? 0 : 2; }
 #endif
 // LDS of one workgroup: hbuf | rhbuf | the gate x-part chunks that are not in registers | upper layers: the x block |
-// last layer: the epilogue | first layer: the mel frame.  (The window tail adds kWinTailWordsBytes behind that.)
+// last layer: the partial-logit ring | first layer: the mel frame.  (The window tail adds kWinTailWordsBytes behind that.)
 constexpr size_t resident_lds_bytes(int kcx, bool first, bool last, bool window) {
     size_t n = 2 * 8 * 64 * 16 + (size_t)4 * (kcx - resident_kreg(kcx, first, last, window)) * 64 * 16;
     if (!first) n += 8 * 64 * 16;
-    if (last) n += kEpilogueLdsBytes;
+    if (last) n += kPartialRingLdsBytes;
     if (first) n += (size_t)64 * xs_stride(kcx) * 4;
     return n;
 }
@@ -88,15 +88,15 @@ __device__ __forceinline__ void gru_layer_resident_body(const GruLayerParams& p)
     f32x4* xsb = wlds + 4 * KL * 64;                     // [NT][64]  upper layers: x(t+1) of the group, xl layout (see "x stream")
     char* const lds_tail = reinterpret_cast<char*>(xsb + (FIRST ? 0 : NT * 64));
     static_assert(resident_lds_bytes(KCX, FIRST, LAST, WINDOW) + (WINDOW ? kWinTailWordsBytes : 0) <= 160 * 1024, "LDS per CU");
-    EpilogueLds epi = epilogue_carve(lds_tail);          // LAST only
-    if constexpr (WINDOW) epi.cwords = reinterpret_cast<int8_t*>(lds_tail + kEpilogueLdsBytes);
-    const uint8_t* win_dl = reinterpret_cast<const uint8_t*>(epi.cwords) + 16 * kWinTailWordsStride;     // WINDOW only: the label matcher
+    float* const pring = reinterpret_cast<float*>(lds_tail);     // LAST only: the partial logits of 16 frames (gru_device.h)
+    int8_t* const cwords = WINDOW ? reinterpret_cast<int8_t*>(lds_tail + kPartialRingLdsBytes) : nullptr;
+    const uint8_t* win_dl = reinterpret_cast<const uint8_t*>(cwords) + 16 * kWinTailWordsStride;     // WINDOW only: the label matcher
     constexpr size_t kWinOffset = offsetof(GruLayerParams, win);
     if constexpr (WINDOW) window_tail_prepare(window_tail_params_from_kernarg(kWinOffset), const_cast<uint8_t*>(win_dl), tid);   // (visible after the group loop's first barrier)
     // FIRST only: one frame of mel for the group, [16 streams x 4 lane groups][kXsStride] floats, row
     // (4s+g) holds x[s][4*kc+g] for kc = 0..KCX-1 -- each lane's B operands are contiguous
     constexpr int kXsStride = xs_stride(KCX);       // 4 * odd: rows 16 apart in one ds_read_b128 group spread over the banks
-    float* xs = reinterpret_cast<float*>(lds_tail + (LAST ? kEpilogueLdsBytes : 0));
+    float* xs = reinterpret_cast<float*>(lds_tail + (LAST ? kPartialRingLdsBytes : 0));
 
     // ---- stage weights: registers (recurrent + candidate) and LDS (gate x-part) ------------------
     // p.wh is the group-of-4 layout [NT][3][KCH/4][64][4]: one dwordx4 per four fragments.  p.wx is the
@@ -201,6 +201,7 @@ __device__ __forceinline__ void gru_layer_resident_body(const GruLayerParams& p)
 
     // ---- per-group state: set by enter_group() -----------------------------------------------------
     int len_s = T;                       // MASKED only
+    int carry = -1;                      // LAST only: the word before the flush's next block, of this lane's stream there (4w + lane / 16)
     f32x4 hreg[2];
     const float4* xl_src = nullptr;
     const float4* xprev = nullptr;
@@ -221,11 +222,10 @@ __device__ __forceinline__ void gru_layer_resident_body(const GruLayerParams& p)
             hreg[j] = do_reset ? splat4(0.f) : ld4(p.state_in + (size_t)b * H + n * 16 + 4 * g);
             hbuf[n * 64 + lane] = hreg[j];
         }
-        if (LAST && tid < 16) {
-            const int bb = group * kStreamsPerGroup + tid;
-            int pw = -1;
-            if (bb < p.B && p.prev_word && !(p.reset && p.reset[bb])) pw = p.prev_word[bb];
-            epi.carry[tid] = pw;          // block 0 reads carry[0][.]
+        if (LAST) {
+            const int bb = group * kStreamsPerGroup + 4 * w + (lane >> 4);
+            carry = -1;
+            if (bb < p.B && p.prev_word && !(p.reset && p.reset[bb])) carry = p.prev_word[bb];
         }
         if constexpr (FIRST) {
             const int xl_b = min(group * kStreamsPerGroup + 4 * w + (xl_active ? xl_row : 0), p.B - 1);
@@ -471,33 +471,32 @@ __device__ __forceinline__ void gru_layer_resident_body(const GruLayerParams& p)
                     make_float4(o[0], o[1], o[2], o[3]);
             }
         }
-        if (LAST) {
-            // partial logits over this wave's 32 units: Wfc^T[:, units] h'[units]
+        if constexpr (LAST) {
+            // partial logits over this wave's 32 units, Wfc^T[:, units] h'[units], into the frame's slot of the ring (gru_device.h).
+            // The fence keeps region B one VALU run: without it single logit MFMAs move up between the ops of the state update
+            // and split its packed multiplies and adds
+            __builtin_amdgcn_sched_barrier(0);
             f32x4 accf = bfc4;
 #pragma unroll
             for (int j = 0; j < 2; ++j)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) accf = mfma4(wfc[j][e], MASKED ? hout[j][e] : hreg[j][e], accf);
-            if (g < 2) *reinterpret_cast<f32x4*>(epi.pstage + (w * 16 + s) * 8 + 4 * g) = accf;
+            if (g < 2) *reinterpret_cast<f32x4*>(partial_slot(pring, t) + (w * 16 + s) * 8 + 4 * g) = accf;
         }
         __builtin_amdgcn_sched_barrier(0);
         static_for<0, NPRE>(cand_x_mfma);     // most of frame t+1's candidate x-part covers the LDS write
         __builtin_amdgcn_sched_barrier(0);
-        lds_barrier();           // #2: h_t visible; every wave is done reading rhbuf
+        lds_barrier();           // #2: h_t and the frame's partial logits visible; every wave is done reading rhbuf
         hb_a = hbuf[0 * 64 + lane];
         hb_b = hbuf[1 * 64 + lane];
-        FoldRegs fold;
-        const bool folder = LAST && w == (t & 3);
-        if (folder) epilogue_fold_load(epi, lane, fold);      // LDS reads in flight behind the MFMAs below
         __builtin_amdgcn_sched_barrier(0);
         static_for<NPRE, NCX>(cand_x_mfma);   // the rest of frame t+1's candidate x-part hides the hbuf read
         __builtin_amdgcn_sched_barrier(0);
-        if (LAST) {
-            if (folder) epilogue_fold_store(epi, t, lane, fold);
+        if constexpr (LAST) {
+            // every 16 frames and at the end of the call: no barrier, see epilogue_flush_partials
             if (((t + 1) & (kRingFrames - 1)) == 0 || t == T - 1) {
                 const int t0 = t & ~(kRingFrames - 1);
-                lds_barrier();                       // the fold of frame t is visible to every wave
-                epilogue_flush(p, epi, group, t0, t - t0 + 1, w, lane, t == T - 1);
+                epilogue_flush_partials(p, pring, cwords, group, t0, t - t0 + 1, w, lane, t == T - 1, carry);
             }
         }
     };
@@ -512,7 +511,7 @@ __device__ __forceinline__ void gru_layer_resident_body(const GruLayerParams& p)
             group_commit();
         }
     }
-    __syncthreads();             // staged weights (first group) / this group's state, carry and x(1) are in LDS
+    __syncthreads();             // staged weights (first group) / this group's state and x(1) are in LDS
     if (T > 0) {
         if constexpr (FIRST) {
             coop_issue(0);
@@ -543,11 +542,11 @@ __device__ __forceinline__ void gru_layer_resident_body(const GruLayerParams& p)
     }
     __syncthreads();             // every wave is done with this group's LDS state before the next group overwrites it
     if constexpr (WINDOW) {
-        // detector.py:195-209 for this group's 16 streams: the call's frame words wait in epi.cwords, the scratch is hbuf | rhbuf
+        // detector.py:195-209 for this group's 16 streams: the call's frame words wait in cwords, the scratch is hbuf | rhbuf
         const WindowTail win = window_tail_params_from_kernarg(kWinOffset);
         WindowTailRegs<2> wreq;
         window_tail_request<2>(win, p.B, group * kStreamsPerGroup, tid, wreq);
-        window_tail<2>(win, p.B, group * kStreamsPerGroup, T, epi.cwords, kWinTailWordsStride, win_dl, reinterpret_cast<char*>(hbuf), tid, wreq);
+        window_tail<2>(win, p.B, group * kStreamsPerGroup, T, cwords, kWinTailWordsStride, win_dl, reinterpret_cast<char*>(hbuf), tid, wreq);
         __syncthreads();
     }
     }
