@@ -554,18 +554,35 @@ int kws_enroll_stats(kws_enroll_handle h, size_t* device_bytes, int32_t* allocs,
  *                     borrowed like state / restart -- the caller rewrites user[b] on the device when a slot is recycled for a new
  *                     client.  The policy is kws_stream_create_heads' unchanged (silence clears both windows and resets the state;
  *                     fired = hit_1 | hit_2 clears both and requests the restart; hit[b] = hit_1 | hit_2 << 1; a zero-frame chunk puts
- *                     an empty entry into both windows; a skipped stream of the ragged feed gets no slot in either).  ONE label2 is
- *                     bound to window 2 for the whole manager: with a fixed n_new the new words are classes C-1 .. C+n_new-2 for
- *                     every user, so "56" is everybody's keyword pattern over their own columns; users whose keyword has another word
- *                     pattern belong to another manager.  The handle is a stream handle (kws_stream_feed / _feed_ragged / _recycle /
+ *                     an empty entry into both windows; a skipped stream of the ragged feed gets no slot in either).  label2 is
+ *                     bound to window 2 and is the pattern of every slot WITHOUT a keyword of its own: with a fixed n_new the new words
+ *                     are classes C-1 .. C+n_new-2 for every user, so "56" is everybody's keyword pattern over their own columns;
+ *                     users whose keyword has another word pattern or fewer new words set it on their slot (kws_bank_set_keyword) and
+ *                     share the manager.  The handle is a stream handle (kws_stream_feed / _feed_ragged / _recycle /
  *                     _carry / _reset / _destroy); recycling does what it does on a heads manager.  The launch stages the group's
  *                     columns (16 H n_new floats + 512 bytes) next to what heads_window_kernel stages: more than 160 KiB of LDS is
  *                     KWS_ERR_UNSUPPORTED with the byte counts.
  *   kws_step_bank_window     kws_step_heads_window with `bank, user` added (mel-fed); softmax2 rows are bitwise kws_step_bank's.
- * One host thread at a time per bank (KWS_ERR_BUSY) in kws_bank_set / _get, kws_step_bank and kws_step_bank_window.  The feeds of a bank
+ *   kws_bank_set_keyword     slot `slot` gets a keyword of its own: its head 2 has C + n_used classes (1 <= n_used <= n_new: trained classes
+ *                     0..C-2, the slot's first n_used columns, the blank), and window 2 of every stream on that slot matches `label`
+ *                     instead of the manager's label2.  logits2 / softmax2 rows keep C + n_new entries, those past C + n_used - 1 are 0;
+ *                     the word and the tokens come from the C + n_used row.  label == NULL: back to "no keyword of its own" (n_used must
+ *                     then be n_new).  Refused before the device is touched (KWS_ERR_INVALID_ARGUMENT): slot outside [0, capacity),
+ *                     n_used outside [1, n_new], a label of more than 15 digits (the matcher has 16 states), a digit outside '1'..'9',
+ *                     a digit d > C + n_used - 2 (a word class the slot's head does not have: it could never fire).  Stream-ordered
+ *                     like kws_bank_set.  From the first keyword on, every launch on the bank takes the keyword form of its kernel --
+ *                     kws_last_launch names bank_keyword_heads_kernel<H/16> / bank_keyword_window_kernel<H/16> -- which stages the group's
+ *                     sixteen matchers (4 KiB + 128 bytes of LDS more; counted in the 160 KiB refusal); a bank on which no keyword
+ *                     was ever set launches the kernels it always did.
+ *   kws_bank_get_keyword     what the slot was last given: *n_used, label[16] ("" and *own = 0 when it has none).  Host state, no device
+ *                     access.
+ * Window 2's chunk summaries are built with the matcher of the moment, which the library cannot check: after rewriting user[b] to a slot
+ * with another keyword, or after kws_bank_set_keyword on a slot that live streams use, the caller recycles those streams
+ * (kws_stream_recycle) before their next feed.
+ * One host thread at a time per bank (KWS_ERR_BUSY) in kws_bank_set / _get / _set_keyword / _get_keyword, kws_step_bank and kws_step_bank_window.  The feeds of a bank
  * manager (kws_stream_feed / _feed_ragged) do NOT take the bank's guard: they only queue launches that read the bank's fixed device
  * block, so a kws_bank_set from another thread is ordered against them by the caller, on the stream, like any other writer of memory
- * a feed reads.  Out of scope: per-stream labels or per-stream n_new, more than two heads, and
+ * a feed reads.  Out of scope: more than two heads, per-user decode thresholds, labels for head 1, and
  * whatever kws_create_heads refuses (f16x3 / bf16 / int8 stacks, the cell wrappers). */
 typedef struct kws_bank* kws_bank_handle;
 int kws_bank_create(int H, int C, int n_new, int capacity, kws_bank_handle* out);
@@ -573,6 +590,8 @@ int kws_bank_destroy(kws_bank_handle bank);   /* always KWS_OK */
 int kws_bank_set(kws_bank_handle bank, int first, int count, const float* Wn /*[count,H,n_new] device*/, const float* bn /*[count,n_new] device*/,
                  void* stream);
 int kws_bank_get(kws_bank_handle bank, int first, int count, float* Wn, float* bn, void* stream);
+int kws_bank_set_keyword(kws_bank_handle bank, int slot, int n_used, const char* label, void* stream);
+int kws_bank_get_keyword(kws_bank_handle bank, int slot, int* n_used, char* label /*[16]; "" + *own = 0 when none*/, int* own);
 int kws_step_bank(kws_handle model, kws_bank_handle bank, const int32_t* user /*[B] device*/, const float* mel, const float* state_in,
                   float* state_out, const int32_t* seq_len, const uint8_t* reset_mask, float* nn_outputs, const kws_head_io* head1,
                   const kws_head_io* head2, int B, int T, void* stream);

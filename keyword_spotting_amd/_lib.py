@@ -161,6 +161,8 @@ _SIGNATURES = {
     "kws_bank_destroy": (_i, [_vp]),
     "kws_bank_set": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "kws_bank_get": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
+    "kws_bank_set_keyword": (_i, [_vp, _i, _i, ctypes.c_char_p, _vp]),
+    "kws_bank_get_keyword": (_i, [_vp, _i, ctypes.POINTER(_i), ctypes.c_char_p, ctypes.POINTER(_i)]),
     "kws_step_bank": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(KwsHeadIo), ctypes.POINTER(KwsHeadIo), _i, _i, _vp]),
     "kws_stream_create_bank": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, ctypes.c_char_p, ctypes.c_char_p, _vp, _vp, ctypes.POINTER(_vp)]),
     "kws_step_bank_window": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, ctypes.c_char_p, ctypes.c_char_p, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -60,6 +60,8 @@ int kws_host::bank_serves(const kws_bank* bank, const kws_model* h, const char* 
     return KWS_OK;
 }
 
+const kws::BankSlotKeyword* kws_host::bank_slots(const kws_bank* bank) { return bank->keywords_ever ? bank->slots : nullptr; }
+
 kws::BankRef kws_host::bank_ref(const kws_bank* bank, const int32_t* user) {
     kws::BankRef r = {};
     r.Wn = bank->Wn; r.bn = bank->bn; r.user = user; r.capacity = bank->capacity; r.n_new = bank->n_new;
@@ -80,11 +82,21 @@ int kws_bank_create(int H, int C, int n_new, int capacity, kws_bank_handle* out)
     if (!h) return fail(KWS_ERR_OUT_OF_MEMORY, "host allocation failed");
     h->H = H; h->C = C; h->n_new = n_new; h->capacity = capacity;
     const size_t nw = (size_t)capacity * H * n_new, nb = (size_t)capacity * n_new;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->store), (nw + nb) * sizeof(float));
-    if (e == hipSuccess) e = hipMemset(h->store, 0, (nw + nb) * sizeof(float));
+    const size_t floats = ((nw + nb) * sizeof(float) + 15) & ~(size_t)15;      // the slot table is read in 16-byte words
+    // every slot starts without a keyword of its own: the manager's label2 over all n_new columns
+    std::vector<kws::BankSlotKeyword> table((size_t)capacity);
+    memset(table.data(), 0, table.size() * sizeof(kws::BankSlotKeyword));
+    for (auto& s : table) s.n_used = n_new;
+    h->keyword.assign((size_t)capacity, kws_bank::Keyword());
+    for (auto& k : h->keyword) k.n_used = n_new;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->store), floats + table.size() * sizeof(kws::BankSlotKeyword));
+    if (e == hipSuccess) e = hipMemset(h->store, 0, floats);
+    if (e == hipSuccess)
+        e = hipMemcpy(reinterpret_cast<char*>(h->store) + floats, table.data(), table.size() * sizeof(kws::BankSlotKeyword), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { kws_bank_destroy(h); return hip_fail(e, "kws_bank_create"); }
     h->Wn = h->store; h->bn = h->store + nw;
+    h->slots = reinterpret_cast<kws::BankSlotKeyword*>(reinterpret_cast<char*>(h->store) + floats);
     live_register(h);
     *out = h;
     return KWS_OK;
@@ -107,6 +119,47 @@ int kws_bank_get(kws_bank_handle bank, int first, int count, float* Wn, float* b
     return bank_copy(bank, first, count, Wn, bn, false, stream);
 }
 
+int kws_bank_set_keyword(kws_bank_handle bank, int slot, int n_used, const char* label, void* stream) {
+    KWS_TRY(bank_range(bank, 0, 0, nullptr, nullptr));
+    if (slot < 0 || slot >= bank->capacity) return fail(KWS_ERR_INVALID_ARGUMENT, "slot %d outside the bank's capacity %d", slot, bank->capacity);
+    if (n_used < 1 || n_used > bank->n_new)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "n_used=%d: a slot's keyword uses 1..%d of the bank's new columns", n_used, bank->n_new);
+    if (!label && n_used != bank->n_new)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "n_used=%d without a label: a slot without a keyword of its own has the bank's n_new=%d", n_used, bank->n_new);
+    const int n = label ? (int)strnlen(label, 16) : 0;
+    if (n > 15) return fail(KWS_ERR_INVALID_ARGUMENT, "a slot's label has up to 15 digits (the window's matcher has 16 states)");
+    if (label) KWS_TRY(label_digits(label, n, nullptr));
+    for (int i = 0; i < n; ++i)
+        if (label[i] - '0' > bank->C + n_used - 2)
+            return fail(KWS_ERR_INVALID_ARGUMENT, "label '%s': digit %c names a word class the slot's head does not have (C=%d, n_used=%d: words 1..%d)",
+                        label, label[i], bank->C, n_used, bank->C + n_used - 2);
+    BusyGuard guard(bank->in_call);
+    if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this bank");
+    kws::BankSlotKeyword v;
+    memset(&v, 0, sizeof(v));
+    if (label) window_label_delta(label, n, v.delta);
+    v.n_label = n; v.n_used = n_used; v.own = label ? 1 : 0;
+    KWS_TRY(hip_done(kws::launch_bank_set_keyword(bank->slots + slot, v, static_cast<hipStream_t>(stream)), "launch bank_set_keyword"));
+    kws_bank::Keyword& k = bank->keyword[(size_t)slot];
+    k.n_used = n_used; k.own = label != nullptr;
+    memset(k.label, 0, sizeof(k.label));
+    if (label) memcpy(k.label, label, (size_t)n);
+    if (label) bank->keywords_ever = true;
+    return KWS_OK;
+}
+
+int kws_bank_get_keyword(kws_bank_handle bank, int slot, int* n_used, char* label, int* own) {
+    KWS_TRY(bank_range(bank, 0, 0, nullptr, nullptr));
+    if (slot < 0 || slot >= bank->capacity) return fail(KWS_ERR_INVALID_ARGUMENT, "slot %d outside the bank's capacity %d", slot, bank->capacity);
+    BusyGuard guard(bank->in_call);
+    if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this bank");
+    const kws_bank::Keyword& k = bank->keyword[(size_t)slot];
+    if (n_used) *n_used = k.n_used;
+    if (label) memcpy(label, k.label, sizeof(k.label));
+    if (own) *own = k.own ? 1 : 0;
+    return KWS_OK;
+}
+
 int kws_step_bank(kws_handle model, kws_bank_handle bank, const int32_t* user, const float* mel, const float* state_in, float* state_out,
                   const int32_t* seq_len, const uint8_t* reset_mask, float* nn_outputs, const kws_head_io* head1, const kws_head_io* head2, int B,
                   int T, void* stream) {
@@ -117,6 +170,7 @@ int kws_step_bank(kws_handle model, kws_bank_handle bank, const int32_t* user, c
     HeadsArgs ha;
     ha.nn_outputs = nn_outputs;
     ha.bank = &ref;
+    ha.bank_slots = bank_slots(bank);
     if (head1) { ha.head[0] = *head1; ha.on[0] = true; }
     if (head2) { ha.head[1] = *head2; ha.on[1] = true; }
     StepArgs a;
@@ -160,6 +214,7 @@ int kws_step_bank_window(kws_handle h, kws_bank_handle bank, const int32_t* user
     HeadsArgs ha = heads_window_args(window1, window2, clear_before, hit, restart);
     ha.head[0].softmax = softmax1; ha.head[1].softmax = softmax2;
     ha.bank = &ref;
+    ha.bank_slots = bank_slots(bank);
     StepArgs a;
     a.mel = mel; a.state_in = state_in; a.state_out = state_out; a.reset_mask = reset_mask;
     a.B = B; a.T = T; a.stream = static_cast<hipStream_t>(stream); a.heads = &ha;

@@ -141,6 +141,8 @@ struct HeadsArgs {
     // a bank of enrolled heads (kws_step_bank, kws_step_bank_window, a kws_stream_create_bank manager): head 2 of stream b comes from bank
     // slot user[b] instead of the handle's own second head -- bank_heads_kernel / bank_heads_window_kernel in the two kernels' places
     const kws::BankRef* bank = nullptr;
+    // ... and the bank's slot table once kws_bank_set_keyword was called on it (bank_slots): the keyword forms of the two kernels
+    const kws::BankSlotKeyword* bank_slots = nullptr;
 };
 // The arguments of one kws_step (include/kws_amd.h), and what the stream manager adds to them
 struct StepArgs {
@@ -176,6 +178,8 @@ size_t window_inc_lds_bytes(int T, int nq);
 constexpr size_t kWindowIncLdsMax = 160 * 1024;
 // ... binds `label` to the window's incremental state (the queued summaries are label-specific)
 int window_bind_label(kws_window* w, const char* label);
+// ... the matcher itself: the KMP automaton of `label` (n digits 1..9, n <= 15) over emitted words, delta[q * 16 + w]
+void window_label_delta(const char* label, int n, uint8_t* delta);
 // ... the incremental window as kernel arguments: of window_inc_kernel, or of the tail of a GRU launch (StepArgs::wt)
 kws::WindowTail window_tail_params(kws_window* w, const uint8_t* clear_before, int32_t* hit, uint8_t* restart);
 
@@ -195,6 +199,8 @@ int stream_create_impl(const char* who, kws_handle model, kws_frontend_handle fr
 int bank_serves(const kws_bank* bank, const kws_model* h, const char* who);
 // ... the bank and a launch's per-stream slots as kernel arguments
 kws::BankRef bank_ref(const kws_bank* bank, const int32_t* user);
+// ... its slot table for the keyword forms of the bank kernels, or null while no slot was ever given a keyword (the plain kernels)
+const kws::BankSlotKeyword* bank_slots(const kws_bank* bank);
 
 // api_frontend.hip: the 400-point FFT kernel takes a launch of B x T frames (else the dense-DFT kernel, which has magnitude mel only)
 bool frontend_takes_fft400(const kws_frontend* h, int B, int T);
@@ -217,6 +223,13 @@ struct kws_bank {
     int H = 0, C = 0, n_new = 0, capacity = 0;
     float* store = nullptr;          // Wn [capacity,H,n_new] | bn [capacity,n_new]
     float *Wn = nullptr, *bn = nullptr;
+    // Per-slot keywords (kws_bank_set_keyword): the device table [capacity] behind bn in `store`, the host's copy of what each slot was
+    // last given (n_used, own, the label for kws_bank_get_keyword), and whether any slot ever got one -- from then on every launch on
+    // the bank takes the keyword form of its kernel.
+    kws::BankSlotKeyword* slots = nullptr;
+    struct Keyword { int n_used = 0; bool own = false; char label[16] = {0}; };
+    std::vector<Keyword> keyword;
+    bool keywords_ever = false;
     std::atomic<int> in_call{0};
 };
 
@@ -285,7 +298,8 @@ struct kws_model {
     // What follows the top layer inside its profiling slot: nothing (also every layer below; a kws_step_heads call that wants no head and
     // no nn_outputs), the class epilogue in the layer's own kernel -- alone, or with the stream manager's window step behind it --, or
     // one more launch: the int8 projection, the two class heads, the two heads with their windows
-    enum Tail : uint8_t { kTailNone = 0, kTailEpilogue, kTailWindow, kTailOctbitFc, kTailDenseHeads, kTailHeadsWindow, kTailBankHeads, kTailBankWindow };
+    enum Tail : uint8_t { kTailNone = 0, kTailEpilogue, kTailWindow, kTailOctbitFc, kTailDenseHeads, kTailHeadsWindow, kTailBankHeads, kTailBankWindow,
+                          kTailBankKeywordHeads, kTailBankKeywordWindow };
     struct LaunchTag {
         uint8_t family = kNone, kx = 0, first = 0, tail = kTailNone;
         bool last() const { return tail == kTailEpilogue || tail == kTailWindow; }      // the kernels' template argument
@@ -310,6 +324,8 @@ struct kws_model {
             case kTailHeadsWindow: out += " + heads_window_kernel<" + std::to_string(cfg.hidden / 16) + ">"; break;
             case kTailBankHeads: out += " + bank_heads_kernel<" + std::to_string(cfg.hidden / 16) + ">"; break;
             case kTailBankWindow: out += " + bank_heads_window_kernel<" + std::to_string(cfg.hidden / 16) + ">"; break;
+            case kTailBankKeywordHeads: out += " + bank_keyword_heads_kernel<" + std::to_string(cfg.hidden / 16) + ">"; break;
+            case kTailBankKeywordWindow: out += " + bank_keyword_window_kernel<" + std::to_string(cfg.hidden / 16) + ">"; break;
         }
         return out;
     }

@@ -28,8 +28,10 @@ PlanRequest plan_request(const kws_model* h, const StepArgs& a) {
     Tail want = M::kTailEpilogue;
     if (a.heads) {
         const bool bank = a.heads->bank != nullptr;      // head 2 from a bank of enrolled columns: the bank kernels in the two kernels' places
-        want = a.heads->window ? (bank ? M::kTailBankWindow : M::kTailHeadsWindow) :
-               (a.heads->on[0] || a.heads->on[1] || a.heads->nn_outputs) ? (bank ? M::kTailBankHeads : M::kTailDenseHeads) : M::kTailNone;
+        const bool keywords = bank && a.heads->bank_slots;      // ... and their keyword forms once a slot of the bank has a keyword of its own
+        want = a.heads->window ? (keywords ? M::kTailBankKeywordWindow : bank ? M::kTailBankWindow : M::kTailHeadsWindow) :
+               (a.heads->on[0] || a.heads->on[1] || a.heads->nn_outputs) ?
+                   (keywords ? M::kTailBankKeywordHeads : bank ? M::kTailBankHeads : M::kTailDenseHeads) : M::kTailNone;
     }
     else if (a.wt && a.wt->nq <= kws::kWinTailMaxChunks) want = M::kTailWindow;
     return {a.B, a.T, h->profiling, want};
@@ -398,7 +400,12 @@ int launch_window_tail_kernel(const kws_model* h, const StepArgs& a, hipStream_t
     if (a.heads->bank) {
         kws::BankWindowParams bp;
         set_bank_window(bp, h, a);
-        return hip_done(kws::launch_bank_heads_window(bp, h->cfg.hidden, st), "launch bank_heads_window");
+        // (a keyword set on the bank AFTER the manager was sized: the keyword form's LDS is checked where it is launched)
+        const size_t lds = kws::bank_keyword_window_lds_bytes(a.T, bp.w.win[0].nq, bp.w.win[1].nq, h->cfg.hidden, bp.bank.n_new);
+        if (a.heads->bank_slots && lds > kWindowIncLdsMax)
+            return fail(KWS_ERR_UNSUPPORTED, "the bank window step with per-slot keywords needs %zu bytes of LDS for this chunk (%zu of them the "
+                        "group's keyword matchers; limit %zu): use shorter chunks or windows", lds, kws::kBankKeywordStageBytes, kWindowIncLdsMax);
+        return hip_done(kws::launch_bank_heads_window(bp, a.heads->bank_slots, h->cfg.hidden, st), "launch bank_heads_window");
     }
     kws::HeadsWindowParams hp;
     set_heads_window(hp, h, a);
@@ -486,12 +493,12 @@ int launch_slot(const kws_model* h, const StepArgs& a, const StepPlan& plan, int
     }
     if (e != hipSuccess) return hip_fail(e, what);
     switch (t.tail) {      // one more launch inside the top layer's slot, on the rows it left in its seam
-        case M::kTailHeadsWindow: case M::kTailBankWindow:      // both heads and both windows of a two-head manager
+        case M::kTailHeadsWindow: case M::kTailBankWindow: case M::kTailBankKeywordWindow:      // both heads and both windows of a two-head manager
             return launch_window_tail_kernel(h, a, st);
-        case M::kTailBankHeads: {        // the class heads, head 2 from each stream's bank slot
+        case M::kTailBankHeads: case M::kTailBankKeywordHeads: {        // the class heads, head 2 from each stream's bank slot
             kws::BankHeadsParams bp;
             set_bank_heads(bp, h, a);
-            return hip_done(kws::launch_bank_heads(bp, H, st), "launch bank_heads");
+            return hip_done(kws::launch_bank_heads(bp, a.heads->bank_slots, H, st), "launch bank_heads");
         }
         case M::kTailDenseHeads: {       // the class heads
             kws::DenseHeadsParams dp;
@@ -690,6 +697,14 @@ int kws_host::heads_window_check(const kws_model* h, const kws_window* w1, const
                     "(logits %zu, frame words %zu, label tables 512, rings %zu + %zu; limit %zu): use shorter chunks", T, w1->nq, w2->nq, lds,
                     kws::kHeadsWindowLogitsBytes, (size_t)2 * 16 * kws::heads_window_stride(T), kws::window_tail_scratch_bytes(w1->nq),
                     kws::window_tail_scratch_bytes(w2->nq), kWindowIncLdsMax);
+    // a bank with per-slot keywords launches the keyword form, which stages the group's sixteen matchers behind the columns
+    if (bank && bank->keywords_ever && kws::bank_keyword_window_lds_bytes(T, w1->nq, w2->nq, bank->H, bank->n_new) > kWindowIncLdsMax)
+        return fail(KWS_ERR_UNSUPPORTED, "chunks of up to %d frames with windows of %d and %d chunks and a bank of %d new classes at hidden=%d with "
+                    "per-slot keywords need %zu bytes of LDS in the bank window step (logits %zu, frame words %zu, label tables 512, rings %zu + %zu, "
+                    "the group's columns %zu, the group's keyword matchers %zu; limit %zu): use shorter chunks or windows", T, w1->nq, w2->nq,
+                    bank->n_new, bank->H, kws::bank_keyword_window_lds_bytes(T, w1->nq, w2->nq, bank->H, bank->n_new), kws::kHeadsWindowLogitsBytes,
+                    (size_t)2 * 16 * kws::heads_window_stride(T), kws::window_tail_scratch_bytes(w1->nq), kws::window_tail_scratch_bytes(w2->nq),
+                    kws::bank_stage_bytes(bank->H, bank->n_new), kws::kBankKeywordStageBytes, kWindowIncLdsMax);
     if (bank && lds + kws::bank_stage_bytes(bank->H, bank->n_new) > kWindowIncLdsMax)
         return fail(KWS_ERR_UNSUPPORTED, "chunks of up to %d frames with windows of %d and %d chunks and a bank of %d new classes at hidden=%d need %zu "
                     "bytes of LDS in the bank window step (logits %zu, frame words %zu, label tables 512, rings %zu + %zu, the group's columns %zu; "

@@ -29,6 +29,7 @@ int stream_decode(kws_stream_handle h, int T, const int32_t* frames, const uint8
         ha.frames = frames; ha.skip = skip;
         const kws::BankRef bank = h->bank ? bank_ref(h->bank, h->user) : kws::BankRef{};
         if (h->bank) ha.bank = &bank;            // head 2 of every stream from its own bank slot (bank_heads_window_kernel)
+        if (h->bank) ha.bank_slots = bank_slots(h->bank);      // ... over its slot's own keyword where the bank has any
         step.heads = &ha;
         return step_impl(h->model, step);
     }

@@ -5,7 +5,7 @@
 
 using namespace kws_host;
 
-namespace {
+namespace kws_host {
 
 // The label matcher of the incremental window: KMP automaton over emitted words, delta[q * 16 + w] = digits of the label
 // matched after reading word w (1..15) with q matched before (q < len); words the label does not contain lead to 0.
@@ -23,10 +23,6 @@ void window_label_delta(const char* label, int n, uint8_t* delta) {
             delta[q * 16 + w] = (uint8_t)k;
         }
 }
-
-}  // namespace
-
-namespace kws_host {
 
 int label_digits(const char* label, int n, int32_t* digits) {
     for (int i = 0; i < n; ++i) {

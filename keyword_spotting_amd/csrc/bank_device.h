@@ -63,6 +63,24 @@ __device__ __forceinline__ void bank_project(const f32x4 (&v)[NT], const float* 
     }
 }
 
+// The keyword form (kws_bank_set_keyword on any slot of the bank): the group's sixteen label matchers -> LDS next to the columns, one
+// 16-byte load per thread, and per stream kwn[2 s] = n_label, kwn[2 s + 1] = n_used | own << 8.  A stream whose slot has no keyword of
+// its own (or no slot) stages no matcher: it walks window 2's (default_label = that window's n_label) over the bank's full width.
+// 256 threads call this; the caller synchronises before bank_keyword_*.
+__device__ __forceinline__ void bank_keywords_stage(const BankRef& k, const BankSlotKeyword* slots, int b0, int B, int default_label,
+                                                    uint8_t* kwdl, int* kwn, int tid) {
+    const int s = (tid >> 4) & 15, q = tid & 15;
+    const int u = bank_user(k, b0 + s, B);
+    const BankSlotKeyword* slot = slots + (u >= 0 ? u : 0);
+    const bool own = u >= 0 && slot->own != 0;
+    if (own) *reinterpret_cast<uint4*>(kwdl + s * 256 + 16 * q) = *reinterpret_cast<const uint4*>(slot->delta + 16 * q);
+    if (q == 0) {
+        kwn[2 * s] = own ? slot->n_label : default_label;
+        kwn[2 * s + 1] = own ? (slot->n_used | 256) : k.n_new;
+    }
+}
+__device__ __forceinline__ int bank_keyword_width(const int* kwn, int s) { return kwn[2 * s + 1] & 255; }      // the stream's n_used
+
 // Head 2's row from head 1's raw logits and the stream's new classes: lg1[0..C-2], nw[0..n_new-1], lg1[C-1] (the blank last)
 __device__ __forceinline__ void bank_row(const float (&lg1)[kMaxClasses], const float (&nw)[kMaxClasses], int C, int n_new, float (&lg2)[kMaxClasses]) {
     float blank = 0.f;

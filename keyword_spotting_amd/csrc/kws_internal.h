@@ -290,6 +290,18 @@ struct BankRef {
 };
 struct BankHeadsParams { DenseHeadsParams d; BankRef bank; };       // d.head[0] is always bound (its outputs may all be null)
 struct BankWindowParams { HeadsWindowParams w; BankRef bank; };
+// A slot's keyword of its own (kws_bank_set_keyword): the matcher of its label (api_window.hip's KMP table, what window_tail walks),
+// the label's length, and the width of its head -- head 2 of a stream on the slot has C + n_used classes (the slot's first n_used
+// columns), rows zero-padded to C + n_new.  own == 0: no keyword of its own -- the manager's label2 over all n_new columns.
+struct BankSlotKeyword {
+    uint8_t delta[256];
+    int32_t n_label, n_used, own, pad;
+};
+static_assert(sizeof(BankSlotKeyword) == 272, "16-byte loads of the matcher");
+// The keyword forms of the two kernels (a bank on which kws_bank_set_keyword was ever called): the slot table [capacity] behind the
+// arguments of the plain forms, which keep their layout
+struct BankKeywordHeadsParams { BankHeadsParams b; const BankSlotKeyword* slots; };
+struct BankKeywordWindowParams { BankWindowParams b; const BankSlotKeyword* slots; };
 constexpr size_t kBankHeadsLogitsBytes = (size_t)2 * 16 * (kHeadFrames + 1) * 8 * sizeof(float);      // [head 1 | new classes][stream][slot][8]
 constexpr size_t kBankHeadsWordsBytes = (size_t)2 * 16 * (kHeadFrames + 1) * sizeof(int);
 // LDS of a group's staged columns [n_new][H/16][64 lanes][4] and biases [16][8]
@@ -298,8 +310,15 @@ __host__ __device__ inline size_t bank_heads_lds_bytes(int H, int n_new) { retur
 __host__ __device__ inline size_t bank_window_lds_bytes(int T, int nq1, int nq2, int H, int n_new) {
     return heads_window_lds_bytes(T, nq1, nq2) + bank_stage_bytes(H, n_new);
 }
-hipError_t launch_bank_heads(const BankHeadsParams& p, int hidden, hipStream_t st);
-hipError_t launch_bank_heads_window(const BankWindowParams& p, int hidden, hipStream_t st);
+// ... the keyword form stages the group's sixteen matchers and per stream (n_label, n_used) behind the columns
+constexpr size_t kBankKeywordStageBytes = (size_t)16 * 256 + 16 * 2 * sizeof(int);
+__host__ __device__ inline size_t bank_keyword_window_lds_bytes(int T, int nq1, int nq2, int H, int n_new) {
+    return bank_window_lds_bytes(T, nq1, nq2, H, n_new) + kBankKeywordStageBytes;
+}
+hipError_t launch_bank_set_keyword(BankSlotKeyword* dst, const BankSlotKeyword& v, hipStream_t st);      // *dst = v, stream-ordered
+// slots == null: the plain kernels; else their keyword forms
+hipError_t launch_bank_heads(const BankHeadsParams& p, const BankSlotKeyword* slots, int hidden, hipStream_t st);
+hipError_t launch_bank_heads_window(const BankWindowParams& p, const BankSlotKeyword* slots, int hidden, hipStream_t st);
 
 // decode window of the stream manager (stream_kernels.hip)
 struct WindowParams {

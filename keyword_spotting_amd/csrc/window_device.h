@@ -106,11 +106,16 @@ __device__ __forceinline__ void window_tail_request(const WindowTail& W, int B, 
 // chunks of different lengths may sit side by side); live = false: the lane's stream writes nothing (a skipped iteration).
 // Returns the lane's stream's hit (the same in its 16 lanes; meaningless where nothing is written): heads_window_kernel couples
 // two windows on it, every other caller drops it.
-template <int R>
+//
+// PER_LANE: the matcher per lane -- `dl` and `nl_lane` are the table and label length of the lane's stream (the same in its 16 lanes;
+// another stream of the wave may walk another label: the bank manager's per-slot keywords, bank_heads.hip).  Every other caller takes
+// the workgroup-uniform form, W's label and one table for all, and compiles to the code it always did (tools/isa_diff.sh): the choice
+// is a template argument because a wrapper around a shared body changed their register allocation.
+template <int R, bool PER_LANE = false>
 __device__ __forceinline__ bool window_tail(const WindowTail& W, int B, int b0, int T, const int8_t* cw, int cw_stride, const uint8_t* dl,
-                                            char* scratch, int tid, const WindowTailRegs<R>& g, bool live = true) {
+                                            char* scratch, int tid, const WindowTailRegs<R>& g, bool live = true, int nl_lane = 0) {
     if (tid >= 256) return false;
-    const int nq = W.nq, nl = W.n_label;
+    const int nq = W.nq, nl = PER_LANE ? nl_lane : W.n_label;
     const int s = tid >> 4, q = tid & 15;
     const bool valid = live && b0 + s < B;
     const int b = valid ? b0 + s : B - 1;

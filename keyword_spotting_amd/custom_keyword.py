@@ -25,6 +25,12 @@ per user:
     bank.set(0, new_columns, new_bias)            # device tensors straight from Enroller.fit: no host copy
     r = bank.forward(mel, state, users)           # users [B] int32: the slot of each stream (-1: no second head)
     manager = detector.StreamManager(model, batch, label="12", bank=bank, users=users, label2="56")
+
+Users whose keyword has another word pattern, or fewer new words than the bank is wide, share that bank and that manager: a slot can
+carry a keyword of its own -- a label and how many of its columns are in use --, and label2 is the pattern of the slots that have none:
+
+    bank.set(7, columns_of_a_one_word_enroller, bias, labels=["5"])      # [count, H, 1]: padded to n_new, keyword ("5", n_used 1)
+    bank.set_keyword(8, "1256")                                          # a trained word followed by the two new ones
 """
 import copy
 import ctypes
@@ -241,6 +247,7 @@ class KeywordBank(object):
         self.num_classes2 = cfg.num_classes + self.n_new
         self._lib = _lib.load()
         self._handle = ctypes.c_void_p()
+        self._has_keywords = False
         import torch
         with torch.cuda.device(self.device):
             _lib.check(self._lib.kws_bank_create(cfg.hidden_size, cfg.num_classes, self.n_new, self.capacity, ctypes.byref(self._handle)))
@@ -267,24 +274,65 @@ class KeywordBank(object):
             pass
 
     def _slots(self, columns, bias):
+        """-> (columns [count,H,n_new], bias [count,n_new], n_u): narrower columns [count,H,n_u] (an Enroller of fewer new words) are
+        padded with zero columns."""
         import torch
         wn = torch.as_tensor(columns).to(device=self.device, dtype=torch.float32).contiguous()
         bn = torch.as_tensor(bias).to(device=self.device, dtype=torch.float32).contiguous()
         if wn.dim() == 2:
             wn, bn = wn.unsqueeze(0), bn.reshape(1, -1)
         h, n = self.config.hidden_size, self.n_new
-        if wn.dim() != 3 or tuple(wn.shape[1:]) != (h, n) or tuple(bn.shape) != (wn.shape[0], n):
+        n_u = int(wn.shape[2]) if wn.dim() == 3 else -1
+        if wn.dim() != 3 or int(wn.shape[1]) != h or not 1 <= n_u <= n or tuple(bn.shape) != (wn.shape[0], n_u):
             raise _lib.InvalidArgumentError(-1, "columns / bias must be [count,%d,%d] / [count,%d], got %s %s" % (h, n, n, tuple(wn.shape), tuple(bn.shape)))
-        return wn, bn
+        if n_u < n:
+            wn = torch.nn.functional.pad(wn, (0, n - n_u)).contiguous()
+            bn = torch.nn.functional.pad(bn, (0, n - n_u)).contiguous()
+        return wn, bn, n_u
 
-    def set(self, first, columns, bias):
+    def set(self, first, columns, bias, labels=None):
         """Slots first .. first+count-1 <- columns [count,H,n_new], bias [count,n_new] (device tensors or arrays, e.g. straight from
-        Enroller.fit; one slot may come as [H,n_new], [n_new]).  Stream-ordered on the current stream (kws_bank_set)."""
+        Enroller.fit; one slot may come as [H,n_new], [n_new]).  Stream-ordered on the current stream (kws_bank_set).
+        Columns [count,H,n_u] with n_u < n_new -- what Enroller(model, n_u).fit returns -- are padded with zero columns.  labels (count
+        strings, or one for all): each slot's keyword becomes (labels[i], n_u) (set_keyword); narrower columns need them."""
         import torch
-        wn, bn = self._slots(columns, bias)
+        wn, bn, n_u = self._slots(columns, bias)
+        count = int(wn.shape[0])
+        if labels is None and n_u != self.n_new:
+            raise _lib.InvalidArgumentError(-1, "columns of %d new words in a bank of %d need labels (the slots' keywords)" % (n_u, self.n_new))
+        if labels is not None:
+            labels = [labels] * count if isinstance(labels, str) else [str(l) for l in labels]
+            if len(labels) != count:
+                raise _lib.InvalidArgumentError(-1, "labels: %d for %d slots" % (len(labels), count))
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_bank_set(self._handle, int(first), int(wn.shape[0]), _lib.ptr(wn), _lib.ptr(bn), _lib.current_stream_ptr()))
+            _lib.check(self._lib.kws_bank_set(self._handle, int(first), count, _lib.ptr(wn), _lib.ptr(bn), _lib.current_stream_ptr()))
+        for i, label in enumerate(labels or ()):
+            self.set_keyword(int(first) + i, label, n_u)
         return self
+
+    def set_keyword(self, slot, label, n_used=None):
+        """Slot `slot` gets a keyword of its own (kws_bank_set_keyword): head 2 of a stream on it has num_classes + n_used classes (n_used
+        of the slot's columns, default all n_new) and its window 2 matches `label` instead of the manager's label2.  label None: back to
+        no keyword of its own.  Stream-ordered.  Streams of a live manager on that slot are recycled by the caller before their next feed
+        (their queued chunk summaries were built for the label before)."""
+        import torch
+        n_used = self.n_new if n_used is None else int(n_used)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_bank_set_keyword(self._handle, int(slot), n_used, None if label is None else str(label).encode(),
+                                                      _lib.current_stream_ptr()))
+        self._has_keywords = self._has_keywords or label is not None
+        return self
+
+    def keyword(self, slot):
+        """-> (label or None, n_used) of the slot (kws_bank_get_keyword)."""
+        n_used, own = ctypes.c_int(), ctypes.c_int()
+        label = ctypes.create_string_buffer(16)
+        _lib.check(self._lib.kws_bank_get_keyword(self._handle, int(slot), ctypes.byref(n_used), label, ctypes.byref(own)))
+        return (label.value.decode() if own.value else None), int(n_used.value)
+
+    def has_keywords(self):
+        """A keyword was set on some slot: from then on the bank's launches take the keyword form of their kernels."""
+        return self._has_keywords
 
     def get(self, first=0, count=None):
         """-> (columns [count,H,n_new], bias [count,n_new]) device tensors: the slots as the bank holds them (kws_bank_get)."""

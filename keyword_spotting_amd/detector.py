@@ -161,15 +161,30 @@ class HotwordDetector(object):
         return fired
 
     def _window_hits(self, queues, num_classes, thres, label):
-        """detector.py:197-201 for every stream of one head: concatenate the window, ctc_decode2, ctc_predict -> [B] 0 / 1."""
-        windows = [torch.cat(q.get_all(), 0) for q in queues]            # :197
+        """detector.py:197-201 for the streams of `queues`, one head: concatenate the window, ctc_decode2, ctc_predict -> [len(queues)]
+        0 / 1.  Queued rows wider than num_classes are sliced to it (a bank slot's own width: the rows are zero-padded to the bank's)."""
+        windows = [torch.cat(q.get_all(), 0)[:, :num_classes] for q in queues]            # :197
         lens = torch.tensor([w.shape[0] for w in windows], dtype=torch.int32)
-        tmax = int(lens.max()) if self.batch else 0
-        padded = torch.zeros(self.batch, max(tmax, 1), num_classes, device=self.model.device)
+        tmax = int(lens.max()) if len(queues) else 0
+        padded = torch.zeros(len(queues), max(tmax, 1), num_classes, device=self.model.device)
         for b, w in enumerate(windows):
             padded[b, :w.shape[0]] = w
         words, counts = decode_batch(_lib.DECODE2, padded, lens, 3, thres, 0.0)   # :200
         return _ctc_predict((words, counts), label).cpu().numpy()                 # :201
+
+    def _bank_window_hits(self):
+        """Window 2 of a bank whose slots carry keywords of their own (KeywordBank.set_keyword): stream b is decoded against its slot's
+        label over its slot's C + n_used classes -- at the bank's full width the slot's blank column would be read as a word class --,
+        a stream on a slot without one (or without a slot) against label2 over the full width.  Streams that share both go together."""
+        users = self.users.cpu().numpy()
+        groups = {}
+        for b in range(self.batch):
+            label, n_used = self.bank.keyword(int(users[b])) if 0 <= users[b] < self.bank.capacity else (None, self.bank.n_new)
+            groups.setdefault((self.label2 if label is None else label, self.config.num_classes + n_used), []).append(b)
+        hits = np.zeros(self.batch, np.int64)
+        for (label, classes), idx in groups.items():
+            hits[idx] = self._window_hits([self.prob_queue2[b] for b in idx], classes, self.decode_thres2, label)
+        return hits
 
     def _feed_heads(self, mel):
         """The loop body for both heads (the VAD part is done): the stack once, head k's softmax into queue k, each window decoded
@@ -182,7 +197,8 @@ class HotwordDetector(object):
             self.prob_queue[b].add(sm1[b])
             self.prob_queue2[b].add(sm2[b])
         hit1 = self._window_hits(self.prob_queue, self.config.num_classes, self.decode_thres, self.label)
-        hit2 = self._window_hits(self.prob_queue2, self.model.num_classes2, self.decode_thres2, self.label2)
+        hit2 = self._bank_window_hits() if self.bank is not None and self.bank.has_keywords() else \
+            self._window_hits(self.prob_queue2, self.model.num_classes2, self.decode_thres2, self.label2)
         self.hit_mask = (hit1 != 0).astype(np.int32) | ((hit2 != 0).astype(np.int32) << 1)
         fired = []
         for b in np.nonzero(self.hit_mask)[0]:
@@ -296,8 +312,11 @@ class StreamManager(object):
     bank (custom_keyword.KeywordBank) with users [B] and label2: per-user customised keywords on one manager -- head 2 of stream b is
     projected with the columns of bank slot users[b] (kws_stream_create_bank / kws_step_bank_window), everything else as with label2
     alone; `model` is the one-head model the bank was built on, the manager runs on the bank's own heads stack.  self.users is the
-    device tensor the feeds read: rewrite users[b] in place when a slot is recycled for a new client (-1: no second head).  One label2
-    serves the whole manager: with a fixed n_new every user's new words are classes C-1 .. C+n_new-2 over their own columns.
+    device tensor the feeds read: rewrite users[b] in place when a slot is recycled for a new client (-1: no second head).  label2
+    is the pattern of every slot without a keyword of its own: with a fixed n_new every user's new words are classes C-1 .. C+n_new-2
+    over their own columns; a slot given its own label and width (KeywordBank.set_keyword) is matched against that -- the bank carries
+    the keywords, the manager takes no further argument.  After set_keyword on a slot live streams use, or after moving users[b] to a
+    slot with another keyword, recycle those streams before their next feed.
     Identical to HotwordDetector(bank=..., users=..., label2=...) (tests/test_gpu_bank_stream.py)."""
 
     def __init__(self, model, batch, window_chunks=15, max_frames=32, vad_thres=30, label=None, decode_thres=0.4, label2=None,

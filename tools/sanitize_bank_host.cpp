@@ -20,6 +20,12 @@ int main() {
     EXPECT(kws_bank_set(nullptr, 0, 1, dummyf, dummyf, nullptr), KWS_ERR_INVALID_ARGUMENT, "bank is null");
     EXPECT(kws_bank_set((kws_bank_handle)dummy, 0, 1, dummyf, dummyf, nullptr), KWS_ERR_INVALID_ARGUMENT, "not alive");
     EXPECT(kws_bank_get((kws_bank_handle)dummy, 0, 1, dummyf, dummyf, nullptr), KWS_ERR_INVALID_ARGUMENT, "not alive");
+    EXPECT(kws_bank_set_keyword(nullptr, 0, 1, "5", nullptr), KWS_ERR_INVALID_ARGUMENT, "bank is null");
+    EXPECT(kws_bank_set_keyword((kws_bank_handle)dummy, 0, 1, "5", nullptr), KWS_ERR_INVALID_ARGUMENT, "not alive");
+    EXPECT(kws_bank_set_keyword((kws_bank_handle)dummy, -1, 0, nullptr, nullptr), KWS_ERR_INVALID_ARGUMENT, "not alive");
+    { int n = 0, own = 0; char label[16];
+      EXPECT(kws_bank_get_keyword(nullptr, 0, &n, label, &own), KWS_ERR_INVALID_ARGUMENT, "bank is null");
+      EXPECT(kws_bank_get_keyword((kws_bank_handle)dummy, 0, &n, label, &own), KWS_ERR_INVALID_ARGUMENT, "not alive"); }
     EXPECT(kws_step_bank(nullptr, (kws_bank_handle)dummy, dummyi, dummyf, dummyf, dummyf, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1, nullptr),
            KWS_ERR_INVALID_ARGUMENT, "handle is null");
     EXPECT(kws_step_bank((kws_handle)dummy, nullptr, dummyi, dummyf, dummyf, dummyf, nullptr, nullptr, nullptr, nullptr, nullptr, 1, 1, nullptr),
