@@ -352,6 +352,55 @@ int kws_frontend_create_dataset(const kws_dataset_config* cfg, kws_frontend_hand
 int kws_frontend_frames_of(kws_frontend_handle h, int n_samples);
 int kws_frontend_window(kws_frontend_handle h, float* window_host);
 
+/* The training reader's noise augmentation (reader.py:207-280, config/rnn_config.py:67-73): a slice of a background-noise
+ * spectrogram is added to the utterance's |STFT| -- in the LINEAR domain, before the squaring and the mel / MFCC projection -- at a
+ * level of gain_db relative to the utterance's own (compute_db, reader.py:325-332).  Two entry points, fft_size = 400 and the FFT
+ * kernel only (KWS_ERR_UNSUPPORTED otherwise), on every handle that kws_frontend_run_lengths serves: either framing, with and
+ * without pre-emphasis, whatever the handle's features are.
+ *
+ * kws_frontend_linear_size: 201, the bins 0..200 of a row of the linear spectrum.
+ * kws_frontend_run_linear: kws_frontend_run_lengths with the magnitudes themselves as the output.  B utterances in rows of n_max
+ *   samples, n_b = clamp(n_samples[b], 0, n_max) of them in utterance b (NULL: n_max for all) ->
+ *     spec [B, T_max, 201]    |X| of the handle's frames, T_max = kws_frontend_frames_of(n_max) >= 1; rows t >= T_b are written as 0
+ *     frames_out [B] int32    T_b = kws_frontend_frames_of(n_b)
+ *     energy_out [B]          sum over t < T_b and the 201 bins of spec^2: what compute_db sums (the zero rows add nothing).  A
+ *                             frame's bins are summed in float32 in one fixed order, the frames of an utterance in float64 in one
+ *                             fixed order, rounded once: the value does not depend on what else is in the batch.
+ *   Two launches (the spectra, then one workgroup per utterance for the energies), no allocation, any stream.  Noise clips are
+ *   utterances and take the same call.
+ * kws_frontend_augment: R rows of the handle's own features from a set of clean spectra (spec [B, T_max, 201], frames [B],
+ *   energy [B]: what kws_frontend_run_linear wrote) and a set of noise spectra (the same triple, [K, Tn_max, 201]).  Row r, with
+ *   b = src[r], k = noise[r], T_r = frames[b]:
+ *     db(E, n) = 10 log10(E / fft_size^2 / n)
+ *     factor   = 10 ^ ((db(energy[b], frames[b]) - db(noise_energy[k], noise_frames[k]) + gain_db[r]) / 20)
+ *              = sqrt((energy[b] / frames[b]) / (noise_energy[k] / noise_frames[k])) * 10 ^ (gain_db[r] / 20), evaluated in double
+ *     mixed[t, f] = spec[b, t, f] + factor * noise_spec[k, start[r] + t, f]      t < T_r; a noise frame at or past noise_frames[k]
+ *                                                                             adds 0 (the reader's zero padding of its noise)
+ *     out[r, t, :] = the handle's features of mixed[t, :] -- mel of mixed, mel of mixed^2, or MFCC + deltas of mixed^2 with the delta
+ *                    edges at T_r; rows t >= T_r are written as 0.  out is [R, T_max, feature_size].
+ *   All arrays are DEVICE memory, which the host cannot check: the kernels decide the edge cases, and read nothing out of bounds in
+ *   any of them.
+ *     noise[r] outside [0, K)                         no noise for that row (-1 by convention)
+ *     src[r] outside [0, B)                           a row of zeros
+ *     start[r] < 0                                    read as 0
+ *     frames[b] / noise_frames[k]                     clamped to [0, T_max] / [0, Tn_max]
+ *     energy[b] == 0 (or not positive: NaN)           factor = 0 (the reference's 10 ** -inf)
+ *     noise_energy[k] not positive, noise_frames[k] == 0, or a factor that is not finite (gain_db)
+ *                                                     factor = 0, no noise (the reference would produce NaN)
+ *   A row without noise holds exactly the bits kws_frontend_run_lengths gives a (KWS_FEAT_MEL, power 1) handle; on power 2 and
+ *   MFCC it differs in the last bits, because this path squares the magnitude (reader.py:267-268) where that one takes re^2 + im^2.
+ *   A row's bits do not depend on the other rows of the call.  One small launch that turns the row arrays into a plan, the feature
+ *   launch and, for MFCC, the delta launch; the plan (36 bytes per row) is a stream-ordered allocation released behind them.
+ * B, n_max, K, Tn_max, R, T_max < 1 and null pointers are KWS_ERR_INVALID_ARGUMENT, decided before the device is touched. */
+int kws_frontend_linear_size(kws_frontend_handle h);
+int kws_frontend_run_linear(kws_frontend_handle h, const float* pcm /*[B, n_max] device*/, const int32_t* n_samples /*[B] device or NULL*/,
+                            int B, int n_max, float* spec /*[B, T_max, 201]*/, int32_t* frames_out /*[B]*/, float* energy_out /*[B]*/,
+                            void* stream);
+int kws_frontend_augment(kws_frontend_handle h, const float* spec, const int32_t* frames, const float* energy, int B, int T_max,
+                         const float* noise_spec, const int32_t* noise_frames, const float* noise_energy, int K, int Tn_max,
+                         const int32_t* src /*[R]*/, const int32_t* noise /*[R]*/, const int32_t* start /*[R]*/, const float* gain_db /*[R]*/,
+                         int R, float* out /*[R, T_max, feature_size]*/, void* stream);
+
 /* Device-side decode window of the streaming loop (detector.py:122,168-209; utils/queue.py): per stream a
  * bounded FIFO of up to `max_chunks` (1..64) softmax chunks (each <= max_frames frames; 2 * max_chunks *
  * round_up(max_frames, 16) bytes must fit 48 KiB, else KWS_ERR_UNSUPPORTED).  The frame ring behind kws_window_step is

@@ -123,6 +123,10 @@ _SIGNATURES = {
     "kws_frontend_create_dataset": (_i, [ctypes.POINTER(KwsDatasetConfig), ctypes.POINTER(_vp)]),
     "kws_frontend_frames_of": (_i, [_vp, _i]),
     "kws_frontend_window": (_i, [_vp, _vp]),
+    # the reader's noise augmentation: the linear spectrum as an output, and the mix in front of the feature epilogues
+    "kws_frontend_linear_size": (_i, [_vp]),
+    "kws_frontend_run_linear": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    "kws_frontend_augment": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "kws_window_create": (_i, [_i, _i, _i, _i, _f, ctypes.POINTER(_vp)]),
     "kws_window_destroy": (_i, [_vp]),
     "kws_window_step": (_i, [_vp, _vp, _i, _vp, ctypes.c_char_p, _vp, _vp, _vp]),

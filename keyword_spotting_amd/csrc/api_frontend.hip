@@ -372,6 +372,54 @@ int kws_frontend_run_lengths(kws_frontend_handle h, const float* pcm, const int3
     return hip_done(kws::launch_features_fft400(p, B, static_cast<hipStream_t>(stream)), "launch features_fft400");
 }
 
+int kws_frontend_linear_size(kws_frontend_handle h) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    if (!h->use_fft) return frontend_needs_fft400(h, "the linear spectrum and the noise mix");
+    return 201;
+}
+
+// Both entry points below decide sizes, then pointers, then the handle's kind: all of it host work, in front of any device call.
+int kws_frontend_run_linear(kws_frontend_handle h, const float* pcm, const int32_t* n_samples, int B, int n_max, float* spec,
+                            int32_t* frames_out, float* energy_out, void* stream) {
+    if (B < 1 || n_max < 1) return fail(KWS_ERR_INVALID_ARGUMENT, "kws_frontend_run_linear: B=%d n_max=%d must be positive", B, n_max);
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "kws_frontend_run_linear: handle is null");
+    if (!pcm || !spec || !frames_out || !energy_out)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "kws_frontend_run_linear: null pointer argument (pcm, spec, frames_out and energy_out are required)");
+    if (!h->use_fft) return frontend_needs_fft400(h, "kws_frontend_run_linear: the linear spectrum and the noise mix");
+    const int T = kws_frontend_frames_of(h, n_max);
+    if (T < 1) return fail(KWS_ERR_INVALID_ARGUMENT, "kws_frontend_run_linear: n_max=%d samples hold no frame", n_max);
+    if (!frontend_takes_fft400(h, B, T)) return fail(KWS_ERR_UNSUPPORTED, "B*T_max=%lld frames exceed the grid limit", (long long)B * T);
+    kws::FrontendParams p = frontend_params(h, true, B, T);
+    p.pcm = pcm; p.carry = pcm; p.mel = spec; p.n_samples = n_max; p.lens = n_samples; p.n_max = n_max;
+    return hip_done(kws::launch_linear_fft400(p, B, frames_out, energy_out, static_cast<hipStream_t>(stream)), "launch linear_fft400");
+}
+
+int kws_frontend_augment(kws_frontend_handle h, const float* spec, const int32_t* frames, const float* energy, int B, int T_max,
+                         const float* noise_spec, const int32_t* noise_frames, const float* noise_energy, int K, int Tn_max,
+                         const int32_t* src, const int32_t* noise, const int32_t* start, const float* gain_db, int R, float* out,
+                         void* stream) {
+    if (B < 1 || T_max < 1 || K < 1 || Tn_max < 1 || R < 1)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "kws_frontend_augment: B=%d T_max=%d K=%d Tn_max=%d R=%d must be positive", B, T_max, K, Tn_max, R);
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "kws_frontend_augment: handle is null");
+    if (!spec || !frames || !energy || !noise_spec || !noise_frames || !noise_energy)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "kws_frontend_augment: null pointer argument (the clean and the noise set are spec, frames and energy each)");
+    if (!src || !noise || !start || !gain_db || !out)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "kws_frontend_augment: null pointer argument (src, noise, start, gain_db and out are required)");
+    if (!h->use_fft) return frontend_needs_fft400(h, "kws_frontend_augment: the linear spectrum and the noise mix");
+    // every index of the three sets stays below 2^31 elements' worth of frames (the kernels' 32-bit frame index)
+    if ((long long)R * T_max >= (1LL << 31) || (long long)B * T_max >= (1LL << 31) || (long long)K * Tn_max >= (1LL << 31))
+        return fail(KWS_ERR_UNSUPPORTED, "kws_frontend_augment: R*T_max, B*T_max and K*Tn_max frames must stay below 2^31");
+    const hipStream_t st = static_cast<hipStream_t>(stream);
+    kws::FrontendParams p = frontend_params(h, true, R, T_max);
+    p.pcm = spec; p.carry = noise_spec; p.mel = out;
+    kws::AugmentRows rows = {frames, noise_frames, energy, noise_energy, src, noise, start, gain_db, B, K, R, T_max, Tn_max, nullptr};
+    // the plan travels as one stream-ordered block, released behind the launches that read it
+    KWS_HIP(hipMallocAsync(reinterpret_cast<void**>(&rows.plan), (size_t)R * (kws::kPlanInts + 1) * sizeof(int32_t), st));
+    const hipError_t e = kws::launch_augment_fft400(p, rows, st);
+    (void)hipFreeAsync(rows.plan, st);
+    return hip_done(e, "launch augment_fft400");
+}
+
 int kws_frontend_run_carry(kws_frontend_handle h, const float* carry, int n_carry, const float* chunk, int n_chunk, int B,
                            float* mel, float* next_carry, int n_next, void* stream) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");

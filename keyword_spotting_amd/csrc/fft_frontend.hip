@@ -135,10 +135,21 @@ template <typename S, int EPI> struct Utterances {};
 // but the first two and the last two or three -- load as the other instantiations do; the others take the index per tap.
 // (A tag again: every instantiation above keeps its name and its code.)
 template <typename S, int EPI, bool PRE> struct DatasetFrames {};
+// kEpiLinear, a fourth EPI of Utterances / DatasetFrames (kws_frontend_run_linear): the magnitudes themselves leave the kernel, bins
+// 0..200 of every frame as rows of p.mel = spec [B, T, 201] -- the block's 16 rows are one contiguous run of the flattened frame index,
+// stored straight from the bin-order spectrum; rows past T_b are the transform of zeros: zero.  No mel tile: instantiated with MT = 1.
+constexpr int kEpiLinear = 3;
+constexpr int kLinearBins = 201;
+// Mixed<EPI> in place of the sample type (without GATE; kws_frontend_augment): stages 1 and 2 are replaced by "load the 16 frames x 201
+// magnitudes of the clean rows and of their noise slices, mix, store into the S[bin][frame] planes" (reader.py:238-253); the epilogues
+// follow as they stand, on mixed (kEpiMel) or mixed^2 (kEpiPower, kEpiMfcc; reader.py:264-268).  The grid is R x p.T frames; row r is
+// described by p.carry_len[r * kPlanInts ..] (kws_internal.h), which augment_plan_kernel below wrote.
+// (A tag again: every instantiation above keeps its name and its code.)
+template <int EPI> struct Mixed {};
 namespace {
 template <typename T> struct SampleOf {
     using type = T;
-    static constexpr bool ragged = false, lengths = false, centred = false, pre = false;
+    static constexpr bool ragged = false, lengths = false, centred = false, pre = false, mixed = false;
     static constexpr int epi = kEpiMel;
 };
 template <typename S> struct SampleOf<RaggedRows<S>> : SampleOf<S> { static constexpr bool ragged = true; };
@@ -146,6 +157,7 @@ template <typename S, int EPI> struct SampleOf<Utterances<S, EPI>> : SampleOf<S>
 template <typename S, int EPI, bool PRE> struct SampleOf<DatasetFrames<S, EPI, PRE>> : SampleOf<Utterances<S, EPI>> {
     static constexpr bool centred = true, pre = PRE;
 };
+template <int EPI> struct SampleOf<Mixed<EPI>> : SampleOf<Utterances<float, EPI>> { static constexpr bool mixed = true; };
 
 __device__ __forceinline__ int ragged_len(const FrontendParams& p, unsigned b) {      // clamped to [0, n_max] (kws_amd.h)
     const int n = p.lens ? p.lens[b] : p.n_max;
@@ -184,13 +196,18 @@ __device__ __forceinline__ void ragged_gate(const FrontendParams& p, unsigned b,
 }
 }  // namespace
 
+// kEpiLinear aims at one workgroup per CU fewer: it is bound by its stores (804 B per frame against 160 B of mel), and with the 96
+// registers of five workgroups the pre-emphasis edge path keeps its 25 taps, window values and predecessors without scratch
+constexpr int fe_occupancy(int epi) { return epi == kEpiLinear && KWS_FE_OCC > 1 ? KWS_FE_OCC - 1 : KWS_FE_OCC; }
 template <int MT, typename SampleTag, bool GATE>
-__global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const FrontendParams p) {
+__global__ void __launch_bounds__(256, fe_occupancy(SampleOf<SampleTag>::epi)) mel_fft400_kernel(const FrontendParams p) {
     using SampleT = typename SampleOf<SampleTag>::type;
     constexpr bool RAGGED = SampleOf<SampleTag>::ragged;
     constexpr bool LENGTHS = SampleOf<SampleTag>::lengths;
     constexpr int EPI = SampleOf<SampleTag>::epi;
     constexpr bool CENTRED = SampleOf<SampleTag>::centred, PRE = SampleOf<SampleTag>::pre;
+    constexpr bool MIXED = SampleOf<SampleTag>::mixed;
+    static_assert(!MIXED || EPI != kEpiLinear, "the mix feeds the feature epilogues");
     static_assert(GATE || !RAGGED, "the ragged feed always carries the gate");
     static_assert(!(GATE && LENGTHS), "whole utterances have no stream gate");
     __shared__ __attribute__((aligned(16))) char lds[kFftLds];
@@ -297,7 +314,7 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
     }
 
     // ---- stage 1: this wave's four frames ----
-    {
+    if constexpr (!MIXED) {
         const int n2 = lo;
         const int f = 4 * w + hi;
         unsigned fidx = f0 + f;
@@ -464,7 +481,7 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
         }
     }
     KWS_FE_STAMP(2);
-    __syncthreads();
+    if constexpr (!MIXED) __syncthreads();
     KWS_FE_STAMP(3);
     if (GATE && gate_b != 0xffffffffu) {
         if constexpr (RAGGED) {
@@ -480,7 +497,7 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
     // ---- stage 2: pass q = w, k1 = 4w + g ----
     const int g = hi, f = lo, q = w;
     float mag[16];
-    {
+    if constexpr (!MIXED) {
         const int k1 = 4 * q + g < 12 ? 4 * q + g : 12;         // lanes past k1 = 12 recompute plane 12 and store nothing
         const int sf = (f >> 1) & 7;
         const char* row = lds + k1 * kPlaneBytes + f * kRowBytes;
@@ -517,13 +534,13 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
         }
 #pragma unroll
         for (int k2 = 0; k2 < 16; ++k2) {
-            if constexpr (EPI == kEpiMel) mag[k2] = __builtin_amdgcn_sqrtf(fmaf(o[k2].re, o[k2].re, o[k2].im * o[k2].im));
+            if constexpr (EPI == kEpiMel || EPI == kEpiLinear) mag[k2] = __builtin_amdgcn_sqrtf(fmaf(o[k2].re, o[k2].re, o[k2].im * o[k2].im));
             else mag[k2] = fmaf(o[k2].re, o[k2].re, o[k2].im * o[k2].im);            // utils/mfcc.py:77: the power spectrum itself
         }
     }
     // basis fragments of this wave's mel tile: the first kMelRegs groups of its run wait in registers (the loads fly while the
     // spectrum is written and the workgroup meets at the barrier); a longer run streams the rest
-    const int lo4 = w < MT ? p.mel_lo[w] : 0, n = w < MT ? p.mel_cnt[w] : 0;   // first 4-bin group, number of groups (multiple of 4; zero-padded table)
+    const int lo4 = w < MT ? p.mel_lo[w] : 0, n = EPI != kEpiLinear && w < MT ? p.mel_cnt[w] : 0;   // first 4-bin group, number of groups (multiple of 4; zero-padded table)
     // table: [tile][group / 4][64 lanes] float4 (the fragments of four consecutive groups side by side): one 16-byte load each
     const f32x4* A = reinterpret_cast<const f32x4*>(p.melw) + ((size_t)(w < MT ? p.mel_off[w] : 0) / 4 * 64 + lane);
     float a[kMelRegs];
@@ -535,11 +552,53 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
         }
     }
     KWS_FE_STAMP(4);
-    lds_barrier();             // every wave has read its planes: the spectrum takes their place
+    if constexpr (!MIXED) lds_barrier();             // every wave has read its planes: the spectrum takes their place
     KWS_FE_STAMP(5);
     // ---- |X| in bin order: S[bin][frame], 64 B rows.  bin = k1 + 25 k2 folded at 200 ----
     float* S = reinterpret_cast<float*>(lds);
-    {
+    if constexpr (MIXED) {
+        // The block's 16 frames lie in one row of the call or straddle several (p.T < 16: up to 16).  Lanes 0..15 of wave 0 read
+        // their frame's row plan and park where its 201 clean magnitudes and its noise slice's begin (-1: none) behind the
+        // spectrum and the DCT partials; then element i = 201 f + bin of the block goes to thread i % 256: consecutive lanes read
+        // consecutive floats of a row (a row is 804 contiguous bytes in both sets), whatever the plan says.
+        long long* at = reinterpret_cast<long long*>(lds + kSpecRows * 64 + 4 * kMaxDctTiles * 64 * 16);      // [16][clean, noise]
+        float* fac = reinterpret_cast<float*>(at + 32);                                                        // [16]
+        if (tid < 16) {
+            const unsigned fo = f0 + tid;
+            long long ca = -1, na = -1;
+            float fc = 0.f;
+            if (fo < total) {
+                const unsigned r = fo / (unsigned)p.T;
+                const int t = (int)(fo - r * (unsigned)p.T);
+                const int32_t* plan = p.carry_len + (size_t)r * kPlanInts;
+                const int b = plan[0], k = plan[1];
+                if (b >= 0 && t < plan[5]) {
+                    ca = ((long long)b * p.T + t) * kLinearBins;
+                    if (k >= 0 && t < plan[3]) {
+                        na = ((long long)k * p.carry_stride + plan[2] + t) * kLinearBins;
+                        fc = __int_as_float(plan[4]);
+                    }
+                }
+            }
+            at[2 * tid] = ca; at[2 * tid + 1] = na; fac[tid] = fc;
+        }
+        if (tid < 16 * (kSpecRows - 201)) S[201 * 16 + tid] = 0.f;     // padding rows the last block may read
+        lds_barrier();
+#pragma unroll
+        for (int j = 0; j < (16 * kLinearBins + 255) / 256; ++j) {
+            const int i = tid + 256 * j;
+            if (i < 16 * kLinearBins) {
+                const int fr = i / kLinearBins, bin = i - fr * kLinearBins;
+                const long long ca = at[2 * fr], na = at[2 * fr + 1];
+                float v = 0.f;
+                if (ca >= 0) {
+                    v = p.pcm[ca + bin];
+                    if (na >= 0) v = v + fac[fr] * p.carry[na + bin];   // reader.py:238,252: two roundings (contraction is off)
+                }
+                S[bin * 16 + fr] = EPI == kEpiMel ? v : v * v;         // reader.py:267-268, utils/mfcc.py:77
+            }
+        }
+    } else {
         const int k1 = 4 * q + g;
         if (k1 <= 12) {
 #pragma unroll
@@ -555,6 +614,17 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
     }
     lds_barrier();
     KWS_FE_STAMP(6);
+    if constexpr (EPI == kEpiLinear) {
+        // the 16 rows of this block are elements [201 f0, 201 (f0 + 16)) of spec: consecutive lanes store consecutive floats
+        float* out = p.mel + (size_t)f0 * kLinearBins;
+        const unsigned left = total - f0;
+        const int count = kLinearBins * (int)(left < 16u ? left : 16u);
+        for (int i = tid; i < count; i += 256) {
+            const int fr = i / kLinearBins, bin = i - fr * kLinearBins;
+            out[i] = S[bin * 16 + fr];
+        }
+        return;
+    }
 
     // ---- mel projection: wave m = mel tile m over its contiguous run of 4-bin groups.  A = basis fragments
     // [tile][group][64 lanes], B = four spectrum rows (k = g) x 16 frames; two accumulators break the dependent chain ----
@@ -633,7 +703,9 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
             const unsigned fo = f0 + f;
             if (fo < total) {
                 const unsigned sb = fo / (unsigned)p.T;
-                const bool live = (int)(fo - sb * (unsigned)p.T) < utterance_frames<CENTRED>(p, ragged_len(p, sb));
+                bool live;
+                if constexpr (MIXED) live = (int)(fo - sb * (unsigned)p.T) < p.carry_len[(size_t)sb * kPlanInts + 5];
+                else live = (int)(fo - sb * (unsigned)p.T) < utterance_frames<CENTRED>(p, ragged_len(p, sb));
                 float* out = p.mel + (size_t)fo * (3 * p.n_mfcc);
                 const int c0 = 16 * w + 4 * g;
 #pragma unroll
@@ -643,6 +715,83 @@ __global__ void __launch_bounds__(256, KWS_FE_OCC) mel_fft400_kernel(const Front
         }
     }
     KWS_FE_STAMP(7);
+}
+
+// The energies behind the kEpiLinear launch (kws_frontend_run_linear): energy[b] = sum_{t < T_b} sum_f spec[b, t, f]^2, what the
+// reader's compute_db sums (reader.py:325-332).  One workgroup per utterance, so the value cannot depend on the rest of the batch.
+// A frame: lane l adds the squares of bins l, l + 64, l + 128, l + 192 in that order, then the xor butterfly over the 64 lanes -- float32,
+// one fixed tree.  The frames: wave w adds frames w, w + 4, ... in that order in float64, the four waves meet as (0 + 1) + (2 + 3), and
+// the sum is rounded to float32 once.  The spectrum was written by the launch in front and comes back out of L2.
+__global__ void __launch_bounds__(256) linear_energy_kernel(const FrontendParams p, int32_t* frames_out, float* energy_out) {
+    __shared__ double part[4];
+    const unsigned b = blockIdx.x;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n = ragged_len(p, b);
+    const int tb = p.centred ? centred_frames(p, n) : ragged_frames(p, n);      // <= p.T: n <= n_max
+    const float* rows = p.mel + (size_t)b * p.T * kLinearBins;
+    double sum = 0.0;
+    for (int t = w; t < tb; t += 4) {
+        const float* row = rows + (size_t)t * kLinearBins;
+        float acc = 0.f;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int bin = lane + 64 * j;
+            const float v = bin < kLinearBins ? row[bin] : 0.f;
+            acc = fmaf(v, v, acc);
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) acc = acc + __shfl_xor(acc, off, 64);
+        sum += (double)acc;
+    }
+    if (lane == 0) part[w] = sum;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        energy_out[b] = (float)((part[0] + part[1]) + (part[2] + part[3]));
+        frames_out[b] = tb;
+    }
+}
+
+// The rows of kws_frontend_augment -> the plan the Mixed launch reads (kws_internal.h) and the sample counts mfcc_delta_kernel takes
+// its edges from.  Every edge case of the device-side arrays is decided here, once per row (kws_amd.h lists them); what leaves is in
+// range: b and k index their sets or are -1, start + (frames from start on) <= Tn, T_r <= T.
+//   factor = 10^((db_a - db_n + gain) / 20), db(E, n) = 10 log10(E / fft^2 / n)  (reader.py:226-234,325-332)
+//          = sqrt((E_a / n_a) / (E_n / n_n)) 10^(gain / 20) in double, rounded to float once
+__global__ void __launch_bounds__(256) augment_plan_kernel(const AugmentRows a, int fft, int hop, int centred) {
+    const int r = (int)(blockIdx.x * 256u + threadIdx.x);
+    if (r >= a.R) return;
+    const int b = a.src[r];
+    const bool ok = b >= 0 && b < a.B;
+    int tr = ok ? a.frames[b] : 0;
+    tr = tr < 0 ? 0 : (tr > a.T ? a.T : tr);
+    const int k = a.noise[r];
+    int st = a.start[r];
+    st = st < 0 ? 0 : st;
+    int nf = 0;
+    float factor = 0.f;
+    if (ok && tr > 0 && k >= 0 && k < a.K) {
+        nf = a.noise_frames[k];
+        nf = nf < 0 ? 0 : (nf > a.Tn ? a.Tn : nf);
+        const float ea = a.energy[b], en = a.noise_energy[k];
+        if (nf > 0 && ea > 0.f && en > 0.f) {           // (a NaN energy compares false)
+            const float f = (float)(sqrt(((double)ea / tr) / ((double)en / nf)) * pow(10.0, (double)a.gain_db[r] / 20.0));
+            if (f == f && fabsf(f) <= 3.402823466e38f) factor = f;
+        }
+    }
+    const int avail = nf > st ? nf - st : 0;
+    const bool mix = factor != 0.f && avail > 0;
+    int32_t* plan = a.plan + (size_t)r * kPlanInts;
+    plan[0] = ok ? b : -1;
+    plan[1] = mix ? k : -1;
+    plan[2] = mix ? st : 0;
+    plan[3] = mix ? avail : 0;
+    plan[4] = __float_as_int(mix ? factor : 0.f);
+    plan[5] = tr;
+    plan[6] = 0;
+    plan[7] = 0;
+    // the fewest samples that hold tr frames: 1 + n / hop centred frames for n > fft / 2, 1 + (n - fft) / hop deploy frames
+    int n = 0;
+    if (tr > 0) n = centred ? ((tr - 1) * hop > fft / 2 ? (tr - 1) * hop : fft / 2 + 1) : fft + (tr - 1) * hop;
+    a.plan[(size_t)a.R * kPlanInts + r] = n;
 }
 
 // The delta thirds of the MFCC rows (utils/mfcc.py:45-69,96-99), in place behind the launch above: with
@@ -695,6 +844,42 @@ hipError_t launch_features_fft400(const FrontendParams& p, int B, hipStream_t st
     if (p.n_mfcc == 0) return p.power == 2 ? launch_features_tiles<kEpiPower>(q, grid, st) : launch_features_tiles<kEpiMel>(q, grid, st);
     if (p.n_mfcc > 16 * kMaxDctTiles || p.dct_tiles != (p.n_mfcc + 15) / 16 || !p.dct) return hipErrorInvalidValue;
     hipError_t e = launch_features_tiles<kEpiMfcc>(q, grid, st);
+    if (e != hipSuccess) return e;
+    const unsigned long long cells = (unsigned long long)total * (unsigned)p.n_mfcc;       // < 2^36
+    return launch_lds<mfcc_delta_kernel>(dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, q);
+}
+
+hipError_t launch_linear_fft400(const FrontendParams& p, int B, int32_t* frames_out, float* energy_out, hipStream_t st) {
+    const long long total = (long long)B * p.T;        // 0 < total < 2^31 (checked by the caller)
+    if (p.fft != 400 || p.gate || p.pcm_i16 || p.n_carry != 0 || (p.centred && !p.win) || total <= 0) return hipErrorInvalidValue;
+    const unsigned grid = (unsigned)(((total + 15) / 16 + 7) / 8 * 8);
+    FrontendParams q = p;
+    q.fft_blocks = (int)grid;
+    q.B = B;
+    hipError_t e;
+    if (!p.centred) e = launch_lds<mel_fft400_kernel<1, Utterances<float, kEpiLinear>, false>>(dim3(grid), dim3(256), 0, st, q);
+    else if (p.pre_emphasis != 0.f) e = launch_lds<mel_fft400_kernel<1, DatasetFrames<float, kEpiLinear, true>, false>>(dim3(grid), dim3(256), 0, st, q);
+    else e = launch_lds<mel_fft400_kernel<1, DatasetFrames<float, kEpiLinear, false>, false>>(dim3(grid), dim3(256), 0, st, q);
+    if (e != hipSuccess) return e;
+    return launch_lds<linear_energy_kernel>(dim3((unsigned)B), dim3(256), 0, st, q, frames_out, energy_out);
+}
+
+hipError_t launch_augment_fft400(const FrontendParams& p, const AugmentRows& rows, hipStream_t st) {
+    const long long total = (long long)rows.R * rows.T;        // 0 < total < 2^31 (checked by the caller)
+    if (p.fft != 400 || total <= 0 || total >= (1LL << 31) || !rows.plan) return hipErrorInvalidValue;
+    if ((long long)rows.T * p.hop + p.fft > 0x7fffffffLL) return hipErrorInvalidValue;      // the plan's sample counts are int32
+    hipError_t e = launch_lds<augment_plan_kernel>(dim3((unsigned)((rows.R + 255) / 256)), dim3(256), 0, st, rows, p.fft, p.hop, p.centred);
+    if (e != hipSuccess) return e;
+    const unsigned grid = (unsigned)(((total + 15) / 16 + 7) / 8 * 8);
+    FrontendParams q = p;
+    q.fft_blocks = (int)grid;
+    q.B = rows.R; q.T = rows.T;
+    q.gate = 0; q.pcm_i16 = nullptr; q.n_carry = 0; q.n_samples = 0;
+    q.carry_len = rows.plan; q.lens = rows.plan + (size_t)rows.R * kPlanInts; q.n_max = 0x7fffffff; q.carry_stride = rows.Tn;
+    if (p.n_mfcc == 0)
+        return p.power == 2 ? launch_fft400_tiles<Mixed<kEpiPower>, false>(q, grid, st) : launch_fft400_tiles<Mixed<kEpiMel>, false>(q, grid, st);
+    if (p.n_mfcc > 16 * kMaxDctTiles || p.dct_tiles != (p.n_mfcc + 15) / 16 || !p.dct) return hipErrorInvalidValue;
+    e = launch_fft400_tiles<Mixed<kEpiMfcc>, false>(q, grid, st);
     if (e != hipSuccess) return e;
     const unsigned long long cells = (unsigned long long)total * (unsigned)p.n_mfcc;       // < 2^36
     return launch_lds<mfcc_delta_kernel>(dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, q);

@@ -416,6 +416,27 @@ hipError_t launch_mel_fft400(const FrontendParams& p, int B, hipStream_t st);   
 // ... B whole utterances with per-utterance lengths -> mel (p.power) or MFCC + deltas (p.n_mfcc > 0: two launches); float PCM, no gate;
 // p.centred: the dataset's frames (DatasetFrames)
 hipError_t launch_features_fft400(const FrontendParams& p, int B, hipStream_t st);
+// ... the linear spectrum of the same utterances (kws_frontend_run_linear; the kEpiLinear epilogue): p.mel = spec [B, T, 201], and behind
+// it one workgroup per utterance that writes frames_out [B] = T_b and energy_out [B] = sum_{t < T_b} sum_f spec^2
+hipError_t launch_linear_fft400(const FrontendParams& p, int B, int32_t* frames_out, float* energy_out, hipStream_t st);
+// ... and the reader's noise mix in front of the three feature epilogues (kws_frontend_augment; the Mixed tag): R rows of T frames, row r
+// = features(spec[src[r]] + factor_r * noise_spec[noise[r]][start[r] ..]).  augment_plan_kernel turns the row arrays into plan and
+// lens; the feature launch reads them through FrontendParams as laid out here (no field of its own: the struct is the kernarg of every
+// front-end kernel):
+//   pcm = the clean spectra [B, T, 201], carry = the noise spectra [K, Tn, 201], carry_stride = Tn, mel = out [R, T, feature]
+//   carry_len = plan [R][kPlanInts]: {b or -1, k or -1, start, noise frames from start on, bits of factor, T_r, 0, 0}
+//   lens = [R] a sample count whose frame count under the handle's framing is T_r (what mfcc_delta_kernel derives its edges from),
+//   n_max = INT_MAX (nothing clamps it)
+constexpr int kPlanInts = 8;
+struct AugmentRows {
+    const int32_t *frames, *noise_frames;      // [B], [K]
+    const float *energy, *noise_energy;        // [B], [K]
+    const int32_t *src, *noise, *start;        // [R]
+    const float* gain_db;                      // [R]
+    int B, K, R, T, Tn;
+    int32_t* plan;                             // [R][kPlanInts] followed by lens [R]
+};
+hipError_t launch_augment_fft400(const FrontendParams& p, const AugmentRows& rows, hipStream_t st);
 hipError_t launch_carry_tail(const float* carry, int n_carry, const float* chunk, int n_chunk, float* next, int n_next, int B,
                              hipStream_t st);
 

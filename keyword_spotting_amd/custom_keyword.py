@@ -31,6 +31,14 @@ carry a keyword of its own -- a label and how many of its columns are in use --,
 
     bank.set(7, columns_of_a_one_word_enroller, bias, labels=["5"])      # [count, H, 1]: padded to n_new, keyword ("5", n_used 1)
     bank.set_keyword(8, "1256")                                          # a trained word followed by the two new ones
+
+Three clean utterances seen at every step are a narrow training set.  The reference's reader mixes a slice of background noise into
+the linear spectrogram on every training step (reader.py:207-280); Enroller.fit_augmented does the same on the device, with fresh
+noise per batch of optimiser steps:
+
+    frontend = DatasetFrontend(config)                                   # a mel front-end of |X| (config.power 1)
+    clean, noise = frontend.linear(utterances, n_samples), frontend.linear(noise_clips, noise_samples)
+    new_columns, new_bias, loss_trace = enroller.fit_augmented(frontend, clean, noise, NoiseAugmenter(seed=1), labels, steps=100)
 """
 import copy
 import ctypes
@@ -115,6 +123,48 @@ def truncated_normal(shape, seed=0):
         x[bad] = rng.standard_normal(int(bad.sum()))
         bad = np.abs(x) > 2.0
     return x.astype(np.float32)
+
+
+class NoiseAugmenter(object):
+    """The random variables of the reader's background-noise augmentation (reader.py:229-253) with the shipped config's values as
+    defaults (config/rnn_config.py:60,69-73): per BATCH one decay ~ U[bg_decay_min_db, bg_decay_max_db) dB, one start ~ uniform integer
+    in [0, max_sequence_length - T) and one Bernoulli(bg_noise_prob) that decides whether the whole batch gets noise -- drawn in that
+    order, as the reader's graph lists them.  Row i is paired with noise clip i % n_noise (the reader pairs row i of the utterance
+    batch with row i of the noise batch).  per_row=True draws all three per row instead: more variety from a handful of utterances.
+
+    The draws come from a numpy.random.Generator seeded with `seed`.  TensorFlow's random stream cannot be reproduced (its kernels'
+    Philox streams are keyed by graph-level and op-level seeds and by the op's position in the graph): only the distributions are the
+    reader's, not the numbers."""
+
+    def __init__(self, bg_noise_prob=0.5, bg_decay_min_db=-15, bg_decay_max_db=-5, max_sequence_length=2000, seed=0, per_row=False):
+        if not 0.0 <= float(bg_noise_prob) <= 1.0:
+            raise _lib.InvalidArgumentError(-1, "bg_noise_prob=%r is no probability" % (bg_noise_prob,))
+        if not float(bg_decay_min_db) <= float(bg_decay_max_db):
+            raise _lib.InvalidArgumentError(-1, "bg_decay_min_db=%r above bg_decay_max_db=%r" % (bg_decay_min_db, bg_decay_max_db))
+        self.bg_noise_prob = float(bg_noise_prob)
+        self.bg_decay_min_db, self.bg_decay_max_db = float(bg_decay_min_db), float(bg_decay_max_db)
+        self.max_sequence_length, self.per_row = int(max_sequence_length), bool(per_row)
+        self._rng = np.random.default_rng(seed)
+
+    def draw(self, rows, n_noise, T):
+        """-> (src, noise_index, start, gain_db), each [rows] (int32, int32, int32, float32): the row arrays of
+        DatasetFrontend.augment for `rows` utterances of up to T frames and n_noise noise clips.  src is 0..rows-1; noise_index is
+        i % n_noise, or -1 where the Bernoulli said no noise.  T >= max_sequence_length is refused, as tf.random_uniform refuses an
+        empty range (reader.py:241-243)."""
+        rows, n_noise, T = int(rows), int(n_noise), int(T)
+        if rows < 1 or n_noise < 1:
+            raise _lib.InvalidArgumentError(-1, "rows=%d n_noise=%d: at least one of each" % (rows, n_noise))
+        if T >= self.max_sequence_length:
+            raise _lib.InvalidArgumentError(-1, "T=%d frames leave no start in [0, max_sequence_length - T) with max_sequence_length=%d"
+                                            % (T, self.max_sequence_length))
+        n = rows if self.per_row else 1
+        decay = self._rng.uniform(self.bg_decay_min_db, self.bg_decay_max_db, n)
+        start = self._rng.integers(0, self.max_sequence_length - T, n)
+        add = self._rng.random(n) < self.bg_noise_prob
+        src = np.arange(rows, dtype=np.int32)
+        noise_index = np.where(np.broadcast_to(add, (rows,)), src % n_noise, -1).astype(np.int32)
+        return (src, noise_index, np.broadcast_to(start, (rows,)).astype(np.int32),
+                np.broadcast_to(decay, (rows,)).astype(np.float32))
 
 
 class Enroller(object):
@@ -208,6 +258,53 @@ class Enroller(object):
             _lib.check(self._lib.kws_enroll_set(self._handle, _lib.ptr(wn), _lib.ptr(bn), stream))
             _lib.check(self._lib.kws_enroll_fit(self._handle, _lib.ptr(nn), _lib.ptr(logits1), sl_p, lab_p, lab_len_p, t, int(lab.shape[1]),
                                                 float(lr), int(steps), _lib.ptr(trace), stream))
+            out_w, out_b = torch.empty_like(wn), torch.empty_like(bn)
+            _lib.check(self._lib.kws_enroll_get(self._handle, _lib.ptr(out_w), _lib.ptr(out_b), stream))
+        return out_w, out_b, trace
+
+    def fit_augmented(self, frontend, clean, noise, augmenter, labels, steps, steps_per_batch=1, lr=1.5e-3, init=None, seed=0):
+        """fit on noisy versions of the utterances, redrawn every steps_per_batch optimiser steps as the reference's training loop draws
+        them per step (reader.py:207-280).  frontend: a front-end whose features are the model's mel input (DatasetFrontend /
+        MelFrontend of n_mel filters); clean: frontend.linear of the E*K utterances (enrolment e owns rows e*K .. e*K+K-1; an utterance
+        without frames is an empty slot); noise: frontend.linear of the noise clips; augmenter: a NoiseAugmenter.  Per batch:
+        augmenter.draw -> frontend.augment -> features (the frozen stack) -> kws_enroll_fit for the batch's steps.  kws_enroll_set is
+        called once, in front: Adam's moments and its step count run on across the batches.  labels, lr, init, seed and the result
+        (new_columns, new_bias, loss_trace [steps, E*K]) are fit's."""
+        import torch
+        e, k, h, n = self.enrolments, self.slots, self.config.hidden_size, self.n_new
+        b = e * k
+        steps, per = int(steps), int(steps_per_batch)
+        if steps < 1 or per < 1:
+            raise _lib.InvalidArgumentError(-1, "steps=%d steps_per_batch=%d: at least one of each" % (steps, per))
+        if int(frontend._lib.kws_frontend_feature_size(frontend._handle)) != int(self.config.n_mel) or getattr(frontend.config, "mfcc", False):
+            raise _lib.InvalidArgumentError(-1, "fit_augmented needs a front-end whose features are the model's %d mel filters" % self.config.n_mel)
+        if int(clean.spec.shape[0]) != b:
+            raise _lib.InvalidArgumentError(-1, "clean holds %d utterances for %d enrolments of %d slots" % (int(clean.spec.shape[0]), e, k))
+        lab, lab_len = _pack_labels(labels, b)
+        if lab.shape[1] > MAX_LABEL:
+            raise _lib.InvalidArgumentError(-1, "labels of up to %d entries, got %d" % (MAX_LABEL, lab.shape[1]))
+        if init is None:
+            init = (truncated_normal((e, h, n), seed), np.zeros((e, n), np.float32))
+        wn = torch.as_tensor(init[0]).to(device=self.device, dtype=torch.float32).contiguous()
+        bn = torch.as_tensor(init[1]).to(device=self.device, dtype=torch.float32).contiguous()
+        if tuple(wn.shape) != (e, h, n) or tuple(bn.shape) != (e, n):
+            raise _lib.InvalidArgumentError(-1, "init must be ([%d,%d,%d], [%d,%d]), got %s %s" % (e, h, n, e, n, tuple(wn.shape), tuple(bn.shape)))
+        t, n_noise = int(clean.spec.shape[1]), int(noise.spec.shape[0])
+        frames = torch.as_tensor(clean.frames).to(device=self.device, dtype=torch.int32).contiguous()
+        lengths = frames.cpu().numpy()          # the one host copy: kws_enroll_fit takes seq_len from host memory
+        sl, sl_p = _ints(lengths)
+        lab, lab_p = _ints(lab)
+        lab_len, lab_len_p = _ints(lab_len)
+        trace = torch.empty(steps, b, dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            stream = _lib.current_stream_ptr()
+            _lib.check(self._lib.kws_enroll_set(self._handle, _lib.ptr(wn), _lib.ptr(bn), stream))
+            for s0 in range(0, steps, per):
+                src, noise_index, start, gain_db = augmenter.draw(b, n_noise, t)
+                mel = frontend.augment(clean, noise, src, noise_index, start, gain_db)
+                nn, logits1 = self.features(mel, frames)
+                _lib.check(self._lib.kws_enroll_fit(self._handle, _lib.ptr(nn), _lib.ptr(logits1), sl_p, lab_p, lab_len_p, t, int(lab.shape[1]),
+                                                    float(lr), min(per, steps - s0), _lib.ptr(trace[s0:]), stream))
             out_w, out_b = torch.empty_like(wn), torch.empty_like(bn)
             _lib.check(self._lib.kws_enroll_get(self._handle, _lib.ptr(out_w), _lib.ptr(out_b), stream))
         return out_w, out_b, trace

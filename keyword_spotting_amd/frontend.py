@@ -4,7 +4,13 @@ MfccFrontend -- the config.mfcc branch of models/attention_ctc.py:249-250 (utils
 -> dB -> DCT -> [c | delta | delta-delta], a whole-utterance transform (kws_frontend_create_features / kws_frontend_run_lengths).
 DatasetFrontend -- the features the models are trained and validated on (process_wav.py:38-44,69-78 -> reader.py:264-269;
 server_demo.py:59-82): optional pre-emphasis -> |librosa.stft(y, 400, 160)| (centred, reflect-padded, Hann-windowed) -> mel of |X| or
-|X|^2, or MFCC + deltas (kws_frontend_create_dataset / kws_frontend_run_lengths)."""
+|X|^2, or MFCC + deltas (kws_frontend_create_dataset / kws_frontend_run_lengths).
+Every fft-400 front-end also hands out the linear spectrum and mixes background noise into it in front of its own features, as the
+training reader does on every step (reader.py:207-280; kws_frontend_run_linear / kws_frontend_augment):
+
+    clean, noise = frontend.linear(utterances, n_samples), frontend.linear(noise_clips, noise_samples)
+    features = frontend.augment(clean, noise, src, noise_index, start, gain_db)        # one row per entry of src"""
+import collections
 import ctypes
 
 import numpy as np
@@ -13,8 +19,14 @@ import torch
 from . import _lib
 
 
+LinearSpec = collections.namedtuple("LinearSpec", ["spec", "frames", "energy"])
+LinearSpec.__doc__ = """What _Frontend.linear returns, device tensors: spec [B, T_max, 201] float32 (|X|, rows past an utterance's own frame
+count zero), frames [B] int32 (T_b), energy [B] float32 (the sum of spec ** 2 over the utterance: what reader.py's compute_db sums)."""
+
+
 class _Frontend(object):
-    """What the two front-ends share: the handle and its lifetime, the mel basis, the PCM normalisation."""
+    """What the front-ends share: the handle and its lifetime, the mel basis, the PCM normalisation, the linear spectrum and the
+    noise mix."""
 
     def __init__(self, config, device, create, features=None, dataset=None):
         self.config = config
@@ -74,6 +86,62 @@ class _Frontend(object):
             _lib.check(self._lib.kws_frontend_run_lengths(self._handle, _lib.ptr(x), _lib.ptr(n_samples), b, n, _lib.ptr(out),
                                                           _lib.current_stream_ptr()))
         return out[0] if single else out
+
+    def linear(self, pcm, n_samples=None):
+        """kws_frontend_run_linear: pcm [B,N] (or [N]) float, n_samples [B] int32 or None (= N for all) -> LinearSpec of the B utterances
+        (always batched: spec [B, num_frames(N), 201]).  Noise clips are utterances and take the same call."""
+        x, b, n, _ = self._pcm(pcm)
+        if n_samples is not None:
+            n_samples = torch.as_tensor(n_samples).to(device=self.device, dtype=torch.int32).contiguous()
+            if tuple(n_samples.shape) != (b,):
+                raise _lib.InvalidArgumentError(-1, "n_samples must be [%d]" % b)
+        with torch.cuda.device(self.device):
+            bins = self._lib.kws_frontend_linear_size(self._handle)
+            if bins < 0:
+                _lib.check(bins)
+            spec = torch.empty(b, max(self.num_frames(n), 0), bins, dtype=torch.float32, device=self.device)
+            frames = torch.empty(b, dtype=torch.int32, device=self.device)
+            energy = torch.empty(b, dtype=torch.float32, device=self.device)
+            _lib.check(self._lib.kws_frontend_run_linear(self._handle, _lib.ptr(x), _lib.ptr(n_samples), b, n, _lib.ptr(spec),
+                                                         _lib.ptr(frames), _lib.ptr(energy), _lib.current_stream_ptr()))
+        return LinearSpec(spec, frames, energy)
+
+    def augment(self, clean, noise, src, noise_index, start, gain_db):
+        """kws_frontend_augment: clean, noise: LinearSpec (of this front-end's linear); src, noise_index, start [R] int32 and gain_db
+        [R] float32 (arrays or tensors) -> this front-end's features [R, T_max, feature_size] of
+            clean.spec[src[r]] + factor_r * noise.spec[noise_index[r], start[r]:start[r] + T_r]
+        with factor_r the reader's 10 ** ((db(clean) - db(noise) + gain_db[r]) / 20) (reader.py:226-253).  noise_index -1: no noise for
+        that row; the other edge cases are the kernel's (include/kws_amd.h)."""
+        def triple(s, what):
+            spec = torch.as_tensor(s.spec).to(device=self.device, dtype=torch.float32).contiguous()
+            frames = torch.as_tensor(s.frames).to(device=self.device, dtype=torch.int32).contiguous()
+            energy = torch.as_tensor(s.energy).to(device=self.device, dtype=torch.float32).contiguous()
+            if spec.dim() != 3 or tuple(frames.shape) != (spec.shape[0],) or tuple(energy.shape) != (spec.shape[0],):
+                raise _lib.InvalidArgumentError(-1, "%s must be (spec [B,T,bins], frames [B], energy [B]), got %s %s %s" %
+                                                (what, tuple(spec.shape), tuple(frames.shape), tuple(energy.shape)))
+            return spec, frames, energy
+
+        with torch.cuda.device(self.device):
+            bins = self._lib.kws_frontend_linear_size(self._handle)
+            if bins < 0:
+                _lib.check(bins)
+        cs, cf, ce = triple(clean, "clean")
+        ns, nf, ne = triple(noise, "noise")
+        if int(cs.shape[2]) != bins or int(ns.shape[2]) != bins:
+            raise _lib.InvalidArgumentError(-1, "spectra of %d bins, got %d and %d" % (bins, cs.shape[2], ns.shape[2]))
+        rows = [torch.as_tensor(a).to(device=self.device, dtype=torch.int32).contiguous() for a in (src, noise_index, start)]
+        rows.append(torch.as_tensor(gain_db).to(device=self.device, dtype=torch.float32).contiguous())
+        r = int(rows[0].numel())
+        if any(a.dim() != 1 or int(a.numel()) != r for a in rows):
+            raise _lib.InvalidArgumentError(-1, "src, noise_index, start and gain_db must be [R], got %s" % ([tuple(a.shape) for a in rows],))
+        with torch.cuda.device(self.device):
+            width = int(self._lib.kws_frontend_feature_size(self._handle))
+            out = torch.empty(r, int(cs.shape[1]), width, dtype=torch.float32, device=self.device)
+            _lib.check(self._lib.kws_frontend_augment(self._handle, _lib.ptr(cs), _lib.ptr(cf), _lib.ptr(ce), int(cs.shape[0]), int(cs.shape[1]),
+                                                      _lib.ptr(ns), _lib.ptr(nf), _lib.ptr(ne), int(ns.shape[0]), int(ns.shape[1]),
+                                                      _lib.ptr(rows[0]), _lib.ptr(rows[1]), _lib.ptr(rows[2]), _lib.ptr(rows[3]), r,
+                                                      _lib.ptr(out), _lib.current_stream_ptr()))
+        return out
 
 
 class MelFrontend(_Frontend):
