@@ -18,6 +18,8 @@
  *                              respectively", README "Customize keyword"), the decisions ORed (server_demo.py:122-129)
  *   kws_enroll_fit             the training of the README's "Customize keyword" step: tf.nn.ctc_loss + AdamOptimizer on the new
  *                              columns of the class projection (models/rnn_ctc.py:59-101), frozen stack
+ *   kws_ctc_beam_search        tf.nn.ctc_beam_search_decoder as models/rnn_ctc.py:105-110, :166-176 would call it (commented out
+ *                              there): top paths and their log-probabilities
  *   kws_octbit_matmul          REGISTER_OP("OctbitMatMul") octbit/octbit_ops_reg.cc:7-15,
  *                              OctbitMatMulOp::Compute octbit/octbit_mat_mul_op.cc:49-183
  *   kws_octbit_quantize        octize_weight_int8_signed octbit/octbit_graph.py:191-215
@@ -576,6 +578,31 @@ int kws_enroll_fit(kws_enroll_handle h, const float* nn_outputs, const float* lo
 int kws_enroll_get(kws_enroll_handle h, float* Wn, float* bn, void* stream);
 int kws_enroll_moments(kws_enroll_handle h, float* m, float* v, void* stream);
 int kws_enroll_stats(kws_enroll_handle h, size_t* device_bytes, int32_t* allocs, int32_t* steps);
+
+/* CTC prefix beam search: the top_paths best labellings of every utterance and their log-probabilities (the decoder both graphs of
+ * models/rnn_ctc.py leave commented out: tf.nn.ctc_beam_search_decoder(log(softmax), seqLengths, beam_width=config.beam_size,
+ * top_paths=1)).  One wave per utterance; stateless, stream-ordered, allocates nothing, never synchronises.
+ *   logits   [B,T,C] f32 device, 16-byte aligned, C in 3..8.  The kernel takes the log-softmax of each row itself, so raw logits and
+ *            log(softmax) give the same result.  The blank is the LAST class; labels are 0..C-2.
+ *   seq_len  [B] i32 DEVICE memory, or NULL for T; values are clamped to 0..T, frames t >= seq_len[b] are never read.
+ *   The beam is a set of at most beam_width (1..32) label prefixes, each with (lp_b, lp_nb): the log-probability of the paths that
+ *   collapse to it and end in the blank / in a label; it starts as the empty prefix at (0, -inf).  Per frame every prefix p stays
+ *   (lp_b' += (lp_b + lp_nb) lp[blank]; lp_nb' += lp_nb lp[last(p)]) and is extended by every label c unless len(p) == L_max
+ *   (p+c: lp_nb' += lp[c] (lp_b if c == last(p), else lp_b + lp_nb); sums and products of probabilities, computed in the log domain).
+ *   Candidates with the same prefix merge, however they arose -- identity is the prefix's content -- and the beam_width candidates with
+ *   the largest lp_b' + lp_nb' survive; ties go to the smaller candidate index (8 x beam slot + label, the stay last), so one input
+ *   always gives the same bits.  This is the exact-candidate form: TensorFlow's decoder prunes further once its beam is full; with
+ *   beam_width >= the number of labellings the two coincide.
+ *   paths    [B,top_paths,L_max] i32 out: rank k's labels, -1 past the end; L_max in 1..64, top_paths in 1..beam_width
+ *   lengths  [B,top_paths] i32 out
+ *   log_prob [B,top_paths] f32 out, descending: log(P_b + P_nb) of the prefix.  Ranks past the prefixes that exist: length 0, all -1,
+ *            -inf.  seq_len[b] == 0: the empty prefix with log_prob 0 at rank 0.
+ *   merge_repeated != 0 drops a label equal to its predecessor as the path is written (tf.nn.ctc_beam_search_decoder's output option,
+ *            on by default there); the scores are untouched.
+ * Every refusal (null pointers, the ranges above, B or T < 1, alignment: KWS_ERR_INVALID_ARGUMENT; 32 T + 7552 bytes of LDS above
+ * 160 KiB: KWS_ERR_UNSUPPORTED with the byte counts) is decided before the device is probed. */
+int kws_ctc_beam_search(const float* logits, const int32_t* seq_len_or_null, int B, int T, int C, int beam_width, int top_paths, int L_max,
+                        int merge_repeated, int32_t* paths, int32_t* lengths, float* log_prob, void* stream);
 
 /* Per-user customised keywords: ONE bank of enrolled heads behind one frozen model.  kws_enroll_fit produces one set of columns per
  * user; a heads handle bakes one second head into the model.  A bank keeps `capacity` slots of n_new columns Wn[u] [H, n_new] and their

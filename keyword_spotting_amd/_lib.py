@@ -153,6 +153,7 @@ _SIGNATURES = {
     "kws_attention_pe_table": (_i, [_vp, _vp]),
     "kws_attention_selftest": (_i, [_vp]),
     "kws_ctc_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "kws_ctc_beam_search": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "kws_enroll_create": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_vp)]),
     "kws_enroll_destroy": (_i, [_vp]),
     "kws_enroll_set": (_i, [_vp, _vp, _vp, _vp]),

@@ -475,6 +475,16 @@ inline size_t enroll_fit_lds_bytes(int H, int n, int K, int T, int S_max) {
 // logits [B,T,C]; seq_len / label_len [B], labels [B,S_max]: device copies the host side has range-checked; grad [B,T,C] or null
 hipError_t launch_ctc_loss(const float* logits, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int C,
                            int S_max, float* loss, float* grad, hipStream_t st);
+// beam_kernels.hip: CTC prefix beam search, one wave per utterance.  A beam of at most kBeamMax prefixes of at most kBeamRow labels
+// (a row of bytes each, double-buffered); a frame has at most kBeamMax stays + kBeamMax x 7 extensions = kBeamCandidates candidates.
+// LDS: lp [T][8] | the candidates' 64-bit keys | their merged-away stamps | the next beam's (lp_b, lp_nb, source) | the two string buffers
+constexpr int kBeamMax = 32, kBeamRow = 64, kBeamCandidates = 8 * kBeamMax;
+inline size_t ctc_beam_lds_bytes(int T) {
+    return sizeof(float) * 8 * (size_t)T + kBeamCandidates * (8 + 4) + kBeamMax * 3 * 4 + 2 * kBeamMax * kBeamRow;
+}
+// logits [B,T,C]; seq_len [B] on the device or null (T); paths [B,K,L_max], lengths [B,K], log_prob [B,K]
+hipError_t launch_ctc_beam(const float* logits, const int32_t* seq_len, int B, int T, int C, int W, int K, int L_max, int merge_repeated,
+                           int32_t* paths, int32_t* lengths, float* log_prob, hipStream_t st);
 struct EnrollFitParams {
     const float *nn, *logits1;                      // [E*K,T,H], [E*K,T,C]
     const int32_t *seq_len, *labels, *label_len;    // [E*K], [E*K,S_max], [E*K]

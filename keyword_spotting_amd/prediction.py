@@ -105,6 +105,51 @@ def ctc_predict(seq, label="1233"):
     return int(ctc_predict((words, counts), label)[0].item())
 
 
+def ctc_beam_search_decode(inputs, lengths=None, beam_width=None, top_paths=1, merge_repeated=True, max_len=64, device=None):
+    """tf.nn.ctc_beam_search_decoder as models/rnn_ctc.py:105-110 would call it (kws_ctc_beam_search, the exact-candidate form):
+    inputs [B,T,C] logits or log(softmax) -- the kernel normalises each row itself --, the blank the last class.  beam_width None
+    is C - 1, config.beam_size.  -> (dense [B,K,max_len] int32 padded with -1, log_probs [B,K]) device tensors, descending per
+    utterance; a [T,C] input is one utterance and returns [K,max_len] and [K].  A row of `dense` goes straight into ctc_predict."""
+    lib = _lib.load()
+    x, single = _as_batch(inputs, device)
+    if x.data_ptr() % 16:
+        x = x.clone()
+    b, t, c = (int(v) for v in x.shape)
+    width = c - 1 if beam_width is None else int(beam_width)
+    k, l_max = int(top_paths), int(max_len)
+    if lengths is not None:
+        lengths = torch.as_tensor(lengths).to(device=x.device, dtype=torch.int32).contiguous()
+        if tuple(lengths.shape) != (b,):
+            raise _lib.InvalidArgumentError(-1, "lengths must be [%d], got %s" % (b, tuple(lengths.shape)))
+    dense = torch.empty(b, max(k, 0), max(l_max, 0), dtype=torch.int32, device=x.device)
+    lens = torch.empty(b, max(k, 0), dtype=torch.int32, device=x.device)
+    log_probs = torch.empty(b, max(k, 0), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(lib.kws_ctc_beam_search(_lib.ptr(x), _lib.ptr(lengths), b, t, c, width, k, l_max, 1 if merge_repeated else 0,
+                                           _lib.ptr(dense), _lib.ptr(lens), _lib.ptr(log_probs), _lib.current_stream_ptr()))
+    return (dense[0], log_probs[0]) if single else (dense, log_probs)
+
+
+def decode_best(inputs, lengths=None, beam_width=None, merge_repeated=True, max_len=64, device=None):
+    """The beam search's top path in the form of the other decoders: the words (labels above the space class 0) as the int32 array
+    [0,w1,0,w2,0,...]; a batch gives a list of them.  What WERCalculator.cal_batch_wer and ctc_predict / evaluate take."""
+    dense, _ = ctc_beam_search_decode(inputs, lengths, beam_width, 1, merge_repeated, max_len, device)
+    single = dense.dim() == 2
+    outs = [path_to_seq(row) for row in dense.reshape(-1, dense.shape[-1]).cpu().numpy()]
+    return outs[0] if single else outs
+
+
+def path_to_seq(path):
+    """One row of ctc_beam_search_decode's dense output (labels, -1 past the end) -> the reference's [0,w,0,...] form."""
+    row = np.asarray(path).ravel()
+    end = np.flatnonzero(row < 0)
+    row = row[:end[0] if len(end) else len(row)]
+    w = row[row > 0].astype(np.int32)
+    seq = np.zeros(2 * len(w) + 1, np.int32)
+    seq[1::2] = w
+    return seq
+
+
 def evaluate(result, target):
     """utils/prediction.py:203 -- (miss, positives, false_accept)."""
     if len(result) != len(target):
