@@ -679,6 +679,15 @@ int kws_host::step_impl(kws_handle h, const StepArgs& a) {
     return rc != KWS_OK ? rc : rl;
 }
 
+// what the LDS of a window step is made of, for the refusals below: the two-head step's terms, then a bank's columns and keyword matchers
+static std::string heads_window_lds_terms(int T, int nq1, int nq2, size_t cols, size_t matchers) {
+    std::string s = "logits " + std::to_string(kws::kHeadsWindowLogitsBytes) + ", frame words " + std::to_string((size_t)2 * 16 * kws::heads_window_stride(T)) +
+                    ", label tables 512, rings " + std::to_string(kws::window_tail_scratch_bytes(nq1)) + " + " + std::to_string(kws::window_tail_scratch_bytes(nq2));
+    if (cols) s += ", the group's columns " + std::to_string(cols);
+    if (matchers) s += ", the group's keyword matchers " + std::to_string(matchers);
+    return s;
+}
+
 int kws_host::heads_window_check(const kws_model* h, const kws_window* w1, const kws_window* w2, int B, int T, const kws_bank* bank) {
     if (h->num_classes2 <= 0)
         return fail(KWS_ERR_INVALID_ARGUMENT, "a two-head stream manager needs a model handle with a second class head (kws_create_heads)");
@@ -694,23 +703,15 @@ int kws_host::heads_window_check(const kws_model* h, const kws_window* w1, const
     const size_t lds = kws::heads_window_lds_bytes(T, w1->nq, w2->nq);
     if (lds > kWindowIncLdsMax)
         return fail(KWS_ERR_UNSUPPORTED, "chunks of up to %d frames with windows of %d and %d chunks need %zu bytes of LDS in the two-head window step "
-                    "(logits %zu, frame words %zu, label tables 512, rings %zu + %zu; limit %zu): use shorter chunks", T, w1->nq, w2->nq, lds,
-                    kws::kHeadsWindowLogitsBytes, (size_t)2 * 16 * kws::heads_window_stride(T), kws::window_tail_scratch_bytes(w1->nq),
-                    kws::window_tail_scratch_bytes(w2->nq), kWindowIncLdsMax);
+                    "(%s; limit %zu): use shorter chunks", T, w1->nq, w2->nq, lds, heads_window_lds_terms(T, w1->nq, w2->nq, 0, 0).c_str(), kWindowIncLdsMax);
+    if (!bank) return KWS_OK;
     // a bank with per-slot keywords launches the keyword form, which stages the group's sixteen matchers behind the columns
-    if (bank && bank->keywords_ever && kws::bank_keyword_window_lds_bytes(T, w1->nq, w2->nq, bank->H, bank->n_new) > kWindowIncLdsMax)
-        return fail(KWS_ERR_UNSUPPORTED, "chunks of up to %d frames with windows of %d and %d chunks and a bank of %d new classes at hidden=%d with "
-                    "per-slot keywords need %zu bytes of LDS in the bank window step (logits %zu, frame words %zu, label tables 512, rings %zu + %zu, "
-                    "the group's columns %zu, the group's keyword matchers %zu; limit %zu): use shorter chunks or windows", T, w1->nq, w2->nq,
-                    bank->n_new, bank->H, kws::bank_keyword_window_lds_bytes(T, w1->nq, w2->nq, bank->H, bank->n_new), kws::kHeadsWindowLogitsBytes,
-                    (size_t)2 * 16 * kws::heads_window_stride(T), kws::window_tail_scratch_bytes(w1->nq), kws::window_tail_scratch_bytes(w2->nq),
-                    kws::bank_stage_bytes(bank->H, bank->n_new), kws::kBankKeywordStageBytes, kWindowIncLdsMax);
-    if (bank && lds + kws::bank_stage_bytes(bank->H, bank->n_new) > kWindowIncLdsMax)
-        return fail(KWS_ERR_UNSUPPORTED, "chunks of up to %d frames with windows of %d and %d chunks and a bank of %d new classes at hidden=%d need %zu "
-                    "bytes of LDS in the bank window step (logits %zu, frame words %zu, label tables 512, rings %zu + %zu, the group's columns %zu; "
-                    "limit %zu): use shorter chunks or windows", T, w1->nq, w2->nq, bank->n_new, bank->H, lds + kws::bank_stage_bytes(bank->H, bank->n_new),
-                    kws::kHeadsWindowLogitsBytes, (size_t)2 * 16 * kws::heads_window_stride(T), kws::window_tail_scratch_bytes(w1->nq),
-                    kws::window_tail_scratch_bytes(w2->nq), kws::bank_stage_bytes(bank->H, bank->n_new), kWindowIncLdsMax);
+    const size_t cols = kws::bank_stage_bytes(bank->H, bank->n_new), matchers = bank->keywords_ever ? kws::kBankKeywordStageBytes : 0;
+    if (lds + cols + matchers > kWindowIncLdsMax)
+        return fail(KWS_ERR_UNSUPPORTED, "chunks of up to %d frames with windows of %d and %d chunks and a bank of %d new classes at hidden=%d%s need %zu "
+                    "bytes of LDS in the bank window step (%s; limit %zu): use shorter chunks or windows", T, w1->nq, w2->nq, bank->n_new, bank->H,
+                    matchers ? " with per-slot keywords" : "", lds + cols + matchers, heads_window_lds_terms(T, w1->nq, w2->nq, cols, matchers).c_str(),
+                    kWindowIncLdsMax);
     return KWS_OK;
 }
 

@@ -18,20 +18,16 @@
 // stream ahead of the launch (DenseHead::prev_in, as the int8 path's oct_prev), and only that copy is read here.  A block with
 // t0 > 0 gets the word of frame t0 - 1 by projecting that frame itself in slot 0 -- the same loop body, so the same
 // instruction sequence and the same bits as the block that owns the frame.
+//
+// The phases -- operand load, seam row with the zero row and the nn_outputs store, projection, the row's softmax and word, tokens and the
+// carried word -- are the functions of dense_heads_device.h, the ones bank_heads_kernel (bank_heads.hip) calls: one text per phase.
 #include "dense_heads_device.h"
 #include "launch.h"
 
 namespace kws {
 
-namespace {
-
-constexpr int kHeadSlots = kHeadFrames + 1;        // slot f <-> frame t0 - 1 + f; slot 0 is the halo
-
-}  // namespace
-
 template <int NT>
 __global__ void __launch_bounds__(256) dense_heads_kernel(const DenseHeadsParams p) {
-    constexpr int H = 16 * NT;
     __shared__ float lgs[2][16][kHeadSlots][8];      // logits of [head][stream][slot]: a lane of the row phase reads its 8 as two float4
     __shared__ int words[2][16][kHeadSlots];
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, g = lane >> 4, s = lane & 15;
@@ -39,16 +35,11 @@ __global__ void __launch_bounds__(256) dense_heads_kernel(const DenseHeadsParams
     const int b = G * kStreamsPerGroup + s;
     const bool bvalid = b < p.B;
 
-    // A operands: Wfc^T of each head, k-chunk kc in wa[hd][kc]; an absent head (C == 0) keeps zeros and is skipped below
+    // A operands of each head; an absent head (C == 0) keeps zeros and is skipped below
     float wa[2][4 * NT];
     f32x4 bias4[2];
 #pragma unroll
-    for (int hd = 0; hd < 2; ++hd) {
-        const bool on = p.head[hd].C > 0;
-#pragma unroll
-        for (int kc = 0; kc < 4 * NT; ++kc) wa[hd][kc] = on ? p.head[hd].wfc[kc * 64 + lane] : 0.f;
-        bias4[hd] = on ? ld4(p.head[hd].bfc + 4 * g) : splat4(0.f);
-    }
+    for (int hd = 0; hd < 2; ++hd) head_operands<NT>(p.head[hd], p.head[hd].C > 0, lane, g, wa[hd], bias4[hd]);
     int len_s = T;
     if (p.seq_len && bvalid) len_s = p.seq_len[b];
 
@@ -57,20 +48,7 @@ __global__ void __launch_bounds__(256) dense_heads_kernel(const DenseHeadsParams
     for (int f = (w == 0 && t0 == 0) ? 4 : w; f < f_end; f += 4) {      // the first block has no halo
         const int t = t0 - 1 + f;
         f32x4 v[NT];
-#pragma unroll
-        for (int n = 0; n < NT; ++n) {
-            const float4 x = src[((size_t)t * NT + n) * 64];
-            v[n] = (f32x4){x.x, x.y, x.z, x.w};
-        }
-        if (t >= len_s) {             // dynamic_rnn's zero row
-#pragma unroll
-            for (int n = 0; n < NT; ++n) v[n] = splat4(0.f);
-        }
-        if (p.nn_outputs && f > 0 && bvalid) {
-            float4* dst = reinterpret_cast<float4*>(p.nn_outputs + ((size_t)b * T + t) * H + 4 * g);
-#pragma unroll
-            for (int n = 0; n < NT; ++n) dst[4 * n] = make_float4(v[n][0], v[n][1], v[n][2], v[n][3]);
-        }
+        seam_row_step<NT>(src, t, len_s, p.nn_outputs, f > 0 && bvalid, b, T, g, v);
 #pragma unroll
         for (int hd = 0; hd < 2; ++hd) {
             if (p.head[hd].C == 0) continue;
@@ -92,12 +70,7 @@ __global__ void __launch_bounds__(256) dense_heads_kernel(const DenseHeadsParams
             if (hp.C == 0) continue;
             if (!in_call) { words[hd][si][f] = -1; continue; }
             float lg[kMaxClasses], pr[kMaxClasses];
-            {
-                const f32x4* row = reinterpret_cast<const f32x4*>(&lgs[hd][si][f][0]);
-                const f32x4 lo = row[0], hi = row[1];
-#pragma unroll
-                for (int c = 0; c < 4; ++c) { lg[c] = lo[c]; lg[4 + c] = hi[c]; }
-            }
+            load_row8(&lgs[hd][si][f][0], lg);
             const int word = head_row(lg, pr, hp.C, p.use_relu, p.value_clip, hp.decode_thres);
             words[hd][si][f] = t < len ? word : -1;
             if (f > 0 && bi < p.B) {
@@ -109,23 +82,7 @@ __global__ void __launch_bounds__(256) dense_heads_kernel(const DenseHeadsParams
     }
     __syncthreads();
 
-    // tokens (utils/prediction.py:76-80) and the carried word
-    for (int item = tid; item < 16 * kHeadFrames; item += 256) {
-        const int si = item / kHeadFrames, f = 1 + (item - si * kHeadFrames);
-        const int t = t0 - 1 + f, bi = G * kStreamsPerGroup + si;
-        if (t >= T || bi >= p.B) continue;
-#pragma unroll
-        for (int hd = 0; hd < 2; ++hd) {
-            const DenseHead& hp = p.head[hd];
-            if (hp.C == 0 || !hp.prev_word) continue;
-            const int word = words[hd][si][f];
-            int prev;
-            if (t == 0) prev = (p.reset && p.reset[bi]) ? -1 : hp.prev_in[bi];
-            else prev = words[hd][si][f - 1];
-            if (hp.tokens) hp.tokens[(size_t)bi * T + t] = (int8_t)((word >= 0 && word != prev) ? word + 1 : 0);
-            if (t == T - 1) hp.prev_word[bi] = word;
-        }
-    }
+    heads_tokens(p, &words[0][0][0], G, t0, tid);
 }
 
 hipError_t launch_dense_heads(const DenseHeadsParams& p, int hidden, hipStream_t st) {

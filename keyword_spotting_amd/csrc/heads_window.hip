@@ -19,6 +19,10 @@
 // and skip[b] behaves as in window_inc_kernel<true>: no slot in either window, restart untouched, hit 0.
 //
 // T == 0 (a chunk that completes no frame): no stack ran, h_top is not read; an empty entry goes into both windows.
+//
+// The LDS carve, the seam row, the logit row and the coupling are the functions of dense_heads_device.h, the ones bank_heads_window_kernel
+// (bank_heads.hip) calls: one text per phase.  The operand load is written out here: through head_operands this kernel was 0.5 us per
+// chunk slower at 4096 streams than the parent's (profiles/heads_family_refactor_ab.txt), with it inline it is not.
 #include "dense_heads_device.h"
 #include "launch.h"
 #include "window_device.h"
@@ -28,22 +32,18 @@ namespace kws {
 template <int NT, bool RAGGED>
 __global__ void __launch_bounds__(256) heads_window_kernel(const HeadsWindowParams p) {
     extern __shared__ __attribute__((aligned(16))) char hlds[];
-    const int T = p.T, B = p.B, stride = heads_window_stride(T);
-    float* lgs = reinterpret_cast<float*>(hlds);                                        // [head][stream][frame of the block][8]
-    int8_t* cw = reinterpret_cast<int8_t*>(hlds + kHeadsWindowLogitsBytes);             // [head][stream][stride]
-    uint8_t* dl = reinterpret_cast<uint8_t*>(cw) + (size_t)2 * 16 * stride;             // [head][16 states][16 words]
-    char* scratch = reinterpret_cast<char*>(dl) + 512;                                  // window 1's ring staging | window 2's
+    const int T = p.T, B = p.B;
+    const HeadsWindowLds L = heads_window_carve(hlds, T, p.win[0].nq, p.win[1].nq);
     const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, g = lane >> 4, s = lane & 15;
     const int G = blockIdx.x, b0 = G * kStreamsPerGroup;
-    window_tail_prepare(p.win[0], dl, tid);
-    window_tail_prepare(p.win[1], dl + 256, tid);
+    window_tail_prepare(p.win[0], L.dl, tid);
+    window_tail_prepare(p.win[1], L.dl + 256, tid);
 
     if (T > 0) {
-        // A operands: Wfc^T of each head, k-chunk kc in wa[hd][kc]
         float wa[2][4 * NT];
         f32x4 bias4[2];
 #pragma unroll
-        for (int hd = 0; hd < 2; ++hd) {
+        for (int hd = 0; hd < 2; ++hd) {      // head_operands' two statements, inline: as the function this kernel measured 0.5 us slower per chunk
 #pragma unroll
             for (int kc = 0; kc < 4 * NT; ++kc) wa[hd][kc] = p.head[hd].wfc[kc * 64 + lane];
             bias4[hd] = ld4(p.head[hd].bfc + 4 * g);
@@ -54,15 +54,11 @@ __global__ void __launch_bounds__(256) heads_window_kernel(const HeadsWindowPara
             for (int f = w; f < f_end; f += 4) {
                 const int t = t0 + f;
                 f32x4 v[NT];
-#pragma unroll
-                for (int n = 0; n < NT; ++n) {
-                    const float4 x = src[((size_t)t * NT + n) * 64];
-                    v[n] = (f32x4){x.x, x.y, x.z, x.w};
-                }
+                seam_row<NT>(src, t, v);
 #pragma unroll
                 for (int hd = 0; hd < 2; ++hd) {
                     KWS_HEAD_PROJECT(acc, NT, wa[hd], bias4[hd], v);
-                    if (g < 2) *reinterpret_cast<f32x4*>(&lgs[(((hd * 16 + s) * kHeadFrames) + f) * 8 + 4 * g]) = acc;
+                    if (g < 2) *reinterpret_cast<f32x4*>(&L.lgs[(((hd * 16 + s) * kHeadFrames) + f) * 8 + 4 * g]) = acc;
                 }
             }
             __syncthreads();
@@ -76,14 +72,9 @@ __global__ void __launch_bounds__(256) heads_window_kernel(const HeadsWindowPara
                 for (int hd = 0; hd < 2; ++hd) {
                     const HeadsWindowHead& hp = p.head[hd];
                     float lg[kMaxClasses], pr[kMaxClasses];
-                    {
-                        const f32x4* row = reinterpret_cast<const f32x4*>(&lgs[(((hd * 16 + si) * kHeadFrames) + f) * 8]);
-                        const f32x4 lo = row[0], hi = row[1];
-#pragma unroll
-                        for (int c = 0; c < 4; ++c) { lg[c] = lo[c]; lg[4 + c] = hi[c]; }
-                    }
+                    load_row8(&L.lgs[(((hd * 16 + si) * kHeadFrames) + f) * 8], lg);
                     const int word = head_row(lg, pr, hp.C, p.use_relu, p.value_clip, hp.decode_thres);
-                    cw[(hd * 16 + si) * stride + t] = (int8_t)word;
+                    L.cw[(hd * 16 + si) * L.stride + t] = (int8_t)word;
                     if (hp.softmax && bi < B) store_row(hp.softmax + ((size_t)bi * T + t) * hp.C, pr, hp.C);
                 }
             }
@@ -100,23 +91,10 @@ __global__ void __launch_bounds__(256) heads_window_kernel(const HeadsWindowPara
     const int bt = min(b0 + (tid >> 4), B - 1);                  // window_tail's stream of this lane
     const int Tt = RAGGED ? min(p.frames[bt], T) : T;
     const bool live = RAGGED ? p.skip[bt] == 0 : true;
-    const bool hit1 = window_tail<4>(p.win[0], B, b0, Tt, cw, stride, dl, scratch, tid, req1, live);
-    const bool hit2 = window_tail<4>(p.win[1], B, b0, Tt, cw + 16 * stride, stride, dl + 256, scratch + window_tail_scratch_bytes(p.win[0].nq),
+    const bool hit1 = window_tail<4>(p.win[0], B, b0, Tt, L.cw, L.stride, L.dl, L.scratch, tid, req1, live);
+    const bool hit2 = window_tail<4>(p.win[1], B, b0, Tt, L.cw + 16 * L.stride, L.stride, L.dl + 256, L.scratch + window_tail_scratch_bytes(p.win[0].nq),
                                      tid, req2, live);
-    if ((tid & 15) == 0 && b0 + (tid >> 4) < B) {
-        if (live) {
-            // (the tails wrote hit / head / count of their own window from this same lane: these stores follow them in program order)
-            const bool fired = hit1 || hit2;
-            if (fired) {                                         // detector.py:202-208, whichever head fired
-                p.win[0].head[bt] = 0; p.win[0].count[bt] = 0;
-                p.win[1].head[bt] = 0; p.win[1].count[bt] = 0;
-            }
-            if (p.restart) p.restart[bt] = fired ? 1 : 0;
-            p.hit[bt] = (hit1 ? 1 : 0) | (hit2 ? 2 : 0);
-        } else {
-            p.hit[bt] = 0;
-        }
-    }
+    heads_window_couple(p, b0, tid, bt, live, hit1, hit2, [](int) { return true; });
 }
 
 // kws_stream_recycle on a two-head manager: head 2's window of the recycled streams (head 1's goes with stream_recycle_kernel)
