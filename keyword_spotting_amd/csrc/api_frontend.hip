@@ -411,11 +411,11 @@ int kws_frontend_augment(kws_frontend_handle h, const float* spec, const int32_t
         return fail(KWS_ERR_UNSUPPORTED, "kws_frontend_augment: R*T_max, B*T_max and K*Tn_max frames must stay below 2^31");
     const hipStream_t st = static_cast<hipStream_t>(stream);
     kws::FrontendParams p = frontend_params(h, true, R, T_max);
-    p.pcm = spec; p.carry = noise_spec; p.mel = out;
+    p.mel = out;
     kws::AugmentRows rows = {frames, noise_frames, energy, noise_energy, src, noise, start, gain_db, B, K, R, T_max, Tn_max, nullptr};
     // the plan travels as one stream-ordered block, released behind the launches that read it
     KWS_HIP(hipMallocAsync(reinterpret_cast<void**>(&rows.plan), (size_t)R * (kws::kPlanInts + 1) * sizeof(int32_t), st));
-    const hipError_t e = kws::launch_augment_fft400(p, rows, st);
+    const hipError_t e = kws::launch_augment_fft400(p, spec, noise_spec, rows, st);
     (void)hipFreeAsync(rows.plan, st);
     return hip_done(e, "launch augment_fft400");
 }

@@ -25,13 +25,14 @@
 // frames).  In stage 2 lane = (g, frame f of 16) takes k1 = 4q + g in pass q (= wave q); the magnitudes return to LDS in BIN
 // order, where the mel projection (v_mfma_f32_16x16x4_f32 over 4-bin groups) only touches the blocks of the basis that are
 // not all zero.  ~9 kflop per frame on the VALU instead of the 100 kflop of the dense contraction.
+// Below: the tags of the kernel's variants, its phases as one function each in calling order, the kernel, its small companions, the launchers.
 #include <cstdlib>
 
 #include "gru_device.h"
 #include "launch.h"
 #include "vad_device.h"
 
-#pragma clang fp contract(off)      // only the fmaf() written below fuse: every frame sees one fixed instruction sequence
+#pragma clang fp contract(off)      // only the fmaf() written below fuse: one fixed instruction sequence per frame (lexical: covers every phase below)
 
 namespace kws {
 
@@ -95,7 +96,8 @@ constexpr int kMelRegs = 24;                   // basis fragments (4-bin groups)
 constexpr int kSpecRows = 208;                 // spectrum rows (bins 0..200 + zero padding) of 16 frames: 13,312 B of the same space
 constexpr int kMaxDctTiles = 2;                // MFCC: coefficient tiles of 16 (n_mfcc <= 32, kws_amd.h); the mel tiles' partial
                                                // products [4 tiles][kMaxDctTiles][64 lanes] float4 sit behind the spectrum
-static_assert(kSpecRows * 64 + 4 * kMaxDctTiles * 64 * 16 <= kFftLds, "the DCT partials must fit behind the spectrum");
+constexpr int kDctPartBytes = 4 * kMaxDctTiles * 64 * 16;
+static_assert(kSpecRows * 64 + kDctPartBytes <= kFftLds, "the DCT partials must fit behind the spectrum");
 
 }  // namespace
 
@@ -108,611 +110,655 @@ static_assert(kSpecRows * 64 + 4 * kMaxDctTiles * 64 * 16 <= kFftLds, "the DCT p
 // SampleT: float samples, or int16 PCM as the sound card delivers it (detector.py:40-43,74-79: scaled by 2^-15 on load --
 // read once, in place, no widened copy).  GATE: the head of a stream-manager iteration rides along in the same launch: the
 // workgroup that transforms a stream's FIRST frame also takes the vad sum of its new samples (the masks silent / reset) and writes
-// its next sample carry (detector.py:168-183) -- see the block below.
+// its next sample carry (detector.py:168-183) -- see gate_streams below.
 #ifndef KWS_FE_OCC
 #define KWS_FE_OCC 6          // workgroups per CU the register allocation aims at (tools/build_variant.sh -DKWS_FE_OCC=n for A/B)
 #endif
-// RaggedRows<S> in place of the sample type S (with GATE; kws_stream_feed_ragged): every stream has its own chunk length
-// (p.lens) and carry length (p.carry_len, or p.n_carry for all); the grid is B x T frames for the longest possible chunk, and
-// frames past a stream's own count load nothing and store zeros.  See ragged_gate below for what the gate writes.  (A tag on
-// the sample type rather than a fourth template parameter: the lock-step instantiations keep their names and their code.)
+// The kernel's variants are tags in place of the sample type: every instantiation keeps the name it was first given.
+// RaggedRows<S> (with GATE; kws_stream_feed_ragged): every stream has its own chunk length (p.lens) and carry length (p.carry_len, or
+// p.n_carry for all); the grid is B x T frames for the longest possible chunk, and frames past a stream's own count load nothing and
+// store zeros.  See stream_gate below for what the gate writes.
 template <typename S> struct RaggedRows {};
-// Utterances<S, EPI> in place of the sample type S (without GATE; kws_frontend_run_lengths): B whole utterances in rows of
-// p.n_max samples, utterance b with its own sample count (p.lens, null: n_max for all) and so its own frame count T_b <= p.T;
-// frames past T_b load nothing.  EPI picks what leaves the kernel (kws_feature_config; utils/mfcc.py:72-99, reader.py:267-268):
+// Utterances<S, EPI> (without GATE; kws_frontend_run_lengths): B whole utterances in rows of p.n_max samples, utterance b with its own
+// sample count (p.lens, null: n_max for all) and so its own frame count T_b <= p.T; frames past T_b load nothing.  EPI picks what
+// leaves the kernel (kws_feature_config; utils/mfcc.py:72-99, reader.py:267-268):
 //   kEpiMel    |X| -> mel, as the plain instantiations
 //   kEpiPower  |X|^2 = re^2 + im^2 (no sqrt) -> mel
 //   kEpiMfcc   |X|^2 -> mel -> 10 log10(max(1e-10, .)) -> DCT: the static coefficients [c < n_mfcc] of rows of 3 n_mfcc floats;
 //              rows past T_b are zero.  mfcc_delta_kernel below fills the other two thirds of every row.
-// (A tag again: the mel instantiations above keep their names and their code.)
-constexpr int kEpiMel = 0, kEpiPower = 1, kEpiMfcc = 2;
+//   kEpiLinear (kws_frontend_run_linear) the magnitudes themselves, bins 0..200 of every frame as rows of p.mel = spec [B, T, 201] --
+//              the block's 16 rows are one contiguous run of the flattened frame index, stored straight from the bin-order spectrum;
+//              rows past T_b are the transform of zeros: zero.  No mel tile: instantiated with MT = 1.
+constexpr int kEpiMel = 0, kEpiPower = 1, kEpiMfcc = 2, kEpiLinear = 3;
+constexpr int kLinearBins = 201;
 template <typename S, int EPI> struct Utterances {};
-// DatasetFrames<S, EPI, PRE> in place of the sample type S: Utterances<S, EPI> with the dataset's framing (p.centred; kws_amd.h).
+// DatasetFrames<S, EPI, PRE>: Utterances<S, EPI> with the dataset's framing (p.centred; kws_amd.h).
 // Frame t of utterance b (n samples) is centred on sample t * hop: tap i reads s = t * hop + i - 200, reflected once at either end
 // (s < 0: -s; s >= n: 2 (n - 1) - s -- np.pad(mode='reflect') for n >= 201, the shortest utterance that has frames), times the
 // Hann window p.win[i]; T_b = 1 + n / hop.  PRE: the samples pass y[0] = x[0], y[i] = x[i] - fl32(p.pre_emphasis * x[i-1]) first, two
 // roundings as numpy's float32 arrays take them.  Frames whose 400 taps and their predecessors all lie inside the utterance -- all
 // but the first two and the last two or three -- load as the other instantiations do; the others take the index per tap.
-// (A tag again: every instantiation above keeps its name and its code.)
 template <typename S, int EPI, bool PRE> struct DatasetFrames {};
-// kEpiLinear, a fourth EPI of Utterances / DatasetFrames (kws_frontend_run_linear): the magnitudes themselves leave the kernel, bins
-// 0..200 of every frame as rows of p.mel = spec [B, T, 201] -- the block's 16 rows are one contiguous run of the flattened frame index,
-// stored straight from the bin-order spectrum; rows past T_b are the transform of zeros: zero.  No mel tile: instantiated with MT = 1.
-constexpr int kEpiLinear = 3;
-constexpr int kLinearBins = 201;
-// Mixed<EPI> in place of the sample type (without GATE; kws_frontend_augment): stages 1 and 2 are replaced by "load the 16 frames x 201
-// magnitudes of the clean rows and of their noise slices, mix, store into the S[bin][frame] planes" (reader.py:238-253); the epilogues
-// follow as they stand, on mixed (kEpiMel) or mixed^2 (kEpiPower, kEpiMfcc; reader.py:264-268).  The grid is R x p.T frames; row r is
-// described by p.carry_len[r * kPlanInts ..] (kws_internal.h), which augment_plan_kernel below wrote.
-// (A tag again: every instantiation above keeps its name and its code.)
+// Mixed<EPI> (without GATE; kws_frontend_augment): stages 1 and 2 are replaced by "load the 16 frames x 201 magnitudes of the clean
+// rows and of their noise slices, mix, store into the S[bin][frame] planes" (reader.py:238-253); the epilogues follow as they stand,
+// on mixed (kEpiMel) or mixed^2 (kEpiPower, kEpiMfcc; reader.py:264-268).  The grid is R x p.T frames; row r is described by its
+// PlanRow (kws_internal.h), which augment_plan_kernel below wrote.
 template <int EPI> struct Mixed {};
+
 namespace {
-template <typename T> struct SampleOf {
+template <typename T> struct SampleOf {          // what a tag says about the sample type, the framing and the epilogue
     using type = T;
     static constexpr bool ragged = false, lengths = false, centred = false, pre = false, mixed = false;
     static constexpr int epi = kEpiMel;
 };
 template <typename S> struct SampleOf<RaggedRows<S>> : SampleOf<S> { static constexpr bool ragged = true; };
 template <typename S, int EPI> struct SampleOf<Utterances<S, EPI>> : SampleOf<S> { static constexpr bool lengths = true; static constexpr int epi = EPI; };
-template <typename S, int EPI, bool PRE> struct SampleOf<DatasetFrames<S, EPI, PRE>> : SampleOf<Utterances<S, EPI>> {
-    static constexpr bool centred = true, pre = PRE;
-};
+template <typename S, int EPI, bool PRE> struct SampleOf<DatasetFrames<S, EPI, PRE>> : SampleOf<Utterances<S, EPI>> { static constexpr bool centred = true, pre = PRE; };
 template <int EPI> struct SampleOf<Mixed<EPI>> : SampleOf<Utterances<float, EPI>> { static constexpr bool mixed = true; };
-
+template <typename SampleT> constexpr float kPcmScale = sizeof(SampleT) == 2 ? 1.0f / 32768.0f : 1.0f;      // int16 PCM is scaled by 2^-15 on load
+template <typename SampleT> __device__ __forceinline__ const SampleT* pcm_rows(const FrontendParams& p) {
+    return sizeof(SampleT) == 2 ? reinterpret_cast<const SampleT*>(p.pcm_i16) : reinterpret_cast<const SampleT*>(p.pcm);
+}
+// the new samples of stream b: rows of n_max samples on the ragged feed, of the chunk's length in lock step
+template <bool RAGGED, typename SampleT> __device__ __forceinline__ const SampleT* stream_row(const FrontendParams& p, const SampleT* rows, int n_chunk, unsigned b) {
+    return rows + (size_t)b * (RAGGED ? p.n_max : n_chunk);
+}
+// The mix's arguments: the clean spectra [B, T, 201], the noise spectra [K, noise_stride frames, 201], the plan [R].  FrontendParams, the
+// kernarg of every front-end kernel, has no field for them: they travel in fields the Mixed instantiations do not otherwise read.
+// These two functions, and nothing else, know which.
+struct MixRows { const float *clean, *noise; int noise_stride; const PlanRow* plan; };
+void bind_mix_rows(FrontendParams& q, const MixRows& m) {
+    q.pcm = m.clean; q.carry = m.noise; q.carry_stride = m.noise_stride; q.carry_len = reinterpret_cast<const int32_t*>(m.plan);
+}
+__device__ __forceinline__ MixRows mix_rows(const FrontendParams& p) {
+    return {p.pcm, p.carry, p.carry_stride, reinterpret_cast<const PlanRow*>(p.carry_len)};
+}
 __device__ __forceinline__ int ragged_len(const FrontendParams& p, unsigned b) {      // clamped to [0, n_max] (kws_amd.h)
     const int n = p.lens ? p.lens[b] : p.n_max;
     return n < 0 ? 0 : (n > p.n_max ? p.n_max : n);
 }
 __device__ __forceinline__ int ragged_carry(const FrontendParams& p, unsigned b) { return p.carry_len ? p.carry_len[b] : p.n_carry; }
-__device__ __forceinline__ int ragged_frames(const FrontendParams& p, int total) { return total < p.fft ? 0 : 1 + (total - p.fft) / p.hop; }
-__device__ __forceinline__ int centred_frames(const FrontendParams& p, int n) { return n > p.fft / 2 ? 1 + n / p.hop : 0; }
-// frames of a whole utterance of n samples under the instantiation's framing
-template <bool CENTRED> __device__ __forceinline__ int utterance_frames(const FrontendParams& p, int n) {
-    if constexpr (CENTRED) return centred_frames(p, n);
-    else return ragged_frames(p, n);
+// frames of n samples: 1 + n / hop centred ones once half a frame fits, else the whole frames of the deploy graph ...
+__device__ __forceinline__ int frames_of(const FrontendParams& p, bool centred, int n) {
+    return centred ? (n > p.fft / 2 ? 1 + n / p.hop : 0) : (n < p.fft ? 0 : 1 + (n - p.fft) / p.hop);
 }
-
-// The gate of one stream of a ragged chunk (detector.py:162-183 for this stream alone): n == 0 skips the iteration -- carry
-// copied through, reset 0 (the GRU hands the state back over zero frames), skip set; otherwise the vad masks of its n new samples,
-// the next carry (all samples while fewer than 400, else what detector.py:181-182 keeps) and its frame count.
-template <typename SampleT>
-__device__ __forceinline__ void ragged_gate(const FrontendParams& p, unsigned b, float vad_sum, int n, int nc, const SampleT* row, int tid) {
-    const float* crow = p.carry + (size_t)b * p.carry_stride;
-    float* nrow = p.next + (size_t)b * (p.fft - 1);
-    const int total = nc + n;
-    const int keep = n == 0 || total < p.fft ? total : (total - p.fft) % p.hop + (p.fft - p.hop);
-    if (tid == 0) {
-        if (n > 0) {
-            vad_masks(vad_sum, p.vad_thres, b, p.restart, p.silent, p.reset);
-        } else {
-            p.silent[b] = 0;
-            p.reset[b] = 0;
+// ... and of row b of the launch: the kernel knows its framing from its tag (Mixed: the plan says), the kernels around it from p.centred
+template <typename Tag> __device__ __forceinline__ int row_frames(const FrontendParams& p, unsigned b) {
+    if constexpr (SampleOf<Tag>::mixed) return mix_rows(p).plan[b].frames;
+    else return frames_of(p, SampleOf<Tag>::centred, ragged_len(p, b));
+}
+__device__ __forceinline__ int row_frames(const FrontendParams& p, unsigned b) { return frames_of(p, p.centred != 0, ragged_len(p, b)); }
+// ---- block map.  XCD-aware block -> frame-block map.  Workgroups go round-robin over the 8 XCDs (blockIdx % 8), each with its own L2;
+// a stream's frames span two or three 16-frame blocks, every frame re-reads 240 samples of its predecessor, and with GATE
+// the block of a stream's first frame reads its whole row.  Giving XCD x the CONTIGUOUS run of blocks [x F, (x+1) F),
+// F = fft_blocks / 8, keeps all readers of a row behind one L2, so the PCM leaves HBM once (the grid is a multiple of 8).
+// The block's first frame is 16 x this; one at or past B * T is a padding block of the rounded-up grid.
+__device__ __forceinline__ unsigned frame_block(const FrontendParams& p) {
+    const unsigned xcd = blockIdx.x & 7u, seq = blockIdx.x >> 3;       // XCD, position in that XCD's sequence
+    const unsigned F = (unsigned)p.fft_blocks >> 3;                   // transform blocks per XCD
+    return xcd * F + seq;
+}
+// ---- gate.  GATE: the stream whose FIRST frame lies in this block gets its vad sum, masks and next carry here.  The row is requested
+// before the frames' samples and summed while those are in flight; the four wave totals cross at the transform's own first
+// barrier.  block_abs_sum's association term by term (thread t owns groups t, t + 256, ...; shuffle tree; the four wave
+// totals pairwise), so kws_vad, the stream manager's gate kernel and this one still take the same decision on the same
+// samples.  The transform reads the same row right behind: the PCM leaves HBM once (67 MB per 4096 x 3600-sample launch; gate
+// workgroups in front of the transforms pulled each XCD's 7 MB of rows through its 4 MB L2 first: 94-100 MB; round 3: 140).
+struct GateRow {      // workgroup-uniform: the stream handled the fast way (none), its chunk and carry lengths; this thread's four groups of its row
+    unsigned b = 0xffffffffu;
+    int n = 0, nc = 0;
+    float v[4][4];
+    __device__ __forceinline__ bool taken() const { return b != 0xffffffffu; }
+};
+// fetch the row, four float4 / short4 groups per thread (n <= 4096, a multiple of 4, the row aligned to a group)
+template <typename SampleT> __device__ __forceinline__ void gate_row_fetch(const SampleT* row, int n, int tid, float (&v)[4][4]) {
+    const int full = n >> 2;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int i = tid + 256 * k;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[k][e] = 0.f;
+        if (i < full) {
+            if constexpr (sizeof(SampleT) == 2) {
+                const short4 q4 = reinterpret_cast<const short4*>(row)[i];
+                v[k][0] = (float)q4.x * kPcmScale<SampleT>; v[k][1] = (float)q4.y * kPcmScale<SampleT>;
+                v[k][2] = (float)q4.z * kPcmScale<SampleT>; v[k][3] = (float)q4.w * kPcmScale<SampleT>;
+            } else {
+                const float4 q4 = reinterpret_cast<const float4*>(row)[i];
+                v[k][0] = q4.x; v[k][1] = q4.y; v[k][2] = q4.z; v[k][3] = q4.w;
+            }
         }
-        p.skip[b] = n == 0 ? 1 : 0;
-        p.frames[b] = n == 0 ? 0 : ragged_frames(p, total);
-        p.next_len[b] = keep;
     }
-    carry_tail<SampleT>(crow, nc, row, n, nrow, keep, tid, 256);
+}
+// What the gate writes for stream b once the vad sum of its row is known.  In lock step: the masks and the next carry, the same lengths for
+// every stream.  On the ragged feed (detector.py:162-183 for this stream alone): n == 0 skips the iteration -- carry copied through,
+// reset 0 (the GRU hands the state back over zero frames), skip set; otherwise the vad masks of its n new samples, the next carry (all
+// samples while fewer than 400, else what detector.py:181-182 keeps) and its frame count.
+template <bool RAGGED, typename SampleT>
+__device__ __forceinline__ void stream_gate(const FrontendParams& p, unsigned b, float vad_sum, int n, int nc, const SampleT* row, int tid) {
+    if constexpr (RAGGED) {
+        const float* crow = p.carry + (size_t)b * p.carry_stride;
+        float* nrow = p.next + (size_t)b * (p.fft - 1);
+        const int total = nc + n;
+        const int keep = n == 0 || total < p.fft ? total : (total - p.fft) % p.hop + (p.fft - p.hop);
+        if (tid == 0) {
+            if (n > 0) {
+                vad_masks(vad_sum, p.vad_thres, b, p.restart, p.silent, p.reset);
+            } else {
+                p.silent[b] = 0;
+                p.reset[b] = 0;
+            }
+            p.skip[b] = n == 0 ? 1 : 0;
+            p.frames[b] = n == 0 ? 0 : frames_of(p, false, total);
+            p.next_len[b] = keep;
+        }
+        carry_tail<SampleT>(crow, nc, row, n, nrow, keep, tid, 256);
+    } else {
+        if (tid == 0) vad_masks(vad_sum, p.vad_thres, b, p.restart, p.silent, p.reset);
+        carry_tail<SampleT>(p.carry + (size_t)b * p.n_carry, p.n_carry, row, n, p.next + (size_t)b * p.n_next, p.n_next, tid, 256);
+    }
+}
+// Every stream whose first frame lies in this block.  The first of them, if its row is short and aligned enough, goes the fast way:
+// its row is only requested here (g), summed behind the tap loads (gate_wave_sum) and gated behind barrier 1.  A second stream
+// starting in this block (chunks shorter than 16 frames) and long or unaligned rows are gated on the spot, one after the other; an
+// empty ragged chunk has nothing to sum.
+template <bool RAGGED, typename SampleT>
+__device__ __forceinline__ void gate_streams(const FrontendParams& p, unsigned f0, unsigned total, const SampleT* rows, int n_chunk, int tid, GateRow& g) {
+    const unsigned T = (unsigned)p.T;
+    const unsigned f_end = f0 + 16u < total ? f0 + 16u : total;
+    const unsigned sb0 = (f0 + T - 1u) / T;
+    for (unsigned sb = sb0; sb < (unsigned)p.B && sb * T < f_end; ++sb) {
+        const int n = RAGGED ? __builtin_amdgcn_readfirstlane(ragged_len(p, sb)) : n_chunk;
+        const int nc = RAGGED ? __builtin_amdgcn_readfirstlane(ragged_carry(p, sb)) : p.n_carry;
+        const SampleT* row = stream_row<RAGGED>(p, rows, n_chunk, sb);
+        if (RAGGED && n == 0) {
+            stream_gate<RAGGED, SampleT>(p, sb, 0.f, 0, nc, row, tid);
+        } else if (sb == sb0 && n <= 4096 && (n & 3) == 0 && (reinterpret_cast<uintptr_t>(row) & (4 * sizeof(SampleT) - 1)) == 0) {
+            g.b = sb; g.n = n; g.nc = nc;
+            gate_row_fetch<SampleT>(row, n, tid, g.v);
+        } else {
+            const float tot = block_abs_sum<SampleT>(row, n, nullptr);
+            stream_gate<RAGGED, SampleT>(p, sb, tot, n, nc, row, tid);
+            __syncthreads();
+        }
+    }
+}
+// the fetched row's |samples|, summed per wave into part[w]
+__device__ __forceinline__ void gate_wave_sum(const GateRow& g, int w, int lane, float* part) {
+    if (!g.taken()) return;
+    float acc = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)      // a thread without group k adds +0: the same bits as not adding
+        acc += (fabsf(g.v[k][0]) + fabsf(g.v[k][1])) + (fabsf(g.v[k][2]) + fabsf(g.v[k][3]));
+    acc = wave_sum_lane0(acc);
+    if (lane == 0) part[w] = acc;
+}
+// ---- tap load: the lane's 25 taps x[n1] = sample 16 n1 + n2 of its frame, one function per framing; false: a dead frame, nothing loaded
+// the frame's samples lie in one array: src points at tap 0
+template <typename SampleT> __device__ __forceinline__ void taps_from(const SampleT* src, float (&x)[25]) {
+#pragma unroll
+    for (int n1 = 0; n1 < 25; ++n1) x[n1] = (float)src[16 * n1] * kPcmScale<SampleT>;
+}
+// the frame may straddle the seam between the nc carried samples and the new ones: per-sample select
+template <typename SampleT> __device__ __forceinline__ void taps_across(const float* carry, int nc, const SampleT* chunk, int s0, float (&x)[25]) {
+#pragma unroll
+    for (int n1 = 0; n1 < 25; ++n1) {
+        const int idx = s0 + 16 * n1;
+        x[n1] = idx < nc ? carry[idx] : (float)chunk[idx - nc] * kPcmScale<SampleT>;
+    }
+}
+// lock step: the signal of stream sb is carry[sb] (n_carry samples, may be 0) followed by pcm[sb] (detector.py:179)
+template <typename SampleT>
+__device__ __forceinline__ bool taps_lockstep(const FrontendParams& p, const SampleT* rows, int n_chunk, unsigned sb, int st, int n2, float (&x)[25]) {
+    const float* xc_ = p.carry + (size_t)sb * p.n_carry;
+    const SampleT* xp_ = stream_row<false>(p, rows, n_chunk, sb);
+    const int s0 = st * p.hop + n2;
+    const bool seam = s0 - n2 < p.n_carry && s0 - n2 + 400 > p.n_carry;
+    const unsigned long long any_seam = __builtin_amdgcn_ballot_w64(seam);
+    const unsigned long long any_carry = __builtin_amdgcn_ballot_w64(s0 - n2 < p.n_carry);
+    if (!any_carry) {
+        // every frame of this wave lies in the new samples (all but the first rounds of a chunk)
+        taps_from(xp_ + (s0 - p.n_carry), x);
+    } else if (!any_seam && sizeof(SampleT) == 4) {
+        // whole frames, some in the carried samples, some in the new ones; one float array each
+        taps_from(s0 - n2 >= p.n_carry ? reinterpret_cast<const float*>(xp_) + (s0 - p.n_carry) : xc_ + s0, x);
+    } else {
+        // some frame of this wave straddles the seam (the first two or three frames of a chunk)
+        taps_across(xc_, p.n_carry, xp_, s0, x);
+    }
+    return true;
+}
+// ragged feed: stream sb's carry row (nc samples) followed by its n new samples; frames past its own count are dead
+template <typename SampleT> __device__ __forceinline__ bool taps_ragged(const FrontendParams& p, const SampleT* rows, unsigned sb, int st, int n2, float (&x)[25]) {
+    const int s0 = st * p.hop + n2;
+    const int n = ragged_len(p, sb), nc = ragged_carry(p, sb);
+    const bool live = n > 0 && st < frames_of(p, false, nc + n);
+    const float* xc_ = p.carry + (size_t)sb * p.carry_stride;
+    const SampleT* xp_ = stream_row<true>(p, rows, 0, sb);
+    const unsigned long long any_carry = __builtin_amdgcn_ballot_w64(live && s0 - n2 < nc);
+    if (!live) return false;
+    if (!any_carry) taps_from(xp_ + (s0 - nc), x);
+    else taps_across(xc_, nc, xp_, s0, x);
+    return true;
+}
+// Centred: frame st of utterance sb spans samples [s0, s0 + 400) of its reflected signal, under the window.  An interior frame (and,
+// for PRE, the sample in front of it) lies inside [0, n); a wave of interior frames loads as Utterances does, one with an edge frame
+// -- decided by ballot, as the seam path above -- takes the reflected index per tap.  Same operations on the same samples either
+// way: a frame's bits do not depend on its neighbours in the wave.
+template <typename Tag> __device__ __forceinline__ bool taps_centred(const FrontendParams& p, const float* rows, unsigned sb, int st, int n2, float (&x)[25]) {
+    constexpr bool PRE = SampleOf<Tag>::pre;
+    const float pre = p.pre_emphasis;
+    const int n = ragged_len(p, sb);
+    const bool live = st < row_frames<Tag>(p, sb);
+    const int s0 = st * p.hop - 200;
+    const unsigned long long any_edge = __builtin_amdgcn_ballot_w64(live && (s0 < 1 || s0 + 400 > n));
+    const float* row = rows + (size_t)sb * p.n_max;
+    if (!live) return false;
+    // The window: 25 registers from here on.  PRE multiplies in the path -- its edge path has no registers to spare and takes each value
+    // with its tap; without PRE the 25 products stand once behind both paths (as two copies the edge path spills).
+    const float* wtab = p.win + n2;
+    float win[25];
+    if (!PRE || !any_edge) {
+#pragma unroll
+        for (int n1 = 0; n1 < 25; ++n1) win[n1] = wtab[16 * n1];
+    }
+    if (!any_edge) {
+        const float* src = row + (s0 + n2);
+#pragma unroll
+        for (int n1 = 0; n1 < 25; ++n1) {
+            float t = src[16 * n1];
+            if constexpr (PRE) t = t - pre * src[16 * n1 - 1];
+            x[n1] = PRE ? t * win[n1] : t;
+        }
+    } else {
+#pragma unroll
+        for (int n1 = 0; n1 < 25; ++n1) {
+            int s = s0 + n2 + 16 * n1;                  // n >= 201: one reflection at most, then 0 <= s < n
+            s = s < 0 ? -s : s;
+            s = s >= n ? 2 * (n - 1) - s : s;
+            float t = row[s];
+            if constexpr (PRE) {
+                const float pred = pre * row[s > 0 ? s - 1 : 0];
+                t = s > 0 ? t - pred : t;
+            }
+            x[n1] = PRE ? t * wtab[16 * n1] : t;
+            // the rare path: five taps' loads in flight at a time, not 25 addresses (the register budget of six workgroups per CU)
+            if (n1 % 5 == 4) __builtin_amdgcn_sched_barrier(0);
+        }
+    }
+    if constexpr (!PRE) {
+#pragma unroll
+        for (int n1 = 0; n1 < 25; ++n1) x[n1] = x[n1] * win[n1];
+    }
+    return true;
+}
+// Frame f of the block -> its stream and frame in it, the framing the tag names, zeros for a dead frame.
+template <typename Tag, typename SampleT>
+__device__ __forceinline__ void frame_taps(const FrontendParams& p, const SampleT* rows, int n_chunk, unsigned f0, unsigned total, int f, int n2, float (&x)[25]) {
+    using V = SampleOf<Tag>;
+    unsigned fidx = f0 + f;
+    fidx = fidx < total ? fidx : total - 1;         // frames past the end redo the last one (finite values, never stored)
+    const unsigned sb = fidx / (unsigned)p.T;
+    const int st = (int)(fidx - sb * (unsigned)p.T);
+    bool live;
+    if constexpr (V::centred) {
+        static_assert(sizeof(SampleT) == 4, "the dataset's utterances are float PCM");
+        live = taps_centred<Tag>(p, rows, sb, st, n2, x);
+    } else if constexpr (V::lengths) {        // whole utterance sb: the first n samples of its row; a live frame (st < T_b) ends before sample n
+        live = st < row_frames<Tag>(p, sb);
+        if (live) taps_from(rows + (size_t)sb * p.n_max + (st * p.hop + n2), x);
+    } else if constexpr (V::ragged) {
+        live = taps_ragged(p, rows, sb, st, n2, x);
+    } else {
+        live = taps_lockstep(p, rows, n_chunk, sb, st, n2, x);
+    }
+    if (!live) {
+#pragma unroll
+        for (int n1 = 0; n1 < 25; ++n1) x[n1] = 0.f;
+    }
+}
+// ---- transform.  W400^{n2 k1}, k1 = 1..12, for this lane's n2: table [6 pairs of k1][16 n2] float4 = (cos, sin) of k1 = 2i+1 and 2i+2
+__device__ __forceinline__ void load_twiddles(const FrontendParams& p, int n2, float2 (&tw)[12]) {
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        const f32x4 t = reinterpret_cast<const f32x4*>(p.dft)[k * 16 + n2];
+        tw[2 * k] = make_float2(t[0], t[1]);
+        tw[2 * k + 1] = make_float2(t[2], t[3]);
+    }
+}
+// Stage 1 of frame f, column n2: the 25-point DFT of the lane's real taps, twiddled and parked in the planes
+__device__ __forceinline__ void dft25_to_planes(const float (&x)[25], const float2 (&tw)[12], char* lds, int f, int n2) {
+    // Z_b[c] = sum_a x[5a + b] W5^{ac}
+    float z0[5];
+    c32 z1[5], z2[5];
+#pragma unroll
+    for (int b = 0; b < 5; ++b) rdft5(x[b], x[5 + b], x[10 + b], x[15 + b], x[20 + b], z0[b], z1[b], z2[b]);
+    c32 Y[13];
+    {   // c = 0: real inputs again
+        float y0;
+        rdft5(z0[0], z0[1], z0[2], z0[3], z0[4], y0, Y[5], Y[10]);
+        Y[0] = {y0, 0.f};
+    }
+    {   // c = 1: Y1, Y6, Y11, Y16, Y21
+        c32 y16, y21;
+        cdft5(z1[0], cmul(z1[1], kW25c[1], -kW25s[1]), cmul(z1[2], kW25c[2], -kW25s[2]), cmul(z1[3], kW25c[3], -kW25s[3]),
+              cmul(z1[4], kW25c[4], -kW25s[4]), Y[1], Y[6], Y[11], y16, y21);
+        Y[9] = conj(y16);
+        Y[4] = conj(y21);
+    }
+    {   // c = 2: Y2, Y7, Y12, Y17, Y22
+        c32 y17, y22;
+        cdft5(z2[0], cmul(z2[1], kW25c[2], -kW25s[2]), cmul(z2[2], kW25c[4], -kW25s[4]), cmul(z2[3], kW25c[6], -kW25s[6]),
+              cmul(z2[4], kW25c[8], -kW25s[8]), Y[2], Y[7], Y[12], y17, y22);
+        Y[8] = conj(y17);
+        Y[3] = conj(y22);
+    }
+    // twiddle W400^{n2 k1} and park the row: plane k1, row f, column n2 ^ (f & 14) (the swizzle that makes the
+    // stage-2 ds_read_b128 of sixteen different rows conflict-free)
+    char* dst = lds + f * kRowBytes + ((n2 ^ (f & 14)) << 3);
+    *reinterpret_cast<float2*>(dst) = make_float2(Y[0].re, Y[0].im);
+#pragma unroll
+    for (int k1 = 1; k1 < 13; ++k1) {
+        const c32 t = cmul(Y[k1], tw[k1 - 1].x, -tw[k1 - 1].y);
+        *reinterpret_cast<float2*>(dst + k1 * kPlaneBytes) = make_float2(t.re, t.im);
+    }
+}
+// Stage 2: the 16-point FFT over n2 of row f of plane k1 (n2 = 4a + b, k2 = c + 4d) -> o[k2] = X[k1 + 25 k2]
+__device__ __forceinline__ void fft16_plane_row(const char* lds, int k1, int f, c32 (&o)[16]) {
+    const int sf = (f >> 1) & 7;
+    const char* row = lds + k1 * kPlaneBytes + f * kRowBytes;
+    c32 z[16];
+#pragma unroll
+    for (int pr = 0; pr < 8; ++pr) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(row + ((pr ^ sf) << 4));
+        z[2 * pr] = {v[0], v[1]};
+        z[2 * pr + 1] = {v[2], v[3]};
+    }
+    c32 u[4][4];
+#pragma unroll
+    for (int b = 0; b < 4; ++b) bfly4(z[b], z[4 + b], z[8 + b], z[12 + b], u[b][0], u[b][1], u[b][2], u[b][3]);
+    bfly4(u[0][0], u[1][0], u[2][0], u[3][0], o[0], o[4], o[8], o[12]);
+    {   // c = 1: W16^1, W16^2, W16^3
+        const c32 v1 = cmul(u[1][1], kW16c1, -kW16s1);
+        const c32 v2 = {(u[2][1].re + u[2][1].im) * kR2, (u[2][1].im - u[2][1].re) * kR2};
+        const c32 v3 = cmul(u[3][1], kW16s1, -kW16c1);
+        bfly4(u[0][1], v1, v2, v3, o[1], o[5], o[9], o[13]);
+    }
+    {   // c = 2: W16^2, W16^4 = -i, W16^6
+        const c32 v1 = {(u[1][2].re + u[1][2].im) * kR2, (u[1][2].im - u[1][2].re) * kR2};
+        const c32 v2 = {u[2][2].im, -u[2][2].re};
+        const c32 v3 = {(u[3][2].im - u[3][2].re) * kR2, -(u[3][2].re + u[3][2].im) * kR2};
+        bfly4(u[0][2], v1, v2, v3, o[2], o[6], o[10], o[14]);
+    }
+    {   // c = 3: W16^3, W16^6, W16^9 = -W16^1
+        const c32 v1 = cmul(u[1][3], kW16s1, -kW16c1);
+        const c32 v2 = {(u[2][3].im - u[2][3].re) * kR2, -(u[2][3].re + u[2][3].im) * kR2};
+        const c32 v3 = cmul(u[3][3], -kW16c1, kW16s1);
+        bfly4(u[0][3], v1, v2, v3, o[3], o[7], o[11], o[15]);
+    }
+}
+// |X| for the magnitude epilogues, |X|^2 (utils/mfcc.py:77: the power spectrum itself, no sqrt) for the others
+template <int EPI> __device__ __forceinline__ void spectrum_values(const c32 (&o)[16], float (&mag)[16]) {
+#pragma unroll
+    for (int k2 = 0; k2 < 16; ++k2) {
+        const float pw = fmaf(o[k2].re, o[k2].re, o[k2].im * o[k2].im);
+        mag[k2] = EPI == kEpiMel || EPI == kEpiLinear ? __builtin_amdgcn_sqrtf(pw) : pw;
+    }
+}
+// the padding rows of the bin-order spectrum that the last 4-bin group may read
+__device__ __forceinline__ void zero_spectrum_padding(float* S, int tid) {
+    if (tid < 16 * (kSpecRows - 201)) S[201 * 16 + tid] = 0.f;
+}
+// The values of (k1, frame f) in bin order: S[bin][frame], 64 B rows.  bin = k1 + 25 k2 folded at 200
+__device__ __forceinline__ void spectrum_store(const float (&mag)[16], int k1, int f, int tid, float* S) {
+    if (k1 <= 12) {
+#pragma unroll
+        for (int k2 = 0; k2 < 8; ++k2) S[(k1 + 25 * k2) * 16 + f] = mag[k2];
+        if (k1 == 0) {
+            S[200 * 16 + f] = mag[8];
+        } else {
+#pragma unroll
+            for (int k2 = 8; k2 < 16; ++k2) S[(400 - 25 * k2 - k1) * 16 + f] = mag[k2];
+        }
+    }
+    zero_spectrum_padding(S, tid);
+}
+// ---- mix, the Mixed input stage in place of the transform.  The block's 16 frames lie in one row of the call or straddle several (p.T < 16: up to 16).  Lanes 0..15 of wave 0 read
+// their frame's row plan and park where its 201 clean magnitudes and its noise slice's begin (-1: none) behind the
+// spectrum and the DCT partials; then element i = 201 f + bin of the block goes to thread i % 256: consecutive lanes read
+// consecutive floats of a row (a row is 804 contiguous bytes in both sets), whatever the plan says.
+template <int EPI> __device__ __forceinline__ void mix_to_spectrum(const FrontendParams& p, const MixRows rows, unsigned f0, unsigned total, int tid, float* __restrict__ S, char* __restrict__ park) {
+    typedef long long i64x2 __attribute__((ext_vector_type(2)));                            // where a frame's clean and noise rows begin (-1: none):
+    i64x2* at = reinterpret_cast<i64x2*>(park);                                                        // [16], one 16-byte read per element
+    float* fac = reinterpret_cast<float*>(at + 16);                                         // [16]
+    if (tid < 16) {
+        const unsigned fo = f0 + tid;
+        long long ca = -1, na = -1;
+        float fc = 0.f;
+        if (fo < total) {
+            const unsigned r = fo / (unsigned)p.T;
+            const int t = (int)(fo - r * (unsigned)p.T);
+            const PlanRow& plan = rows.plan[r];
+            const int b = plan.src, k = plan.noise;
+            if (b >= 0 && t < plan.frames) {
+                ca = ((long long)b * p.T + t) * kLinearBins;
+                if (k >= 0 && t < plan.noise_avail) {
+                    na = ((long long)k * rows.noise_stride + plan.start + t) * kLinearBins;
+                    fc = __int_as_float(plan.factor_bits);
+                }
+            }
+        }
+        at[tid] = i64x2{ca, na}; fac[tid] = fc;
+    }
+    zero_spectrum_padding(S, tid);
+    lds_barrier();
+#pragma unroll
+    for (int j = 0; j < (16 * kLinearBins + 255) / 256; ++j) {
+        const int i = tid + 256 * j;
+        if (i < 16 * kLinearBins) {
+            const int fr = i / kLinearBins, bin = i - fr * kLinearBins;
+            const i64x2 a = at[fr];
+            const long long ca = a[0], na = a[1];
+            float v = 0.f;
+            if (ca >= 0) {
+                v = rows.clean[ca + bin];
+                if (na >= 0) v = v + fac[fr] * rows.noise[na + bin];   // reader.py:238,252: two roundings (contraction is off)
+            }
+            S[bin * 16 + fr] = EPI == kEpiMel ? v : v * v;         // reader.py:267-268, utils/mfcc.py:77
+        }
+    }
+}
+// ---- epilogues.  kEpiLinear: the 16 rows of this block are elements [201 f0, 201 (f0 + 16)) of spec: consecutive lanes store consecutive floats
+__device__ __forceinline__ void linear_rows_store(const FrontendParams& p, const float* S, unsigned f0, unsigned total, int tid) {
+    float* out = p.mel + (size_t)f0 * kLinearBins;
+    const unsigned left = total - f0;
+    const int count = kLinearBins * (int)(left < 16u ? left : 16u);
+    for (int i = tid; i < count; i += 256) {
+        const int fr = i / kLinearBins, bin = i - fr * kLinearBins;
+        out[i] = S[bin * 16 + fr];
+    }
+}
+// Basis fragments of wave w's mel tile: the first kMelRegs groups of its run wait in registers (the loads fly while the spectrum is
+// written and the workgroup meets at the barrier); a longer run streams the rest
+struct MelTile {             // first 4-bin group and number of groups (multiple of 4; zero-padded table); the table [tile][group / 4][64 lanes]
+    int lo4, n;              // float4 (the fragments of four consecutive groups side by side); the fragments in registers
+    const f32x4* A;
+    float a[kMelRegs];
+};
+template <int MT, int EPI> __device__ __forceinline__ void mel_tile_fetch(const FrontendParams& p, int w, int lane, MelTile& t) {
+    t.lo4 = w < MT ? p.mel_lo[w] : 0;
+    t.n = EPI != kEpiLinear && w < MT ? p.mel_cnt[w] : 0;
+    t.A = reinterpret_cast<const f32x4*>(p.melw) + ((size_t)(w < MT ? p.mel_off[w] : 0) / 4 * 64 + lane);
+    if (t.n > 0) {         // every tile's table holds at least kMelRegs groups (zero padded): no clamping, one base + immediate offsets
+#pragma unroll
+        for (int e4 = 0; e4 < kMelRegs / 4; ++e4) {
+            const f32x4 v = t.A[e4 * 64];
+            t.a[4 * e4] = v[0]; t.a[4 * e4 + 1] = v[1]; t.a[4 * e4 + 2] = v[2]; t.a[4 * e4 + 3] = v[3];
+        }
+    }
+}
+// Mel projection: wave m = mel tile m over its contiguous run of 4-bin groups.  A = basis fragments [tile][group][64 lanes],
+// B = four spectrum rows (k = g) x 16 frames; two accumulators break the dependent chain.  D[filter 16w + 4g + e][frame f]
+__device__ __forceinline__ f32x4 mel_project(const MelTile& t, const float* S, int lane) {
+    const float* Sg = S + t.lo4 * 64 + lane;
+    f32x4 acc0 = splat4(0.f), acc1 = splat4(0.f);
+    // runs are padded to multiples of four groups: four spectrum reads in flight, then four MFMAs
+    static_for<0, kMelRegs / 4>([&](auto c) {
+        constexpr int e0 = 4 * decltype(c)::value;
+        if (e0 < t.n) {
+            const float b0 = Sg[e0 * 64], b1 = Sg[(e0 + 1) * 64], b2 = Sg[(e0 + 2) * 64], b3 = Sg[(e0 + 3) * 64];
+            acc0 = mfma4(t.a[e0], b0, acc0);
+            acc1 = mfma4(t.a[e0 + 1], b1, acc1);
+            acc0 = mfma4(t.a[e0 + 2], b2, acc0);
+            acc1 = mfma4(t.a[e0 + 3], b3, acc1);
+        }
+    });
+    for (int e = kMelRegs; e < t.n; e += 4) {
+        const float b0 = Sg[e * 64], b1 = Sg[(e + 1) * 64], b2 = Sg[(e + 2) * 64], b3 = Sg[(e + 3) * 64];
+        const f32x4 v = t.A[(size_t)(e / 4) * 64];
+        acc0 = mfma4(v[0], b0, acc0);
+        acc1 = mfma4(v[1], b1, acc1);
+        acc0 = mfma4(v[2], b2, acc0);
+        acc1 = mfma4(v[3], b3, acc1);
+    }
+    return acc0 + acc1;
+}
+// filters 16w + 4g .. + 3 of frame fo: one 16-byte store where rows keep that alignment, else filter by filter
+__device__ __forceinline__ void mel_row_store(const FrontendParams& p, f32x4 r, unsigned fo, int w, int g) {
+    float* out = p.mel + (size_t)fo * p.n_mel;
+    const int c0 = 16 * w + 4 * g;
+    if ((p.n_mel & 3) == 0 && (reinterpret_cast<uintptr_t>(p.mel) & 15) == 0) {
+        if (c0 < p.n_mel) *reinterpret_cast<f32x4*>(out + c0) = r;
+    } else {
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (c0 + e < p.n_mel) out[c0 + e] = r[e];
+    }
+}
+// kEpiMfcc: the mel C tile r is also the B operand of the DCT (k = g <-> filter 16w + 4g + e in k-chunk e), as the GRU kernels'
+// exchange layout: S = 10 log10(max(1e-10, mel)) (utils/mfcc.py:23; v_log_f32 is log2, operands >= 1e-10: no
+// denormals) goes straight back into the matrix pipe against D^T packed the same way (p.dct: [tile][coefficient
+// tile][64 lanes] float4 over e; rows of filters >= n_mel are zero -- those lanes hold log(floor) = -100 dB, not 0).
+// The tiles' partial products meet in the half of LDS the spectrum does not use.
+__device__ __forceinline__ void mfcc_partials(const FrontendParams& p, f32x4 r, int w, int lane, char* lds) {
+    constexpr float kDbPerLog2 = 3.0102999566398120f;           // 10 log10(2)
+    float s[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) s[e] = __builtin_amdgcn_logf(fmaxf(r[e], 1e-10f)) * kDbPerLog2;
+    f32x4* part = reinterpret_cast<f32x4*>(lds + kSpecRows * 64);
+    for (int ct = 0; ct < p.dct_tiles; ++ct) {
+        const f32x4 d = reinterpret_cast<const f32x4*>(p.dct)[(size_t)(w * p.dct_tiles + ct) * 64 + lane];
+        f32x4 c0 = splat4(0.f), c1 = splat4(0.f);
+        c0 = mfma4(d[0], s[0], c0);
+        c1 = mfma4(d[1], s[1], c1);
+        c0 = mfma4(d[2], s[2], c0);
+        c1 = mfma4(d[3], s[3], c1);
+        part[(w * kMaxDctTiles + ct) * 64 + lane] = c0 + c1;
+    }
+}
+// ... and wave ct adds the tiles' partial products, always in tile order, and stores coefficients 16 ct + 4g + e of frame f:
+// the static third of the row, zero for a frame past its row's own count
+template <int MT, typename Tag> __device__ __forceinline__ void mfcc_reduce_store(const FrontendParams& p, unsigned f0, unsigned total, int w, int lane, const char* lds) {
+    if (w >= p.dct_tiles) return;
+    const int g = lane >> 4, f = lane & 15;
+    const f32x4* part = reinterpret_cast<const f32x4*>(lds + kSpecRows * 64);
+    f32x4 c = part[w * 64 + lane];
+#pragma unroll
+    for (int m = 1; m < MT; ++m) c = c + part[(m * kMaxDctTiles + w) * 64 + lane];
+    const unsigned fo = f0 + f;
+    if (fo < total) {
+        const unsigned sb = fo / (unsigned)p.T;
+        const bool live = (int)(fo - sb * (unsigned)p.T) < row_frames<Tag>(p, sb);
+        float* out = p.mel + (size_t)fo * (3 * p.n_mfcc);
+        const int c0 = 16 * w + 4 * g;
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            if (c0 + e < p.n_mfcc) out[c0 + e] = live ? c[e] : 0.f;
+    }
 }
 }  // namespace
 
 // kEpiLinear aims at one workgroup per CU fewer: it is bound by its stores (804 B per frame against 160 B of mel), and with the 96
 // registers of five workgroups the pre-emphasis edge path keeps its 25 taps, window values and predecessors without scratch
 constexpr int fe_occupancy(int epi) { return epi == kEpiLinear && KWS_FE_OCC > 1 ? KWS_FE_OCC - 1 : KWS_FE_OCC; }
-template <int MT, typename SampleTag, bool GATE>
-__global__ void __launch_bounds__(256, fe_occupancy(SampleOf<SampleTag>::epi)) mel_fft400_kernel(const FrontendParams p) {
-    using SampleT = typename SampleOf<SampleTag>::type;
-    constexpr bool RAGGED = SampleOf<SampleTag>::ragged;
-    constexpr bool LENGTHS = SampleOf<SampleTag>::lengths;
-    constexpr int EPI = SampleOf<SampleTag>::epi;
-    constexpr bool CENTRED = SampleOf<SampleTag>::centred, PRE = SampleOf<SampleTag>::pre;
-    constexpr bool MIXED = SampleOf<SampleTag>::mixed;
-    static_assert(!MIXED || EPI != kEpiLinear, "the mix feeds the feature epilogues");
-    static_assert(GATE || !RAGGED, "the ragged feed always carries the gate");
-    static_assert(!(GATE && LENGTHS), "whole utterances have no stream gate");
-    __shared__ __attribute__((aligned(16))) char lds[kFftLds];
-    const int tid = threadIdx.x;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int lane = tid & 63;
-    const int hi = lane >> 4, lo = lane & 15;          // stage 1: (frame j of 4, n2); stage 2 / MFMA: (g, frame f of 16)
-    const unsigned total = (unsigned)p.B * (unsigned)p.T;
-    // XCD-aware block -> frame-block map.  Workgroups go round-robin over the 8 XCDs (blockIdx % 8), each with its own L2;
-    // a stream's frames span two or three 16-frame blocks, every frame re-reads 240 samples of its predecessor, and with GATE
-    // the block of a stream's first frame reads its whole row.  Giving XCD x the CONTIGUOUS run of blocks [x F, (x+1) F),
-    // F = fft_blocks / 8, keeps all readers of a row behind one L2, so the PCM leaves HBM once (the grid is a multiple of 8).
-    constexpr float kScale = sizeof(SampleT) == 2 ? 1.0f / 32768.0f : 1.0f;
-    const SampleT* chunk_all = sizeof(SampleT) == 2 ? reinterpret_cast<const SampleT*>(p.pcm_i16) : reinterpret_cast<const SampleT*>(p.pcm);
-    const int n_chunk = p.n_samples - p.n_carry;
-    const unsigned xcd = blockIdx.x & 7u, seq = blockIdx.x >> 3;       // XCD, position in that XCD's sequence
-    const unsigned F = (unsigned)p.fft_blocks >> 3;                   // transform blocks per XCD
-    const unsigned local = seq;                                         // this XCD's transform block index
-    const unsigned blk = xcd * F + local;
-    const unsigned f0 = blk * 16u;
-    if (f0 >= total) return;                            // padding block of the rounded-up grid (uniform: before any barrier)
 #ifdef KWS_FE_TIMING       // tools/ubench/fe_phases.hip: s_memtime at the phase boundaries of every wave
 #define KWS_FE_STAMP(i) do { if (lane == 0) p.timing[((size_t)blk * 4 + w) * 8 + (i)] = __builtin_readcyclecounter(); } while (0)
 #else
 #define KWS_FE_STAMP(i) do {} while (0)
 #endif
-    KWS_FE_STAMP(0);
-
-    // GATE: the stream whose FIRST frame lies in this block gets its vad sum, masks and next carry here.  The row is requested
-    // before the frames' samples and summed while those are in flight; the four wave totals cross at the transform's own first
-    // barrier.  block_abs_sum's association term by term (thread t owns groups t, t + 256, ...; shuffle tree; the four wave
-    // totals pairwise), so kws_vad, the stream manager's gate kernel and this one still take the same decision on the same
-    // samples.  The transform reads the same row right behind: the PCM leaves HBM once (67 MB per 4096 x 3600-sample launch; gate
-    // workgroups in front of the transforms pulled each XCD's 7 MB of rows through its 4 MB L2 first: 94-100 MB; round 3: 140).
+template <int MT, typename SampleTag, bool GATE>
+__global__ void __launch_bounds__(256, fe_occupancy(SampleOf<SampleTag>::epi)) mel_fft400_kernel(const FrontendParams p) {
+    using V = SampleOf<SampleTag>;
+    using SampleT = typename V::type;
+    constexpr int EPI = V::epi;
+    static_assert(!V::mixed || EPI != kEpiLinear, "the mix feeds the feature epilogues");
+    static_assert(GATE || !V::ragged, "the ragged feed always carries the gate");
+    static_assert(!(GATE && V::lengths), "whole utterances have no stream gate");
+    __shared__ __attribute__((aligned(16))) char lds[kFftLds];
     __shared__ float gate_part[4];
-    unsigned gate_b = 0xffffffffu;                      // workgroup-uniform: the stream handled the fast way
-    int gate_n = 0, gate_nc = 0;                        // RAGGED: its chunk and carry lengths
-    float gate_v[4][4];
-    if constexpr (GATE) {
-        const unsigned T = (unsigned)p.T;
-        const unsigned f_end = f0 + 16u < total ? f0 + 16u : total;
-        const unsigned sb0 = (f0 + T - 1u) / T;
-        const bool fast = n_chunk <= 4096 && (n_chunk & 3) == 0 && ((size_t)n_chunk * sizeof(SampleT)) % (4 * sizeof(SampleT)) == 0 &&
-                          (reinterpret_cast<uintptr_t>(chunk_all) & (4 * sizeof(SampleT) - 1)) == 0;
-        for (unsigned sb = sb0; sb < (unsigned)p.B && sb * T < f_end; ++sb) {
-            if constexpr (RAGGED) {
-                // rows of n_max samples, of which the stream's own n count; lengths read once per workgroup (uniform)
-                const int n = __builtin_amdgcn_readfirstlane(ragged_len(p, sb)), nc = __builtin_amdgcn_readfirstlane(ragged_carry(p, sb));
-                const SampleT* row = chunk_all + (size_t)sb * p.n_max;
-                if (n == 0) {
-                    ragged_gate<SampleT>(p, sb, 0.f, 0, nc, row, tid);
-                } else if (sb == sb0 && n <= 4096 && (n & 3) == 0 && (reinterpret_cast<uintptr_t>(row) & (4 * sizeof(SampleT) - 1)) == 0) {
-                    gate_b = sb; gate_n = n; gate_nc = nc;
-                    const int full = n >> 2;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const int i = tid + 256 * k;
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) gate_v[k][e] = 0.f;
-                        if (i < full) {
-                            if constexpr (sizeof(SampleT) == 2) {
-                                const short4 q4 = reinterpret_cast<const short4*>(row)[i];
-                                gate_v[k][0] = (float)q4.x * kScale; gate_v[k][1] = (float)q4.y * kScale; gate_v[k][2] = (float)q4.z * kScale; gate_v[k][3] = (float)q4.w * kScale;
-                            } else {
-                                const float4 q4 = reinterpret_cast<const float4*>(row)[i];
-                                gate_v[k][0] = q4.x; gate_v[k][1] = q4.y; gate_v[k][2] = q4.z; gate_v[k][3] = q4.w;
-                            }
-                        }
-                    }
-                } else {
-                    const float tot = block_abs_sum<SampleT>(row, n, nullptr);
-                    ragged_gate<SampleT>(p, sb, tot, n, nc, row, tid);
-                    __syncthreads();
-                }
-                continue;
-            }
-            const SampleT* row = chunk_all + (size_t)sb * n_chunk;
-            if (fast && sb == sb0) {
-                gate_b = sb;
-                const int full = n_chunk >> 2;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int i = tid + 256 * k;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) gate_v[k][e] = 0.f;
-                    if (i < full) {
-                        if constexpr (sizeof(SampleT) == 2) {
-                            const short4 q4 = reinterpret_cast<const short4*>(row)[i];
-                            gate_v[k][0] = (float)q4.x * kScale; gate_v[k][1] = (float)q4.y * kScale; gate_v[k][2] = (float)q4.z * kScale; gate_v[k][3] = (float)q4.w * kScale;
-                        } else {
-                            const float4 q4 = reinterpret_cast<const float4*>(row)[i];
-                            gate_v[k][0] = q4.x; gate_v[k][1] = q4.y; gate_v[k][2] = q4.z; gate_v[k][3] = q4.w;
-                        }
-                    }
-                }
-            } else {
-                // a second stream starting in this block (chunks shorter than 16 frames), long or unaligned rows: one after the other
-                const float tot = block_abs_sum<SampleT>(row, n_chunk, nullptr);
-                if (tid == 0) vad_masks(tot, p.vad_thres, sb, p.restart, p.silent, p.reset);
-                carry_tail<SampleT>(p.carry + (size_t)sb * p.n_carry, p.n_carry, row, n_chunk, p.next + (size_t)sb * p.n_next, p.n_next, tid, 256);
-                __syncthreads();
-            }
-        }
-    }
-
-    // ---- stage 1: this wave's four frames ----
-    if constexpr (!MIXED) {
-        const int n2 = lo;
-        const int f = 4 * w + hi;
-        unsigned fidx = f0 + f;
-        fidx = fidx < total ? fidx : total - 1;         // frames past the end redo the last one (finite values, never stored)
-        const unsigned sb = fidx / (unsigned)p.T;
-        const int st = (int)(fidx - sb * (unsigned)p.T);
+    const int tid = threadIdx.x;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int lane = tid & 63;
+    const int hi = lane >> 4, lo = lane & 15;          // stage 1: (frame j of 4, n2); stage 2 / MFMA: (g, frame f of 16)
+    const unsigned total = (unsigned)p.B * (unsigned)p.T;
+    const SampleT* rows = pcm_rows<SampleT>(p);
+    const int n_chunk = p.n_samples - p.n_carry;
+    const unsigned blk = frame_block(p), f0 = blk * 16u;
+    if (f0 >= total) return;                            // padding block (uniform: before any barrier)
+    KWS_FE_STAMP(0);
+    GateRow gate;
+    if constexpr (GATE) gate_streams<V::ragged>(p, f0, total, rows, n_chunk, tid, gate);
+    float mag[16];
+    if constexpr (!V::mixed) {          // stage 1: this wave's four frames
         float x[25];
-        if constexpr (CENTRED) {
-            static_assert(sizeof(SampleT) == 4, "the dataset's utterances are float PCM");
-            // utterance sb: frame st spans samples [s0, s0 + 400) of its reflected signal.  An interior frame (and, for PRE, the
-            // sample in front of it) lies inside [0, n); a wave of interior frames loads as Utterances does, one with an edge frame
-            // -- decided by ballot, as the seam path below -- takes the reflected index per tap.  Same operations on the same
-            // samples either way: a frame's bits do not depend on its neighbours in the wave.
-            const int n = ragged_len(p, sb);
-            const bool live = st < centred_frames(p, n);
-            const int s0 = st * p.hop - 200;
-            const unsigned long long any_edge = __builtin_amdgcn_ballot_w64(live && (s0 < 1 || s0 + 400 > n));
-            const SampleT* row = chunk_all + (size_t)sb * p.n_max;
-            if (!live) {
-#pragma unroll
-                for (int n1 = 0; n1 < 25; ++n1) x[n1] = 0.f;
-            } else {
-                float win[25];
-#pragma unroll
-                for (int n1 = 0; n1 < 25; ++n1) win[n1] = p.win[16 * n1 + n2];
-                if (!any_edge) {
-                    const SampleT* src = row + (s0 + n2);
-#pragma unroll
-                    for (int n1 = 0; n1 < 25; ++n1) {
-                        float v = src[16 * n1];
-                        if constexpr (PRE) v = v - p.pre_emphasis * src[16 * n1 - 1];
-                        x[n1] = v * win[n1];
-                    }
-                } else {
-#pragma unroll
-                    for (int n1 = 0; n1 < 25; ++n1) {
-                        int s = s0 + n2 + 16 * n1;                  // n >= 201: one reflection at most, then 0 <= s < n
-                        s = s < 0 ? -s : s;
-                        s = s >= n ? 2 * (n - 1) - s : s;
-                        float v = row[s];
-                        if constexpr (PRE) {
-                            const float pred = p.pre_emphasis * row[s > 0 ? s - 1 : 0];
-                            v = s > 0 ? v - pred : v;
-                        }
-                        x[n1] = v * win[n1];
-                        // the rare path: five taps' loads in flight at a time, not 25 addresses (the register budget of six workgroups per CU)
-                        if (n1 % 5 == 4) __builtin_amdgcn_sched_barrier(0);
-                    }
-                }
-            }
-        } else if constexpr (LENGTHS) {
-            // utterance sb: the first n samples of its row; a live frame (st < T_b) ends before sample n, a dead one loads nothing
-            const bool live = st < ragged_frames(p, ragged_len(p, sb));
-            const SampleT* src = chunk_all + (size_t)sb * p.n_max + (st * p.hop + n2);
-            if (!live) {
-#pragma unroll
-                for (int n1 = 0; n1 < 25; ++n1) x[n1] = 0.f;
-            } else {
-#pragma unroll
-                for (int n1 = 0; n1 < 25; ++n1) x[n1] = (float)src[16 * n1] * kScale;
-            }
-        } else if constexpr (RAGGED) {
-            const int s0 = st * p.hop + n2;
-            // stream sb: carry row (nc samples) followed by its n new samples; frames past its own count are dead: no loads, zeros
-            const int n = ragged_len(p, sb), nc = ragged_carry(p, sb);
-            const bool live = n > 0 && st < ragged_frames(p, nc + n);
-            const float* xc_ = p.carry + (size_t)sb * p.carry_stride;
-            const SampleT* xp_ = chunk_all + (size_t)sb * p.n_max;
-            const unsigned long long any_carry = __builtin_amdgcn_ballot_w64(live && s0 - n2 < nc);
-            if (!live) {
-#pragma unroll
-                for (int n1 = 0; n1 < 25; ++n1) x[n1] = 0.f;
-            } else if (!any_carry) {
-                const SampleT* src = xp_ + (s0 - nc);
-#pragma unroll
-                for (int n1 = 0; n1 < 25; ++n1) x[n1] = (float)src[16 * n1] * kScale;
-            } else {
-#pragma unroll
-                for (int n1 = 0; n1 < 25; ++n1) {
-                    const int idx = s0 + 16 * n1;
-                    x[n1] = idx < nc ? xc_[idx] : (float)xp_[idx - nc] * kScale;
-                }
-            }
-        } else {
-            // the signal of stream sb is carry[sb] (n_carry samples, may be 0) followed by pcm[sb] (detector.py:179)
-            const float* xc_ = p.carry + (size_t)sb * p.n_carry;
-            const SampleT* xp_ = chunk_all + (size_t)sb * n_chunk;
-            const int s0 = st * p.hop + n2;
-            const bool seam = s0 - n2 < p.n_carry && s0 - n2 + 400 > p.n_carry;
-            const unsigned long long any_seam = __builtin_amdgcn_ballot_w64(seam);
-            const unsigned long long any_carry = __builtin_amdgcn_ballot_w64(s0 - n2 < p.n_carry);
-            if (!any_carry) {
-                // every frame of this wave lies in the new samples (all but the first rounds of a chunk)
-                const SampleT* src = xp_ + (s0 - p.n_carry);
-#pragma unroll
-                for (int n1 = 0; n1 < 25; ++n1) x[n1] = (float)src[16 * n1] * kScale;
-            } else if (!any_seam && sizeof(SampleT) == 4) {
-                // whole frames, some in the carried samples, some in the new ones; one float array each
-                const float* src = s0 - n2 >= p.n_carry ? reinterpret_cast<const float*>(xp_) + (s0 - p.n_carry) : xc_ + s0;
-#pragma unroll
-                for (int n1 = 0; n1 < 25; ++n1) x[n1] = src[16 * n1];
-            } else {
-                // some frame of this wave straddles the seam (the first two or three frames of a chunk): per-sample select
-#pragma unroll
-                for (int n1 = 0; n1 < 25; ++n1) {
-                    const int idx = s0 + 16 * n1;
-                    x[n1] = idx < p.n_carry ? xc_[idx] : (float)xp_[idx - p.n_carry] * kScale;
-                }
-            }
-        }
-        // W400^{n2 k1}, k1 = 1..12, for this lane's n2 (cos, sin): [12][16] float2
-        float2 tw[12];          // table: [6 pairs of k1][16 n2] float4 = (cos, sin) of k1 = 2i+1 and 2i+2: six 16-byte loads
-#pragma unroll
-        for (int k = 0; k < 6; ++k) {
-            const f32x4 t = reinterpret_cast<const f32x4*>(p.dft)[k * 16 + n2];
-            tw[2 * k] = make_float2(t[0], t[1]);
-            tw[2 * k + 1] = make_float2(t[2], t[3]);
-        }
+        float2 tw[12];
+        frame_taps<SampleTag>(p, rows, n_chunk, f0, total, 4 * w + hi, lo, x);
+        load_twiddles(p, lo, tw);
 #ifdef KWS_FE_TIMING
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         KWS_FE_STAMP(1);
 #endif
-        if (GATE && gate_b != 0xffffffffu) {
-            float acc = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; ++k)      // a thread without group k adds +0: the same bits as not adding
-                acc += (fabsf(gate_v[k][0]) + fabsf(gate_v[k][1])) + (fabsf(gate_v[k][2]) + fabsf(gate_v[k][3]));
-            acc = wave_sum_lane0(acc);
-            if (lane == 0) gate_part[w] = acc;
-        }
-        // Z_b[c] = sum_a x[5a + b] W5^{ac}
-        float z0[5];
-        c32 z1[5], z2[5];
-#pragma unroll
-        for (int b = 0; b < 5; ++b) rdft5(x[b], x[5 + b], x[10 + b], x[15 + b], x[20 + b], z0[b], z1[b], z2[b]);
-        c32 Y[13];
-        {   // c = 0: real inputs again
-            float y0;
-            rdft5(z0[0], z0[1], z0[2], z0[3], z0[4], y0, Y[5], Y[10]);
-            Y[0] = {y0, 0.f};
-        }
-        {   // c = 1: Y1, Y6, Y11, Y16, Y21
-            c32 y16, y21;
-            cdft5(z1[0], cmul(z1[1], kW25c[1], -kW25s[1]), cmul(z1[2], kW25c[2], -kW25s[2]), cmul(z1[3], kW25c[3], -kW25s[3]),
-                  cmul(z1[4], kW25c[4], -kW25s[4]), Y[1], Y[6], Y[11], y16, y21);
-            Y[9] = conj(y16);
-            Y[4] = conj(y21);
-        }
-        {   // c = 2: Y2, Y7, Y12, Y17, Y22
-            c32 y17, y22;
-            cdft5(z2[0], cmul(z2[1], kW25c[2], -kW25s[2]), cmul(z2[2], kW25c[4], -kW25s[4]), cmul(z2[3], kW25c[6], -kW25s[6]),
-                  cmul(z2[4], kW25c[8], -kW25s[8]), Y[2], Y[7], Y[12], y17, y22);
-            Y[8] = conj(y17);
-            Y[3] = conj(y22);
-        }
-        // twiddle W400^{n2 k1} and park the row: plane k1, row f, column n2 ^ (f & 14) (the swizzle that makes the
-        // stage-2 ds_read_b128 of sixteen different rows conflict-free)
-        char* dst = lds + f * kRowBytes + ((n2 ^ (f & 14)) << 3);
-        *reinterpret_cast<float2*>(dst) = make_float2(Y[0].re, Y[0].im);
-#pragma unroll
-        for (int k1 = 1; k1 < 13; ++k1) {
-            const c32 t = cmul(Y[k1], tw[k1 - 1].x, -tw[k1 - 1].y);
-            *reinterpret_cast<float2*>(dst + k1 * kPlaneBytes) = make_float2(t.re, t.im);
-        }
+        if constexpr (GATE) gate_wave_sum(gate, w, lane, gate_part);
+        dft25_to_planes(x, tw, lds, 4 * w + hi, lo);
     }
     KWS_FE_STAMP(2);
-    if constexpr (!MIXED) __syncthreads();
+    if constexpr (!V::mixed) __syncthreads();
     KWS_FE_STAMP(3);
-    if (GATE && gate_b != 0xffffffffu) {
-        if constexpr (RAGGED) {
-            ragged_gate<SampleT>(p, gate_b, (gate_part[0] + gate_part[1]) + (gate_part[2] + gate_part[3]), gate_n, gate_nc,
-                                 chunk_all + (size_t)gate_b * p.n_max, tid);
-        } else {
-            if (tid == 0) vad_masks((gate_part[0] + gate_part[1]) + (gate_part[2] + gate_part[3]), p.vad_thres, gate_b, p.restart, p.silent, p.reset);
-            carry_tail<SampleT>(p.carry + (size_t)gate_b * p.n_carry, p.n_carry, chunk_all + (size_t)gate_b * n_chunk, n_chunk,
-                                p.next + (size_t)gate_b * p.n_next, p.n_next, tid, 256);
-        }
-    }
-
-    // ---- stage 2: pass q = w, k1 = 4w + g ----
-    const int g = hi, f = lo, q = w;
-    float mag[16];
-    if constexpr (!MIXED) {
-        const int k1 = 4 * q + g < 12 ? 4 * q + g : 12;         // lanes past k1 = 12 recompute plane 12 and store nothing
-        const int sf = (f >> 1) & 7;
-        const char* row = lds + k1 * kPlaneBytes + f * kRowBytes;
-        c32 z[16];
-#pragma unroll
-        for (int pr = 0; pr < 8; ++pr) {
-            const f32x4 v = *reinterpret_cast<const f32x4*>(row + ((pr ^ sf) << 4));
-            z[2 * pr] = {v[0], v[1]};
-            z[2 * pr + 1] = {v[2], v[3]};
-        }
-        // 16-point FFT, n2 = 4a + b, k2 = c + 4d
-        c32 u[4][4];
-#pragma unroll
-        for (int b = 0; b < 4; ++b) bfly4(z[b], z[4 + b], z[8 + b], z[12 + b], u[b][0], u[b][1], u[b][2], u[b][3]);
+    if (GATE && gate.taken())           // the four wave totals have met
+        stream_gate<V::ragged>(p, gate.b, (gate_part[0] + gate_part[1]) + (gate_part[2] + gate_part[3]), V::ragged ? gate.n : n_chunk, gate.nc,
+                               stream_row<V::ragged>(p, rows, n_chunk, gate.b), tid);
+    if constexpr (!V::mixed) {          // stage 2: pass q = w, k1 = 4w + g; lanes past k1 = 12 recompute plane 12 and store nothing
         c32 o[16];
-        bfly4(u[0][0], u[1][0], u[2][0], u[3][0], o[0], o[4], o[8], o[12]);
-        {   // c = 1: W16^1, W16^2, W16^3
-            const c32 v1 = cmul(u[1][1], kW16c1, -kW16s1);
-            const c32 v2 = {(u[2][1].re + u[2][1].im) * kR2, (u[2][1].im - u[2][1].re) * kR2};
-            const c32 v3 = cmul(u[3][1], kW16s1, -kW16c1);
-            bfly4(u[0][1], v1, v2, v3, o[1], o[5], o[9], o[13]);
-        }
-        {   // c = 2: W16^2, W16^4 = -i, W16^6
-            const c32 v1 = {(u[1][2].re + u[1][2].im) * kR2, (u[1][2].im - u[1][2].re) * kR2};
-            const c32 v2 = {u[2][2].im, -u[2][2].re};
-            const c32 v3 = {(u[3][2].im - u[3][2].re) * kR2, -(u[3][2].re + u[3][2].im) * kR2};
-            bfly4(u[0][2], v1, v2, v3, o[2], o[6], o[10], o[14]);
-        }
-        {   // c = 3: W16^3, W16^6, W16^9 = -W16^1
-            const c32 v1 = cmul(u[1][3], kW16s1, -kW16c1);
-            const c32 v2 = {(u[2][3].im - u[2][3].re) * kR2, -(u[2][3].re + u[2][3].im) * kR2};
-            const c32 v3 = cmul(u[3][3], -kW16c1, kW16s1);
-            bfly4(u[0][3], v1, v2, v3, o[3], o[7], o[11], o[15]);
-        }
-#pragma unroll
-        for (int k2 = 0; k2 < 16; ++k2) {
-            if constexpr (EPI == kEpiMel || EPI == kEpiLinear) mag[k2] = __builtin_amdgcn_sqrtf(fmaf(o[k2].re, o[k2].re, o[k2].im * o[k2].im));
-            else mag[k2] = fmaf(o[k2].re, o[k2].re, o[k2].im * o[k2].im);            // utils/mfcc.py:77: the power spectrum itself
-        }
+        fft16_plane_row(lds, 4 * w + hi < 12 ? 4 * w + hi : 12, lo, o);
+        spectrum_values<EPI>(o, mag);
     }
-    // basis fragments of this wave's mel tile: the first kMelRegs groups of its run wait in registers (the loads fly while the
-    // spectrum is written and the workgroup meets at the barrier); a longer run streams the rest
-    const int lo4 = w < MT ? p.mel_lo[w] : 0, n = EPI != kEpiLinear && w < MT ? p.mel_cnt[w] : 0;   // first 4-bin group, number of groups (multiple of 4; zero-padded table)
-    // table: [tile][group / 4][64 lanes] float4 (the fragments of four consecutive groups side by side): one 16-byte load each
-    const f32x4* A = reinterpret_cast<const f32x4*>(p.melw) + ((size_t)(w < MT ? p.mel_off[w] : 0) / 4 * 64 + lane);
-    float a[kMelRegs];
-    if (n > 0) {         // every tile's table holds at least kMelRegs groups (zero padded): no clamping, one base + immediate offsets
-#pragma unroll
-        for (int e4 = 0; e4 < kMelRegs / 4; ++e4) {
-            const f32x4 v = A[e4 * 64];
-            a[4 * e4] = v[0]; a[4 * e4 + 1] = v[1]; a[4 * e4 + 2] = v[2]; a[4 * e4 + 3] = v[3];
-        }
-    }
+    MelTile tile;
+    mel_tile_fetch<MT, EPI>(p, w, lane, tile);
     KWS_FE_STAMP(4);
-    if constexpr (!MIXED) lds_barrier();             // every wave has read its planes: the spectrum takes their place
+    if constexpr (!V::mixed) lds_barrier();             // every wave has read its planes: the spectrum takes their place
     KWS_FE_STAMP(5);
-    // ---- |X| in bin order: S[bin][frame], 64 B rows.  bin = k1 + 25 k2 folded at 200 ----
     float* S = reinterpret_cast<float*>(lds);
-    if constexpr (MIXED) {
-        // The block's 16 frames lie in one row of the call or straddle several (p.T < 16: up to 16).  Lanes 0..15 of wave 0 read
-        // their frame's row plan and park where its 201 clean magnitudes and its noise slice's begin (-1: none) behind the
-        // spectrum and the DCT partials; then element i = 201 f + bin of the block goes to thread i % 256: consecutive lanes read
-        // consecutive floats of a row (a row is 804 contiguous bytes in both sets), whatever the plan says.
-        long long* at = reinterpret_cast<long long*>(lds + kSpecRows * 64 + 4 * kMaxDctTiles * 64 * 16);      // [16][clean, noise]
-        float* fac = reinterpret_cast<float*>(at + 32);                                                        // [16]
-        if (tid < 16) {
-            const unsigned fo = f0 + tid;
-            long long ca = -1, na = -1;
-            float fc = 0.f;
-            if (fo < total) {
-                const unsigned r = fo / (unsigned)p.T;
-                const int t = (int)(fo - r * (unsigned)p.T);
-                const int32_t* plan = p.carry_len + (size_t)r * kPlanInts;
-                const int b = plan[0], k = plan[1];
-                if (b >= 0 && t < plan[5]) {
-                    ca = ((long long)b * p.T + t) * kLinearBins;
-                    if (k >= 0 && t < plan[3]) {
-                        na = ((long long)k * p.carry_stride + plan[2] + t) * kLinearBins;
-                        fc = __int_as_float(plan[4]);
-                    }
-                }
-            }
-            at[2 * tid] = ca; at[2 * tid + 1] = na; fac[tid] = fc;
-        }
-        if (tid < 16 * (kSpecRows - 201)) S[201 * 16 + tid] = 0.f;     // padding rows the last block may read
-        lds_barrier();
-#pragma unroll
-        for (int j = 0; j < (16 * kLinearBins + 255) / 256; ++j) {
-            const int i = tid + 256 * j;
-            if (i < 16 * kLinearBins) {
-                const int fr = i / kLinearBins, bin = i - fr * kLinearBins;
-                const long long ca = at[2 * fr], na = at[2 * fr + 1];
-                float v = 0.f;
-                if (ca >= 0) {
-                    v = p.pcm[ca + bin];
-                    if (na >= 0) v = v + fac[fr] * p.carry[na + bin];   // reader.py:238,252: two roundings (contraction is off)
-                }
-                S[bin * 16 + fr] = EPI == kEpiMel ? v : v * v;         // reader.py:267-268, utils/mfcc.py:77
-            }
-        }
-    } else {
-        const int k1 = 4 * q + g;
-        if (k1 <= 12) {
-#pragma unroll
-            for (int k2 = 0; k2 < 8; ++k2) S[(k1 + 25 * k2) * 16 + f] = mag[k2];
-            if (k1 == 0) {
-                S[200 * 16 + f] = mag[8];
-            } else {
-#pragma unroll
-                for (int k2 = 8; k2 < 16; ++k2) S[(400 - 25 * k2 - k1) * 16 + f] = mag[k2];
-            }
-        }
-        if (tid < 16 * (kSpecRows - 201)) S[201 * 16 + tid] = 0.f;     // padding rows the last block may read
-    }
+    if constexpr (V::mixed) mix_to_spectrum<EPI>(p, mix_rows(p), f0, total, tid, S, lds + kSpecRows * 64 + kDctPartBytes);   // parked behind the spectrum and the DCT partials
+    else spectrum_store(mag, 4 * w + hi, lo, tid, S);
     lds_barrier();
     KWS_FE_STAMP(6);
     if constexpr (EPI == kEpiLinear) {
-        // the 16 rows of this block are elements [201 f0, 201 (f0 + 16)) of spec: consecutive lanes store consecutive floats
-        float* out = p.mel + (size_t)f0 * kLinearBins;
-        const unsigned left = total - f0;
-        const int count = kLinearBins * (int)(left < 16u ? left : 16u);
-        for (int i = tid; i < count; i += 256) {
-            const int fr = i / kLinearBins, bin = i - fr * kLinearBins;
-            out[i] = S[bin * 16 + fr];
-        }
+        linear_rows_store(p, S, f0, total, tid);
         return;
     }
-
-    // ---- mel projection: wave m = mel tile m over its contiguous run of 4-bin groups.  A = basis fragments
-    // [tile][group][64 lanes], B = four spectrum rows (k = g) x 16 frames; two accumulators break the dependent chain ----
-    // (kEpiMfcc: every tile takes part in the DCT, one without a weight -- n == 0 -- with mel = 0)
-    const bool project = EPI == kEpiMfcc ? w < MT : n > 0;
+    const bool project = EPI == kEpiMfcc ? w < MT : tile.n > 0;      // kEpiMfcc: every tile takes part in the DCT, one without a weight with mel = 0
 #ifdef KWS_ABL_NOMEL          // experiment builds only (tools/build_variant.sh nomel -DKWS_ABL_NOMEL): the kernel without its mel projection
     if (project && p.n_mel < 0) {
 #else
     if (project) {
 #endif
-        const float* Sg = S + lo4 * 64 + lane;
-        f32x4 acc0 = splat4(0.f), acc1 = splat4(0.f);
-        // runs are padded to multiples of four groups: four spectrum reads in flight, then four MFMAs
-        static_for<0, kMelRegs / 4>([&](auto c) {
-            constexpr int e0 = 4 * decltype(c)::value;
-            if (e0 < n) {
-                const float b0 = Sg[e0 * 64], b1 = Sg[(e0 + 1) * 64], b2 = Sg[(e0 + 2) * 64], b3 = Sg[(e0 + 3) * 64];
-                acc0 = mfma4(a[e0], b0, acc0);
-                acc1 = mfma4(a[e0 + 1], b1, acc1);
-                acc0 = mfma4(a[e0 + 2], b2, acc0);
-                acc1 = mfma4(a[e0 + 3], b3, acc1);
-            }
-        });
-        for (int e = kMelRegs; e < n; e += 4) {
-            const float b0 = Sg[e * 64], b1 = Sg[(e + 1) * 64], b2 = Sg[(e + 2) * 64], b3 = Sg[(e + 3) * 64];
-            const f32x4 v = A[(size_t)(e / 4) * 64];
-            acc0 = mfma4(v[0], b0, acc0);
-            acc1 = mfma4(v[1], b1, acc1);
-            acc0 = mfma4(v[2], b2, acc0);
-            acc1 = mfma4(v[3], b3, acc1);
-        }
-        const f32x4 r = acc0 + acc1;
-        // D[filter 16w + 4g + e][frame f]
-        const unsigned fo = f0 + f;
-        if constexpr (EPI == kEpiMfcc) {
-            // This C tile is also the B operand of the DCT (k = g <-> filter 16w + 4g + e in k-chunk e), as the GRU kernels'
-            // exchange layout: S = 10 log10(max(1e-10, mel)) (utils/mfcc.py:23; v_log_f32 is log2, operands >= 1e-10: no
-            // denormals) goes straight back into the matrix pipe against D^T packed the same way (p.dct: [tile][coefficient
-            // tile][64 lanes] float4 over e; rows of filters >= n_mel are zero -- those lanes hold log(floor) = -100 dB, not 0).
-            // The tiles' partial products meet in the half of LDS the spectrum does not use.
-            constexpr float kDbPerLog2 = 3.0102999566398120f;           // 10 log10(2)
-            float s[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) s[e] = __builtin_amdgcn_logf(fmaxf(r[e], 1e-10f)) * kDbPerLog2;
-            f32x4* part = reinterpret_cast<f32x4*>(lds + kSpecRows * 64);
-            for (int ct = 0; ct < p.dct_tiles; ++ct) {
-                const f32x4 d = reinterpret_cast<const f32x4*>(p.dct)[(size_t)(w * p.dct_tiles + ct) * 64 + lane];
-                f32x4 c0 = splat4(0.f), c1 = splat4(0.f);
-                c0 = mfma4(d[0], s[0], c0);
-                c1 = mfma4(d[1], s[1], c1);
-                c0 = mfma4(d[2], s[2], c0);
-                c1 = mfma4(d[3], s[3], c1);
-                part[(w * kMaxDctTiles + ct) * 64 + lane] = c0 + c1;
-            }
-        } else if (fo < total) {
-            float* out = p.mel + (size_t)fo * p.n_mel;
-            const int c0 = 16 * w + 4 * g;
-            if ((p.n_mel & 3) == 0 && (reinterpret_cast<uintptr_t>(p.mel) & 15) == 0) {
-                if (c0 < p.n_mel) *reinterpret_cast<f32x4*>(out + c0) = r;
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (c0 + e < p.n_mel) out[c0 + e] = r[e];
-            }
-        }
+        const f32x4 r = mel_project(tile, S, lane);
+        if constexpr (EPI == kEpiMfcc) mfcc_partials(p, r, w, lane, lds);
+        else if (f0 + lo < total) mel_row_store(p, r, f0 + lo, w, hi);
     }
     if constexpr (EPI == kEpiMfcc) {
-        // wave ct adds the tiles' partial products, always in tile order, and stores coefficients 16 ct + 4g + e of frame f:
-        // the static third of the row, zero for a frame past its utterance's own count
         lds_barrier();
-        if (w < p.dct_tiles) {
-            const f32x4* part = reinterpret_cast<const f32x4*>(lds + kSpecRows * 64);
-            f32x4 c = part[w * 64 + lane];
-#pragma unroll
-            for (int m = 1; m < MT; ++m) c = c + part[(m * kMaxDctTiles + w) * 64 + lane];
-            const unsigned fo = f0 + f;
-            if (fo < total) {
-                const unsigned sb = fo / (unsigned)p.T;
-                bool live;
-                if constexpr (MIXED) live = (int)(fo - sb * (unsigned)p.T) < p.carry_len[(size_t)sb * kPlanInts + 5];
-                else live = (int)(fo - sb * (unsigned)p.T) < utterance_frames<CENTRED>(p, ragged_len(p, sb));
-                float* out = p.mel + (size_t)fo * (3 * p.n_mfcc);
-                const int c0 = 16 * w + 4 * g;
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (c0 + e < p.n_mfcc) out[c0 + e] = live ? c[e] : 0.f;
-            }
-        }
+        mfcc_reduce_store<MT, SampleTag>(p, f0, total, w, lane, lds);
     }
     KWS_FE_STAMP(7);
 }
@@ -726,8 +772,7 @@ __global__ void __launch_bounds__(256) linear_energy_kernel(const FrontendParams
     __shared__ double part[4];
     const unsigned b = blockIdx.x;
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int n = ragged_len(p, b);
-    const int tb = p.centred ? centred_frames(p, n) : ragged_frames(p, n);      // <= p.T: n <= n_max
+    const int tb = row_frames(p, b);      // <= p.T: n <= n_max
     const float* rows = p.mel + (size_t)b * p.T * kLinearBins;
     double sum = 0.0;
     for (int t = w; t < tb; t += 4) {
@@ -779,15 +824,7 @@ __global__ void __launch_bounds__(256) augment_plan_kernel(const AugmentRows a, 
     }
     const int avail = nf > st ? nf - st : 0;
     const bool mix = factor != 0.f && avail > 0;
-    int32_t* plan = a.plan + (size_t)r * kPlanInts;
-    plan[0] = ok ? b : -1;
-    plan[1] = mix ? k : -1;
-    plan[2] = mix ? st : 0;
-    plan[3] = mix ? avail : 0;
-    plan[4] = __float_as_int(mix ? factor : 0.f);
-    plan[5] = tr;
-    plan[6] = 0;
-    plan[7] = 0;
+    reinterpret_cast<PlanRow*>(a.plan)[r] = {ok ? b : -1, mix ? k : -1, mix ? st : 0, mix ? avail : 0, __float_as_int(mix ? factor : 0.f), tr, {0, 0}};
     // the fewest samples that hold tr frames: 1 + n / hop centred frames for n > fft / 2, 1 + (n - fft) / hop deploy frames
     int n = 0;
     if (tr > 0) n = centred ? ((tr - 1) * hop > fft / 2 ? (tr - 1) * hop : fft / 2 + 1) : fft + (tr - 1) * hop;
@@ -807,7 +844,7 @@ __global__ void __launch_bounds__(256) mfcc_delta_kernel(const FrontendParams p)
     const unsigned c = (unsigned)(i - row * nc);
     const unsigned b = (unsigned)(row / (unsigned)p.T);
     const int t = (int)(row - (unsigned long long)b * (unsigned)p.T);
-    const int tb = p.centred ? centred_frames(p, ragged_len(p, b)) : ragged_frames(p, ragged_len(p, b));
+    const int tb = row_frames(p, b);
     float* out = p.mel + (size_t)row * (3 * nc);
     float d1 = 0.f, d2 = 0.f;
     if (t < tb) {
@@ -820,82 +857,81 @@ __global__ void __launch_bounds__(256) mfcc_delta_kernel(const FrontendParams p)
     out[nc + c] = d1;
     out[2 * nc + c] = d2;
 }
-
+// ---- launchers.  p on the grid of `total` frames: 16 per workgroup, rounded up to a multiple of 8 for the kernel's XCD-aware block map
+static FrontendParams on_fft400_grid(FrontendParams q, long long total) {        // total < 2^31 (checked by the callers)
+    q.fft_blocks = (int)(((total + 15) / 16 + 7) / 8 * 8);
+    return q;
+}
 template <typename SampleT, bool GATE>
-static hipError_t launch_fft400_tiles(const FrontendParams& p, unsigned grid, hipStream_t st) {
-    return with_int<1, 2, 3, 4>(p.mel_tiles, [&](auto mt) {
-        return launch_lds<mel_fft400_kernel<mt(), SampleT, GATE>>(dim3(grid), dim3(256), 0, st, p);
+static hipError_t launch_fft400_tiles(const FrontendParams& q, hipStream_t st) {
+    return with_int<1, 2, 3, 4>(q.mel_tiles, [&](auto mt) {
+        return launch_lds<mel_fft400_kernel<mt(), SampleT, GATE>>(dim3((unsigned)q.fft_blocks), dim3(256), 0, st, q);
     });
 }
-template <int EPI>
-static hipError_t launch_features_tiles(const FrontendParams& p, unsigned grid, hipStream_t st) {
-    if (!p.centred) return launch_fft400_tiles<Utterances<float, EPI>, false>(p, grid, st);
-    if (p.pre_emphasis != 0.f) return launch_fft400_tiles<DatasetFrames<float, EPI, true>, false>(p, grid, st);
-    return launch_fft400_tiles<DatasetFrames<float, EPI, false>, false>(p, grid, st);
+// whole utterances under the handle's framing: launch(tag) starts the instantiation of that tag
+template <int EPI, typename F>
+static hipError_t with_utterance_tag(const FrontendParams& q, F&& launch) {
+    if (!q.centred) return launch(Utterances<float, EPI>{});
+    if (q.pre_emphasis != 0.f) return launch(DatasetFrames<float, EPI, true>{});
+    return launch(DatasetFrames<float, EPI, false>{});
+}
+// The feature q names -- mel, power mel, or MFCC with mfcc_delta_kernel behind it -- of `total` frames; launch(epi) starts the
+// transform with that epilogue
+template <typename F>
+static hipError_t launch_feature(const FrontendParams& q, long long total, hipStream_t st, F&& launch) {
+    if (q.n_mfcc == 0) return q.power == 2 ? launch(std::integral_constant<int, kEpiPower>{}) : launch(std::integral_constant<int, kEpiMel>{});
+    if (q.n_mfcc > 16 * kMaxDctTiles || q.dct_tiles != (q.n_mfcc + 15) / 16 || !q.dct) return hipErrorInvalidValue;
+    const hipError_t e = launch(std::integral_constant<int, kEpiMfcc>{});
+    if (e != hipSuccess) return e;
+    const unsigned long long cells = (unsigned long long)total * (unsigned)q.n_mfcc;       // < 2^36
+    return launch_lds<mfcc_delta_kernel>(dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, q);
 }
 
 hipError_t launch_features_fft400(const FrontendParams& p, int B, hipStream_t st) {
     const long long total = (long long)B * p.T;        // 0 < total < 2^31 (checked by the caller)
     if (p.fft != 400 || p.gate || p.pcm_i16 || p.n_carry != 0 || (p.centred && !p.win)) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)(((total + 15) / 16 + 7) / 8 * 8);
-    FrontendParams q = p;
-    q.fft_blocks = (int)grid;
+    FrontendParams q = on_fft400_grid(p, total);
     q.B = B;
-    if (p.n_mfcc == 0) return p.power == 2 ? launch_features_tiles<kEpiPower>(q, grid, st) : launch_features_tiles<kEpiMel>(q, grid, st);
-    if (p.n_mfcc > 16 * kMaxDctTiles || p.dct_tiles != (p.n_mfcc + 15) / 16 || !p.dct) return hipErrorInvalidValue;
-    hipError_t e = launch_features_tiles<kEpiMfcc>(q, grid, st);
-    if (e != hipSuccess) return e;
-    const unsigned long long cells = (unsigned long long)total * (unsigned)p.n_mfcc;       // < 2^36
-    return launch_lds<mfcc_delta_kernel>(dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, q);
+    return launch_feature(q, total, st, [&](auto epi) {
+        return with_utterance_tag<epi()>(q, [&](auto tag) { return launch_fft400_tiles<decltype(tag), false>(q, st); });
+    });
 }
 
 hipError_t launch_linear_fft400(const FrontendParams& p, int B, int32_t* frames_out, float* energy_out, hipStream_t st) {
     const long long total = (long long)B * p.T;        // 0 < total < 2^31 (checked by the caller)
     if (p.fft != 400 || p.gate || p.pcm_i16 || p.n_carry != 0 || (p.centred && !p.win) || total <= 0) return hipErrorInvalidValue;
-    const unsigned grid = (unsigned)(((total + 15) / 16 + 7) / 8 * 8);
-    FrontendParams q = p;
-    q.fft_blocks = (int)grid;
+    FrontendParams q = on_fft400_grid(p, total);
     q.B = B;
-    hipError_t e;
-    if (!p.centred) e = launch_lds<mel_fft400_kernel<1, Utterances<float, kEpiLinear>, false>>(dim3(grid), dim3(256), 0, st, q);
-    else if (p.pre_emphasis != 0.f) e = launch_lds<mel_fft400_kernel<1, DatasetFrames<float, kEpiLinear, true>, false>>(dim3(grid), dim3(256), 0, st, q);
-    else e = launch_lds<mel_fft400_kernel<1, DatasetFrames<float, kEpiLinear, false>, false>>(dim3(grid), dim3(256), 0, st, q);
+    const hipError_t e = with_utterance_tag<kEpiLinear>(q, [&](auto tag) {        // no mel tile: the MT = 1 instantiation
+        return launch_lds<mel_fft400_kernel<1, decltype(tag), false>>(dim3((unsigned)q.fft_blocks), dim3(256), 0, st, q);
+    });
     if (e != hipSuccess) return e;
     return launch_lds<linear_energy_kernel>(dim3((unsigned)B), dim3(256), 0, st, q, frames_out, energy_out);
 }
 
-hipError_t launch_augment_fft400(const FrontendParams& p, const AugmentRows& rows, hipStream_t st) {
+hipError_t launch_augment_fft400(const FrontendParams& p, const float* spec, const float* noise_spec, const AugmentRows& rows, hipStream_t st) {
     const long long total = (long long)rows.R * rows.T;        // 0 < total < 2^31 (checked by the caller)
     if (p.fft != 400 || total <= 0 || total >= (1LL << 31) || !rows.plan) return hipErrorInvalidValue;
     if ((long long)rows.T * p.hop + p.fft > 0x7fffffffLL) return hipErrorInvalidValue;      // the plan's sample counts are int32
-    hipError_t e = launch_lds<augment_plan_kernel>(dim3((unsigned)((rows.R + 255) / 256)), dim3(256), 0, st, rows, p.fft, p.hop, p.centred);
+    const hipError_t e = launch_lds<augment_plan_kernel>(dim3((unsigned)((rows.R + 255) / 256)), dim3(256), 0, st, rows, p.fft, p.hop, p.centred);
     if (e != hipSuccess) return e;
-    const unsigned grid = (unsigned)(((total + 15) / 16 + 7) / 8 * 8);
-    FrontendParams q = p;
-    q.fft_blocks = (int)grid;
+    FrontendParams q = on_fft400_grid(p, total);
     q.B = rows.R; q.T = rows.T;
     q.gate = 0; q.pcm_i16 = nullptr; q.n_carry = 0; q.n_samples = 0;
-    q.carry_len = rows.plan; q.lens = rows.plan + (size_t)rows.R * kPlanInts; q.n_max = 0x7fffffff; q.carry_stride = rows.Tn;
-    if (p.n_mfcc == 0)
-        return p.power == 2 ? launch_fft400_tiles<Mixed<kEpiPower>, false>(q, grid, st) : launch_fft400_tiles<Mixed<kEpiMel>, false>(q, grid, st);
-    if (p.n_mfcc > 16 * kMaxDctTiles || p.dct_tiles != (p.n_mfcc + 15) / 16 || !p.dct) return hipErrorInvalidValue;
-    e = launch_fft400_tiles<Mixed<kEpiMfcc>, false>(q, grid, st);
-    if (e != hipSuccess) return e;
-    const unsigned long long cells = (unsigned long long)total * (unsigned)p.n_mfcc;       // < 2^36
-    return launch_lds<mfcc_delta_kernel>(dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, st, q);
+    bind_mix_rows(q, {spec, noise_spec, rows.Tn, reinterpret_cast<const PlanRow*>(rows.plan)});
+    // behind the plan, per row a sample count with T_r frames under the handle's framing: mfcc_delta_kernel's edges (nothing clamps it)
+    q.lens = rows.plan + (size_t)rows.R * kPlanInts; q.n_max = 0x7fffffff;
+    return launch_feature(q, total, st, [&](auto epi) { return launch_fft400_tiles<Mixed<epi()>, false>(q, st); });
 }
 
 hipError_t launch_mel_fft400(const FrontendParams& p, int B, hipStream_t st) {
-    const long long total = (long long)B * p.T;        // < 2^31 (checked by the caller)
-    const unsigned grid = (unsigned)(((total + 15) / 16 + 7) / 8 * 8);     // multiple of 8: the kernel's XCD-aware block map
-    FrontendParams q = p;
-    q.fft_blocks = (int)grid;
+    const FrontendParams q = on_fft400_grid(p, (long long)B * p.T);        // < 2^31 (checked by the caller)
     if (p.frames) {
         if (!p.gate || p.fft != 400) return hipErrorInvalidValue;
-        return p.pcm_i16 ? launch_fft400_tiles<RaggedRows<int16_t>, true>(q, grid, st) : launch_fft400_tiles<RaggedRows<float>, true>(q, grid, st);
+        return p.pcm_i16 ? launch_fft400_tiles<RaggedRows<int16_t>, true>(q, st) : launch_fft400_tiles<RaggedRows<float>, true>(q, st);
     }
-    if (!p.gate) return p.pcm_i16 ? launch_fft400_tiles<int16_t, false>(q, grid, st) : launch_fft400_tiles<float, false>(q, grid, st);
-    return p.pcm_i16 ? launch_fft400_tiles<int16_t, true>(q, grid, st) : launch_fft400_tiles<float, true>(q, grid, st);
+    if (!p.gate) return p.pcm_i16 ? launch_fft400_tiles<int16_t, false>(q, st) : launch_fft400_tiles<float, false>(q, st);
+    return p.pcm_i16 ? launch_fft400_tiles<int16_t, true>(q, st) : launch_fft400_tiles<float, true>(q, st);
 }
 
 }  // namespace kws

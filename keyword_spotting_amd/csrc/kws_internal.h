@@ -420,23 +420,23 @@ hipError_t launch_features_fft400(const FrontendParams& p, int B, hipStream_t st
 // it one workgroup per utterance that writes frames_out [B] = T_b and energy_out [B] = sum_{t < T_b} sum_f spec^2
 hipError_t launch_linear_fft400(const FrontendParams& p, int B, int32_t* frames_out, float* energy_out, hipStream_t st);
 // ... and the reader's noise mix in front of the three feature epilogues (kws_frontend_augment; the Mixed tag): R rows of T frames, row r
-// = features(spec[src[r]] + factor_r * noise_spec[noise[r]][start[r] ..]).  augment_plan_kernel turns the row arrays into plan and
-// lens; the feature launch reads them through FrontendParams as laid out here (no field of its own: the struct is the kernarg of every
-// front-end kernel):
-//   pcm = the clean spectra [B, T, 201], carry = the noise spectra [K, Tn, 201], carry_stride = Tn, mel = out [R, T, feature]
-//   carry_len = plan [R][kPlanInts]: {b or -1, k or -1, start, noise frames from start on, bits of factor, T_r, 0, 0}
-//   lens = [R] a sample count whose frame count under the handle's framing is T_r (what mfcc_delta_kernel derives its edges from),
-//   n_max = INT_MAX (nothing clamps it)
+// = features(spec[src[r]] + factor_r * noise_spec[noise[r]][start[r] ..]) into p.mel = out [R, T, feature].  augment_plan_kernel turns
+// the row arrays into one PlanRow per row; how the spectra and the plan reach the feature launch through FrontendParams (no field of
+// its own: the struct is the kernarg of every front-end kernel) is the business of bind_mix_rows / mix_rows in fft_frontend.hip alone.
 constexpr int kPlanInts = 8;
+struct PlanRow {     // clean row b and noise row k (-1: a zero row / nothing mixed in), first noise frame and how many from there on, the float factor, T_r
+    int32_t src, noise, start, noise_avail, factor_bits, frames, pad[2];
+};
+static_assert(sizeof(PlanRow) == kPlanInts * sizeof(int32_t), "a plan row is kPlanInts ints");
 struct AugmentRows {
     const int32_t *frames, *noise_frames;      // [B], [K]
     const float *energy, *noise_energy;        // [B], [K]
     const int32_t *src, *noise, *start;        // [R]
     const float* gain_db;                      // [R]
     int B, K, R, T, Tn;
-    int32_t* plan;                             // [R][kPlanInts] followed by lens [R]
+    int32_t* plan;                             // PlanRow [R] followed by lens [R]
 };
-hipError_t launch_augment_fft400(const FrontendParams& p, const AugmentRows& rows, hipStream_t st);
+hipError_t launch_augment_fft400(const FrontendParams& p, const float* spec, const float* noise_spec, const AugmentRows& rows, hipStream_t st);
 hipError_t launch_carry_tail(const float* carry, int n_carry, const float* chunk, int n_chunk, float* next, int n_next, int B,
                              hipStream_t st);
 
