@@ -679,6 +679,81 @@ int kws_step_bank_window(kws_handle model, kws_bank_handle bank, const int32_t* 
                          const char* label1, const char* label2, const uint8_t* clear_before, float* softmax1, float* softmax2,
                          int32_t* hit /*[B]*/, uint8_t* restart, void* stream);
 
+/* Training of the stack itself (main.py's training loop on models/rnn_ctc.py:34-101,179-284): the L-layer GRU and the class projection
+ * under tf.nn.ctc_loss, with tf.clip_by_global_norm and tf.train.AdamOptimizer or MomentumOptimizer(0.9, use_nesterov=True).  A train
+ * handle owns the parameters (the canonical blob of kws_weights_nbytes, on the device), the optimiser's moments and the step count.
+ *
+ * The graph of one step, from the zero state (initial_state=None):
+ *   layer l     TF 1.x GRUCell as kws_step computes it: [r,u] = sigma([x,h].Wg + bg), c = tanh([x, r o h].Wc + bc), h' = u o h + (1-u) o c;
+ *               dynamic_rnn(sequence_length): at t >= seq_len[b] the state is copied and the output is 0
+ *   dropout     DropoutWrapper(output_keep_prob): the layer's output is y = h' o mask / keep_prob, the carried state the undropped h'.
+ *               drop: uint8 [L,B,T,H] on the device (0 = dropped), 4-byte aligned (the kernels read four units' masks at a time), or NULL for none.  Input dropout is the caller's (on x, no gradient).
+ *   loss        logits = y_top . Wfc + bfc; loss = sum_b ctc_b / B with kws_ctc_loss's conventions (above): the blank is the last class,
+ *               S_max <= 31, seq_len / labels / label_len are HOST arrays range-checked before any launch, seq_len[b] == 0 is an empty slot
+ *               that adds 0 and still counts in B.  An utterance without a valid path has loss +inf and contributes a gradient of exactly 0;
+ *               its loss[b] is +inf, so the step loss sum(loss) / B a caller forms is +inf as well.
+ *   clipping    only when max_grad_norm > 0: g *= max_grad_norm / max(||g||_2, max_grad_norm) over all tensors
+ *   Adam        beta 0.9 / 0.999, eps 1e-8 outside the root, lr_t = lr sqrt(1 - 0.999^t) / (1 - 0.9^t) (as kws_enroll_fit)
+ *   Nesterov    a <- 0.9 a + g; theta <- theta - lr g - lr 0.9 a
+ * The learning rate is an argument of every step (the exponential-decay schedule is host arithmetic).
+ *
+ * Backward, frames in reverse, dh' = dy o mask / keep_prob + the carried dh:
+ *   du = dh' o (h - c), dc = dh' o (1 - u), dh = dh' o u;  dc^ = dc o (1 - c^2);  [dx_c | d(rh)] = dc^ . Wc^T;  dh += d(rh) o r;
+ *   dr^ = d(rh) o h o r (1 - r);  du^ = du o u (1 - u);  [dx_g | dh_g] = [dr^ | du^] . Wg^T;  dh += dh_g;  dx = dx_c + dx_g;
+ *   dWc += [x, r o h]^T dc^;  dWg += [x, h]^T [dr^ | du^];  the biases are the column sums.  Frames t >= seq_len[b] pass dh through.
+ * Nothing is summed with float atomics: the same call twice gives the same bits.
+ *
+ * kws_train_create   refuses, before the device is probed, with KWS_ERR_UNSUPPORTED and a message that names the field: model.use_relu /
+ *                    model.value_clip (the gradient of TensorFlow's relu and clip at their ties is not pinned), wrappers.use_layer_norm /
+ *                    wrappers.use_residual, variational_recurrent, any model.precision but KWS_FP32, keep_prob outside (0, 1]; with
+ *                    KWS_ERR_INVALID_ARGUMENT an unknown optimizer and the ranges of kws_config (hidden 64 / 128 / 256, 1..8 layers,
+ *                    n_mel 1..1024, 3..8 classes).  The parameters start as zeros: kws_train_set_weights comes first.
+ * kws_train_check    the refusals of kws_train_create and of a kws_train_grad / _step call on a handle of this config, decided from
+ *                    host memory alone: KWS_OK where the call would go on to the device.  x and loss are only compared with NULL and
+ *                    checked for alignment.
+ * kws_train_set_weights / _get_weights   the canonical blob in HOST memory (nbytes = kws_weights_nbytes(&cfg.model)); set zeroes the
+ *                    moments and the step count.  Both wait for `stream`.
+ * kws_train_reserve  sizes the handle's tape for calls up to this B, T, S_max (else the first call of a larger shape does: either waits
+ *                    for the device once and counts in kws_train_stats' allocs).  A tape the device cannot hold is KWS_ERR_OUT_OF_MEMORY
+ *                    with the byte counts, before anything is freed or allocated.
+ * kws_train_grad     x [B,T,n_mel] f32 device; loss [B] f32 device out: every utterance's -log P; grad_blob (device, the blob's layout and
+ *                    size) out: the gradient of sum(loss) / B BEFORE clipping; logits [B,T,C] device out or NULL (rows t >= seq_len[b] are
+ *                    bfc).  Changes neither the parameters nor the moments.
+ * kws_train_step     the same forward and backward, then clip and update with learning rate lr; grad_norm (device, one float) or NULL:
+ *                    the global norm before clipping.  One call is one optimiser step.
+ * kws_train_moments  the optimiser's slots -> HOST memory, blob layout each: Adam's m and v; Nesterov's accumulator in m, v zeros
+ * kws_train_stats    device bytes the handle holds; device (re)allocations since create; optimiser steps since set_weights; kernel
+ *                    launches of the last grad / step call; rows per chunk of the weight-gradient reduction for the last shape (the B*T
+ *                    rows are summed in chunks of this many, the chunks in order).  Any pointer may be NULL.
+ * Refused before the device is touched (KWS_ERR_INVALID_ARGUMENT): null pointers, B or T < 1, S_max outside [0, 31], labels / lengths out
+ * of range, lr not positive and finite, pointers (drop included) not 4-byte aligned; KWS_ERR_UNSUPPORTED: 4 T (8 + 2 S_max + 1) bytes of LDS above 160 KiB,
+ * as kws_ctc_loss.  One host thread at a time per handle (KWS_ERR_BUSY); a call on another stream than the previous one is ordered behind
+ * it by the handle's event; no call synchronises the device in the steady state. */
+enum { KWS_OPT_ADAM = 0, KWS_OPT_NESTEROV = 1 };
+typedef struct kws_train_config {
+    kws_config model;
+    kws_cell_wrappers wrappers;       /* both must be 0 */
+    int32_t variational_recurrent;    /* must be 0 */
+    int32_t optimizer;                /* KWS_OPT_ADAM / KWS_OPT_NESTEROV */
+    float max_grad_norm;              /* <= 0: no clipping (config/rnn_config.py:55: -1) */
+    float keep_prob;                  /* output keep probability the masks were drawn with, (0, 1] */
+} kws_train_config;
+typedef struct kws_train* kws_train_handle;
+size_t kws_sizeof_train_config(void);
+int kws_train_create(const kws_train_config* cfg, kws_train_handle* out);
+int kws_train_check(const kws_train_config* cfg, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
+                    int T, int S_max, const float* loss);
+int kws_train_destroy(kws_train_handle h);   /* always KWS_OK */
+int kws_train_set_weights(kws_train_handle h, const void* blob /*host*/, size_t nbytes, void* stream);
+int kws_train_get_weights(kws_train_handle h, void* blob /*host*/, size_t nbytes, void* stream);
+int kws_train_reserve(kws_train_handle h, int B, int T, int S_max);
+int kws_train_grad(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
+                   int S_max, const uint8_t* drop_or_null, float* loss, float* grad_blob, float* logits_or_null, void* stream);
+int kws_train_step(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
+                   int S_max, const uint8_t* drop_or_null, float lr, float* loss, float* grad_norm_or_null, void* stream);
+int kws_train_moments(kws_train_handle h, float* m /*host*/, float* v /*host*/, void* stream);
+int kws_train_stats(kws_train_handle h, size_t* device_bytes, int32_t* allocs, int32_t* steps, int32_t* launches, int32_t* chunk_rows);
+
 /* OctbitMatMul: out[A,N] = (sum_k u8(x)[a,k] * Wq[n,k] - signed*bias[n]) * scale_w * s_x.
  *   x [A,K] f32, Wq [N,K] s8 (pre-transposed), bias [N] f32, out [A,N] f32.  K % 64 == 0, scale_w > 0.
  *   per_row_scale = 0: one dynamic activation range over the whole x (the reference op, whose A is

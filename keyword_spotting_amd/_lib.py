@@ -17,6 +17,7 @@ DECODE, DECODE2, DECODE_STRICT = 0, 1, 2
 FP32, BF16, INT8, F16X3 = 0, 1, 2, 3
 FEAT_MEL, FEAT_MFCC = 0, 1
 FRAMES_DEPLOY, FRAMES_DATASET = 0, 1
+OPT_ADAM, OPT_NESTEROV = 0, 1
 
 
 class KwsConfig(ctypes.Structure):
@@ -44,6 +45,13 @@ class KwsDatasetConfig(ctypes.Structure):
 class KwsCellWrappers(ctypes.Structure):
     """kws_cell_wrappers: the reference's get_cell options (config/rnn_config.py:78-79), 0 or 1 each."""
     _fields_ = [("use_layer_norm", ctypes.c_int32), ("use_residual", ctypes.c_int32)]
+
+
+class KwsTrainConfig(ctypes.Structure):
+    """kws_train_config: the model, the options a train handle refuses (wrappers, variational_recurrent), the optimiser, the global-norm
+    clip (<= 0: none) and the output keep probability of the dropout masks."""
+    _fields_ = [("model", KwsConfig), ("wrappers", KwsCellWrappers), ("variational_recurrent", ctypes.c_int32),
+                ("optimizer", ctypes.c_int32), ("max_grad_norm", ctypes.c_float), ("keep_prob", ctypes.c_float)]
 
 
 class KwsHeadIo(ctypes.Structure):
@@ -161,6 +169,19 @@ _SIGNATURES = {
     "kws_enroll_get": (_i, [_vp, _vp, _vp, _vp]),
     "kws_enroll_moments": (_i, [_vp, _vp, _vp, _vp]),
     "kws_enroll_stats": (_i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    # training of the stack: taped forward, BPTT, CTC loss, clip, Adam / Nesterov
+    "kws_sizeof_train_config": (ctypes.c_size_t, []),
+    "kws_train_create": (_i, [ctypes.POINTER(KwsTrainConfig), ctypes.POINTER(_vp)]),
+    "kws_train_check": (_i, [ctypes.POINTER(KwsTrainConfig), _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "kws_train_destroy": (_i, [_vp]),
+    "kws_train_set_weights": (_i, [_vp, _vp, ctypes.c_size_t, _vp]),
+    "kws_train_get_weights": (_i, [_vp, _vp, ctypes.c_size_t, _vp]),
+    "kws_train_reserve": (_i, [_vp, _i, _i, _i]),
+    "kws_train_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    "kws_train_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
+    "kws_train_moments": (_i, [_vp, _vp, _vp, _vp]),
+    "kws_train_stats": (_i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                             ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     # a bank of enrolled heads: per-user customised keywords on one frozen model
     "kws_bank_create": (_i, [_i, _i, _i, _i, ctypes.POINTER(_vp)]),
     "kws_bank_destroy": (_i, [_vp]),
@@ -198,6 +219,7 @@ def load():
                 lib.kws_sizeof_feature_config() != ctypes.sizeof(KwsFeatureConfig) or \
                 lib.kws_sizeof_dataset_config() != ctypes.sizeof(KwsDatasetConfig) or \
                 lib.kws_sizeof_attention_config() != ctypes.sizeof(KwsAttentionConfig) or \
+                lib.kws_sizeof_train_config() != ctypes.sizeof(KwsTrainConfig) or \
                 lib.kws_sizeof_head_io() != ctypes.sizeof(KwsHeadIo):
             raise ImportError("%s was built from a different include/kws_amd.h than this binding (struct sizes differ); "
                               "rebuild it" % LIB_PATH)

@@ -22,7 +22,7 @@ struct kws_enroll {
     hipEvent_t last_done = nullptr;
 };
 
-namespace {
+namespace kws_host {
 
 // seq_len / label_len / labels (host memory) against the shape; what = the class count the labels index (blank = classes - 1)
 int check_labels(const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int S_max, int classes) {
@@ -49,6 +49,10 @@ void pack_ints(const int32_t* seq_len, const int32_t* labels, const int32_t* lab
     std::copy(label_len, label_len + B, out->begin() + B);
     if (S_max > 0) std::copy(labels, labels + (size_t)B * S_max, out->begin() + 2 * (size_t)B);
 }
+
+}  // namespace kws_host
+
+namespace {
 
 int enroll_device_probe() {
     int ndev = 0;

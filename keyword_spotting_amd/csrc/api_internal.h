@@ -202,6 +202,13 @@ kws::BankRef bank_ref(const kws_bank* bank, const int32_t* user);
 // ... its slot table for the keyword forms of the bank kernels, or null while no slot was ever given a keyword (the plain kernels)
 const kws::BankSlotKeyword* bank_slots(const kws_bank* bank);
 
+// api_enroll.hip: what every CTC entry point does with its host arrays (kws_ctc_loss, kws_enroll_fit, kws_train_grad / _step).
+// seq_len / label_len / labels against the shape; classes = the class count the labels index (blank = classes - 1)
+int check_labels(const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int S_max, int classes);
+bool misaligned(const void* p);      // not 4-byte aligned
+// ... [seq_len | label_len | labels] as the one block that travels to the device
+void pack_ints(const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int S_max, std::vector<int32_t>* out);
+
 // api_frontend.hip: the 400-point FFT kernel takes a launch of B x T frames (else the dense-DFT kernel, which has magnitude mel only)
 bool frontend_takes_fft400(const kws_frontend* h, int B, int T);
 // ... the refusal of `what` ("per-stream chunk lengths") on a handle whose launches go to the dense-DFT kernel

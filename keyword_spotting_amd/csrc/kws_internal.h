@@ -495,6 +495,69 @@ struct EnrollFitParams {
 };
 hipError_t launch_enroll_fit(const EnrollFitParams& p, int hidden, int E, hipStream_t st);
 
+// Training of the stack (gru_train.hip: the two frame loops; train_kernels.hip: everything around them).  Every activation block is
+// plain row-major [B*T, width] fp32, row = b * T + t; `live` [B*T] is 1 for t < seq_len[b].
+//   packed weights of a layer, rebuilt on the device after every update (train_pack_kernel):
+//     wx [I, 3H] the x rows of (Wg | Wc), columns r | u | c      wh [H, 3H] the h rows      wht [3H, H] = wh transposed      b3 [3H]
+struct TrainForwardParams {
+    const float* xg;        // [B*T, 3H] x-part products + bias (rows past seq_len: the bias)
+    const float* wh;
+    const int32_t* seq_len; // [B], device
+    const uint8_t* drop;    // [B*T, H] this layer's output-dropout mask, or null
+    float *ar, *au, *ac, *hp, *rh;  // the tape [B*T, H]: pre-activations of r, u, c, the state the frame started from, r o hp; rows t < seq_len only
+    float* y;               // [B*T, H] what goes up: h' o mask / keep_prob, zero rows at t >= seq_len
+    float keep_prob;
+    int B, T;
+};
+struct TrainBackwardParams {
+    const float* dy;        // [B*T, H] gradient with respect to y
+    const float* wht;
+    const int32_t* seq_len;
+    const uint8_t* drop;
+    const float *ar, *au, *ac, *hp;
+    float* dhat;            // [B*T, 3H] pre-activation gradients dr^ | du^ | dc^, zero rows at t >= seq_len
+    float keep_prob;
+    int B, T;
+};
+hipError_t launch_gru_train_forward(const TrainForwardParams& p, int hidden, hipStream_t st);
+hipError_t launch_gru_train_backward(const TrainBackwardParams& p, int hidden, hipStream_t st);
+// out [M, N] = bias + a [M, K] . W, W(k, n) = w[k * swk + n * swn]; a row with live[row] == 0 reads as zeros (so out = bias there)
+struct TrainRowsGemm {
+    const float* a; int lda;
+    const uint8_t* live;    // [M] or null
+    const float* w; int swk, swn;
+    const float* bias;      // [N] or null
+    float* out; int ldo;
+    int M, K, N;
+};
+hipError_t launch_train_rows_gemm(const TrainRowsGemm& p, hipStream_t st);
+// One product of the weight-gradient launch: out [K, N] (at float offset `out` of a blob-layout image, row stride ldo) =
+// sum over the live rows of a[row, 0..K)^T d[row, 0..N).  src: kWgradRows = a; kWgradOnes = a row of ones with K = 1 (a bias: the
+// column sums); kWgradInput = the launch's x (the caller's features: the one operand that is not the handle's own memory).
+// A wave owns 16 k x 64 n outputs ("unit"); the job's units are [unit0, unit0 + ceil(K / 16) * ceil(N / 64)).
+enum { kWgradRows = 0, kWgradOnes = 1, kWgradInput = 2 };
+struct TrainWgradJob {
+    const float* a; const float* d;
+    size_t out;
+    int src, lda, K, ldd, N, ldo, unit0, pad;
+};
+// partial [chunks][P]: chunk c sums rows [c * chunk_rows, (c + 1) * chunk_rows); the jobs cover every float of the blob image
+hipError_t launch_train_wgrad(const TrainWgradJob* jobs, int njobs, int units, const float* x, const uint8_t* live, int M, int chunk_rows,
+                              int chunks, float* partial, size_t P, hipStream_t st);
+constexpr int kTrainReduceSpan = 1024;      // floats of the blob one workgroup of the reduction sums
+inline int train_reduce_blocks(size_t P) { return (int)((P + kTrainReduceSpan - 1) / kTrainReduceSpan); }
+// grad[i] = sum_c partial[c][i] in chunk order; sumsq[block] = the block's sum of grad^2 (double, fixed tree)
+hipError_t launch_train_reduce(const float* partial, int chunks, size_t P, float* grad, double* sumsq, hipStream_t st);
+// the optimiser over the flat blob: norm = sqrt(sum of sumsq in block order); max_grad_norm > 0: g *= clip / max(norm, clip);
+// adam != 0: TensorFlow's Adam with step size lr_t (bias corrections folded in by the host); else momentum 0.9 with use_nesterov
+hipError_t launch_train_update(float* theta, float* m, float* v, const float* grad, const double* sumsq, int nblocks, size_t P, int adam,
+                               float lr_t, float max_grad_norm, float* grad_norm_or_null, hipStream_t st);
+struct TrainPackLayer { const float *wg, *bg, *wc, *bc; float *wx, *wh, *wht, *b3; int in; };
+struct TrainPackParams { TrainPackLayer layer[8]; int L, H; };
+hipError_t launch_train_pack(const TrainPackParams& p, hipStream_t st);
+hipError_t launch_train_rowmask(const int32_t* seq_len, int B, int T, uint8_t* live, hipStream_t st);
+hipError_t launch_train_scale(float* x, size_t n, float s, hipStream_t st);
+
 // octbit_kernels.hip
 hipError_t launch_octbit_matmul(const float* x, const int8_t* Wq, float scale_w, const float* bias,
                                 float* out, int A, int K, int N, int per_row, float* range_ws,

@@ -1,0 +1,191 @@
+"""Training of the GRU stack on the device (main.py's loop over models/rnn_ctc.py:34-101): taped forward, back-propagation through
+time, tf.nn.ctc_loss, tf.clip_by_global_norm and tf.train.AdamOptimizer / MomentumOptimizer(0.9, use_nesterov=True) behind
+kws_train_* (include/kws_amd.h).  A Trainer owns the parameters on the device; weights() / save() / deploy() hand them to the
+serving side."""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from . import weights as _weights
+from .custom_keyword import _ints, _pack_labels
+
+OPTIMIZERS = {"adam": _lib.OPT_ADAM, "nesterov": _lib.OPT_NESTEROV}
+
+
+def learning_rate_at(step, learning_rate=1.5e-3, lr_decay=0.8, decay_step=20000):
+    """tf.train.exponential_decay(learning_rate, global_step, decay_step, lr_decay), staircase=False (models/rnn_ctc.py:76-78)."""
+    return float(learning_rate) * float(lr_decay) ** (float(step) / float(decay_step))
+
+
+def train_config(config, optimizer="adam", max_grad_norm=-1.0, keep_prob=1.0):
+    """The kws_train_config of a model config: every option a train handle refuses travels with its own field, so the refusal names it."""
+    if optimizer not in OPTIMIZERS:
+        raise _lib.InvalidArgumentError(-1, "optimizer %r: 'adam' or 'nesterov' (models/rnn_ctc.py:80-87)" % (optimizer,))
+    model = _lib.KwsConfig(config.n_mel, config.hidden_size, config.num_layers, config.num_classes, int(bool(config.use_relu)),
+                           float(config.value_clip),
+                           {"fp32": _lib.FP32, "bf16": _lib.BF16, "int8": _lib.INT8, "f16x3": _lib.F16X3}[getattr(config, "precision", "fp32")])
+    wrap = _lib.KwsCellWrappers(int(bool(getattr(config, "use_layer_norm", False))), int(bool(getattr(config, "use_residual", False))))
+    return _lib.KwsTrainConfig(model, wrap, int(bool(getattr(config, "variational_recurrent", False))), OPTIMIZERS[optimizer],
+                               float(max_grad_norm), float(keep_prob))
+
+
+class Trainer(object):
+    """The reference's training graph on one device.  Defaults: config/rnn_config.py:44-55,77 (learning_rate 1.5e-3, lr_decay 0.8,
+    decay_step 20000, adam, max_grad_norm -1 = no clipping); keep_prob defaults to 1 (the reference file ships 0.6, :81).
+
+    weights: a dict (weights.init_weights' form), a blob, or None for init_weights(config, seed)."""
+
+    def __init__(self, config, weights=None, optimizer="adam", learning_rate=1.5e-3, lr_decay=0.8, decay_step=20000, max_grad_norm=-1,
+                 keep_prob=1.0, seed=0, device="cuda:0"):
+        import torch
+        self.config = config
+        self.optimizer, self.learning_rate, self.lr_decay, self.decay_step = optimizer, float(learning_rate), float(lr_decay), int(decay_step)
+        self.max_grad_norm, self.keep_prob = float(max_grad_norm), float(keep_prob)
+        self._cfg = train_config(config, optimizer, max_grad_norm, keep_prob)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.InvalidArgumentError(-1, "Trainer needs a CUDA/HIP device, got %s" % device)
+        self._lib = _lib.load()
+        self._handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_train_create(ctypes.byref(self._cfg), ctypes.byref(self._handle)))
+        self._gen = torch.Generator(device=self.device)
+        self._gen.manual_seed(int(seed))
+        self.global_step = 0
+        if weights is None:
+            weights = _weights.init_weights(config, seed=seed)
+        self.set_weights(weights)
+
+    # -- lifecycle ---------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_handle", None) is not None and self._handle.value:
+            self._lib.kws_train_destroy(self._handle)
+            self._handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return _lib.current_stream_ptr()
+
+    # -- parameters --------------------------------------------------------------------------
+    def set_weights(self, weights):
+        """Loads parameters; zeroes the optimiser's moments and the step count of its bias corrections."""
+        import torch
+        blob = weights if isinstance(weights, np.ndarray) else _weights.to_blob(self.config, weights)
+        blob = np.ascontiguousarray(blob, np.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_train_set_weights(self._handle, blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes, self._stream()))
+
+    def weights_blob(self):
+        import torch
+        blob = np.empty(self._lib.kws_weights_nbytes(ctypes.byref(self._cfg.model)) // 4, np.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_train_get_weights(self._handle, blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes, self._stream()))
+        return blob
+
+    def weights(self):
+        """The current parameters in the canonical dict form (weights.from_blob)."""
+        return _weights.from_blob(self.config, self.weights_blob())
+
+    def moments(self):
+        """(m, v) in the dict form: Adam's moments; Nesterov's accumulator and zeros."""
+        import torch
+        n = self._lib.kws_weights_nbytes(ctypes.byref(self._cfg.model)) // 4
+        m, v = np.empty(n, np.float32), np.empty(n, np.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_train_moments(self._handle, m.ctypes.data_as(ctypes.c_void_p), v.ctypes.data_as(ctypes.c_void_p), self._stream()))
+        return _weights.from_blob(self.config, m), _weights.from_blob(self.config, v)
+
+    def save(self, path):
+        _weights.save_npz(path, self.weights())
+
+    def deploy(self, **kw):
+        """rnn_ctc.DeployModel on the current parameters; kw: config overrides (precision="f16x3") and DeployModel's kernel=."""
+        import copy
+        from .rnn_ctc import DeployModel
+        cfg = copy.copy(self.config)
+        kernel = kw.pop("kernel", "auto")
+        for k, v in kw.items():
+            if not hasattr(cfg, k):
+                raise AttributeError("unknown config key %r" % k)
+            setattr(cfg, k, v)
+        return DeployModel(cfg, self.weights_blob(), device=str(self.device), kernel=kernel)
+
+    def reserve(self, batch, frames, max_label=31):
+        _lib.check(self._lib.kws_train_reserve(self._handle, int(batch), int(frames), int(max_label)))
+
+    def stats(self):
+        """dict(device_bytes, allocs, steps, launches of the last call, chunk_rows of the weight-gradient reduction)."""
+        nbytes = ctypes.c_size_t()
+        a, s, l, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(self._lib.kws_train_stats(self._handle, ctypes.byref(nbytes), ctypes.byref(a), ctypes.byref(s), ctypes.byref(l), ctypes.byref(c)))
+        return dict(device_bytes=int(nbytes.value), allocs=a.value, steps=s.value, launches=l.value, chunk_rows=c.value)
+
+    # -- compute -----------------------------------------------------------------------------
+    def learning_rate_at(self, step):
+        return learning_rate_at(step, self.learning_rate, self.lr_decay, self.decay_step)
+
+    def _inputs(self, x, lengths, labels, drop):
+        import torch
+        cfg = self.config
+        x = torch.as_tensor(x)
+        if x.dim() != 3 or x.shape[2] != cfg.n_mel:
+            raise _lib.InvalidArgumentError(-1, "x must be [B,T,%d], got %s" % (cfg.n_mel, tuple(x.shape)))
+        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        b, t = int(x.shape[0]), int(x.shape[1])
+        lab, lab_len = _pack_labels(labels, b)
+        sl = np.full(b, t) if lengths is None else np.asarray(lengths)
+        if sl.shape != (b,):
+            raise _lib.InvalidArgumentError(-1, "lengths: %s for %d utterances" % (sl.shape, b))
+        if drop is not None:
+            drop = torch.as_tensor(drop).to(device=self.device, dtype=torch.uint8).contiguous()
+            if tuple(drop.shape) != (cfg.num_layers, b, t, cfg.hidden_size):
+                raise _lib.InvalidArgumentError(-1, "drop must be [%d,%d,%d,%d], got %s" % (cfg.num_layers, b, t, cfg.hidden_size, tuple(drop.shape)))
+        return x, b, t, _ints(sl), _ints(lab), _ints(lab_len), drop
+
+    def loss_and_grad(self, x, lengths, labels, drop=None, want_logits=False):
+        """-> (loss = sum_b ctc_b / B, gradients in the dict form, per-utterance losses [B]) [, logits [B,T,C]]; the parameters stay.
+        labels: B sequences over classes 0..C-2 (prediction.ctc_label's form), or one for all."""
+        import torch
+        x, b, t, (sl, sl_p), (lab, lab_p), (ll, ll_p), drop = self._inputs(x, lengths, labels, drop)
+        loss = torch.empty(b, dtype=torch.float32, device=self.device)
+        grad = torch.empty(self._lib.kws_weights_nbytes(ctypes.byref(self._cfg.model)) // 4, dtype=torch.float32, device=self.device)
+        logits = torch.empty(b, t, self.config.num_classes, dtype=torch.float32, device=self.device) if want_logits else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_train_grad(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]), _lib.ptr(drop),
+                                                _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(logits), self._stream()))
+        per = loss.cpu().numpy()
+        out = (float(per.astype(np.float64).sum() / b), _weights.from_blob(self.config, grad.cpu().numpy()), per)
+        return out + (logits,) if want_logits else out
+
+    def step_raw(self, x, lengths, labels, lr, drop=None, want_norm=False):
+        """One kws_train_step at learning rate lr with the given masks -> per-utterance losses [B] (device) [, global norm (device)]."""
+        import torch
+        x, b, t, (sl, sl_p), (lab, lab_p), (ll, ll_p), drop = self._inputs(x, lengths, labels, drop)
+        loss = torch.empty(b, dtype=torch.float32, device=self.device)
+        norm = torch.empty(1, dtype=torch.float32, device=self.device) if want_norm else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_train_step(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]), _lib.ptr(drop), float(lr),
+                                                _lib.ptr(loss), _lib.ptr(norm), self._stream()))
+        return (loss, norm) if want_norm else loss
+
+    def step(self, x, lengths, labels):
+        """One training step as main.py runs it: input dropout on x and one output mask per layer, both floor(keep_prob + U) from the
+        trainer's own generator (keep_prob < 1 only), the scheduled learning rate, then the update -> loss = sum_b ctc_b / B."""
+        import torch
+        x = torch.as_tensor(x).to(device=self.device, dtype=torch.float32)
+        drop = None
+        if self.keep_prob < 1.0:
+            cfg = self.config
+            keep = torch.floor(self.keep_prob + torch.rand(x.shape, generator=self._gen, device=self.device))
+            x = x / self.keep_prob * keep           # tf.nn.dropout(inputX, keep_prob) (models/rnn_ctc.py:41-42)
+            drop = torch.floor(self.keep_prob + torch.rand((cfg.num_layers, x.shape[0], x.shape[1], cfg.hidden_size), generator=self._gen,
+                                                           device=self.device)).to(torch.uint8)
+        loss = self.step_raw(x, lengths, labels, self.learning_rate_at(self.global_step), drop=drop)
+        self.global_step += 1
+        return float(loss.cpu().numpy().astype(np.float64).sum() / loss.shape[0])
