@@ -213,7 +213,7 @@ int grad_impl(kws_train* h, const float* x, const int32_t* seq_len, const int32_
         KWS_LAUNCH(h, kws::launch_train_rows_gemm(g, st), "launch train_rows_gemm (logits)");
     }
     KWS_LAUNCH(h, kws::launch_ctc_loss(cv.logits, d_seq, d_lab, d_len, B, T, C, S_max, loss, cv.gl, st), "launch ctc_loss");
-    KWS_LAUNCH(h, kws::launch_train_scale(cv.gl, (size_t)M * C, 1.0f / (float)B, st), "launch train_scale");      // loss = sum_b ctc_b / B
+    KWS_LAUNCH(h, kws::launch_train_scale(cv.gl, cv.logits, (size_t)M, C, 1.0f / (float)B, st), "launch train_scale");      // loss = sum_b ctc_b / B
     {
         kws::TrainRowsGemm g = {};          // dy_top = grad_logits . Wfc^T
         g.a = cv.gl; g.lda = C; g.w = wfc; g.swk = 1; g.swn = C;

@@ -556,7 +556,8 @@ struct TrainPackLayer { const float *wg, *bg, *wc, *bc; float *wx, *wh, *wht, *b
 struct TrainPackParams { TrainPackLayer layer[8]; int L, H; };
 hipError_t launch_train_pack(const TrainPackParams& p, hipStream_t st);
 hipError_t launch_train_rowmask(const int32_t* seq_len, int B, int T, uint8_t* live, hipStream_t st);
-hipError_t launch_train_scale(float* x, size_t n, float s, hipStream_t st);
+// g [rows, C], ctc_loss_kernel's grad_logits of `logits`: each frame's occupancies renormalised to sum 1, then g *= s
+hipError_t launch_train_scale(float* g, const float* logits, size_t rows, int C, float s, hipStream_t st);
 
 // octbit_kernels.hip
 hipError_t launch_octbit_matmul(const float* x, const int8_t* Wq, float scale_w, const float* bias,

@@ -203,8 +203,11 @@ __global__ void __launch_bounds__(256) train_update_kernel(float* __restrict__ t
     if (i >= P) return;
     const float g = grad[i] * factor;
     if (adam) {
-        const float m1 = 0.9f * m[i] + (1.0f - 0.9f) * g;
-        const float v1 = 0.999f * v[i] + (1.0f - 0.999f) * (g * g);
+        // m += (g - m) (1 - beta1), v += (g^2 - v) (1 - beta2) as TensorFlow's kernel writes them, with 1 - beta the float nearest to
+        // 0.1 / 0.001: 1.0f - 0.999f is 0.00099998713, and v came out 1.29e-5 below Adam's (kws_train_moments against the fp64
+        // optimiser, seven times the floor of that comparison); 1 - 0.001f is 0.999 to 5e-11
+        const float m1 = m[i] + (g - m[i]) * 0.1f;
+        const float v1 = v[i] + (g * g - v[i]) * 0.001f;
         m[i] = m1;
         v[i] = v1;
         theta[i] -= lr_t * m1 / (sqrtf(v1) + 1e-8f);
@@ -256,13 +259,39 @@ hipError_t launch_train_rowmask(const int32_t* seq_len, int B, int T, uint8_t* l
     return launch_lds<train_rowmask_kernel>(dim3((unsigned)(((size_t)B * T + 255) / 256)), dim3(256), 0, st, seq_len, B, T, live);
 }
 
-__global__ void __launch_bounds__(256) train_scale_kernel(float* __restrict__ x, size_t n, float s) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) x[i] *= s;
+// ------------------------------------------------------------------------------------------------
+// grad_logits of ctc_loss_kernel -> the gradient of sum(loss) / B, a thread per frame.  A row of the CTC kernel is softmax - occupancy
+// with occupancy = exp(alpha + beta - lp + nll) from the fp32 log-domain recursions: what alpha, beta and nll have drifted by over the
+// frames is one factor (1 - delta) on all occupancies of a frame, of one sign for much of an utterance, so it does not average out
+// over the rows (T = 250: 1.2e-4 on dbfc, four times the deviation of the float32 reference).  The occupancies of a frame sum to 1,
+// so delta = sum_c g[c] -- 0 in exact arithmetic -- measures the factor, and g[c] - occupancy[c] * delta takes it out, with
+// occupancy[c] = softmax[c] - g[c] from the logits.  A row of zeros (t >= seq_len, an empty slot, no valid path) stays zeros.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) train_scale_kernel(float* __restrict__ g, const float* __restrict__ logits, size_t rows, int C, float s) {
+    const size_t row = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (row >= rows) return;
+    float v[kMaxClasses], z[kMaxClasses];
+    float delta = 0.f, mx = -INFINITY;
+#pragma unroll
+    for (int c = 0; c < kMaxClasses; ++c) {
+        v[c] = c < C ? g[row * C + c] : 0.f;
+        z[c] = c < C ? logits[row * C + c] : -INFINITY;
+        delta += v[c];
+        mx = fmaxf(mx, z[c]);
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < kMaxClasses; ++c) {
+        z[c] = c < C ? expf(z[c] - mx) : 0.f;
+        sum += z[c];
+    }
+#pragma unroll
+    for (int c = 0; c < kMaxClasses; ++c)
+        if (c < C) g[row * C + c] = (v[c] - (z[c] / sum - v[c]) * delta) * s;
 }
 
-hipError_t launch_train_scale(float* x, size_t n, float s, hipStream_t st) {
-    return launch_lds<train_scale_kernel>(dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, n, s);
+hipError_t launch_train_scale(float* g, const float* logits, size_t rows, int C, float s, hipStream_t st) {
+    return launch_lds<train_scale_kernel>(dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, g, logits, rows, C, s);
 }
 
 }  // namespace kws

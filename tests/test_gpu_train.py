@@ -1,7 +1,9 @@
 """Training of the stack on the device (kws_train_*, keyword_spotting_amd.training.Trainer) against the fp64 restatement
 tests/train_model.py, with the deviation of the identical torch graph in float32 (CPU) as the yardstick: per tensor, bound = max(4 x
 that deviation, 16 * 2^-23 * max|reference|) -- the project's bound for this kind of comparison (tests/test_gpu_enroll.py).  Every
-comparison prints a TRAIN-RATIO line (kernel / float32-CPU / bound) before it asserts."""
+comparison prints a TRAIN-RATIO line (kernel / float32-CPU / bound) before it asserts.  What has to hold to the bit -- inputs off a
+16-byte boundary, a re-carved arena against a fresh handle, calls from two streams, Trainer.step against a twin fed the same draws -- is
+compared as uint32."""
 import ctypes
 import threading
 
@@ -66,7 +68,9 @@ def test_new_entry_points_exist():
 @pytest.mark.parametrize("name", sorted(M.CASES))
 def test_taped_forward_logits(name, refs):
     """No dropout: logits against the restatement (1e-4), rows t >= seq_len are bfc bitwise, and at full length the logits of
-    kws_step on the same weights (2e-5)."""
+    kws_step on the same weights (2e-5) for the first nine cases.  The later cases go where the serving kernels' own distance from fp64
+    (bound 1e-4, tests/test_gpu_config_space.py; 1.5e-5 measured at n_mel 1024) leaves no room for 2e-5 between the two: there each
+    side is held against the restatement's full-length logits at 1e-4 and the difference between them is printed."""
     from keyword_spotting_amd.rnn_ctc import DeployModel
     p = M.make_problem(name)
     t = _trainer(p)
@@ -82,14 +86,24 @@ def test_taped_forward_logits(name, refs):
     for b in range(p["B"]):
         dead = logits[b, p["seq_len"][b]:]
         assert np.array_equal(dead, np.broadcast_to(p["w"]["bfc"], dead.shape)), b
+    if name == "dead_group":          # the workgroup that never enters its frame loops: bfc at EVERY frame
+        assert (p["seq_len"][16:32] == 0).all() and (p["seq_len"][:16] > 0).any() and p["seq_len"][32] == p["T"]
+        assert np.array_equal(logits[16:32], np.broadcast_to(p["w"]["bfc"], logits[16:32].shape))
     m = DeployModel(p["config"], p["w"])
     try:
         served = m.forward(torch.from_numpy(p["x"]), m.zero_state(p["B"]), want_softmax=False)["logits"].cpu().numpy()
     finally:
         m.close()
     err = float(np.abs(full - served).max())
-    print("TRAIN-RATIO forward vs kws_step %s: %.3e  bound 2.000e-05" % (name, err))
-    assert err <= 2e-5
+    if name in M.FIRST_CASES:
+        print("TRAIN-RATIO forward vs kws_step %s: %.3e  bound 2.000e-05" % (name, err))
+        assert err <= 2e-5
+        return
+    want_full = M.forward(p["w"], p["x"], np.full(p["B"], p["T"]))[0]
+    e_train, e_served = float(np.abs(full - want_full).max()), float(np.abs(served - want_full).max())
+    print("TRAIN-RATIO forward at full length %s: kernel %.3e  kws_step %.3e  bound 1.000e-04  (kernel vs kws_step %.3e, not asserted)"
+          % (name, e_train, e_served, err))
+    assert e_train <= 1e-4 and e_served <= 1e-4
 
 
 @pytest.mark.parametrize("name", sorted(M.CASES))
@@ -120,9 +134,14 @@ def test_gradients_against_the_restatement(name, refs):
     if name == "split_rows":
         rows, chunk = p["B"] * p["T"], stats["chunk_rows"]
         assert rows >= 2.5 * chunk and rows % chunk != 0, (rows, chunk)
+    if name == "rows_chunk512":          # the chunk has grown past its unit of 256 rows, and the last chunk is partial
+        rows = p["B"] * p["T"]
+        assert stats["chunk_rows"] == 512 and rows % 512 != 0, (rows, stats["chunk_rows"])
+    if name == "dead_group":
+        assert (p["seq_len"][16:32] == 0).all() and (loss[16:32] == 0).all() and (loss[:16] > 0).all() and loss[32] > 0
 
 
-@pytest.mark.parametrize("name", ["odd_mel", "ref_shape"])
+@pytest.mark.parametrize("name", ["odd_mel", "ref_shape", "h256", "l8"])
 def test_dropout_masks(name):
     p = M.make_problem(name)
     drop = M.drop_masks(p, 0.6)
@@ -197,12 +216,28 @@ def test_one_step_is_the_fp64_update_of_the_devices_own_gradient(kind):
     assert not all(np.array_equal(a, b) for (_, a), (_, b) in zip(M.flat(after["none"]), M.flat(after["active"])))
 
 
+def _check_trajectory(what, got_loss, got_path, loss64, path64, loss32, path32):
+    """Losses and parameter blobs after every step against the fp64 trajectory.  The yardstick at step s is the largest deviation the
+    float32 torch trajectory has shown from the fp64 one up to s; bound_s = max(4 x that, s x floor) --
+    test_twenty_step_fit_follows_the_restatement's."""
+    dev_l = dev_w = worst = 0.0
+    for s in range(len(got_path)):
+        dev_l = max(dev_l, float(np.abs(loss32[s] - loss64[s]).max()))
+        dev_w = max(dev_w, float(np.abs(path32[s] - path64[s]).max()))
+        b_l = max(4 * dev_l, (s + 1) * FLOOR * float(np.abs(loss64[s]).max()))
+        b_w = max(4 * dev_w, (s + 1) * FLOOR * float(np.abs(path64[s]).max()))
+        e_l = float(np.abs(got_loss[s] - loss64[s]).max())
+        e_w = float(np.abs(got_path[s] - path64[s]).max())
+        worst = max(worst, e_l / b_l, e_w / b_w)
+        assert e_l <= b_l and e_w <= b_w, (s, e_l, b_l, e_w, b_w)
+    print("TRAIN-RATIO %s: worst kernel/bound %.3f (float32-CPU drift: loss %.3e, parameters %.3e)" % (what, worst, dev_l, dev_w))
+
+
 @pytest.mark.parametrize("kind", ["adam", "nesterov"])
-@pytest.mark.parametrize("name", ["t2", "ref_shape", "c8_s_long"])
+@pytest.mark.parametrize("name", ["t2", "ref_shape", "c8_s_long", "h256"])
 def test_twenty_steps_follow_the_restatement(name, kind):
-    """Losses and parameters after every step against the fp64 restatement, one call per step, weights read back each step.  The
-    yardstick at step s is the largest deviation the float32 torch trajectory has shown from the fp64 one up to s; bound_s = max(4 x
-    that, s x floor) -- test_twenty_step_fit_follows_the_restatement's."""
+    """Losses and parameters after every step against the fp64 restatement, one call per step, weights read back each step, under
+    _check_trajectory's bound."""
     steps, lr = 20, M.TRAJECTORY_LR[kind]
     p = M.make_problem(name)
     loss64, path64 = M.trajectory(name, kind, steps, lr)
@@ -215,17 +250,233 @@ def test_twenty_steps_follow_the_restatement(name, kind):
             got_path.append(t.weights_blob())
     finally:
         t.close()
-    dev_l = dev_w = worst = 0.0
-    for s in range(steps):
-        dev_l = max(dev_l, float(np.abs(loss32[s] - loss64[s]).max()))
-        dev_w = max(dev_w, float(np.abs(path32[s] - path64[s]).max()))
-        b_l = max(4 * dev_l, (s + 1) * FLOOR * float(np.abs(loss64[s]).max()))
-        b_w = max(4 * dev_w, (s + 1) * FLOOR * float(np.abs(path64[s]).max()))
-        e_l = float(np.abs(got_loss[s] - loss64[s]).max())
-        e_w = float(np.abs(got_path[s] - path64[s]).max())
-        worst = max(worst, e_l / b_l, e_w / b_w)
-        assert e_l <= b_l and e_w <= b_w, (s, e_l, b_l, e_w, b_w)
-    print("TRAIN-RATIO twenty steps %s %s: worst kernel/bound %.3f (float32-CPU drift: loss %.3e, parameters %.3e)" % (name, kind, worst, dev_l, dev_w))
+    _check_trajectory("twenty steps %s %s" % (name, kind), got_loss, got_path, loss64, path64, loss32, path32)
+
+
+@pytest.mark.parametrize("kind", ["adam", "nesterov"])
+def test_trainer_step_draws_masks_and_follows_the_schedule(kind):
+    """Trainer.step as main.py runs it (keep_prob 0.6, the rate halving every two steps), three steps on odd_mel.  A twin trainer gets
+    the same draws made here -- a generator of the same seed, per step the x mask then the [L,B,T,H] masks -- through step_raw: equal
+    losses, the same weights bitwise after every step; and those weights follow the restatement run with these masks and rates under
+    _check_trajectory's bound."""
+    from keyword_spotting_amd.training import learning_rate_at
+    p = M.make_problem("odd_mel")
+    cfg, seed, keep_prob, steps = p["config"], 11, 0.6, 3
+    kw = dict(keep_prob=keep_prob, learning_rate=0.1, lr_decay=0.5, decay_step=2, optimizer=kind)
+    t, twin = _trainer(p, seed=seed, **kw), _trainer(p, seed=seed + 1, **kw)          # the twin's own generator is never drawn from
+    xs, drops, lrs, got_loss, got_path = [], [], [], [], []
+    try:
+        gen = torch.Generator(device=t.device)
+        gen.manual_seed(seed)
+        x = torch.from_numpy(p["x"]).to(t.device)
+        for s in range(steps):
+            keep = torch.floor(keep_prob + torch.rand(x.shape, generator=gen, device=t.device))
+            xd = x / keep_prob * keep
+            drop = torch.floor(keep_prob + torch.rand((cfg.num_layers, p["B"], p["T"], cfg.hidden_size), generator=gen, device=t.device)).to(torch.uint8)
+            lr = learning_rate_at(s, 0.1, 0.5, 2)
+            assert lr == t.learning_rate_at(t.global_step)
+            total = t.step(p["x"], p["seq_len"], p["labels"])
+            per = twin.step_raw(xd, p["seq_len"], p["labels"], lr, drop=drop).cpu().numpy()
+            assert total == float(per.astype(np.float64).sum() / p["B"]), s
+            mine, theirs = t.weights_blob(), twin.weights_blob()
+            assert np.array_equal(mine.view(np.uint32), theirs.view(np.uint32)), s
+            xs.append(xd.cpu().numpy()); drops.append(drop.cpu().numpy()); lrs.append(lr); got_loss.append(per); got_path.append(mine)
+        assert t.global_step == steps and t.stats()["steps"] == steps
+    finally:
+        t.close()
+        twin.close()
+    assert lrs == [0.1, 0.1 * 0.5 ** 0.5, 0.05]
+    for d, xd in zip(drops, xs):          # both kinds of dropout are live, and no two steps share a draw
+        assert 0.3 < d.mean() < 0.9 and 0.3 < (xd != 0).mean() < 0.9
+    assert not np.array_equal(drops[0], drops[1]) and not np.array_equal(xs[0], xs[1])
+
+    def run(float32):
+        w = p["w"] if float32 else M.as_dtype(p["w"], np.float64)
+        opt = M.Optimizer(w, kind, np.float32 if float32 else np.float64)
+        losses, path = [], []
+        for s in range(steps):
+            if float32:
+                r = M.torch_reference(w, xs[s], p["seq_len"], p["labels"], torch.float32, drops[s], keep_prob)
+                loss, grads = r["loss"], r["grads"]
+            else:
+                loss, grads, _ = M.loss_and_grad(w, xs[s], p["seq_len"], p["labels"], drops[s], keep_prob)
+            w = opt.apply(w, grads, lrs[s])
+            losses.append(np.asarray(loss, np.float64))
+            path.append(M.blob_of(w))
+        return losses, path
+    loss64, path64 = run(False)
+    loss32, path32 = run(True)
+    _check_trajectory("Trainer.step odd_mel %s" % kind, got_loss, got_path, loss64, path64, loss32, path32)
+
+
+@pytest.mark.parametrize("kind", ["adam", "nesterov"])
+def test_moments_after_three_steps(kind):
+    """kws_train_moments: Adam's m and v (Nesterov: the accumulator, and zeros) against the fp64 optimiser fed the device's own
+    gradients, within the bound's floor per tensor as the one-step test; set_weights zeroes them and the step count.
+
+    The regression test of Adam's 1 - beta2: formed as 1.0f - 0.999f = 0.00099998713 it left v 1.29e-5 below the fp64 optimiser's on
+    every tensor (l0_Wg: 2.296e-10 against a floor of 3.392e-11), which no comparison of the parameters is fine enough to see."""
+    p = M.make_problem("t2")
+    lr = M.TRAJECTORY_LR[kind]
+    opt, opt32 = M.Optimizer(p["w"], kind), M.Optimizer(p["w"], kind, np.float32)
+    t = _trainer(p, optimizer=kind)
+    try:
+        for _ in range(3):
+            _, g, _ = t.loss_and_grad(p["x"], p["seq_len"], p["labels"])          # the gradient the step below takes: the parameters stay
+            opt.apply(t.weights(), g, lr)
+            opt32.apply(t.weights(), g, lr)
+            t.step_raw(p["x"], p["seq_len"], p["labels"], lr)
+        m, v = t.moments()
+        assert t.stats()["steps"] == 3
+        t.set_weights(p["w"])
+        m0, v0 = t.moments()
+        assert t.stats()["steps"] == 0
+    finally:
+        t.close()
+    assert all(not a.any() and not b.any() for (_, a), (_, b) in zip(M.flat(m0), M.flat(v0)))
+    over = []
+    for i, ((key, got_m), (_, got_v)) in enumerate(zip(M.flat(m), M.flat(v))):
+        for what, got, ref, ref32 in (("m", got_m, opt.m[i], opt32.m[i]), ("v", got_v, opt.v[i], opt32.v[i])):
+            assert got.shape == ref.shape
+            err, floor = float(np.abs(got - ref).max()), FLOOR * float(np.abs(ref).max())
+            print("TRAIN-RATIO moments %s %s %s: kernel %.3e  floor %.3e  (against the float32 optimiser %.3e, not asserted)"
+                  % (kind, what, key, err, floor, float(np.abs(got - ref32.astype(np.float64)).max())))
+            if err > floor:
+                over.append((what, key, err, floor))
+        assert np.abs(opt.m[i]).max() > 0, key
+        if kind == "nesterov":
+            assert not got_v.any(), key
+        else:
+            assert np.abs(opt.v[i]).max() > 0, key
+    assert not over, over
+
+
+# ---- bitwise properties: alignment of the inputs, reuse of the arena, calls from two streams ---------------------------------------
+
+def _bits(t, x, seq_len, labels, drop=None):
+    """One loss_and_grad -> [(name, array)]: the per-utterance losses, the logits and every gradient tensor."""
+    _, g, loss, logits = t.loss_and_grad(x, seq_len, labels, drop=drop, want_logits=True)
+    return [("loss", loss), ("logits", logits.cpu().numpy())] + M.flat(g)
+
+
+def _assert_same_bits(a, b, what):
+    assert len(a) == len(b)
+    for (key, u), (_, v) in zip(a, b):
+        assert u.shape == v.shape and np.array_equal(u.view(np.uint32), v.view(np.uint32)), (what, key)
+
+
+@pytest.mark.parametrize("name", ["mel72", "ref_shape"])
+def test_x_one_float_past_a_16_byte_boundary_gives_the_same_bits(name):
+    """The x-part GEMM takes 16-byte loads only from a 16-byte aligned base; the ABI asks for 4 bytes.  The scalar loads fetch the same
+    floats into the same products in the same order, so nothing may move by a bit (mel72: behind the first pass of the K loop too)."""
+    p = M.make_problem(name)
+    aligned = torch.from_numpy(p["x"]).cuda()
+    store = torch.empty(1 + p["x"].size, dtype=torch.float32, device="cuda")
+    store[1:] = aligned.reshape(-1)
+    shifted = store[1:].view(p["x"].shape)
+    t = _trainer(p)
+    try:
+        for x, off in ((aligned, 0), (shifted, 4)):          # the pointer the C entry gets is the tensor's own
+            assert t._inputs(x, p["seq_len"], p["labels"], None)[0].data_ptr() == x.data_ptr() and x.data_ptr() % 16 == off
+        want = _bits(t, aligned, p["seq_len"], p["labels"])
+        got = _bits(t, shifted, p["seq_len"], p["labels"])
+    finally:
+        t.close()
+    _assert_same_bits(want, got, name)
+
+
+def test_drop_masks_four_bytes_past_a_16_byte_boundary_give_the_same_bits():
+    """The masks are read four units at a time from a pointer that has to be 4-byte aligned and no more: through the C entry."""
+    from keyword_spotting_amd import _lib, weights
+    p = M.make_problem("ref_shape")
+    drop = M.drop_masks(p, 0.6)
+    store = torch.zeros(4 + drop.size, dtype=torch.uint8, device="cuda")
+    store[4:] = torch.from_numpy(drop.reshape(-1)).cuda()
+    assert store.data_ptr() % 16 == 0
+    t = _trainer(p, keep_prob=0.6)
+    try:
+        want = _bits(t, p["x"], p["seq_len"], p["labels"], drop=drop)
+        x, b, frames, (_, sl_p), (lab, lab_p), (_, ll_p), _ = t._inputs(p["x"], p["seq_len"], p["labels"], None)
+        loss = torch.empty(b, device="cuda")
+        grad = torch.empty(t.weights_blob().size, device="cuda")
+        logits = torch.empty(b, frames, p["config"].num_classes, device="cuda")
+        masks = ctypes.c_void_p(store.data_ptr() + 4)
+        assert masks.value % 4 == 0 and masks.value % 16 != 0
+        _lib.check(t._lib.kws_train_grad(t._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, frames, int(lab.shape[1]), masks, _lib.ptr(loss),
+                                         _lib.ptr(grad), _lib.ptr(logits), _lib.current_stream_ptr()))
+        got = [("loss", loss.cpu().numpy()), ("logits", logits.cpu().numpy())] + M.flat(weights.from_blob(p["config"], grad.cpu().numpy()))
+    finally:
+        t.close()
+    _assert_same_bits(want, got, "drop")
+
+
+def test_a_recarved_arena_gives_the_bits_of_a_fresh_handle():
+    """One handle through ref_shape, t2's shape, mel60_l3's shape (smaller and larger B x T, another S_max), ref_shape again, then
+    reserve() for something larger and ref_shape once more: every call the bits of a fresh handle at that shape, and the arena is
+    allocated anew exactly when a shape needs more bytes than any before it."""
+    p = M.make_problem("ref_shape")
+    rng = np.random.default_rng(5)
+
+    def shaped(b, frames, seq_len, labels):
+        return rng.standard_normal((b, frames, p["config"].n_mel)).astype(np.float32), np.array(seq_len, np.int32), labels
+    calls = {"ref_shape": (p["x"], p["seq_len"], p["labels"]), "t2": shaped(*M.CASES["t2"][4:]), "mel60_l3": shaped(*M.CASES["mel60_l3"][4:])}
+    fresh, need = {}, {}
+    for key, args in calls.items():
+        t = _trainer(p)
+        try:
+            fresh[key] = _bits(t, *args)
+            need[key] = t.stats()["device_bytes"]          # the handle's fixed state + the arena of this one shape
+            assert t.stats()["allocs"] == 1
+        finally:
+            t.close()
+    assert need["t2"] < need["ref_shape"] < need["mel60_l3"]
+    t = _trainer(p)
+    try:
+        high = 0
+        for key in ("ref_shape", "t2", "mel60_l3", "ref_shape"):
+            before = t.stats()["allocs"]
+            _assert_same_bits(fresh[key], _bits(t, *calls[key]), key)
+            after = t.stats()
+            assert after["allocs"] == before + (1 if need[key] > high else 0), (key, before, after)
+            high = max(high, need[key])
+            assert after["device_bytes"] == high, (key, after, high)
+        assert t.stats()["allocs"] == 2
+        t.reserve(40, 30)
+        grown = t.stats()
+        assert grown["allocs"] == 3 and grown["device_bytes"] > high
+        _assert_same_bits(fresh["ref_shape"], _bits(t, *calls["ref_shape"]), "after reserve")
+        assert t.stats()["allocs"] == 3 and t.stats()["device_bytes"] == grown["device_bytes"]
+    finally:
+        t.close()
+
+
+def test_calls_from_two_streams_are_ordered_by_the_handle():
+    """A step on one stream, a step on a second stream without synchronising in between, a gradient call on the default stream: the
+    handle orders them by an event wait, so weights and gradient are the bits of the same three calls made on one stream."""
+    p = M.make_problem("ref_shape")
+    args = (p["x"], p["seq_len"], p["labels"])
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    one, two = _trainer(p), _trainer(p)
+    try:
+        want_loss = [one.step_raw(*args, 0.01), one.step_raw(*args, 0.01)]
+        want = _bits(one, *args)
+        want_w = one.weights_blob()
+        with torch.cuda.stream(s1):
+            l1 = two.step_raw(*args, 0.01)
+        with torch.cuda.stream(s2):
+            l2 = two.step_raw(*args, 0.01)
+        got = _bits(two, *args)
+        got_w = two.weights_blob()
+        torch.cuda.synchronize()
+        assert two.stats()["steps"] == 2
+        for a, b in zip(want_loss, (l1, l2)):
+            assert torch.equal(a, b)
+    finally:
+        one.close()
+        two.close()
+    _assert_same_bits(want, got, "two streams")
+    assert np.array_equal(want_w.view(np.uint32), got_w.view(np.uint32))
+    assert not np.array_equal(want_w, M.blob_of(p["w"]).astype(np.float32))          # ... and the two steps did move the weights
 
 
 def _train_toy(hidden):

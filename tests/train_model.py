@@ -195,8 +195,8 @@ class Optimizer(object):
             g = np.asarray(g, f)
             if self.kind == "adam":
                 lr_t = f(lr * np.sqrt(1.0 - 0.999 ** self.t) / (1.0 - 0.9 ** self.t))
-                self.m[i] = f(0.9) * self.m[i] + (f(1) - f(0.9)) * g
-                self.v[i] = f(0.999) * self.v[i] + (f(1) - f(0.999)) * g * g
+                self.m[i] = self.m[i] + (g - self.m[i]) * f(0.1)          # the kernel's form: 1 - beta is the constant, not beta
+                self.v[i] = self.v[i] + (g * g - self.v[i]) * f(0.001)
                 out.append(theta - lr_t * self.m[i] / (np.sqrt(self.v[i]) + f(1e-8)))
             else:
                 self.m[i] = f(0.9) * self.m[i] + g
@@ -244,7 +244,16 @@ def _ragged(b, t, zero_at, full_at, seed):
     return s.tolist()
 
 
+def _ragged_short(b, t, empty, full_at, seed):
+    """As _ragged with a list of empty slots, for the short T of the cases below: lengths from max(3, t // 3)."""
+    rng = np.random.default_rng(seed)
+    s = rng.integers(max(3, t // 3), t, size=b)
+    s[list(empty)], s[full_at] = 0, t
+    return s.tolist()
+
+
 _REF_LABELS = [[1, 2, 3, 3], [0, 1, 0, 2, 0], [4], [], [1, 2, 3, 3], [2, 2], [0, 4, 0]]
+_MEL_BATCH = (4, 4, 5, [5, 3, 4, 5], [[1], [0, 2], [2], [1, 1]])          # C, B, T, seq_len, labels of mel70 / mel72
 CASES = {
     "t1": (64, 1, 4, 3, 1, 1, [1], [[1]]),
     "t2": (64, 1, 4, 3, 1, 2, [2], [[0, 1]]),
@@ -258,7 +267,28 @@ CASES = {
     "no_path": (64, 2, 8, 6, 3, 8, [8, 5, 6], [[1, 2], [3, 3, 3, 3], [2]]),
     # 20 x 33 = 660 rows: 2.58 chunks of the weight-gradient reduction's 256 rows
     "split_rows": (64, 1, 8, 4, 20, 33, _ragged(20, 33, 3, 19, 3), [[1, 2], [0, 1, 0], [2]] * 6 + [[1], [2, 2, 1]]),
+    # ---- the paths the kernels specialise on outside the nine above, each at the smallest shape that reaches it ----
+    # hidden 256: gru_train_forward<4> / gru_train_backward<4> (four tiles per wave), a second group of two streams, C = 5
+    "h256": (256, 2, 24, 5, 18, 9, _ragged_short(18, 9, [4], 17, 4), [[1, 2, 3][:1 + i % 3] for i in range(18)]),
+    # 8 layers: every slot of the handle's per-layer tables, 6 * 8 + 2 = 50 weight-gradient jobs, seven flips of the dy ping-pong, C = 7
+    "l8": (64, 8, 8, 7, 3, 6, [6, 4, 5], [[1, 5], [0], [2, 2]]),
+    # the x-part GEMM beyond its first pass over K (64 k a pass): n_mel % 4 = 2 -> scalar loads and a partial block behind a full pass
+    "mel70": (64, 1, 70) + _MEL_BATCH,
+    # ... the same on the 16-byte loads: at k = 64 lane groups 2 and 3 have k + 3 >= K
+    "mel72": (64, 1, 72) + _MEL_BATCH,
+    # three passes, n_mel % 4 = 1, nine k-units of the weight gradient with the last one partial
+    "mel133": (128, 1, 133, 3, 2, 4, [4, 3], [[1], [0, 1]]),
+    # the largest n_mel a handle accepts: 16 full passes
+    "mel1024": (64, 1, 1024, 3, 2, 3, [3, 2], [[1], [0]]),
+    # streams 16..31 are all empty: the middle workgroup has tmax == 0 and runs only its zero-fill tails
+    "dead_group": (64, 2, 8, 4, 33, 7, _ragged_short(33, 7, range(16, 32), 32, 5), [[1, 2][:1 + i % 2] for i in range(33)]),
+    # two whole groups at full length: no invalid lane, no dead frame
+    "full_groups": (128, 1, 8, 6, 32, 6, [6] * 32, [_REF_LABELS[i % 7][:3] for i in range(32)]),
+    # 66 x 250 = 16500 rows: the weight-gradient reduction's chunks grow to 512 rows, 33 chunks with the last one partial
+    "rows_chunk512": (64, 1, 4, 3, 66, 250, _ragged_short(66, 250, [7], 65, 6), [[i % 2, 1, 0][:1 + i % 3] for i in range(66)]),
 }
+# the first nine: the cases whose full-length logits are also held against kws_step's at 2e-5 (tests/test_gpu_train.py)
+FIRST_CASES = ("t1", "t2", "odd_mel", "mel1", "ref_shape", "mel60_l3", "c8_s_long", "no_path", "split_rows")
 
 
 @functools.lru_cache(maxsize=None)
