@@ -1,5 +1,10 @@
-"""bf16 variant (BASELINE configs[2]) of the GRU path: against an oracle that rounds where the kernel
-rounds, and against the fp32 reference semantics (error and token-agreement report)."""
+"""bf16 variant (BASELINE configs[2]) of the GRU path over many frames: against an oracle that rounds where the kernel
+rounds, and against the fp32 reference semantics (error and token-agreement report).
+
+The tolerances here (6e-2 max / 6e-3 mean on the logits, 2e-2 on the state) have to absorb bf16 tie flips that the recurrence
+carries on, so they say nothing about an error below 1e-2.  The tight pin of the bf16 kernels is tests/test_gpu_bf16_step.py:
+one-frame calls against tests/bf16_step_model.py at fp32 accuracy (a few 1e-6, with a per-unit allowance only where r*h sits on
+a bf16 tie), long calls bit-equal to the chain of one-frame calls, and the 4-wave two-layer kernel in a child process."""
 import numpy as np
 import pytest
 import torch
