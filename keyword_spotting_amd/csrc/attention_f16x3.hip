@@ -18,35 +18,14 @@
 // lanes of two k offsets: for any odd 16-byte row stride two of the sixteen reads share a bank quad).
 // The embedding stages mel * 2^-8 against W_in * 2^8 (both exact): features up to 2^8 * 65504 stay representable.
 #include "attention_device.h"
+#include "f16x3_device.h"
 #include "launch.h"
 
 namespace kws {
 namespace {
 
-typedef _Float16 h16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float kLoScale = 2048.f, kLoInv = 1.f / 2048.f, kMelScale = 1.f / 256.f, kHalfMax = 65504.f;
 constexpr int kPlane = 2 * 64;      // 16-byte units of one 32-wide k chunk of an A plane: [2 row halves][64 lanes]
 
-__device__ __forceinline__ f32x4 mfma16(u32x4 a, u32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h16x8, a), __builtin_bit_cast(h16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ float clamp_half(float v) { return __builtin_fminf(__builtin_fmaxf(v, -kHalfMax), kHalfMax); }
-// two clamped values -> their packed hi and (2^11-scaled) lo pieces
-__device__ __forceinline__ void split2(f32x2 x, unsigned& hi, unsigned& lo) {
-    const h16x2 h = __builtin_convertvector(x, h16x2);
-    const f32x2 r = (x - __builtin_convertvector(h, f32x2)) * kLoScale;
-    const h16x2 l = __builtin_convertvector(r, h16x2);
-    hi = __builtin_bit_cast(unsigned, h);
-    lo = __builtin_bit_cast(unsigned, l);
-}
-__device__ __forceinline__ void split1(float x, _Float16& hi, _Float16& lo) {
-    hi = (_Float16)x;
-    lo = (_Float16)((x - (float)hi) * kLoScale);
-}
 // position (in halves) of X[r][k] in an A plane
 __device__ __forceinline__ int a_half_index(int r, int k) {
     return (((k >> 5) * 2 + (r >> 4)) * 64 + 16 * ((k >> 3) & 3) + (r & 15)) * 8 + (k & 7);
@@ -90,12 +69,12 @@ __device__ __forceinline__ void gemm32h(f32x4 (&acc)[2][NT], f32x4 (&lo)[2][NT],
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
             const u32x4 bh = wk[n * 128], bl = wk[n * 128 + 64];
-            acc[0][n] = mfma16(a0h, bh, acc[0][n]);
-            acc[1][n] = mfma16(a1h, bh, acc[1][n]);
-            lo[0][n] = mfma16(a0h, bl, lo[0][n]);
-            lo[1][n] = mfma16(a1h, bl, lo[1][n]);
-            lo[0][n] = mfma16(a0l, bh, lo[0][n]);
-            lo[1][n] = mfma16(a1l, bh, lo[1][n]);
+            acc[0][n] = mfma_f16(a0h, bh, acc[0][n]);
+            acc[1][n] = mfma_f16(a1h, bh, acc[1][n]);
+            lo[0][n] = mfma_f16(a0h, bl, lo[0][n]);
+            lo[1][n] = mfma_f16(a1h, bl, lo[1][n]);
+            lo[0][n] = mfma_f16(a0l, bh, lo[0][n]);
+            lo[1][n] = mfma_f16(a1l, bh, lo[1][n]);
         }
     }
 }

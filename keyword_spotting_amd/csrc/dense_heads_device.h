@@ -1,7 +1,8 @@
 // The phases of the class-head kernels behind the GRU stack, each defined once: dense_heads_kernel (dense_heads.hip: kws_step_heads),
 // heads_window_kernel (heads_window.hip: the two-head stream manager) and the two bank kernels (bank_heads.hip, with bank_device.h
 // for what only a bank has) all compile this code, so a row's logits, softmax and word are the same bits through any of them.
-//   per frame      head_operands, seam_row / seam_row_step, KWS_HEAD_PROJECT, load_row8 / store_row8, head_row, store_row
+//   per frame      head_operands, seam_row / seam_row_step, KWS_HEAD_PROJECT; the row tail (load_row8 / store_row8, head_row,
+//                  store_row) is gru_device.h's, shared with the fused epilogues of the GRU kernels
 //   a step         heads_tokens (tokens and the carried word of a frame block)
 //   a manager      heads_window_carve (the LDS of the launch), heads_window_couple (a hit of either head clears both windows)
 #pragma once
@@ -26,64 +27,6 @@ namespace {      // internal linkage, as when these lived in dense_heads.hip
             _Pragma("unroll") for (int e = 0; e < 4; ++e) part[n / (NT / 4)] = mfma4(wa[4 * n + e], v[n][e], part[n / (NT / 4)]); \
         acc = ((part[0] + part[1]) + part[2]) + part[3];                                                                     \
     }
-
-// relu / clip, softmax and the ctc_decode2 frame rule of one row: the arithmetic of epilogue_flush (gru_device.h)
-__device__ __forceinline__ int head_row(float (&lg)[kMaxClasses], float (&pr)[kMaxClasses], int C, int use_relu, float value_clip, float thres) {
-    if (use_relu) {
-#pragma unroll
-        for (int c = 0; c < kMaxClasses; ++c) {
-            lg[c] = fmaxf(lg[c], 0.f);
-            if (value_clip > 0.f) lg[c] = fminf(lg[c], 20.f);
-        }
-    }
-    float m = lg[0];
-#pragma unroll
-    for (int c = 1; c < kMaxClasses; ++c) m = (c < C) ? fmaxf(m, lg[c]) : m;
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < kMaxClasses; ++c) {
-        pr[c] = (c < C) ? __expf(lg[c] - m) : 0.f;
-        sum += pr[c];
-    }
-    const float inv = __builtin_amdgcn_rcpf(sum);
-#pragma unroll
-    for (int c = 0; c < kMaxClasses; ++c) pr[c] *= inv;
-    // classes 1..C-2 (utils/prediction.py:67,74-75): first maximum, strict >
-    int word = -1;
-    float best = -1.f;
-#pragma unroll
-    for (int c = 1; c < kMaxClasses - 1; ++c) {
-        if (c < C - 1 && pr[c] > best) { best = pr[c]; word = c - 1; }
-    }
-    return best > thres ? word : -1;
-}
-
-// a row of C floats; rows of an even C are 8-byte aligned (the outputs are, as kws_step's)
-__device__ __forceinline__ void store_row(float* dst, const float (&v)[kMaxClasses], int C) {
-    if ((C & 1) == 0) {
-        float2* o = reinterpret_cast<float2*>(dst);
-#pragma unroll
-        for (int c = 0; c < kMaxClasses / 2; ++c)
-            if (2 * c < C) o[c] = make_float2(v[2 * c], v[2 * c + 1]);
-    } else {
-#pragma unroll
-        for (int c = 0; c < kMaxClasses; ++c)
-            if (c < C) dst[c] = v[c];
-    }
-}
-
-// the 8 floats of one LDS logit row, as two b128
-__device__ __forceinline__ void load_row8(const float* src, float (&lg)[kMaxClasses]) {
-    const f32x4* row = reinterpret_cast<const f32x4*>(src);
-    const f32x4 lo = row[0], hi = row[1];
-#pragma unroll
-    for (int c = 0; c < 4; ++c) { lg[c] = lo[c]; lg[4 + c] = hi[c]; }
-}
-__device__ __forceinline__ void store_row8(float* dst, const float (&v)[kMaxClasses]) {
-    f32x4* row = reinterpret_cast<f32x4*>(dst);
-    row[0] = (f32x4){v[0], v[1], v[2], v[3]};
-    row[1] = (f32x4){v[4], v[5], v[6], v[7]};
-}
 
 // A operands of one head (DenseHead or HeadsWindowHead): Wfc^T, k-chunk kc in wa[kc], and the lane's four biases; an absent head
 // (on == false) reads nothing and keeps zeros

@@ -1,5 +1,10 @@
-// Device helpers shared by the GRU kernels (gru_kernels.hip, gru_resident.hip, gru_bf16.hip, gru_f16x3.hip, gru_f16x3_generic.hip, gru_octbit.hip)
-// and the mel front-ends (frontend_kernels.hip, fft_frontend.hip).
+// Device helpers shared by the GRU kernels (gru_kernels.hip, gru_resident.hip, gru_bf16.hip, gru_f16x3.hip, gru_f16x3_generic.hip, gru_octbit.hip),
+// the class-head kernels (through dense_heads_device.h) and the mel front-ends (frontend_kernels.hip, fft_frontend.hip):
+//   arithmetic      mfma4, KWS_MFMA_A and its fences, the activations, bitsel, static_for, lds_barrier
+//   the row tail    head_row, store_row, load_row8 / store_row8 -- one text for every path that turns 8 logits into a row of outputs --
+//                   and carried_word, the word a stream brings into a call
+//   the epilogues   epilogue_fold / epilogue_flush (a folded ring) and epilogue_flush_partials (the resident kernels), store_rows
+// The f16x3 operand split is f16x3_device.h, the layer-pipelined protocol pipeline_device.h.
 #pragma once
 #include <type_traits>
 
@@ -107,6 +112,105 @@ __device__ __forceinline__ void lds_barrier() {
     asm volatile("" ::: "memory");
 }
 // ------------------------------------------------------------------------------------------------
+// The row tail: what every path does with the 8 logits of one frame of one stream (models/rnn_ctc.py:247-284 behind the dense
+// product, :165, utils/prediction.py:65-86).  Written ONCE: the epilogues below, the class-head kernels (dense_heads_device.h) and
+// the int8 projection (gru_octbit.hip) all call it, so a row is the same bits through any of them.
+// ------------------------------------------------------------------------------------------------
+// relu / clip, softmax and the ctc_decode2 frame rule of one row; returns the frame's word or -1
+__device__ __forceinline__ int head_row(float (&lg)[kMaxClasses], float (&pr)[kMaxClasses], int C, int use_relu, float value_clip, float thres) {
+    if (use_relu) {
+#pragma unroll
+        for (int c = 0; c < kMaxClasses; ++c) {
+            lg[c] = fmaxf(lg[c], 0.f);
+            if (value_clip > 0.f) lg[c] = fminf(lg[c], 20.f);
+        }
+    }
+    float m = lg[0];
+#pragma unroll
+    for (int c = 1; c < kMaxClasses; ++c) m = (c < C) ? fmaxf(m, lg[c]) : m;
+    float sum = 0.f;
+#pragma unroll
+    for (int c = 0; c < kMaxClasses; ++c) {
+        pr[c] = (c < C) ? __expf(lg[c] - m) : 0.f;     // arguments <= 0: abs error < 1e-7
+        sum += pr[c];
+    }
+    const float inv = __builtin_amdgcn_rcpf(sum);
+#pragma unroll
+    for (int c = 0; c < kMaxClasses; ++c) pr[c] *= inv;
+    // classes 1..C-2 (utils/prediction.py:67,74-75): first maximum, strict >
+    int word = -1;
+    float best = -1.f;
+#pragma unroll
+    for (int c = 1; c < kMaxClasses - 1; ++c) {
+        if (c < C - 1 && pr[c] > best) { best = pr[c]; word = c - 1; }
+    }
+    return best > thres ? word : -1;
+}
+
+// a row of C floats; rows of an even C are 8-byte aligned (the outputs are, as kws_step's)
+__device__ __forceinline__ void store_row(float* dst, const float (&v)[kMaxClasses], int C) {
+    if ((C & 1) == 0) {
+        float2* o = reinterpret_cast<float2*>(dst);
+#pragma unroll
+        for (int c = 0; c < kMaxClasses / 2; ++c)
+            if (2 * c < C) o[c] = make_float2(v[2 * c], v[2 * c + 1]);
+    } else {
+#pragma unroll
+        for (int c = 0; c < kMaxClasses; ++c)
+            if (c < C) dst[c] = v[c];
+    }
+}
+
+// the 8 floats of one LDS logit row, as two b128
+__device__ __forceinline__ void load_row8(const float* src, float (&lg)[kMaxClasses]) {
+    const f32x4* row = reinterpret_cast<const f32x4*>(src);
+    const f32x4 lo = row[0], hi = row[1];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) { lg[c] = lo[c]; lg[4 + c] = hi[c]; }
+}
+__device__ __forceinline__ void store_row8(float* dst, const float (&v)[kMaxClasses]) {
+    f32x4* row = reinterpret_cast<f32x4*>(dst);
+    row[0] = (f32x4){v[0], v[1], v[2], v[3]};
+    row[1] = (f32x4){v[4], v[5], v[6], v[7]};
+}
+// The fused epilogues' store of output row `row` ([B, T, C] row-major), logits and softmax each where asked for.  The same bytes as
+// two store_row; written apart because the shape matters inside the GRU kernels: the product's C == 6 as three unconditional
+// 8-byte stores and every other C scalar-wise costs the last-layer frame loops fewer scalar registers than store_row's four
+// predicated pairs (with store_row here, 11 last-layer kernels went past their SGPR-spill bounds in spill_expectations.txt).
+__device__ __forceinline__ void store_rows(const GruLayerParams& p, size_t row, const float (&lg)[kMaxClasses], const float (&pr)[kMaxClasses]) {
+    const int C = p.C;
+    if (C == 6) {       // rows are 24 B
+        if (p.logits) {
+            float2* o = reinterpret_cast<float2*>(p.logits + row * 6);
+            o[0] = make_float2(lg[0], lg[1]); o[1] = make_float2(lg[2], lg[3]); o[2] = make_float2(lg[4], lg[5]);
+        }
+        if (p.softmax) {
+            float2* o = reinterpret_cast<float2*>(p.softmax + row * 6);
+            o[0] = make_float2(pr[0], pr[1]); o[1] = make_float2(pr[2], pr[3]); o[2] = make_float2(pr[4], pr[5]);
+        }
+    } else {
+        if (p.logits) {
+#pragma unroll
+            for (int c = 0; c < kMaxClasses; ++c)
+                if (c < C) p.logits[row * C + c] = lg[c];
+        }
+        if (p.softmax) {
+#pragma unroll
+            for (int c = 0; c < kMaxClasses; ++c)
+                if (c < C) p.softmax[row * C + c] = pr[c];
+        }
+    }
+}
+// The word stream b carries into a call: prev_word, or -1 for a reset stream, a stream past the batch, or with no prev_word at all.
+// The kernel-argument fields come by REFERENCE and are read where the test needs them: taken by value they are fetched ahead of
+// the call and wait in scalar registers, which the last-layer kernels have not got (gru_stack_bf16_ls went past its bounds in
+// spill_expectations.txt that way).
+__device__ __forceinline__ int carried_word(const int32_t* const& prev_word, const uint8_t* const& reset, int b, const int& B) {
+    int pw = -1;
+    if (b < B && prev_word && !(reset && reset[b])) pw = prev_word[b];
+    return pw;
+}
+// ------------------------------------------------------------------------------------------------
 // Last-layer epilogue.  Each wave leaves the partial logits of its 32 units in `pstage`; after the
 // frame's second barrier ONE wave (rotating, w == t & 3) folds the four partials into a 16-frame ring.
 // Every kRingFrames frames (and at the end of the call) ALL FOUR waves flush: wave w takes frames
@@ -136,6 +240,12 @@ __device__ __forceinline__ EpilogueLds epilogue_carve(char* base) {
     return e;
 }
 
+// top of a group, before its first barrier: the words the group's 16 streams carry in
+__device__ __forceinline__ void epilogue_carry_init(const EpilogueLds& e, const int32_t* const& prev_word, const uint8_t* const& reset, int group,
+                                                    const int& B, int tid) {
+    if (tid < 16) e.carry[tid] = carried_word(prev_word, reset, group * kStreamsPerGroup + tid, B);
+}
+
 // fold the 4 partial logit vectors of frame t into the ring: 32 lanes, (stream, half) each
 __device__ __forceinline__ void epilogue_fold(const EpilogueLds& e, int t, int lane) {
     if (lane < 32) {
@@ -159,42 +269,9 @@ __device__ __forceinline__ void epilogue_flush(const GruLayerParams& p, const Ep
     const int f = 4 * w + (lane & 3);          // frame within the block
     const int s = lane >> 2;
     const int b = group * kStreamsPerGroup + s;
-    const int C = p.C;
-    float lg[kMaxClasses];
-    {
-        const f32x4* row = reinterpret_cast<const f32x4*>(e.lring + (f * 16 + s) * 8);
-        const f32x4 lo = row[0], hi = row[1];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { lg[c] = lo[c]; lg[4 + c] = hi[c]; }
-    }
-    if (p.use_relu) {
-#pragma unroll
-        for (int c = 0; c < kMaxClasses; ++c) {
-            lg[c] = fmaxf(lg[c], 0.f);
-            if (p.value_clip > 0.f) lg[c] = fminf(lg[c], 20.f);
-        }
-    }
-    float m = lg[0];
-#pragma unroll
-    for (int c = 1; c < kMaxClasses; ++c) m = (c < C) ? fmaxf(m, lg[c]) : m;
-    float pr[kMaxClasses];
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < kMaxClasses; ++c) {
-        pr[c] = (c < C) ? __expf(lg[c] - m) : 0.f;     // arguments <= 0: abs error < 1e-7
-        sum += pr[c];
-    }
-    const float inv = __builtin_amdgcn_rcpf(sum);
-#pragma unroll
-    for (int c = 0; c < kMaxClasses; ++c) pr[c] *= inv;
-    // ctc_decode2 frame rule over classes 1..C-2 (utils/prediction.py:67,74-75): first maximum, strict >
-    int word = -1;
-    float best = -1.f;
-#pragma unroll
-    for (int c = 1; c < kMaxClasses - 1; ++c) {
-        if (c < C - 1 && pr[c] > best) { best = pr[c]; word = c - 1; }
-    }
-    if (!(best > p.decode_thres)) word = -1;
+    float lg[kMaxClasses], pr[kMaxClasses];
+    load_row8(e.lring + (f * 16 + s) * 8, lg);
+    const int word = head_row(lg, pr, p.C, p.use_relu, p.value_clip, p.decode_thres);
     e.words[f * 16 + s] = word;
     if (e.cwords != nullptr) {       // the call's words wait for the window tail (row offset from an opaque copy of the lane, as above)
         int ln = lane;
@@ -204,29 +281,7 @@ __device__ __forceinline__ void epilogue_flush(const GruLayerParams& p, const Ep
     }
     const bool mine = b < p.B && f < n;
     const size_t row = (size_t)b * (p.t_stride ? p.t_stride : p.T) + (t0 + f);
-    if (mine) {
-        if (C == 6) {       // rows are 24 B: three 8-byte stores
-            if (p.logits) {
-                float2* o = reinterpret_cast<float2*>(p.logits + row * 6);
-                o[0] = make_float2(lg[0], lg[1]); o[1] = make_float2(lg[2], lg[3]); o[2] = make_float2(lg[4], lg[5]);
-            }
-            if (p.softmax) {
-                float2* o = reinterpret_cast<float2*>(p.softmax + row * 6);
-                o[0] = make_float2(pr[0], pr[1]); o[1] = make_float2(pr[2], pr[3]); o[2] = make_float2(pr[4], pr[5]);
-            }
-        } else {
-            if (p.logits) {
-#pragma unroll
-                for (int c = 0; c < kMaxClasses; ++c)
-                    if (c < C) p.logits[row * C + c] = lg[c];
-            }
-            if (p.softmax) {
-#pragma unroll
-                for (int c = 0; c < kMaxClasses; ++c)
-                    if (c < C) p.softmax[row * C + c] = pr[c];
-            }
-        }
-    }
+    if (mine) store_rows(p, row, lg, pr);
     lds_barrier();            // every wave's words are in LDS
     const int blk = (t0 / kRingFrames) & 1;
     const int prev = f == 0 ? e.carry[blk * 16 + s] : e.words[(f - 1) * 16 + s];
@@ -268,7 +323,6 @@ __device__ __forceinline__ void epilogue_flush_partials(const GruLayerParams& p,
     const int f = lane & 15;                   // frame within the block
     const int s = 4 * w + (lane >> 4);
     const int b = group * kStreamsPerGroup + s;
-    const int C = p.C;
     float lg[kMaxClasses];
     {
         const f32x4* row = reinterpret_cast<const f32x4*>(ring + f * kPartialSlotFloats + s * 8);
@@ -278,60 +332,12 @@ __device__ __forceinline__ void epilogue_flush_partials(const GruLayerParams& p,
 #pragma unroll
         for (int c = 0; c < 4; ++c) { lg[c] = lo[c]; lg[4 + c] = hi[c]; }
     }
-    if (p.use_relu) {
-#pragma unroll
-        for (int c = 0; c < kMaxClasses; ++c) {
-            lg[c] = fmaxf(lg[c], 0.f);
-            if (p.value_clip > 0.f) lg[c] = fminf(lg[c], 20.f);
-        }
-    }
-    float m = lg[0];
-#pragma unroll
-    for (int c = 1; c < kMaxClasses; ++c) m = (c < C) ? fmaxf(m, lg[c]) : m;
     float pr[kMaxClasses];
-    float sum = 0.f;
-#pragma unroll
-    for (int c = 0; c < kMaxClasses; ++c) {
-        pr[c] = (c < C) ? __expf(lg[c] - m) : 0.f;     // arguments <= 0: abs error < 1e-7
-        sum += pr[c];
-    }
-    const float inv = __builtin_amdgcn_rcpf(sum);
-#pragma unroll
-    for (int c = 0; c < kMaxClasses; ++c) pr[c] *= inv;
-    // ctc_decode2 frame rule over classes 1..C-2 (utils/prediction.py:67,74-75): first maximum, strict >
-    int word = -1;
-    float best = -1.f;
-#pragma unroll
-    for (int c = 1; c < kMaxClasses - 1; ++c) {
-        if (c < C - 1 && pr[c] > best) { best = pr[c]; word = c - 1; }
-    }
-    if (!(best > p.decode_thres)) word = -1;
+    const int word = head_row(lg, pr, p.C, p.use_relu, p.value_clip, p.decode_thres);
     if (cwords != nullptr && f < n) cwords[s * kWinTailWordsStride + t0 + f] = (int8_t)word;
     const bool mine = b < p.B && f < n;
     const size_t row = (size_t)b * (p.t_stride ? p.t_stride : p.T) + (t0 + f);
-    if (mine) {
-        if (C == 6) {       // rows are 24 B: three 8-byte stores
-            if (p.logits) {
-                float2* o = reinterpret_cast<float2*>(p.logits + row * 6);
-                o[0] = make_float2(lg[0], lg[1]); o[1] = make_float2(lg[2], lg[3]); o[2] = make_float2(lg[4], lg[5]);
-            }
-            if (p.softmax) {
-                float2* o = reinterpret_cast<float2*>(p.softmax + row * 6);
-                o[0] = make_float2(pr[0], pr[1]); o[1] = make_float2(pr[2], pr[3]); o[2] = make_float2(pr[4], pr[5]);
-            }
-        } else {
-            if (p.logits) {
-#pragma unroll
-                for (int c = 0; c < kMaxClasses; ++c)
-                    if (c < C) p.logits[row * C + c] = lg[c];
-            }
-            if (p.softmax) {
-#pragma unroll
-                for (int c = 0; c < kMaxClasses; ++c)
-                    if (c < C) p.softmax[row * C + c] = pr[c];
-            }
-        }
-    }
+    if (mine) store_rows(p, row, lg, pr);
     // row_shr:1 -- lane f takes the word of lane f - 1 of its row; the row's first lane has no source and keeps `carry`
     const int prev = __builtin_amdgcn_update_dpp(carry, word, 0x111, 0xf, 0xf, false);
     const int token = (word >= 0 && word != prev) ? word + 1 : 0;   // utils/prediction.py:76-80

@@ -20,42 +20,15 @@
 // counters, exactly the protocol of gru_stack_generic_pipelined.
 #include <cstddef>
 
+#include "f16x3_device.h"
 #include "gru_device.h"
 #include "launch.h"
+#include "pipeline_device.h"
 
 namespace kws {
 
 namespace {
-
-typedef _Float16 g16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 g16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned gu32x4 __attribute__((ext_vector_type(4)));
-typedef int gi32x4 __attribute__((ext_vector_type(4)));
-
-constexpr float kGLoScale = 2048.f, kGLoInv = 1.f / 2048.f, kGMelScale = 1.f / 256.f, kGHalfMax = 65504.f;
-
-__device__ __forceinline__ g16x8 g_f16x8(gu32x4 v) { return __builtin_bit_cast(g16x8, v); }
-__device__ __forceinline__ f32x4 g_mfma(gu32x4 a, gu32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(g_f16x8(a), g_f16x8(b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void g_split2(f32x2 x, unsigned& hi, unsigned& lo) {
-    const g16x2 h = __builtin_convertvector(x, g16x2);
-    const f32x2 r = (x - __builtin_convertvector(h, f32x2)) * kGLoScale;
-    const g16x2 l = __builtin_convertvector(r, g16x2);
-    hi = __builtin_bit_cast(unsigned, h);
-    lo = __builtin_bit_cast(unsigned, l);
-}
-// two C tiles -> one chunk of the next B operand, (hi, lo)
-__device__ __forceinline__ void g_split8(const f32x4& a, const f32x4& b, gu32x4& hi, gu32x4& lo) {
-    unsigned h[4], l[4];
-    g_split2((f32x2){a[0], a[1]}, h[0], l[0]);
-    g_split2((f32x2){a[2], a[3]}, h[1], l[1]);
-    g_split2((f32x2){b[0], b[1]}, h[2], l[2]);
-    g_split2((f32x2){b[2], b[3]}, h[3], l[3]);
-    hi = (gu32x4){h[0], h[1], h[2], h[3]};
-    lo = (gu32x4){l[0], l[1], l[2], l[3]};
-}
-
+typedef int i32x4 __attribute__((ext_vector_type(4)));
 }  // namespace
 
 size_t gru_f16x3_generic_lds_bytes(int hidden, bool last) {
@@ -81,24 +54,23 @@ __device__ __forceinline__ void gru_f16x3_generic_body(const GruF16Params& p, co
     const int KX = FIRST ? 2 * ((p.I + 63) / 64) : HC, KC = KX + HC;      // the first layer's x chunks padded to an even count (zero operands)
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    gu32x4* hb = reinterpret_cast<gu32x4*>(smem);              // [HC][hi|lo][64]  h_{t-1}
-    gu32x4* rhb = hb + HC * 2 * 64;                             // [HC][2][64]      r (.) h_{t-1}
-    gu32x4* xsb = rhb + HC * 2 * 64;                            // [HC][2][64]      this frame's input (the first layer uses KX <= 2 chunks)
+    u32x4* hb = reinterpret_cast<u32x4*>(smem);              // [HC][hi|lo][64]  h_{t-1}
+    u32x4* rhb = hb + HC * 2 * 64;                             // [HC][2][64]      r (.) h_{t-1}
+    u32x4* xsb = rhb + HC * 2 * 64;                            // [HC][2][64]      this frame's input (the first layer uses KX <= 2 chunks)
     float* biasl = reinterpret_cast<float*>(xsb + HC * 2 * 64); // [3][H] + [16]
     const EpilogueLds epi = epilogue_carve(reinterpret_cast<char*>(biasl + 3 * H + 16 + 4));  // LAST only ([3H + 16 .. +4): the pipelined launch's flag)
 
     // the weight stream: buffer loads, lane offset in one VGPR, the operand index in the scalar offset (1 KiB per operand)
     const __amdgpu_buffer_rsrc_t w_rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint4*>(p.w), (short)0, 0x7fffffff, 0x00020000);
     const int lane16 = lane * 16;
-    auto wload = [&](int tile, int q, int c, int hl) -> gu32x4 {
-        return __builtin_bit_cast(gu32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, lane16, ((((tile * 3 + q) * KC + c) * 2 + hl)) * 1024, 0));
+    auto wload = [&](int tile, int q, int c, int hl) -> u32x4 {
+        return __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(w_rsrc, lane16, ((((tile * 3 + q) * KC + c) * 2 + hl)) * 1024, 0));
     };
-    constexpr int kSysScope = 1 | 16;            // sc0 | sc1: past the non-coherent cache levels (the pipelined launch's seams)
 
     // kws_create folded the exponent scales into the weights (gates: -log2 e, candidate: 2 log2 e): the biases get them here
     for (int i = tid; i < 3 * H; i += 256) biasl[i] = p.bias[i] * (i < 2 * H ? -kLog2e : 2.0f * kLog2e);
     if (LAST && tid < 16) biasl[3 * H + tid] = p.bfc[tid];
-    for (int i = tid; i < HC * 2 * 64; i += 256) xsb[i] = (gu32x4){0u, 0u, 0u, 0u};
+    for (int i = tid; i < HC * 2 * 64; i += 256) xsb[i] = (u32x4){0u, 0u, 0u, 0u};
     const f32x4* bl = reinterpret_cast<const f32x4*>(biasl);
 
     const bool do_reset = p.reset != nullptr && p.reset[b] != 0;
@@ -108,24 +80,19 @@ __device__ __forceinline__ void gru_f16x3_generic_body(const GruF16Params& p, co
     for (int j = 0; j < TPW; ++j) hreg[j] = do_reset ? splat4(0.f) : ld4(p.state_in + (size_t)b * H + (TPW * w + j) * 16 + 4 * g);
 #pragma unroll
     for (int jj = 0; jj < CPW; ++jj) {
-        gu32x4 hi, lo;
-        g_split8(hreg[2 * jj], hreg[2 * jj + 1], hi, lo);
+        u32x4 hi, lo;
+        split8_scaled(hreg[2 * jj], hreg[2 * jj + 1], hi, lo);
         hb[((CPW * w + jj) * 2 + 0) * 64 + lane] = hi;
         hb[((CPW * w + jj) * 2 + 1) * 64 + lane] = lo;
     }
-    if (LAST && tid < 16) {
-        const int bb = group * kStreamsPerGroup + tid;
-        int pw = -1;
-        if (bb < p.B && p.epi.prev_word && !(p.reset && p.reset[bb])) pw = p.epi.prev_word[bb];
-        epi.carry[tid] = pw;
-    }
+    if (LAST) epilogue_carry_init(epi, p.epi.prev_word, p.reset, group, p.B, tid);
     // the projection's operands: this wave's chunks of Wfc^T (hi, lo), resident
-    gu32x4 wfc[CPW][2];
+    u32x4 wfc[CPW][2];
     if (LAST) {
 #pragma unroll
         for (int jj = 0; jj < CPW; ++jj)
 #pragma unroll
-            for (int hl = 0; hl < 2; ++hl) wfc[jj][hl] = __builtin_bit_cast(gu32x4, p.wfc[((CPW * w + jj) * 2 + hl) * 64 + lane]);
+            for (int hl = 0; hl < 2; ++hl) wfc[jj][hl] = __builtin_bit_cast(u32x4, p.wfc[((CPW * w + jj) * 2 + hl) * 64 + lane]);
     }
 
     // ---- input: FIRST: wave w brings streams 4w..4w+3 of the mel frame (one dwordx4 per lane), scales, clamps, splits and scatters
@@ -143,14 +110,10 @@ __device__ __forceinline__ void gru_f16x3_generic_body(const GruF16Params& p, co
     };
     auto mel_commit = [&]() {
         if (xl_active) {
-            f32x4 v = melv * kGMelScale;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) v[e] = __builtin_fminf(__builtin_fmaxf(v[e], -kGHalfMax), kGHalfMax);
-            unsigned h0, l0, h1, l1;
-            g_split2((f32x2){v[0], v[1]}, h0, l0);
-            g_split2((f32x2){v[2], v[3]}, h1, l1);
-            *reinterpret_cast<uint2*>(xsb_dw + xs_lane) = make_uint2(h0, h1);
-            *reinterpret_cast<uint2*>(xsb_dw + 64 * 4 + xs_lane) = make_uint2(l0, l1);
+            uint2 hi, lo;
+            mel_split4(melv, hi, lo);
+            *reinterpret_cast<uint2*>(xsb_dw + xs_lane) = hi;
+            *reinterpret_cast<uint2*>(xsb_dw + 64 * 4 + xs_lane) = lo;
         }
     };
     // this group's [T][HC][2][64] x 16 B blocks of the seams
@@ -159,12 +122,12 @@ __device__ __forceinline__ void gru_f16x3_generic_body(const GruF16Params& p, co
     const __amdgpu_buffer_rsrc_t ho_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         LAST ? const_cast<uint4*>(p.w) : const_cast<uint4*>(p.h_out + (size_t)group * T * HC * 2 * 64), (short)0, 0x7fffffff, 0x00020000);
     constexpr int XF = HC * 2 / 4;                // seam operands (1 KiB) of a frame per wave
-    gu32x4 xin[XF];
+    u32x4 xin[XF];
     auto seam_fetch = [&](int t_req) {          // the pipelined launch reads rows another CU has just written: system scope
         const int t = t_req < T ? t_req : T - 1;
 #pragma unroll
         for (int i = 0; i < XF; ++i)
-            xin[i] = __builtin_bit_cast(gu32x4, __builtin_amdgcn_raw_buffer_load_b128(xp_rsrc, lane16, (t * (HC * 2) + (w + 4 * i)) * 1024, PIPE ? kSysScope : 0));
+            xin[i] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(xp_rsrc, lane16, (t * (HC * 2) + (w + 4 * i)) * 1024, PIPE ? kSysScope : 0));
     };
     auto seam_commit = [&]() {
 #pragma unroll
@@ -182,7 +145,7 @@ __device__ __forceinline__ void gru_f16x3_generic_body(const GruF16Params& p, co
     // NEXT phase's first row instead -- the weights do not depend on the data, so the stream never drains at a phase
     // boundary, a barrier or a frame boundary (the candidate's first row lands during the r / u activations, the next frame's
     // first x row during tanh / update).
-    struct Row { gu32x4 a[TPW * 6]; };
+    struct Row { u32x4 a[TPW * 6]; };
     auto load_x = [&](Row& r, int c) {
 #pragma unroll
         for (int j = 0; j < TPW; ++j)
@@ -231,14 +194,7 @@ __device__ __forceinline__ void gru_f16x3_generic_body(const GruF16Params& p, co
                 al[j][q] = splat4(0.f);
             }
         if (PIPE && !FIRST && !have_x) {
-            // frame t of the layer below must have landed (its workgroup runs concurrently on another CU): every wave polls for
-            // itself, bounded -- a protocol bug becomes a wrong answer plus an error flag, not a hung GPU (gru_kernels.hip)
-            int spins = 0;
-            while (__hip_atomic_load(p.epi.ready_in + group, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= t) {
-                __builtin_amdgcn_s_sleep(2);
-                if (++spins > (1 << 24)) { if (lane == 0) *reinterpret_cast<volatile int*>(p.epi.pipe_error) = 1; break; }
-            }
-            asm volatile("" ::: "memory");
+            pipeline_wait(p.epi.ready_in, p.epi.pipe_error, group, t, lane);     // frame t of the layer below has landed
             seam_fetch(t);
             seam_commit();
             __syncthreads();
@@ -246,41 +202,49 @@ __device__ __forceinline__ void gru_f16x3_generic_body(const GruF16Params& p, co
         int ahead = 0;
         if (PIPE && !FIRST && tid == 0 && t + 1 < T)
             ahead = __hip_atomic_load(p.epi.ready_in + group, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);       // (lands under the MFMAs below)
+        // One row against one 32-wide chunk of a B operand in LDS (op: its hi block, the lo block 64 x 16 B behind it): gates
+        // 0..NQ-1 of every tile, three MFMAs per product, pinned behind the row's load.  X rows carry NQ = 3 gates, H rows 2.
+        auto mma_gates = [&](auto nq_, const Row& r, const u32x4* op) {
+            constexpr int NQ = decltype(nq_)::value;
+            const u32x4 xh = op[lane], xl = op[64 + lane];
+#pragma unroll
+            for (int j = 0; j < TPW; ++j)
+#pragma unroll
+                for (int q = 0; q < NQ; ++q) {
+                    am[j][q] = mfma_f16(r.a[(j * NQ + q) * 2 + 0], xh, am[j][q]);
+                    al[j][q] = mfma_f16(r.a[(j * NQ + q) * 2 + 1], xh, al[j][q]);
+                    al[j][q] = mfma_f16(r.a[(j * NQ + q) * 2 + 0], xl, al[j][q]);
+                }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        // ... a candidate row: two chunks of r (.) h, gate 2 of every tile
+        auto mma_cand = [&](const Row& r, int m2) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+                const u32x4 xh = rhb[((2 * m2 + k) * 2 + 0) * 64 + lane], xl = rhb[((2 * m2 + k) * 2 + 1) * 64 + lane];
+#pragma unroll
+                for (int j = 0; j < TPW; ++j) {
+                    am[j][2] = mfma_f16(r.a[(k * TPW + j) * 2 + 0], xh, am[j][2]);
+                    al[j][2] = mfma_f16(r.a[(k * TPW + j) * 2 + 1], xh, al[j][2]);
+                    al[j][2] = mfma_f16(r.a[(k * TPW + j) * 2 + 0], xl, al[j][2]);
+                }
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        constexpr std::integral_constant<int, 3> kGatesX{};
+        constexpr std::integral_constant<int, 2> kGatesH{};
         // ---- x-part of r, u, c ----
-#define KWS_G_MMA_X(R_, C_)                                                                             \
-        {                                                                                                \
-            const gu32x4 xh = xsb[((C_) * 2 + 0) * 64 + lane], xl = xsb[((C_) * 2 + 1) * 64 + lane];     \
-            _Pragma("unroll") for (int j = 0; j < TPW; ++j)                                              \
-                _Pragma("unroll") for (int q = 0; q < 3; ++q) {                                          \
-                    am[j][q] = g_mfma(R_.a[(j * 3 + q) * 2 + 0], xh, am[j][q]);                          \
-                    al[j][q] = g_mfma(R_.a[(j * 3 + q) * 2 + 1], xh, al[j][q]);                          \
-                    al[j][q] = g_mfma(R_.a[(j * 3 + q) * 2 + 0], xl, al[j][q]);                          \
-                }                                                                                        \
-            __builtin_amdgcn_sched_barrier(0);                                                           \
-        }
 #pragma nounroll
         for (int c = 0; c < KX; c += 2) {                       // KX is even
-            KWS_G_MMA_X(ra, c);
+            mma_gates(kGatesX, ra, xsb + c * 2 * 64);
             if (c + 2 < KX) load_x(ra, c + 2); else load_h(ra, 0);
-            KWS_G_MMA_X(rb, c + 1);
+            mma_gates(kGatesX, rb, xsb + (c + 1) * 2 * 64);
             if (c + 3 < KX) load_x(rb, c + 3); else load_h(rb, 1);
         }
-#undef KWS_G_MMA_X
         // ---- recurrent part of r and u ----
-#define KWS_G_MMA_H(R_, M_)                                                                             \
-        {                                                                                                \
-            const gu32x4 xh = hb[((M_) * 2 + 0) * 64 + lane], xl = hb[((M_) * 2 + 1) * 64 + lane];       \
-            _Pragma("unroll") for (int j = 0; j < TPW; ++j)                                              \
-                _Pragma("unroll") for (int q = 0; q < 2; ++q) {                                          \
-                    am[j][q] = g_mfma(R_.a[(j * 2 + q) * 2 + 0], xh, am[j][q]);                          \
-                    al[j][q] = g_mfma(R_.a[(j * 2 + q) * 2 + 1], xh, al[j][q]);                          \
-                    al[j][q] = g_mfma(R_.a[(j * 2 + q) * 2 + 0], xl, al[j][q]);                          \
-                }                                                                                        \
-            __builtin_amdgcn_sched_barrier(0);                                                           \
-        }
 #pragma nounroll
         for (int m = 0; m < HC; m += 2) {                       // HC is even
-            KWS_G_MMA_H(ra, m);
+            mma_gates(kGatesH, ra, hb + m * 2 * 64);
             if (m + 2 < HC) load_h(ra, m + 2);
             else {
                 // ... the candidate's rows do not depend on the exchange below.  Pipelined producer: the seam rows of the frame
@@ -290,10 +254,9 @@ __device__ __forceinline__ void gru_f16x3_generic_body(const GruF16Params& p, co
                 if (PIPE && !LAST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 load_c(ra, 0);
             }
-            KWS_G_MMA_H(rb, m + 1);
+            mma_gates(kGatesH, rb, hb + (m + 1) * 2 * 64);
             if (m + 3 < HC) load_h(rb, m + 3); else load_c(rb, 1);
         }
-#undef KWS_G_MMA_H
         // ---- r; r (.) h split -> LDS (the u sigmoid waits for the candidate phase: only the update needs it) ----
 #pragma unroll
         for (int jj = 0; jj < CPW; ++jj) {
@@ -303,19 +266,18 @@ __device__ __forceinline__ void gru_f16x3_generic_body(const GruF16Params& p, co
                 const int j = 2 * jj + k;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float pr = __builtin_fmaf(al[j][0][e], kGLoInv, am[j][0][e]);
+                    const float pr = __builtin_fmaf(al[j][0][e], kLoInv, am[j][0][e]);
                     rh[k][e] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(pr)) * hreg[j][e];
                 }
             }
-            gu32x4 hi, lo;
-            g_split8(rh[0], rh[1], hi, lo);
+            u32x4 hi, lo;
+            split8_scaled(rh[0], rh[1], hi, lo);
             rhb[((CPW * w + jj) * 2 + 0) * 64 + lane] = hi;
             rhb[((CPW * w + jj) * 2 + 1) * 64 + lane] = lo;
         }
         if (PIPE && !FIRST && tid == 0) *next_flag = ahead > t + 1 ? 1 : 0;
         __syncthreads();              // #1: r (.) h visible; hb and xsb fully consumed
-        if (PIPE && !LAST && t > 0 && tid == 0)
-            __hip_atomic_store(p.epi.ready_out + group, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // frames 0..t-1 are out (every wave drained its stores above)
+        if (PIPE && !LAST && t > 0 && tid == 0) pipeline_publish(p.epi.ready_out, group, t);      // frames 0..t-1 are out (every wave drained its stores above)
         // the next frame's input: xsb is free now
         if (FIRST) { mel_commit(); mel_fetch(t + 2); }
         else if (!PIPE) { seam_commit(); seam_fetch(t + 2); }
@@ -325,36 +287,23 @@ __device__ __forceinline__ void gru_f16x3_generic_body(const GruF16Params& p, co
         }
         // ---- recurrent part of the candidate; the u sigmoid rides in the stream's shadow ----
         f32x4 u[TPW];
-#define KWS_G_MMA_C(R_, M2_)                                                                            \
-        {                                                                                                \
-            _Pragma("unroll") for (int k = 0; k < 2; ++k) {                                              \
-                const gu32x4 xh = rhb[((2 * (M2_) + k) * 2 + 0) * 64 + lane], xl = rhb[((2 * (M2_) + k) * 2 + 1) * 64 + lane]; \
-                _Pragma("unroll") for (int j = 0; j < TPW; ++j) {                                        \
-                    am[j][2] = g_mfma(R_.a[(k * TPW + j) * 2 + 0], xh, am[j][2]);                        \
-                    al[j][2] = g_mfma(R_.a[(k * TPW + j) * 2 + 1], xh, al[j][2]);                        \
-                    al[j][2] = g_mfma(R_.a[(k * TPW + j) * 2 + 0], xl, al[j][2]);                        \
-                }                                                                                        \
-            }                                                                                            \
-            __builtin_amdgcn_sched_barrier(0);                                                           \
-        }
         // HC / 2 rows, an even count (HC = 4 or 8); the first pair peeled
-        KWS_G_MMA_C(ra, 0);
+        mma_cand(ra, 0);
         if (2 < HC / 2) load_c(ra, 2); else load_x(ra, 0);                    // ... the next frame's first x rows
 #pragma unroll
         for (int j = 0; j < TPW; ++j)
 #pragma unroll
             for (int e = 0; e < 4; ++e)
-                u[j][e] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(__builtin_fmaf(al[j][1][e], kGLoInv, am[j][1][e])));
-        KWS_G_MMA_C(rb, 1);
+                u[j][e] = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(__builtin_fmaf(al[j][1][e], kLoInv, am[j][1][e])));
+        mma_cand(rb, 1);
         if (3 < HC / 2) load_c(rb, 3); else load_x(rb, 1);
 #pragma nounroll
         for (int m2 = 2; m2 < HC / 2; m2 += 2) {
-            KWS_G_MMA_C(ra, m2);
+            mma_cand(ra, m2);
             if (m2 + 2 < HC / 2) load_c(ra, m2 + 2); else load_x(ra, 0);
-            KWS_G_MMA_C(rb, m2 + 1);
+            mma_cand(rb, m2 + 1);
             if (m2 + 3 < HC / 2) load_c(rb, m2 + 3); else load_x(rb, 1);
         }
-#undef KWS_G_MMA_C
         if (PIPE && !FIRST && have_x) seam_commit();
         // ---- tanh, update, split -> LDS, seam / projection ----
         const unsigned live = t < len_s ? 0xffffffffu : 0u;
@@ -368,33 +317,33 @@ __device__ __forceinline__ void gru_f16x3_generic_body(const GruF16Params& p, co
                 const int j = 2 * jj + k;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
-                    const float pc = __builtin_fmaf(al[j][2][e], kGLoInv, am[j][2][e]);
+                    const float pc = __builtin_fmaf(al[j][2][e], kLoInv, am[j][2][e]);
                     const float c = __builtin_fmaf(__builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(pc)), -2.0f, 1.0f);      // tanh
                     const float hn = __builtin_fmaf(u[j][e], hreg[j][e] - c, c);                                                 // c + u (h - c)
                     hreg[j][e] = bitsel(live, hn, hreg[j][e]);
                     hout[k][e] = bitsel(live, hn, 0.f);
                 }
             }
-            gu32x4 hi, lo;
-            g_split8(hreg[2 * jj], hreg[2 * jj + 1], hi, lo);
+            u32x4 hi, lo;
+            split8_scaled(hreg[2 * jj], hreg[2 * jj + 1], hi, lo);
             hb[((CPW * w + jj) * 2 + 0) * 64 + lane] = hi;
             hb[((CPW * w + jj) * 2 + 1) * 64 + lane] = lo;
             // the layer's OUTPUT row is zero past seq_len (dynamic_rnn), its state is copied through
-            gu32x4 ohi = hi, olo = lo;
+            u32x4 ohi = hi, olo = lo;
 #pragma unroll
             for (int e = 0; e < 4; ++e) { ohi[e] &= live; olo[e] &= live; }
             if (!LAST) {
                 const int frag = (t * HC + CPW * w + jj) * 2;
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(gi32x4, ohi), ho_rsrc, lane16, (frag + 0) * 1024, PIPE ? kSysScope : 0);
-                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(gi32x4, olo), ho_rsrc, lane16, (frag + 1) * 1024, PIPE ? kSysScope : 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, ohi), ho_rsrc, lane16, (frag + 0) * 1024, PIPE ? kSysScope : 0);
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(i32x4, olo), ho_rsrc, lane16, (frag + 1) * 1024, PIPE ? kSysScope : 0);
             } else {
-                fm = g_mfma(wfc[jj][0], ohi, fm);
-                fl = g_mfma(wfc[jj][1], ohi, fl);
-                fl = g_mfma(wfc[jj][0], olo, fl);
+                fm = mfma_f16(wfc[jj][0], ohi, fm);
+                fl = mfma_f16(wfc[jj][1], ohi, fl);
+                fl = mfma_f16(wfc[jj][0], olo, fl);
             }
         }
         if (LAST) {
-            const f32x4 accf = fm + fl * kGLoInv;
+            const f32x4 accf = fm + fl * kLoInv;
             if (g < 2) *reinterpret_cast<f32x4*>(epi.pstage + (w * 16 + s) * 8 + 4 * g) = accf;
         }
         __syncthreads();              // #2: h(t), x(t+1), the partial logits visible
@@ -407,11 +356,7 @@ __device__ __forceinline__ void gru_f16x3_generic_body(const GruF16Params& p, co
             }
         }
     }
-    if (PIPE && !LAST) {                         // the last frame
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(p.epi.ready_out + group, T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (PIPE && !LAST) pipeline_close(p.epi.ready_out, group, T, tid);
     if (bvalid) {
 #pragma unroll
         for (int j = 0; j < TPW; ++j)
@@ -429,15 +374,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))
 template <int TPW>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) gru_stack_f16x3_pipelined(const GruF16StackParams sp) {
     int layer, group;
-    if (sp.xcd_affine) {
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per = 8 / sp.L;
-        layer = xcd % sp.L;
-        group = slot * per + xcd / sp.L;
-        if (group >= sp.G) return;
-    } else {
-        layer = blockIdx.x / sp.G;
-        group = blockIdx.x - layer * sp.G;
-    }
+    if (!pipelined_block(sp.L, sp.G, sp.xcd_affine, layer, group)) return;
     if (layer == 0) gru_f16x3_generic_body<TPW, true, false, true>(sp.layer[0], group);
     else if (layer == sp.L - 1) gru_f16x3_generic_body<TPW, false, true, true>(sp.layer[layer], group);
     else gru_f16x3_generic_body<TPW, false, false, true>(sp.layer[layer], group);

@@ -19,6 +19,7 @@
 
 #include "gru_device.h"
 #include "launch.h"
+#include "pipeline_device.h"
 #include "window_device.h"
 
 namespace kws {
@@ -37,6 +38,14 @@ namespace kws {
 // ------------------------------------------------------------------------------------------------
 constexpr float kResidualScale = 0.7071067811865475f;     // utils/custom_wrapper.py:116
 constexpr float kLayerNormEps = 1e-5f;                    // utils/custom_wrapper.py:126
+
+namespace {
+// One "row" of the weight stream = the fragments of all TPW tiles of a wave for one k-group (half rows, two tiles at TPW = 4, were
+// measured 10-15 % slower)
+template <int TPW> struct RowX { f32x4 a[TPW][3]; f32x4 xb; };      // x-part of r, u, c and the frame's input block
+template <int TPW> struct RowH { f32x4 a[TPW][2]; };                // h-part of r, u
+template <int TPW> struct RowC { f32x4 a[TPW]; };                   // h-part of c
+}  // namespace
 
 template <int TPW, bool FIRST, bool LAST, bool PIPE, bool WRAP = false>
 __device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, const int group,
@@ -90,12 +99,7 @@ __device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, 
     f32x4 bfc4 = splat4(0.f);
     if (LAST) {
         if (w == 0) bfc4 = ld4(p.bfc + 4 * g);
-        if (tid < 16) {
-            const int bb = group * kStreamsPerGroup + tid;
-            int pw = -1;
-            if (bb < p.B && p.prev_word && !(p.reset && p.reset[bb])) pw = p.prev_word[bb];
-            epi.carry[tid] = pw;
-        }
+        epilogue_carry_init(epi, p.prev_word, p.reset, group, p.B, tid);
     }
     const float* xrow = FIRST ? p.x_mel + (size_t)b * (p.t_stride ? p.t_stride : T) * I : nullptr;
     const __amdgpu_buffer_rsrc_t xp_rsrc = __builtin_amdgcn_make_buffer_rsrc(
@@ -103,66 +107,10 @@ __device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, 
         (short)0, 0x7fffffff, 0x00020000);       // this group's [T][NT][64] float4 block of the seam
     const __amdgpu_buffer_rsrc_t ho_rsrc = __builtin_amdgcn_make_buffer_rsrc(
         LAST ? const_cast<float*>(p.wh) : reinterpret_cast<float*>(p.h_out + (size_t)group * T * NT * 64), (short)0, 0x7fffffff, 0x00020000);
-    constexpr int kSysScope = 1 | 16;            // cache-policy bits sc0 | sc1: system scope, past the non-coherent cache levels
     const bool vec_ok = (I & 3) == 0;
     __syncthreads();
 
-    // Weight fragments stream from L2 every frame.  One "row" = the fragments of all TPW tiles for one k-group;
-    // rows ping-pong between two register sets, the next row's loads pinned ahead of the current row's MFMAs
-    // (12 TPW MFMAs = 1.5k cycles at TPW = 4, more than an L2 round trip).  Left to hipcc, every tile's three loads
-    // were waited for right before their MFMAs and the kernel ran latency-bound at half the MFMA rate.
-    auto x_operand = [&](int t, int k4) -> f32x4 {
-        f32x4 xb;
-        if (WRAP && w_staged) {
-            xb = (w_ln ? xln : xstage)[k4 * 64 + lane];     // WRAP: staged at the top of the frame (wrap_frame)
-        } else if (FIRST) {
-            const int k = 16 * k4 + 4 * g;
-            const float* src = xrow + (size_t)t * I + k;
-            if (vec_ok && k + 3 < I) {
-                xb = ld4(src);
-            } else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) xb[e] = (k + e < I) ? src[e] : 0.f;
-            }
-        } else if (PIPE) {
-            xb = xstage[k4 * 64 + lane];          // staged at the top of the frame (below)
-        } else {
-            xb = bload(xp_rsrc, t * NT + k4);
-        }
-        return xb;
-    };
-    // a row covers RT tiles of one k-group: all of the wave's tiles (half rows, RT = 2 at TPW = 4, were measured
-    // 10-15 % slower).  The streaming loops must stay rolled (#pragma nounroll): unrolled, hipcc materialises a
-    // 64-bit address pair per load and the TPW = 4 kernels spill.
-    constexpr int RT = TPW, NP = TPW / RT;
-    struct RowX { f32x4 a[RT][3]; f32x4 xb; };
-    struct RowH { f32x4 a[RT][2]; };
-    struct RowC { f32x4 a[RT]; };
-    auto load_x = [&](RowX& r, int t, int q) {
-        const int qq = q < KCX4 * NP ? q : KCX4 * NP - 1, kk = qq / NP, part = qq - kk * NP;
-#pragma unroll
-        for (int j = 0; j < RT; ++j)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) r.a[j][c] = bload(wx_rsrc, ((TPW * w + part * RT + j) * 3 + c) * KCX4 + kk);
-        r.xb = x_operand(t, kk);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto load_h = [&](RowH& r, int q) {
-        const int qq = q < NT * NP ? q : NT * NP - 1, kk = qq / NP, part = qq - kk * NP;
-#pragma unroll
-        for (int j = 0; j < RT; ++j)
-#pragma unroll
-            for (int c = 0; c < 2; ++c) r.a[j][c] = bload(wh_rsrc, ((TPW * w + part * RT + j) * 3 + c) * NT + kk);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto load_c = [&](RowC& r, int q) {
-        const int qq = q < NT * NP ? q : NT * NP - 1, kk = qq / NP, part = qq - kk * NP;
-#pragma unroll
-        for (int j = 0; j < RT; ++j) r.a[j] = bload(wh_rsrc, ((TPW * w + part * RT + j) * 3 + 2) * NT + kk);
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    // WRAP: frame t's input block to LDS and, under layer norm, the normalised operand beside it (see the header above)
-    auto mel_operand = [&](int t, int k4) -> f32x4 {     // the first layer's x operand as x_operand reads it (zero past I)
+    auto mel_operand = [&](int t, int k4) -> f32x4 {     // the first layer's x operand (zero past I)
         f32x4 xb;
         const int k = 16 * k4 + 4 * g;
         const float* src = xrow + (size_t)t * I + k;
@@ -174,6 +122,42 @@ __device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, 
         }
         return xb;
     };
+    auto x_operand = [&](int t, int k4) -> f32x4 {
+        if (WRAP && w_staged) return (w_ln ? xln : xstage)[k4 * 64 + lane];     // WRAP: staged at the top of the frame (wrap_frame)
+        if (FIRST) return mel_operand(t, k4);
+        if (PIPE) return xstage[k4 * 64 + lane];       // staged at the top of the frame (below)
+        return bload(xp_rsrc, t * NT + k4);
+    };
+    // Weight fragments stream from L2 every frame, row by row (RowX / RowH / RowC above); rows ping-pong between two register
+    // sets, the next row's loads pinned ahead of the current row's MFMAs (12 TPW MFMAs = 1.5k cycles at TPW = 4, more than an
+    // L2 round trip).  Left to hipcc, every tile's three loads were waited for right before their MFMAs and the kernel ran
+    // latency-bound at half the MFMA rate.
+    // The streaming loops must stay rolled (#pragma nounroll): unrolled, hipcc materialises a 64-bit address pair per load and
+    // the TPW = 4 kernels spill.  A load past a phase's last row fetches that last row again.
+    auto load_x = [&](RowX<TPW>& r, int t, int q) {
+        const int kk = q < KCX4 ? q : KCX4 - 1;
+#pragma unroll
+        for (int j = 0; j < TPW; ++j)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) r.a[j][c] = bload(wx_rsrc, ((TPW * w + j) * 3 + c) * KCX4 + kk);
+        r.xb = x_operand(t, kk);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto load_h = [&](RowH<TPW>& r, int q) {
+        const int kk = q < NT ? q : NT - 1;
+#pragma unroll
+        for (int j = 0; j < TPW; ++j)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) r.a[j][c] = bload(wh_rsrc, ((TPW * w + j) * 3 + c) * NT + kk);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto load_c = [&](RowC<TPW>& r, int q) {
+        const int kk = q < NT ? q : NT - 1;
+#pragma unroll
+        for (int j = 0; j < TPW; ++j) r.a[j] = bload(wh_rsrc, ((TPW * w + j) * 3 + 2) * NT + kk);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    // WRAP: frame t's input block to LDS and, under layer norm, the normalised operand beside it (see the header above)
     auto wrap_frame = [&](int t) {
         f32x4* const raw = FIRST ? xln : xstage;
         if (FIRST) {
@@ -248,19 +232,35 @@ __device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, 
             const int n = TPW * w + j;
             acc_r[j] = biasl[(0 * NT + n) * 4 + g]; acc_u[j] = biasl[(1 * NT + n) * 4 + g]; acc_c[j] = biasl[(2 * NT + n) * 4 + g];
         }
+        // a row's MFMAs.  Lambdas in the frame loop, the scheduling barrier behind each call: as function templates over the
+        // accumulator arrays the hidden-256 kernels were allocated 44 more VGPRs and 32 more AGPRs (profiles/gru_shared_phases_isa.txt)
+        auto mma_x = [&](const RowX<TPW>& r) {
+#pragma unroll
+            for (int j = 0; j < TPW; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    acc_r[j] = mfma4(r.a[j][0][e], r.xb[e], acc_r[j]);
+                    acc_u[j] = mfma4(r.a[j][1][e], r.xb[e], acc_u[j]);
+                    acc_c[j] = mfma4(r.a[j][2][e], r.xb[e], acc_c[j]);
+                }
+        };
+        auto mma_h = [&](const RowH<TPW>& r, const f32x4 hb) {
+#pragma unroll
+            for (int j = 0; j < TPW; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    acc_r[j] = mfma4(r.a[j][0][e], hb[e], acc_r[j]);
+                    acc_u[j] = mfma4(r.a[j][1][e], hb[e], acc_u[j]);
+                }
+        };
+        auto mma_c = [&](const RowC<TPW>& r, const f32x4 rb) {
+#pragma unroll
+            for (int j = 0; j < TPW; ++j)
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc_c[j] = mfma4(r.a[j][e], rb[e], acc_c[j]);
+        };
         if (PIPE && !FIRST) {
-            // layer-pipelined launch: frame t of the layer below must have landed (its workgroup runs concurrently
-            // on another CU).  Every wave polls for itself; the bound turns a protocol bug into a wrong answer plus
-            // an error flag instead of a hung GPU.
-            // Seams and counters live in FINE-GRAINED device memory (uncached in L2, coherent across XCDs), so no
-            // cache-wide acquire is needed -- an agent-scope acquire invalidates the L2 and with it the weight
-            // stream of every workgroup on the XCD, once per frame (measured: slower than the sequential launches).
-            int spins = 0;
-            while (__hip_atomic_load(p.ready_in + group, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) <= t) {
-                __builtin_amdgcn_s_sleep(2);
-                if (++spins > (1 << 24)) { if (lane == 0) *reinterpret_cast<volatile int*>(p.pipe_error) = 1; break; }
-            }
-            asm volatile("" ::: "memory");
+            pipeline_wait(p.ready_in, p.pipe_error, group, t, lane);       // frame t of the layer below has landed
             // The frame's input block was written by a workgroup on another CU / XCD while this kernel runs:
             // system-scope (sc0 sc1) loads go past the non-coherent cache levels, dword by dword, at memory
             // latency -- so the whole block is fetched at once (all loads in flight) and parked in LDS.
@@ -277,50 +277,31 @@ __device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, 
         if constexpr (WRAP) {
             if (w_staged) wrap_frame(t);
         }
-        // x-part (gates and candidate): rows q = k4 * NP + part, ping-pong, unrolled by two (NP == 2 keeps the parity
-        // of q equal to the part, NP == 1 has a single part)
+        // x-part (gates and candidate): one row per k-group, ping-pong, unrolled by two
         {
-#define KWS_MMA_X(P_)                                                                                 \
-            _Pragma("unroll") for (int j = 0; j < RT; ++j)                                             \
-                _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                        \
-                    acc_r[P_ * RT + j] = mfma4(rr.a[j][0][e], rr.xb[e], acc_r[P_ * RT + j]);           \
-                    acc_u[P_ * RT + j] = mfma4(rr.a[j][1][e], rr.xb[e], acc_u[P_ * RT + j]);           \
-                    acc_c[P_ * RT + j] = mfma4(rr.a[j][2][e], rr.xb[e], acc_c[P_ * RT + j]);           \
-                }
-            RowX ra, rb;
-            const int NQ = KCX4 * NP;
+            RowX<TPW> ra, rb;
             load_x(ra, t, 0);
 #pragma nounroll
-            for (int q = 0; q < NQ; q += 2) {
+            for (int q = 0; q < KCX4; q += 2) {
                 load_x(rb, t, q + 1);
-                { const RowX& rr = ra; KWS_MMA_X(0); __builtin_amdgcn_sched_barrier(0); }
-                if (q + 1 < NQ) {
+                mma_x(ra); __builtin_amdgcn_sched_barrier(0);
+                if (q + 1 < KCX4) {
                     load_x(ra, t, q + 2);
-                    { const RowX& rr = rb; if (NP == 2) { KWS_MMA_X((NP - 1)); } else { KWS_MMA_X(0); } __builtin_amdgcn_sched_barrier(0); }
+                    mma_x(rb); __builtin_amdgcn_sched_barrier(0);
                 }
             }
-#undef KWS_MMA_X
         }
-        // gates, h-part
+        // gates, h-part (NT rows: an even count)
         {
-#define KWS_MMA_H(P_)                                                                                 \
-            _Pragma("unroll") for (int j = 0; j < RT; ++j)                                             \
-                _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                        \
-                    acc_r[P_ * RT + j] = mfma4(rr.a[j][0][e], hb[e], acc_r[P_ * RT + j]);              \
-                    acc_u[P_ * RT + j] = mfma4(rr.a[j][1][e], hb[e], acc_u[P_ * RT + j]);              \
-                }
-            RowH ra, rb;
-            constexpr int NQ = NT * NP;                   // even
+            RowH<TPW> ra, rb;
             load_h(ra, 0);
 #pragma nounroll
-            for (int q = 0; q < NQ; q += 2) {
+            for (int q = 0; q < NT; q += 2) {
                 load_h(rb, q + 1);
-                { const RowH& rr = ra; const f32x4 hb = hbuf[(q / NP) * 64 + lane]; KWS_MMA_H(0); __builtin_amdgcn_sched_barrier(0); }
+                mma_h(ra, hbuf[q * 64 + lane]); __builtin_amdgcn_sched_barrier(0);
                 load_h(ra, q + 2);
-                { const RowH& rr = rb; const f32x4 hb = hbuf[((q + 1) / NP) * 64 + lane];
-                  if (NP == 2) { KWS_MMA_H((NP - 1)); } else { KWS_MMA_H(0); } __builtin_amdgcn_sched_barrier(0); }
+                mma_h(rb, hbuf[(q + 1) * 64 + lane]); __builtin_amdgcn_sched_barrier(0);
             }
-#undef KWS_MMA_H
         }
         f32x4 u[TPW];
 #pragma unroll
@@ -333,27 +314,17 @@ __device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, 
             }
             rhbuf[(TPW * w + j) * 64 + lane] = rh;
         }
-        RowC ca, cb;
+        RowC<TPW> ca, cb;
         if (PIPE && !LAST) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // last frame's rows (half a frame old): written through
         load_c(ca, 0);                 // does not depend on the exchange: issued ahead of the barrier
         __syncthreads();
-        if (PIPE && !LAST && t > 0 && tid == 0)
-            __hip_atomic_store(p.ready_out + group, t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        {
-#define KWS_MMA_C(P_)                                                                                 \
-            _Pragma("unroll") for (int j = 0; j < RT; ++j)                                             \
-                _Pragma("unroll") for (int e = 0; e < 4; ++e)                                          \
-                    acc_c[P_ * RT + j] = mfma4(rr.a[j][e], rb[e], acc_c[P_ * RT + j]);
-            constexpr int NQ = NT * NP;
+        if (PIPE && !LAST && t > 0 && tid == 0) pipeline_publish(p.ready_out, group, t);      // frames 0..t-1: drained above
 #pragma nounroll
-            for (int q = 0; q < NQ; q += 2) {
-                load_c(cb, q + 1);
-                { const RowC& rr = ca; const f32x4 rb = rhbuf[(q / NP) * 64 + lane]; KWS_MMA_C(0); __builtin_amdgcn_sched_barrier(0); }
-                load_c(ca, q + 2);
-                { const RowC& rr = cb; const f32x4 rb = rhbuf[((q + 1) / NP) * 64 + lane];
-                  if (NP == 2) { KWS_MMA_C((NP - 1)); } else { KWS_MMA_C(0); } __builtin_amdgcn_sched_barrier(0); }
-            }
-#undef KWS_MMA_C
+        for (int q = 0; q < NT; q += 2) {
+            load_c(cb, q + 1);
+            mma_c(ca, rhbuf[q * 64 + lane]); __builtin_amdgcn_sched_barrier(0);
+            load_c(ca, q + 2);
+            mma_c(cb, rhbuf[(q + 1) * 64 + lane]); __builtin_amdgcn_sched_barrier(0);
         }
         const unsigned live = t < len_s ? 0xffffffffu : 0u;
         f32x4 accf = bfc4;
@@ -407,11 +378,7 @@ __device__ __forceinline__ void gru_layer_generic_body(const GruLayerParams& p, 
             }
         }
     }
-    if (PIPE && !LAST) {                         // the last frame
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) __hip_atomic_store(p.ready_out + group, T, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    if (PIPE && !LAST) pipeline_close(p.ready_out, group, T, tid);
     if (bvalid) {
 #pragma unroll
         for (int j = 0; j < TPW; ++j)
@@ -438,15 +405,7 @@ __global__ void __launch_bounds__(256) gru_layer_generic(const GruLayerParams p)
 template <int TPW>
 __global__ void __launch_bounds__(256) gru_stack_generic_pipelined(const GruStackParams sp) {
     int layer, group;
-    if (sp.xcd_affine) {
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per = 8 / sp.L;
-        layer = xcd % sp.L;
-        group = slot * per + xcd / sp.L;
-        if (group >= sp.G) return;              // grid padded to a multiple of 8; nobody waits for a padding block
-    } else {
-        layer = blockIdx.x / sp.G;
-        group = blockIdx.x - layer * sp.G;
-    }
+    if (!pipelined_block(sp.L, sp.G, sp.xcd_affine, layer, group)) return;
     if (layer == 0) gru_layer_generic_body<TPW, true, false, true>(sp.layer[0], group);
     else if (layer == sp.L - 1) gru_layer_generic_body<TPW, false, true, true>(sp.layer[layer], group);
     else gru_layer_generic_body<TPW, false, false, true>(sp.layer[layer], group);
@@ -459,16 +418,8 @@ __global__ void __launch_bounds__(256) gru_layer_generic_wrapped(const GruLayerP
 }
 template <int TPW>
 __global__ void __launch_bounds__(256) gru_stack_generic_pipelined_wrapped(const GruStackParams sp, const GruWrapParams wp) {
-    int layer, group;                           // block -> (layer, group) as gru_stack_generic_pipelined
-    if (sp.xcd_affine) {
-        const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per = 8 / sp.L;
-        layer = xcd % sp.L;
-        group = slot * per + xcd / sp.L;
-        if (group >= sp.G) return;
-    } else {
-        layer = blockIdx.x / sp.G;
-        group = blockIdx.x - layer * sp.G;
-    }
+    int layer, group;
+    if (!pipelined_block(sp.L, sp.G, sp.xcd_affine, layer, group)) return;
     if (layer == 0) gru_layer_generic_body<TPW, true, false, true, true>(sp.layer[0], group, wp.layer[0]);
     else if (layer == sp.L - 1) gru_layer_generic_body<TPW, false, true, true, true>(sp.layer[layer], group, wp.layer[layer]);
     else gru_layer_generic_body<TPW, false, false, true, true>(sp.layer[layer], group, wp.layer[layer]);

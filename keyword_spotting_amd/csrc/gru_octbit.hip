@@ -461,33 +461,13 @@ __global__ void __launch_bounds__(512) octbit_fc_kernel(const OctbitFcParams p) 
             float of = (float)iacc[f][si][c];
             if (sg) of = sub_rn(of, p.b127[c]);
             lg[c] = c < C ? add_rn(mul_rn(of, sc), p.bfc[c]) : 0.f;
-            if (p.use_relu) {
-                lg[c] = fmaxf(lg[c], 0.f);
-                if (p.value_clip > 0.f) lg[c] = fminf(lg[c], 20.f);
-            }
         }
-        float m = lg[0];
-#pragma unroll
-        for (int c = 1; c < kMaxClasses; ++c) m = (c < C) ? fmaxf(m, lg[c]) : m;
-        float sum = 0.f;
-#pragma unroll
-        for (int c = 0; c < kMaxClasses; ++c) { pr[c] = (c < C) ? __expf(lg[c] - m) : 0.f; sum += pr[c]; }
-        const float inv = __builtin_amdgcn_rcpf(sum);
-        int word = -1;
-        float best = -1.f;
-#pragma unroll
-        for (int c = 0; c < kMaxClasses; ++c) {
-            pr[c] *= inv;
-            if (c >= 1 && c < C - 1 && pr[c] > best) { best = pr[c]; word = c - 1; }   // utils/prediction.py:67,74-75
-        }
-        if (!(best > p.decode_thres)) word = -1;
+        const int word = head_row(lg, pr, C, p.use_relu, p.value_clip, p.decode_thres);
         words[f][si] = word;
         if (f >= 1 && bi < p.B) {
             const size_t row = (size_t)bi * T + t;
-            for (int c = 0; c < C; ++c) {
-                if (p.logits) p.logits[row * C + c] = lg[c];
-                if (p.softmax) p.softmax[row * C + c] = pr[c];
-            }
+            if (p.logits) store_row(p.logits + row * C, lg, C);
+            if (p.softmax) store_row(p.softmax + row * C, pr, C);
         }
     }
     __syncthreads();

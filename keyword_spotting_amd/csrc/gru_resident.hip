@@ -223,9 +223,7 @@ __device__ __forceinline__ void gru_layer_resident_body(const GruLayerParams& p)
             hbuf[n * 64 + lane] = hreg[j];
         }
         if (LAST) {
-            const int bb = group * kStreamsPerGroup + 4 * w + (lane >> 4);
-            carry = -1;
-            if (bb < p.B && p.prev_word && !(p.reset && p.reset[bb])) carry = p.prev_word[bb];
+            carry = carried_word(p.prev_word, p.reset, group * kStreamsPerGroup + 4 * w + (lane >> 4), p.B);
         }
         if constexpr (FIRST) {
             const int xl_b = min(group * kStreamsPerGroup + 4 * w + (xl_active ? xl_row : 0), p.B - 1);
