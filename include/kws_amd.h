@@ -688,6 +688,8 @@ int kws_step_bank_window(kws_handle model, kws_bank_handle bank, const int32_t* 
  *               dynamic_rnn(sequence_length): at t >= seq_len[b] the state is copied and the output is 0
  *   dropout     DropoutWrapper(output_keep_prob): the layer's output is y = h' o mask / keep_prob, the carried state the undropped h'.
  *               drop: uint8 [L,B,T,H] on the device (0 = dropped), 4-byte aligned (the kernels read four units' masks at a time), or NULL for none.  Input dropout is the caller's (on x, no gradient).
+ *               On a kws_train_create_wrapped handle with variational_recurrent = 1, drop is uint8 [L,B,H]: one mask per stream and layer,
+ *               held for all frames (DropoutWrapper(variational_recurrent=True), models/rnn_ctc.py:191-195) -- the same arithmetic.
  *   loss        logits = y_top . Wfc + bfc; loss = sum_b ctc_b / B with kws_ctc_loss's conventions (above): the blank is the last class,
  *               S_max <= 31, seq_len / labels / label_len are HOST arrays range-checked before any launch, seq_len[b] == 0 is an empty slot
  *               that adds 0 and still counts in B.  An utterance without a valid path has loss +inf and contributes a gradient of exactly 0;
@@ -703,11 +705,32 @@ int kws_step_bank_window(kws_handle model, kws_bank_handle bank, const int32_t* 
  *   dWc += [x, r o h]^T dc^;  dWg += [x, h]^T [dr^ | du^];  the biases are the column sums.  Frames t >= seq_len[b] pass dh through.
  * Nothing is summed with float atomics: the same call twice gives the same bits.
  *
+ * The cell wrappers (kws_train_create_wrapped; kws_cell_wrappers above): the graph of a layer is Residual(Dropout(LayerNormalizer(GRUCell))),
+ * the residual on layers >= 1 only.  M = B T rows, in_l the input of layer l (x, or out_{l-1}) of width I_l, k = 0.7071067811865475;
+ * rows t >= seq_len[b] are written as zeros and never read (the padding of x may be NaN), and add exactly 0 to every sum.
+ *   layer norm  m = mean(in_l), v = mean((in_l - m)^2), rstd = 1 / sqrt(v + 1e-5), xn = (in_l - m) rstd, x^ = xn ibeta_l + igamma_l: the
+ *               cell's x-part reads x^ (ibeta the scalar scale, igamma the per-feature shift, as in kws_create_wrapped)
+ *   residual    out_l = k (y_l + in_l) for l >= 1, y_l the layer's output after dropout; the state stays the cell's; the dense layer reads
+ *               out_{L-1}
+ *   backward    given dout_l: with the residual dy_l = k dout_l enters the frame loop.  g = [dr^ | du^ | dc^] . (Wg_x | Wc_x)^T is dx^_l
+ *               (with the layer norm on layer 0 too); dn = g ibeta, a = mean(dn), c = mean(dn o xn):
+ *               d in_l = rstd (dn - a - xn c), d ibeta_l = sum over rows and features of g o xn, d igamma_l = sum over rows of g; without
+ *               the layer norm d in_l = g.  With the residual k dout_l is added to d in_l; the sum is dout_{l-1}.  The x rows of dWg and
+ *               dWc are taken with x^ in the place of in_l.
+ *   parameters  ibeta and igamma are trained like every other tensor: they lie behind the canonical blob as in kws_weights_nbytes_wrapped
+ *               (weights, gradient and both moments), enter the global norm and the clip, and take the same update.
+ *
  * kws_train_create   refuses, before the device is probed, with KWS_ERR_UNSUPPORTED and a message that names the field: model.use_relu /
  *                    model.value_clip (the gradient of TensorFlow's relu and clip at their ties is not pinned), wrappers.use_layer_norm /
- *                    wrappers.use_residual, variational_recurrent, any model.precision but KWS_FP32, keep_prob outside (0, 1]; with
+ *                    wrappers.use_residual, variational_recurrent (all three: kws_train_create_wrapped takes them, and the message says
+ *                    so), any model.precision but KWS_FP32, keep_prob outside (0, 1]; with
  *                    KWS_ERR_INVALID_ARGUMENT an unknown optimizer and the ranges of kws_config (hidden 64 / 128 / 256, 1..8 layers,
  *                    n_mel 1..1024, 3..8 classes).  The parameters start as zeros: kws_train_set_weights comes first.
+ * kws_train_create_wrapped   the same struct with wrappers.use_layer_norm, wrappers.use_residual and variational_recurrent each 0 or 1, in any
+ *                    combination (another value: KWS_ERR_INVALID_ARGUMENT, naming the field); every other refusal of kws_train_create holds.
+ *                    With all three 0 it is kws_train_create: the same launches, the same bits.  Every kws_train_* call below takes either
+ *                    kind of handle; the blobs of a wrapped handle have kws_weights_nbytes_wrapped(&cfg.model, &cfg.wrappers) bytes.
+ *                    kws_train_check_wrapped is kws_train_check for such a handle.
  * kws_train_check    the refusals of kws_train_create and of a kws_train_grad / _step call on a handle of this config, decided from
  *                    host memory alone: KWS_OK where the call would go on to the device.  x and loss are only compared with NULL and
  *                    checked for alignment.
@@ -732,8 +755,8 @@ int kws_step_bank_window(kws_handle model, kws_bank_handle bank, const int32_t* 
 enum { KWS_OPT_ADAM = 0, KWS_OPT_NESTEROV = 1 };
 typedef struct kws_train_config {
     kws_config model;
-    kws_cell_wrappers wrappers;       /* both must be 0 */
-    int32_t variational_recurrent;    /* must be 0 */
+    kws_cell_wrappers wrappers;       /* kws_train_create: both must be 0; kws_train_create_wrapped: each 0 or 1 */
+    int32_t variational_recurrent;    /* kws_train_create: must be 0; kws_train_create_wrapped: 1 = one mask per stream, drop [L,B,H] */
     int32_t optimizer;                /* KWS_OPT_ADAM / KWS_OPT_NESTEROV */
     float max_grad_norm;              /* <= 0: no clipping (config/rnn_config.py:55: -1) */
     float keep_prob;                  /* output keep probability the masks were drawn with, (0, 1] */
@@ -743,6 +766,9 @@ size_t kws_sizeof_train_config(void);
 int kws_train_create(const kws_train_config* cfg, kws_train_handle* out);
 int kws_train_check(const kws_train_config* cfg, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
                     int T, int S_max, const float* loss);
+int kws_train_create_wrapped(const kws_train_config* cfg, kws_train_handle* out);
+int kws_train_check_wrapped(const kws_train_config* cfg, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
+                            int B, int T, int S_max, const float* loss);
 int kws_train_destroy(kws_train_handle h);   /* always KWS_OK */
 int kws_train_set_weights(kws_train_handle h, const void* blob /*host*/, size_t nbytes, void* stream);
 int kws_train_get_weights(kws_train_handle h, void* blob /*host*/, size_t nbytes, void* stream);

@@ -173,6 +173,8 @@ _SIGNATURES = {
     "kws_sizeof_train_config": (ctypes.c_size_t, []),
     "kws_train_create": (_i, [ctypes.POINTER(KwsTrainConfig), ctypes.POINTER(_vp)]),
     "kws_train_check": (_i, [ctypes.POINTER(KwsTrainConfig), _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "kws_train_create_wrapped": (_i, [ctypes.POINTER(KwsTrainConfig), ctypes.POINTER(_vp)]),
+    "kws_train_check_wrapped": (_i, [ctypes.POINTER(KwsTrainConfig), _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "kws_train_destroy": (_i, [_vp]),
     "kws_train_set_weights": (_i, [_vp, _vp, ctypes.c_size_t, _vp]),
     "kws_train_get_weights": (_i, [_vp, _vp, ctypes.c_size_t, _vp]),

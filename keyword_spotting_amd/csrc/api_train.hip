@@ -1,5 +1,6 @@
 // C ABI of libkws_amd.so (include/kws_amd.h): the train handle -- taped forward, back-propagation through time, the CTC loss through
-// ctc_loss_kernel, global-norm clipping and Adam / Nesterov on the canonical blob (gru_train.hip, train_kernels.hip).
+// ctc_loss_kernel, global-norm clipping and Adam / Nesterov on the canonical blob (gru_train.hip, train_kernels.hip), with the cell
+// wrappers of kws_train_create_wrapped around the two frame loops (train_wrap_kernels.hip).
 #include <new>
 
 #include "api_internal.h"
@@ -9,6 +10,8 @@ using namespace kws_host;
 struct kws_train {
     kws_train_config cfg;
     BlobLayout bl;
+    WrapLayout wl;                   // the layer norm's ibeta / igamma behind the canonical blob (kws_train_create_wrapped)
+    bool ln = false, res = false, var = false;      // wrappers.use_layer_norm, wrappers.use_residual, variational_recurrent
     size_t P = 0;                    // floats of the blob
     // one allocation fixed at create: theta | m | v | grad [4 P], the packed copies of every layer (wx, wh, wht, b3), then the
     // reduction's per-workgroup sums of squares (doubles)
@@ -19,7 +22,9 @@ struct kws_train {
     size_t state_bytes = 0;
     int nred = 0;
     // one allocation that only grows, carved for the shape of the call (carve): lengths and labels, the row mask, the job table of the
-    // weight-gradient launch, the tape, the gradients of the activations, the row chunks' partial weight gradients
+    // weight-gradient launch, the tape, the gradients of the activations, the row chunks' partial weight gradients.  With the layer norm
+    // a layer also keeps xhat and xn [M, I_l] and rstd [M] from the forward, g = dxhat [M, I_l] and gs [M] (the rows' terms of d ibeta)
+    // from the backward; with the residual a layer >= 1 keeps out [M, H] = 0.7071 (y + its input)
     char* arena = nullptr;
     size_t arena_bytes = 0;
     struct Carved {
@@ -28,7 +33,7 @@ struct kws_train {
         uint8_t* live = nullptr;
         kws::TrainWgradJob* jobs = nullptr;
         float *xg = nullptr, *dy[2] = {nullptr, nullptr}, *logits = nullptr, *gl = nullptr, *partial = nullptr;
-        struct Layer { float *ar, *au, *ac, *hp, *rh, *y, *dhat; } layer[8] = {};          // ar, au, ac: the pre-activations of r, u, c
+        struct Layer { float *ar, *au, *ac, *hp, *rh, *y, *dhat, *xhat, *xn, *rstd, *g, *gs, *out; } layer[8] = {};   // ar, au, ac: the pre-activations of r, u, c
         int njobs = 0, units = 0, chunk_rows = 0, chunks = 0;
     } cv;
     std::vector<kws::TrainWgradJob> jobs_host;
@@ -46,6 +51,11 @@ namespace {
 constexpr size_t kAlign = 256;
 size_t aligned(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
 constexpr int kWgradChunkUnit = 256, kWgradMaxChunks = 64;
+constexpr float kResidualScale = 0.7071067811865475f;      // utils/custom_wrapper.py:116
+
+bool residual_on(const kws_train* h, int l) { return h->res && l >= 1; }
+// what layer l hands to the layer above and to the dense layer
+const float* layer_output(const kws_train* h, const kws_train::Carved& cv, int l) { return residual_on(h, l) ? cv.layer[l].out : cv.layer[l].y; }
 
 int train_enter(kws_train* h, hipStream_t st) {
     if (h->last_stream_valid && h->last_stream != st) KWS_HIP(hipStreamWaitEvent(st, h->last_done, 0));
@@ -80,7 +90,7 @@ size_t carve(const kws_train* h, int B, int T, int S_max, char* base, kws_train:
     auto take = [&](size_t bytes) { char* p = base ? base + at : nullptr; at += aligned(bytes); return p; };
     kws_train::Carved o;
     o.B = B; o.T = T; o.S_max = S_max;
-    o.njobs = 6 * c.num_layers + 2;
+    o.njobs = (h->ln ? 8 : 6) * c.num_layers + 2;
     o.chunk_rows = wgrad_chunk_rows(M);
     o.chunks = (int)((M + o.chunk_rows - 1) / o.chunk_rows);
     o.ints = reinterpret_cast<int32_t*>(take((size_t)B * (2 + S_max) * sizeof(int32_t)));
@@ -94,13 +104,18 @@ size_t carve(const kws_train* h, int B, int T, int S_max, char* base, kws_train:
         kws_train::Carved::Layer& y = o.layer[l];
         y.ar = floats(M * H); y.au = floats(M * H); y.ac = floats(M * H); y.hp = floats(M * H); y.rh = floats(M * H); y.y = floats(M * H);
         y.dhat = floats(M * 3 * H);
+        const size_t in = (size_t)h->bl.layer[l].in;
+        if (h->ln) { y.xhat = floats(M * in); y.xn = floats(M * in); y.rstd = floats(M); y.g = floats(M * in); y.gs = floats(M); }
+        if (residual_on(h, l)) y.out = floats(M * H);
     }
     o.partial = floats((size_t)o.chunks * h->P);
     if (cv) *cv = o;
     return at;
 }
 
-// the products of the weight-gradient launch for the carved shape: per layer (Wg | Wc) x (input rows, state rows, bias), then the dense layer
+// the products of the weight-gradient launch for the carved shape: per layer (Wg | Wc) x (input rows, state rows, bias), then the dense
+// layer; with the layer norm the input rows are the taped xhat (on layer 0 too), and each layer adds the column sums of g (d igamma)
+// and of gs (d ibeta) at wrap_layout's offsets
 void build_jobs(kws_train* h) {
     const kws_config& c = h->cfg.model;
     const int H = c.hidden, C = c.num_classes;
@@ -116,8 +131,8 @@ void build_jobs(kws_train* h) {
     for (int l = 0; l < c.num_layers; ++l) {
         const BlobLayout::Layer& b = h->bl.layer[l];
         const kws_train::Carved::Layer& y = cv.layer[l];
-        const int in = b.in, src = l == 0 ? kws::kWgradInput : kws::kWgradRows;
-        const float* below = l == 0 ? nullptr : cv.layer[l - 1].y;
+        const int in = b.in, src = l == 0 && !h->ln ? kws::kWgradInput : kws::kWgradRows;
+        const float* below = h->ln ? y.xhat : l == 0 ? nullptr : layer_output(h, cv, l - 1);
         add(src, below, in, in, y.dhat, 3 * H, 2 * H, b.wg, 2 * H);
         add(kws::kWgradRows, y.hp, H, H, y.dhat, 3 * H, 2 * H, b.wg + (size_t)in * 2 * H, 2 * H);
         add(kws::kWgradOnes, nullptr, 0, 1, y.dhat, 3 * H, 2 * H, b.bg, 2 * H);
@@ -125,8 +140,13 @@ void build_jobs(kws_train* h) {
         add(kws::kWgradRows, y.rh, H, H, y.dhat + 2 * H, 3 * H, H, b.wc + (size_t)in * H, H);
         add(kws::kWgradOnes, nullptr, 0, 1, y.dhat + 2 * H, 3 * H, H, b.bc, H);
     }
-    add(kws::kWgradRows, cv.layer[c.num_layers - 1].y, H, H, cv.gl, C, C, h->bl.wfc, C);
+    add(kws::kWgradRows, layer_output(h, cv, c.num_layers - 1), H, H, cv.gl, C, C, h->bl.wfc, C);
     add(kws::kWgradOnes, nullptr, 0, 1, cv.gl, C, C, h->bl.bfc, C);
+    for (int l = 0; h->ln && l < c.num_layers; ++l) {
+        const int in = h->bl.layer[l].in;
+        add(kws::kWgradOnes, nullptr, 0, 1, cv.layer[l].gs, 1, 1, h->wl.ibeta[l], 1);
+        add(kws::kWgradOnes, nullptr, 0, 1, cv.layer[l].g, in, in, h->wl.igamma[l], in);
+    }
     cv.units = unit;
 }
 
@@ -192,23 +212,36 @@ int grad_impl(kws_train* h, const float* x, const int32_t* seq_len, const int32_
     const int32_t *d_seq = cv.ints, *d_len = cv.ints + B, *d_lab = cv.ints + 2 * (size_t)B;
     h->launches = 0;
     KWS_LAUNCH(h, kws::launch_train_rowmask(d_seq, B, T, cv.live, st), "launch train_rowmask");
+    // the masks: one per frame [L, B, T, H], or one per stream held for all frames [L, B, H] (variational_recurrent)
+    const size_t drop_layer = (h->var ? (size_t)B : (size_t)M) * H;
+    const int drop_bs = h->var ? 1 : T, drop_ts = h->var ? 0 : 1;
     for (int l = 0; l < L; ++l) {
         const kws::TrainPackLayer& pk = h->pack.layer[l];
         const kws_train::Carved::Layer& y = cv.layer[l];
+        const float* in = l == 0 ? x : layer_output(h, cv, l - 1);
+        if (h->ln) {
+            kws::TrainLnForward n = {};
+            n.in = in; n.live = cv.live; n.ibeta = h->theta + h->wl.ibeta[l]; n.igamma = h->theta + h->wl.igamma[l];
+            n.xhat = y.xhat; n.xn = y.xn; n.rstd = y.rstd; n.M = M; n.I = pk.in;
+            KWS_LAUNCH(h, kws::launch_train_ln_forward(n, st), "launch train_ln_forward");
+        }
         kws::TrainRowsGemm g = {};
-        g.a = l == 0 ? x : cv.layer[l - 1].y; g.lda = pk.in; g.live = cv.live;
+        g.a = h->ln ? y.xhat : in; g.lda = pk.in; g.live = cv.live;
         g.w = pk.wx; g.swk = 3 * H; g.swn = 1; g.bias = pk.b3;
         g.out = cv.xg; g.ldo = 3 * H; g.M = M; g.K = pk.in; g.N = 3 * H;
         KWS_LAUNCH(h, kws::launch_train_rows_gemm(g, st), "launch train_rows_gemm (x-part)");
         kws::TrainForwardParams f = {};
-        f.xg = cv.xg; f.wh = pk.wh; f.seq_len = d_seq; f.drop = drop ? drop + (size_t)l * M * H : nullptr;
+        f.xg = cv.xg; f.wh = pk.wh; f.seq_len = d_seq; f.drop = drop ? drop + (size_t)l * drop_layer : nullptr;
+        f.drop_bs = drop_bs; f.drop_ts = drop_ts;
         f.ar = y.ar; f.au = y.au; f.ac = y.ac; f.hp = y.hp; f.rh = y.rh; f.y = y.y; f.keep_prob = h->cfg.keep_prob; f.B = B; f.T = T;
         KWS_LAUNCH(h, kws::launch_gru_train_forward(f, H, st), "launch gru_train_forward");
+        if (residual_on(h, l))          // both operands are zero rows at t >= seq_len: so is out
+            KWS_LAUNCH(h, kws::launch_train_residual(y.y, in, kResidualScale, y.out, (size_t)M * H, st), "launch train_residual (forward)");
     }
     const float* wfc = h->theta + h->bl.wfc;
     {
         kws::TrainRowsGemm g = {};
-        g.a = cv.layer[L - 1].y; g.lda = H; g.w = wfc; g.swk = C; g.swn = 1; g.bias = h->theta + h->bl.bfc;
+        g.a = layer_output(h, cv, L - 1); g.lda = H; g.w = wfc; g.swk = C; g.swn = 1; g.bias = h->theta + h->bl.bfc;
         g.out = cv.logits; g.ldo = C; g.M = M; g.K = H; g.N = C;
         KWS_LAUNCH(h, kws::launch_train_rows_gemm(g, st), "launch train_rows_gemm (logits)");
     }
@@ -224,17 +257,30 @@ int grad_impl(kws_train* h, const float* x, const int32_t* seq_len, const int32_
     for (int l = L - 1; l >= 0; --l) {
         const kws::TrainPackLayer& pk = h->pack.layer[l];
         const kws_train::Carved::Layer& y = cv.layer[l];
+        // cv.dy[cur] holds dout of this layer.  With the residual it becomes 0.7071 dout in place: the dy of the frame loop, and the
+        // share of d in that is added behind the x-part's
+        if (residual_on(h, l))
+            KWS_LAUNCH(h, kws::launch_train_residual(cv.dy[cur], nullptr, kResidualScale, cv.dy[cur], (size_t)M * H, st), "launch train_residual (dout)");
         kws::TrainBackwardParams b = {};
-        b.dy = cv.dy[cur]; b.wht = pk.wht; b.seq_len = d_seq; b.drop = drop ? drop + (size_t)l * M * H : nullptr;
+        b.dy = cv.dy[cur]; b.wht = pk.wht; b.seq_len = d_seq; b.drop = drop ? drop + (size_t)l * drop_layer : nullptr;
+        b.drop_bs = drop_bs; b.drop_ts = drop_ts;
         b.ar = y.ar; b.au = y.au; b.ac = y.ac; b.hp = y.hp; b.dhat = y.dhat; b.keep_prob = h->cfg.keep_prob; b.B = B; b.T = T;
         KWS_LAUNCH(h, kws::launch_gru_train_backward(b, H, st), "launch gru_train_backward");
-        if (l > 0) {          // the dy of the layer below: [dr^ | du^ | dc^] . (Wg_x | Wc_x)^T
+        if (l > 0 || h->ln) {          // [dr^ | du^ | dc^] . (Wg_x | Wc_x)^T: the dy of the layer below, or dxhat under the layer norm
             kws::TrainRowsGemm g = {};
             g.a = y.dhat; g.lda = 3 * H; g.w = pk.wx; g.swk = 1; g.swn = 3 * H;
-            g.out = cv.dy[cur ^ 1]; g.ldo = H; g.M = M; g.K = 3 * H; g.N = pk.in;
+            g.out = h->ln ? y.g : cv.dy[cur ^ 1]; g.ldo = pk.in; g.M = M; g.K = 3 * H; g.N = pk.in;
             KWS_LAUNCH(h, kws::launch_train_rows_gemm(g, st), "launch train_rows_gemm (dx)");
-            cur ^= 1;
         }
+        if (h->ln) {
+            kws::TrainLnBackward n = {};
+            n.g = y.g; n.xn = y.xn; n.rstd = y.rstd; n.live = cv.live; n.ibeta = h->theta + h->wl.ibeta[l];
+            n.resid = residual_on(h, l) ? cv.dy[cur] : nullptr; n.din = l > 0 ? cv.dy[cur ^ 1] : nullptr; n.gs = y.gs; n.M = M; n.I = pk.in;
+            KWS_LAUNCH(h, kws::launch_train_ln_backward(n, st), "launch train_ln_backward");
+        } else if (residual_on(h, l)) {
+            KWS_LAUNCH(h, kws::launch_train_residual(cv.dy[cur ^ 1], cv.dy[cur], 1.0f, cv.dy[cur ^ 1], (size_t)M * H, st), "launch train_residual (d in)");
+        }
+        if (l > 0) cur ^= 1;
     }
     KWS_LAUNCH(h, kws::launch_train_wgrad(cv.jobs, cv.njobs, cv.units, x, cv.live, M, cv.chunk_rows, cv.chunks, cv.partial, h->P, st),
                "launch train_wgrad");
@@ -242,17 +288,26 @@ int grad_impl(kws_train* h, const float* x, const int32_t* seq_len, const int32_
     return KWS_OK;
 }
 
-// every refusal of kws_train_create that needs no device
-int check_config(const kws_train_config& cfg) {
+// every refusal of kws_train_create (wrapped: of kws_train_create_wrapped) that needs no device
+int check_config(const kws_train_config& cfg, bool wrapped) {
     const kws_config& c = cfg.model;
     if (c.use_relu || c.value_clip > 0.f)
         return fail(KWS_ERR_UNSUPPORTED, "model.use_relu=%d / model.value_clip=%g: training through relu and clip is out of scope (the gradient of "
                     "TensorFlow's relu and clip at their ties is not pinned)", c.use_relu, (double)c.value_clip);
-    if (cfg.wrappers.use_layer_norm || cfg.wrappers.use_residual)
-        return fail(KWS_ERR_UNSUPPORTED, "wrappers.use_layer_norm=%d / wrappers.use_residual=%d: the cell wrappers have no backward kernels",
-                    cfg.wrappers.use_layer_norm, cfg.wrappers.use_residual);
-    if (cfg.variational_recurrent)
-        return fail(KWS_ERR_UNSUPPORTED, "variational_recurrent=%d: one mask per frame only (DropoutWrapper's default)", cfg.variational_recurrent);
+    if (wrapped) {
+        const struct { const char* name; int v; } sw[3] = {{"wrappers.use_layer_norm", cfg.wrappers.use_layer_norm},
+                                                           {"wrappers.use_residual", cfg.wrappers.use_residual},
+                                                           {"variational_recurrent", cfg.variational_recurrent}};
+        for (const auto& f : sw)
+            if (f.v != 0 && f.v != 1) return fail(KWS_ERR_INVALID_ARGUMENT, "%s=%d: 0 or 1", f.name, f.v);
+    } else {
+        if (cfg.wrappers.use_layer_norm || cfg.wrappers.use_residual)
+            return fail(KWS_ERR_UNSUPPORTED, "wrappers.use_layer_norm=%d / wrappers.use_residual=%d: kws_train_create trains the plain cell "
+                        "(the wrapped stack: kws_train_create_wrapped)", cfg.wrappers.use_layer_norm, cfg.wrappers.use_residual);
+        if (cfg.variational_recurrent)
+            return fail(KWS_ERR_UNSUPPORTED, "variational_recurrent=%d: kws_train_create takes one mask per frame (DropoutWrapper's default; "
+                        "one mask per stream: kws_train_create_wrapped)", cfg.variational_recurrent);
+    }
     if (c.precision != KWS_FP32) return fail(KWS_ERR_UNSUPPORTED, "model.precision=%d: training is fp32 (KWS_FP32) only", c.precision);
     if (!(cfg.keep_prob > 0.f && cfg.keep_prob <= 1.f))
         return fail(KWS_ERR_UNSUPPORTED, "keep_prob=%g outside (0, 1]", (double)cfg.keep_prob);
@@ -273,24 +328,20 @@ int probe_device() {
     return KWS_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-size_t kws_sizeof_train_config(void) { return sizeof(kws_train_config); }
-
-int kws_train_create(const kws_train_config* cfg, kws_train_handle* out) {
+int create_impl(const kws_train_config* cfg, bool wrapped, kws_train_handle* out) {
     if (!out) return fail(KWS_ERR_INVALID_ARGUMENT, "out handle pointer is null");
     *out = nullptr;
     if (!cfg) return fail(KWS_ERR_INVALID_ARGUMENT, "config is null");
-    KWS_TRY(check_config(*cfg));
+    KWS_TRY(check_config(*cfg, wrapped));
     const kws_config& c = cfg->model;
     KWS_TRY(probe_device());
     kws_train* h = new (std::nothrow) kws_train();
     if (!h) return fail(KWS_ERR_OUT_OF_MEMORY, "host allocation failed");
     h->cfg = *cfg;
     h->bl = blob_layout(c);
-    h->P = h->bl.total;
+    h->wl = wrap_layout(c, cfg->wrappers);
+    h->ln = cfg->wrappers.use_layer_norm != 0; h->res = cfg->wrappers.use_residual != 0; h->var = cfg->variational_recurrent != 0;
+    h->P = h->wl.total;          // the canonical blob's, without the layer norm
     h->nred = kws::train_reduce_blocks(h->P);
     const size_t H = (size_t)c.hidden;
     size_t floats = 4 * h->P;
@@ -320,10 +371,26 @@ int kws_train_create(const kws_train_config* cfg, kws_train_handle* out) {
     return KWS_OK;
 }
 
+}  // namespace
+
+extern "C" {
+
+size_t kws_sizeof_train_config(void) { return sizeof(kws_train_config); }
+
+int kws_train_create(const kws_train_config* cfg, kws_train_handle* out) { return create_impl(cfg, false, out); }
+int kws_train_create_wrapped(const kws_train_config* cfg, kws_train_handle* out) { return create_impl(cfg, true, out); }
+
 int kws_train_check(const kws_train_config* cfg, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
                     int T, int S_max, const float* loss) {
     if (!cfg) return fail(KWS_ERR_INVALID_ARGUMENT, "config is null");
-    KWS_TRY(check_config(*cfg));
+    KWS_TRY(check_config(*cfg, false));
+    return check_call(*cfg, x, seq_len, labels, label_len, B, T, S_max, loss);
+}
+
+int kws_train_check_wrapped(const kws_train_config* cfg, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
+                            int B, int T, int S_max, const float* loss) {
+    if (!cfg) return fail(KWS_ERR_INVALID_ARGUMENT, "config is null");
+    KWS_TRY(check_config(*cfg, true));
     return check_call(*cfg, x, seq_len, labels, label_len, B, T, S_max, loss);
 }
 

@@ -1,7 +1,8 @@
 // Training of the GRU stack (models/rnn_ctc.py:34-101,179-284): the two frame loops, one launch per layer each.
 //
 //   gru_train_forward<TPW>    the taped forward of one layer: TF 1.x GRUCell under dynamic_rnn(sequence_length) and
-//                             DropoutWrapper(output_keep_prob), from the zero state
+//                             DropoutWrapper(output_keep_prob) -- a mask per frame, or variational_recurrent's one mask per stream
+//                             (the mask's strides are launch arguments) --, from the zero state
 //                               [r,u] = sigma(xg_ru + h.Wg_h)    c = tanh(xg_c + (r o h).Wc_h)    h' = u o h + (1 - u) o c
 //                               y = h' o mask / keep_prob   (what goes up; the carried state is the undropped h')
 //                             at t >= seq_len[b] the state is copied and y = 0.  It keeps r, u, c, h (the state the frame started
@@ -62,6 +63,9 @@ __device__ __forceinline__ int group_frames(const int32_t* seq_len, int group, i
     return tmax;
 }
 __device__ __forceinline__ void st4(float* p, f32x4 v) { *reinterpret_cast<f32x4*>(p) = v; }
+// where the dropout mask of (stream b, frame t) begins: one mask per frame, or one per stream held for all frames (kws_internal.h)
+template <int H, typename Params>
+__device__ __forceinline__ size_t mask_row(const Params& p, int b, int t) { return ((size_t)b * p.drop_bs + (size_t)t * p.drop_ts) * H; }
 // v o mask / keep_prob on four consecutive units (the offset is a multiple of 4): a true division, as TensorFlow's x / keep_prob * mask --
 // a rounded reciprocal would scale every output of the layer by the same relative error, which does not average out
 __device__ __forceinline__ f32x4 dropped(f32x4 v, const uint8_t* drop, size_t at, float keep_prob) {
@@ -169,7 +173,7 @@ __global__ void __launch_bounds__(256) gru_train_forward(const TrainForwardParam
             for (int e = 0; e < 4; ++e) hn[e] = fmaf(uu[j][e], hreg[j][e], un[j][e] * tanhf(acc_c[j][e]));
             if (live) {
                 st4(p.ar + at, acc_r[j]); st4(p.au + at, acc_u[j]); st4(p.ac + at, acc_c[j]); st4(p.hp + at, hreg[j]); st4(p.rh + at, rh[j]);
-                y = p.drop ? dropped(hn, p.drop, at, p.keep_prob) : hn;
+                y = p.drop ? dropped(hn, p.drop, mask_row<H>(p, b, t) + n * 16 + 4 * g, p.keep_prob) : hn;
                 hreg[j] = hn;          // a dead frame copies the state
             }
             if (bvalid) st4(p.y + at, y);
@@ -224,7 +228,7 @@ __global__ void __launch_bounds__(256) gru_train_backward(const TrainBackwardPar
             ar[j] = splat4(0.f); hp[j] = splat4(0.f);
             if (live) {          // the tape has rows t < seq_len only
                 ar[j] = ld4(p.ar + at); au = ld4(p.au + at); ac = ld4(p.ac + at); hp[j] = ld4(p.hp + at); dy = ld4(p.dy + at);
-                if (p.drop) dy = dropped(dy, p.drop, at, p.keep_prob);
+                if (p.drop) dy = dropped(dy, p.drop, mask_row<H>(p, b, t) + n * 16 + 4 * g, p.keep_prob);
             }
 #pragma unroll
             for (int e = 0; e < 4; ++e) {

@@ -503,7 +503,8 @@ struct TrainForwardParams {
     const float* xg;        // [B*T, 3H] x-part products + bias (rows past seq_len: the bias)
     const float* wh;
     const int32_t* seq_len; // [B], device
-    const uint8_t* drop;    // [B*T, H] this layer's output-dropout mask, or null
+    const uint8_t* drop;    // this layer's output-dropout mask, or null: the mask row of (b, t) is b * drop_bs + t * drop_ts, H bytes each --
+    int drop_bs, drop_ts;   // one mask per frame [B*T, H]: (T, 1); one per stream held for all frames [B, H] (variational): (1, 0)
     float *ar, *au, *ac, *hp, *rh;  // the tape [B*T, H]: pre-activations of r, u, c, the state the frame started from, r o hp; rows t < seq_len only
     float* y;               // [B*T, H] what goes up: h' o mask / keep_prob, zero rows at t >= seq_len
     float keep_prob;
@@ -514,6 +515,7 @@ struct TrainBackwardParams {
     const float* wht;
     const int32_t* seq_len;
     const uint8_t* drop;
+    int drop_bs, drop_ts;   // as the forward's
     const float *ar, *au, *ac, *hp;
     float* dhat;            // [B*T, 3H] pre-activation gradients dr^ | du^ | dc^, zero rows at t >= seq_len
     float keep_prob;
@@ -558,6 +560,24 @@ hipError_t launch_train_pack(const TrainPackParams& p, hipStream_t st);
 hipError_t launch_train_rowmask(const int32_t* seq_len, int B, int T, uint8_t* live, hipStream_t st);
 // g [rows, C], ctc_loss_kernel's grad_logits of `logits`: each frame's occupancies renormalised to sum 1, then g *= s
 hipError_t launch_train_scale(float* g, const float* logits, size_t rows, int C, float s, hipStream_t st);
+// The cell wrappers in training (train_wrap_kernels.hip), rows [M, I]; live [M] as above: dead rows are written as zeros and not read.
+//   forward: x^ = xn ibeta + igamma with xn = (in - mean) rstd, rstd = 1 / sqrt(var + 1e-5); ibeta (one float) and igamma [I] on the device
+struct TrainLnForward {
+    const float* in; const uint8_t* live; const float *ibeta, *igamma;
+    float *xhat, *xn, *rstd;          // [M, I], [M, I], [M]
+    int M, I;
+};
+hipError_t launch_train_ln_forward(const TrainLnForward& p, hipStream_t st);
+//   backward: g [M, I] = dx^; din [M, I] = rstd (dn - mean(dn) - xn mean(dn o xn)) with dn = g ibeta, plus resid [M, I] where given;
+//   din null: not wanted (layer 0).  gs [M]: sum_i g_i xn_i, the row's term of d ibeta
+struct TrainLnBackward {
+    const float *g, *xn, *rstd; const uint8_t* live; const float* ibeta; const float* resid;
+    float *din, *gs;
+    int M, I;
+};
+hipError_t launch_train_ln_backward(const TrainLnBackward& p, hipStream_t st);
+// out = s (a + b) over n floats (n % 4 == 0, 16-byte aligned blocks); b null: out = s a; out may be a
+hipError_t launch_train_residual(const float* a, const float* b_or_null, float s, float* out, size_t n, hipStream_t st);
 
 // octbit_kernels.hip
 hipError_t launch_octbit_matmul(const float* x, const int8_t* Wq, float scale_w, const float* bias,

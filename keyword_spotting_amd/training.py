@@ -1,7 +1,8 @@
 """Training of the GRU stack on the device (main.py's loop over models/rnn_ctc.py:34-101): taped forward, back-propagation through
 time, tf.nn.ctc_loss, tf.clip_by_global_norm and tf.train.AdamOptimizer / MomentumOptimizer(0.9, use_nesterov=True) behind
 kws_train_* (include/kws_amd.h).  A Trainer owns the parameters on the device; weights() / save() / deploy() hand them to the
-serving side."""
+serving side.  config.use_layer_norm / use_residual / variational_recurrent (get_cell's wrappers, models/rnn_ctc.py:179-199) take the
+handle of kws_train_create_wrapped: the layer norm's ibeta / igamma are then parameters like the others."""
 import ctypes
 
 import numpy as np
@@ -19,7 +20,8 @@ def learning_rate_at(step, learning_rate=1.5e-3, lr_decay=0.8, decay_step=20000)
 
 
 def train_config(config, optimizer="adam", max_grad_norm=-1.0, keep_prob=1.0):
-    """The kws_train_config of a model config: every option a train handle refuses travels with its own field, so the refusal names it."""
+    """The kws_train_config of a model config: every option a train handle refuses travels with its own field, so the refusal names it.
+    The three switches of kws_train_create_wrapped are read from the config (use_layer_norm, use_residual, variational_recurrent)."""
     if optimizer not in OPTIMIZERS:
         raise _lib.InvalidArgumentError(-1, "optimizer %r: 'adam' or 'nesterov' (models/rnn_ctc.py:80-87)" % (optimizer,))
     model = _lib.KwsConfig(config.n_mel, config.hidden_size, config.num_layers, config.num_classes, int(bool(config.use_relu)),
@@ -34,10 +36,14 @@ class Trainer(object):
     """The reference's training graph on one device.  Defaults: config/rnn_config.py:44-55,77 (learning_rate 1.5e-3, lr_decay 0.8,
     decay_step 20000, adam, max_grad_norm -1 = no clipping); keep_prob defaults to 1 (the reference file ships 0.6, :81).
 
-    weights: a dict (weights.init_weights' form), a blob, or None for init_weights(config, seed)."""
+    weights: a dict (weights.init_weights' form), a blob, or None for init_weights(config, seed).  With config.use_layer_norm the dict
+    carries each layer's ibeta / igamma and the blob is kws_weights_nbytes_wrapped's; with config.variational_recurrent the output masks
+    are [L,B,H], one per stream and layer held for all frames.
+    wrapped: None takes kws_train_create_wrapped exactly when one of the three switches is set; True takes it always (with every switch
+    off it gives kws_train_create's handle: the same launches, the same bits)."""
 
     def __init__(self, config, weights=None, optimizer="adam", learning_rate=1.5e-3, lr_decay=0.8, decay_step=20000, max_grad_norm=-1,
-                 keep_prob=1.0, seed=0, device="cuda:0"):
+                 keep_prob=1.0, seed=0, device="cuda:0", wrapped=None):
         import torch
         self.config = config
         self.optimizer, self.learning_rate, self.lr_decay, self.decay_step = optimizer, float(learning_rate), float(lr_decay), int(decay_step)
@@ -48,8 +54,12 @@ class Trainer(object):
             raise _lib.InvalidArgumentError(-1, "Trainer needs a CUDA/HIP device, got %s" % device)
         self._lib = _lib.load()
         self._handle = ctypes.c_void_p()
+        self.variational = bool(self._cfg.variational_recurrent)
+        if wrapped is None:
+            wrapped = self.variational or bool(self._cfg.wrappers.use_layer_norm) or bool(self._cfg.wrappers.use_residual)
+        create = self._lib.kws_train_create_wrapped if wrapped else self._lib.kws_train_create
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_train_create(ctypes.byref(self._cfg), ctypes.byref(self._handle)))
+            _lib.check(create(ctypes.byref(self._cfg), ctypes.byref(self._handle)))
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(int(seed))
         self.global_step = 0
@@ -72,6 +82,14 @@ class Trainer(object):
     def _stream(self):
         return _lib.current_stream_ptr()
 
+    def _floats(self):
+        """Floats of the handle's blobs: the canonical blob and, with the layer norm, every layer's ibeta and igamma behind it."""
+        return self._lib.kws_weights_nbytes_wrapped(ctypes.byref(self._cfg.model), ctypes.byref(self._cfg.wrappers)) // 4
+
+    def _drop_shape(self, b, t):
+        cfg = self.config
+        return (cfg.num_layers, b, cfg.hidden_size) if self.variational else (cfg.num_layers, b, t, cfg.hidden_size)
+
     # -- parameters --------------------------------------------------------------------------
     def set_weights(self, weights):
         """Loads parameters; zeroes the optimiser's moments and the step count of its bias corrections."""
@@ -83,7 +101,7 @@ class Trainer(object):
 
     def weights_blob(self):
         import torch
-        blob = np.empty(self._lib.kws_weights_nbytes(ctypes.byref(self._cfg.model)) // 4, np.float32)
+        blob = np.empty(self._floats(), np.float32)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.kws_train_get_weights(self._handle, blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes, self._stream()))
         return blob
@@ -95,7 +113,7 @@ class Trainer(object):
     def moments(self):
         """(m, v) in the dict form: Adam's moments; Nesterov's accumulator and zeros."""
         import torch
-        n = self._lib.kws_weights_nbytes(ctypes.byref(self._cfg.model)) // 4
+        n = self._floats()
         m, v = np.empty(n, np.float32), np.empty(n, np.float32)
         with torch.cuda.device(self.device):
             _lib.check(self._lib.kws_train_moments(self._handle, m.ctypes.data_as(ctypes.c_void_p), v.ctypes.data_as(ctypes.c_void_p), self._stream()))
@@ -144,8 +162,10 @@ class Trainer(object):
             raise _lib.InvalidArgumentError(-1, "lengths: %s for %d utterances" % (sl.shape, b))
         if drop is not None:
             drop = torch.as_tensor(drop).to(device=self.device, dtype=torch.uint8).contiguous()
-            if tuple(drop.shape) != (cfg.num_layers, b, t, cfg.hidden_size):
-                raise _lib.InvalidArgumentError(-1, "drop must be [%d,%d,%d,%d], got %s" % (cfg.num_layers, b, t, cfg.hidden_size, tuple(drop.shape)))
+            if tuple(drop.shape) != self._drop_shape(b, t):
+                raise _lib.InvalidArgumentError(-1, "drop must be [%s]%s, got %s" % (",".join(map(str, self._drop_shape(b, t))),
+                                                    " (variational_recurrent: one mask per stream and layer)" if self.variational else "",
+                                                    tuple(drop.shape)))
         return x, b, t, _ints(sl), _ints(lab), _ints(lab_len), drop
 
     def loss_and_grad(self, x, lengths, labels, drop=None, want_logits=False):
@@ -154,7 +174,7 @@ class Trainer(object):
         import torch
         x, b, t, (sl, sl_p), (lab, lab_p), (ll, ll_p), drop = self._inputs(x, lengths, labels, drop)
         loss = torch.empty(b, dtype=torch.float32, device=self.device)
-        grad = torch.empty(self._lib.kws_weights_nbytes(ctypes.byref(self._cfg.model)) // 4, dtype=torch.float32, device=self.device)
+        grad = torch.empty(self._floats(), dtype=torch.float32, device=self.device)
         logits = torch.empty(b, t, self.config.num_classes, dtype=torch.float32, device=self.device) if want_logits else None
         with torch.cuda.device(self.device):
             _lib.check(self._lib.kws_train_grad(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]), _lib.ptr(drop),
@@ -175,16 +195,16 @@ class Trainer(object):
         return (loss, norm) if want_norm else loss
 
     def step(self, x, lengths, labels):
-        """One training step as main.py runs it: input dropout on x and one output mask per layer, both floor(keep_prob + U) from the
-        trainer's own generator (keep_prob < 1 only), the scheduled learning rate, then the update -> loss = sum_b ctc_b / B."""
+        """One training step as main.py runs it: input dropout on x and one output mask per layer ([L,B,T,H]; variational: [L,B,H]), both
+        floor(keep_prob + U) from the trainer's own generator (keep_prob < 1 only), the scheduled learning rate, then the update
+        -> loss = sum_b ctc_b / B."""
         import torch
         x = torch.as_tensor(x).to(device=self.device, dtype=torch.float32)
         drop = None
         if self.keep_prob < 1.0:
-            cfg = self.config
             keep = torch.floor(self.keep_prob + torch.rand(x.shape, generator=self._gen, device=self.device))
             x = x / self.keep_prob * keep           # tf.nn.dropout(inputX, keep_prob) (models/rnn_ctc.py:41-42)
-            drop = torch.floor(self.keep_prob + torch.rand((cfg.num_layers, x.shape[0], x.shape[1], cfg.hidden_size), generator=self._gen,
+            drop = torch.floor(self.keep_prob + torch.rand(self._drop_shape(x.shape[0], x.shape[1]), generator=self._gen,
                                                            device=self.device)).to(torch.uint8)
         loss = self.step_raw(x, lengths, labels, self.learning_rate_at(self.global_step), drop=drop)
         self.global_step += 1
