@@ -855,6 +855,75 @@ int kws_attention_pe_table(kws_attention_handle h, float* host_out);
  * of the contract above; synchronises.  KWS_OK, or KWS_ERR_HIP with the deviation and kws_version(). */
 int kws_attention_selftest(kws_attention_handle h);
 
+/* Training of the self-attention CTC model (main.py --model attention; models/attention_ctc.py:131-202): taped forward, backward,
+ * tf.nn.ctc_loss, tf.clip_by_global_norm, Adam / Nesterov.  fp32 only.
+ *
+ * What is trained is the function kws_attention_run serves, per utterance: stacking by combine_frame, embedding + positional table and
+ * the L layers, each utterance over its own T'_b = frames_out(T_b) rows only -- attention over the utterance's own keys, layer-norm
+ * moments over the utterance's own [T'_b, H] block (eps 1e-12).  This is the reference's training graph whenever all utterances of a
+ * batch have the same length; on a padded batch the reference lets the padded rows take part as keys and in the layer-norm moments,
+ * and this trainer does not (what is trained is what is served).  Rows at or past T'_b are never read into a result: NaN padding of x
+ * gives the bits of zero padding.
+ *
+ * Training-only: dropout at the reference's three sites, each x * keep / keep_prob with a true division:
+ *   site 0  the attention probabilities behind the softmax (:51-52; coordinates layer, b, head, row = query, col = key); the softmax's
+ *           normaliser is the undropped sum
+ *   site 1  the attention output in front of its residual sum (:106-108; head = 0, row = t', col = the unit 0..H-1)
+ *   site 2  the FFN output in front of its residual sum (:114-116; as site 1)
+ * The masks are no arrays: every keep decision is a stateless function of the call's drop_seed and (site, layer, b, head, row, col),
+ *   ctr = site << 62 | layer << 58 | head << 52 | b << 28 | row << 14 | col
+ *   z   = drop_seed + ctr * 0x9E3779B97F4A7C15                                       (all arithmetic modulo 2^64)
+ *   z  ^= z >> 30;  z *= 0xBF58476D1CE4E5B9;  z ^= z >> 27;  z *= 0x94D049BB133111EB;  z ^= z >> 31
+ *   keep iff (z >> 32) < floor((double)keep_prob * 2^32)
+ * kws_attention_drop_keep evaluates it on the host for n (row, col) pairs: keep [n] bytes (0 / 1).  keep_prob == 1 ignores the seed and
+ * gives the bits of a call without dropout.
+ * Loss: tf.nn.ctc_loss on the (post-relu when use_relu) logits with sequence_length = T'_b, averaged as sum / B.  kws_train_grad's
+ * conventions: blank is the last class; S_max <= 31; host seq_len (frames T_b, 0..T) / labels / label_len are range-checked before any
+ * launch; an utterance without a valid path has loss +inf and a gradient of exactly 0; ctc_loss_kernel's LDS limit applies to T'.
+ * Both relus (FFN inner, logits) use TensorFlow's ReluGrad, g * (pre > 0).  Clip, Adam and Nesterov exactly as kws_train_step; the
+ * learning rate is an argument of every step.
+ *
+ * The entries are shaped after their kws_train_* namesakes: refusals come before the device is touched and name the field
+ * (kws_attention_train_check decides them from host memory alone); the config space is kws_attention_create's; one host thread per
+ * handle (KWS_ERR_BUSY); calls are ordered by the handle's event across streams; nothing allocates and nothing waits for the device
+ * once the tape of a shape exists (kws_attention_train_reserve, or the first call of a larger shape) and the call's seq_len, labels and
+ * label_len are those of the call before.  When they differ, the call uploads them (B * (3 + S_max) ints) from pageable host memory, as
+ * kws_train_grad does: the runtime finishes that copy on the host before the call goes on, so the host waits for the stream's earlier
+ * work once, and for nothing after it.
+ *   x [B,T,n_mel] f32 device; seq_len [B], labels [B,S_max], label_len [B] host; loss [B] f32 device out
+ *   grad_blob: device, kws_attention_weights_nbytes' layout, the gradient of sum(loss) / B; logits_or_null [B,T'max,C] device (rows past
+ *   T'_b are 0); lr > 0; grad_norm_or_null: device, one float, the global norm before the clip
+ *   set / get_weights, moments: the canonical blob in HOST memory; set zeroes the optimiser's slots and its step count
+ *   stats: device bytes held; (re)allocations since create; optimiser steps since set_weights; kernel launches of the last grad / step
+ *   call (12 + 19 L + use_relu, one more for a step); rows per chunk of the weight-gradient reduction */
+typedef struct kws_attention_train_config {
+    kws_attention_config model;
+    int32_t optimizer;                /* KWS_OPT_ADAM / KWS_OPT_NESTEROV */
+    float max_grad_norm;              /* <= 0: no clipping */
+    float keep_prob;                  /* (0, 1] */
+} kws_attention_train_config;
+typedef struct kws_attention_train* kws_attention_train_handle;
+size_t kws_sizeof_attention_train_config(void);
+int kws_attention_train_create(const kws_attention_train_config* cfg, kws_attention_train_handle* out);
+int kws_attention_train_check(const kws_attention_train_config* cfg, const float* x, const int32_t* seq_len, const int32_t* labels,
+                              const int32_t* label_len, int B, int T, int S_max, const float* loss);
+int kws_attention_train_destroy(kws_attention_train_handle h);   /* always KWS_OK */
+int kws_attention_train_set_weights(kws_attention_train_handle h, const void* blob /*host*/, size_t nbytes, void* stream);
+int kws_attention_train_get_weights(kws_attention_train_handle h, void* blob /*host*/, size_t nbytes, void* stream);
+int kws_attention_train_reserve(kws_attention_train_handle h, int B, int T, int S_max);
+int kws_attention_train_grad(kws_attention_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels,
+                             const int32_t* label_len, int B, int T, int S_max, uint64_t drop_seed, float* loss, float* grad_blob,
+                             float* logits_or_null, void* stream);
+int kws_attention_train_step(kws_attention_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels,
+                             const int32_t* label_len, int B, int T, int S_max, uint64_t drop_seed, float lr, float* loss,
+                             float* grad_norm_or_null, void* stream);
+int kws_attention_train_moments(kws_attention_train_handle h, float* m /*host*/, float* v /*host*/, void* stream);
+int kws_attention_train_stats(kws_attention_train_handle h, size_t* device_bytes, int32_t* allocs, int32_t* steps, int32_t* launches,
+                              int32_t* chunk_rows);
+/* site 0..2, layer 0..7, b 0..65535, head 0..15, rows / cols [n] in 0..16383 (host); keep [n] bytes out (host) */
+int kws_attention_drop_keep(uint64_t drop_seed, float keep_prob, int site, int layer, int b, int head, const int32_t* rows,
+                            const int32_t* cols, int n, uint8_t* keep);
+
 #ifdef __cplusplus
 }
 #endif

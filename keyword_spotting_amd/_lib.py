@@ -68,6 +68,12 @@ class KwsAttentionConfig(ctypes.Structure):
                 ("num_classes", ctypes.c_int32), ("use_relu", ctypes.c_int32), ("max_frames", ctypes.c_int32)]
 
 
+class KwsAttentionTrainConfig(ctypes.Structure):
+    """kws_attention_train_config: the attention model, the optimiser, the global-norm clip (<= 0: none) and the keep probability of the
+    three dropout sites."""
+    _fields_ = [("model", KwsAttentionConfig), ("optimizer", ctypes.c_int32), ("max_grad_norm", ctypes.c_float), ("keep_prob", ctypes.c_float)]
+
+
 class KwsError(RuntimeError):
     """Base of the errors the C ABI reports."""
 
@@ -184,6 +190,20 @@ _SIGNATURES = {
     "kws_train_moments": (_i, [_vp, _vp, _vp, _vp]),
     "kws_train_stats": (_i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                              ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    # training of the self-attention CTC model: taped forward, backward, CTC loss, clip, Adam / Nesterov; the dropout hash on the host
+    "kws_sizeof_attention_train_config": (ctypes.c_size_t, []),
+    "kws_attention_train_create": (_i, [ctypes.POINTER(KwsAttentionTrainConfig), ctypes.POINTER(_vp)]),
+    "kws_attention_train_check": (_i, [ctypes.POINTER(KwsAttentionTrainConfig), _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "kws_attention_train_destroy": (_i, [_vp]),
+    "kws_attention_train_set_weights": (_i, [_vp, _vp, ctypes.c_size_t, _vp]),
+    "kws_attention_train_get_weights": (_i, [_vp, _vp, ctypes.c_size_t, _vp]),
+    "kws_attention_train_reserve": (_i, [_vp, _i, _i, _i]),
+    "kws_attention_train_grad": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_uint64, _vp, _vp, _vp, _vp]),
+    "kws_attention_train_step": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_uint64, _f, _vp, _vp, _vp]),
+    "kws_attention_train_moments": (_i, [_vp, _vp, _vp, _vp]),
+    "kws_attention_train_stats": (_i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
+                                       ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    "kws_attention_drop_keep": (_i, [ctypes.c_uint64, _f, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
     # a bank of enrolled heads: per-user customised keywords on one frozen model
     "kws_bank_create": (_i, [_i, _i, _i, _i, ctypes.POINTER(_vp)]),
     "kws_bank_destroy": (_i, [_vp]),
@@ -222,6 +242,7 @@ def load():
                 lib.kws_sizeof_dataset_config() != ctypes.sizeof(KwsDatasetConfig) or \
                 lib.kws_sizeof_attention_config() != ctypes.sizeof(KwsAttentionConfig) or \
                 lib.kws_sizeof_train_config() != ctypes.sizeof(KwsTrainConfig) or \
+                lib.kws_sizeof_attention_train_config() != ctypes.sizeof(KwsAttentionTrainConfig) or \
                 lib.kws_sizeof_head_io() != ctypes.sizeof(KwsHeadIo):
             raise ImportError("%s was built from a different include/kws_amd.h than this binding (struct sizes differ); "
                               "rebuild it" % LIB_PATH)

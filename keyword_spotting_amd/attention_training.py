@@ -1,0 +1,229 @@
+"""Training of the self-attention CTC model on the device (main.py --model attention over models/attention_ctc.py:131-202): taped
+forward, backward, tf.nn.ctc_loss, tf.clip_by_global_norm and tf.train.AdamOptimizer / MomentumOptimizer(0.9, use_nesterov=True)
+behind kws_attention_train_* (include/kws_amd.h).  An AttentionTrainer owns the parameters on the device; weights() / save() /
+deploy() hand them to the serving side (attention_ctc.DeployModel).
+
+What is trained is what is served: every utterance over its own T'_b rows (its own keys, its own layer-norm block).  That is the
+reference's graph whenever all utterances of a batch have the same length; on padded batches the reference lets the padded rows
+take part as keys and in the layer-norm moments, and this trainer does not.  The dropout masks of the three sites are a counter
+hash of a per-call seed (drop_keep below restates it through the library's host entry)."""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from . import attention_weights as _weights
+from .custom_keyword import _ints, _pack_labels
+from .training import OPTIMIZERS
+
+SITE_PROB, SITE_ATT, SITE_FFN = 0, 1, 2
+
+
+def exponential_decay(learning_rate, step, decay_step, lr_decay):
+    """tf.train.exponential_decay, staircase=False."""
+    return float(learning_rate) * float(lr_decay) ** (float(step) / float(decay_step))
+
+
+def polynomial_decay(learning_rate, step, decay_steps, end_learning_rate, power):
+    """tf.train.polynomial_decay, cycle=False: the step is clamped to decay_steps."""
+    s = min(float(step), float(decay_steps))
+    return (float(learning_rate) - float(end_learning_rate)) * (1.0 - s / float(decay_steps)) ** float(power) + float(end_learning_rate)
+
+
+def learning_rate_at(step, learning_rate=1e-3, lr_decay=0.9, decay_step=40000, warmup=False):
+    """models/attention_ctc.py:171-181: the exponential decay of the configured rate; with warmup the smaller of
+    polynomial_decay(5e-3, step, 40000, 1.35e-3, power 0.5) and exponential_decay(1.5e-3, step, decay_step, lr_decay)."""
+    if warmup:
+        return min(polynomial_decay(5e-3, step, 40000, 1.35e-3, 0.5), exponential_decay(1.5e-3, step, decay_step, lr_decay))
+    return exponential_decay(learning_rate, step, decay_step, lr_decay)
+
+
+def attention_config_struct(config):
+    return _lib.KwsAttentionConfig(int(config.freq_size), int(config.combine_frame), int(config.hidden_size), int(config.multi_head_num),
+                                   int(config.feed_forward_inner_size), int(config.num_layers), int(config.num_classes),
+                                   int(bool(config.use_relu)), int(config.max_frames))
+
+
+def train_config(config, optimizer="adam", max_grad_norm=-1.0, keep_prob=1.0):
+    if optimizer not in OPTIMIZERS:
+        raise _lib.InvalidArgumentError(-1, "optimizer %r: 'adam' or 'nesterov' (models/attention_ctc.py:183-190)" % (optimizer,))
+    return _lib.KwsAttentionTrainConfig(attention_config_struct(config), OPTIMIZERS[optimizer], float(max_grad_norm), float(keep_prob))
+
+
+def drop_keep(seed, keep_prob, site, layer, b, head, rows, cols):
+    """kws_attention_drop_keep: the keep decisions (uint8, the shape of rows / cols) of one site at the given coordinates.  Host code."""
+    rows, cols = np.broadcast_arrays(np.asarray(rows, np.int32), np.asarray(cols, np.int32))
+    r, c = np.ascontiguousarray(rows).ravel(), np.ascontiguousarray(cols).ravel()
+    out = np.empty(r.size, np.uint8)
+    _lib.check(_lib.load().kws_attention_drop_keep(ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), float(keep_prob), int(site), int(layer), int(b),
+                                                   int(head), r.ctypes.data_as(ctypes.c_void_p), c.ctypes.data_as(ctypes.c_void_p), int(r.size),
+                                                   out.ctypes.data_as(ctypes.c_void_p)))
+    return out.reshape(rows.shape)
+
+
+def check_call(config, x_shape, lengths, labels, optimizer="adam", max_grad_norm=-1.0, keep_prob=1.0):
+    """kws_attention_train_check on host memory alone (no device): raises what a create / grad / step of these arguments would."""
+    cfg = train_config(config, optimizer, max_grad_norm, keep_prob)
+    b, t = int(x_shape[0]), int(x_shape[1])
+    lab, lab_len = _pack_labels(labels, b)
+    sl, sl_p = _ints(np.full(b, t) if lengths is None else lengths)
+    lab, lab_p = _ints(lab)
+    lab_len, ll_p = _ints(lab_len)
+    dummy = np.zeros(4, np.float32)      # x and loss are only checked for null and alignment
+    p = dummy.ctypes.data_as(ctypes.c_void_p)
+    _lib.check(_lib.load().kws_attention_train_check(ctypes.byref(cfg), p, sl_p, lab_p, ll_p, b, t, int(lab.shape[1]), p))
+
+
+class AttentionTrainer(object):
+    """The reference's attention training graph on one device.  Defaults: config/attention_config.py:49-56,81 (learning_rate 1e-3,
+    lr_decay 0.9, decay_step 40000, adam, no clipping, no warm-up); keep_prob defaults to 1 (the reference file ships 0.9, :83).
+    weights: a dict (attention_weights.init's form), a blob, or None for attention_weights.init(config, seed)."""
+
+    def __init__(self, config, weights=None, optimizer="adam", learning_rate=1e-3, lr_decay=0.9, decay_step=40000, warmup=False,
+                 max_grad_norm=-1, keep_prob=1.0, seed=0, device="cuda:0"):
+        import torch
+        self.config = config
+        self.optimizer, self.learning_rate, self.lr_decay, self.decay_step = optimizer, float(learning_rate), float(lr_decay), int(decay_step)
+        self.warmup, self.max_grad_norm, self.keep_prob = bool(warmup), float(max_grad_norm), float(keep_prob)
+        self._cfg = train_config(config, optimizer, max_grad_norm, keep_prob)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise _lib.InvalidArgumentError(-1, "AttentionTrainer needs a CUDA/HIP device, got %s" % device)
+        self._lib = _lib.load()
+        self._handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_attention_train_create(ctypes.byref(self._cfg), ctypes.byref(self._handle)))
+        self._rng = np.random.default_rng(int(seed))          # the seeds of step()
+        self.global_step = 0
+        if weights is None:
+            weights = _weights.init(config, seed=seed)
+        self.set_weights(weights)
+
+    # -- lifecycle ---------------------------------------------------------------------------
+    def close(self):
+        if getattr(self, "_handle", None) is not None and self._handle.value:
+            self._lib.kws_attention_train_destroy(self._handle)
+            self._handle = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _stream(self):
+        return _lib.current_stream_ptr()
+
+    def _floats(self):
+        return self._lib.kws_attention_weights_nbytes(ctypes.byref(self._cfg.model)) // 4
+
+    def frames_out(self, frames):
+        c = int(self.config.combine_frame)
+        return frames // c + 1 if c > 1 else frames
+
+    # -- parameters --------------------------------------------------------------------------
+    def set_weights(self, weights):
+        """Loads parameters; zeroes the optimiser's moments and the step count of its bias corrections."""
+        import torch
+        blob = weights if isinstance(weights, np.ndarray) else _weights.to_blob(self.config, weights)
+        blob = np.ascontiguousarray(blob, np.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_attention_train_set_weights(self._handle, blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes, self._stream()))
+
+    def weights_blob(self):
+        import torch
+        blob = np.empty(self._floats(), np.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_attention_train_get_weights(self._handle, blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes, self._stream()))
+        return blob
+
+    def weights(self):
+        return _weights.from_blob(self.config, self.weights_blob())
+
+    def moments(self):
+        """(m, v) in the dict form: Adam's moments; Nesterov's accumulator and zeros."""
+        import torch
+        n = self._floats()
+        m, v = np.empty(n, np.float32), np.empty(n, np.float32)
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_attention_train_moments(self._handle, m.ctypes.data_as(ctypes.c_void_p), v.ctypes.data_as(ctypes.c_void_p),
+                                                             self._stream()))
+        return _weights.from_blob(self.config, m), _weights.from_blob(self.config, v)
+
+    def save(self, path):
+        w = self.weights()
+        flat = {k: w[k] for k in _weights.TOP_KEYS}
+        for j, lay in enumerate(w["layers"]):
+            for k in _weights.LAYER_KEYS:
+                flat["layer_%d/%s" % (j, k)] = lay[k]
+        np.savez(path, **flat)
+
+    def deploy(self, precision="fp32"):
+        """attention_ctc.DeployModel on the current parameters."""
+        from .attention_ctc import DeployModel
+        return DeployModel(self.config, self.weights_blob(), device=str(self.device), precision=precision)
+
+    def reserve(self, batch, frames, max_label=31):
+        _lib.check(self._lib.kws_attention_train_reserve(self._handle, int(batch), int(frames), int(max_label)))
+
+    def stats(self):
+        """dict(device_bytes, allocs, steps, launches of the last call, chunk_rows of the weight-gradient reduction)."""
+        nbytes = ctypes.c_size_t()
+        a, s, l, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(self._lib.kws_attention_train_stats(self._handle, ctypes.byref(nbytes), ctypes.byref(a), ctypes.byref(s), ctypes.byref(l),
+                                                       ctypes.byref(c)))
+        return dict(device_bytes=int(nbytes.value), allocs=a.value, steps=s.value, launches=l.value, chunk_rows=c.value)
+
+    # -- compute -----------------------------------------------------------------------------
+    def learning_rate_at(self, step):
+        return learning_rate_at(step, self.learning_rate, self.lr_decay, self.decay_step, self.warmup)
+
+    def _inputs(self, x, lengths, labels):
+        import torch
+        cfg = self.config
+        x = torch.as_tensor(x)
+        if x.dim() != 3 or x.shape[2] != cfg.freq_size:
+            raise _lib.InvalidArgumentError(-1, "x must be [B,T,%d], got %s" % (cfg.freq_size, tuple(x.shape)))
+        x = x.to(device=self.device, dtype=torch.float32).contiguous()
+        b, t = int(x.shape[0]), int(x.shape[1])
+        lab, lab_len = _pack_labels(labels, b)
+        sl = np.full(b, t) if lengths is None else np.asarray(lengths)
+        if sl.shape != (b,):
+            raise _lib.InvalidArgumentError(-1, "lengths: %s for %d utterances" % (sl.shape, b))
+        return x, b, t, _ints(sl), _ints(lab), _ints(lab_len)
+
+    def loss_and_grad(self, x, lengths, labels, seed=0, want_logits=False):
+        """-> (loss = sum_b ctc_b / B, gradients in the dict form, per-utterance losses [B]) [, logits [B,T',C]]; the parameters stay.
+        labels: B sequences over classes 0..C-2, or one for all; seed: the dropout seed of the call (ignored at keep_prob 1)."""
+        import torch
+        x, b, t, (sl, sl_p), (lab, lab_p), (ll, ll_p) = self._inputs(x, lengths, labels)
+        loss = torch.empty(b, dtype=torch.float32, device=self.device)
+        grad = torch.empty(self._floats(), dtype=torch.float32, device=self.device)
+        logits = torch.empty(b, self.frames_out(t), self.config.num_classes, dtype=torch.float32, device=self.device) if want_logits else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_attention_train_grad(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]),
+                                                          ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _lib.ptr(loss), _lib.ptr(grad),
+                                                          _lib.ptr(logits), self._stream()))
+        per = loss.cpu().numpy()
+        out = (float(per.astype(np.float64).sum() / b), _weights.from_blob(self.config, grad.cpu().numpy()), per)
+        return out + (logits,) if want_logits else out
+
+    def step_raw(self, x, lengths, labels, lr, seed=0, want_norm=False):
+        """One kws_attention_train_step at learning rate lr with the masks of `seed` -> per-utterance losses [B] (device) [, global norm]."""
+        import torch
+        x, b, t, (sl, sl_p), (lab, lab_p), (ll, ll_p) = self._inputs(x, lengths, labels)
+        loss = torch.empty(b, dtype=torch.float32, device=self.device)
+        norm = torch.empty(1, dtype=torch.float32, device=self.device) if want_norm else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.kws_attention_train_step(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]),
+                                                          ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), float(lr), _lib.ptr(loss), _lib.ptr(norm),
+                                                          self._stream()))
+        return (loss, norm) if want_norm else loss
+
+    def step(self, x, lengths, labels):
+        """One training step as main.py runs it: a fresh dropout seed from the trainer's own generator, the scheduled learning rate, the
+        update -> loss = sum_b ctc_b / B."""
+        seed = int(self._rng.integers(0, 2 ** 63))
+        loss = self.step_raw(x, lengths, labels, self.learning_rate_at(self.global_step), seed=seed)
+        self.global_step += 1
+        return float(loss.cpu().numpy().astype(np.float64).sum() / loss.shape[0])

@@ -27,14 +27,8 @@ struct kws_attention {
     hipEvent_t last_done = nullptr;
 };
 
-namespace {
+namespace kws_host {
 
-enum { kQkvW, kQkvB, kLnaBeta, kLnaGamma, kW1, kB1, kW2, kB2, kLnbBeta, kLnbGamma, kLayerParts };
-
-// offsets (floats) of the canonical blob
-struct AttnLayout {
-    size_t w_in, b_in, layer[8][kLayerParts], w_out, b_out, total;
-};
 AttnLayout attn_layout(const kws_attention_config& c) {
     AttnLayout o{};
     const size_t H = c.hidden, Fi = c.ffn_inner, K = (size_t)c.n_mel * c.combine_frame;
@@ -69,6 +63,10 @@ bool attn_config_ok(const kws_attention_config* c, int* code) {
     if (c->max_frames < 1 || c->max_frames > 8192) return bad("max_frames", c->max_frames, "1..8192");
     return true;
 }
+
+}  // namespace kws_host
+
+namespace {
 
 int frames_out(const kws_attention_config& c, int T) { return c.combine_frame > 1 ? T / c.combine_frame + 1 : T; }
 

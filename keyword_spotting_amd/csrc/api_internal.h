@@ -209,6 +209,23 @@ bool misaligned(const void* p);      // not 4-byte aligned
 // ... [seq_len | label_len | labels] as the one block that travels to the device
 void pack_ints(const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int S_max, std::vector<int32_t>* out);
 
+// both train handles (api_train.hip, api_attention_train.hip): the rows of the weight-gradient reduction are summed in at most
+// kWgradMaxChunks chunks of a multiple of kWgradChunkUnit rows
+constexpr int kWgradChunkUnit = 256, kWgradMaxChunks = 64;
+inline int wgrad_chunk_rows(size_t rows) {
+    const size_t per = (rows + (size_t)kWgradChunkUnit * kWgradMaxChunks - 1) / ((size_t)kWgradChunkUnit * kWgradMaxChunks);
+    return (int)(kWgradChunkUnit * (per < 1 ? 1 : per));
+}
+
+// api_attention.hip: the canonical blob of the attention model (offsets in floats) and the refusals of its config, shared with the
+// train handle (api_attention_train.hip)
+enum { kQkvW, kQkvB, kLnaBeta, kLnaGamma, kW1, kB1, kW2, kB2, kLnbBeta, kLnbGamma, kLayerParts };
+struct AttnLayout {
+    size_t w_in, b_in, layer[8][kLayerParts], w_out, b_out, total;
+};
+AttnLayout attn_layout(const kws_attention_config& c);
+bool attn_config_ok(const kws_attention_config* c, int* code);      // false: *code is the failure, kws_last_error names the field
+
 // api_frontend.hip: the 400-point FFT kernel takes a launch of B x T frames (else the dense-DFT kernel, which has magnitude mel only)
 bool frontend_takes_fft400(const kws_frontend* h, int B, int T);
 // ... the refusal of `what` ("per-stream chunk lengths") on a handle whose launches go to the dense-DFT kernel

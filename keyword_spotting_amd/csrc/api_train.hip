@@ -50,7 +50,6 @@ namespace {
 
 constexpr size_t kAlign = 256;
 size_t aligned(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
-constexpr int kWgradChunkUnit = 256, kWgradMaxChunks = 64;
 constexpr float kResidualScale = 0.7071067811865475f;      // utils/custom_wrapper.py:116
 
 bool residual_on(const kws_train* h, int l) { return h->res && l >= 1; }
@@ -74,12 +73,6 @@ int train_finish(kws_train* h, hipStream_t st, int rc) {
     if (rc == KWS_OK) return train_leave(h, st);
     if (hipEventRecord(h->last_done, st) == hipSuccess) { h->last_stream = st; h->last_stream_valid = true; }
     return rc;
-}
-
-// the rows of the weight-gradient reduction are summed in at most kWgradMaxChunks chunks of a multiple of kWgradChunkUnit rows
-int wgrad_chunk_rows(size_t rows) {
-    const size_t per = (rows + (size_t)kWgradChunkUnit * kWgradMaxChunks - 1) / ((size_t)kWgradChunkUnit * kWgradMaxChunks);
-    return (int)(kWgradChunkUnit * (per < 1 ? 1 : per));
 }
 
 // Lays the arena out for (B, T, S_max).  base == null: only the size.  Returns the bytes.

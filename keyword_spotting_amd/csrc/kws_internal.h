@@ -579,6 +579,70 @@ hipError_t launch_train_ln_backward(const TrainLnBackward& p, hipStream_t st);
 // out = s (a + b) over n floats (n % 4 == 0, 16-byte aligned blocks); b null: out = s a; out may be a
 hipError_t launch_train_residual(const float* a, const float* b_or_null, float s, float* out, size_t n, hipStream_t st);
 
+// Training of the self-attention CTC model (attention_train_kernels.hip; host: api_attention_train.hip).  Activation blocks are
+// row-major [B*T1, width] fp32, row = b * T1 + t with T1 = T'_max; t1 [B] (device) holds every utterance's T'_b, and a row is live
+// iff t < t1[b].  Every weight product and weight gradient goes through the GEMM / wgrad / reduce / update kernels above.
+//
+// The keep decision of a dropout site (include/kws_amd.h, kws_attention_drop_keep): a counter hash, stateless in
+// (seed, site, layer, b, head, row, col).  thr = floor(keep_prob * 2^32) computed in double by attn_drop_threshold.
+enum { kAttnDropProb = 0, kAttnDropAtt = 1, kAttnDropFfn = 2 };
+__host__ __device__ inline uint64_t attn_drop_threshold(float keep_prob) { return (uint64_t)((double)keep_prob * 4294967296.0); }
+__host__ __device__ inline bool attn_drop_keep(uint64_t seed, int site, int layer, int b, int head, int row, int col, uint64_t thr) {
+    const uint64_t ctr = ((uint64_t)site << 62) | ((uint64_t)layer << 58) | ((uint64_t)head << 52) | ((uint64_t)b << 28) |
+                         ((uint64_t)row << 14) | (uint64_t)col;
+    uint64_t x = seed + ctr * 0x9E3779B97F4A7C15ull;
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    x ^= x >> 31;
+    return (x >> 32) < thr;
+}
+struct AttnTrainDrop { uint64_t seed, thr; float keep_prob; int layer; };      // keep_prob == 1: no hash is evaluated
+// xs [B*T1, c F]: the stacked rows of mel [B, T, F] (tlen [B]: frames T_b; pad frames, frames past T_b and dead rows read as 0)
+hipError_t launch_attn_train_stack(const float* mel, const int32_t* tlen, const int32_t* t1, int B, int T, int T1, int F, int c, float* xs,
+                                   hipStream_t st);
+// x [B*T1, H] += pe[t] on live rows, 0 on dead rows
+hipError_t launch_attn_train_addpe(float* x, const float* pe, const int32_t* t1, int B, int T1, int H, hipStream_t st);
+// v [B*T1, N]: live rows relu(v) (relu != 0) or v, dead rows 0
+hipError_t launch_attn_train_relu(float* v, const int32_t* t1, int B, int T1, int N, int relu, hipStream_t st);
+// g [B*T1, N] = post > 0 on a live row ? g : 0 (tf ReluGrad on the taped output of the relu)
+hipError_t launch_attn_train_relumask(float* g, const float* post, const int32_t* t1, int B, int T1, int N, hipStream_t st);
+struct AttnTrainCore {
+    const float* qkv;       // [B*T1, 3H]
+    const int32_t* t1;
+    float* att;             // [B*T1, H]   forward out / backward in: O = (P o keep / keep_prob) V
+    float* lse;             // [B*T1, NH]  log-sum-exp of the scaled scores
+    const float* datt;      // [B*T1, H]   backward: dO
+    float* dsum;            // [B*T1, NH]  backward: rowsum(dO o O), written by the dq launch, read by the dk/dv launch
+    float* dqkv;            // [B*T1, 3H]  backward out
+    AttnTrainDrop drop;
+    int B, T1, H, NH;
+};
+hipError_t launch_attn_train_core_forward(const AttnTrainCore& p, hipStream_t st);
+hipError_t launch_attn_train_core_dq(const AttnTrainCore& p, hipStream_t st);
+hipError_t launch_attn_train_core_dkv(const AttnTrainCore& p, hipStream_t st);
+// u = (a o keep / keep_prob) + r on live rows (site's mask; 0 on dead rows) and the (count, mean, M2) of each 32-row tile of u
+struct AttnTrainResid {
+    const float *a, *r; const int32_t* t1; float* u; float4* part;      // part [B][ntile]
+    AttnTrainDrop drop; int site, B, T1, H;
+};
+hipError_t launch_attn_train_resid(const AttnTrainResid& p, hipStream_t st);
+// block layer norm over each utterance's [T'_b, H]: the tiles' partials merged in tile order; xn = (u - mean) rstd, y = xn g + bt; rstd [B]
+struct AttnTrainLn {
+    const float* u; const float4* part; const int32_t* t1; const float *g, *bt;
+    float *xn, *y, *rstd; int B, T1, H;
+};
+hipError_t launch_attn_train_ln_forward(const AttnTrainLn& p, hipStream_t st);
+// backward: dy = g1 + g2 (g2 null: g1), prod = dy o xn (the rows' terms of d beta and d gamma), the tiles' (sum dxn, sum dxn o xn)
+// with dxn = dy gamma; then dx = rstd (dxn - mean(dxn) - xn mean(dxn o xn)) and ddrop = dx o keep / keep_prob of `site` (null: not wanted)
+struct AttnTrainLnBwd {
+    const float *g1, *g2, *xn, *rstd, *gamma; const int32_t* t1;
+    float *dy, *prod; float2* sums;      // sums [B][ntile]
+    float *dx, *ddrop;
+    AttnTrainDrop drop; int site, B, T1, H;
+};
+hipError_t launch_attn_train_ln_bwd_sums(const AttnTrainLnBwd& p, hipStream_t st);
+hipError_t launch_attn_train_ln_bwd_apply(const AttnTrainLnBwd& p, hipStream_t st);
+
 // octbit_kernels.hip
 hipError_t launch_octbit_matmul(const float* x, const int8_t* Wq, float scale_w, const float* bias,
                                 float* out, int A, int K, int N, int per_row, float* range_ws,
