@@ -84,7 +84,7 @@ def _create(prec, n_mel, hidden, layers, classes, relu=0, clip=-1.0):
     lib = _lib.load()
     cfg = _lib.KwsConfig(n_mel, hidden, layers, classes, relu, clip, S.PRECISION[prec])
     nbytes = lib.kws_weights_nbytes(ctypes.byref(cfg))
-    blob = np.zeros(max(nbytes // 4, 1), np.float32)
+    blob = np.full(max(nbytes // 4, 1), 0.01, np.float32)       # not zeros: the int8 quantiser refuses an all-zero matrix (scale 0)
     h = ctypes.c_void_p()
     rc = lib.kws_create(ctypes.byref(cfg), blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes, ctypes.byref(h))
     if h.value:
