@@ -855,6 +855,64 @@ int kws_attention_pe_table(kws_attention_handle h, float* host_out);
  * of the contract above; synchronises.  KWS_OK, or KWS_ERR_HIP with the deviation and kws_version(). */
 int kws_attention_selftest(kws_attention_handle h);
 
+/* The self-attention model on live streams: a sliding-window manager for B independent streams, ONE call per chunk and no host work
+ * per stream.  The model carries no state, so "streaming" is what detector.py:158-209 does with its queue of softmax chunks, one stage
+ * earlier: per stream a bounded FIFO of the last `window_chunks` chunks of MEL frames, cleared by the VAD on silence and by a trigger;
+ * after every chunk the model runs over the concatenated window and ctc_decode2 + ctc_predict run over all of its output rows.  The
+ * whole window is recomputed per chunk -- the positional table and the whole-block layer norm make every row depend on the window's
+ * start and content, so nothing can be cached across chunks: a chunk costs one kws_attention_run over up to W frames per stream.
+ * Arrival is per stream, as in kws_stream_feed_ragged: stream b reads the first n_b = n_per_stream[b] samples of row b of `pcm`
+ * [B, n_max]; the lengths stay on the device (no host read, no host wait), are CLAMPED to [0, n_max], NULL means n_max for all;
+ * n_max itself must lie in [0, max_chunk_samples].  Per feed and stream:
+ *   n_b == 0                 the iteration is skipped: carry, window and chunk count stay bitwise as they are, hit[b] = 0, the stream
+ *                            enters the model call with length 0 (an unchanged window that did not fire cannot fire)
+ *   otherwise  VAD           vad(the n_b samples, vad_thres) false -> the window is emptied first                 (:168-177)
+ *              front-end     mel of [carried samples | chunk], keep_b samples carried; carry_b + n_b < fft_size: every sample
+ *                            is carried and the chunk completes zero frames                                      (:179-183)
+ *              window        the chunk's frames (possibly none) take one slot; with window_chunks slots held the OLDEST slot is
+ *                            dropped first with all of its frames (utils/queue.py:26-32, SimpleQueue.add)
+ *              model         exactly kws_attention_run(window, lengths[b] = len_b frames, oldest first), frame stacking and zero pad
+ *                            frames included
+ *              decision      len_b == 0: no row is decoded, hit[b] = 0.  Otherwise ctc_decode2 (the first maximum over classes
+ *                            1..C-2, strictly above decode_thres, repeats collapsed) over the T'_b = frames_out(len_b) rows and
+ *                            hit[b] = `label` occurs in the decoded words (ctc_predict); on a hit the window is emptied (frames and
+ *                            chunk count 0)
+ *   softmax (or NULL)        [B, T'_max, C], T'_max = frames_out(W), W = window_chunks x frames(fft_size - 1 + max_chunk_samples):
+ *                            what that kws_attention_run wrote, i.e. the rows the decision was taken on and zeros past T'_b (a
+ *                            stream of length 0 has T'_b = 0 rows decoded; with combine_frame > 1 the model still writes its one
+ *                            all-pad row)
+ * A call with n_max == 0 skips every stream: hit and softmax are zeroed, nothing else is touched.
+ * The handle BORROWS the attention and front-end handles (a call after either was destroyed: KWS_ERR_INVALID_ARGUMENT) and follows the
+ * attention handle's rules: one host thread at a time (KWS_ERR_BUSY), a stream switch ordered by the handle's event.  It OWNS, per
+ * stream, 2 x (fft_size - 1) carried samples and their lengths, the window of W x n_mel floats and window_chunks + 2 ints -- 86.1 KB
+ * at the reference shape (n_mel 60, 15 chunks of 3600 samples: W = 15 x 23 = 345) -- and nothing else: one chunk's mel, the softmax, the gate's
+ * masks and the model's lengths are carved out of a staging block of the ATTENTION handle that all its managers share; create also
+ * reserves the model's scratch for (B, W), so a feed never allocates.  Both precisions of kws_attention_create_precision are served.
+ * Launches per feed: front-end + gate, window update, the model's 2 + 3 L, decision = 5 + 3 L (kws_attention_stream_stats).
+ * Refused before any device work, each naming the field: B < 1; window_chunks outside 1..64; a label that is empty, longer than 15
+ * or with a digit outside 1..C-2; a null required pointer; handles that are not alive; a front-end that is not the magnitude-mel
+ * 400-point FFT one (MFCC, power 2 and the dataset's framing are whole-utterance transforms; KWS_ERR_UNSUPPORTED); a front-end whose
+ * n_mel differs from the model's; W greater than the model's max_frames (KWS_ERR_UNSUPPORTED). */
+typedef struct kws_attention_stream* kws_attention_stream_handle;
+int kws_attention_stream_create(kws_attention_handle model, kws_frontend_handle frontend, int B, int max_chunk_samples,
+                                int window_chunks, float vad_thres, float decode_thres, const char* label,
+                                kws_attention_stream_handle* out);
+int kws_attention_stream_destroy(kws_attention_stream_handle h);   /* always KWS_OK */
+int kws_attention_stream_feed(kws_attention_stream_handle h, const void* pcm /*[B,n_max] device*/, int n_max,
+                              const int32_t* n_per_stream /*[B] device or NULL = n_max for all*/, int pcm_int16,
+                              int32_t* hit /*[B] device*/, float* softmax /*[B,T'_max,C] device or NULL*/, void* stream);
+/* Every stream b with slots[b] != 0 becomes what a fresh manager's stream is: carry length 0 and an empty window.  The other
+ * streams stay bitwise untouched.  One launch. */
+int kws_attention_stream_recycle(kws_attention_stream_handle h, const uint8_t* slots /*[B] device*/, void* stream);
+/* Inspection, copies only, ordered like a feed: the windows as they stand -- mel [B, W, n_mel] (or NULL), the first frames[b] rows of
+ * stream b oldest first (the rest is unspecified), and the slots held chunks[b] <= window_chunks. */
+int kws_attention_stream_window(kws_attention_stream_handle h, float* mel /*[B,W,n_mel] device or NULL*/, int32_t* frames /*[B] device*/,
+                                int32_t* chunks /*[B] device*/, void* stream);
+/* The carried samples, as kws_stream_carry: samples [B, fft_size - 1], lengths [B], device. */
+int kws_attention_stream_carry(kws_attention_stream_handle h, float* samples, int32_t* lengths, void* stream);
+/* Bytes of device memory the handle owns, and the kernel launches of its last feed (0 after an n_max == 0 call); either may be NULL. */
+int kws_attention_stream_stats(kws_attention_stream_handle h, size_t* device_bytes, int32_t* launches_last_feed);
+
 /* Training of the self-attention CTC model (main.py --model attention; models/attention_ctc.py:131-202): taped forward, backward,
  * tf.nn.ctc_loss, tf.clip_by_global_norm, Adam / Nesterov.  fp32 only.
  *

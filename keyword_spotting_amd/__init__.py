@@ -14,4 +14,13 @@ a compute entry point without the library raises.
 """
 from .config import Config, get_config  # noqa: F401
 
-__all__ = ["Config", "get_config"]
+__all__ = ["Config", "get_config", "AttentionStreamManager", "AttentionHotwordDetector"]
+
+
+def __getattr__(name):
+    # attention_stream.AttentionStreamManager / AttentionHotwordDetector: the self-attention model on live streams.  Resolved on first
+    # use, so importing the package still loads neither torch nor the library.
+    if name in ("AttentionStreamManager", "AttentionHotwordDetector"):
+        from . import attention_stream
+        return getattr(attention_stream, name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -166,6 +166,14 @@ _SIGNATURES = {
     "kws_attention_run": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "kws_attention_pe_table": (_i, [_vp, _vp]),
     "kws_attention_selftest": (_i, [_vp]),
+    # the self-attention model on live streams: the sliding-window manager
+    "kws_attention_stream_create": (_i, [_vp, _vp, _i, _i, _i, _f, _f, ctypes.c_char_p, ctypes.POINTER(_vp)]),
+    "kws_attention_stream_destroy": (_i, [_vp]),
+    "kws_attention_stream_feed": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "kws_attention_stream_recycle": (_i, [_vp, _vp, _vp]),
+    "kws_attention_stream_window": (_i, [_vp, _vp, _vp, _vp, _vp]),
+    "kws_attention_stream_carry": (_i, [_vp, _vp, _vp, _vp]),
+    "kws_attention_stream_stats": (_i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32)]),
     "kws_ctc_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "kws_ctc_beam_search": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "kws_enroll_create": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_vp)]),

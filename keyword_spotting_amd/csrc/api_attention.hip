@@ -9,24 +9,6 @@
 
 using namespace kws_host;
 
-struct kws_attention {
-    kws_attention_config cfg;
-    int precision = KWS_FP32;         // KWS_FP32 or KWS_F16X3: which GEMM image d_w holds and which GEMM kernels run
-    std::vector<float> blob;          // the canonical blob (the self-test's host loop reads it)
-    std::vector<float> pe;            // [pe_rows][H]
-    int pe_rows = 0, KE = 0;
-    float* d_w = nullptr;             // packed weights, biases, LN tables and the positional table: one allocation
-    kws::AttnLayerW layer[8];
-    const float4* w_in = nullptr;
-    const float *b_in = nullptr, *w_out = nullptr, *b_out = nullptr, *d_pe = nullptr;
-    char* scratch = nullptr;          // activations and LN partials; only grows
-    size_t scratch_bytes = 0;
-    std::atomic<int> in_call{0};
-    hipStream_t last_stream = nullptr;
-    bool last_stream_valid = false;
-    hipEvent_t last_done = nullptr;
-};
-
 namespace kws_host {
 
 AttnLayout attn_layout(const kws_attention_config& c) {
@@ -218,6 +200,66 @@ int ensure_scratch(kws_attention_handle h, size_t need) {
 
 }  // namespace
 
+namespace kws_host {
+
+int attn_reserve_locked(kws_attention* h, int B, int T_max) { return ensure_scratch(h, scratch_need(h->cfg, B, T_max, nullptr)); }
+
+int attn_stage_reserve_locked(kws_attention* h, size_t bytes) {
+    if (bytes <= h->stage_bytes) return KWS_OK;
+    KWS_HIP(hipDeviceSynchronize());          // a feed in flight may still use the old block
+    if (h->stage) hipFree(h->stage);
+    h->stage = nullptr;
+    h->stage_bytes = 0;
+    KWS_HIP(hipMalloc(reinterpret_cast<void**>(&h->stage), bytes));
+    h->stage_bytes = bytes;
+    return KWS_OK;
+}
+
+int attn_call_enter(kws_attention* h, hipStream_t st) {
+    if (h->last_stream_valid && st != h->last_stream) KWS_HIP(hipStreamWaitEvent(st, h->last_done, 0));
+    h->last_stream = st;
+    h->last_stream_valid = true;
+    return KWS_OK;
+}
+
+int attn_call_leave(kws_attention* h, hipStream_t st) { return hip_done(hipEventRecord(h->last_done, st), "hipEventRecord"); }
+
+// The model's 2 + 3L launches over B utterances of up to T_max frames (validated by the caller, T'_max > 0), the scratch reserved
+int attn_run_locked(kws_attention* h, const float* mel, const int32_t* lengths, int B, int T_max, float* logits, float* softmax,
+                    hipStream_t st) {
+    const kws_attention_config& c = h->cfg;
+    int Tp = 0;
+    if (scratch_need(c, B, T_max, &Tp) > h->scratch_bytes) return fail(KWS_ERR_INVALID_ARGUMENT, "internal: the attention scratch was not reserved");
+    const int H = c.hidden;
+    kws::AttnParams p{};
+    p.mel = mel;
+    p.lengths = lengths;
+    p.B = B, p.T_max = T_max, p.F = c.n_mel, p.c = c.combine_frame, p.KE = h->KE;
+    p.T1max = frames_out(c, T_max), p.Tp = Tp, p.ntile = Tp / kws::kAttnRows;
+    p.Fi = c.ffn_inner, p.C = c.num_classes, p.use_relu = c.use_relu;
+    p.w_in = h->w_in, p.b_in = h->b_in, p.pe = h->d_pe, p.w_out = h->w_out, p.b_out = h->b_out;
+    float* s = reinterpret_cast<float*>(h->scratch);
+    const size_t act = (size_t)B * Tp * H;
+    p.S = s, p.QKV = s + act, p.U = s + 4 * act;
+    p.st_a = reinterpret_cast<float4*>(s + 5 * act);
+    p.st_b = p.st_a + (size_t)B * p.ntile;
+    p.logits = logits, p.softmax = softmax;
+
+    // the three GEMM kernels in the handle's precision; the core and the output kernel are fp32 for both
+    const bool f16 = h->precision == KWS_F16X3;
+    hipError_t e = f16 ? kws::launch_attn_embed_f16x3(p, H, st) : kws::launch_attn_embed(p, H, st);
+    for (int l = 0; l < c.num_layers && e == hipSuccess; ++l) {
+        const kws::AttnLayerW* prev = l > 0 ? &h->layer[l - 1] : nullptr;
+        e = f16 ? kws::launch_attn_qkv_f16x3(p, h->layer[l], prev, H, st) : kws::launch_attn_qkv(p, h->layer[l], prev, H, st);
+        if (e == hipSuccess) e = kws::launch_attn_core(p, prev, H, H / c.num_heads, st);
+        if (e == hipSuccess) e = f16 ? kws::launch_attn_ffn_f16x3(p, h->layer[l], H, st) : kws::launch_attn_ffn(p, h->layer[l], H, st);
+    }
+    if (e == hipSuccess) e = kws::launch_attn_out(p, h->layer[c.num_layers - 1], H, st);
+    return hip_done(e, "attention kernel launch");
+}
+
+}  // namespace kws_host
+
 extern "C" {
 
 size_t kws_sizeof_attention_config(void) { return sizeof(kws_attention_config); }
@@ -333,15 +375,18 @@ int kws_attention_create_precision(const kws_attention_config* cfg, int precisio
             return rc;
         }
     }
+    live_register(m);      // stream managers borrow the handle (kws_attention_stream_create)
     *out = m;
     return KWS_OK;
 }
 
 int kws_attention_destroy(kws_attention_handle h) {
     if (!h) return KWS_OK;
+    live_unregister(h);
     hipDeviceSynchronize();
     if (h->d_w) hipFree(h->d_w);
     if (h->scratch) hipFree(h->scratch);
+    if (h->stage) hipFree(h->stage);
     if (h->last_done) hipEventDestroy(h->last_done);
     delete h;
     return KWS_OK;
@@ -353,7 +398,7 @@ int kws_attention_reserve(kws_attention_handle h, int B, int T_max) {
     if (!busy.owned) return fail(KWS_ERR_BUSY, "kws_attention_reserve: another host thread is inside a call on this handle");
     if (B < 0 || T_max < 0) return fail(KWS_ERR_INVALID_ARGUMENT, "negative B=%d or T_max=%d", B, T_max);
     if (T_max > h->cfg.max_frames) return fail(KWS_ERR_UNSUPPORTED, "T_max=%d exceeds max_frames=%d", T_max, h->cfg.max_frames);
-    return ensure_scratch(h, scratch_need(h->cfg, B, T_max, nullptr));
+    return attn_reserve_locked(h, B, T_max);
 }
 
 int kws_attention_run(kws_attention_handle h, const float* mel, const int32_t* lengths, int B, int T_max, float* logits,
@@ -364,49 +409,17 @@ int kws_attention_run(kws_attention_handle h, const float* mel, const int32_t* l
     if (T_max > c.max_frames) return fail(KWS_ERR_UNSUPPORTED, "T_max=%d exceeds max_frames=%d", T_max, c.max_frames);
     if (B > 65535) return fail(KWS_ERR_UNSUPPORTED, "B=%d unsupported (<= 65535)", B);
     if (!logits && !softmax) return fail(KWS_ERR_INVALID_ARGUMENT, "logits and softmax are both null");
-    const int T1max = frames_out(c, T_max);
-    if (B == 0 || T1max == 0) return KWS_OK;
+    if (B == 0 || frames_out(c, T_max) == 0) return KWS_OK;
     if (!mel && T_max > 0) return fail(KWS_ERR_INVALID_ARGUMENT, "mel is null");
     BusyGuard busy(h->in_call);
     if (!busy.owned)
         return fail(KWS_ERR_BUSY, "kws_attention_run: another host thread is inside a call on this handle (one thread at a time per handle)");
     const hipStream_t st = static_cast<hipStream_t>(stream);
-    int Tp = 0;
-    int rc = ensure_scratch(h, scratch_need(c, B, T_max, &Tp));
-    if (rc != KWS_OK) return rc;
-    if (h->last_stream_valid && st != h->last_stream) KWS_HIP(hipStreamWaitEvent(st, h->last_done, 0));
-    h->last_stream = st;
-    h->last_stream_valid = true;
-
-    const int H = c.hidden;
-    kws::AttnParams p{};
-    p.mel = mel;
-    p.lengths = lengths;
-    p.B = B, p.T_max = T_max, p.F = c.n_mel, p.c = c.combine_frame, p.KE = h->KE;
-    p.T1max = T1max, p.Tp = Tp, p.ntile = Tp / kws::kAttnRows;
-    p.Fi = c.ffn_inner, p.C = c.num_classes, p.use_relu = c.use_relu;
-    p.w_in = h->w_in, p.b_in = h->b_in, p.pe = h->d_pe, p.w_out = h->w_out, p.b_out = h->b_out;
-    float* s = reinterpret_cast<float*>(h->scratch);
-    const size_t act = (size_t)B * Tp * H;
-    p.S = s, p.QKV = s + act, p.U = s + 4 * act;
-    p.st_a = reinterpret_cast<float4*>(s + 5 * act);
-    p.st_b = p.st_a + (size_t)B * p.ntile;
-    p.logits = logits, p.softmax = softmax;
-
-    // the three GEMM kernels in the handle's precision; the core and the output kernel are fp32 for both
-    const bool f16 = h->precision == KWS_F16X3;
-    hipError_t e = f16 ? kws::launch_attn_embed_f16x3(p, H, st) : kws::launch_attn_embed(p, H, st);
-    for (int l = 0; l < c.num_layers && e == hipSuccess; ++l) {
-        const kws::AttnLayerW* prev = l > 0 ? &h->layer[l - 1] : nullptr;
-        e = f16 ? kws::launch_attn_qkv_f16x3(p, h->layer[l], prev, H, st) : kws::launch_attn_qkv(p, h->layer[l], prev, H, st);
-        if (e == hipSuccess) e = kws::launch_attn_core(p, prev, H, H / c.num_heads, st);
-        if (e == hipSuccess) e = f16 ? kws::launch_attn_ffn_f16x3(p, h->layer[l], H, st) : kws::launch_attn_ffn(p, h->layer[l], H, st);
-    }
-    if (e == hipSuccess) e = kws::launch_attn_out(p, h->layer[c.num_layers - 1], H, st);
-    const hipError_t er = hipEventRecord(h->last_done, st);   // also after a failure: what was queued is what the next call waits for
-    if (e != hipSuccess) return hip_fail(e, "attention kernel launch");
-    if (er != hipSuccess) return hip_fail(er, "hipEventRecord");
-    return KWS_OK;
+    KWS_TRY(attn_reserve_locked(h, B, T_max));
+    KWS_TRY(attn_call_enter(h, st));
+    const int rc = attn_run_locked(h, mel, lengths, B, T_max, logits, softmax, st);
+    const int rl = attn_call_leave(h, st);      // also after a failure: what was queued is what the next call waits for
+    return rc != KWS_OK ? rc : rl;
 }
 
 int kws_attention_pe_table(kws_attention_handle h, float* host_out) {

@@ -1,5 +1,5 @@
 // Host-side state and helpers shared by the C ABI translation units of libkws_amd.so: one api_*.hip per surface (model, step, ops,
-// attention, window, frontend, stream -- which drives the two before it through kws_host --, enroll, bank), weight_pack.hip, selftest.hip.  Never
+// attention, attention_stream, window, frontend, stream -- which drives the two before it through kws_host --, enroll, bank), weight_pack.hip, selftest.hip.  Never
 // included by a kernel file: the kernel/host surface is kws_internal.h.
 #pragma once
 #include <algorithm>
@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "kws_internal.h"
+#include "attention_internal.h"
 
 // Helpers shared across the host files; hidden, so the library's dynamic symbol table holds the C ABI and the kernels only.
 #pragma GCC visibility push(hidden)
@@ -225,6 +226,16 @@ struct AttnLayout {
 };
 AttnLayout attn_layout(const kws_attention_config& c);
 bool attn_config_ok(const kws_attention_config* c, int* code);      // false: *code is the failure, kws_last_error names the field
+// ... kws_attention_run for a caller that already holds the handle (kws_attention::in_call; api_attention_stream.hip): the scratch of
+// a call shape and the staging block of the stream managers (both only grow; growing synchronises), the ordering of a call against
+// the handle's previous one (attn_call_enter waits for last_done on a stream switch, attn_call_leave records it), and the model's
+// 2 + 3L launches themselves -- arguments validated by the caller, the scratch reserved
+int attn_reserve_locked(kws_attention* h, int B, int T_max);
+int attn_stage_reserve_locked(kws_attention* h, size_t bytes);
+int attn_call_enter(kws_attention* h, hipStream_t st);
+int attn_call_leave(kws_attention* h, hipStream_t st);
+int attn_run_locked(kws_attention* h, const float* mel, const int32_t* lengths, int B, int T_max, float* logits, float* softmax,
+                    hipStream_t st);
 
 // api_frontend.hip: the 400-point FFT kernel takes a launch of B x T frames (else the dense-DFT kernel, which has magnitude mel only)
 bool frontend_takes_fft400(const kws_frontend* h, int B, int T);
@@ -353,6 +364,29 @@ struct kws_model {
         }
         return out;
     }
+};
+
+struct kws_attention {
+    kws_attention_config cfg;
+    int precision = KWS_FP32;         // KWS_FP32 or KWS_F16X3: which GEMM image d_w holds and which GEMM kernels run
+    std::vector<float> blob;          // the canonical blob (the self-test's host loop reads it)
+    std::vector<float> pe;            // [pe_rows][H]
+    int pe_rows = 0, KE = 0;
+    float* d_w = nullptr;             // packed weights, biases, LN tables and the positional table: one allocation
+    kws::AttnLayerW layer[8];
+    const float4* w_in = nullptr;
+    const float *b_in = nullptr, *w_out = nullptr, *b_out = nullptr, *d_pe = nullptr;
+    char* scratch = nullptr;          // activations and LN partials; only grows
+    size_t scratch_bytes = 0;
+    // Staging of the stream managers that borrow this handle (kws_attention_stream_feed): one chunk's mel, the softmax, the gate's masks
+    // and the lengths the model runs over.  They live only inside a feed and feeds of one handle are ordered, so every manager on the
+    // handle carves the same block, as the GRU managers do with kws_model::stage.  Grows at kws_attention_stream_create only.
+    char* stage = nullptr;
+    size_t stage_bytes = 0;
+    std::atomic<int> in_call{0};
+    hipStream_t last_stream = nullptr;
+    bool last_stream_valid = false;
+    hipEvent_t last_done = nullptr;
 };
 
 struct kws_window {

@@ -61,4 +61,39 @@ hipError_t launch_attn_embed_f16x3(const AttnParams& p, int H, hipStream_t st);
 hipError_t launch_attn_qkv_f16x3(const AttnParams& p, const AttnLayerW& w, const AttnLayerW* prev, int H, hipStream_t st);
 hipError_t launch_attn_ffn_f16x3(const AttnParams& p, const AttnLayerW& w, int H, hipStream_t st);
 
+// ---- the sliding-window manager (attention_stream_kernels.hip, api_attention_stream.hip).  Per stream the manager owns a LINEAR
+// window win[b] = [W][F] mel frames, oldest first, of which the first len[b] are live, and the frame counts of its count[b] <= nq
+// slots (chunks), oldest first: slot_frames[b][0 .. count[b]).  W = nq x the frames of the longest chunk, so a slot always fits.
+
+// Behind the front-end's ragged gate launch (frames / skip / silent are its outputs; mel [B][T][F] the chunk's frames).  Per stream:
+// skip -> nothing but run_len[b] = 0; else clear on silent, drop the oldest slot with its frames when nq slots are held
+// (SimpleQueue.add), append the chunk's frames as the newest slot; run_len[b] = len[b], the length the model runs over.
+struct AttnStreamWindowParams {
+    const float* mel;
+    const int32_t* frames;
+    const uint8_t *skip, *silent;
+    float* win;
+    int32_t *slot_frames, *count, *len, *run_len;
+    int B, T, W, F, nq;
+};
+// Behind the model: ctc_decode2's frame rule over the T'_b = frames_out(run_len[b]) softmax rows (none where run_len[b] == 0), repeats
+// collapsed, the label's matcher (window_label_delta) over the emitted words; hit[b]; a hit empties the window (count, len = 0).
+struct AttnStreamDecideParams {
+    const float* softmax;   // [B][T1max][C]
+    const int32_t* run_len;
+    int32_t *count, *len, *hit;
+    int B, T1max, C, c, n_label;
+    float thres;
+    uint8_t delta[256];
+};
+// kws_attention_stream_recycle: slots[b] != 0 -> carry length 0, empty window
+struct AttnStreamRecycleParams {
+    const uint8_t* slots;
+    int32_t *carry_len, *count, *len;
+    int B;
+};
+hipError_t launch_attn_stream_window(const AttnStreamWindowParams& p, hipStream_t st);
+hipError_t launch_attn_stream_decide(const AttnStreamDecideParams& p, hipStream_t st);
+hipError_t launch_attn_stream_recycle(const AttnStreamRecycleParams& p, hipStream_t st);
+
 }  // namespace kws
