@@ -330,6 +330,7 @@ void set_octbit_fc(kws::OctbitFcParams& fp, const kws_model* h, const StepArgs& 
     fp.bfc = h->d_weights + h->pk.bfc_off;
     fp.scale_w = h->pk.oct_scale_fc;
     fp.h_top = h->scratch[top % h->nscratch];
+    fp.seq_len = a.seq_len;
     fp.range = h->oct_range;
     fp.range_ready = h->pk.oct[top].quantised ? 1 : 0;
     fp.prev_in = a.prev_word ? h->oct_prev : nullptr;

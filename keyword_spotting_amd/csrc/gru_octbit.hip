@@ -377,13 +377,18 @@ __global__ void __launch_bounds__(512) gru_layer_octbit_kernel(const GruOctbitPa
     }
 }
 
-// per-stream range of the call's [T, H] top-layer block (the projection's one op call, :92-99)
-__global__ void __launch_bounds__(512) octbit_top_range_kernel(const float4* __restrict__ h_top, int T, float2* __restrict__ range) {
+// per-stream range of the call's [T, H] top-layer block (the projection's one op call, :92-99).  The fp32 layer that wrote the
+// seam stores its carried state for frames t >= seq_len[b], where dynamic_rnn emits the zero row: those rows are taken as
+// zero rows here, as gru_layer_octbit_kernel tracks its range (and a stream that is not in the batch has none).
+__global__ void __launch_bounds__(512) octbit_top_range_kernel(const float4* __restrict__ h_top, const int32_t* __restrict__ seq_len,
+                                                               int B, int T, float2* __restrict__ range) {
     __shared__ float rmn[8][16], rmx[8][16];
     const int tid = threadIdx.x, n = tid >> 6, lane = tid & 63, G = blockIdx.x;
+    const int b = G * 16 + (lane & 15);
+    const int len = b < B ? (seq_len ? seq_len[b] : T) : 0;
     float mn = 3.402823466e+38f, mx = -3.402823466e+38f;
     const float4* src = h_top + ((size_t)G * T * 8 + n) * 64 + lane;
-    for (int t = 0; t < T; ++t) {
+    for (int t = 0; t < T && t < len; ++t) {
         const float4 v = src[(size_t)t * 8 * 64];
         mn = fminf(mn, fminf(fminf(v.x, v.y), fminf(v.z, v.w)));
         mx = fmaxf(mx, fmaxf(fmaxf(v.x, v.y), fmaxf(v.z, v.w)));
@@ -395,6 +400,7 @@ __global__ void __launch_bounds__(512) octbit_top_range_kernel(const float4* __r
     if (tid < 16) {
 #pragma unroll
         for (int k = 1; k < 8; ++k) { mn = fminf(mn, rmn[k][tid]); mx = fmaxf(mx, rmx[k][tid]); }
+        if (len < T) { mn = fminf(mn, 0.f); mx = fmaxf(mx, 0.f); }          // finished frames emit the zero row
         range[G * 16 + tid] = make_float2(mn, mx);
     }
 }
@@ -419,12 +425,15 @@ __global__ void __launch_bounds__(512) octbit_fc_kernel(const OctbitFcParams p) 
         range_to_scale(r.x, r.y, bscale, is_signed);
     }
     const float off = is_signed ? 127.0f : 0.0f;
+    // rows past seq_len are zero rows whatever the seam holds there (an fp32 top layer stores its carried state, dense_heads.hip)
+    const int len = b < p.B ? (p.seq_len ? p.seq_len[b] : T) : 0;
     __syncthreads();
     // frame slot f <-> frame t0 - 1 + f; slot 0 is the halo that supplies the previous word
     for (int f = (t0 == 0 ? 1 : 0); f <= kFcFrames; ++f) {
         const int t = t0 - 1 + f;
         if (t >= T) break;
-        const float4 v = p.h_top[(((size_t)G * T + t) * 8 + n) * 64 + lane];
+        float4 v = p.h_top[(((size_t)G * T + t) * 8 + n) * 64 + lane];
+        if (t >= len) v = make_float4(0.f, 0.f, 0.f, 0.f);
         const uint32_t q0 = quant_u8(v.x, bscale, off), q1 = quant_u8(v.y, bscale, off);
         const uint32_t q2 = quant_u8(v.z, bscale, off), q3 = quant_u8(v.w, bscale, off);
         const uint32_t ae = q0 | (q2 << 16), ao = q1 | (q3 << 16);
@@ -491,7 +500,7 @@ hipError_t launch_gru_layer_octbit(const GruOctbitParams& p, hipStream_t st) {
 hipError_t launch_octbit_fc(const OctbitFcParams& p, hipStream_t st) {
     const int groups = groups_of(p.B);
     if (!p.range_ready) {        // top layer ran on the fp32 kernels (one-layer models): scan its rows
-        const hipError_t e = launch_lds<octbit_top_range_kernel>(dim3(groups), dim3(512), 0, st, p.h_top, p.T, p.range);
+        const hipError_t e = launch_lds<octbit_top_range_kernel>(dim3(groups), dim3(512), 0, st, p.h_top, p.seq_len, p.B, p.T, p.range);
         if (e != hipSuccess) return e;
     }
     return launch_lds<octbit_fc_kernel>(dim3(groups, (p.T + kFcFrames - 1) / kFcFrames), dim3(512), 0, st, p);

@@ -213,6 +213,7 @@ struct OctbitFcParams {
     const float* bfc;       // [16] padded
     float scale_w;
     const float4* h_top;    // top layer output, xl layout
+    const int32_t* seq_len; // rows t >= seq_len[b] are zero rows, whatever the seam holds (or null)
     float2* range;          // [G*16] (min, max) of each stream's [T,H] block
     int range_ready;        // the top int8 layer already produced it
     const int32_t* prev_in; // copy of prev_word taken before the launch (or null)

@@ -37,7 +37,10 @@ def _octbit_cell(lay, x, h):
 @pytest.mark.parametrize("wscale,batch", [(1.0, 64), (8.0, 37)])
 def test_single_step_is_exact_given_the_same_fp32_inputs(wscale, batch):
     """T = 1: layer 1 sees x = new layer-0 state and the projection sees h' = new layer-1 state, both returned by
-    the call -- so the oracle can be fed the very same floats.  wscale = 8 makes most pair sums saturate."""
+    the call -- so the oracle can be fed the very same floats.  wscale = 8 scales layer 1's pre-activations by 8 (the output
+    scale of the op) and NOT the share of pair sums that saturate: the weight quantiser divides by the matrix's own maximum, so
+    W_q is the same with and without the factor (about 0.7 % of the pair sums clip on either side).  The clip-heavy family of
+    tests/test_gpu_octbit_step.py drives the int16 clamp."""
     w = G.random_weights(40, 128, 2, 6, seed=301)
     w["layers"][1]["Wg"] = (w["layers"][1]["Wg"] * wscale).astype(np.float32)
     w["layers"][1]["Wc"] = (w["layers"][1]["Wc"] * wscale).astype(np.float32)
