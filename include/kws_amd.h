@@ -683,7 +683,7 @@ int kws_step_bank_window(kws_handle model, kws_bank_handle bank, const int32_t* 
  * under tf.nn.ctc_loss, with tf.clip_by_global_norm and tf.train.AdamOptimizer or MomentumOptimizer(0.9, use_nesterov=True).  A train
  * handle owns the parameters (the canonical blob of kws_weights_nbytes, on the device), the optimiser's moments and the step count.
  *
- * The graph of one step, from the zero state (initial_state=None):
+ * The graph of one step, from the zero state (initial_state=None; from a carried state: kws_train_grad_state, below):
  *   layer l     TF 1.x GRUCell as kws_step computes it: [r,u] = sigma([x,h].Wg + bg), c = tanh([x, r o h].Wc + bc), h' = u o h + (1-u) o c;
  *               dynamic_rnn(sequence_length): at t >= seq_len[b] the state is copied and the output is 0
  *   dropout     DropoutWrapper(output_keep_prob): the layer's output is y = h' o mask / keep_prob, the carried state the undropped h'.
@@ -751,7 +751,40 @@ int kws_step_bank_window(kws_handle model, kws_bank_handle bank, const int32_t* 
  * Refused before the device is touched (KWS_ERR_INVALID_ARGUMENT): null pointers, B or T < 1, S_max outside [0, 31], labels / lengths out
  * of range, lr not positive and finite, pointers (drop included) not 4-byte aligned; KWS_ERR_UNSUPPORTED: 4 T (8 + 2 S_max + 1) bytes of LDS above 160 KiB,
  * as kws_ctc_loss.  One host thread at a time per handle (KWS_ERR_BUSY); a call on another stream than the previous one is ordered behind
- * it by the handle's event; no call synchronises the device in the steady state. */
+ * it by the handle's event; no call synchronises the device in the steady state.
+ *
+ * Carried states (kws_train_grad_state / kws_train_step_state; kws_train_state_io below).  The graph above starts every layer from
+ * state_in[l] in the place of zeros (initial_state of models/rnn_ctc.py:202-244) and hands out state_out[l], the state of layer l after
+ * frame seq_len[b] - 1: [L,B,H] fp32 on the device as kws_step's, the carried state the undropped h' (dropout, above).  The objective is
+ *   J = sum_b ctc_b / B + <dstate_out, state_out>
+ * with dstate_out [L,B,H] the gradient of whatever the caller computes from state_out (NULL: zeros).  grad_blob is dJ / d parameters and
+ * dstate_in [L,B,H] is dJ / d state_in: the backward loop's dh starts from dstate_out[l] and what is left of it in front of frame 0 is
+ * dstate_in[l].  The formulas do not change; the h of frame 0 is state_in.
+ *   chains      a recording cut into segments: run segment A, run B from A's state_out, run A again with dstate_out = B's dstate_in; the sum
+ *               of the two grad_blobs is the gradient of the whole recording's loss, A's dstate_in that of A's state_in (A's forward runs
+ *               twice: 1.5 x the cost of one pass).  Forward alone, A then B gives the logits and the final state of one call bit for bit:
+ *               no frame's arithmetic depends on T.
+ *   seq_len     a stream with seq_len[b] == 0, and every stream of a workgroup that runs no frame, copies state_in[b] to state_out[b] and
+ *               dstate_out[b] to dstate_in[b] bit for bit.  Rows b >= B do not exist: nothing is written behind [L,B,H].
+ *   no path     an utterance without a CTC path still adds exactly 0 from its loss; its state_out is computed and dstate_out still flows
+ *               back through its frames into grad_blob and dstate_in.
+ *   wrappers    both kinds of handle take the calls; layer norm, residual and dropout never touch the state.
+ *   pointers    each of the four may be NULL; state_out may be state_in and dstate_in may be dstate_out (a lane reads its 16 bytes before
+ *               the frame loop and writes the same 16 bytes behind it); no other overlap.  Each must be 16-byte aligned
+ *               (KWS_ERR_INVALID_ARGUMENT naming the field, before the device is touched).
+ * io == NULL, or all four fields NULL, is kws_train_grad / kws_train_step: the same launches, the same bits.  Otherwise the two frame loops of
+ * every layer run in their state form: as many launches as the plain call (kws_train_stats), the loads and stores outside the frame
+ * loops.  kws_train_step_state applies the gradient of J, dstate_out included.  Every refusal, KWS_ERR_BUSY, the ordering across streams
+ * and "nothing synchronises in the steady state" are the plain calls'.
+ * kws_train_check_state   the refusals of kws_train_create (wrapped != 0: of kws_train_create_wrapped) and of a _state call with this io,
+ *                    from host memory alone.
+ * kws_train_apply    one optimiser step from a gradient the caller supplies (device, the blob's layout and size; the sum of a chain's
+ *                    gradients, of accumulated batches or of several devices): tf.clip_by_global_norm over it, then Adam or Nesterov with
+ *                    the handle's moments and step count, then the packed weights -- what kws_train_step does behind its own gradient, bit
+ *                    for bit when fed kws_train_grad's.  grad_norm as kws_train_step's.  Refused: NULL grad_blob, lr not positive and
+ *                    finite, pointers not 4-byte aligned.  Three launches.
+ * Out of scope: a learned initial state owned by the handle (the stream managers reset to zeros on the device: serving one would touch
+ * every serving kernel family), the attention trainer, anything but fp32. */
 enum { KWS_OPT_ADAM = 0, KWS_OPT_NESTEROV = 1 };
 typedef struct kws_train_config {
     kws_config model;
@@ -779,6 +812,22 @@ int kws_train_step(kws_train_handle h, const float* x, const int32_t* seq_len, c
                    int S_max, const uint8_t* drop_or_null, float lr, float* loss, float* grad_norm_or_null, void* stream);
 int kws_train_moments(kws_train_handle h, float* m /*host*/, float* v /*host*/, void* stream);
 int kws_train_stats(kws_train_handle h, size_t* device_bytes, int32_t* allocs, int32_t* steps, int32_t* launches, int32_t* chunk_rows);
+typedef struct kws_train_state_io {
+    const float* state_in;    /* [L,B,H] f32 device, or NULL = the zero state */
+    float*       state_out;   /* [L,B,H] out, or NULL; may alias state_in */
+    const float* dstate_out;  /* [L,B,H] device, or NULL = zeros: gradient of the caller's objective w.r.t. state_out */
+    float*       dstate_in;   /* [L,B,H] out, or NULL; may alias dstate_out */
+} kws_train_state_io;
+size_t kws_sizeof_train_state_io(void);
+int kws_train_grad_state(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
+                         int T, int S_max, const uint8_t* drop_or_null, float* loss, float* grad_blob, float* logits_or_null,
+                         const kws_train_state_io* io_or_null, void* stream);
+int kws_train_step_state(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
+                         int T, int S_max, const uint8_t* drop_or_null, float lr, float* loss, float* grad_norm_or_null,
+                         const kws_train_state_io* io_or_null, void* stream);
+int kws_train_check_state(const kws_train_config* cfg, int wrapped, const float* x, const int32_t* seq_len, const int32_t* labels,
+                          const int32_t* label_len, int B, int T, int S_max, const float* loss, const kws_train_state_io* io);
+int kws_train_apply(kws_train_handle h, const float* grad_blob /*device, blob layout*/, float lr, float* grad_norm_or_null, void* stream);
 
 /* OctbitMatMul: out[A,N] = (sum_k u8(x)[a,k] * Wq[n,k] - signed*bias[n]) * scale_w * s_x.
  *   x [A,K] f32, Wq [N,K] s8 (pre-transposed), bias [N] f32, out [A,N] f32.  K % 64 == 0, scale_w > 0.

@@ -54,6 +54,12 @@ class KwsTrainConfig(ctypes.Structure):
                 ("optimizer", ctypes.c_int32), ("max_grad_norm", ctypes.c_float), ("keep_prob", ctypes.c_float)]
 
 
+class KwsTrainStateIo(ctypes.Structure):
+    """kws_train_state_io: the carried states of a kws_train_grad_state / kws_train_step_state call, [L,B,H] f32 device pointers, 16-byte
+    aligned, each may be NULL -- state_in (NULL: zeros), state_out, dstate_out (NULL: zeros), dstate_in."""
+    _fields_ = [("state_in", ctypes.c_void_p), ("state_out", ctypes.c_void_p), ("dstate_out", ctypes.c_void_p), ("dstate_in", ctypes.c_void_p)]
+
+
 class KwsHeadIo(ctypes.Structure):
     """kws_head_io: one class head's outputs in kws_step_heads -- logits / softmax [B,T,C_i], tokens [B,T], prev_word [B] (device
     pointers, each may be NULL; tokens needs prev_word) and the head's ctc_decode2 threshold."""
@@ -198,6 +204,12 @@ _SIGNATURES = {
     "kws_train_moments": (_i, [_vp, _vp, _vp, _vp]),
     "kws_train_stats": (_i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                              ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
+    # ... from and to carried states, and the optimiser step from a gradient the caller supplies
+    "kws_sizeof_train_state_io": (ctypes.c_size_t, []),
+    "kws_train_grad_state": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.POINTER(KwsTrainStateIo), _vp]),
+    "kws_train_step_state": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _vp, _vp, ctypes.POINTER(KwsTrainStateIo), _vp]),
+    "kws_train_check_state": (_i, [ctypes.POINTER(KwsTrainConfig), _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, ctypes.POINTER(KwsTrainStateIo)]),
+    "kws_train_apply": (_i, [_vp, _vp, _f, _vp, _vp]),
     # training of the self-attention CTC model: taped forward, backward, CTC loss, clip, Adam / Nesterov; the dropout hash on the host
     "kws_sizeof_attention_train_config": (ctypes.c_size_t, []),
     "kws_attention_train_create": (_i, [ctypes.POINTER(KwsAttentionTrainConfig), ctypes.POINTER(_vp)]),
@@ -250,6 +262,7 @@ def load():
                 lib.kws_sizeof_dataset_config() != ctypes.sizeof(KwsDatasetConfig) or \
                 lib.kws_sizeof_attention_config() != ctypes.sizeof(KwsAttentionConfig) or \
                 lib.kws_sizeof_train_config() != ctypes.sizeof(KwsTrainConfig) or \
+                lib.kws_sizeof_train_state_io() != ctypes.sizeof(KwsTrainStateIo) or \
                 lib.kws_sizeof_attention_train_config() != ctypes.sizeof(KwsAttentionTrainConfig) or \
                 lib.kws_sizeof_head_io() != ctypes.sizeof(KwsHeadIo):
             raise ImportError("%s was built from a different include/kws_amd.h than this binding (struct sizes differ); "

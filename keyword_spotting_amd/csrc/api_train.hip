@@ -183,13 +183,29 @@ int check_call(const kws_train_config& cfg, const float* x, const int32_t* seq_l
     return KWS_OK;
 }
 
+// the state pointers of a kws_train_*_state call: the kernels read and write a stream's state 16 bytes at a time
+int check_state_io(const kws_train_state_io* io) {
+    if (!io) return KWS_OK;
+    const struct { const char* name; const void* p; } f[4] = {{"state_in", io->state_in}, {"state_out", io->state_out},
+                                                            {"dstate_out", io->dstate_out}, {"dstate_in", io->dstate_in}};
+    for (const auto& e : f)
+        if (reinterpret_cast<uintptr_t>(e.p) % 16 != 0)
+            return fail(KWS_ERR_INVALID_ARGUMENT, "io->%s must be 16-byte aligned (a lane moves four units of a stream's state at a time)", e.name);
+    return KWS_OK;
+}
+// a call from or to a carried state: any of the four fields set (none: the plain call, its launches and its bits)
+bool carries_state(const kws_train_state_io* io) { return io && (io->state_in || io->state_out || io->dstate_out || io->dstate_in); }
+
 #define KWS_LAUNCH(h, call, what) do { KWS_TRY(hip_done((call), what)); ++(h)->launches; } while (0)
 
-// forward, loss, backward: leaves loss [B], the logits and the gradient of sum(loss) / B (h->grad, with the sums of squares of its blocks)
+// forward, loss, backward: leaves loss [B], the logits and the gradient of sum(loss) / B + <dstate_out, state_out> (h->grad, with the sums
+// of squares of its blocks); io: null or all null for the zero state and no state outputs
 int grad_impl(kws_train* h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int S_max,
-              const uint8_t* drop, float* loss, hipStream_t st) {
+              const uint8_t* drop, float* loss, const kws_train_state_io* io, hipStream_t st) {
     const kws_config& c = h->cfg.model;
     const int H = c.hidden, C = c.num_classes, L = c.num_layers, M = B * T;
+    const bool stateful = carries_state(io);
+    const size_t state_layer = (size_t)B * H;          // floats of one layer of [L, B, H]
     KWS_TRY(prepare_shape(h, B, T, S_max));
     kws_train::Carved& cv = h->cv;
     if (h->jobs_dirty) {
@@ -227,7 +243,15 @@ int grad_impl(kws_train* h, const float* x, const int32_t* seq_len, const int32_
         f.xg = cv.xg; f.wh = pk.wh; f.seq_len = d_seq; f.drop = drop ? drop + (size_t)l * drop_layer : nullptr;
         f.drop_bs = drop_bs; f.drop_ts = drop_ts;
         f.ar = y.ar; f.au = y.au; f.ac = y.ac; f.hp = y.hp; f.rh = y.rh; f.y = y.y; f.keep_prob = h->cfg.keep_prob; f.B = B; f.T = T;
-        KWS_LAUNCH(h, kws::launch_gru_train_forward(f, H, st), "launch gru_train_forward");
+        if (stateful) {
+            kws::TrainForwardStateParams fs = {};
+            static_cast<kws::TrainForwardParams&>(fs) = f;
+            fs.io.in = io->state_in ? io->state_in + l * state_layer : nullptr;
+            fs.io.out = io->state_out ? io->state_out + l * state_layer : nullptr;
+            KWS_LAUNCH(h, kws::launch_gru_train_forward_state(fs, H, st), "launch gru_train_forward_state");
+        } else {
+            KWS_LAUNCH(h, kws::launch_gru_train_forward(f, H, st), "launch gru_train_forward");
+        }
         if (residual_on(h, l))          // both operands are zero rows at t >= seq_len: so is out
             KWS_LAUNCH(h, kws::launch_train_residual(y.y, in, kResidualScale, y.out, (size_t)M * H, st), "launch train_residual (forward)");
     }
@@ -258,7 +282,15 @@ int grad_impl(kws_train* h, const float* x, const int32_t* seq_len, const int32_
         b.dy = cv.dy[cur]; b.wht = pk.wht; b.seq_len = d_seq; b.drop = drop ? drop + (size_t)l * drop_layer : nullptr;
         b.drop_bs = drop_bs; b.drop_ts = drop_ts;
         b.ar = y.ar; b.au = y.au; b.ac = y.ac; b.hp = y.hp; b.dhat = y.dhat; b.keep_prob = h->cfg.keep_prob; b.B = B; b.T = T;
-        KWS_LAUNCH(h, kws::launch_gru_train_backward(b, H, st), "launch gru_train_backward");
+        if (stateful) {
+            kws::TrainBackwardStateParams bs = {};
+            static_cast<kws::TrainBackwardParams&>(bs) = b;
+            bs.io.in = io->dstate_out ? io->dstate_out + l * state_layer : nullptr;
+            bs.io.out = io->dstate_in ? io->dstate_in + l * state_layer : nullptr;
+            KWS_LAUNCH(h, kws::launch_gru_train_backward_state(bs, H, st), "launch gru_train_backward_state");
+        } else {
+            KWS_LAUNCH(h, kws::launch_gru_train_backward(b, H, st), "launch gru_train_backward");
+        }
         if (l > 0 || h->ln) {          // [dr^ | du^ | dc^] . (Wg_x | Wc_x)^T: the dy of the layer below, or dxhat under the layer norm
             kws::TrainRowsGemm g = {};
             g.a = y.dhat; g.lda = 3 * H; g.w = pk.wx; g.swk = 1; g.swn = 3 * H;
@@ -278,6 +310,18 @@ int grad_impl(kws_train* h, const float* x, const int32_t* seq_len, const int32_
     KWS_LAUNCH(h, kws::launch_train_wgrad(cv.jobs, cv.njobs, cv.units, x, cv.live, M, cv.chunk_rows, cv.chunks, cv.partial, h->P, st),
                "launch train_wgrad");
     KWS_LAUNCH(h, kws::launch_train_reduce(cv.partial, cv.chunks, h->P, h->grad, h->sumsq, st), "launch train_reduce");
+    return KWS_OK;
+}
+
+// clip over h->grad (its blocks' sums of squares in h->sumsq), one optimiser step with the handle's moments and step count, re-pack
+int update_impl(kws_train* h, float lr, float* grad_norm_or_null, hipStream_t st) {
+    const bool adam = h->cfg.optimizer == KWS_OPT_ADAM;
+    const double step = (double)(h->steps + 1);
+    const float lr_t = adam ? (float)((double)lr * sqrt(1.0 - pow(0.999, step)) / (1.0 - pow(0.9, step))) : lr;
+    KWS_LAUNCH(h, kws::launch_train_update(h->theta, h->m, h->v, h->grad, h->sumsq, h->nred, h->P, adam ? 1 : 0, lr_t, h->cfg.max_grad_norm,
+                                           grad_norm_or_null, st), "launch train_update");
+    KWS_LAUNCH(h, kws::launch_train_pack(h->pack, st), "launch train_pack");
+    ++h->steps;
     return KWS_OK;
 }
 
@@ -387,6 +431,16 @@ int kws_train_check_wrapped(const kws_train_config* cfg, const float* x, const i
     return check_call(*cfg, x, seq_len, labels, label_len, B, T, S_max, loss);
 }
 
+size_t kws_sizeof_train_state_io(void) { return sizeof(kws_train_state_io); }
+
+int kws_train_check_state(const kws_train_config* cfg, int wrapped, const float* x, const int32_t* seq_len, const int32_t* labels,
+                          const int32_t* label_len, int B, int T, int S_max, const float* loss, const kws_train_state_io* io) {
+    if (!cfg) return fail(KWS_ERR_INVALID_ARGUMENT, "config is null");
+    KWS_TRY(check_config(*cfg, wrapped != 0));
+    KWS_TRY(check_call(*cfg, x, seq_len, labels, label_len, B, T, S_max, loss));
+    return check_state_io(io);
+}
+
 int kws_train_destroy(kws_train_handle h) {
     if (!h) return KWS_OK;
     hipDeviceSynchronize();
@@ -456,17 +510,24 @@ int kws_train_reserve(kws_train_handle h, int B, int T, int S_max) {
 
 int kws_train_grad(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
                    int S_max, const uint8_t* drop_or_null, float* loss, float* grad_blob, float* logits_or_null, void* stream) {
+    return kws_train_grad_state(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, loss, grad_blob, logits_or_null, nullptr, stream);
+}
+
+int kws_train_grad_state(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
+                         int T, int S_max, const uint8_t* drop_or_null, float* loss, float* grad_blob, float* logits_or_null,
+                         const kws_train_state_io* io, void* stream) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
     KWS_TRY(check_call(h->cfg, x, seq_len, labels, label_len, B, T, S_max, loss));
     if (!grad_blob) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
     if (misaligned(grad_blob) || misaligned(logits_or_null) || misaligned(drop_or_null))
         return fail(KWS_ERR_INVALID_ARGUMENT, "grad_blob, logits and drop must be 4-byte aligned (the masks are read four units at a time)");
+    KWS_TRY(check_state_io(io));
     BusyGuard guard(h->in_call);
     if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this train handle");
     hipStream_t st = static_cast<hipStream_t>(stream);
     KWS_TRY(train_enter(h, st));
     return train_finish(h, st, [&]() -> int {
-        KWS_TRY(grad_impl(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, loss, st));
+        KWS_TRY(grad_impl(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, loss, io, st));
         KWS_HIP(hipMemcpyAsync(grad_blob, h->grad, h->P * sizeof(float), hipMemcpyDeviceToDevice, st));
         if (logits_or_null)
             KWS_HIP(hipMemcpyAsync(logits_or_null, h->cv.logits, (size_t)B * T * h->cfg.model.num_classes * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -476,25 +537,42 @@ int kws_train_grad(kws_train_handle h, const float* x, const int32_t* seq_len, c
 
 int kws_train_step(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
                    int S_max, const uint8_t* drop_or_null, float lr, float* loss, float* grad_norm_or_null, void* stream) {
+    return kws_train_step_state(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, lr, loss, grad_norm_or_null, nullptr, stream);
+}
+
+int kws_train_step_state(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
+                         int T, int S_max, const uint8_t* drop_or_null, float lr, float* loss, float* grad_norm_or_null,
+                         const kws_train_state_io* io, void* stream) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
     KWS_TRY(check_call(h->cfg, x, seq_len, labels, label_len, B, T, S_max, loss));
     if (!(lr > 0.f) || !std::isfinite(lr)) return fail(KWS_ERR_INVALID_ARGUMENT, "lr=%g has to be positive and finite", (double)lr);
     if (misaligned(grad_norm_or_null) || misaligned(drop_or_null))
         return fail(KWS_ERR_INVALID_ARGUMENT, "grad_norm and drop must be 4-byte aligned (the masks are read four units at a time)");
+    KWS_TRY(check_state_io(io));
     BusyGuard guard(h->in_call);
     if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this train handle");
     hipStream_t st = static_cast<hipStream_t>(stream);
     KWS_TRY(train_enter(h, st));
     return train_finish(h, st, [&]() -> int {
-        KWS_TRY(grad_impl(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, loss, st));
-        const bool adam = h->cfg.optimizer == KWS_OPT_ADAM;
-        const double step = (double)(h->steps + 1);
-        const float lr_t = adam ? (float)((double)lr * sqrt(1.0 - pow(0.999, step)) / (1.0 - pow(0.9, step))) : lr;
-        KWS_LAUNCH(h, kws::launch_train_update(h->theta, h->m, h->v, h->grad, h->sumsq, h->nred, h->P, adam ? 1 : 0, lr_t, h->cfg.max_grad_norm,
-                                               grad_norm_or_null, st), "launch train_update");
-        KWS_LAUNCH(h, kws::launch_train_pack(h->pack, st), "launch train_pack");
-        ++h->steps;
-        return KWS_OK;
+        KWS_TRY(grad_impl(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, loss, io, st));
+        return update_impl(h, lr, grad_norm_or_null, st);
+    }());
+}
+
+int kws_train_apply(kws_train_handle h, const float* grad_blob, float lr, float* grad_norm_or_null, void* stream) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    if (!grad_blob) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
+    if (!(lr > 0.f) || !std::isfinite(lr)) return fail(KWS_ERR_INVALID_ARGUMENT, "lr=%g has to be positive and finite", (double)lr);
+    if (misaligned(grad_blob) || misaligned(grad_norm_or_null)) return fail(KWS_ERR_INVALID_ARGUMENT, "grad_blob and grad_norm must be 4-byte aligned");
+    BusyGuard guard(h->in_call);
+    if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this train handle");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    KWS_TRY(train_enter(h, st));
+    return train_finish(h, st, [&]() -> int {
+        h->launches = 0;
+        // the caller's gradient as the one chunk of the reduction: h->grad = 0 + g, the blocks' sums of squares as behind a backward pass
+        KWS_LAUNCH(h, kws::launch_train_reduce(grad_blob, 1, h->P, h->grad, h->sumsq, st), "launch train_reduce");
+        return update_impl(h, lr, grad_norm_or_null, st);
     }());
 }
 

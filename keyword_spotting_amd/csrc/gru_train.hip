@@ -1,19 +1,22 @@
 // Training of the GRU stack (models/rnn_ctc.py:34-101,179-284): the two frame loops, one launch per layer each.
 //
-//   gru_train_forward<TPW>    the taped forward of one layer: TF 1.x GRUCell under dynamic_rnn(sequence_length) and
+//   gru_train_forward<TPW, STATE>   the taped forward of one layer: TF 1.x GRUCell under dynamic_rnn(sequence_length) and
 //                             DropoutWrapper(output_keep_prob) -- a mask per frame, or variational_recurrent's one mask per stream
-//                             (the mask's strides are launch arguments) --, from the zero state
+//                             (the mask's strides are launch arguments) --, from the zero state (STATE: from state_in)
 //                               [r,u] = sigma(xg_ru + h.Wg_h)    c = tanh(xg_c + (r o h).Wc_h)    h' = u o h + (1 - u) o c
 //                               y = h' o mask / keep_prob   (what goes up; the carried state is the undropped h')
 //                             at t >= seq_len[b] the state is copied and y = 0.  It keeps r, u, c, h (the state the frame started
 //                             from) and r o h of every frame t < seq_len -- the gates and the candidate as their pre-activations.
-//   gru_train_backward<TPW>   back-propagation through time of one layer, frames in reverse.  With dh' = dy o mask / keep_prob + the
+//   gru_train_backward<TPW, STATE>  back-propagation through time of one layer, frames in reverse.  With dh' = dy o mask / keep_prob + the
 //                             carried dh:
 //                               du = dh' o (h - c)    dc = dh' o (1 - u)    dh = dh' o u
 //                               dc^ = dc o (1 - c^2)  du^ = du o u (1 - u)
 //                               d(rh) = dc^ . Wc_h^T  dh += d(rh) o r       dr^ = d(rh) o h o r (1 - r)
 //                               dh += [dr^ | du^] . Wg_h^T
 //                             It writes dr^ | du^ | dc^ [B*T, 3H]; frames t >= seq_len[b] pass dh through and write zeros.
+//   STATE = true              the same two loops from a carried state (kws_train_grad_state): h starts from state_in and ends in
+//                             state_out, dh starts from dstate_out and ends in dstate_in; the loads and stores sit outside the frame
+//                             loops, and the STATE = false instantiations are the machine code they were without the parameter.
 //
 // What is NOT in the frame loops: every product with the layer's input.  x . (Wg_x | Wc_x) + bias of all frames is one GEMM in front of
 // the forward loop (xg), the dx of all frames one GEMM behind the backward loop, and the weight gradients one reduction over the B*T
@@ -29,6 +32,7 @@
 // backward loop recomputes r, u, c from them (the forward's bits) together with 1 - u, u (1 - u), r (1 - r) and 1 - c^2 in forms
 // that do not cancel (sigmoid_parts, tanh_slope).
 #include "gru_device.h"
+#include <type_traits>
 #include "launch.h"
 
 namespace kws {
@@ -77,8 +81,12 @@ __device__ __forceinline__ f32x4 dropped(f32x4 v, const uint8_t* drop, size_t at
 
 }  // namespace
 
-template <int TPW>
-__global__ void __launch_bounds__(256) gru_train_forward(const TrainForwardParams p) {
+// STATE: the layer starts from state_in[b] and leaves the state after frame seq_len[b] - 1 in
+// state_out[b] (TrainStateIo, kws_internal.h; each pointer may be null).  Lane (g, s) of wave w holds, for tile j, units
+// 16 (TPW w + j) + 4 g .. + 3 of stream s: one 16-byte piece of the row state[b], read before the frame loop and written behind it by
+// the same lane -- so state_out may be state_in, and a workgroup or a stream that runs no frame copies the bits.
+template <int TPW, bool STATE>
+__global__ void __launch_bounds__(256) gru_train_forward(const std::conditional_t<STATE, TrainForwardStateParams, TrainForwardParams> p) {
     constexpr int NT = 4 * TPW, H = 64 * TPW, H3 = 3 * H;
     const int tid = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -95,6 +103,9 @@ __global__ void __launch_bounds__(256) gru_train_forward(const TrainForwardParam
 #pragma unroll
     for (int j = 0; j < TPW; ++j) {
         hreg[j] = splat4(0.f);
+        if constexpr (STATE) {
+            if (bvalid && p.io.in) hreg[j] = ld4(p.io.in + (size_t)b * H + (TPW * w + j) * 16 + 4 * g);
+        }
         hbuf[(TPW * w + j) * 64 + lane] = hreg[j];
     }
     __syncthreads();
@@ -187,10 +198,17 @@ __global__ void __launch_bounds__(256) gru_train_forward(const TrainForwardParam
             for (int j = 0; j < TPW; ++j) st4(p.y + ((size_t)b * T + t) * H + (TPW * w + j) * 16 + 4 * g, splat4(0.f));
         }
     }
+    if constexpr (STATE) {
+        if (bvalid && p.io.out) {
+#pragma unroll
+            for (int j = 0; j < TPW; ++j) st4(p.io.out + (size_t)b * H + (TPW * w + j) * 16 + 4 * g, hreg[j]);
+        }
+    }
 }
 
-template <int TPW>
-__global__ void __launch_bounds__(256) gru_train_backward(const TrainBackwardParams p) {
+// STATE: dh starts from dstate_out[b] (io.in) and what is left after frame 0 goes to dstate_in[b] (io.out), by the same lanes as above
+template <int TPW, bool STATE>
+__global__ void __launch_bounds__(256) gru_train_backward(const std::conditional_t<STATE, TrainBackwardStateParams, TrainBackwardParams> p) {
     constexpr int NT = 4 * TPW, H = 64 * TPW, H3 = 3 * H;
     const int tid = threadIdx.x;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -205,7 +223,12 @@ __global__ void __launch_bounds__(256) gru_train_backward(const TrainBackwardPar
     __shared__ f32x4 dcbuf[NT * 64], dubuf[NT * 64], drbuf[NT * 64];
     f32x4 dh[TPW];
 #pragma unroll
-    for (int j = 0; j < TPW; ++j) dh[j] = splat4(0.f);
+    for (int j = 0; j < TPW; ++j) {
+        dh[j] = splat4(0.f);
+        if constexpr (STATE) {
+            if (bvalid && p.io.in) dh[j] = ld4(p.io.in + (size_t)b * H + (TPW * w + j) * 16 + 4 * g);
+        }
+    }
     if (bvalid) {
         for (int t = tmax; t < T; ++t) {
 #pragma unroll
@@ -305,17 +328,36 @@ __global__ void __launch_bounds__(256) gru_train_backward(const TrainBackwardPar
         // the next frame's stores to dcbuf / dubuf come behind this frame's second barrier, which every wave passes only after its
         // first-phase reads; drbuf is next written behind the next frame's first barrier, after every wave's second-phase reads
     }
+    if constexpr (STATE) {
+        if (bvalid && p.io.out) {
+#pragma unroll
+            for (int j = 0; j < TPW; ++j) st4(p.io.out + (size_t)b * H + (TPW * w + j) * 16 + 4 * g, dh[j]);
+        }
+    }
 }
+
 
 hipError_t launch_gru_train_forward(const TrainForwardParams& p, int hidden, hipStream_t st) {
     return with_tpw<1, 2, 4>(hidden, [&](auto tpw) {
-        return launch_lds<gru_train_forward<tpw()>>(dim3(groups_of(p.B)), dim3(256), 0, st, p);
+        return launch_lds<gru_train_forward<tpw(), false>>(dim3(groups_of(p.B)), dim3(256), 0, st, p);
     });
 }
 
 hipError_t launch_gru_train_backward(const TrainBackwardParams& p, int hidden, hipStream_t st) {
     return with_tpw<1, 2, 4>(hidden, [&](auto tpw) {
-        return launch_lds<gru_train_backward<tpw()>>(dim3(groups_of(p.B)), dim3(256), 0, st, p);
+        return launch_lds<gru_train_backward<tpw(), false>>(dim3(groups_of(p.B)), dim3(256), 0, st, p);
+    });
+}
+
+hipError_t launch_gru_train_forward_state(const TrainForwardStateParams& p, int hidden, hipStream_t st) {
+    return with_tpw<1, 2, 4>(hidden, [&](auto tpw) {
+        return launch_lds<gru_train_forward<tpw(), true>>(dim3(groups_of(p.B)), dim3(256), 0, st, p);
+    });
+}
+
+hipError_t launch_gru_train_backward_state(const TrainBackwardStateParams& p, int hidden, hipStream_t st) {
+    return with_tpw<1, 2, 4>(hidden, [&](auto tpw) {
+        return launch_lds<gru_train_backward<tpw(), true>>(dim3(groups_of(p.B)), dim3(256), 0, st, p);
     });
 }
 

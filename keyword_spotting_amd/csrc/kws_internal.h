@@ -524,6 +524,14 @@ struct TrainBackwardParams {
 };
 hipError_t launch_gru_train_forward(const TrainForwardParams& p, int hidden, hipStream_t st);
 hipError_t launch_gru_train_backward(const TrainBackwardParams& p, int hidden, hipStream_t st);
+// The same launches from a carried state (kws_train_grad_state): one layer's rows [B, H] fp32, 16-byte aligned, either may be null
+// and out may be in.  Forward: in = state_in[l] (null: zeros), out = state_out[l], the state after frame seq_len[b] - 1.  Backward:
+// in = dstate_out[l] (null: zeros), out = dstate_in[l].  A stream with seq_len[b] == 0 copies in to out bitwise; rows b >= B are not written.
+struct TrainStateIo { const float* in; float* out; };
+struct TrainForwardStateParams : TrainForwardParams { TrainStateIo io; };
+struct TrainBackwardStateParams : TrainBackwardParams { TrainStateIo io; };
+hipError_t launch_gru_train_forward_state(const TrainForwardStateParams& p, int hidden, hipStream_t st);
+hipError_t launch_gru_train_backward_state(const TrainBackwardStateParams& p, int hidden, hipStream_t st);
 // out [M, N] = bias + a [M, K] . W, W(k, n) = w[k * swk + n * swn]; a row with live[row] == 0 reads as zeros (so out = bias there)
 struct TrainRowsGemm {
     const float* a; int lda;
