@@ -13,15 +13,11 @@ import numpy as np
 
 from . import _lib
 from . import attention_weights as _weights
+from ._trainer import _TrainerBase, exponential_decay
 from .custom_keyword import _ints, _pack_labels
 from .training import OPTIMIZERS
 
 SITE_PROB, SITE_ATT, SITE_FFN = 0, 1, 2
-
-
-def exponential_decay(learning_rate, step, decay_step, lr_decay):
-    """tf.train.exponential_decay, staircase=False."""
-    return float(learning_rate) * float(lr_decay) ** (float(step) / float(decay_step))
 
 
 def polynomial_decay(learning_rate, step, decay_steps, end_learning_rate, power):
@@ -74,45 +70,25 @@ def check_call(config, x_shape, lengths, labels, optimizer="adam", max_grad_norm
     _lib.check(_lib.load().kws_attention_train_check(ctypes.byref(cfg), p, sl_p, lab_p, ll_p, b, t, int(lab.shape[1]), p))
 
 
-class AttentionTrainer(object):
+class AttentionTrainer(_TrainerBase):
     """The reference's attention training graph on one device.  Defaults: config/attention_config.py:49-56,81 (learning_rate 1e-3,
     lr_decay 0.9, decay_step 40000, adam, no clipping, no warm-up); keep_prob defaults to 1 (the reference file ships 0.9, :83).
     weights: a dict (attention_weights.init's form), a blob, or None for attention_weights.init(config, seed)."""
 
+    _prefix, _weights_mod, _feature = "kws_attention_train", _weights, "freq_size"
+
     def __init__(self, config, weights=None, optimizer="adam", learning_rate=1e-3, lr_decay=0.9, decay_step=40000, warmup=False,
                  max_grad_norm=-1, keep_prob=1.0, seed=0, device="cuda:0"):
-        import torch
         self.config = config
         self.optimizer, self.learning_rate, self.lr_decay, self.decay_step = optimizer, float(learning_rate), float(lr_decay), int(decay_step)
         self.warmup, self.max_grad_norm, self.keep_prob = bool(warmup), float(max_grad_norm), float(keep_prob)
         self._cfg = train_config(config, optimizer, max_grad_norm, keep_prob)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.InvalidArgumentError(-1, "AttentionTrainer needs a CUDA/HIP device, got %s" % device)
-        self._lib = _lib.load()
-        self._handle = ctypes.c_void_p()
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_attention_train_create(ctypes.byref(self._cfg), ctypes.byref(self._handle)))
+        self._open(device, "kws_attention_train_create")
         self._rng = np.random.default_rng(int(seed))          # the seeds of step()
         self.global_step = 0
         if weights is None:
             weights = _weights.init(config, seed=seed)
         self.set_weights(weights)
-
-    # -- lifecycle ---------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_handle", None) is not None and self._handle.value:
-            self._lib.kws_attention_train_destroy(self._handle)
-            self._handle = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        return _lib.current_stream_ptr()
 
     def _floats(self):
         return self._lib.kws_attention_weights_nbytes(ctypes.byref(self._cfg.model)) // 4
@@ -122,34 +98,6 @@ class AttentionTrainer(object):
         return frames // c + 1 if c > 1 else frames
 
     # -- parameters --------------------------------------------------------------------------
-    def set_weights(self, weights):
-        """Loads parameters; zeroes the optimiser's moments and the step count of its bias corrections."""
-        import torch
-        blob = weights if isinstance(weights, np.ndarray) else _weights.to_blob(self.config, weights)
-        blob = np.ascontiguousarray(blob, np.float32)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_attention_train_set_weights(self._handle, blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes, self._stream()))
-
-    def weights_blob(self):
-        import torch
-        blob = np.empty(self._floats(), np.float32)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_attention_train_get_weights(self._handle, blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes, self._stream()))
-        return blob
-
-    def weights(self):
-        return _weights.from_blob(self.config, self.weights_blob())
-
-    def moments(self):
-        """(m, v) in the dict form: Adam's moments; Nesterov's accumulator and zeros."""
-        import torch
-        n = self._floats()
-        m, v = np.empty(n, np.float32), np.empty(n, np.float32)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_attention_train_moments(self._handle, m.ctypes.data_as(ctypes.c_void_p), v.ctypes.data_as(ctypes.c_void_p),
-                                                             self._stream()))
-        return _weights.from_blob(self.config, m), _weights.from_blob(self.config, v)
-
     def save(self, path):
         w = self.weights()
         flat = {k: w[k] for k in _weights.TOP_KEYS}
@@ -163,34 +111,9 @@ class AttentionTrainer(object):
         from .attention_ctc import DeployModel
         return DeployModel(self.config, self.weights_blob(), device=str(self.device), precision=precision)
 
-    def reserve(self, batch, frames, max_label=31):
-        _lib.check(self._lib.kws_attention_train_reserve(self._handle, int(batch), int(frames), int(max_label)))
-
-    def stats(self):
-        """dict(device_bytes, allocs, steps, launches of the last call, chunk_rows of the weight-gradient reduction)."""
-        nbytes = ctypes.c_size_t()
-        a, s, l, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-        _lib.check(self._lib.kws_attention_train_stats(self._handle, ctypes.byref(nbytes), ctypes.byref(a), ctypes.byref(s), ctypes.byref(l),
-                                                       ctypes.byref(c)))
-        return dict(device_bytes=int(nbytes.value), allocs=a.value, steps=s.value, launches=l.value, chunk_rows=c.value)
-
     # -- compute -----------------------------------------------------------------------------
     def learning_rate_at(self, step):
         return learning_rate_at(step, self.learning_rate, self.lr_decay, self.decay_step, self.warmup)
-
-    def _inputs(self, x, lengths, labels):
-        import torch
-        cfg = self.config
-        x = torch.as_tensor(x)
-        if x.dim() != 3 or x.shape[2] != cfg.freq_size:
-            raise _lib.InvalidArgumentError(-1, "x must be [B,T,%d], got %s" % (cfg.freq_size, tuple(x.shape)))
-        x = x.to(device=self.device, dtype=torch.float32).contiguous()
-        b, t = int(x.shape[0]), int(x.shape[1])
-        lab, lab_len = _pack_labels(labels, b)
-        sl = np.full(b, t) if lengths is None else np.asarray(lengths)
-        if sl.shape != (b,):
-            raise _lib.InvalidArgumentError(-1, "lengths: %s for %d utterances" % (sl.shape, b))
-        return x, b, t, _ints(sl), _ints(lab), _ints(lab_len)
 
     def loss_and_grad(self, x, lengths, labels, seed=0, want_logits=False):
         """-> (loss = sum_b ctc_b / B, gradients in the dict form, per-utterance losses [B]) [, logits [B,T',C]]; the parameters stay.

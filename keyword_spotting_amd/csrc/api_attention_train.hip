@@ -11,25 +11,16 @@
 //   residual (d of the embedding), wgrad, reduce
 #include <new>
 
-#include "api_internal.h"
+#include "train_core.h"
 #include "attention_internal.h"
 
 using namespace kws_host;
 
-struct kws_attention_train {
+struct kws_attention_train : TrainCore {      // tail: the positional table
     kws_attention_train_config cfg;
     AttnLayout lay;
-    size_t P = 0;
     int pe_rows = 0;
-    // one allocation fixed at create: theta | m | v | grad [4 P], the positional table, the reduction's sums of squares (doubles)
-    float* state = nullptr;
-    float *theta = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr, *pe = nullptr;
-    double* sumsq = nullptr;
-    size_t state_bytes = 0;
-    int nred = 0;
-    // one allocation that only grows, carved for the shape of the call
-    char* arena = nullptr;
-    size_t arena_bytes = 0;
+    // the arena, carved for the shape of the call
     struct Carved {
         int B = 0, T = 0, T1 = 0, S_max = -1;
         int32_t* ints = nullptr;          // T'_b [B] | label_len [B] | labels [B, S_max] | T_b [B]
@@ -39,73 +30,49 @@ struct kws_attention_train {
         float4* part = nullptr;
         float2* sums = nullptr;
         struct Layer { float *qkv, *att, *lse, *xn_a, *y, *hin, *xn_b, *rstd_a, *rstd_b, *dy_b, *prod_b, *dz, *dh, *dy_a, *prod_a, *dqkv; } layer[8] = {};
-        int njobs = 0, units = 0, chunk_rows = 0, chunks = 0;
+        int njobs = 0, chunk_rows = 0, chunks = 0;
     } cv;
-    std::vector<kws::TrainWgradJob> jobs_host;
-    bool jobs_dirty = false;
-    std::vector<int32_t> ints_host;
-    int steps = 0, allocs = 0, launches = 0;
-    std::atomic<int> in_call{0};
-    hipStream_t last_stream = nullptr;
-    bool last_stream_valid = false;
-    hipEvent_t last_done = nullptr;
 };
 
 namespace {
 
 typedef kws_attention_train Handle;
-constexpr size_t kAlign = 256;
-size_t aligned(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
 constexpr size_t kMaxRows = (size_t)1 << 28;
 
 int frames_out(const kws_attention_config& c, int T) { return c.combine_frame > 1 ? T / c.combine_frame + 1 : T; }
-
-int enter(Handle* h, hipStream_t st) {
-    if (h->last_stream_valid && h->last_stream != st) KWS_HIP(hipStreamWaitEvent(st, h->last_done, 0));
-    return KWS_OK;
-}
-// at the end of a call's queued work, failed or not: what went out is what a call on another stream has to wait for
-int finish(Handle* h, hipStream_t st, int rc) {
-    const hipError_t e = hipEventRecord(h->last_done, st);
-    if (e == hipSuccess) { h->last_stream = st; h->last_stream_valid = true; }
-    if (rc != KWS_OK) return rc;
-    return hip_done(e, "hipEventRecord");
-}
 
 // Lays the arena out for (B, T, S_max).  base == null: only the size.
 size_t carve(const Handle* h, int B, int T, int S_max, char* base, Handle::Carved* cv) {
     const kws_attention_config& c = h->cfg.model;
     const int T1 = frames_out(c, T), ntile = (T1 + kws::kAttnRows - 1) / kws::kAttnRows;
     const size_t M = (size_t)B * T1, H = (size_t)c.hidden, Fi = (size_t)c.ffn_inner, NH = (size_t)c.num_heads, C = (size_t)c.num_classes;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + at : nullptr; at += aligned(bytes); return p; };
-    auto floats = [&](size_t n) { return reinterpret_cast<float*>(take(n * sizeof(float))); };
+    Carver cut(base);
     Handle::Carved o;
     o.B = B; o.T = T; o.T1 = T1; o.S_max = S_max;
     o.njobs = 4 + 10 * c.num_layers;
     o.chunk_rows = wgrad_chunk_rows(M);
     o.chunks = (int)((M + o.chunk_rows - 1) / o.chunk_rows);
-    o.ints = reinterpret_cast<int32_t*>(take((size_t)B * (3 + S_max) * sizeof(int32_t)));
-    o.live = reinterpret_cast<uint8_t*>(take(M));
-    o.jobs = reinterpret_cast<kws::TrainWgradJob*>(take((size_t)o.njobs * sizeof(kws::TrainWgradJob)));
-    o.part = reinterpret_cast<float4*>(take((size_t)B * ntile * sizeof(float4)));
-    o.sums = reinterpret_cast<float2*>(take((size_t)B * ntile * sizeof(float2)));
-    o.xs = floats(M * c.combine_frame * c.n_mel);
-    for (int l = 0; l <= c.num_layers; ++l) o.x[l] = floats(M * H);
-    for (float*& s : o.sh) s = floats(M * H);
-    o.de = floats(M * H);
-    o.logits = floats(M * C); o.gl = floats(M * C);
-    o.dsum = floats(M * NH);
+    o.ints = reinterpret_cast<int32_t*>(cut.take((size_t)B * (3 + S_max) * sizeof(int32_t)));
+    o.live = reinterpret_cast<uint8_t*>(cut.take(M));
+    o.jobs = reinterpret_cast<kws::TrainWgradJob*>(cut.take((size_t)o.njobs * sizeof(kws::TrainWgradJob)));
+    o.part = reinterpret_cast<float4*>(cut.take((size_t)B * ntile * sizeof(float4)));
+    o.sums = reinterpret_cast<float2*>(cut.take((size_t)B * ntile * sizeof(float2)));
+    o.xs = cut.floats(M * c.combine_frame * c.n_mel);
+    for (int l = 0; l <= c.num_layers; ++l) o.x[l] = cut.floats(M * H);
+    for (float*& s : o.sh) s = cut.floats(M * H);
+    o.de = cut.floats(M * H);
+    o.logits = cut.floats(M * C); o.gl = cut.floats(M * C);
+    o.dsum = cut.floats(M * NH);
     for (int l = 0; l < c.num_layers; ++l) {
         Handle::Carved::Layer& y = o.layer[l];
-        y.qkv = floats(M * 3 * H); y.att = floats(M * H); y.lse = floats(M * NH); y.xn_a = floats(M * H); y.y = floats(M * H);
-        y.hin = floats(M * Fi); y.xn_b = floats(M * H); y.rstd_a = floats(B); y.rstd_b = floats(B);
-        y.dy_b = floats(M * H); y.prod_b = floats(M * H); y.dz = floats(M * H); y.dh = floats(M * Fi);
-        y.dy_a = floats(M * H); y.prod_a = floats(M * H); y.dqkv = floats(M * 3 * H);
+        y.qkv = cut.floats(M * 3 * H); y.att = cut.floats(M * H); y.lse = cut.floats(M * NH); y.xn_a = cut.floats(M * H); y.y = cut.floats(M * H);
+        y.hin = cut.floats(M * Fi); y.xn_b = cut.floats(M * H); y.rstd_a = cut.floats(B); y.rstd_b = cut.floats(B);
+        y.dy_b = cut.floats(M * H); y.prod_b = cut.floats(M * H); y.dz = cut.floats(M * H); y.dh = cut.floats(M * Fi);
+        y.dy_a = cut.floats(M * H); y.prod_a = cut.floats(M * H); y.dqkv = cut.floats(M * 3 * H);
     }
-    o.partial = floats((size_t)o.chunks * h->P);
+    o.partial = cut.floats((size_t)o.chunks * h->P);
     if (cv) *cv = o;
-    return at;
+    return cut.at;
 }
 
 // the products of the weight-gradient launch for the carved shape, in blob order; the layer norms' d beta / d gamma are the column
@@ -113,14 +80,9 @@ size_t carve(const Handle* h, int B, int T, int S_max, char* base, Handle::Carve
 void build_jobs(Handle* h) {
     const kws_attention_config& c = h->cfg.model;
     const int H = c.hidden, Fi = c.ffn_inner, C = c.num_classes, cF = c.combine_frame * c.n_mel;
-    Handle::Carved& cv = h->cv;
-    h->jobs_host.clear();
-    int unit = 0;
+    const Handle::Carved& cv = h->cv;
     auto add = [&](const float* a, int lda, int K, const float* d, int ldd, int N, size_t out) {
-        kws::TrainWgradJob j = {};
-        j.a = a; j.d = d; j.out = out; j.src = a ? kws::kWgradRows : kws::kWgradOnes; j.lda = lda; j.K = K; j.ldd = ldd; j.N = N; j.ldo = N; j.unit0 = unit;
-        unit += ((K + 15) / 16) * ((N + 63) / 64);
-        h->jobs_host.push_back(j);
+        h->add_job(a ? kws::kWgradRows : kws::kWgradOnes, a, lda, K, d, ldd, N, out, N);
     };
     add(cv.xs, cF, cF, cv.de, H, H, h->lay.w_in);
     add(nullptr, 0, 1, cv.de, H, H, h->lay.b_in);
@@ -140,29 +102,16 @@ void build_jobs(Handle* h) {
     }
     add(cv.x[c.num_layers], H, H, cv.gl, C, C, h->lay.w_out);
     add(nullptr, 0, 1, cv.gl, C, C, h->lay.b_out);
-    cv.units = unit;
 }
 
+// the arena for (B, T, S_max): grown if it has to be (waits for the device once), carved anew when the shape differs from the last call's
 int prepare_shape(Handle* h, int B, int T, int S_max) {
     if (h->cv.B == B && h->cv.T == T && h->cv.S_max == S_max && h->arena) return KWS_OK;
-    const size_t need = carve(h, B, T, S_max, nullptr, nullptr);
-    if (need > h->arena_bytes) {
-        size_t free_b = 0, total_b = 0;
-        KWS_HIP(hipMemGetInfo(&free_b, &total_b));
-        if (need > free_b + h->arena_bytes)
-            return fail(KWS_ERR_OUT_OF_MEMORY, "the tape of B=%d utterances x T=%d frames x %d layers takes %zu bytes: the device has %zu free "
-                        "(%zu in all; fewer utterances per step or shorter ones)", B, T, h->cfg.model.num_layers, need, free_b + h->arena_bytes, total_b);
-        KWS_HIP(hipDeviceSynchronize());
-        if (h->arena) (void)hipFree(h->arena);
-        h->arena = nullptr; h->arena_bytes = 0; h->cv = Handle::Carved(); h->ints_host.clear();
-        KWS_HIP(hipMalloc(reinterpret_cast<void**>(&h->arena), need));
-        h->arena_bytes = need;
-        ++h->allocs;
-    }
+    const int rc = train_arena_reserve(h, carve(h, B, T, S_max, nullptr, nullptr), B, T, h->cfg.model.num_layers);
+    if (!h->arena) h->cv = Handle::Carved();      // freed and not replaced: no layout
+    KWS_TRY(rc);
     carve(h, B, T, S_max, h->arena, &h->cv);
-    h->ints_host.clear();
     build_jobs(h);
-    h->jobs_dirty = true;
     return KWS_OK;
 }
 
@@ -171,26 +120,17 @@ int check_config(const kws_attention_train_config* cfg) {
     if (!cfg) return fail(KWS_ERR_INVALID_ARGUMENT, "config is null");
     int code = KWS_OK;
     if (!attn_config_ok(&cfg->model, &code)) return code;
-    if (!(cfg->keep_prob > 0.f && cfg->keep_prob <= 1.f)) return fail(KWS_ERR_UNSUPPORTED, "keep_prob=%g outside (0, 1]", (double)cfg->keep_prob);
-    if (cfg->optimizer != KWS_OPT_ADAM && cfg->optimizer != KWS_OPT_NESTEROV)
-        return fail(KWS_ERR_INVALID_ARGUMENT, "optimizer=%d: KWS_OPT_ADAM (0) or KWS_OPT_NESTEROV (1)", cfg->optimizer);
-    if (!std::isfinite(cfg->max_grad_norm)) return fail(KWS_ERR_INVALID_ARGUMENT, "max_grad_norm=%g is not finite", (double)cfg->max_grad_norm);
-    return KWS_OK;
+    return check_optimizer(cfg->keep_prob, cfg->optimizer, cfg->max_grad_norm);
 }
 
 int check_shape(const kws_attention_config& c, int B, int T, int S_max) {
     if (B < 1 || T < 1) return fail(KWS_ERR_INVALID_ARGUMENT, "bad shape B=%d T=%d: at least one utterance and one frame", B, T);
-    if (S_max < 0 || S_max > 31)
-        return fail(KWS_ERR_INVALID_ARGUMENT, "S_max=%d out of range [0,31]: one lane of a wave per state of the extended label", S_max);
+    KWS_TRY(check_s_max(S_max));
     if (T > c.max_frames) return fail(KWS_ERR_UNSUPPORTED, "T=%d exceeds model.max_frames=%d", T, c.max_frames);
     if (B > 65535) return fail(KWS_ERR_UNSUPPORTED, "B=%d unsupported (<= 65535)", B);
     const int T1 = frames_out(c, T);
     if ((size_t)B * T1 > kMaxRows) return fail(KWS_ERR_UNSUPPORTED, "B=%d x T'=%d: more than 2^28 rows in one call", B, T1);
-    const size_t lds = kws::ctc_loss_lds_bytes(T1, S_max);
-    if (lds > kWindowIncLdsMax)
-        return fail(KWS_ERR_UNSUPPORTED, "the CTC loss keeps T'=%d rows x (8 log-probabilities + %d states) in LDS: %zu bytes exceed the %zu a "
-                    "workgroup may hold", T1, 2 * S_max + 1, lds, kWindowIncLdsMax);
-    return KWS_OK;
+    return check_ctc_lds(T1, S_max, "T'=%d rows");
 }
 
 // the refusals of a grad / step call from host memory alone; t1 (if given): every utterance's T'_b
@@ -210,8 +150,6 @@ int check_call(const kws_attention_train_config& cfg, const float* x, const int3
     return KWS_OK;
 }
 
-#define KWS_LAUNCH(h, call, what) do { KWS_TRY(hip_done((call), what)); ++(h)->launches; } while (0)
-
 // forward, loss, backward: leaves loss [B], the logits and the gradient of sum(loss) / B (h->grad, with the sums of squares of its blocks)
 int grad_impl(Handle* h, const float* x, const int32_t* seq_len, const std::vector<int32_t>& t1, const int32_t* labels, const int32_t* label_len,
               int B, int T, int S_max, uint64_t seed, float* loss, hipStream_t st) {
@@ -220,19 +158,10 @@ int grad_impl(Handle* h, const float* x, const int32_t* seq_len, const std::vect
     KWS_TRY(prepare_shape(h, B, T, S_max));
     Handle::Carved& cv = h->cv;
     const int T1 = cv.T1, M = B * T1;
-    if (h->jobs_dirty) {
-        KWS_HIP(hipMemcpyAsync(cv.jobs, h->jobs_host.data(), h->jobs_host.size() * sizeof(kws::TrainWgradJob), hipMemcpyHostToDevice, st));
-        h->jobs_dirty = false;
-    }
-    // lengths or labels other than the last call's: one upload from pageable memory, which the runtime completes on the host (the
-    // header says so); a repeated batch uploads nothing
     std::vector<int32_t> ints;
     pack_ints(t1.data(), labels, label_len, B, S_max, &ints);
     ints.insert(ints.end(), seq_len, seq_len + B);
-    if (ints != h->ints_host) {
-        KWS_HIP(hipMemcpyAsync(cv.ints, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        h->ints_host.swap(ints);
-    }
+    KWS_TRY(train_upload(h, cv.jobs, cv.ints, &ints, st));
     const int32_t *d_t1 = cv.ints, *d_len = cv.ints + B, *d_lab = cv.ints + 2 * (size_t)B, *d_tlen = cv.ints + (size_t)B * (2 + S_max);
     const float kp = h->cfg.keep_prob;
     const bool drop = kp < 1.0f;
@@ -248,7 +177,7 @@ int grad_impl(Handle* h, const float* x, const int32_t* seq_len, const std::vect
     KWS_LAUNCH(h, kws::launch_train_rowmask(d_t1, B, T1, cv.live, st), "launch train_rowmask");
     KWS_LAUNCH(h, kws::launch_attn_train_stack(x, d_tlen, d_t1, B, T, T1, c.n_mel, c.combine_frame, cv.xs, st), "launch attn_train_stack");
     KWS_TRY(gemm(cv.xs, cF, th + h->lay.w_in, H, 1, th + h->lay.b_in, cv.x[0], H, "launch train_rows_gemm (embedding)"));
-    KWS_LAUNCH(h, kws::launch_attn_train_addpe(cv.x[0], h->pe, d_t1, B, T1, H, st), "launch attn_train_addpe");
+    KWS_LAUNCH(h, kws::launch_attn_train_addpe(cv.x[0], h->tail, d_t1, B, T1, H, st), "launch attn_train_addpe");
     float *s_z = cv.sh[0], *s_u = cv.sh[1];
     for (int l = 0; l < L; ++l) {
         const size_t* o = h->lay.layer[l];
@@ -307,7 +236,7 @@ int grad_impl(Handle* h, const float* x, const int32_t* seq_len, const std::vect
         g2 = s_du;
     }
     KWS_LAUNCH(h, kws::launch_train_residual(s_dxq, s_du, 1.0f, cv.de, (size_t)M * H, st), "launch train_residual (d of the embedding)");
-    KWS_LAUNCH(h, kws::launch_train_wgrad(cv.jobs, cv.njobs, cv.units, cv.xs, cv.live, M, cv.chunk_rows, cv.chunks, cv.partial, h->P, st),
+    KWS_LAUNCH(h, kws::launch_train_wgrad(cv.jobs, cv.njobs, h->units, cv.xs, cv.live, M, cv.chunk_rows, cv.chunks, cv.partial, h->P, st),
                "launch train_wgrad");
     KWS_LAUNCH(h, kws::launch_train_reduce(cv.partial, cv.chunks, h->P, h->grad, h->sumsq, st), "launch train_reduce");
     return KWS_OK;
@@ -353,8 +282,7 @@ int kws_attention_train_create(const kws_attention_train_config* cfg, kws_attent
     const kws_attention_config& c = cfg->model;
     h->cfg = *cfg;
     h->lay = attn_layout(c);
-    h->P = h->lay.total;
-    h->nred = kws::train_reduce_blocks(h->P);
+    h->optimizer = cfg->optimizer; h->max_grad_norm = cfg->max_grad_norm;
     const int H = c.hidden;
     h->pe_rows = c.max_frames / c.combine_frame + 1;
     std::vector<float> pe((size_t)h->pe_rows * H);          // positional_encoding_op.cc:44-48: double, stored as float
@@ -364,77 +292,24 @@ int kws_attention_train_create(const kws_attention_train_config* cfg, kws_attent
             pe[(size_t)p * H + 2 * i] = (float)std::sin(a);
             pe[(size_t)p * H + 2 * i + 1] = (float)std::cos(a);
         }
-    size_t floats = 4 * h->P + pe.size();
-    floats = (floats + 1) & ~(size_t)1;          // the doubles behind it
-    h->state_bytes = floats * sizeof(float) + (size_t)h->nred * sizeof(double);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->state), h->state_bytes);
-    if (e == hipSuccess) e = hipMemset(h->state, 0, h->state_bytes);
-    if (e == hipSuccess) e = hipMemcpy(h->state + 4 * h->P, pe.data(), pe.size() * sizeof(float), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->last_done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { kws_attention_train_destroy(h); return hip_fail(e, "kws_attention_train_create"); }
-    h->theta = h->state; h->m = h->theta + h->P; h->v = h->m + h->P; h->grad = h->v + h->P; h->pe = h->grad + h->P;
-    h->sumsq = reinterpret_cast<double*>(h->state + floats);
+    const int rc = train_core_create(h, h->lay.total, pe.size(), pe.data(), "kws_attention_train_create");
+    if (rc != KWS_OK) { delete h; return rc; }
     *out = h;
     return KWS_OK;
 }
 
 int kws_attention_train_destroy(kws_attention_train_handle h) {
     if (!h) return KWS_OK;
-    hipDeviceSynchronize();
-    if (h->state) hipFree(h->state);
-    if (h->arena) hipFree(h->arena);
-    if (h->last_done) hipEventDestroy(h->last_done);
+    train_core_destroy(h);
     delete h;
     return KWS_OK;
 }
 
 int kws_attention_train_set_weights(kws_attention_train_handle h, const void* blob, size_t nbytes, void* stream) {
-    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
-    if (!blob) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
-    if (nbytes != h->P * sizeof(float)) return fail(KWS_ERR_INVALID_ARGUMENT, "the weight blob has %zu bytes, the config needs %zu", nbytes, h->P * sizeof(float));
-    BusyGuard guard(h->in_call);
-    if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this train handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KWS_TRY(enter(h, st));
-    KWS_TRY(finish(h, st, [&]() -> int {
-        KWS_HIP(hipMemcpyAsync(h->theta, blob, nbytes, hipMemcpyHostToDevice, st));
-        KWS_HIP(hipMemsetAsync(h->m, 0, 2 * h->P * sizeof(float), st));
-        h->steps = 0;
-        return KWS_OK;
-    }()));
-    KWS_HIP(hipStreamSynchronize(st));
-    return KWS_OK;
+    return train_set_weights(h, blob, nbytes, stream, nullptr);
 }
-
-int kws_attention_train_get_weights(kws_attention_train_handle h, void* blob, size_t nbytes, void* stream) {
-    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
-    if (!blob) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
-    if (nbytes != h->P * sizeof(float)) return fail(KWS_ERR_INVALID_ARGUMENT, "the weight blob has %zu bytes, the config needs %zu", nbytes, h->P * sizeof(float));
-    BusyGuard guard(h->in_call);
-    if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this train handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KWS_TRY(enter(h, st));
-    KWS_TRY(finish(h, st, hip_done(hipMemcpyAsync(blob, h->theta, nbytes, hipMemcpyDeviceToHost, st), "copy of the weights")));
-    KWS_HIP(hipStreamSynchronize(st));
-    return KWS_OK;
-}
-
-int kws_attention_train_moments(kws_attention_train_handle h, float* m, float* v, void* stream) {
-    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
-    if (!m || !v) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
-    BusyGuard guard(h->in_call);
-    if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this train handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KWS_TRY(enter(h, st));
-    KWS_TRY(finish(h, st, [&]() -> int {
-        KWS_HIP(hipMemcpyAsync(m, h->m, h->P * sizeof(float), hipMemcpyDeviceToHost, st));
-        KWS_HIP(hipMemcpyAsync(v, h->v, h->P * sizeof(float), hipMemcpyDeviceToHost, st));
-        return KWS_OK;
-    }()));
-    KWS_HIP(hipStreamSynchronize(st));
-    return KWS_OK;
-}
+int kws_attention_train_get_weights(kws_attention_train_handle h, void* blob, size_t nbytes, void* stream) { return train_get_weights(h, blob, nbytes, stream); }
+int kws_attention_train_moments(kws_attention_train_handle h, float* m, float* v, void* stream) { return train_moments(h, m, v, stream); }
 
 int kws_attention_train_reserve(kws_attention_train_handle h, int B, int T, int S_max) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
@@ -451,18 +326,14 @@ int kws_attention_train_grad(kws_attention_train_handle h, const float* x, const
     KWS_TRY(check_call(h->cfg, x, seq_len, labels, label_len, B, T, S_max, loss, &t1));
     if (!grad_blob) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
     if (misaligned(grad_blob) || misaligned(logits_or_null)) return fail(KWS_ERR_INVALID_ARGUMENT, "grad_blob and logits must be 4-byte aligned");
-    BusyGuard guard(h->in_call);
-    if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this train handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KWS_TRY(enter(h, st));
-    return finish(h, st, [&]() -> int {
+    return train_call(h, stream, [&](hipStream_t st) -> int {
         KWS_TRY(grad_impl(h, x, seq_len, t1, labels, label_len, B, T, S_max, drop_seed, loss, st));
         KWS_HIP(hipMemcpyAsync(grad_blob, h->grad, h->P * sizeof(float), hipMemcpyDeviceToDevice, st));
         if (logits_or_null)
             KWS_HIP(hipMemcpyAsync(logits_or_null, h->cv.logits, (size_t)B * h->cv.T1 * h->cfg.model.num_classes * sizeof(float),
                                    hipMemcpyDeviceToDevice, st));
         return KWS_OK;
-    }());
+    });
 }
 
 int kws_attention_train_step(kws_attention_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
@@ -472,31 +343,15 @@ int kws_attention_train_step(kws_attention_train_handle h, const float* x, const
     KWS_TRY(check_call(h->cfg, x, seq_len, labels, label_len, B, T, S_max, loss, &t1));
     if (!(lr > 0.f) || !std::isfinite(lr)) return fail(KWS_ERR_INVALID_ARGUMENT, "lr=%g has to be positive and finite", (double)lr);
     if (misaligned(grad_norm_or_null)) return fail(KWS_ERR_INVALID_ARGUMENT, "grad_norm must be 4-byte aligned");
-    BusyGuard guard(h->in_call);
-    if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this train handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KWS_TRY(enter(h, st));
-    return finish(h, st, [&]() -> int {
+    return train_call(h, stream, [&](hipStream_t st) -> int {
         KWS_TRY(grad_impl(h, x, seq_len, t1, labels, label_len, B, T, S_max, drop_seed, loss, st));
-        const bool adam = h->cfg.optimizer == KWS_OPT_ADAM;
-        const double step = (double)(h->steps + 1);
-        const float lr_t = adam ? (float)((double)lr * sqrt(1.0 - pow(0.999, step)) / (1.0 - pow(0.9, step))) : lr;
-        KWS_LAUNCH(h, kws::launch_train_update(h->theta, h->m, h->v, h->grad, h->sumsq, h->nred, h->P, adam ? 1 : 0, lr_t, h->cfg.max_grad_norm,
-                                               grad_norm_or_null, st), "launch train_update");
-        ++h->steps;
-        return KWS_OK;
-    }());
+        return train_update(h, lr, grad_norm_or_null, st);
+    });
 }
 
 int kws_attention_train_stats(kws_attention_train_handle h, size_t* device_bytes, int32_t* allocs, int32_t* steps, int32_t* launches,
                               int32_t* chunk_rows) {
-    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
-    if (device_bytes) *device_bytes = h->state_bytes + h->arena_bytes;
-    if (allocs) *allocs = h->allocs;
-    if (steps) *steps = h->steps;
-    if (launches) *launches = h->launches;
-    if (chunk_rows) *chunk_rows = h->cv.chunk_rows;
-    return KWS_OK;
+    return train_stats(h, h ? h->cv.chunk_rows : 0, device_bytes, allocs, steps, launches, chunk_rows);
 }
 
 }  // extern "C"

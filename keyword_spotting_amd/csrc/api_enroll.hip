@@ -1,7 +1,7 @@
 // C ABI of libkws_amd.so (include/kws_amd.h): the CTC loss as a whole-batch op and the customised-keyword enrolment handle.
 #include <new>
 
-#include "api_internal.h"
+#include "train_core.h"
 
 using namespace kws_host;
 
@@ -17,9 +17,7 @@ struct kws_enroll {
     std::vector<int32_t> ints_host;
     int allocs = 0;                  // device (re)allocations after create; each one waited for the device
     std::atomic<int> in_call{0};
-    hipStream_t last_stream = nullptr;
-    bool last_stream_valid = false;
-    hipEvent_t last_done = nullptr;
+    CallOrder order;                 // against the handle's previous call, as a train handle's (train_core.h)
 };
 
 namespace kws_host {
@@ -57,18 +55,6 @@ namespace {
 int enroll_device_probe() {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(KWS_ERR_NO_DEVICE, "no HIP device visible");
-    return KWS_OK;
-}
-
-// the ordering of a call against the handle's previous one (as a model handle's): another stream waits for last_done on the device
-int enroll_enter(kws_enroll* h, hipStream_t st) {
-    if (h->last_stream_valid && h->last_stream != st) KWS_HIP(hipStreamWaitEvent(st, h->last_done, 0));
-    return KWS_OK;
-}
-int enroll_leave(kws_enroll* h, hipStream_t st) {
-    KWS_HIP(hipEventRecord(h->last_done, st));
-    h->last_stream = st;
-    h->last_stream_valid = true;
     return KWS_OK;
 }
 
@@ -118,7 +104,7 @@ int kws_enroll_create(int H, int C, int n_new, int E, int K, kws_enroll_handle* 
     const size_t nw = (size_t)E * H * n_new, nb = (size_t)E * n_new;
     hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->state), 3 * (nw + nb) * sizeof(float));
     if (e == hipSuccess) e = hipMemset(h->state, 0, 3 * (nw + nb) * sizeof(float));
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->last_done, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->order.last_done, hipEventDisableTiming);
     if (e == hipSuccess) e = hipDeviceSynchronize();
     if (e != hipSuccess) { kws_enroll_destroy(h); return hip_fail(e, "kws_enroll_create"); }
     h->W = h->state; h->b = h->W + nw; h->mW = h->b + nb; h->mb = h->mW + nw; h->vW = h->mb + nb; h->vb = h->vW + nw;
@@ -131,7 +117,7 @@ int kws_enroll_destroy(kws_enroll_handle h) {
     hipDeviceSynchronize();
     if (h->state) hipFree(h->state);
     if (h->ints) hipFree(h->ints);
-    if (h->last_done) hipEventDestroy(h->last_done);
+    if (h->order.last_done) hipEventDestroy(h->order.last_done);
     delete h;
     return KWS_OK;
 }
@@ -143,12 +129,14 @@ int kws_enroll_set(kws_enroll_handle h, const float* Wn, const float* bn, void* 
     if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this enrolment handle");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t nw = (size_t)h->E * h->H * h->n, nb = (size_t)h->E * h->n;
-    KWS_TRY(enroll_enter(h, st));
-    KWS_HIP(hipMemcpyAsync(h->W, Wn, nw * sizeof(float), hipMemcpyDeviceToDevice, st));
-    KWS_HIP(hipMemcpyAsync(h->b, bn, nb * sizeof(float), hipMemcpyDeviceToDevice, st));
-    KWS_HIP(hipMemsetAsync(h->mW, 0, 2 * (nw + nb) * sizeof(float), st));
-    h->steps = 0;
-    return enroll_leave(h, st);
+    KWS_TRY(h->order.enter(st));
+    return h->order.finish(st, [&]() -> int {
+        KWS_HIP(hipMemcpyAsync(h->W, Wn, nw * sizeof(float), hipMemcpyDeviceToDevice, st));
+        KWS_HIP(hipMemcpyAsync(h->b, bn, nb * sizeof(float), hipMemcpyDeviceToDevice, st));
+        KWS_HIP(hipMemsetAsync(h->mW, 0, 2 * (nw + nb) * sizeof(float), st));
+        h->steps = 0;
+        return KWS_OK;
+    }());
 }
 
 int kws_enroll_fit(kws_enroll_handle h, const float* nn_outputs, const float* logits1, const int32_t* seq_len, const int32_t* labels,
@@ -171,30 +159,32 @@ int kws_enroll_fit(kws_enroll_handle h, const float* nn_outputs, const float* lo
     BusyGuard guard(h->in_call);
     if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this enrolment handle");
     hipStream_t st = static_cast<hipStream_t>(stream);
-    KWS_TRY(enroll_enter(h, st));
-    std::vector<int32_t> ints;
-    pack_ints(seq_len, labels, label_len, B, S_max, &ints);
-    if (ints.size() > h->ints_cap) {          // the first call at this shape: the block only grows (waits for the device once)
-        KWS_HIP(hipDeviceSynchronize());
-        if (h->ints) (void)hipFree(h->ints);
-        h->ints = nullptr; h->ints_cap = 0; h->ints_host.clear();
-        KWS_HIP(hipMalloc(reinterpret_cast<void**>(&h->ints), ints.size() * sizeof(int32_t)));
-        h->ints_cap = ints.size();
-        ++h->allocs;
-    }
-    if (ints != h->ints_host) {
-        KWS_HIP(hipMemcpyAsync(h->ints, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        h->ints_host.swap(ints);
-    }
-    kws::EnrollFitParams p = {};
-    p.nn = nn_outputs; p.logits1 = logits1;
-    p.seq_len = h->ints; p.label_len = h->ints + B; p.labels = h->ints + 2 * (size_t)B;
-    p.W = h->W; p.b = h->b; p.mW = h->mW; p.mb = h->mb; p.vW = h->vW; p.vb = h->vb;
-    p.loss_trace = loss_trace_or_null; p.lr = lr;
-    p.K = h->K; p.n = h->n; p.C = h->C; p.T = T; p.S_max = S_max; p.iterations = iterations; p.step0 = h->steps;
-    KWS_TRY(hip_done(kws::launch_enroll_fit(p, h->H, h->E, st), "launch enroll_fit"));
-    h->steps += iterations;
-    return enroll_leave(h, st);
+    KWS_TRY(h->order.enter(st));
+    return h->order.finish(st, [&]() -> int {
+        std::vector<int32_t> ints;
+        pack_ints(seq_len, labels, label_len, B, S_max, &ints);
+        if (ints.size() > h->ints_cap) {          // the first call at this shape: the block only grows (waits for the device once)
+            KWS_HIP(hipDeviceSynchronize());
+            if (h->ints) (void)hipFree(h->ints);
+            h->ints = nullptr; h->ints_cap = 0; h->ints_host.clear();
+            KWS_HIP(hipMalloc(reinterpret_cast<void**>(&h->ints), ints.size() * sizeof(int32_t)));
+            h->ints_cap = ints.size();
+            ++h->allocs;
+        }
+        if (ints != h->ints_host) {
+            KWS_HIP(hipMemcpyAsync(h->ints, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+            h->ints_host.swap(ints);
+        }
+        kws::EnrollFitParams p = {};
+        p.nn = nn_outputs; p.logits1 = logits1;
+        p.seq_len = h->ints; p.label_len = h->ints + B; p.labels = h->ints + 2 * (size_t)B;
+        p.W = h->W; p.b = h->b; p.mW = h->mW; p.mb = h->mb; p.vW = h->vW; p.vb = h->vb;
+        p.loss_trace = loss_trace_or_null; p.lr = lr;
+        p.K = h->K; p.n = h->n; p.C = h->C; p.T = T; p.S_max = S_max; p.iterations = iterations; p.step0 = h->steps;
+        KWS_TRY(hip_done(kws::launch_enroll_fit(p, h->H, h->E, st), "launch enroll_fit"));
+        h->steps += iterations;
+        return KWS_OK;
+    }());
 }
 
 int kws_enroll_get(kws_enroll_handle h, float* Wn, float* bn, void* stream) {
@@ -204,10 +194,12 @@ int kws_enroll_get(kws_enroll_handle h, float* Wn, float* bn, void* stream) {
     if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this enrolment handle");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t nw = (size_t)h->E * h->H * h->n, nb = (size_t)h->E * h->n;
-    KWS_TRY(enroll_enter(h, st));
-    KWS_HIP(hipMemcpyAsync(Wn, h->W, nw * sizeof(float), hipMemcpyDeviceToDevice, st));
-    KWS_HIP(hipMemcpyAsync(bn, h->b, nb * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return enroll_leave(h, st);
+    KWS_TRY(h->order.enter(st));
+    return h->order.finish(st, [&]() -> int {
+        KWS_HIP(hipMemcpyAsync(Wn, h->W, nw * sizeof(float), hipMemcpyDeviceToDevice, st));
+        KWS_HIP(hipMemcpyAsync(bn, h->b, nb * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return KWS_OK;
+    }());
 }
 
 int kws_enroll_moments(kws_enroll_handle h, float* m, float* v, void* stream) {
@@ -217,10 +209,12 @@ int kws_enroll_moments(kws_enroll_handle h, float* m, float* v, void* stream) {
     if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this enrolment handle");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t nm = (size_t)h->E * (h->H + 1) * h->n;
-    KWS_TRY(enroll_enter(h, st));
-    KWS_HIP(hipMemcpyAsync(m, h->mW, nm * sizeof(float), hipMemcpyDeviceToDevice, st));
-    KWS_HIP(hipMemcpyAsync(v, h->vW, nm * sizeof(float), hipMemcpyDeviceToDevice, st));
-    return enroll_leave(h, st);
+    KWS_TRY(h->order.enter(st));
+    return h->order.finish(st, [&]() -> int {
+        KWS_HIP(hipMemcpyAsync(m, h->mW, nm * sizeof(float), hipMemcpyDeviceToDevice, st));
+        KWS_HIP(hipMemcpyAsync(v, h->vW, nm * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return KWS_OK;
+    }());
 }
 
 int kws_enroll_stats(kws_enroll_handle h, size_t* device_bytes, int32_t* allocs, int32_t* steps) {

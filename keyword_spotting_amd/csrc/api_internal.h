@@ -1,6 +1,7 @@
 // Host-side state and helpers shared by the C ABI translation units of libkws_amd.so: one api_*.hip per surface (model, step, ops,
-// attention, attention_stream, window, frontend, stream -- which drives the two before it through kws_host --, enroll, bank), weight_pack.hip, selftest.hip.  Never
-// included by a kernel file: the kernel/host surface is kws_internal.h.
+// attention, attention_stream, window, frontend, stream -- which drives the two before it through kws_host --, enroll, bank, beam, train,
+// attention_train), weight_pack.hip, selftest.hip.  What only the train handles share -- and the call ordering the enrolment handle takes
+// from them -- is train_core.h / api_train_core.hip.  Never included by a kernel file: the kernel/host surface is kws_internal.h.
 #pragma once
 #include <algorithm>
 #include <atomic>
@@ -209,14 +210,6 @@ int check_labels(const int32_t* seq_len, const int32_t* labels, const int32_t* l
 bool misaligned(const void* p);      // not 4-byte aligned
 // ... [seq_len | label_len | labels] as the one block that travels to the device
 void pack_ints(const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int S_max, std::vector<int32_t>* out);
-
-// both train handles (api_train.hip, api_attention_train.hip): the rows of the weight-gradient reduction are summed in at most
-// kWgradMaxChunks chunks of a multiple of kWgradChunkUnit rows
-constexpr int kWgradChunkUnit = 256, kWgradMaxChunks = 64;
-inline int wgrad_chunk_rows(size_t rows) {
-    const size_t per = (rows + (size_t)kWgradChunkUnit * kWgradMaxChunks - 1) / ((size_t)kWgradChunkUnit * kWgradMaxChunks);
-    return (int)(kWgradChunkUnit * (per < 1 ? 1 : per));
-}
 
 // api_attention.hip: the canonical blob of the attention model (offsets in floats) and the refusals of its config, shared with the
 // train handle (api_attention_train.hip)

@@ -3,30 +3,20 @@
 // wrappers of kws_train_create_wrapped around the two frame loops (train_wrap_kernels.hip).
 #include <new>
 
-#include "api_internal.h"
+#include "train_core.h"
 
 using namespace kws_host;
 
-struct kws_train {
+struct kws_train : TrainCore {       // tail: the packed copies of every layer (wx, wh, wht, b3)
     kws_train_config cfg;
     BlobLayout bl;
     WrapLayout wl;                   // the layer norm's ibeta / igamma behind the canonical blob (kws_train_create_wrapped)
     bool ln = false, res = false, var = false;      // wrappers.use_layer_norm, wrappers.use_residual, variational_recurrent
-    size_t P = 0;                    // floats of the blob
-    // one allocation fixed at create: theta | m | v | grad [4 P], the packed copies of every layer (wx, wh, wht, b3), then the
-    // reduction's per-workgroup sums of squares (doubles)
-    float* state = nullptr;
-    float *theta = nullptr, *m = nullptr, *v = nullptr, *grad = nullptr;
     kws::TrainPackParams pack = {};
-    double* sumsq = nullptr;
-    size_t state_bytes = 0;
-    int nred = 0;
-    // one allocation that only grows, carved for the shape of the call (carve): lengths and labels, the row mask, the job table of the
+    // the arena, carved for the shape of the call (carve): lengths and labels, the row mask, the job table of the
     // weight-gradient launch, the tape, the gradients of the activations, the row chunks' partial weight gradients.  With the layer norm
     // a layer also keeps xhat and xn [M, I_l] and rstd [M] from the forward, g = dxhat [M, I_l] and gs [M] (the rows' terms of d ibeta)
     // from the backward; with the residual a layer >= 1 keeps out [M, H] = 0.7071 (y + its input)
-    char* arena = nullptr;
-    size_t arena_bytes = 0;
     struct Carved {
         int B = 0, T = 0, S_max = -1;
         int32_t* ints = nullptr;
@@ -34,76 +24,45 @@ struct kws_train {
         kws::TrainWgradJob* jobs = nullptr;
         float *xg = nullptr, *dy[2] = {nullptr, nullptr}, *logits = nullptr, *gl = nullptr, *partial = nullptr;
         struct Layer { float *ar, *au, *ac, *hp, *rh, *y, *dhat, *xhat, *xn, *rstd, *g, *gs, *out; } layer[8] = {};   // ar, au, ac: the pre-activations of r, u, c
-        int njobs = 0, units = 0, chunk_rows = 0, chunks = 0;
+        int njobs = 0, chunk_rows = 0, chunks = 0;
     } cv;
-    std::vector<kws::TrainWgradJob> jobs_host;
-    bool jobs_dirty = false;         // carved anew since the table last went to the device
-    std::vector<int32_t> ints_host;
-    int steps = 0, allocs = 0, launches = 0;
-    std::atomic<int> in_call{0};
-    hipStream_t last_stream = nullptr;
-    bool last_stream_valid = false;
-    hipEvent_t last_done = nullptr;
 };
 
 namespace {
 
-constexpr size_t kAlign = 256;
-size_t aligned(size_t n) { return (n + kAlign - 1) / kAlign * kAlign; }
 constexpr float kResidualScale = 0.7071067811865475f;      // utils/custom_wrapper.py:116
 
 bool residual_on(const kws_train* h, int l) { return h->res && l >= 1; }
 // what layer l hands to the layer above and to the dense layer
 const float* layer_output(const kws_train* h, const kws_train::Carved& cv, int l) { return residual_on(h, l) ? cv.layer[l].out : cv.layer[l].y; }
 
-int train_enter(kws_train* h, hipStream_t st) {
-    if (h->last_stream_valid && h->last_stream != st) KWS_HIP(hipStreamWaitEvent(st, h->last_done, 0));
-    return KWS_OK;
-}
-int train_leave(kws_train* h, hipStream_t st) {
-    KWS_HIP(hipEventRecord(h->last_done, st));
-    h->last_stream = st;
-    h->last_stream_valid = true;
-    return KWS_OK;
-}
-
-// ... at the end of a call's queued work, failed or not: launches that went out before a failure are still on `st`, and a following
-// call on another stream has to be ordered behind them.  rc: the call's result so far (its message stays the last error).
-int train_finish(kws_train* h, hipStream_t st, int rc) {
-    if (rc == KWS_OK) return train_leave(h, st);
-    if (hipEventRecord(h->last_done, st) == hipSuccess) { h->last_stream = st; h->last_stream_valid = true; }
-    return rc;
-}
-
 // Lays the arena out for (B, T, S_max).  base == null: only the size.  Returns the bytes.
 size_t carve(const kws_train* h, int B, int T, int S_max, char* base, kws_train::Carved* cv) {
     const kws_config& c = h->cfg.model;
     const size_t M = (size_t)B * T, H = (size_t)c.hidden;
-    size_t at = 0;
-    auto take = [&](size_t bytes) { char* p = base ? base + at : nullptr; at += aligned(bytes); return p; };
+    Carver cut(base);
     kws_train::Carved o;
     o.B = B; o.T = T; o.S_max = S_max;
     o.njobs = (h->ln ? 8 : 6) * c.num_layers + 2;
     o.chunk_rows = wgrad_chunk_rows(M);
     o.chunks = (int)((M + o.chunk_rows - 1) / o.chunk_rows);
-    o.ints = reinterpret_cast<int32_t*>(take((size_t)B * (2 + S_max) * sizeof(int32_t)));
-    o.live = reinterpret_cast<uint8_t*>(take(M));
-    o.jobs = reinterpret_cast<kws::TrainWgradJob*>(take((size_t)o.njobs * sizeof(kws::TrainWgradJob)));
-    auto floats = [&](size_t n) { return reinterpret_cast<float*>(take(n * sizeof(float))); };
-    o.xg = floats(M * 3 * H);
-    o.dy[0] = floats(M * H); o.dy[1] = floats(M * H);
-    o.logits = floats(M * c.num_classes); o.gl = floats(M * c.num_classes);
+    o.ints = reinterpret_cast<int32_t*>(cut.take((size_t)B * (2 + S_max) * sizeof(int32_t)));
+    o.live = reinterpret_cast<uint8_t*>(cut.take(M));
+    o.jobs = reinterpret_cast<kws::TrainWgradJob*>(cut.take((size_t)o.njobs * sizeof(kws::TrainWgradJob)));
+    o.xg = cut.floats(M * 3 * H);
+    o.dy[0] = cut.floats(M * H); o.dy[1] = cut.floats(M * H);
+    o.logits = cut.floats(M * c.num_classes); o.gl = cut.floats(M * c.num_classes);
     for (int l = 0; l < c.num_layers; ++l) {
         kws_train::Carved::Layer& y = o.layer[l];
-        y.ar = floats(M * H); y.au = floats(M * H); y.ac = floats(M * H); y.hp = floats(M * H); y.rh = floats(M * H); y.y = floats(M * H);
-        y.dhat = floats(M * 3 * H);
+        y.ar = cut.floats(M * H); y.au = cut.floats(M * H); y.ac = cut.floats(M * H); y.hp = cut.floats(M * H); y.rh = cut.floats(M * H); y.y = cut.floats(M * H);
+        y.dhat = cut.floats(M * 3 * H);
         const size_t in = (size_t)h->bl.layer[l].in;
-        if (h->ln) { y.xhat = floats(M * in); y.xn = floats(M * in); y.rstd = floats(M); y.g = floats(M * in); y.gs = floats(M); }
-        if (residual_on(h, l)) y.out = floats(M * H);
+        if (h->ln) { y.xhat = cut.floats(M * in); y.xn = cut.floats(M * in); y.rstd = cut.floats(M); y.g = cut.floats(M * in); y.gs = cut.floats(M); }
+        if (residual_on(h, l)) y.out = cut.floats(M * H);
     }
-    o.partial = floats((size_t)o.chunks * h->P);
+    o.partial = cut.floats((size_t)o.chunks * h->P);
     if (cv) *cv = o;
-    return at;
+    return cut.at;
 }
 
 // the products of the weight-gradient launch for the carved shape: per layer (Wg | Wc) x (input rows, state rows, bias), then the dense
@@ -112,75 +71,48 @@ size_t carve(const kws_train* h, int B, int T, int S_max, char* base, kws_train:
 void build_jobs(kws_train* h) {
     const kws_config& c = h->cfg.model;
     const int H = c.hidden, C = c.num_classes;
-    kws_train::Carved& cv = h->cv;
-    h->jobs_host.clear();
-    int unit = 0;
-    auto add = [&](int src, const float* a, int lda, int K, const float* d, int ldd, int N, size_t out, int ldo) {
-        kws::TrainWgradJob j = {};
-        j.a = a; j.d = d; j.out = out; j.src = src; j.lda = lda; j.K = K; j.ldd = ldd; j.N = N; j.ldo = ldo; j.unit0 = unit;
-        unit += ((K + 15) / 16) * ((N + 63) / 64);
-        h->jobs_host.push_back(j);
-    };
+    const kws_train::Carved& cv = h->cv;
     for (int l = 0; l < c.num_layers; ++l) {
         const BlobLayout::Layer& b = h->bl.layer[l];
         const kws_train::Carved::Layer& y = cv.layer[l];
         const int in = b.in, src = l == 0 && !h->ln ? kws::kWgradInput : kws::kWgradRows;
         const float* below = h->ln ? y.xhat : l == 0 ? nullptr : layer_output(h, cv, l - 1);
-        add(src, below, in, in, y.dhat, 3 * H, 2 * H, b.wg, 2 * H);
-        add(kws::kWgradRows, y.hp, H, H, y.dhat, 3 * H, 2 * H, b.wg + (size_t)in * 2 * H, 2 * H);
-        add(kws::kWgradOnes, nullptr, 0, 1, y.dhat, 3 * H, 2 * H, b.bg, 2 * H);
-        add(src, below, in, in, y.dhat + 2 * H, 3 * H, H, b.wc, H);
-        add(kws::kWgradRows, y.rh, H, H, y.dhat + 2 * H, 3 * H, H, b.wc + (size_t)in * H, H);
-        add(kws::kWgradOnes, nullptr, 0, 1, y.dhat + 2 * H, 3 * H, H, b.bc, H);
+        h->add_job(src, below, in, in, y.dhat, 3 * H, 2 * H, b.wg, 2 * H);
+        h->add_job(kws::kWgradRows, y.hp, H, H, y.dhat, 3 * H, 2 * H, b.wg + (size_t)in * 2 * H, 2 * H);
+        h->add_job(kws::kWgradOnes, nullptr, 0, 1, y.dhat, 3 * H, 2 * H, b.bg, 2 * H);
+        h->add_job(src, below, in, in, y.dhat + 2 * H, 3 * H, H, b.wc, H);
+        h->add_job(kws::kWgradRows, y.rh, H, H, y.dhat + 2 * H, 3 * H, H, b.wc + (size_t)in * H, H);
+        h->add_job(kws::kWgradOnes, nullptr, 0, 1, y.dhat + 2 * H, 3 * H, H, b.bc, H);
     }
-    add(kws::kWgradRows, layer_output(h, cv, c.num_layers - 1), H, H, cv.gl, C, C, h->bl.wfc, C);
-    add(kws::kWgradOnes, nullptr, 0, 1, cv.gl, C, C, h->bl.bfc, C);
+    h->add_job(kws::kWgradRows, layer_output(h, cv, c.num_layers - 1), H, H, cv.gl, C, C, h->bl.wfc, C);
+    h->add_job(kws::kWgradOnes, nullptr, 0, 1, cv.gl, C, C, h->bl.bfc, C);
     for (int l = 0; h->ln && l < c.num_layers; ++l) {
         const int in = h->bl.layer[l].in;
-        add(kws::kWgradOnes, nullptr, 0, 1, cv.layer[l].gs, 1, 1, h->wl.ibeta[l], 1);
-        add(kws::kWgradOnes, nullptr, 0, 1, cv.layer[l].g, in, in, h->wl.igamma[l], in);
+        h->add_job(kws::kWgradOnes, nullptr, 0, 1, cv.layer[l].gs, 1, 1, h->wl.ibeta[l], 1);
+        h->add_job(kws::kWgradOnes, nullptr, 0, 1, cv.layer[l].g, in, in, h->wl.igamma[l], in);
     }
-    cv.units = unit;
 }
 
 // the arena for (B, T, S_max): grown if it has to be (waits for the device once), carved anew when the shape differs from the last call's
 int prepare_shape(kws_train* h, int B, int T, int S_max) {
     if (h->cv.B == B && h->cv.T == T && h->cv.S_max == S_max && h->arena) return KWS_OK;
-    const size_t need = carve(h, B, T, S_max, nullptr, nullptr);
-    if (need > h->arena_bytes) {
-        size_t free_b = 0, total_b = 0;
-        KWS_HIP(hipMemGetInfo(&free_b, &total_b));
-        if (need > free_b + h->arena_bytes)
-            return fail(KWS_ERR_OUT_OF_MEMORY, "the tape of B=%d utterances x T=%d frames x %d layers takes %zu bytes: the device has %zu free "
-                        "(%zu in all; fewer utterances per step or shorter ones)", B, T, h->cfg.model.num_layers, need, free_b + h->arena_bytes, total_b);
-        KWS_HIP(hipDeviceSynchronize());
-        if (h->arena) (void)hipFree(h->arena);
-        h->arena = nullptr; h->arena_bytes = 0; h->cv = kws_train::Carved(); h->ints_host.clear();
-        KWS_HIP(hipMalloc(reinterpret_cast<void**>(&h->arena), need));
-        h->arena_bytes = need;
-        ++h->allocs;
-    }
+    const int rc = train_arena_reserve(h, carve(h, B, T, S_max, nullptr, nullptr), B, T, h->cfg.model.num_layers);
+    if (!h->arena) h->cv = kws_train::Carved();      // freed and not replaced: no layout
+    KWS_TRY(rc);
     carve(h, B, T, S_max, h->arena, &h->cv);
-    h->ints_host.clear();
     build_jobs(h);
-    h->jobs_dirty = true;
     return KWS_OK;
 }
 
 int check_call(const kws_train_config& cfg, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
                int S_max, const float* loss) {
     if (B < 1 || T < 1) return fail(KWS_ERR_INVALID_ARGUMENT, "bad shape B=%d T=%d: at least one utterance and one frame", B, T);
-    if (S_max < 0 || S_max > 31)
-        return fail(KWS_ERR_INVALID_ARGUMENT, "S_max=%d out of range [0,31]: one lane of a wave per state of the extended label", S_max);
+    KWS_TRY(check_s_max(S_max));
     if (!x || !seq_len || !label_len || !loss || (!labels && S_max > 0)) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
     if (misaligned(x) || misaligned(loss)) return fail(KWS_ERR_INVALID_ARGUMENT, "x and loss must be 4-byte aligned");
     if ((size_t)B * T > (size_t)0x7fffffff) return fail(KWS_ERR_UNSUPPORTED, "B=%d x T=%d: more than 2^31 - 1 frames in one call", B, T);
     KWS_TRY(check_labels(seq_len, labels, label_len, B, T, S_max, cfg.model.num_classes));
-    const size_t lds = kws::ctc_loss_lds_bytes(T, S_max);
-    if (lds > kWindowIncLdsMax)
-        return fail(KWS_ERR_UNSUPPORTED, "the CTC loss keeps %d frames x (8 log-probabilities + %d states) in LDS: %zu bytes exceed the %zu a "
-                    "workgroup may hold", T, 2 * S_max + 1, lds, kWindowIncLdsMax);
-    return KWS_OK;
+    return check_ctc_lds(T, S_max, "%d frames");
 }
 
 // the state pointers of a kws_train_*_state call: the kernels read and write a stream's state 16 bytes at a time
@@ -196,8 +128,6 @@ int check_state_io(const kws_train_state_io* io) {
 // a call from or to a carried state: any of the four fields set (none: the plain call, its launches and its bits)
 bool carries_state(const kws_train_state_io* io) { return io && (io->state_in || io->state_out || io->dstate_out || io->dstate_in); }
 
-#define KWS_LAUNCH(h, call, what) do { KWS_TRY(hip_done((call), what)); ++(h)->launches; } while (0)
-
 // forward, loss, backward: leaves loss [B], the logits and the gradient of sum(loss) / B + <dstate_out, state_out> (h->grad, with the sums
 // of squares of its blocks); io: null or all null for the zero state and no state outputs
 int grad_impl(kws_train* h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int S_max,
@@ -208,16 +138,9 @@ int grad_impl(kws_train* h, const float* x, const int32_t* seq_len, const int32_
     const size_t state_layer = (size_t)B * H;          // floats of one layer of [L, B, H]
     KWS_TRY(prepare_shape(h, B, T, S_max));
     kws_train::Carved& cv = h->cv;
-    if (h->jobs_dirty) {
-        KWS_HIP(hipMemcpyAsync(cv.jobs, h->jobs_host.data(), h->jobs_host.size() * sizeof(kws::TrainWgradJob), hipMemcpyHostToDevice, st));
-        h->jobs_dirty = false;
-    }
     std::vector<int32_t> ints;
     pack_ints(seq_len, labels, label_len, B, S_max, &ints);
-    if (ints != h->ints_host) {
-        KWS_HIP(hipMemcpyAsync(cv.ints, ints.data(), ints.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
-        h->ints_host.swap(ints);
-    }
+    KWS_TRY(train_upload(h, cv.jobs, cv.ints, &ints, st));
     const int32_t *d_seq = cv.ints, *d_len = cv.ints + B, *d_lab = cv.ints + 2 * (size_t)B;
     h->launches = 0;
     KWS_LAUNCH(h, kws::launch_train_rowmask(d_seq, B, T, cv.live, st), "launch train_rowmask");
@@ -307,21 +230,16 @@ int grad_impl(kws_train* h, const float* x, const int32_t* seq_len, const int32_
         }
         if (l > 0) cur ^= 1;
     }
-    KWS_LAUNCH(h, kws::launch_train_wgrad(cv.jobs, cv.njobs, cv.units, x, cv.live, M, cv.chunk_rows, cv.chunks, cv.partial, h->P, st),
+    KWS_LAUNCH(h, kws::launch_train_wgrad(cv.jobs, cv.njobs, h->units, x, cv.live, M, cv.chunk_rows, cv.chunks, cv.partial, h->P, st),
                "launch train_wgrad");
     KWS_LAUNCH(h, kws::launch_train_reduce(cv.partial, cv.chunks, h->P, h->grad, h->sumsq, st), "launch train_reduce");
     return KWS_OK;
 }
 
-// clip over h->grad (its blocks' sums of squares in h->sumsq), one optimiser step with the handle's moments and step count, re-pack
+// the optimiser step over h->grad, then the packed copies of the new weights
 int update_impl(kws_train* h, float lr, float* grad_norm_or_null, hipStream_t st) {
-    const bool adam = h->cfg.optimizer == KWS_OPT_ADAM;
-    const double step = (double)(h->steps + 1);
-    const float lr_t = adam ? (float)((double)lr * sqrt(1.0 - pow(0.999, step)) / (1.0 - pow(0.9, step))) : lr;
-    KWS_LAUNCH(h, kws::launch_train_update(h->theta, h->m, h->v, h->grad, h->sumsq, h->nred, h->P, adam ? 1 : 0, lr_t, h->cfg.max_grad_norm,
-                                           grad_norm_or_null, st), "launch train_update");
+    KWS_TRY(train_update(h, lr, grad_norm_or_null, st));
     KWS_LAUNCH(h, kws::launch_train_pack(h->pack, st), "launch train_pack");
-    ++h->steps;
     return KWS_OK;
 }
 
@@ -346,11 +264,7 @@ int check_config(const kws_train_config& cfg, bool wrapped) {
                         "one mask per stream: kws_train_create_wrapped)", cfg.variational_recurrent);
     }
     if (c.precision != KWS_FP32) return fail(KWS_ERR_UNSUPPORTED, "model.precision=%d: training is fp32 (KWS_FP32) only", c.precision);
-    if (!(cfg.keep_prob > 0.f && cfg.keep_prob <= 1.f))
-        return fail(KWS_ERR_UNSUPPORTED, "keep_prob=%g outside (0, 1]", (double)cfg.keep_prob);
-    if (cfg.optimizer != KWS_OPT_ADAM && cfg.optimizer != KWS_OPT_NESTEROV)
-        return fail(KWS_ERR_INVALID_ARGUMENT, "optimizer=%d: KWS_OPT_ADAM (0) or KWS_OPT_NESTEROV (1)", cfg.optimizer);
-    if (!std::isfinite(cfg.max_grad_norm)) return fail(KWS_ERR_INVALID_ARGUMENT, "max_grad_norm=%g is not finite", (double)cfg.max_grad_norm);
+    KWS_TRY(check_optimizer(cfg.keep_prob, cfg.optimizer, cfg.max_grad_norm));
     if (c.hidden != 64 && c.hidden != 128 && c.hidden != 256) return fail(KWS_ERR_INVALID_ARGUMENT, "model.hidden=%d unsupported (64, 128, 256)", c.hidden);
     if (c.num_layers < 1 || c.num_layers > 8) return fail(KWS_ERR_INVALID_ARGUMENT, "model.num_layers=%d out of range [1,8]", c.num_layers);
     if (c.n_mel < 1 || c.n_mel > 1024) return fail(KWS_ERR_INVALID_ARGUMENT, "model.n_mel=%d out of range [1,1024]", c.n_mel);
@@ -378,31 +292,23 @@ int create_impl(const kws_train_config* cfg, bool wrapped, kws_train_handle* out
     h->bl = blob_layout(c);
     h->wl = wrap_layout(c, cfg->wrappers);
     h->ln = cfg->wrappers.use_layer_norm != 0; h->res = cfg->wrappers.use_residual != 0; h->var = cfg->variational_recurrent != 0;
-    h->P = h->wl.total;          // the canonical blob's, without the layer norm
-    h->nred = kws::train_reduce_blocks(h->P);
+    h->optimizer = cfg->optimizer; h->max_grad_norm = cfg->max_grad_norm;
     const size_t H = (size_t)c.hidden;
-    size_t floats = 4 * h->P;
-    size_t pk_at[8];
+    size_t pk_at[8], packed = 0;
     for (int l = 0; l < c.num_layers; ++l) {
-        pk_at[l] = floats;
-        floats += ((size_t)h->bl.layer[l].in + 2 * H) * 3 * H + 3 * H;
+        pk_at[l] = packed;
+        packed += ((size_t)h->bl.layer[l].in + 2 * H) * 3 * H + 3 * H;
     }
-    floats = (floats + 1) & ~(size_t)1;          // the doubles behind it
-    h->state_bytes = floats * sizeof(float) + (size_t)h->nred * sizeof(double);
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&h->state), h->state_bytes);
-    if (e == hipSuccess) e = hipMemset(h->state, 0, h->state_bytes);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&h->last_done, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e != hipSuccess) { kws_train_destroy(h); return hip_fail(e, "kws_train_create"); }
-    h->theta = h->state; h->m = h->theta + h->P; h->v = h->m + h->P; h->grad = h->v + h->P;
-    h->sumsq = reinterpret_cast<double*>(h->state + floats);
+    // wl.total: the canonical blob's, without the layer norm
+    const int rc = train_core_create(h, h->wl.total, packed, nullptr, "kws_train_create");
+    if (rc != KWS_OK) { delete h; return rc; }
     h->pack.L = c.num_layers; h->pack.H = c.hidden;
     for (int l = 0; l < c.num_layers; ++l) {
         const BlobLayout::Layer& b = h->bl.layer[l];
         kws::TrainPackLayer& p = h->pack.layer[l];
         p.in = b.in;
         p.wg = h->theta + b.wg; p.bg = h->theta + b.bg; p.wc = h->theta + b.wc; p.bc = h->theta + b.bc;
-        p.wx = h->state + pk_at[l]; p.wh = p.wx + (size_t)b.in * 3 * H; p.wht = p.wh + H * 3 * H; p.b3 = p.wht + 3 * H * H;
+        p.wx = h->tail + pk_at[l]; p.wh = p.wx + (size_t)b.in * 3 * H; p.wht = p.wh + H * 3 * H; p.b3 = p.wht + 3 * H * H;
     }
     *out = h;
     return KWS_OK;
@@ -443,61 +349,16 @@ int kws_train_check_state(const kws_train_config* cfg, int wrapped, const float*
 
 int kws_train_destroy(kws_train_handle h) {
     if (!h) return KWS_OK;
-    hipDeviceSynchronize();
-    if (h->state) hipFree(h->state);
-    if (h->arena) hipFree(h->arena);
-    if (h->last_done) hipEventDestroy(h->last_done);
+    train_core_destroy(h);
     delete h;
     return KWS_OK;
 }
 
 int kws_train_set_weights(kws_train_handle h, const void* blob, size_t nbytes, void* stream) {
-    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
-    if (!blob) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
-    if (nbytes != h->P * sizeof(float)) return fail(KWS_ERR_INVALID_ARGUMENT, "the weight blob has %zu bytes, the config needs %zu", nbytes, h->P * sizeof(float));
-    BusyGuard guard(h->in_call);
-    if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this train handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KWS_TRY(train_enter(h, st));
-    KWS_TRY(train_finish(h, st, [&]() -> int {
-        KWS_HIP(hipMemcpyAsync(h->theta, blob, nbytes, hipMemcpyHostToDevice, st));
-        KWS_HIP(hipMemsetAsync(h->m, 0, 2 * h->P * sizeof(float), st));
-        KWS_TRY(hip_done(kws::launch_train_pack(h->pack, st), "launch train_pack"));
-        h->steps = 0;
-        return KWS_OK;
-    }()));
-    KWS_HIP(hipStreamSynchronize(st));
-    return KWS_OK;
+    return train_set_weights(h, blob, nbytes, stream, [h](hipStream_t st) { return hip_done(kws::launch_train_pack(h->pack, st), "launch train_pack"); });
 }
-
-int kws_train_get_weights(kws_train_handle h, void* blob, size_t nbytes, void* stream) {
-    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
-    if (!blob) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
-    if (nbytes != h->P * sizeof(float)) return fail(KWS_ERR_INVALID_ARGUMENT, "the weight blob has %zu bytes, the config needs %zu", nbytes, h->P * sizeof(float));
-    BusyGuard guard(h->in_call);
-    if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this train handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KWS_TRY(train_enter(h, st));
-    KWS_TRY(train_finish(h, st, hip_done(hipMemcpyAsync(blob, h->theta, nbytes, hipMemcpyDeviceToHost, st), "copy of the weights")));
-    KWS_HIP(hipStreamSynchronize(st));
-    return KWS_OK;
-}
-
-int kws_train_moments(kws_train_handle h, float* m, float* v, void* stream) {
-    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
-    if (!m || !v) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
-    BusyGuard guard(h->in_call);
-    if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this train handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KWS_TRY(train_enter(h, st));
-    KWS_TRY(train_finish(h, st, [&]() -> int {
-        KWS_HIP(hipMemcpyAsync(m, h->m, h->P * sizeof(float), hipMemcpyDeviceToHost, st));
-        KWS_HIP(hipMemcpyAsync(v, h->v, h->P * sizeof(float), hipMemcpyDeviceToHost, st));
-        return KWS_OK;
-    }()));
-    KWS_HIP(hipStreamSynchronize(st));
-    return KWS_OK;
-}
+int kws_train_get_weights(kws_train_handle h, void* blob, size_t nbytes, void* stream) { return train_get_weights(h, blob, nbytes, stream); }
+int kws_train_moments(kws_train_handle h, float* m, float* v, void* stream) { return train_moments(h, m, v, stream); }
 
 int kws_train_reserve(kws_train_handle h, int B, int T, int S_max) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
@@ -522,17 +383,13 @@ int kws_train_grad_state(kws_train_handle h, const float* x, const int32_t* seq_
     if (misaligned(grad_blob) || misaligned(logits_or_null) || misaligned(drop_or_null))
         return fail(KWS_ERR_INVALID_ARGUMENT, "grad_blob, logits and drop must be 4-byte aligned (the masks are read four units at a time)");
     KWS_TRY(check_state_io(io));
-    BusyGuard guard(h->in_call);
-    if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this train handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KWS_TRY(train_enter(h, st));
-    return train_finish(h, st, [&]() -> int {
+    return train_call(h, stream, [&](hipStream_t st) -> int {
         KWS_TRY(grad_impl(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, loss, io, st));
         KWS_HIP(hipMemcpyAsync(grad_blob, h->grad, h->P * sizeof(float), hipMemcpyDeviceToDevice, st));
         if (logits_or_null)
             KWS_HIP(hipMemcpyAsync(logits_or_null, h->cv.logits, (size_t)B * T * h->cfg.model.num_classes * sizeof(float), hipMemcpyDeviceToDevice, st));
         return KWS_OK;
-    }());
+    });
 }
 
 int kws_train_step(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
@@ -549,14 +406,10 @@ int kws_train_step_state(kws_train_handle h, const float* x, const int32_t* seq_
     if (misaligned(grad_norm_or_null) || misaligned(drop_or_null))
         return fail(KWS_ERR_INVALID_ARGUMENT, "grad_norm and drop must be 4-byte aligned (the masks are read four units at a time)");
     KWS_TRY(check_state_io(io));
-    BusyGuard guard(h->in_call);
-    if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this train handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KWS_TRY(train_enter(h, st));
-    return train_finish(h, st, [&]() -> int {
+    return train_call(h, stream, [&](hipStream_t st) -> int {
         KWS_TRY(grad_impl(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, loss, io, st));
         return update_impl(h, lr, grad_norm_or_null, st);
-    }());
+    });
 }
 
 int kws_train_apply(kws_train_handle h, const float* grad_blob, float lr, float* grad_norm_or_null, void* stream) {
@@ -564,26 +417,16 @@ int kws_train_apply(kws_train_handle h, const float* grad_blob, float lr, float*
     if (!grad_blob) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
     if (!(lr > 0.f) || !std::isfinite(lr)) return fail(KWS_ERR_INVALID_ARGUMENT, "lr=%g has to be positive and finite", (double)lr);
     if (misaligned(grad_blob) || misaligned(grad_norm_or_null)) return fail(KWS_ERR_INVALID_ARGUMENT, "grad_blob and grad_norm must be 4-byte aligned");
-    BusyGuard guard(h->in_call);
-    if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this train handle");
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    KWS_TRY(train_enter(h, st));
-    return train_finish(h, st, [&]() -> int {
+    return train_call(h, stream, [&](hipStream_t st) -> int {
         h->launches = 0;
         // the caller's gradient as the one chunk of the reduction: h->grad = 0 + g, the blocks' sums of squares as behind a backward pass
         KWS_LAUNCH(h, kws::launch_train_reduce(grad_blob, 1, h->P, h->grad, h->sumsq, st), "launch train_reduce");
         return update_impl(h, lr, grad_norm_or_null, st);
-    }());
+    });
 }
 
 int kws_train_stats(kws_train_handle h, size_t* device_bytes, int32_t* allocs, int32_t* steps, int32_t* launches, int32_t* chunk_rows) {
-    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
-    if (device_bytes) *device_bytes = h->state_bytes + h->arena_bytes;
-    if (allocs) *allocs = h->allocs;
-    if (steps) *steps = h->steps;
-    if (launches) *launches = h->launches;
-    if (chunk_rows) *chunk_rows = h->cv.chunk_rows;
-    return KWS_OK;
+    return train_stats(h, h ? h->cv.chunk_rows : 0, device_bytes, allocs, steps, launches, chunk_rows);
 }
 
 }  // extern "C"

@@ -14,14 +14,14 @@ import numpy as np
 
 from . import _lib
 from . import weights as _weights
-from .custom_keyword import _ints, _pack_labels
+from ._trainer import _TrainerBase, exponential_decay
 
 OPTIMIZERS = {"adam": _lib.OPT_ADAM, "nesterov": _lib.OPT_NESTEROV}
 
 
 def learning_rate_at(step, learning_rate=1.5e-3, lr_decay=0.8, decay_step=20000):
     """tf.train.exponential_decay(learning_rate, global_step, decay_step, lr_decay), staircase=False (models/rnn_ctc.py:76-78)."""
-    return float(learning_rate) * float(lr_decay) ** (float(step) / float(decay_step))
+    return exponential_decay(learning_rate, step, decay_step, lr_decay)
 
 
 def segment_lengths(lengths, start, frames):
@@ -43,7 +43,7 @@ def train_config(config, optimizer="adam", max_grad_norm=-1.0, keep_prob=1.0):
                                float(max_grad_norm), float(keep_prob))
 
 
-class Trainer(object):
+class Trainer(_TrainerBase):
     """The reference's training graph on one device.  Defaults: config/rnn_config.py:44-55,77 (learning_rate 1.5e-3, lr_decay 0.8,
     decay_step 20000, adam, max_grad_norm -1 = no clipping); keep_prob defaults to 1 (the reference file ships 0.6, :81).
 
@@ -55,6 +55,8 @@ class Trainer(object):
     state_noise: > 0 starts every step() that is given no state from state_noise * randn([L,B,H]) (the reference README's "noisy
     states": a model served with carried state never sees the zero state after its first chunk)."""
 
+    _prefix, _weights_mod, _feature = "kws_train", _weights, "n_mel"
+
     def __init__(self, config, weights=None, optimizer="adam", learning_rate=1.5e-3, lr_decay=0.8, decay_step=20000, max_grad_norm=-1,
                  keep_prob=1.0, seed=0, device="cuda:0", wrapped=None, state_noise=0.0):
         import torch
@@ -62,38 +64,16 @@ class Trainer(object):
         self.optimizer, self.learning_rate, self.lr_decay, self.decay_step = optimizer, float(learning_rate), float(lr_decay), int(decay_step)
         self.max_grad_norm, self.keep_prob, self.state_noise = float(max_grad_norm), float(keep_prob), float(state_noise)
         self._cfg = train_config(config, optimizer, max_grad_norm, keep_prob)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise _lib.InvalidArgumentError(-1, "Trainer needs a CUDA/HIP device, got %s" % device)
-        self._lib = _lib.load()
-        self._handle = ctypes.c_void_p()
         self.variational = bool(self._cfg.variational_recurrent)
         if wrapped is None:
             wrapped = self.variational or bool(self._cfg.wrappers.use_layer_norm) or bool(self._cfg.wrappers.use_residual)
-        create = self._lib.kws_train_create_wrapped if wrapped else self._lib.kws_train_create
-        with torch.cuda.device(self.device):
-            _lib.check(create(ctypes.byref(self._cfg), ctypes.byref(self._handle)))
+        self._open(device, "kws_train_create_wrapped" if wrapped else "kws_train_create")
         self._gen = torch.Generator(device=self.device)
         self._gen.manual_seed(int(seed))
         self.global_step = 0
         if weights is None:
             weights = _weights.init_weights(config, seed=seed)
         self.set_weights(weights)
-
-    # -- lifecycle ---------------------------------------------------------------------------
-    def close(self):
-        if getattr(self, "_handle", None) is not None and self._handle.value:
-            self._lib.kws_train_destroy(self._handle)
-            self._handle = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _stream(self):
-        return _lib.current_stream_ptr()
 
     def _floats(self):
         """Floats of the handle's blobs: the canonical blob and, with the layer norm, every layer's ibeta and igamma behind it."""
@@ -104,34 +84,6 @@ class Trainer(object):
         return (cfg.num_layers, b, cfg.hidden_size) if self.variational else (cfg.num_layers, b, t, cfg.hidden_size)
 
     # -- parameters --------------------------------------------------------------------------
-    def set_weights(self, weights):
-        """Loads parameters; zeroes the optimiser's moments and the step count of its bias corrections."""
-        import torch
-        blob = weights if isinstance(weights, np.ndarray) else _weights.to_blob(self.config, weights)
-        blob = np.ascontiguousarray(blob, np.float32)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_train_set_weights(self._handle, blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes, self._stream()))
-
-    def weights_blob(self):
-        import torch
-        blob = np.empty(self._floats(), np.float32)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_train_get_weights(self._handle, blob.ctypes.data_as(ctypes.c_void_p), blob.nbytes, self._stream()))
-        return blob
-
-    def weights(self):
-        """The current parameters in the canonical dict form (weights.from_blob)."""
-        return _weights.from_blob(self.config, self.weights_blob())
-
-    def moments(self):
-        """(m, v) in the dict form: Adam's moments; Nesterov's accumulator and zeros."""
-        import torch
-        n = self._floats()
-        m, v = np.empty(n, np.float32), np.empty(n, np.float32)
-        with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_train_moments(self._handle, m.ctypes.data_as(ctypes.c_void_p), v.ctypes.data_as(ctypes.c_void_p), self._stream()))
-        return _weights.from_blob(self.config, m), _weights.from_blob(self.config, v)
-
     def save(self, path):
         _weights.save_npz(path, self.weights())
 
@@ -147,39 +99,20 @@ class Trainer(object):
             setattr(cfg, k, v)
         return DeployModel(cfg, self.weights_blob(), device=str(self.device), kernel=kernel)
 
-    def reserve(self, batch, frames, max_label=31):
-        _lib.check(self._lib.kws_train_reserve(self._handle, int(batch), int(frames), int(max_label)))
-
-    def stats(self):
-        """dict(device_bytes, allocs, steps, launches of the last call, chunk_rows of the weight-gradient reduction)."""
-        nbytes = ctypes.c_size_t()
-        a, s, l, c = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
-        _lib.check(self._lib.kws_train_stats(self._handle, ctypes.byref(nbytes), ctypes.byref(a), ctypes.byref(s), ctypes.byref(l), ctypes.byref(c)))
-        return dict(device_bytes=int(nbytes.value), allocs=a.value, steps=s.value, launches=l.value, chunk_rows=c.value)
-
     # -- compute -----------------------------------------------------------------------------
     def learning_rate_at(self, step):
         return learning_rate_at(step, self.learning_rate, self.lr_decay, self.decay_step)
 
     def _inputs(self, x, lengths, labels, drop):
         import torch
-        cfg = self.config
-        x = torch.as_tensor(x)
-        if x.dim() != 3 or x.shape[2] != cfg.n_mel:
-            raise _lib.InvalidArgumentError(-1, "x must be [B,T,%d], got %s" % (cfg.n_mel, tuple(x.shape)))
-        x = x.to(device=self.device, dtype=torch.float32).contiguous()
-        b, t = int(x.shape[0]), int(x.shape[1])
-        lab, lab_len = _pack_labels(labels, b)
-        sl = np.full(b, t) if lengths is None else np.asarray(lengths)
-        if sl.shape != (b,):
-            raise _lib.InvalidArgumentError(-1, "lengths: %s for %d utterances" % (sl.shape, b))
+        x, b, t, sl, lab, lab_len = super(Trainer, self)._inputs(x, lengths, labels)
         if drop is not None:
             drop = torch.as_tensor(drop).to(device=self.device, dtype=torch.uint8).contiguous()
             if tuple(drop.shape) != self._drop_shape(b, t):
                 raise _lib.InvalidArgumentError(-1, "drop must be [%s]%s, got %s" % (",".join(map(str, self._drop_shape(b, t))),
                                                     " (variational_recurrent: one mask per stream and layer)" if self.variational else "",
                                                     tuple(drop.shape)))
-        return x, b, t, _ints(sl), _ints(lab), _ints(lab_len), drop
+        return x, b, t, sl, lab, lab_len, drop
 
     def zero_state(self, batch):
         """[L,B,H] zeros on the trainer's device: the state every call without state= starts from."""
