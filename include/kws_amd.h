@@ -20,6 +20,8 @@
  *                              columns of the class projection (models/rnn_ctc.py:59-101), frozen stack
  *   kws_ctc_beam_search        tf.nn.ctc_beam_search_decoder as models/rnn_ctc.py:105-110, :166-176 would call it (commented out
  *                              there): top paths and their log-probabilities
+ *   kws_ctc_align              the "alignment for word" the README's frame-wise experiment (README.md:48,72) took from an outside
+ *                              model that "can only label the peak frame of each word": word spans, best path, posteriors
  *   kws_octbit_matmul          REGISTER_OP("OctbitMatMul") octbit/octbit_ops_reg.cc:7-15,
  *                              OctbitMatMulOp::Compute octbit/octbit_mat_mul_op.cc:49-183
  *   kws_octbit_quantize        octize_weight_int8_signed octbit/octbit_graph.py:191-215
@@ -551,6 +553,31 @@ int kws_step_heads_window(kws_handle model, const float* mel, const float* state
  *                  occupancy / P, zero at t >= seq_len[b].  One wave per utterance. */
 int kws_ctc_loss(const float* logits, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int C, int S_max,
                  float* loss, float* grad_logits_or_null, void* stream);
+/* CTC forced alignment: given the transcript, where in the utterance each label lies and how sure the model is of it.  kws_ctc_loss's
+ * conventions: logits [B,T,C] f32 device, C in 3..8, the blank is the LAST class, extended label blank, l_1, blank, ..., l_S, blank with
+ * S <= 31 and L = 2S + 1 states; seq_len [B], labels [B,S_max], label_len [B] are HOST memory, range-checked before anything is launched
+ * and shipped as one stream-ordered block; frames t >= seq_len[b] are never read.  One wave per utterance; stateless, stream-ordered,
+ * allocates only that block, never synchronises.
+ *   score  [B] f32 out (required): the log-probability of the best single path through the extended label -- the loss's recursion over the
+ *          log-softmax rows with max in place of log-add-exp (Viterbi).
+ *   states [B,T] i32 out or NULL: that path's state at every frame, 0..2S (even: a blank, 2k+1: label k); -1 at t >= seq_len[b].
+ *   spans  [B,S_max,2] i32 out or NULL: first and last frame (inclusive) the path spends in label k (state 2k+1); -1 at k >= label_len[b].
+ *          On a valid path every label has a span, and the spans are disjoint and increasing.
+ *   loss   [B] f32 out or NULL: -log P(label), bit-identical to kws_ctc_loss's value on the same arguments.
+ *   post   [B,T,S_max] f32 out or NULL: the posterior occupancy of label state 2k+1 at frame t given the label, exp(alpha + beta - lp +
+ *          loss) clamped to 1 -- the quantity kws_ctc_loss's gradient sums per class --, in [0,1]; 0 at t >= seq_len[b] and at
+ *          k >= label_len[b].  The blank states are not written: their total at a frame is 1 - sum_k post[b,t,k].
+ * Ties, so that one input always gives the same bits: at every (frame, state) a predecessor replaces the current choice only when it is
+ * strictly greater, tried in the order stay, s-1, s-2 (s-2 only between different labels); the path ends in state L-1 unless L-2 is
+ * strictly greater.
+ *   seq_len[b] == 0 (an empty slot, its label ignored):  score 0, loss 0, states -1, spans -1, post 0.
+ *   no valid path (seq_len < S + repeats):                score -inf, loss +inf, states -1, spans -1, post 0.
+ * LDS per utterance: 4 T (13 + A) bytes -- 8 log-probabilities, 4 words of back-pointers and 1 state per frame, and A = 2 S_max + 1
+ * states of alpha when loss or post is asked for, A = 0 otherwise.  Every refusal is decided before the device is probed: a NULL among
+ * the required pointers, the ranges above, a pointer that is not 4-byte aligned, a length or label out of range
+ * (KWS_ERR_INVALID_ARGUMENT); more than 160 KiB of LDS (KWS_ERR_UNSUPPORTED with the byte counts). */
+int kws_ctc_align(const float* logits, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int C, int S_max,
+                  int32_t* states_or_null, int32_t* spans_or_null, float* score, float* loss_or_null, float* post_or_null, void* stream);
 /* An enrolment handle: E independent enrolments of K utterance slots each (K in 1..4, B = E*K utterances, enrolment e owns
  * utterances e*K .. e*K+K-1), for a model of hidden size H (64, 128, 256) whose trained head has C classes (3..7) and n_new new
  * ones (C + n_new <= 8).  It owns the new columns Wn [E,H,n_new], their bias bn [E,n_new], Adam's two moments and the step count.

@@ -182,6 +182,7 @@ _SIGNATURES = {
     "kws_attention_stream_stats": (_i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32)]),
     "kws_ctc_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "kws_ctc_beam_search": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp]),
+    "kws_ctc_align": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "kws_enroll_create": (_i, [_i, _i, _i, _i, _i, ctypes.POINTER(_vp)]),
     "kws_enroll_destroy": (_i, [_vp]),
     "kws_enroll_set": (_i, [_vp, _vp, _vp, _vp]),

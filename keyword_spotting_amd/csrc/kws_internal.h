@@ -476,6 +476,16 @@ inline size_t enroll_fit_lds_bytes(int H, int n, int K, int T, int S_max) {
 // logits [B,T,C]; seq_len / label_len [B], labels [B,S_max]: device copies the host side has range-checked; grad [B,T,C] or null
 hipError_t launch_ctc_loss(const float* logits, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int C,
                            int S_max, float* loss, float* grad, hipStream_t st);
+// align_kernels.hip: CTC forced alignment, one wave per utterance.  LDS: lp [T][8] floats | the Viterbi back-pointers, two 64-bit masks
+// per frame | the path's state per frame, [T] int32 | and, only when the loss or the posteriors are asked for, alpha [T][2 S_max + 1]
+// floats: 4 T (13 + (2 S_max + 1 if with_alpha)) bytes
+inline size_t ctc_align_lds_bytes(int T, int S_max, bool with_alpha) {
+    return (size_t)T * (sizeof(float) * 8 + 2 * sizeof(unsigned long long) + sizeof(int32_t) + (with_alpha ? sizeof(float) * (2 * S_max + 1) : 0));
+}
+// logits [B,T,C]; seq_len / label_len [B], labels [B,S_max]: device copies the host side has range-checked; states [B,T], spans
+// [B,S_max,2], loss [B], post [B,T,S_max]: each or null; score [B]
+hipError_t launch_ctc_align(const float* logits, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int C,
+                            int S_max, int32_t* states, int32_t* spans, float* score, float* loss, float* post, hipStream_t st);
 // beam_kernels.hip: CTC prefix beam search, one wave per utterance.  A beam of at most kBeamMax prefixes of at most kBeamRow labels
 // (a row of bytes each, double-buffered); a frame has at most kBeamMax stays + kBeamMax x 7 extensions = kBeamCandidates candidates.
 // LDS: lp [T][8] | the candidates' 64-bit keys | their merged-away stamps | the next beam's (lp_b, lp_nb, source) | the two string buffers

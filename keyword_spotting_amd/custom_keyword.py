@@ -18,6 +18,12 @@ three utterances with the CTC loss and Adam (models/rnn_ctc.py:59-101):
 
 The stack runs once (kws_step_heads: nn_outputs and head 1's logits); every optimiser step is inside kws_enroll_fit.
 
+Whether the new words were found in those recordings, and where, before the columns go anywhere (kws_ctc_align: the best path through
+the transcript, a first and last frame per label, the posterior of every label at every frame):
+
+    found = enroller.align(mel, lengths, labels, new_columns, new_bias)     # Alignment(states, spans, score, loss, post)
+    targets = frame_labels(ctc_align(logits, lengths, labels).states, labels, blank)      # frame-wise targets of any CTC model
+
 Serving thousands of users who each enrolled their own keyword takes ONE bank of those columns on one frozen model, not a model handle
 per user:
 
@@ -40,6 +46,7 @@ noise per batch of optimiser steps:
     clean, noise = frontend.linear(utterances, n_samples), frontend.linear(noise_clips, noise_samples)
     new_columns, new_bias, loss_trace = enroller.fit_augmented(frontend, clean, noise, NoiseAugmenter(seed=1), labels, steps=100)
 """
+import collections
 import copy
 import ctypes
 
@@ -112,6 +119,57 @@ def ctc_loss(logits, seq_len, labels, want_grad=True):
         _lib.check(lib.kws_ctc_loss(_lib.ptr(lg), sl_p, lab_p, lab_len_p, b, t, c, int(lab.shape[1]), _lib.ptr(loss), _lib.ptr(grad),
                                     _lib.current_stream_ptr()))
     return loss, grad
+
+
+Alignment = collections.namedtuple("Alignment", ["states", "spans", "score", "loss", "post"])
+
+
+def ctc_align(logits, seq_len, labels, want_post=False):
+    """kws_ctc_align: where in each utterance the labels of its transcript lie.  logits [B,T,C] (device tensor or array; the blank is
+    class C-1), seq_len [B] or None, labels: B sequences over 0..C-2 (or one for all), as ctc_loss takes them -> Alignment of device
+    tensors: states [B,T] int32, the best path's state of the extended label per frame (2k+1: label k, even: a blank, -1 past
+    seq_len); spans [B,S_max,2] int32, first and last frame (inclusive) of label k, -1 past the utterance's labels; score [B], the best
+    path's log-probability; loss [B], ctc_loss's value bit for bit; post [B,T,S_max], the posterior of label k at frame t (None unless
+    want_post).  An empty slot (seq_len 0) has score 0, loss 0; an utterance without a valid path score -inf, loss +inf; both have
+    states and spans of -1 and zero posteriors."""
+    import torch
+    lib = _lib.load()
+    lg = torch.as_tensor(logits)
+    if lg.dim() != 3:
+        raise _lib.InvalidArgumentError(-1, "logits must be [B,T,C], got %s" % (tuple(lg.shape),))
+    if not lg.is_cuda:
+        lg = lg.to("cuda:0")
+    lg = lg.to(torch.float32).contiguous()
+    b, t, c = (int(v) for v in lg.shape)
+    lab, lab_len = _pack_labels(labels, b)
+    sl, sl_p = _ints(np.full(b, t) if seq_len is None else seq_len)
+    lab, lab_p = _ints(lab)
+    lab_len, lab_len_p = _ints(lab_len)
+    s_max = int(lab.shape[1])
+    states = torch.empty(b, t, dtype=torch.int32, device=lg.device)
+    spans = torch.empty(b, s_max, 2, dtype=torch.int32, device=lg.device)
+    score = torch.empty(b, dtype=torch.float32, device=lg.device)
+    loss = torch.empty(b, dtype=torch.float32, device=lg.device)
+    post = torch.empty(b, t, s_max, dtype=torch.float32, device=lg.device) if want_post else None
+    with torch.cuda.device(lg.device):
+        _lib.check(lib.kws_ctc_align(_lib.ptr(lg), sl_p, lab_p, lab_len_p, b, t, c, s_max, _lib.ptr(states), _lib.ptr(spans), _lib.ptr(score),
+                                     _lib.ptr(loss), _lib.ptr(post), _lib.current_stream_ptr()))
+    return Alignment(states, spans, score, loss, post)
+
+
+def frame_labels(states, labels, blank):
+    """The frame-wise targets of an alignment (the reference README's "frame-wise label with alignment for word"): states [B,T]
+    (Alignment.states, tensor or array) and the B label sequences it was made with (or one for all) -> [B,T] int32 array, the class of
+    every frame: an odd state 2k+1 its label k, an even state `blank`, -1 stays -1.  Host code."""
+    st = states.cpu().numpy() if hasattr(states, "cpu") else np.asarray(states)
+    if st.ndim != 2:
+        raise _lib.InvalidArgumentError(-1, "states must be [B,T], got %s" % (tuple(st.shape),))
+    lab, lab_len = _pack_labels(labels, st.shape[0])
+    if (st < -1).any() or (st > 2 * lab_len[:, None]).any():
+        raise _lib.InvalidArgumentError(-1, "states outside -1..2S of their utterance's label")
+    k = np.minimum(np.maximum(st, 0) // 2, lab.shape[1] - 1)
+    out = np.where(st % 2 == 1, np.take_along_axis(lab, k, axis=1), np.int32(blank))
+    return np.where(st < 0, -1, out).astype(np.int32)
 
 
 def truncated_normal(shape, seed=0):
@@ -261,6 +319,27 @@ class Enroller(object):
             out_w, out_b = torch.empty_like(wn), torch.empty_like(bn)
             _lib.check(self._lib.kws_enroll_get(self._handle, _lib.ptr(out_w), _lib.ptr(out_b), stream))
         return out_w, out_b, trace
+
+    def align(self, inputs, lengths, labels, new_columns, new_bias):
+        """Where the enrolled words lie in the recordings they were enrolled from, and how sure the new head is of them: inputs,
+        lengths and labels as fit takes them, new_columns [E,H,n_new] and new_bias [E,n_new] as fit returns them -> ctc_align's
+        Alignment over the C + n_new classes of the new head.  The stack runs once (features); the head-2 logits are assembled as
+        every fit step assembles them -- head 1's columns 0..C-2, nn_outputs . columns + bias of the row's enrolment, head 1's blank
+        (a batched torch product of n_new columns: plumbing in front of the kernel) -- and aligned by kws_ctc_align."""
+        import torch
+        e, k, h, n = self.enrolments, self.slots, self.config.hidden_size, self.n_new
+        wn = torch.as_tensor(new_columns).to(device=self.device, dtype=torch.float32)
+        bn = torch.as_tensor(new_bias).to(device=self.device, dtype=torch.float32)
+        if tuple(wn.shape) != (e, h, n) or tuple(bn.shape) != (e, n):
+            raise _lib.InvalidArgumentError(-1, "new_columns / new_bias must be [%d,%d,%d] / [%d,%d], got %s %s"
+                                            % (e, h, n, e, n, tuple(wn.shape), tuple(bn.shape)))
+        nn, logits1 = self.features(inputs, lengths)
+        t = int(nn.shape[1])
+        new = torch.bmm(nn.reshape(e, k * t, h), wn).reshape(e * k, t, n) + bn.repeat_interleave(k, 0).unsqueeze(1)
+        logits2 = torch.cat([logits1[..., :-1], new, logits1[..., -1:]], dim=-1)
+        if lengths is not None:
+            lengths = torch.as_tensor(lengths).cpu().numpy()
+        return ctc_align(logits2, lengths, labels, want_post=True)
 
     def fit_augmented(self, frontend, clean, noise, augmenter, labels, steps, steps_per_batch=1, lr=1.5e-3, init=None, seed=0):
         """fit on noisy versions of the utterances, redrawn every steps_per_batch optimiser steps as the reference's training loop draws
