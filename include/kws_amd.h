@@ -1058,6 +1058,73 @@ int kws_attention_train_stats(kws_attention_train_handle h, size_t* device_bytes
 int kws_attention_drop_keep(uint64_t drop_seed, float keep_prob, int site, int layer, int b, int head, const int32_t* rows,
                             const int32_t* cols, int n, uint8_t* keep);
 
+/* Frame-wise targets: the softmax cross-entropy of every frame against a class per frame (the reference README's frame-wise experiment,
+ * "cross-entropy-like loss function ... the data need to be labeled to frame-wise"; the targets are what custom_keyword.frame_labels makes
+ * of kws_ctc_align's path), as a whole-batch op and as the loss -- alone or mixed with the CTC loss -- of both train handles.
+ *
+ * For utterance b with n = seq_len[b], logits rows z_t of C classes (3..8), targets y_t in {-1, 0 .. C-1} (-1: no target for this frame;
+ * the blank, class C-1, is a target like the others: frame_labels emits it) and class weights w_c >= 0, finite (NULL: all 1):
+ *   W_b           = sum_{t<n, y_t>=0} w[y_t]
+ *   ce_b          = (1 / W_b) sum_{t<n, y_t>=0} w[y_t] (logsumexp(z_t) - z_t[y_t])
+ *   d ce_b / d z_t = (w[y_t] / W_b) (softmax(z_t) - e_{y_t}); exactly 0 at t >= n and at y_t = -1
+ * i.e. torch.nn.functional.cross_entropy(z[:n], y[:n], weight=w, ignore_index=-1, reduction='mean') per utterance, except that W_b == 0
+ * (an empty slot, no labelled frame, or only classes of weight 0) gives loss 0 and gradient 0 where torch gives NaN.  Frames
+ * t >= seq_len[b] are never read, neither logits nor targets: NaN or garbage there gives the bits of zero padding.
+ * targets is DEVICE memory ([B,T] int32; the attention handle: [B,T'], T' = kws_attention_frames_out(T)) and cannot be range-checked on
+ * the host: a value outside [-1, C) at a live frame counts as -1, and that utterance's ce_b is reported as NaN -- loud, without an
+ * out-of-bounds read and without a poisoned weight update.  seq_len and class_weight are HOST memory, checked before anything is
+ * launched and shipped stream-ordered, as kws_ctc_loss ships its block.
+ * One workgroup per utterance (an utterance's bits do not depend on its batch), fixed summation orders, no atomics: repeated calls
+ * give the same bits.  No LDS per frame: no limit on T beyond B * T < 2^31.
+ *
+ *   kws_frame_loss   logits [B,T,C] f32 device -> loss [B] = ce_b and, unless NULL, grad_logits [B,T,C] (every row written).  Stateless,
+ *                    stream-ordered, never synchronises, allocates only its host-to-device block.  Refused before the device is probed
+ *                    (KWS_ERR_INVALID_ARGUMENT): B < 0, T < 1, C outside 3..8, B * T >= 2^31 (KWS_ERR_UNSUPPORTED), a NULL among logits /
+ *                    seq_len / targets / loss, a pointer not 4-byte aligned, seq_len[b] outside [0,T], a weight negative or not finite.
+ *
+ * The train handles (plain, wrapped and carried-state alike; io_or_null as kws_train_grad_state's):
+ *   loss[b] = ctc_weight ctc_b + frame_weight ce_b, and the gradient is that of J = sum_b loss[b] / B (plus <dstate_out, state_out>).
+ *   ft->frame_loss, unless NULL, receives ce_b alone.  Between the logits product and the backward pass:
+ *     ctc_weight == 0      one frame_loss launch (write mode, scale frame_weight / B): one launch fewer than the plain call.  labels and
+ *                          label_len may be NULL and S_max is taken as 0; ctc_loss_kernel's LDS limit on T does not apply.
+ *     both weights > 0     ctc_loss, train_scale with ctc_weight / B, then frame_loss adding onto the labelled rows: one launch more.
+ *     frame_weight == 0    exactly the plain call's launches and bits; ctc_weight must then be 1 (a scaled CTC-only objective would
+ *                          need a launch of its own for loss[b]; it is a learning-rate change) and ft->frame_loss is not written.
+ *   The class weights travel in the handle's stream-ordered upload block behind the lengths and labels: the steady state allocates
+ *   nothing and, with the lengths, labels and weights of the call before, uploads nothing.
+ *   Refused before the device is touched: ft or ft->targets NULL; a weight (ctc, frame, class) negative or not finite; both of ctc_weight
+ *   and frame_weight 0; frame_weight == 0 with ctc_weight != 1; targets or frame_loss not 4-byte aligned; everything the _state call
+ *   refuses (with ctc_weight == 0 nothing about the labels).  kws_[attention_]train_check_frames decide all of it from host memory alone.
+ * Out of scope: label smoothing, targets in host memory, kws_enroll_fit with the frame loss. */
+int kws_frame_loss(const float* logits /*device [B,T,C]*/, const int32_t* seq_len /*host [B]*/, const int32_t* targets /*device [B,T]*/,
+                   const float* class_weight_or_null /*host [C]*/, int B, int T, int C, float* loss /*device [B]*/,
+                   float* grad_logits_or_null /*device [B,T,C]*/, void* stream);
+typedef struct kws_frame_targets {
+    const int32_t* targets;       /* device [B,T] (attention: [B,T']) */
+    const float*   class_weight;  /* host [C] or NULL */
+    float          ctc_weight;    /* >= 0 */
+    float          frame_weight;  /* >= 0 */
+    float*         frame_loss;    /* device [B] out or NULL: ce_b alone */
+} kws_frame_targets;
+size_t kws_sizeof_frame_targets(void);
+int kws_train_grad_frames(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
+                          int T, int S_max, const uint8_t* drop_or_null, float* loss, float* grad_blob, float* logits_or_null,
+                          const kws_train_state_io* io_or_null, const kws_frame_targets* ft, void* stream);
+int kws_train_step_frames(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
+                          int T, int S_max, const uint8_t* drop_or_null, float lr, float* loss, float* grad_norm_or_null,
+                          const kws_train_state_io* io_or_null, const kws_frame_targets* ft, void* stream);
+int kws_train_check_frames(const kws_train_config* cfg, int wrapped, const float* x, const int32_t* seq_len, const int32_t* labels,
+                           const int32_t* label_len, int B, int T, int S_max, const float* loss, const kws_train_state_io* io,
+                           const kws_frame_targets* ft);
+int kws_attention_train_grad_frames(kws_attention_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels,
+                                    const int32_t* label_len, int B, int T, int S_max, uint64_t drop_seed, float* loss, float* grad_blob,
+                                    float* logits_or_null, const kws_frame_targets* ft, void* stream);
+int kws_attention_train_step_frames(kws_attention_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels,
+                                    const int32_t* label_len, int B, int T, int S_max, uint64_t drop_seed, float lr, float* loss,
+                                    float* grad_norm_or_null, const kws_frame_targets* ft, void* stream);
+int kws_attention_train_check_frames(const kws_attention_train_config* cfg, const float* x, const int32_t* seq_len, const int32_t* labels,
+                                     const int32_t* label_len, int B, int T, int S_max, const float* loss, const kws_frame_targets* ft);
+
 #ifdef __cplusplus
 }
 #endif

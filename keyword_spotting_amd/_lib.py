@@ -60,6 +60,14 @@ class KwsTrainStateIo(ctypes.Structure):
     _fields_ = [("state_in", ctypes.c_void_p), ("state_out", ctypes.c_void_p), ("dstate_out", ctypes.c_void_p), ("dstate_in", ctypes.c_void_p)]
 
 
+class KwsFrameTargets(ctypes.Structure):
+    """kws_frame_targets: the frame-wise targets of a kws_[attention_]train_*_frames call -- targets [B,T] int32 (device; -1: no target),
+    class_weight [C] f32 (host) or NULL, the two weights of loss[b] = ctc_weight ctc_b + frame_weight ce_b, and frame_loss [B] (device
+    out) or NULL for ce_b alone."""
+    _fields_ = [("targets", ctypes.c_void_p), ("class_weight", ctypes.c_void_p), ("ctc_weight", ctypes.c_float),
+                ("frame_weight", ctypes.c_float), ("frame_loss", ctypes.c_void_p)]
+
+
 class KwsHeadIo(ctypes.Structure):
     """kws_head_io: one class head's outputs in kws_step_heads -- logits / softmax [B,T,C_i], tokens [B,T], prev_word [B] (device
     pointers, each may be NULL; tokens needs prev_word) and the head's ctc_decode2 threshold."""
@@ -225,6 +233,21 @@ _SIGNATURES = {
     "kws_attention_train_stats": (_i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32),
                                        ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),
     "kws_attention_drop_keep": (_i, [ctypes.c_uint64, _f, _i, _i, _i, _i, _vp, _vp, _i, _vp]),
+    # frame-wise targets: the cross-entropy as an op, and as the loss (alone or mixed with the CTC loss) of both train handles
+    "kws_frame_loss": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
+    "kws_sizeof_frame_targets": (ctypes.c_size_t, []),
+    "kws_train_grad_frames": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp, _vp, _vp, ctypes.POINTER(KwsTrainStateIo),
+                                   ctypes.POINTER(KwsFrameTargets), _vp]),
+    "kws_train_step_frames": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _f, _vp, _vp, ctypes.POINTER(KwsTrainStateIo),
+                                   ctypes.POINTER(KwsFrameTargets), _vp]),
+    "kws_train_check_frames": (_i, [ctypes.POINTER(KwsTrainConfig), _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, ctypes.POINTER(KwsTrainStateIo),
+                                    ctypes.POINTER(KwsFrameTargets)]),
+    "kws_attention_train_grad_frames": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_uint64, _vp, _vp, _vp,
+                                             ctypes.POINTER(KwsFrameTargets), _vp]),
+    "kws_attention_train_step_frames": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_uint64, _f, _vp, _vp,
+                                             ctypes.POINTER(KwsFrameTargets), _vp]),
+    "kws_attention_train_check_frames": (_i, [ctypes.POINTER(KwsAttentionTrainConfig), _vp, _vp, _vp, _vp, _i, _i, _i, _vp,
+                                              ctypes.POINTER(KwsFrameTargets)]),
     # a bank of enrolled heads: per-user customised keywords on one frozen model
     "kws_bank_create": (_i, [_i, _i, _i, _i, ctypes.POINTER(_vp)]),
     "kws_bank_destroy": (_i, [_vp]),
@@ -265,6 +288,7 @@ def load():
                 lib.kws_sizeof_train_config() != ctypes.sizeof(KwsTrainConfig) or \
                 lib.kws_sizeof_train_state_io() != ctypes.sizeof(KwsTrainStateIo) or \
                 lib.kws_sizeof_attention_train_config() != ctypes.sizeof(KwsAttentionTrainConfig) or \
+                lib.kws_sizeof_frame_targets() != ctypes.sizeof(KwsFrameTargets) or \
                 lib.kws_sizeof_head_io() != ctypes.sizeof(KwsHeadIo):
             raise ImportError("%s was built from a different include/kws_amd.h than this binding (struct sizes differ); "
                               "rebuild it" % LIB_PATH)

@@ -6,7 +6,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .custom_keyword import _ints, _pack_labels
+from .custom_keyword import _class_weight, _frame_targets, _ints, _pack_labels
 
 
 def exponential_decay(learning_rate, step, decay_step, lr_decay):
@@ -85,9 +85,32 @@ class _TrainerBase(object):
                                                                  ctypes.byref(c)))
         return dict(device_bytes=int(nbytes.value), allocs=a.value, steps=s.value, launches=l.value, chunk_rows=c.value)
 
+    # -- frame-wise targets (kws_*_frames) ---------------------------------------------------
+    def _set_objective(self, frame_weight, ctc_weight, class_weight):
+        """The objective of the calls that are given targets=: loss[b] = ctc_weight ctc_b + frame_weight ce_b, ce_b the cross-entropy of
+        the utterance's labelled frames under class_weight ([C] or None).  Calls without targets stay the CTC loss alone."""
+        self.frame_weight, self.ctc_weight = float(frame_weight), float(ctc_weight)
+        self.class_weight = _class_weight(class_weight, int(self.config.num_classes))[0]
+
+    def _frames(self, targets, b, rows, want_frame_loss=False):
+        """-> (kws_frame_targets or None for targets None, the tensors it points to, the frame_loss tensor or None).  rows: the frames
+        per utterance of the logits (the attention trainer's T')."""
+        import torch
+        if targets is None:
+            if want_frame_loss:
+                raise _lib.InvalidArgumentError(-1, "want_frame_loss needs targets")
+            return None, (), None
+        tg = _frame_targets(targets, (b, rows), int(self.config.num_classes), self.device)
+        ce = torch.empty(b, dtype=torch.float32, device=self.device) if want_frame_loss else None
+        w = self.class_weight
+        ft = _lib.KwsFrameTargets(tg.data_ptr(), None if w is None else w.ctypes.data, self.ctc_weight, self.frame_weight,
+                                  None if ce is None else ce.data_ptr())
+        return ft, (tg, w), ce
+
     # -- compute -----------------------------------------------------------------------------
-    def _inputs(self, x, lengths, labels):
-        """-> x [B,T,F] (float32, on the device), B, T, and lengths, labels and label lengths as _ints gives them."""
+    def _inputs(self, x, lengths, labels, targets=None):
+        """-> x [B,T,F] (float32, on the device), B, T, and lengths, labels and label lengths as _ints gives them.  labels may be None
+        in a call with targets whose objective has no CTC term (ctc_weight 0)."""
         import torch
         feature = getattr(self.config, self._feature)
         x = torch.as_tensor(x)
@@ -95,7 +118,12 @@ class _TrainerBase(object):
             raise _lib.InvalidArgumentError(-1, "x must be [B,T,%d], got %s" % (feature, tuple(x.shape)))
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
         b, t = int(x.shape[0]), int(x.shape[1])
-        lab, lab_len = _pack_labels(labels, b)
+        if labels is None:
+            if targets is None or self.ctc_weight != 0.0:
+                raise _lib.InvalidArgumentError(-1, "labels may be None only with targets and ctc_weight 0")
+            lab, lab_len = np.zeros((b, 1), np.int32), np.zeros(b, np.int32)
+        else:
+            lab, lab_len = _pack_labels(labels, b)
         sl = np.full(b, t) if lengths is None else np.asarray(lengths)
         if sl.shape != (b,):
             raise _lib.InvalidArgumentError(-1, "lengths: %s for %d utterances" % (sl.shape, b))

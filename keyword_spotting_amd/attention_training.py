@@ -73,13 +73,16 @@ def check_call(config, x_shape, lengths, labels, optimizer="adam", max_grad_norm
 class AttentionTrainer(_TrainerBase):
     """The reference's attention training graph on one device.  Defaults: config/attention_config.py:49-56,81 (learning_rate 1e-3,
     lr_decay 0.9, decay_step 40000, adam, no clipping, no warm-up); keep_prob defaults to 1 (the reference file ships 0.9, :83).
-    weights: a dict (attention_weights.init's form), a blob, or None for attention_weights.init(config, seed)."""
+    weights: a dict (attention_weights.init's form), a blob, or None for attention_weights.init(config, seed).
+    frame_weight, ctc_weight, class_weight: the objective of loss_and_grad_frames, step_frames and step_raw's targets= ([B,T'], a class
+    per row of the logits, -1 for none): loss[b] = ctc_weight ctc_b + frame_weight ce_b, as training.Trainer's."""
 
     _prefix, _weights_mod, _feature = "kws_attention_train", _weights, "freq_size"
 
     def __init__(self, config, weights=None, optimizer="adam", learning_rate=1e-3, lr_decay=0.9, decay_step=40000, warmup=False,
-                 max_grad_norm=-1, keep_prob=1.0, seed=0, device="cuda:0"):
+                 max_grad_norm=-1, keep_prob=1.0, seed=0, device="cuda:0", frame_weight=0.0, ctc_weight=1.0, class_weight=None):
         self.config = config
+        self._set_objective(frame_weight, ctc_weight, class_weight)
         self.optimizer, self.learning_rate, self.lr_decay, self.decay_step = optimizer, float(learning_rate), float(lr_decay), int(decay_step)
         self.warmup, self.max_grad_norm, self.keep_prob = bool(warmup), float(max_grad_norm), float(keep_prob)
         self._cfg = train_config(config, optimizer, max_grad_norm, keep_prob)
@@ -118,35 +121,60 @@ class AttentionTrainer(_TrainerBase):
     def loss_and_grad(self, x, lengths, labels, seed=0, want_logits=False):
         """-> (loss = sum_b ctc_b / B, gradients in the dict form, per-utterance losses [B]) [, logits [B,T',C]]; the parameters stay.
         labels: B sequences over classes 0..C-2, or one for all; seed: the dropout seed of the call (ignored at keep_prob 1)."""
+        return self.loss_and_grad_frames(x, lengths, labels, None, seed=seed, want_logits=want_logits)
+
+    def loss_and_grad_frames(self, x, lengths, labels, targets, seed=0, want_logits=False, want_frame_loss=False):
+        """loss_and_grad on frame-wise targets [B,T'] (kws_attention_train_grad_frames): the per-utterance losses are ctc_weight ctc_b +
+        frame_weight ce_b; with want_frame_loss ce [B] (device) is appended.  labels may be None at ctc_weight 0; targets None is
+        loss_and_grad."""
         import torch
-        x, b, t, (sl, sl_p), (lab, lab_p), (ll, ll_p) = self._inputs(x, lengths, labels)
+        x, b, t, (sl, sl_p), (lab, lab_p), (ll, ll_p) = self._inputs(x, lengths, labels, targets)
+        ft, keep_ft, ce = self._frames(targets, b, self.frames_out(t), want_frame_loss)
         loss = torch.empty(b, dtype=torch.float32, device=self.device)
         grad = torch.empty(self._floats(), dtype=torch.float32, device=self.device)
         logits = torch.empty(b, self.frames_out(t), self.config.num_classes, dtype=torch.float32, device=self.device) if want_logits else None
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_attention_train_grad(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]),
-                                                          ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _lib.ptr(loss), _lib.ptr(grad),
-                                                          _lib.ptr(logits), self._stream()))
+            if ft is not None:
+                _lib.check(self._lib.kws_attention_train_grad_frames(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]),
+                                                                     ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _lib.ptr(loss), _lib.ptr(grad),
+                                                                     _lib.ptr(logits), ctypes.byref(ft), self._stream()))
+            else:
+                _lib.check(self._lib.kws_attention_train_grad(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]),
+                                                              ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), _lib.ptr(loss), _lib.ptr(grad),
+                                                              _lib.ptr(logits), self._stream()))
         per = loss.cpu().numpy()
         out = (float(per.astype(np.float64).sum() / b), _weights.from_blob(self.config, grad.cpu().numpy()), per)
-        return out + (logits,) if want_logits else out
+        if want_logits:
+            out += (logits,)
+        return out + (ce,) if want_frame_loss else out
 
-    def step_raw(self, x, lengths, labels, lr, seed=0, want_norm=False):
-        """One kws_attention_train_step at learning rate lr with the masks of `seed` -> per-utterance losses [B] (device) [, global norm]."""
+    def step_raw(self, x, lengths, labels, lr, seed=0, want_norm=False, targets=None):
+        """One kws_attention_train_step at learning rate lr with the masks of `seed` -> per-utterance losses [B] (device) [, global norm].
+        targets [B,T']: the step of the trainer's mixed objective (kws_attention_train_step_frames)."""
         import torch
-        x, b, t, (sl, sl_p), (lab, lab_p), (ll, ll_p) = self._inputs(x, lengths, labels)
+        x, b, t, (sl, sl_p), (lab, lab_p), (ll, ll_p) = self._inputs(x, lengths, labels, targets)
+        ft, keep_ft, _ = self._frames(targets, b, self.frames_out(t))
         loss = torch.empty(b, dtype=torch.float32, device=self.device)
         norm = torch.empty(1, dtype=torch.float32, device=self.device) if want_norm else None
         with torch.cuda.device(self.device):
-            _lib.check(self._lib.kws_attention_train_step(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]),
-                                                          ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), float(lr), _lib.ptr(loss), _lib.ptr(norm),
-                                                          self._stream()))
+            if ft is not None:
+                _lib.check(self._lib.kws_attention_train_step_frames(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]),
+                                                                     ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), float(lr), _lib.ptr(loss),
+                                                                     _lib.ptr(norm), ctypes.byref(ft), self._stream()))
+            else:
+                _lib.check(self._lib.kws_attention_train_step(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]),
+                                                              ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), float(lr), _lib.ptr(loss), _lib.ptr(norm),
+                                                              self._stream()))
         return (loss, norm) if want_norm else loss
 
     def step(self, x, lengths, labels):
         """One training step as main.py runs it: a fresh dropout seed from the trainer's own generator, the scheduled learning rate, the
         update -> loss = sum_b ctc_b / B."""
+        return self.step_frames(x, lengths, labels, None)
+
+    def step_frames(self, x, lengths, labels, targets):
+        """step() on frame-wise targets [B,T']: the update of the trainer's mixed objective -> sum_b (ctc_weight ctc_b + frame_weight ce_b) / B."""
         seed = int(self._rng.integers(0, 2 ** 63))
-        loss = self.step_raw(x, lengths, labels, self.learning_rate_at(self.global_step), seed=seed)
+        loss = self.step_raw(x, lengths, labels, self.learning_rate_at(self.global_step), seed=seed, targets=targets)
         self.global_step += 1
         return float(loss.cpu().numpy().astype(np.float64).sum() / loss.shape[0])

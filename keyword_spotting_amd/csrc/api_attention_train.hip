@@ -5,7 +5,7 @@
 // Launches of a kws_attention_train_grad call, L layers (kws_attention_train_stats counts them: 12 + 19 L + use_relu; _step: one more):
 //   rowmask, stack, gemm (embedding), addpe
 //   per layer: gemm (qkv), core forward, resid, ln forward, gemm (W1), relu, gemm (W2), resid, ln forward
-//   gemm (logits), relu / dead rows, ctc_loss, scale, [relumask]
+//   gemm (logits), relu / dead rows, ctc_loss, scale, [relumask]      (_frames: frame_loss in place of ctc_loss + scale, or behind them)
 //   gemm (d of the top layer's output)
 //   per layer, top down: ln_b sums, ln_b apply, gemm (dh), relumask, gemm (dy), ln_a sums, ln_a apply, core dq, core dk/dv, gemm (dx)
 //   residual (d of the embedding), wgrad, reduce
@@ -23,7 +23,7 @@ struct kws_attention_train : TrainCore {      // tail: the positional table
     // the arena, carved for the shape of the call
     struct Carved {
         int B = 0, T = 0, T1 = 0, S_max = -1;
-        int32_t* ints = nullptr;          // T'_b [B] | label_len [B] | labels [B, S_max] | T_b [B]
+        int32_t* ints = nullptr;          // T'_b [B] | label_len [B] | labels [B, S_max] | T_b [B] | class weights [8] (frame targets)
         uint8_t* live = nullptr;
         kws::TrainWgradJob* jobs = nullptr;
         float *xs = nullptr, *x[9] = {}, *sh[5] = {}, *de = nullptr, *logits = nullptr, *gl = nullptr, *dsum = nullptr, *partial = nullptr;
@@ -52,7 +52,7 @@ size_t carve(const Handle* h, int B, int T, int S_max, char* base, Handle::Carve
     o.njobs = 4 + 10 * c.num_layers;
     o.chunk_rows = wgrad_chunk_rows(M);
     o.chunks = (int)((M + o.chunk_rows - 1) / o.chunk_rows);
-    o.ints = reinterpret_cast<int32_t*>(cut.take((size_t)B * (3 + S_max) * sizeof(int32_t)));
+    o.ints = reinterpret_cast<int32_t*>(cut.take(((size_t)B * (3 + S_max) + kws::kMaxClasses) * sizeof(int32_t)));
     o.live = reinterpret_cast<uint8_t*>(cut.take(M));
     o.jobs = reinterpret_cast<kws::TrainWgradJob*>(cut.take((size_t)o.njobs * sizeof(kws::TrainWgradJob)));
     o.part = reinterpret_cast<float4*>(cut.take((size_t)B * ntile * sizeof(float4)));
@@ -123,44 +123,51 @@ int check_config(const kws_attention_train_config* cfg) {
     return check_optimizer(cfg->keep_prob, cfg->optimizer, cfg->max_grad_norm);
 }
 
-int check_shape(const kws_attention_config& c, int B, int T, int S_max) {
+// ctc false (a _frames call with ctc_weight 0): nothing about S_max, the labels or the LDS of ctc_loss_kernel
+int check_shape(const kws_attention_config& c, int B, int T, int S_max, bool ctc = true) {
     if (B < 1 || T < 1) return fail(KWS_ERR_INVALID_ARGUMENT, "bad shape B=%d T=%d: at least one utterance and one frame", B, T);
-    KWS_TRY(check_s_max(S_max));
+    if (ctc) KWS_TRY(check_s_max(S_max));
     if (T > c.max_frames) return fail(KWS_ERR_UNSUPPORTED, "T=%d exceeds model.max_frames=%d", T, c.max_frames);
     if (B > 65535) return fail(KWS_ERR_UNSUPPORTED, "B=%d unsupported (<= 65535)", B);
     const int T1 = frames_out(c, T);
     if ((size_t)B * T1 > kMaxRows) return fail(KWS_ERR_UNSUPPORTED, "B=%d x T'=%d: more than 2^28 rows in one call", B, T1);
-    return check_ctc_lds(T1, S_max, "T'=%d rows");
+    return ctc ? check_ctc_lds(T1, S_max, "T'=%d rows") : KWS_OK;
 }
 
 // the refusals of a grad / step call from host memory alone; t1 (if given): every utterance's T'_b
 int check_call(const kws_attention_train_config& cfg, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
-               int T, int S_max, const float* loss, std::vector<int32_t>* t1) {
+               int T, int S_max, const float* loss, std::vector<int32_t>* t1, bool ctc = true) {
     const kws_attention_config& c = cfg.model;
-    KWS_TRY(check_shape(c, B, T, S_max));
-    if (!x || !seq_len || !label_len || !loss || (!labels && S_max > 0)) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
+    KWS_TRY(check_shape(c, B, T, S_max, ctc));
+    if (!x || !seq_len || !loss || (ctc && (!label_len || (!labels && S_max > 0)))) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
     if (misaligned(x) || misaligned(loss)) return fail(KWS_ERR_INVALID_ARGUMENT, "x and loss must be 4-byte aligned");
     std::vector<int32_t> rows((size_t)B);
     for (int b = 0; b < B; ++b) {
         if (seq_len[b] < 0 || seq_len[b] > T) return fail(KWS_ERR_INVALID_ARGUMENT, "seq_len[%d]=%d out of range [0,%d]", b, seq_len[b], T);
         rows[b] = frames_out(c, seq_len[b]);
     }
-    KWS_TRY(check_labels(rows.data(), labels, label_len, B, frames_out(c, T), S_max, c.num_classes));
+    if (ctc) KWS_TRY(check_labels(rows.data(), labels, label_len, B, frames_out(c, T), S_max, c.num_classes));
     if (t1) t1->swap(rows);
     return KWS_OK;
 }
 
-// forward, loss, backward: leaves loss [B], the logits and the gradient of sum(loss) / B (h->grad, with the sums of squares of its blocks)
+// forward, loss, backward: leaves loss [B], the logits and the gradient of sum(loss) / B (h->grad, with the sums of squares of its blocks).
+// ft: null for the CTC loss alone, else loss[b] = ctc_weight ctc_b + frame_weight ce_b on ft's targets [B, T'] (ctc_weight 0: labels,
+// label_len and S_max are not looked at)
 int grad_impl(Handle* h, const float* x, const int32_t* seq_len, const std::vector<int32_t>& t1, const int32_t* labels, const int32_t* label_len,
-              int B, int T, int S_max, uint64_t seed, float* loss, hipStream_t st) {
+              int B, int T, int S_max, uint64_t seed, float* loss, const kws_frame_targets* ft, hipStream_t st) {
     const kws_attention_config& c = h->cfg.model;
     const int H = c.hidden, Fi = c.ffn_inner, C = c.num_classes, L = c.num_layers, NH = c.num_heads, cF = c.combine_frame * c.n_mel;
+    const bool ctc = !ft || ft->ctc_weight > 0.f, frames = ft && ft->frame_weight > 0.f;
+    std::vector<int32_t> no_labels;
+    if (!ctc) { no_labels.assign((size_t)B, 0); labels = nullptr; label_len = no_labels.data(); S_max = 0; }
     KWS_TRY(prepare_shape(h, B, T, S_max));
     Handle::Carved& cv = h->cv;
     const int T1 = cv.T1, M = B * T1;
     std::vector<int32_t> ints;
     pack_ints(t1.data(), labels, label_len, B, S_max, &ints);
     ints.insert(ints.end(), seq_len, seq_len + B);
+    if (frames) append_class_weights(ft->class_weight, C, &ints);
     KWS_TRY(train_upload(h, cv.jobs, cv.ints, &ints, st));
     const int32_t *d_t1 = cv.ints, *d_len = cv.ints + B, *d_lab = cv.ints + 2 * (size_t)B, *d_tlen = cv.ints + (size_t)B * (2 + S_max);
     const float kp = h->cfg.keep_prob;
@@ -203,8 +210,16 @@ int grad_impl(Handle* h, const float* x, const int32_t* seq_len, const std::vect
     }
     KWS_TRY(gemm(cv.x[L], H, th + h->lay.w_out, C, 1, th + h->lay.b_out, cv.logits, C, "launch train_rows_gemm (logits)"));
     KWS_LAUNCH(h, kws::launch_attn_train_relu(cv.logits, d_t1, B, T1, C, c.use_relu, st), "launch attn_train_relu (logits)");
-    KWS_LAUNCH(h, kws::launch_ctc_loss(cv.logits, d_t1, d_lab, d_len, B, T1, C, S_max, loss, cv.gl, st), "launch ctc_loss");
-    KWS_LAUNCH(h, kws::launch_train_scale(cv.gl, cv.logits, (size_t)M, C, 1.0f / (float)B, st), "launch train_scale");      // loss = sum_b ctc_b / B
+    if (ctc) {          // J = sum_b ctc_weight ctc_b / B (ctc_weight: 1 without frame targets)
+        KWS_LAUNCH(h, kws::launch_ctc_loss(cv.logits, d_t1, d_lab, d_len, B, T1, C, S_max, loss, cv.gl, st), "launch ctc_loss");
+        KWS_LAUNCH(h, kws::launch_train_scale(cv.gl, cv.logits, (size_t)M, C, (ft ? ft->ctc_weight : 1.0f) / (float)B, st), "launch train_scale");
+    }
+    if (frames) {       // ... + sum_b frame_weight ce_b / B: alone it writes every row of the gradient, behind the CTC term it adds to it
+        kws::FrameLossParams p = train_frame_term(*ft, B);
+        p.logits = cv.logits; p.seq_len = d_t1; p.weight = reinterpret_cast<const float*>(cv.ints + (size_t)B * (3 + S_max));
+        p.loss = loss; p.grad = cv.gl; p.T = T1; p.C = C;
+        KWS_LAUNCH(h, kws::launch_frame_loss(p, B, st), "launch frame_loss");
+    }
     if (c.use_relu) KWS_LAUNCH(h, kws::launch_attn_train_relumask(cv.gl, cv.logits, d_t1, B, T1, C, st), "launch attn_train_relumask (logits)");
     // backward; sh: 0 = d through the qkv product (and of the top output), 1 = du, 2 = ds, 3 = d through W1, 4 = d of the attention output
     float *s_dxq = cv.sh[0], *s_du = cv.sh[1], *s_ds = cv.sh[2], *s_dyf = cv.sh[3], *s_datt = cv.sh[4];
@@ -242,6 +257,40 @@ int grad_impl(Handle* h, const float* x, const int32_t* seq_len, const std::vect
     return KWS_OK;
 }
 
+// kws_attention_train_grad (ft null) and kws_attention_train_grad_frames (ft checked)
+int grad_call(kws_attention_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
+              int B, int T, int S_max, uint64_t drop_seed, float* loss, float* grad_blob, float* logits_or_null, const kws_frame_targets* ft,
+              void* stream) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    std::vector<int32_t> t1;
+    KWS_TRY(check_call(h->cfg, x, seq_len, labels, label_len, B, T, S_max, loss, &t1, !ft || ft->ctc_weight > 0.f));
+    if (!grad_blob) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
+    if (misaligned(grad_blob) || misaligned(logits_or_null)) return fail(KWS_ERR_INVALID_ARGUMENT, "grad_blob and logits must be 4-byte aligned");
+    return train_call(h, stream, [&](hipStream_t st) -> int {
+        KWS_TRY(grad_impl(h, x, seq_len, t1, labels, label_len, B, T, S_max, drop_seed, loss, ft, st));
+        KWS_HIP(hipMemcpyAsync(grad_blob, h->grad, h->P * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (logits_or_null)
+            KWS_HIP(hipMemcpyAsync(logits_or_null, h->cv.logits, (size_t)B * h->cv.T1 * h->cfg.model.num_classes * sizeof(float),
+                                   hipMemcpyDeviceToDevice, st));
+        return KWS_OK;
+    });
+}
+
+// kws_attention_train_step (ft null) and kws_attention_train_step_frames (ft checked)
+int step_call(kws_attention_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
+              int B, int T, int S_max, uint64_t drop_seed, float lr, float* loss, float* grad_norm_or_null, const kws_frame_targets* ft,
+              void* stream) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    std::vector<int32_t> t1;
+    KWS_TRY(check_call(h->cfg, x, seq_len, labels, label_len, B, T, S_max, loss, &t1, !ft || ft->ctc_weight > 0.f));
+    if (!(lr > 0.f) || !std::isfinite(lr)) return fail(KWS_ERR_INVALID_ARGUMENT, "lr=%g has to be positive and finite", (double)lr);
+    if (misaligned(grad_norm_or_null)) return fail(KWS_ERR_INVALID_ARGUMENT, "grad_norm must be 4-byte aligned");
+    return train_call(h, stream, [&](hipStream_t st) -> int {
+        KWS_TRY(grad_impl(h, x, seq_len, t1, labels, label_len, B, T, S_max, drop_seed, loss, ft, st));
+        return train_update(h, lr, grad_norm_or_null, st);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -269,6 +318,13 @@ int kws_attention_train_check(const kws_attention_train_config* cfg, const float
                               const int32_t* label_len, int B, int T, int S_max, const float* loss) {
     KWS_TRY(check_config(cfg));
     return check_call(*cfg, x, seq_len, labels, label_len, B, T, S_max, loss, nullptr);
+}
+
+int kws_attention_train_check_frames(const kws_attention_train_config* cfg, const float* x, const int32_t* seq_len, const int32_t* labels,
+                                     const int32_t* label_len, int B, int T, int S_max, const float* loss, const kws_frame_targets* ft) {
+    KWS_TRY(check_config(cfg));
+    KWS_TRY(check_frame_targets(ft, cfg->model.num_classes));
+    return check_call(*cfg, x, seq_len, labels, label_len, B, T, S_max, loss, nullptr, ft->ctc_weight > 0.f);
 }
 
 int kws_attention_train_create(const kws_attention_train_config* cfg, kws_attention_train_handle* out) {
@@ -321,32 +377,28 @@ int kws_attention_train_reserve(kws_attention_train_handle h, int B, int T, int 
 
 int kws_attention_train_grad(kws_attention_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
                              int B, int T, int S_max, uint64_t drop_seed, float* loss, float* grad_blob, float* logits_or_null, void* stream) {
+    return grad_call(h, x, seq_len, labels, label_len, B, T, S_max, drop_seed, loss, grad_blob, logits_or_null, nullptr, stream);
+}
+
+int kws_attention_train_grad_frames(kws_attention_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels,
+                                    const int32_t* label_len, int B, int T, int S_max, uint64_t drop_seed, float* loss, float* grad_blob,
+                                    float* logits_or_null, const kws_frame_targets* ft, void* stream) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
-    std::vector<int32_t> t1;
-    KWS_TRY(check_call(h->cfg, x, seq_len, labels, label_len, B, T, S_max, loss, &t1));
-    if (!grad_blob) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
-    if (misaligned(grad_blob) || misaligned(logits_or_null)) return fail(KWS_ERR_INVALID_ARGUMENT, "grad_blob and logits must be 4-byte aligned");
-    return train_call(h, stream, [&](hipStream_t st) -> int {
-        KWS_TRY(grad_impl(h, x, seq_len, t1, labels, label_len, B, T, S_max, drop_seed, loss, st));
-        KWS_HIP(hipMemcpyAsync(grad_blob, h->grad, h->P * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if (logits_or_null)
-            KWS_HIP(hipMemcpyAsync(logits_or_null, h->cv.logits, (size_t)B * h->cv.T1 * h->cfg.model.num_classes * sizeof(float),
-                                   hipMemcpyDeviceToDevice, st));
-        return KWS_OK;
-    });
+    KWS_TRY(check_frame_targets(ft, h->cfg.model.num_classes));
+    return grad_call(h, x, seq_len, labels, label_len, B, T, S_max, drop_seed, loss, grad_blob, logits_or_null, ft, stream);
 }
 
 int kws_attention_train_step(kws_attention_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
                              int B, int T, int S_max, uint64_t drop_seed, float lr, float* loss, float* grad_norm_or_null, void* stream) {
+    return step_call(h, x, seq_len, labels, label_len, B, T, S_max, drop_seed, lr, loss, grad_norm_or_null, nullptr, stream);
+}
+
+int kws_attention_train_step_frames(kws_attention_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels,
+                                    const int32_t* label_len, int B, int T, int S_max, uint64_t drop_seed, float lr, float* loss,
+                                    float* grad_norm_or_null, const kws_frame_targets* ft, void* stream) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
-    std::vector<int32_t> t1;
-    KWS_TRY(check_call(h->cfg, x, seq_len, labels, label_len, B, T, S_max, loss, &t1));
-    if (!(lr > 0.f) || !std::isfinite(lr)) return fail(KWS_ERR_INVALID_ARGUMENT, "lr=%g has to be positive and finite", (double)lr);
-    if (misaligned(grad_norm_or_null)) return fail(KWS_ERR_INVALID_ARGUMENT, "grad_norm must be 4-byte aligned");
-    return train_call(h, stream, [&](hipStream_t st) -> int {
-        KWS_TRY(grad_impl(h, x, seq_len, t1, labels, label_len, B, T, S_max, drop_seed, loss, st));
-        return train_update(h, lr, grad_norm_or_null, st);
-    });
+    KWS_TRY(check_frame_targets(ft, h->cfg.model.num_classes));
+    return step_call(h, x, seq_len, labels, label_len, B, T, S_max, drop_seed, lr, loss, grad_norm_or_null, ft, stream);
 }
 
 int kws_attention_train_stats(kws_attention_train_handle h, size_t* device_bytes, int32_t* allocs, int32_t* steps, int32_t* launches,

@@ -211,6 +211,18 @@ bool misaligned(const void* p);      // not 4-byte aligned
 // ... [seq_len | label_len | labels] as the one block that travels to the device
 void pack_ints(const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int S_max, std::vector<int32_t>* out);
 
+// api_frame_loss.hip: frame-wise targets (kws_frame_loss, kws_[attention_]train_*_frames).  The refusals of a kws_frame_targets for C
+// classes, of host class weights (null: none) and of seq_len against T alone
+int check_frame_targets(const kws_frame_targets* ft, int C);
+int check_class_weight(const float* w, int C);
+int check_seq_len(const int32_t* seq_len, int B, int T);
+// ... the class weights (null: ones) as kMaxClasses floats behind the ints of an upload block
+void append_class_weights(const float* w, int C, std::vector<int32_t>* ints);
+// ... and what a train handle's frame_loss launch takes from ft (frame_weight > 0) for a batch of B: the targets, ce_b's destination, the
+// gradient's scale frame_weight / B, and -- behind a CTC term -- accumulate mode with loss[b] = ctc_weight loss[b] + frame_weight ce_b.
+// The caller adds logits, seq_len, weight, loss, grad, T and C
+kws::FrameLossParams train_frame_term(const kws_frame_targets& ft, int B);
+
 // api_attention.hip: the canonical blob of the attention model (offsets in floats) and the refusals of its config, shared with the
 // train handle (api_attention_train.hip)
 enum { kQkvW, kQkvB, kLnaBeta, kLnaGamma, kW1, kB1, kW2, kB2, kLnbBeta, kLnbGamma, kLayerParts };

@@ -1,6 +1,7 @@
 // C ABI of libkws_amd.so (include/kws_amd.h): the train handle -- taped forward, back-propagation through time, the CTC loss through
 // ctc_loss_kernel, global-norm clipping and Adam / Nesterov on the canonical blob (gru_train.hip, train_kernels.hip), with the cell
-// wrappers of kws_train_create_wrapped around the two frame loops (train_wrap_kernels.hip).
+// wrappers of kws_train_create_wrapped around the two frame loops (train_wrap_kernels.hip).  The _frames entry points put the frame-wise
+// cross-entropy (frame_loss_kernels.hip) in the CTC loss's place or on top of it: grad_impl's ft.
 #include <new>
 
 #include "train_core.h"
@@ -46,7 +47,7 @@ size_t carve(const kws_train* h, int B, int T, int S_max, char* base, kws_train:
     o.njobs = (h->ln ? 8 : 6) * c.num_layers + 2;
     o.chunk_rows = wgrad_chunk_rows(M);
     o.chunks = (int)((M + o.chunk_rows - 1) / o.chunk_rows);
-    o.ints = reinterpret_cast<int32_t*>(cut.take((size_t)B * (2 + S_max) * sizeof(int32_t)));
+    o.ints = reinterpret_cast<int32_t*>(cut.take(((size_t)B * (2 + S_max) + kws::kMaxClasses) * sizeof(int32_t)));      // ... | class weights
     o.live = reinterpret_cast<uint8_t*>(cut.take(M));
     o.jobs = reinterpret_cast<kws::TrainWgradJob*>(cut.take((size_t)o.njobs * sizeof(kws::TrainWgradJob)));
     o.xg = cut.floats(M * 3 * H);
@@ -104,13 +105,15 @@ int prepare_shape(kws_train* h, int B, int T, int S_max) {
     return KWS_OK;
 }
 
+// ctc false (a _frames call with ctc_weight 0): nothing about the labels, S_max or the LDS of ctc_loss_kernel
 int check_call(const kws_train_config& cfg, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
-               int S_max, const float* loss) {
+               int S_max, const float* loss, bool ctc = true) {
     if (B < 1 || T < 1) return fail(KWS_ERR_INVALID_ARGUMENT, "bad shape B=%d T=%d: at least one utterance and one frame", B, T);
-    KWS_TRY(check_s_max(S_max));
-    if (!x || !seq_len || !label_len || !loss || (!labels && S_max > 0)) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
+    if (ctc) KWS_TRY(check_s_max(S_max));
+    if (!x || !seq_len || !loss || (ctc && (!label_len || (!labels && S_max > 0)))) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
     if (misaligned(x) || misaligned(loss)) return fail(KWS_ERR_INVALID_ARGUMENT, "x and loss must be 4-byte aligned");
     if ((size_t)B * T > (size_t)0x7fffffff) return fail(KWS_ERR_UNSUPPORTED, "B=%d x T=%d: more than 2^31 - 1 frames in one call", B, T);
+    if (!ctc) return check_seq_len(seq_len, B, T);
     KWS_TRY(check_labels(seq_len, labels, label_len, B, T, S_max, cfg.model.num_classes));
     return check_ctc_lds(T, S_max, "%d frames");
 }
@@ -129,17 +132,22 @@ int check_state_io(const kws_train_state_io* io) {
 bool carries_state(const kws_train_state_io* io) { return io && (io->state_in || io->state_out || io->dstate_out || io->dstate_in); }
 
 // forward, loss, backward: leaves loss [B], the logits and the gradient of sum(loss) / B + <dstate_out, state_out> (h->grad, with the sums
-// of squares of its blocks); io: null or all null for the zero state and no state outputs
+// of squares of its blocks); io: null or all null for the zero state and no state outputs.  ft: null for the CTC loss alone, else loss[b] =
+// ctc_weight ctc_b + frame_weight ce_b on ft's targets (ctc_weight 0: labels, label_len and S_max are not looked at)
 int grad_impl(kws_train* h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int S_max,
-              const uint8_t* drop, float* loss, const kws_train_state_io* io, hipStream_t st) {
+              const uint8_t* drop, float* loss, const kws_train_state_io* io, const kws_frame_targets* ft, hipStream_t st) {
     const kws_config& c = h->cfg.model;
     const int H = c.hidden, C = c.num_classes, L = c.num_layers, M = B * T;
     const bool stateful = carries_state(io);
+    const bool ctc = !ft || ft->ctc_weight > 0.f, frames = ft && ft->frame_weight > 0.f;
     const size_t state_layer = (size_t)B * H;          // floats of one layer of [L, B, H]
+    std::vector<int32_t> no_labels;
+    if (!ctc) { no_labels.assign((size_t)B, 0); labels = nullptr; label_len = no_labels.data(); S_max = 0; }
     KWS_TRY(prepare_shape(h, B, T, S_max));
     kws_train::Carved& cv = h->cv;
     std::vector<int32_t> ints;
     pack_ints(seq_len, labels, label_len, B, S_max, &ints);
+    if (frames) append_class_weights(ft->class_weight, C, &ints);
     KWS_TRY(train_upload(h, cv.jobs, cv.ints, &ints, st));
     const int32_t *d_seq = cv.ints, *d_len = cv.ints + B, *d_lab = cv.ints + 2 * (size_t)B;
     h->launches = 0;
@@ -185,8 +193,16 @@ int grad_impl(kws_train* h, const float* x, const int32_t* seq_len, const int32_
         g.out = cv.logits; g.ldo = C; g.M = M; g.K = H; g.N = C;
         KWS_LAUNCH(h, kws::launch_train_rows_gemm(g, st), "launch train_rows_gemm (logits)");
     }
-    KWS_LAUNCH(h, kws::launch_ctc_loss(cv.logits, d_seq, d_lab, d_len, B, T, C, S_max, loss, cv.gl, st), "launch ctc_loss");
-    KWS_LAUNCH(h, kws::launch_train_scale(cv.gl, cv.logits, (size_t)M, C, 1.0f / (float)B, st), "launch train_scale");      // loss = sum_b ctc_b / B
+    if (ctc) {          // J = sum_b ctc_weight ctc_b / B (ctc_weight: 1 without frame targets)
+        KWS_LAUNCH(h, kws::launch_ctc_loss(cv.logits, d_seq, d_lab, d_len, B, T, C, S_max, loss, cv.gl, st), "launch ctc_loss");
+        KWS_LAUNCH(h, kws::launch_train_scale(cv.gl, cv.logits, (size_t)M, C, (ft ? ft->ctc_weight : 1.0f) / (float)B, st), "launch train_scale");
+    }
+    if (frames) {       // ... + sum_b frame_weight ce_b / B: alone it writes every row of the gradient, behind the CTC term it adds to it
+        kws::FrameLossParams p = train_frame_term(*ft, B);
+        p.logits = cv.logits; p.seq_len = d_seq; p.weight = reinterpret_cast<const float*>(cv.ints + (size_t)B * (2 + S_max));
+        p.loss = loss; p.grad = cv.gl; p.T = T; p.C = C;
+        KWS_LAUNCH(h, kws::launch_frame_loss(p, B, st), "launch frame_loss");
+    }
     {
         kws::TrainRowsGemm g = {};          // dy_top = grad_logits . Wfc^T
         g.a = cv.gl; g.lda = C; g.w = wfc; g.swk = 1; g.swn = C;
@@ -314,6 +330,41 @@ int create_impl(const kws_train_config* cfg, bool wrapped, kws_train_handle* out
     return KWS_OK;
 }
 
+// kws_train_grad_state (ft null) and kws_train_grad_frames (ft checked)
+int grad_call(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
+                     int S_max, const uint8_t* drop_or_null, float* loss, float* grad_blob, float* logits_or_null, const kws_train_state_io* io,
+                     const kws_frame_targets* ft, void* stream) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    KWS_TRY(check_call(h->cfg, x, seq_len, labels, label_len, B, T, S_max, loss, !ft || ft->ctc_weight > 0.f));
+    if (!grad_blob) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
+    if (misaligned(grad_blob) || misaligned(logits_or_null) || misaligned(drop_or_null))
+        return fail(KWS_ERR_INVALID_ARGUMENT, "grad_blob, logits and drop must be 4-byte aligned (the masks are read four units at a time)");
+    KWS_TRY(check_state_io(io));
+    return train_call(h, stream, [&](hipStream_t st) -> int {
+        KWS_TRY(grad_impl(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, loss, io, ft, st));
+        KWS_HIP(hipMemcpyAsync(grad_blob, h->grad, h->P * sizeof(float), hipMemcpyDeviceToDevice, st));
+        if (logits_or_null)
+            KWS_HIP(hipMemcpyAsync(logits_or_null, h->cv.logits, (size_t)B * T * h->cfg.model.num_classes * sizeof(float), hipMemcpyDeviceToDevice, st));
+        return KWS_OK;
+    });
+}
+
+// kws_train_step_state (ft null) and kws_train_step_frames (ft checked)
+int step_call(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
+                     int S_max, const uint8_t* drop_or_null, float lr, float* loss, float* grad_norm_or_null, const kws_train_state_io* io,
+                     const kws_frame_targets* ft, void* stream) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    KWS_TRY(check_call(h->cfg, x, seq_len, labels, label_len, B, T, S_max, loss, !ft || ft->ctc_weight > 0.f));
+    if (!(lr > 0.f) || !std::isfinite(lr)) return fail(KWS_ERR_INVALID_ARGUMENT, "lr=%g has to be positive and finite", (double)lr);
+    if (misaligned(grad_norm_or_null) || misaligned(drop_or_null))
+        return fail(KWS_ERR_INVALID_ARGUMENT, "grad_norm and drop must be 4-byte aligned (the masks are read four units at a time)");
+    KWS_TRY(check_state_io(io));
+    return train_call(h, stream, [&](hipStream_t st) -> int {
+        KWS_TRY(grad_impl(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, loss, io, ft, st));
+        return update_impl(h, lr, grad_norm_or_null, st);
+    });
+}
+
 }  // namespace
 
 extern "C" {
@@ -347,6 +398,16 @@ int kws_train_check_state(const kws_train_config* cfg, int wrapped, const float*
     return check_state_io(io);
 }
 
+int kws_train_check_frames(const kws_train_config* cfg, int wrapped, const float* x, const int32_t* seq_len, const int32_t* labels,
+                           const int32_t* label_len, int B, int T, int S_max, const float* loss, const kws_train_state_io* io,
+                           const kws_frame_targets* ft) {
+    if (!cfg) return fail(KWS_ERR_INVALID_ARGUMENT, "config is null");
+    KWS_TRY(check_config(*cfg, wrapped != 0));
+    KWS_TRY(check_frame_targets(ft, cfg->model.num_classes));
+    KWS_TRY(check_call(*cfg, x, seq_len, labels, label_len, B, T, S_max, loss, ft->ctc_weight > 0.f));
+    return check_state_io(io);
+}
+
 int kws_train_destroy(kws_train_handle h) {
     if (!h) return KWS_OK;
     train_core_destroy(h);
@@ -377,19 +438,15 @@ int kws_train_grad(kws_train_handle h, const float* x, const int32_t* seq_len, c
 int kws_train_grad_state(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
                          int T, int S_max, const uint8_t* drop_or_null, float* loss, float* grad_blob, float* logits_or_null,
                          const kws_train_state_io* io, void* stream) {
+    return grad_call(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, loss, grad_blob, logits_or_null, io, nullptr, stream);
+}
+
+int kws_train_grad_frames(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
+                          int T, int S_max, const uint8_t* drop_or_null, float* loss, float* grad_blob, float* logits_or_null,
+                          const kws_train_state_io* io, const kws_frame_targets* ft, void* stream) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
-    KWS_TRY(check_call(h->cfg, x, seq_len, labels, label_len, B, T, S_max, loss));
-    if (!grad_blob) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
-    if (misaligned(grad_blob) || misaligned(logits_or_null) || misaligned(drop_or_null))
-        return fail(KWS_ERR_INVALID_ARGUMENT, "grad_blob, logits and drop must be 4-byte aligned (the masks are read four units at a time)");
-    KWS_TRY(check_state_io(io));
-    return train_call(h, stream, [&](hipStream_t st) -> int {
-        KWS_TRY(grad_impl(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, loss, io, st));
-        KWS_HIP(hipMemcpyAsync(grad_blob, h->grad, h->P * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if (logits_or_null)
-            KWS_HIP(hipMemcpyAsync(logits_or_null, h->cv.logits, (size_t)B * T * h->cfg.model.num_classes * sizeof(float), hipMemcpyDeviceToDevice, st));
-        return KWS_OK;
-    });
+    KWS_TRY(check_frame_targets(ft, h->cfg.model.num_classes));
+    return grad_call(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, loss, grad_blob, logits_or_null, io, ft, stream);
 }
 
 int kws_train_step(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T,
@@ -400,16 +457,15 @@ int kws_train_step(kws_train_handle h, const float* x, const int32_t* seq_len, c
 int kws_train_step_state(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
                          int T, int S_max, const uint8_t* drop_or_null, float lr, float* loss, float* grad_norm_or_null,
                          const kws_train_state_io* io, void* stream) {
+    return step_call(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, lr, loss, grad_norm_or_null, io, nullptr, stream);
+}
+
+int kws_train_step_frames(kws_train_handle h, const float* x, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B,
+                          int T, int S_max, const uint8_t* drop_or_null, float lr, float* loss, float* grad_norm_or_null,
+                          const kws_train_state_io* io, const kws_frame_targets* ft, void* stream) {
     if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
-    KWS_TRY(check_call(h->cfg, x, seq_len, labels, label_len, B, T, S_max, loss));
-    if (!(lr > 0.f) || !std::isfinite(lr)) return fail(KWS_ERR_INVALID_ARGUMENT, "lr=%g has to be positive and finite", (double)lr);
-    if (misaligned(grad_norm_or_null) || misaligned(drop_or_null))
-        return fail(KWS_ERR_INVALID_ARGUMENT, "grad_norm and drop must be 4-byte aligned (the masks are read four units at a time)");
-    KWS_TRY(check_state_io(io));
-    return train_call(h, stream, [&](hipStream_t st) -> int {
-        KWS_TRY(grad_impl(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, loss, io, st));
-        return update_impl(h, lr, grad_norm_or_null, st);
-    });
+    KWS_TRY(check_frame_targets(ft, h->cfg.model.num_classes));
+    return step_call(h, x, seq_len, labels, label_len, B, T, S_max, drop_or_null, lr, loss, grad_norm_or_null, io, ft, stream);
 }
 
 int kws_train_apply(kws_train_handle h, const float* grad_blob, float lr, float* grad_norm_or_null, void* stream) {

@@ -476,6 +476,22 @@ inline size_t enroll_fit_lds_bytes(int H, int n, int K, int T, int S_max) {
 // logits [B,T,C]; seq_len / label_len [B], labels [B,S_max]: device copies the host side has range-checked; grad [B,T,C] or null
 hipError_t launch_ctc_loss(const float* logits, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int B, int T, int C,
                            int S_max, float* loss, float* grad, hipStream_t st);
+// frame_loss_kernels.hip: the frame-wise softmax cross-entropy of utterance b over its labelled frames (targets >= 0, t < seq_len[b]),
+// ce_b = sum_t w[y_t] (logsumexp(z_t) - z_t[y_t]) / W_b with W_b = sum_t w[y_t] (0 / 0 when W_b == 0; NaN when a live target lies
+// outside [-1, C)), one workgroup per utterance.  Everything is device memory; seq_len is clamped to [0, T], nothing at t >= seq_len is read.
+struct FrameLossParams {
+    const float* logits;          // [B,T,C]
+    const int32_t* seq_len;       // [B]
+    const int32_t* targets;       // [B,T]: -1 no target, 0..C-1 (the blank, C-1, is a target like the others)
+    const float* weight;          // [C] or null (all 1)
+    float* ce;                    // [B] or null: ce_b alone
+    float* loss;                  // [B] or null: loss[b] = (mix_prev != 0 ? mix_prev * loss[b] : 0) + mix_ce * ce_b
+    float* grad;                  // [B,T,C] or null: scale * (w[y_t] / W_b) (softmax(z_t) - onehot(y_t)) ...
+    float scale, mix_prev, mix_ce;
+    int accumulate;               // ... 0: written to every row of the utterance (zeros where no target counts); 1: added to the rows with one
+    int T, C;
+};
+hipError_t launch_frame_loss(const FrameLossParams& p, int B, hipStream_t st);
 // align_kernels.hip: CTC forced alignment, one wave per utterance.  LDS: lp [T][8] floats | the Viterbi back-pointers, two 64-bit masks
 // per frame | the path's state per frame, [T] int32 | and, only when the loss or the posteriors are asked for, alpha [T][2 S_max + 1]
 // floats: 4 T (13 + (2 S_max + 1 if with_alpha)) bytes

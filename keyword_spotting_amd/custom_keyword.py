@@ -121,6 +121,59 @@ def ctc_loss(logits, seq_len, labels, want_grad=True):
     return loss, grad
 
 
+def _class_weight(class_weight, classes):
+    """None, or the [classes] float32 host array of a frame loss's class weights with its pointer."""
+    if class_weight is None:
+        return None, None
+    w = np.ascontiguousarray(class_weight, np.float32)
+    if w.shape != (classes,):
+        raise _lib.InvalidArgumentError(-1, "class_weight: %s for %d classes" % (w.shape, classes))
+    return w, w.ctypes.data_as(ctypes.c_void_p)
+
+
+def _frame_targets(targets, shape, classes, device):
+    """targets [B,T] -> an int32 tensor on `device`.  A host array is range-checked here (-1: no target, else 0..classes-1) before
+    it is uploaded; a device tensor is passed through unsynchronised (the kernel reports a value out of range as a NaN loss)."""
+    import torch
+    if isinstance(targets, torch.Tensor) and targets.is_cuda:
+        t = targets.to(device=device, dtype=torch.int32).contiguous()
+    else:
+        a = targets.numpy() if isinstance(targets, torch.Tensor) else np.asarray(targets)
+        if a.shape == tuple(shape) and ((a < -1).any() or (a >= classes).any()):
+            raise _lib.InvalidArgumentError(-1, "targets outside [-1,%d] (-1: no target; the blank is class %d)" % (classes - 1, classes - 1))
+        t = torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(device)
+    if tuple(t.shape) != tuple(shape):
+        raise _lib.InvalidArgumentError(-1, "targets must be [%d,%d], got %s" % (shape[0], shape[1], tuple(t.shape)))
+    return t
+
+
+def frame_loss(logits, seq_len, targets, class_weight=None, want_grad=True):
+    """kws_frame_loss: logits [B,T,C] (device tensor or array), seq_len [B] or None, targets [B,T] (frame_labels' form: the class of
+    every frame, the blank C-1 included, -1 for none; array or device tensor), class_weight [C] or None -> (loss [B], grad_logits
+    [B,T,C] or None), device tensors.  Per utterance torch's F.cross_entropy(logits[:n], targets[:n], weight=class_weight,
+    ignore_index=-1, reduction='mean') with its gradient, except that an utterance without a labelled frame of positive weight
+    has loss 0 and gradient 0.  A target outside [-1, C) in a device tensor makes its utterance's loss NaN."""
+    import torch
+    lib = _lib.load()
+    lg = torch.as_tensor(logits)
+    if lg.dim() != 3:
+        raise _lib.InvalidArgumentError(-1, "logits must be [B,T,C], got %s" % (tuple(lg.shape),))
+    if not lg.is_cuda:
+        lg = lg.to("cuda:0")
+    lg = lg.to(torch.float32).contiguous()
+    b, t, c = (int(v) for v in lg.shape)
+    tg = _frame_targets(targets, (b, t), c, lg.device)
+    sl, sl_p = _ints(np.full(b, t) if seq_len is None else seq_len)
+    if sl.shape != (b,):
+        raise _lib.InvalidArgumentError(-1, "seq_len: %s for %d utterances" % (sl.shape, b))
+    w, w_p = _class_weight(class_weight, c)
+    loss = torch.empty(b, dtype=torch.float32, device=lg.device)
+    grad = torch.empty_like(lg) if want_grad else None
+    with torch.cuda.device(lg.device):
+        _lib.check(lib.kws_frame_loss(_lib.ptr(lg), sl_p, _lib.ptr(tg), w_p, b, t, c, _lib.ptr(loss), _lib.ptr(grad), _lib.current_stream_ptr()))
+    return loss, grad
+
+
 Alignment = collections.namedtuple("Alignment", ["states", "spans", "score", "loss", "post"])
 
 

@@ -53,14 +53,19 @@ class Trainer(_TrainerBase):
     wrapped: None takes kws_train_create_wrapped exactly when one of the three switches is set; True takes it always (with every switch
     off it gives kws_train_create's handle: the same launches, the same bits).
     state_noise: > 0 starts every step() that is given no state from state_noise * randn([L,B,H]) (the reference README's "noisy
-    states": a model served with carried state never sees the zero state after its first chunk)."""
+    states": a model served with carried state never sees the zero state after its first chunk).
+    frame_weight, ctc_weight, class_weight: the objective of the calls that are given targets= (frame-wise targets [B,T], the form of
+    custom_keyword.frame_labels: a class per frame, the blank included, -1 for none) -- loss_and_grad_frames, step_frames and step_raw's
+    targets=: loss[b] = ctc_weight ctc_b + frame_weight ce_b (kws_train_grad_frames / kws_train_step_frames); with ctc_weight 0 labels
+    may be None.  A call without targets is the CTC loss alone."""
 
     _prefix, _weights_mod, _feature = "kws_train", _weights, "n_mel"
 
     def __init__(self, config, weights=None, optimizer="adam", learning_rate=1.5e-3, lr_decay=0.8, decay_step=20000, max_grad_norm=-1,
-                 keep_prob=1.0, seed=0, device="cuda:0", wrapped=None, state_noise=0.0):
+                 keep_prob=1.0, seed=0, device="cuda:0", wrapped=None, state_noise=0.0, frame_weight=0.0, ctc_weight=1.0, class_weight=None):
         import torch
         self.config = config
+        self._set_objective(frame_weight, ctc_weight, class_weight)
         self.optimizer, self.learning_rate, self.lr_decay, self.decay_step = optimizer, float(learning_rate), float(lr_decay), int(decay_step)
         self.max_grad_norm, self.keep_prob, self.state_noise = float(max_grad_norm), float(keep_prob), float(state_noise)
         self._cfg = train_config(config, optimizer, max_grad_norm, keep_prob)
@@ -103,9 +108,9 @@ class Trainer(_TrainerBase):
     def learning_rate_at(self, step):
         return learning_rate_at(step, self.learning_rate, self.lr_decay, self.decay_step)
 
-    def _inputs(self, x, lengths, labels, drop):
+    def _inputs(self, x, lengths, labels, drop, targets=None):
         import torch
-        x, b, t, sl, lab, lab_len = super(Trainer, self)._inputs(x, lengths, labels)
+        x, b, t, sl, lab, lab_len = super(Trainer, self)._inputs(x, lengths, labels, targets)
         if drop is not None:
             drop = torch.as_tensor(drop).to(device=self.device, dtype=torch.uint8).contiguous()
             if tuple(drop.shape) != self._drop_shape(b, t):
@@ -146,14 +151,29 @@ class Trainer(_TrainerBase):
         are those of sum_b ctc_b / B + <dstate_out, state_out> (dstate_out None: zeros) and dstate_in is that objective's gradient with
         respect to state.  A recording in two segments: (.., (sa, _)) = f(A, want_state=True); (.., gb, .., (sb, da)) = f(B, state=sa,
         want_state=True); (.., ga, .., (_, d0)) = f(A, dstate_out=da, want_state=True): ga + gb is the gradient of both losses."""
+        return self._grad(x, lengths, labels, None, drop, want_logits, state, dstate_out, want_state, False)
+
+    def loss_and_grad_frames(self, x, lengths, labels, targets, drop=None, want_logits=False, state=None, dstate_out=None, want_state=False,
+                             want_frame_loss=False):
+        """loss_and_grad on frame-wise targets [B,T] (kws_train_grad_frames): the per-utterance losses are ctc_weight ctc_b + frame_weight
+        ce_b, the gradients those of their sum / B (+ <dstate_out, state_out>); with want_frame_loss ce [B] (device) is appended to what
+        loss_and_grad returns.  labels may be None at ctc_weight 0; targets None is loss_and_grad."""
+        return self._grad(x, lengths, labels, targets, drop, want_logits, state, dstate_out, want_state, want_frame_loss)
+
+    def _grad(self, x, lengths, labels, targets, drop, want_logits, state, dstate_out, want_state, want_frame_loss):
         import torch
-        x, b, t, (sl, sl_p), (lab, lab_p), (ll, ll_p), drop = self._inputs(x, lengths, labels, drop)
+        x, b, t, (sl, sl_p), (lab, lab_p), (ll, ll_p), drop = self._inputs(x, lengths, labels, drop, targets)
         io, keep, outs = self._state_io(b, state, dstate_out, want_state)
+        ft, keep_ft, ce = self._frames(targets, b, t, want_frame_loss)
         loss = torch.empty(b, dtype=torch.float32, device=self.device)
         grad = torch.empty(self._floats(), dtype=torch.float32, device=self.device)
         logits = torch.empty(b, t, self.config.num_classes, dtype=torch.float32, device=self.device) if want_logits else None
         with torch.cuda.device(self.device):
-            if io is None:
+            if ft is not None:
+                _lib.check(self._lib.kws_train_grad_frames(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]), _lib.ptr(drop),
+                                                           _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(logits),
+                                                           None if io is None else ctypes.byref(io), ctypes.byref(ft), self._stream()))
+            elif io is None:
                 _lib.check(self._lib.kws_train_grad(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]), _lib.ptr(drop),
                                                     _lib.ptr(loss), _lib.ptr(grad), _lib.ptr(logits), self._stream()))
             else:
@@ -163,18 +183,26 @@ class Trainer(_TrainerBase):
         out = (float(per.astype(np.float64).sum() / b), _weights.from_blob(self.config, grad.cpu().numpy()), per)
         if want_logits:
             out += (logits,)
-        return out + (outs,) if want_state else out
+        if want_state:
+            out += (outs,)
+        return out + (ce,) if want_frame_loss else out
 
-    def step_raw(self, x, lengths, labels, lr, drop=None, want_norm=False, state=None, dstate_out=None, want_state=False):
+    def step_raw(self, x, lengths, labels, lr, drop=None, want_norm=False, state=None, dstate_out=None, want_state=False, targets=None):
         """One kws_train_step at learning rate lr with the given masks -> per-utterance losses [B] (device) [, global norm (device)]
-        [, (state_out, dstate_in)]; state / dstate_out as loss_and_grad's: the step applies the gradient of the whole objective."""
+        [, (state_out, dstate_in)]; state / dstate_out as loss_and_grad's: the step applies the gradient of the whole objective.
+        targets [B,T]: the step of the trainer's mixed objective (kws_train_step_frames)."""
         import torch
-        x, b, t, (sl, sl_p), (lab, lab_p), (ll, ll_p), drop = self._inputs(x, lengths, labels, drop)
+        x, b, t, (sl, sl_p), (lab, lab_p), (ll, ll_p), drop = self._inputs(x, lengths, labels, drop, targets)
         io, keep, outs = self._state_io(b, state, dstate_out, want_state)
+        ft, keep_ft, _ = self._frames(targets, b, t)
         loss = torch.empty(b, dtype=torch.float32, device=self.device)
         norm = torch.empty(1, dtype=torch.float32, device=self.device) if want_norm else None
         with torch.cuda.device(self.device):
-            if io is None:
+            if ft is not None:
+                _lib.check(self._lib.kws_train_step_frames(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]), _lib.ptr(drop),
+                                                           float(lr), _lib.ptr(loss), _lib.ptr(norm),
+                                                           None if io is None else ctypes.byref(io), ctypes.byref(ft), self._stream()))
+            elif io is None:
                 _lib.check(self._lib.kws_train_step(self._handle, _lib.ptr(x), sl_p, lab_p, ll_p, b, t, int(lab.shape[1]), _lib.ptr(drop),
                                                     float(lr), _lib.ptr(loss), _lib.ptr(norm), self._stream()))
             else:
@@ -210,6 +238,11 @@ class Trainer(_TrainerBase):
         -> loss = sum_b ctc_b / B [, state_out with want_state].  state [L,B,H]: where the layers start, e.g. the state_out of the
         step on the recording's previous chunk; without one and with state_noise > 0 it is state_noise * randn([L,B,H]), drawn from
         the same generator after the dropout draws."""
+        return self.step_frames(x, lengths, labels, None, state=state, want_state=want_state)
+
+    def step_frames(self, x, lengths, labels, targets, state=None, want_state=False):
+        """step() on frame-wise targets [B,T]: the same draws, the schedule and the update of the trainer's mixed objective
+        (kws_train_step_frames) -> loss = sum_b (ctc_weight ctc_b + frame_weight ce_b) / B [, state_out].  targets None is step()."""
         import torch
         x = torch.as_tensor(x).to(device=self.device, dtype=torch.float32)
         drop = None
@@ -221,7 +254,8 @@ class Trainer(_TrainerBase):
         if state is None and self.state_noise > 0.0:
             state = self.state_noise * torch.randn((self.config.num_layers, x.shape[0], self.config.hidden_size), generator=self._gen,
                                                    device=self.device)
-        out = self.step_raw(x, lengths, labels, self.learning_rate_at(self.global_step), drop=drop, state=state, want_state=want_state)
+        out = self.step_raw(x, lengths, labels, self.learning_rate_at(self.global_step), drop=drop, state=state, want_state=want_state,
+                            targets=targets)
         loss = out[0] if want_state else out
         self.global_step += 1
         total = float(loss.cpu().numpy().astype(np.float64).sum() / loss.shape[0])
