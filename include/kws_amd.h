@@ -590,6 +590,7 @@ int kws_ctc_align(const float* logits, const int32_t* seq_len, const int32_t* la
  *                     lr_t = lr sqrt(1 - 0.999^t) / (1 - 0.9^t), theta -= lr_t m / (sqrt(v) + 1e-8); no gradient clipping.
  *                     loss_trace [iterations, B] (device) or NULL: every slot's loss at every step, before that step's update.
  *                     N calls of one iteration give the bits of one call of N.
+ *   kws_enroll_fit_frames  the same fit on frame-wise targets, alone or mixed with the CTC loss ("Frame-wise targets" below)
  *   kws_enroll_get    the handle's Wn, bn -> device buffers
  *   kws_enroll_moments  Adam's m and v, each [E,H,n_new] followed by [E,n_new], -> device buffers (inspection / tests)
  *   kws_enroll_stats  device bytes the handle holds, device (re)allocations since create (one at the first fit of a shape; each
@@ -1095,7 +1096,31 @@ int kws_attention_drop_keep(uint64_t drop_seed, float keep_prob, int site, int l
  *   Refused before the device is touched: ft or ft->targets NULL; a weight (ctc, frame, class) negative or not finite; both of ctc_weight
  *   and frame_weight 0; frame_weight == 0 with ctc_weight != 1; targets or frame_loss not 4-byte aligned; everything the _state call
  *   refuses (with ctc_weight == 0 nothing about the labels).  kws_[attention_]train_check_frames decide all of it from host memory alone.
- * Out of scope: label smoothing, targets in host memory, kws_enroll_fit with the frame loss. */
+ *
+ * The enrolment handle (kws_enroll_fit_frames): kws_enroll_fit with loss_trace[it,b] = ctc_weight ctc_b + frame_weight ce_b per step, ce_b
+ * as above on the spliced rows logits2 over the C + n_new classes of the extended head -- targets [E*K,T] in ITS numbering: C-1 .. C+n_new-2
+ * the new classes, C+n_new-1 the blank, what frame_labels(states, labels, blank = C+n_new-1) emits; class_weight [C + n_new].  Only the new
+ * columns train: on column j the frame term's gradient at a labelled frame is frame_weight (w[y_t] / W_b) (softmax(z_t)[C-1+j] -
+ * [y_t == C-1+j]) -- at a frame labelled with a trained class or the blank, the mass the new column has there.  The gradient of the
+ * step's loss is summed over the K slots in slot order, divided by K, and goes through the unchanged Adam.  ft->frame_loss, unless
+ * NULL, is [iterations, E*K] and receives ce_b alone at every step.
+ *     ctc_weight == 0      one forward pass per step: project, softmax, accumulate.  No alpha / beta and no LDS per frame -- (3 + K)(H + 1)
+ *                          n_new floats whatever T is, so kws_enroll_fit's limits on T and S_max do not apply (E * K * T < 2^31 does).
+ *                          labels and label_len may be NULL, nothing about them is checked and S_max is taken as 0.
+ *     both weights > 0     the frame term is accumulated in the forward pass (frames 0 .. n-1), the CTC term behind it in the beta pass
+ *                          (frames n-1 .. 0); kws_enroll_fit's LDS.  A slot without a valid CTC path has loss +inf and a CTC gradient
+ *                          of 0, and still contributes its frame term.
+ *     frame_weight == 0    needs ctc_weight == 1: exactly kws_enroll_fit's launch and bits; ft->frame_loss is not written.
+ *   W_b is computed once per launch (lane l of the slot's wave adds frames l, l + 64, .. in fp64, then a butterfly).  A target outside
+ *   [-1, C + n_new) at a live frame counts as -1 and makes that slot's loss_trace and frame_loss NaN at every step; the update is that of
+ *   -1 in its place, and nothing is read out of bounds.  The class weights ride in the handle's upload block behind [seq_len | label_len |
+ *   labels]: with the ints and weights of the call before nothing is uploaded, the steady state allocates nothing, and kws_enroll_stats
+ *   counts one allocation per shape.  The step count and the moments run on as kws_enroll_fit's do (N calls of one iteration give the
+ *   bits of one call of N), and calls of the two entry points may be interleaved on one handle.
+ *   Refused: everything above about ft (for C + n_new classes), everything kws_enroll_fit refuses (with ctc_weight == 0 nothing about
+ *   the labels; LDS above 160 KiB with the byte counts in the mixed case only), E * K * T >= 2^31 (KWS_ERR_UNSUPPORTED).
+ *   kws_enroll_check_frames decides all of it, and kws_enroll_create's refusals of the shape, from host memory alone.
+ * Out of scope: label smoothing, targets in host memory, more than four slots per enrolment, training a frozen column. */
 int kws_frame_loss(const float* logits /*device [B,T,C]*/, const int32_t* seq_len /*host [B]*/, const int32_t* targets /*device [B,T]*/,
                    const float* class_weight_or_null /*host [C]*/, int B, int T, int C, float* loss /*device [B]*/,
                    float* grad_logits_or_null /*device [B,T,C]*/, void* stream);
@@ -1124,6 +1149,11 @@ int kws_attention_train_step_frames(kws_attention_train_handle h, const float* x
                                     float* grad_norm_or_null, const kws_frame_targets* ft, void* stream);
 int kws_attention_train_check_frames(const kws_attention_train_config* cfg, const float* x, const int32_t* seq_len, const int32_t* labels,
                                      const int32_t* label_len, int B, int T, int S_max, const float* loss, const kws_frame_targets* ft);
+int kws_enroll_fit_frames(kws_enroll_handle h, const float* nn_outputs, const float* logits1, const int32_t* seq_len,
+                          const int32_t* labels_or_null, const int32_t* label_len_or_null, int T, int S_max, const kws_frame_targets* ft, float lr,
+                          int iterations, float* loss_trace_or_null, void* stream);
+int kws_enroll_check_frames(int H, int C, int n_new, int E, int K, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
+                            int T, int S_max, const kws_frame_targets* ft, float lr, int iterations);
 
 #ifdef __cplusplus
 }

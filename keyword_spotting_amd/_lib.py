@@ -195,6 +195,8 @@ _SIGNATURES = {
     "kws_enroll_destroy": (_i, [_vp]),
     "kws_enroll_set": (_i, [_vp, _vp, _vp, _vp]),
     "kws_enroll_fit": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _f, _i, _vp, _vp]),
+    "kws_enroll_fit_frames": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, ctypes.POINTER(KwsFrameTargets), _f, _i, _vp, _vp]),
+    "kws_enroll_check_frames": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, ctypes.POINTER(KwsFrameTargets), _f, _i]),
     "kws_enroll_get": (_i, [_vp, _vp, _vp, _vp]),
     "kws_enroll_moments": (_i, [_vp, _vp, _vp, _vp]),
     "kws_enroll_stats": (_i, [_vp, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_int32), ctypes.POINTER(ctypes.c_int32)]),

@@ -52,6 +52,47 @@ void pack_ints(const int32_t* seq_len, const int32_t* labels, const int32_t* lab
 
 namespace {
 
+// what kws_enroll_create refuses about the shape, before the device is probed
+int check_enroll_shape(int H, int C, int n_new, int E, int K) {
+    if (H != 64 && H != 128 && H != 256) return fail(KWS_ERR_UNSUPPORTED, "hidden=%d unsupported (64, 128, 256)", H);
+    if (C < 3 || n_new < 1 || C + n_new > 8)
+        return fail(KWS_ERR_INVALID_ARGUMENT, "C=%d n_new=%d: the trained head has 3..7 classes and the extended one C + n_new <= 8", C, n_new);
+    if (E < 1) return fail(KWS_ERR_INVALID_ARGUMENT, "E=%d enrolments: at least one", E);
+    if (K < 1 || K > 4) return fail(KWS_ERR_INVALID_ARGUMENT, "K=%d utterance slots per enrolment out of range [1,4]", K);
+    return KWS_OK;
+}
+
+// what kws_enroll_fit refuses about a call on B = E x K slots, in its order; with_labels false (the frame loss alone): nothing about the
+// labels, and no LDS that grows with T.  null_ptr / odd_ptr: what the caller found about nn_outputs, logits1 and loss_trace (the host-only
+// checks have none of them: false)
+int check_enroll_call(int H, int n, int K, int B, int classes, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int T,
+                      int S_max, float lr, int iterations, bool with_labels, bool null_ptr, bool odd_ptr) {
+    if (T < 1 || S_max < 0) return fail(KWS_ERR_INVALID_ARGUMENT, "bad shape T=%d S_max=%d", T, S_max);
+    if (S_max > 31) return fail(KWS_ERR_INVALID_ARGUMENT, "S_max=%d out of range [0,31]: one lane of a wave per state of the extended label", S_max);
+    if (iterations < 1) return fail(KWS_ERR_INVALID_ARGUMENT, "iterations=%d: at least one", iterations);
+    if (!(lr > 0.f) || !std::isfinite(lr)) return fail(KWS_ERR_INVALID_ARGUMENT, "lr=%g has to be positive and finite", (double)lr);
+    if (null_ptr || !seq_len || (with_labels && (!label_len || (!labels && S_max > 0)))) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
+    if (odd_ptr) return fail(KWS_ERR_INVALID_ARGUMENT, "nn_outputs, logits1 and loss_trace must be 4-byte aligned");
+    if (with_labels) KWS_TRY(check_labels(seq_len, labels, label_len, B, T, S_max, classes));
+    else KWS_TRY(check_seq_len(seq_len, B, T));
+    const size_t lds = kws::enroll_fit_frames_lds_bytes(H, n, K, T, S_max, with_labels);
+    if (lds > kWindowIncLdsMax)
+        return fail(KWS_ERR_UNSUPPORTED, "an enrolment keeps %d utterances x %d frames x (8 log-probabilities + %d states) and %d x %d parameter "
+                    "images in LDS: %zu bytes exceed the %zu a workgroup may hold (fewer frames, shorter labels or fewer slots)", K, T,
+                    2 * S_max + 1, 3 + K, (H + 1) * n, lds, kWindowIncLdsMax);
+    return KWS_OK;
+}
+
+// ... and kws_enroll_fit_frames, whose labels count only next to a CTC term
+int check_enroll_frames(int H, int C, int n, int E, int K, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len, int T,
+                        int S_max, const kws_frame_targets* ft, float lr, int iterations, bool null_ptr = false, bool odd_ptr = false) {
+    KWS_TRY(check_frame_targets(ft, C + n));
+    const bool ctc = ft->ctc_weight > 0.f;
+    if ((size_t)E * K * (size_t)(T < 0 ? 0 : T) > (size_t)0x7fffffff)
+        return fail(KWS_ERR_UNSUPPORTED, "E=%d x K=%d x T=%d: more than 2^31 - 1 frames in one call", E, K, T);
+    return check_enroll_call(H, n, K, E * K, C + n, seq_len, labels, label_len, T, ctc ? S_max : 0, lr, iterations, ctc, null_ptr, odd_ptr);
+}
+
 int enroll_device_probe() {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return fail(KWS_ERR_NO_DEVICE, "no HIP device visible");
@@ -92,11 +133,7 @@ int kws_ctc_loss(const float* logits, const int32_t* seq_len, const int32_t* lab
 int kws_enroll_create(int H, int C, int n_new, int E, int K, kws_enroll_handle* out) {
     if (!out) return fail(KWS_ERR_INVALID_ARGUMENT, "out handle pointer is null");
     *out = nullptr;
-    if (H != 64 && H != 128 && H != 256) return fail(KWS_ERR_UNSUPPORTED, "hidden=%d unsupported (64, 128, 256)", H);
-    if (C < 3 || n_new < 1 || C + n_new > 8)
-        return fail(KWS_ERR_INVALID_ARGUMENT, "C=%d n_new=%d: the trained head has 3..7 classes and the extended one C + n_new <= 8", C, n_new);
-    if (E < 1) return fail(KWS_ERR_INVALID_ARGUMENT, "E=%d enrolments: at least one", E);
-    if (K < 1 || K > 4) return fail(KWS_ERR_INVALID_ARGUMENT, "K=%d utterance slots per enrolment out of range [1,4]", K);
+    KWS_TRY(check_enroll_shape(H, C, n_new, E, K));
     KWS_TRY(enroll_device_probe());
     kws_enroll* h = new (std::nothrow) kws_enroll();
     if (!h) return fail(KWS_ERR_OUT_OF_MEMORY, "host allocation failed");
@@ -139,30 +176,23 @@ int kws_enroll_set(kws_enroll_handle h, const float* Wn, const float* bn, void* 
     }());
 }
 
-int kws_enroll_fit(kws_enroll_handle h, const float* nn_outputs, const float* logits1, const int32_t* seq_len, const int32_t* labels,
-                   const int32_t* label_len, int T, int S_max, float lr, int iterations, float* loss_trace_or_null, void* stream) {
-    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
-    if (T < 1 || S_max < 0) return fail(KWS_ERR_INVALID_ARGUMENT, "bad shape T=%d S_max=%d", T, S_max);
-    if (S_max > 31) return fail(KWS_ERR_INVALID_ARGUMENT, "S_max=%d out of range [0,31]: one lane of a wave per state of the extended label", S_max);
-    if (iterations < 1) return fail(KWS_ERR_INVALID_ARGUMENT, "iterations=%d: at least one", iterations);
-    if (!(lr > 0.f) || !std::isfinite(lr)) return fail(KWS_ERR_INVALID_ARGUMENT, "lr=%g has to be positive and finite", (double)lr);
-    if (!nn_outputs || !logits1 || !seq_len || !label_len || (!labels && S_max > 0)) return fail(KWS_ERR_INVALID_ARGUMENT, "null pointer argument");
-    if (misaligned(nn_outputs) || misaligned(logits1) || misaligned(loss_trace_or_null))
-        return fail(KWS_ERR_INVALID_ARGUMENT, "nn_outputs, logits1 and loss_trace must be 4-byte aligned");
+// The launch both fit entry points end in, behind their refusals: the host ints (and, with frame targets, the class weights) into the
+// handle's upload block -- [seq_len | label_len | labels | weights], re-sent only when it differs from the call before --, then the
+// plain kernel (ft null) or the frames one.  ft->ctc_weight == 0: labels and label_len may be null and S_max is 0.
+static int enroll_fit_launch(kws_enroll_handle h, const float* nn_outputs, const float* logits1, const int32_t* seq_len, const int32_t* labels,
+                             const int32_t* label_len, int T, int S_max, const kws_frame_targets* ft, float lr, int iterations,
+                             float* loss_trace_or_null, void* stream) {
     const int B = h->E * h->K;
-    KWS_TRY(check_labels(seq_len, labels, label_len, B, T, S_max, h->C + h->n));
-    const size_t lds = kws::enroll_fit_lds_bytes(h->H, h->n, h->K, T, S_max);
-    if (lds > kWindowIncLdsMax)
-        return fail(KWS_ERR_UNSUPPORTED, "an enrolment keeps %d utterances x %d frames x (8 log-probabilities + %d states) and %d x %d parameter "
-                    "images in LDS: %zu bytes exceed the %zu a workgroup may hold (fewer frames, shorter labels or fewer slots)", h->K, T,
-                    2 * S_max + 1, 3 + h->K, (h->H + 1) * h->n, lds, kWindowIncLdsMax);
     BusyGuard guard(h->in_call);
     if (!guard.owned) return fail(KWS_ERR_BUSY, "another host thread is inside a call on this enrolment handle");
     hipStream_t st = static_cast<hipStream_t>(stream);
     KWS_TRY(h->order.enter(st));
     return h->order.finish(st, [&]() -> int {
         std::vector<int32_t> ints;
-        pack_ints(seq_len, labels, label_len, B, S_max, &ints);
+        const std::vector<int32_t> no_labels((size_t)B, 0);
+        pack_ints(seq_len, labels, label_len ? label_len : no_labels.data(), B, S_max, &ints);
+        const size_t weights_at = ints.size();
+        if (ft) append_class_weights(ft->class_weight, h->C + h->n, &ints);
         if (ints.size() > h->ints_cap) {          // the first call at this shape: the block only grows (waits for the device once)
             KWS_HIP(hipDeviceSynchronize());
             if (h->ints) (void)hipFree(h->ints);
@@ -181,10 +211,46 @@ int kws_enroll_fit(kws_enroll_handle h, const float* nn_outputs, const float* lo
         p.W = h->W; p.b = h->b; p.mW = h->mW; p.mb = h->mb; p.vW = h->vW; p.vb = h->vb;
         p.loss_trace = loss_trace_or_null; p.lr = lr;
         p.K = h->K; p.n = h->n; p.C = h->C; p.T = T; p.S_max = S_max; p.iterations = iterations; p.step0 = h->steps;
-        KWS_TRY(hip_done(kws::launch_enroll_fit(p, h->H, h->E, st), "launch enroll_fit"));
+        if (!ft) {
+            KWS_TRY(hip_done(kws::launch_enroll_fit(p, h->H, h->E, st), "launch enroll_fit"));
+        } else {
+            kws::EnrollFitFramesParams q = {};
+            q.fit = p;
+            q.targets = ft->targets; q.weight = reinterpret_cast<const float*>(h->ints + weights_at); q.frame_loss = ft->frame_loss;
+            q.ctc_weight = ft->ctc_weight; q.frame_weight = ft->frame_weight;
+            KWS_TRY(hip_done(kws::launch_enroll_fit_frames(q, h->H, h->E, st), "launch enroll_fit_frames"));
+        }
         h->steps += iterations;
         return KWS_OK;
     }());
+}
+
+int kws_enroll_fit(kws_enroll_handle h, const float* nn_outputs, const float* logits1, const int32_t* seq_len, const int32_t* labels,
+                   const int32_t* label_len, int T, int S_max, float lr, int iterations, float* loss_trace_or_null, void* stream) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    KWS_TRY(check_enroll_call(h->H, h->n, h->K, h->E * h->K, h->C + h->n, seq_len, labels, label_len, T, S_max, lr, iterations, true,
+                              !nn_outputs || !logits1, misaligned(nn_outputs) || misaligned(logits1) || misaligned(loss_trace_or_null)));
+    return enroll_fit_launch(h, nn_outputs, logits1, seq_len, labels, label_len, T, S_max, nullptr, lr, iterations, loss_trace_or_null, stream);
+}
+
+int kws_enroll_check_frames(int H, int C, int n_new, int E, int K, const int32_t* seq_len, const int32_t* labels, const int32_t* label_len,
+                            int T, int S_max, const kws_frame_targets* ft, float lr, int iterations) {
+    KWS_TRY(check_enroll_shape(H, C, n_new, E, K));
+    return check_enroll_frames(H, C, n_new, E, K, seq_len, labels, label_len, T, S_max, ft, lr, iterations);
+}
+
+int kws_enroll_fit_frames(kws_enroll_handle h, const float* nn_outputs, const float* logits1, const int32_t* seq_len,
+                          const int32_t* labels_or_null, const int32_t* label_len_or_null, int T, int S_max, const kws_frame_targets* ft, float lr,
+                          int iterations, float* loss_trace_or_null, void* stream) {
+    if (!h) return fail(KWS_ERR_INVALID_ARGUMENT, "handle is null");
+    KWS_TRY(check_enroll_frames(h->H, h->C, h->n, h->E, h->K, seq_len, labels_or_null, label_len_or_null, T, S_max, ft, lr, iterations,
+                                !nn_outputs || !logits1, misaligned(nn_outputs) || misaligned(logits1) || misaligned(loss_trace_or_null)));
+    if (ft->frame_weight == 0.f)          // the plain call: its launch, its bits, its upload block
+        return enroll_fit_launch(h, nn_outputs, logits1, seq_len, labels_or_null, label_len_or_null, T, S_max, nullptr, lr, iterations,
+                                 loss_trace_or_null, stream);
+    const bool ctc = ft->ctc_weight > 0.f;
+    return enroll_fit_launch(h, nn_outputs, logits1, seq_len, ctc ? labels_or_null : nullptr, ctc ? label_len_or_null : nullptr, T,
+                             ctc ? S_max : 0, ft, lr, iterations, loss_trace_or_null, stream);
 }
 
 int kws_enroll_get(kws_enroll_handle h, float* Wn, float* bn, void* stream) {

@@ -521,6 +521,20 @@ struct EnrollFitParams {
     int K, n, C, T, S_max, iterations, step0;       // step0: optimiser steps taken before this launch
 };
 hipError_t launch_enroll_fit(const EnrollFitParams& p, int hidden, int E, hipStream_t st);
+// The fit on frame-wise targets (kws_enroll_fit_frames, frame_weight > 0): per step and slot loss = ctc_weight ctc_b + frame_weight ce_b
+// with ce_b FrameLossParams' cross-entropy of the spliced rows over the C + n classes, and the gradient of that with respect to the new
+// columns.  ctc_weight == 0: fit.labels / label_len are not read, fit.S_max is 0 and nothing in LDS grows with T.
+struct EnrollFitFramesParams {
+    EnrollFitParams fit;
+    const int32_t* targets;       // [E*K,T]: -1 no target, 0..C+n-1 in the extended head's numbering
+    const float* weight;          // [kMaxClasses]: the class weights (ones: none)
+    float* frame_loss;            // [iterations, E*K] or null: ce_b alone
+    float ctc_weight, frame_weight;
+};
+inline size_t enroll_fit_frames_lds_bytes(int H, int n, int K, int T, int S_max, bool ctc) {
+    return ctc ? enroll_fit_lds_bytes(H, n, K, T, S_max) : enroll_fit_lds_bytes(H, n, K, 0, 0);
+}
+hipError_t launch_enroll_fit_frames(const EnrollFitFramesParams& q, int hidden, int E, hipStream_t st);
 
 // Training of the stack (gru_train.hip: the two frame loops; train_kernels.hip: everything around them).  Every activation block is
 // plain row-major [B*T, width] fp32, row = b * T + t; `live` [B*T] is 1 for t < seq_len[b].

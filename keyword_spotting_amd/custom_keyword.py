@@ -45,6 +45,14 @@ noise per batch of optimiser steps:
     frontend = DatasetFrontend(config)                                   # a mel front-end of |X| (config.power 1)
     clean, noise = frontend.linear(utterances, n_samples), frontend.linear(noise_clips, noise_samples)
     new_columns, new_bias, loss_trace = enroller.fit_augmented(frontend, clean, noise, NoiseAugmenter(seed=1), labels, steps=100)
+
+The CTC loss of three positive recordings never says "do not fire here".  A frame-wise target does: on every frame labelled with a
+trained class or the blank the frame cross-entropy pushes the new columns' mass down (kws_enroll_fit_frames: the frame loss inside the
+fit, alone or mixed with the CTC loss), in the user's own recordings and in a recording without the keyword that sits in a spare slot:
+
+    targets = enroller.frame_targets(mel, lengths, labels, new_columns, new_bias)       # align, then frame_labels: [E*K, T]
+    new_columns, new_bias, loss_trace = enroller.fit_frames(mel, lengths, labels, targets, steps=100, init=(new_columns, new_bias))
+    weights2 = enroll_frames(model, [mel1, mel2, mel3], ctc_label([5, 6]), n_new=2, negatives=[mel4], negative_labels=[0, 4, 0])
 """
 import collections
 import copy
@@ -225,6 +233,19 @@ def frame_labels(states, labels, blank):
     return np.where(st < 0, -1, out).astype(np.int32)
 
 
+def extend_targets(targets, C, n_new):
+    """Frame-wise targets in the numbering of the trained head (C classes, blank C-1) -> the extended head's (C + n_new classes): the
+    blank C-1 becomes C+n_new-1, classes 0..C-2 and -1 stay.  What a recording WITHOUT the new keyword needs before Enroller.fit_frames
+    takes it in a spare slot: its transcript is aligned on head 1's own logits (ctc_align, frame_labels with blank C-1).  Host code."""
+    a = targets.cpu().numpy() if hasattr(targets, "cpu") else np.asarray(targets)
+    c, n = int(C), int(n_new)
+    if c < 3 or n < 1 or c + n > 8:
+        raise _lib.InvalidArgumentError(-1, "C=%d n_new=%d: the trained head has 3..7 classes and the extended one C + n_new <= 8" % (c, n))
+    if a.dtype.kind not in "iu" or (a < -1).any() or (a >= c).any():
+        raise _lib.InvalidArgumentError(-1, "targets outside [-1,%d] (-1: no target; the blank is class %d)" % (c - 1, c - 1))
+    return np.where(a == c - 1, c + n - 1, a).astype(np.int32)
+
+
 def truncated_normal(shape, seed=0):
     """tf.truncated_normal's distribution (models/rnn_ctc.py:266): standard normal, redrawn outside two sigma."""
     rng = np.random.default_rng(seed)
@@ -346,32 +367,78 @@ class Enroller(object):
         steps at learning rate lr from `init` = (columns [E,H,n_new], bias [E,n_new]) or, None, the reference's truncated normal
         (models/rnn_ctc.py:266) with zero bias.  -> (new_columns [E,H,n_new], new_bias [E,n_new], loss_trace [steps, E*K]):
         device tensors; loss_trace[s] holds every slot's loss before step s's update."""
+        return self._fit(inputs, lengths, labels, steps, lr, init, seed, None)
+
+    def fit_frames(self, inputs, lengths, labels, targets, steps, frame_weight=1.0, ctc_weight=1.0, class_weight=None, lr=1.5e-3, init=None,
+                   seed=0, want_frame_loss=False):
+        """fit on frame-wise targets (kws_enroll_fit_frames): per step and slot loss = ctc_weight ctc + frame_weight ce, ce the frame
+        cross-entropy (frame_loss's) of the extended head's rows.  targets [E*K, T] over the C + n_new classes of that head, -1 for no
+        target -- frame_targets' form (array, range-checked here, or device tensor); class_weight [C + n_new] or None.  labels may be None
+        at ctc_weight = 0, and then neither fit's limit on T nor the one on the labels applies.  inputs, lengths, steps, lr, init, seed
+        and the result (new_columns, new_bias, loss_trace) are fit's; with want_frame_loss a fourth tensor [steps, E*K]: ce alone."""
+        return self._fit(inputs, lengths, labels, steps, lr, init, seed, (targets, frame_weight, ctc_weight, class_weight, want_frame_loss))
+
+    def _start(self, labels, init, seed, with_labels):
+        """What both fits take from labels, init and seed: (labels [E*K,S_max], label_len [E*K]) or (None, None), and the start (columns,
+        bias) on the device."""
         import torch
         e, k, h, n = self.enrolments, self.slots, self.config.hidden_size, self.n_new
-        b = e * k
-        lab, lab_len = _pack_labels(labels, b)
-        if lab.shape[1] > MAX_LABEL:
-            raise _lib.InvalidArgumentError(-1, "labels of up to %d entries, got %d" % (MAX_LABEL, lab.shape[1]))
-        nn, logits1 = self.features(inputs, lengths)
-        t = int(nn.shape[1])
+        lab = lab_len = None
+        if with_labels:
+            lab, lab_len = _pack_labels(labels, e * k)
+            if lab.shape[1] > MAX_LABEL:
+                raise _lib.InvalidArgumentError(-1, "labels of up to %d entries, got %d" % (MAX_LABEL, lab.shape[1]))
         if init is None:
             init = (truncated_normal((e, h, n), seed), np.zeros((e, n), np.float32))
         wn = torch.as_tensor(init[0]).to(device=self.device, dtype=torch.float32).contiguous()
         bn = torch.as_tensor(init[1]).to(device=self.device, dtype=torch.float32).contiguous()
         if tuple(wn.shape) != (e, h, n) or tuple(bn.shape) != (e, n):
             raise _lib.InvalidArgumentError(-1, "init must be ([%d,%d,%d], [%d,%d]), got %s %s" % (e, h, n, e, n, tuple(wn.shape), tuple(bn.shape)))
+        return lab, lab_len, wn, bn
+
+    def _frame_term(self, frames, t, steps):
+        """fit_frames' (targets, frame_weight, ctc_weight, class_weight, want_frame_loss) for utterances of t frames -> (kws_frame_targets,
+        what its pointers point to, the ce trace [steps, E*K] or None)."""
+        import torch
+        targets, frame_weight, ctc_weight, class_weight, want = frames
+        b = self.enrolments * self.slots
+        tg = _frame_targets(targets, (b, t), self.num_classes2, self.device)
+        w, _ = _class_weight(class_weight, self.num_classes2)
+        ce = torch.empty(int(steps), b, dtype=torch.float32, device=self.device) if want else None
+        ft = _lib.KwsFrameTargets(tg.data_ptr(), None if w is None else w.ctypes.data, float(ctc_weight), float(frame_weight), None)
+        return ft, (tg, w), ce
+
+    def _steps(self, nn, logits1, sl_p, lab, lab_len, t, ft, ce, lr, s0, count, trace, stream):
+        """`count` optimiser steps from step s0 of the fit on the handle's current state: kws_enroll_fit, or kws_enroll_fit_frames (ft)."""
+        lab_p = None if lab is None else lab.ctypes.data_as(ctypes.c_void_p)
+        lab_len_p = None if lab_len is None else lab_len.ctypes.data_as(ctypes.c_void_p)
+        s_max = 0 if lab is None else int(lab.shape[1])
+        if ft is None:
+            _lib.check(self._lib.kws_enroll_fit(self._handle, _lib.ptr(nn), _lib.ptr(logits1), sl_p, lab_p, lab_len_p, t, s_max, float(lr),
+                                                int(count), _lib.ptr(trace[s0:]), stream))
+        else:
+            ft.frame_loss = None if ce is None else ce[s0:].data_ptr()
+            _lib.check(self._lib.kws_enroll_fit_frames(self._handle, _lib.ptr(nn), _lib.ptr(logits1), sl_p, lab_p, lab_len_p, t, s_max,
+                                                       ctypes.byref(ft), float(lr), int(count), _lib.ptr(trace[s0:]), stream))
+
+    def _fit(self, inputs, lengths, labels, steps, lr, init, seed, frames):
+        import torch
+        b = self.enrolments * self.slots
+        lab, lab_len, wn, bn = self._start(labels, init, seed, frames is None or labels is not None)
+        nn, logits1 = self.features(inputs, lengths)
+        t = int(nn.shape[1])
+        ft, keep, ce = self._frame_term(frames, t, steps) if frames is not None else (None, None, None)
         sl, sl_p = _ints(np.full(b, t) if lengths is None else torch.as_tensor(lengths).cpu().numpy())
-        lab, lab_p = _ints(lab)
-        lab_len, lab_len_p = _ints(lab_len)
+        if lab is not None:
+            lab, lab_len = np.ascontiguousarray(lab, np.int32), np.ascontiguousarray(lab_len, np.int32)
         trace = torch.empty(int(steps), b, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             stream = _lib.current_stream_ptr()
             _lib.check(self._lib.kws_enroll_set(self._handle, _lib.ptr(wn), _lib.ptr(bn), stream))
-            _lib.check(self._lib.kws_enroll_fit(self._handle, _lib.ptr(nn), _lib.ptr(logits1), sl_p, lab_p, lab_len_p, t, int(lab.shape[1]),
-                                                float(lr), int(steps), _lib.ptr(trace), stream))
+            self._steps(nn, logits1, sl_p, lab, lab_len, t, ft, ce, lr, 0, steps, trace, stream)
             out_w, out_b = torch.empty_like(wn), torch.empty_like(bn)
             _lib.check(self._lib.kws_enroll_get(self._handle, _lib.ptr(out_w), _lib.ptr(out_b), stream))
-        return out_w, out_b, trace
+        return (out_w, out_b, trace) if ce is None else (out_w, out_b, trace, ce)
 
     def align(self, inputs, lengths, labels, new_columns, new_bias):
         """Where the enrolled words lie in the recordings they were enrolled from, and how sure the new head is of them: inputs,
@@ -402,8 +469,19 @@ class Enroller(object):
         augmenter.draw -> frontend.augment -> features (the frozen stack) -> kws_enroll_fit for the batch's steps.  kws_enroll_set is
         called once, in front: Adam's moments and its step count run on across the batches.  labels, lr, init, seed and the result
         (new_columns, new_bias, loss_trace [steps, E*K]) are fit's."""
+        return self._fit_augmented(frontend, clean, noise, augmenter, labels, steps, steps_per_batch, lr, init, seed, None)
+
+    def fit_augmented_frames(self, frontend, clean, noise, augmenter, labels, targets, steps, steps_per_batch=1, frame_weight=1.0,
+                             ctc_weight=1.0, class_weight=None, lr=1.5e-3, init=None, seed=0, want_frame_loss=False):
+        """fit_augmented on frame-wise targets: the same loop with kws_enroll_fit_frames for every batch's steps and the SAME targets on
+        every redraw -- additive noise moves no word boundary.  targets, frame_weight, ctc_weight, class_weight, want_frame_loss and the
+        result are fit_frames'; everything else is fit_augmented's."""
+        return self._fit_augmented(frontend, clean, noise, augmenter, labels, steps, steps_per_batch, lr, init, seed,
+                                   (targets, frame_weight, ctc_weight, class_weight, want_frame_loss))
+
+    def _fit_augmented(self, frontend, clean, noise, augmenter, labels, steps, steps_per_batch, lr, init, seed, frames):
         import torch
-        e, k, h, n = self.enrolments, self.slots, self.config.hidden_size, self.n_new
+        e, k = self.enrolments, self.slots
         b = e * k
         steps, per = int(steps), int(steps_per_batch)
         if steps < 1 or per < 1:
@@ -412,21 +490,14 @@ class Enroller(object):
             raise _lib.InvalidArgumentError(-1, "fit_augmented needs a front-end whose features are the model's %d mel filters" % self.config.n_mel)
         if int(clean.spec.shape[0]) != b:
             raise _lib.InvalidArgumentError(-1, "clean holds %d utterances for %d enrolments of %d slots" % (int(clean.spec.shape[0]), e, k))
-        lab, lab_len = _pack_labels(labels, b)
-        if lab.shape[1] > MAX_LABEL:
-            raise _lib.InvalidArgumentError(-1, "labels of up to %d entries, got %d" % (MAX_LABEL, lab.shape[1]))
-        if init is None:
-            init = (truncated_normal((e, h, n), seed), np.zeros((e, n), np.float32))
-        wn = torch.as_tensor(init[0]).to(device=self.device, dtype=torch.float32).contiguous()
-        bn = torch.as_tensor(init[1]).to(device=self.device, dtype=torch.float32).contiguous()
-        if tuple(wn.shape) != (e, h, n) or tuple(bn.shape) != (e, n):
-            raise _lib.InvalidArgumentError(-1, "init must be ([%d,%d,%d], [%d,%d]), got %s %s" % (e, h, n, e, n, tuple(wn.shape), tuple(bn.shape)))
+        lab, lab_len, wn, bn = self._start(labels, init, seed, frames is None or labels is not None)
         t, n_noise = int(clean.spec.shape[1]), int(noise.spec.shape[0])
-        frames = torch.as_tensor(clean.frames).to(device=self.device, dtype=torch.int32).contiguous()
-        lengths = frames.cpu().numpy()          # the one host copy: kws_enroll_fit takes seq_len from host memory
+        ft, keep, ce = self._frame_term(frames, t, steps) if frames is not None else (None, None, None)
+        frames_dev = torch.as_tensor(clean.frames).to(device=self.device, dtype=torch.int32).contiguous()
+        lengths = frames_dev.cpu().numpy()          # the one host copy: kws_enroll_fit takes seq_len from host memory
         sl, sl_p = _ints(lengths)
-        lab, lab_p = _ints(lab)
-        lab_len, lab_len_p = _ints(lab_len)
+        if lab is not None:
+            lab, lab_len = np.ascontiguousarray(lab, np.int32), np.ascontiguousarray(lab_len, np.int32)
         trace = torch.empty(steps, b, dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             stream = _lib.current_stream_ptr()
@@ -434,12 +505,18 @@ class Enroller(object):
             for s0 in range(0, steps, per):
                 src, noise_index, start, gain_db = augmenter.draw(b, n_noise, t)
                 mel = frontend.augment(clean, noise, src, noise_index, start, gain_db)
-                nn, logits1 = self.features(mel, frames)
-                _lib.check(self._lib.kws_enroll_fit(self._handle, _lib.ptr(nn), _lib.ptr(logits1), sl_p, lab_p, lab_len_p, t, int(lab.shape[1]),
-                                                    float(lr), min(per, steps - s0), _lib.ptr(trace[s0:]), stream))
+                nn, logits1 = self.features(mel, frames_dev)
+                self._steps(nn, logits1, sl_p, lab, lab_len, t, ft, ce, lr, s0, min(per, steps - s0), trace, stream)
             out_w, out_b = torch.empty_like(wn), torch.empty_like(bn)
             _lib.check(self._lib.kws_enroll_get(self._handle, _lib.ptr(out_w), _lib.ptr(out_b), stream))
-        return out_w, out_b, trace
+        return (out_w, out_b, trace) if ce is None else (out_w, out_b, trace, ce)
+
+    def frame_targets(self, inputs, lengths, labels, new_columns, new_bias):
+        """The frame-wise targets of the enrolment recordings for fit_frames: align with the given columns, then frame_labels with the
+        extended head's blank -> [E*K, T] int32 array over its C + n_new classes, -1 past an utterance's frames (and in a slot that is
+        empty or has no valid path)."""
+        found = self.align(inputs, lengths, labels, new_columns, new_bias)
+        return frame_labels(found.states, labels, self.num_classes2 - 1)
 
 
 def _frozen_model_check(who, model):
@@ -600,3 +677,65 @@ def enroll(model, utterances, label, n_new, steps=300, lr=1.5e-3, init=None, see
         return enroller.extended_weights(wn[0].cpu().numpy(), bn[0].cpu().numpy())
     finally:
         enroller.close()
+
+
+def _mel_batch(mels):
+    import torch
+    t = max(int(m.shape[0]) for m in mels)
+    batch = torch.zeros(len(mels), t, int(mels[0].shape[1]))
+    for i, m in enumerate(mels):
+        batch[i, :m.shape[0]] = m
+    return batch, [int(m.shape[0]) for m in mels]
+
+
+def enroll_frames(model, utterances, label, n_new, negatives=(), negative_labels=(), steps=300, refit_steps=100, frame_weight=1.0,
+                  ctc_weight=1.0, class_weight=None, lr=1.5e-3, init=None, seed=0):
+    """enroll with a second fit on frame-wise targets, which can say "do not fire here" where the CTC loss cannot: on every frame labelled
+    with a trained class or the blank -- the silence around the user's own words, and whole recordings without the keyword -- the frame
+    loss pushes the new columns' softmax mass down.  utterances, label, n_new, steps, lr, init, seed: enroll's, and the first fit is
+    enroll's (CTC, `steps` steps).  negatives: recordings (mel [T_i, n_mel]) that do NOT hold the keyword, negative_labels their
+    transcripts over the TRAINED head's classes in prediction.ctc_label form (e.g. [0, 4, 0]; one for all, or one each); positives and
+    negatives together fill at most four slots.  Then: Enroller.frame_targets for the positives (the CTC result's own alignment), ctc_align
+    on head 1's logits + extend_targets for the negatives, and refit_steps steps of Enroller.fit_frames from the CTC result on all of
+    them with ctc_weight / frame_weight / class_weight.  -> the weights dict of the customised model, as enroll."""
+    import torch
+    pos = [torch.as_tensor(u, dtype=torch.float32) for u in utterances]
+    neg = [torch.as_tensor(u, dtype=torch.float32) for u in negatives]
+    if not pos or any(m.dim() != 2 for m in pos + neg):
+        raise _lib.InvalidArgumentError(-1, "enroll_frames takes lists of mel utterances [T, n_mel]")
+    if len(pos) + len(neg) > 4:
+        raise _lib.InvalidArgumentError(-1, "%d utterances and %d negatives: an enrolment has at most 4 slots" % (len(pos), len(neg)))
+    neg_labels = []
+    if neg:
+        neg_labels = list(negative_labels)
+        if neg_labels and np.ndim(neg_labels[0]) == 0:
+            neg_labels = [neg_labels] * len(neg)
+        if len(neg_labels) != len(neg):
+            raise _lib.InvalidArgumentError(-1, "negative_labels: %d transcripts for %d negatives" % (len(neg_labels), len(neg)))
+        neg_labels = [[int(v) for v in l] for l in neg_labels]
+    c = model.config.num_classes
+    first = Enroller(model, n_new, enrolments=1, utterances_per_enrolment=len(pos))
+    both = first
+    try:
+        batch, lengths = _mel_batch(pos)
+        labels = [[int(v) for v in label]] * len(pos)
+        wn, bn, _ = first.fit(batch, lengths, labels, steps, lr=lr, init=init, seed=seed)
+        targets = first.frame_targets(batch, lengths, labels, wn, bn)
+        if neg:
+            both = Enroller(model, n_new, enrolments=1, utterances_per_enrolment=len(pos) + len(neg))
+            batch, lengths = _mel_batch(pos + neg)
+            labels = labels + neg_labels
+            _, logits1 = both.features(batch, lengths)
+            states = ctc_align(logits1[len(pos):], lengths[len(pos):], neg_labels).states
+            neg_targets = extend_targets(frame_labels(states, neg_labels, c - 1), c, n_new)
+            full = np.full((len(pos) + len(neg), int(batch.shape[1])), -1, np.int32)
+            full[:len(pos), :targets.shape[1]] = targets
+            full[len(pos):] = neg_targets
+            targets = full
+        wn, bn, _ = both.fit_frames(batch, lengths, labels, targets, refit_steps, frame_weight=frame_weight, ctc_weight=ctc_weight,
+                                    class_weight=class_weight, lr=lr, init=(wn, bn))
+        return both.extended_weights(wn[0].cpu().numpy(), bn[0].cpu().numpy())
+    finally:
+        first.close()
+        if both is not first:
+            both.close()
